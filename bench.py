@@ -13,7 +13,10 @@ solver-level C ABI entry `aoadmm_solve`.  N > 1 (launched by torchrun, one rank 
 GPU): the tensor's first mode is row-sharded, factor matrices are replicated and
 only MTTKRP outputs are all-reduced over RCCL (strong scaling: total work fixed).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` outer iterations and reports them
+(`value`, `ms_per_step`, the roofline of the timed passes).  `--full` adds the measurements that take runs of their
+own: the tail breakdown, the bare mode-1 MTTKRP, the fp64 repeat (`fp32_drift`, `parity_mode`) and the CPU baseline.
+`--dump-outputs DIR` writes what the timed solve returned after its last step as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -107,7 +110,45 @@ def parse_args(argv=None):
     ap.add_argument('--of', type=int, default=0)
     ap.add_argument('--no-drift', action='store_true',
                     help='skip the fp64 repeat of the same iterations (N = 1, fp32 runs only) that measures the factor drift')
-    return ap.parse_args(argv)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline: tail breakdown, bare MTTKRP, fp64 repeat (drift, parity mode) and CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the factors and objective traces of the timed solve as DIR/<name>.npy (float64)')
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    return args
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, state, out, cap=DUMP_CAP_BYTES):
+    """What a caller of the timed solve receives (cmtf_AOADMM.m:193, `Fac` and `out`), after its last step, as float64
+    DIR/<name>.npy: fac_<m>, constraint_fac_<m>, constraint_dual_fac_<m>, coupling_fac_<n>, coupling_dual_fac_<m> and
+    the objective traces of `out` (func_*, f_tensors).  Above `cap` bytes in all, every matrix keeps the same seeded
+    sample of its rows (never reached by the cubic workloads that fit one GPU)."""
+    arrays = {}
+    for key in ('fac', 'constraint_fac', 'constraint_dual_fac', 'coupling_fac', 'coupling_dual_fac'):
+        for m, a in enumerate(state.get(key) or []):
+            if isinstance(a, np.ndarray) and a.size:
+                arrays['%s_%d' % (key, m)] = np.asarray(a, dtype=np.float64)
+    for key in ('func_val_conv', 'func_coupl_conv', 'func_constr_conv', 'func_PAR2_coupl'):
+        arrays[key] = np.asarray(out[key], dtype=np.float64)
+    arrays['f_tensors'] = np.array([out['f_tensors']], dtype=np.float64)
+    mats = sum(a.nbytes for a in arrays.values() if a.ndim == 2)
+    rest = sum(a.nbytes for a in arrays.values() if a.ndim != 2)
+    if mats + rest > cap:
+        rng = np.random.default_rng(0)
+        for name in sorted(arrays):
+            a = arrays[name]
+            if a.ndim == 2:
+                k = max(1, int(a.shape[0] * (cap - rest) / mats))
+                arrays[name] = a[np.sort(rng.choice(a.shape[0], k, replace=False))]
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + '.npy'), a)
+    return sorted(arrays)
 
 
 def launch_plan(gpus, environ, n_devices, argv, port=None):
@@ -243,56 +284,65 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if out['OuterIterations'] != args.steps:
+        raise SystemExit('bench.py: the timed solve ran %d outer iterations, --steps %d' % (out['OuterIterations'], args.steps))
 
-    # factors after exactly warmup + steps iterations, for the fp32-vs-fp64 comparison below (the runs that follow
-    # iterate further)
+    # state after exactly warmup + steps iterations: the dumped outputs and the fp32-vs-fp64 comparison of --full (the
+    # runs that follow iterate further)
     fac32 = None
     share = args.of if args.as_rank >= 0 else 1            # > 1: this process did 1/share of the job (--as-rank)
-    if world == 1 and share == 1 and args.prec == 'f32' and not args.no_drift:
-        fac32 = pkg.download_state(eng, Z, G0)['fac']
+    want_drift = args.full and world == 1 and share == 1 and args.prec == 'f32' and not args.no_drift
+    if args.dump_outputs or want_drift:
+        state = pkg.download_state(eng, Z, G0)
+        if want_drift:
+            fac32 = state['fac']
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, state, out)
 
-    # where the time outside the tensor passes goes: a few more iterations with the reductions over T timed as well
-    # (HIP events around them, switched on by the first kernel_stats(2) call; outside the timed region)
-    tail = None
-    try:
-        msr = C.c_double(); nlr = C.c_int64(); byr = C.c_double()
-        capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 2, 1, None, None, None, None))
+    # --full: measurements beyond the headline, each with runs of its own
+    tail = mttkrp_ms = None
+    if args.full:
+        # where the time outside the tensor passes goes: a few more iterations with the reductions over T timed as well
+        # (HIP events around them, switched on by the first kernel_stats(2) call; outside the timed region)
+        try:
+            msr = C.c_double(); nlr = C.c_int64(); byr = C.c_double()
+            capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 2, 1, None, None, None, None))
+            capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 0, 1, None, None, None, None))
+            capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 1, 1, None, None, None, None))
+            nb = max(args.steps, 1)           # same length as the timed run: the solve's fixed cost weighs the same
+            eng.synchronize()
+            tb = time.perf_counter()
+            pkg.run_solver(eng, opts(nb), 3)
+            eng.synchronize()
+            tb = (time.perf_counter() - tb) / nb * 1e3
+            msp = C.c_double(); msp1 = C.c_double()
+            capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 2, 1, C.byref(msr), C.byref(nlr), C.byref(byr), None))
+            capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 0, 1, C.byref(msp), None, None, None))
+            capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 1, 1, C.byref(msp1), None, None, None))
+            red_ms = msr.value / nb
+            pass_ms = (msp.value + msp1.value) / nb
+            tail = {'iterations': nb, 'ms_per_step': tb, 'tensor_passes_ms': pass_ms, 't_reductions_ms': red_ms,
+                    't_reductions_per_iter': nlr.value / nb,
+                    't_reductions_GBps': (byr.value / (msr.value * 1e-3) / 1e9) if msr.value > 0 else None,
+                    'replicated_small_kernels_ms': tb - pass_ms - red_ms,
+                    'note': 'per rank; the reductions read the partial contraction T once each and shard with the passes; '
+                            'replicated_small_kernels_ms (system builds, ADMM inner loops, Gram matrices, objective) is what '
+                            'every rank repeats'}
+        except Exception as e:   # a report, never a reason to lose the headline number
+            tail = {'error': repr(e)}
+
+        # bare mode-1 MTTKRP on the resident tensor (contraction + reduction), a few repetitions
+        el = C.c_float()
+        reps = []
+        for _ in range(3):
+            capi.check(eng.lib.aoadmm_resident_mttkrp(eng.h, 0, 0, None, C.byref(el)))
+            reps.append(el.value)
+        mttkrp_ms = float(np.median(reps))
+        if dist is not None:
+            tt = torch.tensor([mttkrp_ms], dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            mttkrp_ms = float(tt.item())
         capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 0, 1, None, None, None, None))
-        capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 1, 1, None, None, None, None))
-        nb = max(args.steps, 1)           # same length as the timed run: the solve's fixed cost weighs the same
-        eng.synchronize()
-        tb = time.perf_counter()
-        pkg.run_solver(eng, opts(nb), 3)
-        eng.synchronize()
-        tb = (time.perf_counter() - tb) / nb * 1e3
-        msp = C.c_double(); msp1 = C.c_double()
-        capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 2, 1, C.byref(msr), C.byref(nlr), C.byref(byr), None))
-        capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 0, 1, C.byref(msp), None, None, None))
-        capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 1, 1, C.byref(msp1), None, None, None))
-        red_ms = msr.value / nb
-        pass_ms = (msp.value + msp1.value) / nb
-        tail = {'iterations': nb, 'ms_per_step': tb, 'tensor_passes_ms': pass_ms, 't_reductions_ms': red_ms,
-                't_reductions_per_iter': nlr.value / nb,
-                't_reductions_GBps': (byr.value / (msr.value * 1e-3) / 1e9) if msr.value > 0 else None,
-                'replicated_small_kernels_ms': tb - pass_ms - red_ms,
-                'note': 'per rank; the reductions read the partial contraction T once each and shard with the passes; '
-                        'replicated_small_kernels_ms (system builds, ADMM inner loops, Gram matrices, objective) is what '
-                        'every rank repeats'}
-    except Exception as e:   # a report, never a reason to lose the headline number
-        tail = {'error': repr(e)}
-
-    # bare mode-1 MTTKRP on the resident tensor (contraction + reduction), a few repetitions
-    el = C.c_float()
-    reps = []
-    for _ in range(3):
-        capi.check(eng.lib.aoadmm_resident_mttkrp(eng.h, 0, 0, None, C.byref(el)))
-        reps.append(el.value)
-    mttkrp_ms = float(np.median(reps))
-    if dist is not None:
-        tt = torch.tensor([mttkrp_ms], dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        mttkrp_ms = float(tt.item())
-    capi.check(eng.lib.aoadmm_kernel_stats(eng.h, 0, 1, None, None, None, None))
 
     # fp32-tensor mode against the fp64 parity mode on the SAME synthetic tensor (same seed, generated in HBM), same init,
     # same iterations: relative Frobenius gap of the factors.  Outside the timed region; the engines run one after the
@@ -379,9 +429,11 @@ def main():
                        'resident_copies': 'X(i,j,k) + mode-permuted X(j,k,i) and X(k,i,j): 3 x %.0f GB per node, '
                                           'every pass contracts a trailing mode'
                                           % (I * J * K * (4.0 if args.prec == 'f32' else 8.0) / 1e9)},
-            'mttkrp_mode1_gflops': flops_mttkrp / (mttkrp_ms * 1e-3) / 1e9,
+            # --full only (None otherwise), like tail_breakdown, fp32_drift, parity_mode and cpu_baseline
+            'mttkrp_mode1_gflops': flops_mttkrp / (mttkrp_ms * 1e-3) / 1e9 if mttkrp_ms else None,
             'mttkrp_mode1_ms': mttkrp_ms,
-            'mttkrp_mfma_frac_f32_peak': flops_mttkrp / (mttkrp_ms * 1e-3) / 1e12 / (F32_MFMA_PEAK_TF * world),
+            'mttkrp_mfma_frac_f32_peak': (flops_mttkrp / (mttkrp_ms * 1e-3) / 1e12 / (F32_MFMA_PEAK_TF * world)
+                                          if mttkrp_ms else None),
             'f_tensors_last': out['f_tensors'],
             'rank_share': None if share == 1 else {'rank': args.as_rank, 'of': args.of},
             'fp32_drift': drift,
@@ -405,7 +457,7 @@ def main():
                               'avg_launch_ms': (ms1.value / nl1.value) if nl1.value else None,
                               'achieved_GBps': (by1.value / nl1.value / (ms1.value / nl1.value * 1e-3) / 1e9) if nl1.value and ms1.value > 0 else None},
         }
-        if not args.no_cpu_baseline and world == 1 and share == 1:      # reported on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and share == 1:      # rank 0 at N = 1 only
             try:
                 line['cpu_baseline'] = cpu_baseline(I, J, K, R, rows=(min(args.cpu_rows, I) if args.cpu_rows > 0 else None))
             except Exception as e:  # the baseline is a report, never a reason to lose the GPU number

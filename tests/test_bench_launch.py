@@ -60,3 +60,39 @@ def test_parent_of_self_launch_never_imports_torch_or_touches_gpu():
     src = open(os.path.join(ROOT, 'bench.py')).read()
     main = src[src.index('def main():'):]
     assert main.index("plan['mode'] == 'spawn'") < main.index('import torch') < main.index('pkg.Engine(')
+
+
+def test_plain_run_is_lean_by_default():
+    b = _bench()
+    a = b.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '3'])
+    assert a.steps == 7 and a.warmup == 3 and not a.full and a.dump_outputs is None
+    assert b.parse_args(['--full', '--dump-outputs', 'out']).full
+    with pytest.raises(SystemExit):
+        b.parse_args(['--steps', '0'])
+
+
+def test_dump_outputs_writes_float_arrays_under_the_cap(tmp_path):
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(3)
+    state = {'fac': [rng.random((50, 4)), rng.random((60, 4))], 'constraint_fac': [rng.random((50, 4)), None],
+             'constraint_dual_fac': [[], None], 'coupling_fac': [], 'coupling_dual_fac': [None, None]}
+    out = {'func_val_conv': rng.random(6), 'func_coupl_conv': np.zeros(6), 'func_constr_conv': rng.random(6),
+           'func_PAR2_coupl': np.zeros(6), 'f_tensors': 0.25}
+    names = b.dump_outputs(str(tmp_path / 'a'), state, out)
+    assert names == sorted(['fac_0', 'fac_1', 'constraint_fac_0', 'func_val_conv', 'func_coupl_conv',
+                            'func_constr_conv', 'func_PAR2_coupl', 'f_tensors'])
+    for n in names:
+        assert np.load(str(tmp_path / 'a' / (n + '.npy'))).dtype == np.float64
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'fac_1.npy')), state['fac'][1])
+    # above the cap: the same seeded row sample on every call, within the cap
+    cap = 2000
+    b.dump_outputs(str(tmp_path / 'b'), state, out, cap=cap)
+    b.dump_outputs(str(tmp_path / 'c'), state, out, cap=cap)
+    sizes = 0
+    for n in names:
+        x = np.load(str(tmp_path / 'b' / (n + '.npy')))
+        assert np.array_equal(x, np.load(str(tmp_path / 'c' / (n + '.npy'))))
+        sizes += x.nbytes
+    assert sizes <= cap
+    assert np.load(str(tmp_path / 'b' / 'fac_0.npy')).shape[1] == 4

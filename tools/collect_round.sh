@@ -13,22 +13,22 @@ if [ "${2:-}" != "notests" ]; then
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/gputests.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/gputests.log
 tail -2 $OUT/gputests.log
 fi
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --prec f64 --no-cpu-baseline > $OUT/${TAG}_bench_f64.json 2> $OUT/bench_f64.err; echo "bench f64 rc=$?"
-timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 10 --warmup 2 --no-cpu-baseline --no-drift > $OUT/${TAG}_bench_torchrun_n1.json 2> $OUT/torchrun.err; echo "torchrun n1 rc=$?"
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --prec f64 --no-cpu-baseline > $OUT/${TAG}_bench_f64.json 2> $OUT/bench_f64.err; echo "bench f64 rc=$?"
+timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 10 --warmup 2 --no-cpu-baseline --no-drift > $OUT/${TAG}_bench_torchrun_n1.json 2> $OUT/torchrun.err; echo "torchrun n1 rc=$?"
 for n in 8 4 2; do
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --as-rank 0 --of $n > $OUT/${TAG}_rank0_of_$n.json 2> $OUT/rank0_of_$n.err; echo "rank 0 of $n rc=$?"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --as-rank 0 --of $n > $OUT/${TAG}_rank0_of_$n.json 2> $OUT/rank0_of_$n.err; echo "rank 0 of $n rc=$?"
 done
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --as-rank 7 --of 8 > $OUT/${TAG}_rank7_of_8.json 2> $OUT/rank7_of_8.err; echo "rank 7 of 8 rc=$?"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --as-rank 7 --of 8 > $OUT/${TAG}_rank7_of_8.json 2> $OUT/rank7_of_8.err; echo "rank 7 of 8 rc=$?"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-drift > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/prof.err; echo "prof rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-drift > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/prof.err; echo "prof rc=$?"
 find $OUT/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${TAG}_kernel_stats.csv
 find $OUT/prof -name "*kernel_trace.csv" | head -1 | xargs -I{} python3 $R/tools/kernel_timeline.py {} 12 > $OUT/${TAG}_kernel_timeline.txt
 rm -rf $OUT/prof
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --steps 10 --warmup 2 --prec f64 --no-cpu-baseline > $OUT/${TAG}_bench_f64_under_rocprof.json 2> $OUT/prof64.err; echo "prof f64 rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --full --steps 10 --warmup 2 --prec f64 --no-cpu-baseline > $OUT/${TAG}_bench_f64_under_rocprof.json 2> $OUT/prof64.err; echo "prof f64 rc=$?"
 find $OUT/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${TAG}_kernel_stats_f64.csv
 rm -rf $OUT/prof
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --steps 10 --warmup 2 --as-rank 0 --of 8 > $OUT/${TAG}_rank0_of_8_under_rocprof.json 2> $OUT/prof8.err; echo "prof rank-of-8 rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --full --steps 10 --warmup 2 --as-rank 0 --of 8 > $OUT/${TAG}_rank0_of_8_under_rocprof.json 2> $OUT/prof8.err; echo "prof rank-of-8 rc=$?"
 find $OUT/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${TAG}_rank0_of_8_kernel_stats.csv
 find $OUT/prof -name "*kernel_trace.csv" | head -1 | xargs -I{} python3 $R/tools/kernel_timeline.py {} 12 > $OUT/${TAG}_rank0_of_8_kernel_timeline.txt
 find $OUT/prof -name "*kernel_trace.csv" | head -1 | xargs -I{} python3 $R/tools/iteration_sequence.py {} 9 12 > $OUT/${TAG}_rank0_of_8_iteration_sequence.txt

@@ -6,15 +6,15 @@ OUT=$R/gpurun_out/r03_c1
 mkdir -p $OUT
 cd $R
 timeout -k 10 600 python -m pytest tests/test_gpu_ops.py tests/test_known_answers.py tests/test_gpu_sharded.py -m gpu -x -q > $OUT/tests_a.log 2>&1; echo "tests_a rc=$?"; tail -3 $OUT/tests_a.log
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_l2.json 2> $OUT/bench_l2.err; echo "bench l2 rc=$?"
-AOADMM_CONTRACT_FLUSH=0 timeout -k 10 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_l1.json 2> $OUT/bench_l1.err; echo "bench l1 rc=$?"
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_l2.json 2> $OUT/bench_l2.err; echo "bench l2 rc=$?"
+AOADMM_CONTRACT_FLUSH=0 timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_l1.json 2> $OUT/bench_l1.err; echo "bench l1 rc=$?"
 for f in 1 2 6; do
-AOADMM_CONTRACT_FLUSH=$f timeout -k 10 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_flush$f.json 2> $OUT/bench_flush$f.err; echo "bench flush $f rc=$?"
+AOADMM_CONTRACT_FLUSH=$f timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_flush$f.json 2> $OUT/bench_flush$f.err; echo "bench flush $f rc=$?"
 done
 for n in 8 4 2; do
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --as-rank 0 --of $n > $OUT/rank0_of_$n.json 2> $OUT/rank0_of_$n.err; echo "as-rank of $n rc=$?"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --as-rank 0 --of $n > $OUT/rank0_of_$n.json 2> $OUT/rank0_of_$n.err; echo "as-rank of $n rc=$?"
 done
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --as-rank 3 --of 8 > $OUT/rank3_of_8.json 2> $OUT/rank3_of_8.err; echo "as-rank 3 of 8 rc=$?"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --as-rank 3 --of 8 > $OUT/rank3_of_8.json 2> $OUT/rank3_of_8.err; echo "as-rank 3 of 8 rc=$?"
 python3 - <<PY
 import json,glob
 for f in sorted(glob.glob('$OUT/*.json')):

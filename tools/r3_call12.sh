@@ -8,11 +8,11 @@ cd /tmp && export TMPDIR=/tmp
 for w in 4 2; do
   export AOADMM_CONTRACT_WPW=$w
   for n in 8 4; do
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --steps 10 --warmup 2 --as-rank 0 --of $n > $OUT/rank0_of_${n}_wpw$w.json 2> /dev/null
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --full --steps 10 --warmup 2 --as-rank 0 --of $n > $OUT/rank0_of_${n}_wpw$w.json 2> /dev/null
     f=$(find $OUT/prof -name "*kernel_stats.csv" | head -1); echo "wpw=$w of $n: $(grep contract16 $f | cut -d, -f2-4) ms_per_step=$(python3 -c "import json;print(round(json.loads(open('$OUT/rank0_of_${n}_wpw$w.json').read().strip().splitlines()[-1])['ms_per_step'],4))")"
     rm -rf $OUT/prof
   done
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-drift > $OUT/bench_wpw$w.json 2> /dev/null
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-drift > $OUT/bench_wpw$w.json 2> /dev/null
   f=$(find $OUT/prof -name "*kernel_stats.csv" | head -1); echo "wpw=$w N=1: $(grep contract16 $f | cut -d, -f2-4) ms_per_step=$(python3 -c "import json;print(round(json.loads(open('$OUT/bench_wpw$w.json').read().strip().splitlines()[-1])['ms_per_step'],4))")"
   rm -rf $OUT/prof
 done

@@ -10,10 +10,10 @@ timeout -k 10 600 python -m pytest tests/test_gpu_ops.py tests/test_gpu_solver.p
 cd /tmp && export TMPDIR=/tmp
 for v in 1024 512; do
   if [ $v = 512 ]; then export AOADMM_TV_512=1; else unset AOADMM_TV_512; fi
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --steps 20 --warmup 2 --as-rank 0 --of 8 > $OUT/rank0_of_8_$v.json 2> /dev/null
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --full --steps 20 --warmup 2 --as-rank 0 --of 8 > $OUT/rank0_of_8_$v.json 2> /dev/null
   f=$(find $OUT/prof -name "*kernel_stats.csv" | head -1); echo "$v: $(grep prox_tv $f | cut -d, -f1-4 | cut -c1-90)"
   rm -rf $OUT/prof
   for rep in 1 2; do
-  timeout -k 10 200 python3 $R/bench.py --steps 20 --warmup 5 --as-rank 0 --of 8 2> /dev/null | python3 -c "import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('$v', 'of 8: ms_per_step', round(d['ms_per_step'],4), 'small', round(d['tail_breakdown']['replicated_small_kernels_ms'],4))"
+  timeout -k 10 200 python3 $R/bench.py --full --steps 20 --warmup 5 --as-rank 0 --of 8 2> /dev/null | python3 -c "import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('$v', 'of 8: ms_per_step', round(d['ms_per_step'],4), 'small', round(d['tail_breakdown']['replicated_small_kernels_ms'],4))"
   done
 done

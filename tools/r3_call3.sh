@@ -8,11 +8,11 @@ mkdir -p $OUT
 cd $R
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/gputests.log 2>&1; echo "pytest rc=$?"; tail -5 $OUT/gputests.log
 for n in 8; do
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --as-rank 0 --of $n > $OUT/rank0_of_${n}.json 2> $OUT/rank0_of_$n.err; echo "as-rank of $n rc=$?"
-AOADMM_NO_SYS_RIDER=1 timeout -k 10 300 python bench.py --steps 20 --warmup 5 --as-rank 0 --of $n > $OUT/rank0_of_${n}_norider.json 2> $OUT/rank0_of_${n}_norider.err; echo "as-rank of $n norider rc=$?"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --as-rank 0 --of $n > $OUT/rank0_of_${n}.json 2> $OUT/rank0_of_$n.err; echo "as-rank of $n rc=$?"
+AOADMM_NO_SYS_RIDER=1 timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --as-rank 0 --of $n > $OUT/rank0_of_${n}_norider.json 2> $OUT/rank0_of_${n}_norider.err; echo "as-rank of $n norider rc=$?"
 done
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-drift > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-AOADMM_NO_SYS_RIDER=1 timeout -k 10 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-drift > $OUT/bench_norider.json 2> $OUT/bench_norider.err; echo "bench norider rc=$?"
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-drift > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+AOADMM_NO_SYS_RIDER=1 timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-drift > $OUT/bench_norider.json 2> $OUT/bench_norider.err; echo "bench norider rc=$?"
 timeout -k 10 300 python tools/time_cfg4.py > $OUT/cfg4_single.txt 2>&1; echo "cfg4 single rc=$?"
 timeout -k 10 300 python tools/time_cfg4.py --sharded 4 > $OUT/cfg4_sharded4.txt 2>&1; echo "cfg4 sharded rc=$?"
 timeout -k 10 300 python tools/time_cfg4.py --as-rank 0 --of 4 > $OUT/cfg4_rank0_of_4.txt 2>&1; echo "cfg4 share rc=$?"

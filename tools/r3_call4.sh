@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/r03_c4
 mkdir -p $OUT
 cd $R
 timeout -k 10 900 python -m pytest tests/test_gpu_solver.py tests/test_gpu_sharded.py tests/test_gpu_fuzz.py -m gpu -x -q > $OUT/tests.log 2>&1; echo "tests rc=$?"; tail -4 $OUT/tests.log
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --as-rank 0 --of 8 > $OUT/rank0_of_8.json 2> $OUT/rank0_of_8.err; echo "as-rank rc=$?"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --as-rank 0 --of 8 > $OUT/rank0_of_8.json 2> $OUT/rank0_of_8.err; echo "as-rank rc=$?"
 timeout -k 10 300 python tools/time_em.py 0.2 > $OUT/em_timing_20.txt 2>&1; echo "em 20 rc=$?"; tail -2 $OUT/em_timing_20.txt
 timeout -k 10 300 python tools/time_em.py 0.01 > $OUT/em_timing_01.txt 2>&1; echo "em 1 rc=$?"; tail -2 $OUT/em_timing_01.txt
 cd /tmp && export TMPDIR=/tmp

@@ -6,10 +6,10 @@ OUT=$R/gpurun_out/r03_c6
 mkdir -p $OUT
 cd $R
 timeout -k 10 900 python -m pytest tests/test_gpu_ops.py tests/test_gpu_solver.py tests/test_gpu_sharded.py tests/test_gpu_fuzz.py tests/test_known_answers.py tests/test_gpu_random_models.py tests/test_golden.py -m gpu -x -q > $OUT/tests.log 2>&1; echo "tests rc=$?"; tail -4 $OUT/tests.log
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --as-rank 0 --of 8 > $OUT/rank0_of_8.json 2> $OUT/rank0_of_8.err && echo "as-rank ok"
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-drift > $OUT/bench.json 2> $OUT/bench.err && echo "bench ok"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --as-rank 0 --of 8 > $OUT/rank0_of_8.json 2> $OUT/rank0_of_8.err && echo "as-rank ok"
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-drift > $OUT/bench.json 2> $OUT/bench.err && echo "bench ok"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --steps 10 --warmup 2 --as-rank 0 --of 8 > $OUT/rank0_of_8_under_rocprof.json 2> $OUT/prof.err; echo "prof rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --full --steps 10 --warmup 2 --as-rank 0 --of 8 > $OUT/rank0_of_8_under_rocprof.json 2> $OUT/prof.err; echo "prof rc=$?"
 find $OUT/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/rank0_of_8_kernel_stats.csv
 find $OUT/prof -name "*kernel_trace.csv" | head -1 | xargs -I{} cp {} $OUT/rank0_of_8_kernel_trace.csv
 rm -rf $OUT/prof

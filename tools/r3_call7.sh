@@ -19,10 +19,10 @@ for v in hybrid allglobal; do
   grep -i "rows" $OUT/tv_long_$v.txt | head -12
 done
 unset AOADMM_TV_ALL_GLOBAL
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --steps 10 --warmup 2 --as-rank 0 --of 8 > $OUT/rank0_of_8_under_rocprof.json 2> $OUT/prof.err; echo "prof rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --full --steps 10 --warmup 2 --as-rank 0 --of 8 > $OUT/rank0_of_8_under_rocprof.json 2> $OUT/prof.err; echo "prof rc=$?"
 find $OUT/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/rank0_of_8_kernel_stats.csv
 rm -rf $OUT/prof
 grep -E "reduce_|sys_build" $OUT/rank0_of_8_kernel_stats.csv | cut -c1-60,150-260
 cd $R
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --as-rank 0 --of 8 > $OUT/rank0_of_8.json 2> $OUT/rank0_of_8.err && python3 -c "
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --as-rank 0 --of 8 > $OUT/rank0_of_8.json 2> $OUT/rank0_of_8.err && python3 -c "
 import json; d=json.loads(open('$OUT/rank0_of_8.json').read().strip().splitlines()[-1]); print('rank0_of_8', d['ms_per_step'], d['tail_breakdown'])"
