@@ -45,7 +45,9 @@ enum {
                                  (cmtf_fun_AOADMM.m:142,185,273,362 throw in MATLAB) */
   AOADMM_ERR_RCCL = 4,        /* collective failure */
   AOADMM_ERR_UNSUPPORTED = 5, /* feature routed back to the MATLAB path:
-                                 non-Frobenius loss, 'custom' prox, sptensor */
+                                 non-Frobenius loss, 'custom' prox; also an op the engine has no
+                                 answer for on the data it holds (e.g. resident_unfold_gram of a
+                                 sparse block) */
   AOADMM_ERR_NOMEM = 6
 };
 
@@ -221,6 +223,16 @@ int aoadmm_par2_slab_mask_upload(aoadmm_ctx* ctx, int p, int k, const uint8_t* m
 /* device-side synthetic CP tensor: X = [[A1,..,AN]] + noise, ||X|| = 1;
  * never crosses PCIe.  normsq_out receives ||X||^2 after normalisation. */
 int aoadmm_tensor_synth(aoadmm_ctx* ctx, int p, int rank, uint64_t seed, double noise, int precision);
+/* Z.object{p} as a Tensor Toolbox sptensor (cmtf_AOADMM.m:77-79, :132) or a MATLAB sparse matrix:
+ * nnz nonzeros, subs column-major nnz x n_tensor_modes (the layout of sptensor.subs), 0-based; vals nnz doubles.
+ * Duplicate subscripts are summed (sptensor's constructor rule).  Values stay fp64.
+ * Sizes come from aoadmm_model_set_mode (each below 2^31); a subscript out of range or nnz < 0 is
+ * AOADMM_ERR_INVALID, nnz = 0 is valid.  A later aoadmm_tensor_upload replaces the sparse form and this call
+ * replaces a dense one.  On a sparse block aoadmm_tensor_mask_upload, aoadmm_tensor_upload_rows and
+ * aoadmm_tensor_synth return AOADMM_ERR_INVALID and aoadmm_resident_unfold_gram AOADMM_ERR_UNSUPPORTED;
+ * aoadmm_tensor_normsq, aoadmm_resident_mttkrp and aoadmm_solve work as for dense data.  With a communicator
+ * every rank holds all nonzeros and computes the complete MTTKRP (no collective for the block). */
+int aoadmm_tensor_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* vals);
 /* Znorm_const{p} (cmtf_AOADMM.m:130-156) */
 int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out);
 
@@ -242,7 +254,9 @@ int aoadmm_resident_mttkrp(aoadmm_ctx* ctx, int p, int tensor_mode, double* out_
  * bytes and flops of a tensor-pass kernel since the last reset.  which = 0: register-streaming contraction
  * (contract_f32/f64, trailing modes); which = 1: LDS-transposed leading-mode contraction (contract_lead_f32);
  * which = 2: the reductions over the partial contraction T that finish an MTTKRP (bytes = size of T per reduction;
- * timed only from the first call with which = 2 on, two more events per reduction) */
+ * timed only from the first call with which = 2 on, two more events per reduction); which = 3: the MTTKRPs of
+ * sparse blocks (launches = MTTKRPs, each the streaming kernel plus its carry passes; bytes = nonzeros streamed +
+ * factor rows gathered + output written; flops = nnz * R * N) */
 int aoadmm_kernel_stats(aoadmm_ctx* ctx, int which, int reset, double* contract_ms, int64_t* contract_launches,
                         double* contract_bytes, double* contract_flops);
 

@@ -409,6 +409,14 @@ int aoadmm_par2_slab_mask_upload(aoadmm_ctx* ctx, int p, int k, const uint8_t* m
   CTX_OR_FAIL(ctx);
   return guarded([&] { on_engines(ctx, [&](Engine& e, int) { e.par2_slab_mask_upload(p, k, mask_k); }); });
 }
+int aoadmm_tensor_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* vals) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    AO_REQUIRE(nnz >= 0, "nnz = %lld < 0", (long long)nnz);
+    AO_REQUIRE(nnz == 0 || (subs != nullptr && vals != nullptr), "null subs / vals");
+    on_engines(ctx, [&](Engine& e, int) { e.tensor_upload_coo(p, nnz, subs, vals); });   // replicated on every engine
+  });
+}
 int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out) {
   CTX_OR_FAIL(ctx);
   return guarded([&] {

@@ -14,6 +14,7 @@
 #include "misc.h"
 #include "par2.h"
 #include "small.h"
+#include "sparse.h"
 
 typedef struct ncclComm* ncclComm_t;
 
@@ -71,6 +72,10 @@ struct CpBlock {
   // Z.miss{p}: one byte per entry in the layout of X (and of Xt for matrices), 1 = observed
   DevBuf mask, maskT;
   bool has_mask = false;
+  // sparse form of Z.object{p} (aoadmm_tensor_upload_coo): replaces everything above but nd / dims / has_data; every
+  // rank of a communicator holds all nonzeros and computes the complete MTTKRP (no row sharding, no collective)
+  bool sparse = false;
+  CooBlock coo;
 };
 
 struct ModeInfo {
@@ -192,6 +197,7 @@ class Engine {
 
   // data
   void tensor_upload(int p, const double* data, int prec, int64_t row0, int64_t local_rows);
+  void tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const double* vals);
   void tensor_synth(int p, int rank, uint64_t seed, double noise, int prec);
   void par2_slab_upload(int p, int k, const double* Xk);
   void tensor_mask_upload(int p, const uint8_t* mask);
@@ -305,7 +311,7 @@ class Engine {
   std::vector<hipEvent_t> event_pool_;   // timing events are recycled: creating two per tensor pass cost host time in the loop
   hipEvent_t take_event();
   void fold_finished(KernelStats& ks);
-  KernelStats kstats_[3];   // [0] streaming contraction, [1] leading-mode contraction, [2] reductions over T
+  KernelStats kstats_[4];   // [0] streaming contraction, [1] leading-mode contraction, [2] reductions over T, [3] sparse MTTKRP
   int prepared_mode_ = -1;  // mode whose MTTKRP + system build were enqueued ahead (prepare_next_first_mode)
   bool profile_ = true;
   bool profile_reductions_ = false;   // switched on by the first kernel_stats(2, ...) call: two more events per reduction
@@ -321,6 +327,7 @@ class Engine {
 
   AdmmCtl* ctl_of_mode(int m) { return ctls_.as<AdmmCtl>() + m; }
   AdmmCtl* ctl_of_coupling(int c) { return ctls_.as<AdmmCtl>() + n_modes_ + c; }
+  void sparse_mttkrp(CpBlock& b, int pos, const FactorRef* facs, int R, double scale, double* out, int64_t ldOut);
   void timed_contract(const void* X, int prec, const ContractPlan& pl, const double* F, int64_t ldF,
                       void* frag, void* T);
 };

@@ -587,6 +587,8 @@ void Engine::tensor_upload(int p, const double* data, int prec, int64_t row0, in
   AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
   TensorInfo& t = tensors_[p];
   AO_REQUIRE(!t.par2, "tensor %d is PARAFAC2: use aoadmm_par2_slab_upload", p);
+  AO_REQUIRE(local_rows < 0 || !t.blk.sparse, "tensor %d holds sparse data: a row block cannot replace it (use aoadmm_tensor_upload)", p);
+  if (t.blk.sparse) { t.blk.coo.clear(); t.blk.sparse = false; }   // a dense upload replaces the sparse form
   int64_t dims[8];
   for (int i = 0; i < t.nmodes; ++i) dims[i] = modes_[t.modes[i]].rows;
   if (local_rows < 0) {            // full array given: every rank keeps its block of rows
@@ -610,6 +612,38 @@ void Engine::tensor_upload(int p, const double* data, int prec, int64_t row0, in
   } else {
     block_upload(t.blk, t.nmodes, dims, data, prec, row0, local_rows);
   }
+  t.normsq_valid = false;
+}
+
+// Z.object{p} as a sptensor / sparse matrix (sparse.h): the block keeps the coalesced nonzeros, one sorted copy per
+// mode, and drops whatever dense form it had.  Replicated on every rank of a communicator.
+void Engine::tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const double* vals) {
+  require_usable();
+  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
+  AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
+  TensorInfo& t = tensors_[p];
+  AO_REQUIRE(!t.par2, "tensor %d is PARAFAC2: sparse slabs are not supported", p);
+  AO_REQUIRE(t.nmodes >= 2 && t.nmodes <= kCooMaxModes, "tensor %d: order %d unsupported for sparse data", p, t.nmodes);
+  int64_t dims[8];
+  for (int i = 0; i < t.nmodes; ++i) dims[i] = modes_[t.modes[i]].rows;
+  AO_HIP(hipSetDevice(device_));
+  CooBlock coo;
+  coo_build(coo, t.nmodes, dims, nnz, subs, vals, stream_);     // validates before anything of the old form is dropped
+  CpBlock& b = t.blk;
+  drop_permuted_copies(b);
+  b.X.data.release(); b.Xt.data.release();
+  b.emkr.release(); b.emkr2.release(); b.T.release(); b.frag.release(); b.scratch.release(); b.ft.release();
+  b.tmpA.release(); b.tmpB.release(); b.mask.release(); b.maskT.release();
+  for (int i = 0; i < 2; ++i) { b.own[i].release(); b.own_bytes[i] = 0; b.own_row0[i] = -1; }
+  b.coo = std::move(coo);
+  b.sparse = true;
+  b.nd = t.nmodes;
+  for (int i = 0; i < t.nmodes; ++i) b.dims[i] = dims[i];
+  b.full0 = dims[0]; b.row0 = 0;
+  b.has_data = true; b.has_mask = false; b.x_released = false;
+  b.cached_mode = -1;
+  b.has_xp = b.xp_refused = b.has_xq = b.xq_refused = b.has_xc = b.xc_refused = false;
+  b.xp_ksharded = false;
   t.normsq_valid = false;
 }
 
@@ -641,6 +675,8 @@ double Engine::tensor_normsq(int p) {
     }
     if (t.par2) {   // sum_k ||X_k||_F^2  (cmtf_AOADMM.m:145-155)
       tensor_sumsq(slot, t.p2.X.p, AOADMM_PREC_F64, (int64_t)t.p2.I * t.p2.Jtot, ws.d(), stream_);
+    } else if (t.blk.sparse) {     // norm(sptensor)^2 (:132): the coalesced values; every rank holds all of them
+      tensor_sumsq(slot, t.blk.coo.mode[0].val.p, AOADMM_PREC_F64, t.blk.coo.nnz, ws.d(), stream_);
     } else {
       AO_REQUIRE(!t.blk.x_released, "internal: ||X||^2 of tensor %d asked for after its natural-layout array was released", p);
       tensor_sumsq(slot, t.blk.X.data.p, t.blk.X.prec, t.blk.X.elems_padded(), ws.d(), stream_);
@@ -661,6 +697,7 @@ void Engine::tensor_synth(int p, int rank, uint64_t seed, double noise, int prec
   AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
   TensorInfo& t = tensors_[p];
   AO_REQUIRE(!t.par2 && t.nmodes == 3, "synthetic generator handles 3-way CP blocks");
+  AO_REQUIRE(!t.blk.sparse, "tensor %d holds sparse data: the synthetic generator writes dense blocks (upload dense data first)", p);
   AO_REQUIRE(rank > 0 && rank <= kMaxRank, "bad rank");
   AO_HIP(hipSetDevice(device_));
   const int64_t I = modes_[t.modes[0]].rows, J = modes_[t.modes[1]].rows, K = modes_[t.modes[2]].rows;
@@ -726,6 +763,7 @@ void Engine::tensor_mask_upload(int p, const uint8_t* mask) {
   TensorInfo& t = tensors_[p];
   CpBlock& b = t.blk;
   AO_REQUIRE(b.has_data, "upload Z.object{%d} before Z.miss{%d}", p + 1, p + 1);
+  AO_REQUIRE(!b.sparse, "Missing data (Z.miss) not supported for sptensor objects. Convert to tensor first. (Z.object{%d}, cmtf_AOADMM.m:78-79)", p + 1);
   AO_REQUIRE(!b.x_released, "Z.object{%d} was released after its pass copies were built: upload it again before Z.miss{%d}", p + 1, p + 1);
   AO_HIP(hipSetDevice(device_));
   const int64_t Iloc = b.dims[0], Ip = b.X.pad0, Ifull = b.full0;
@@ -1042,7 +1080,7 @@ void Engine::fold_finished(KernelStats& ks) {
 }
 
 void Engine::kernel_stats(int which, int reset, double* ms, int64_t* launches, double* bytes, double* flops) {
-  AO_REQUIRE(which >= 0 && which <= 2, "kernel_stats: which must be 0, 1 or 2");
+  AO_REQUIRE(which >= 0 && which <= 3, "kernel_stats: which must be 0, 1, 2 or 3");
   if (which == 2) profile_reductions_ = true;
   AO_HIP(hipSetDevice(device_));
   AO_HIP(hipStreamSynchronize(stream_));
@@ -1162,7 +1200,7 @@ bool Engine::ensure_blocked_copy(CpBlock& b) {
 // AOADMM_ERR_UNSUPPORTED (the caller falls back to the host-array form).
 void Engine::maybe_release_natural(TensorInfo& t) {
   CpBlock& b = t.blk;
-  if (b.x_released || b.nd != 3 || !(b.has_xc && b.has_xp && b.has_xq) || b.has_mask || !t.normsq_valid || !b.X.data.p) return;
+  if (b.sparse || b.x_released || b.nd != 3 || !(b.has_xc && b.has_xp && b.has_xq) || b.has_mask || !t.normsq_valid || !b.X.data.p) return;
   const char* pe = getenv("AOADMM_RELEASE_NATURAL");   // read per solve (the test suite switches it inside one process)
   const int policy = pe ? (atoi(pe) != 0 ? 1 : -1) : 0;
   if (policy < 0) return;
@@ -1254,7 +1292,7 @@ bool Engine::prefetch_next_contraction(const aoadmm_options& opt) {
         const ModeInfo& mi = modes_[m];
         if (mi.coupling != cid || mi.tensor != p) continue;
         TensorInfo& t = tensors_[p];                      // first mode the next iteration updates
-        if (t.par2 || t.blk.nd != 3 || small_direct(t.blk, mi.R)) return false;
+        if (t.par2 || t.blk.sparse || t.blk.nd != 3 || small_direct(t.blk, mi.R)) return false;
         FactorRef facs[8];
         for (int i = 0; i < t.nmodes; ++i) {
           const ModeInfo& o = modes_[t.modes[i]];
@@ -1275,6 +1313,10 @@ void Engine::block_mttkrp(CpBlock& b, int pos, const FactorRef* facs, int R, dou
   if (sys_done) *sys_done = false;
   AO_REQUIRE(b.has_data, "tensor has no data");
   AO_REQUIRE(pos >= 0 && pos < b.nd, "mttkrp: mode %d out of range", pos);
+  if (b.sparse) {                  // complete on every rank: no own-rows buffer, no collective, no cache, no rider
+    sparse_mttkrp(b, pos, facs, R, scale, out, ldOut);
+    return;
+  }
   const int prec = b.X.prec;
   const int64_t I = b.dims[0], Ip = b.X.pad0;
   const bool sharded = collective && this->sharded();
@@ -1455,6 +1497,35 @@ void Engine::block_mttkrp(CpBlock& b, int pos, const FactorRef* facs, int R, dou
     } else if (ldOut == out_rows_full) allreduce(out, out_rows_full * R);
     else for (int r = 0; r < R; ++r) allreduce(out + ldOut * r, out_rows_full);
   }
+}
+
+// MTTKRP of a sparse block (sparse.hip): factors gathered through their row-major copy when it is current
+void Engine::sparse_mttkrp(CpBlock& b, int pos, const FactorRef* facs, int R, double scale, double* out, int64_t ldOut) {
+  CooFactor f[kCooMaxModes];
+  int k = 0;
+  for (int m = 0; m < b.nd; ++m) {
+    if (m == pos) continue;
+    f[k++] = facs[m].pT ? CooFactor{facs[m].pT, (int64_t)R, 1} : CooFactor{facs[m].p, 1, facs[m].ld};
+  }
+  KernelStats& ks = kstats_[3];
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (profile_) {
+    if (ks.pending.size() >= 512) fold_finished(ks);
+    if (ks.pending.size() < 4096) {
+      e0 = take_event();
+      e1 = take_event();
+      AO_HIP(hipEventRecord(e0, stream_));
+    }
+  }
+  coo_mttkrp(b.coo, pos, f, R, scale, out, ldOut, stream_);
+  if (e0) {
+    AO_HIP(hipEventRecord(e1, stream_));
+    ks.pending.emplace_back(e0, e1);
+    ks.timed++;
+  }
+  ks.launches++;
+  ks.bytes += coo_mttkrp_bytes(b.coo, pos, R);
+  ks.flops += coo_mttkrp_flops(b.coo, R);
 }
 
 std::vector<int> Engine::update_sequence(int p) const {
@@ -3332,6 +3403,8 @@ void Engine::resident_unfold_gram(int p, int pos, int slab, double* out_host) {
   } else {
     const CpBlock& b = t.blk;
     AO_REQUIRE(b.has_data, "tensor %d has no data", p);
+    if (b.sparse)
+      throw Error(AOADMM_ERR_UNSUPPORTED, fmt("resident unfold_gram: tensor %d is sparse (the Gram matrix of its unfolding is built on the host)", p));
     AO_REQUIRE((b.nd == 2 || b.nd == 3) && pos >= 0 && pos < b.nd, "unfold_gram handles matrices and 3-way tensors");
     if (sharded() && pos == 0)
       throw Error(AOADMM_ERR_UNSUPPORTED, "resident unfold_gram: the first mode of a row-sharded block pairs rows of different ranks");

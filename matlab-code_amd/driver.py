@@ -25,6 +25,8 @@ import numpy as np
 
 from . import _capi as capi
 from .engine import Engine, constraint_descriptor, default_engine
+from .sptensor import coo_of
+from .sptensor import unfold_gram as _sparse_unfold_gram
 
 
 def _which_p(Z):
@@ -85,11 +87,15 @@ def _leading_eigvecs(Y, r):
 def cmtf_nvecs(Z, n, r, engine=None):
     """functions/cmtf_nvecs.m:1-58 for a CP block: first r left singular vectors of the mode-n unfolding (0-based n)
     of the data set that owns mode n.  The I_n x I_n Gram matrix of the unfolding comes from the device
-    (`aoadmm_op_unfold_gram`), the r leading eigenvectors from LAPACK on the host."""
-    eng = engine or default_engine()
+    (`aoadmm_op_unfold_gram`), or for a sparse block from scipy.sparse on the host (no densified tensor); the r
+    leading eigenvectors from LAPACK on the host."""
     which_p = _which_p(Z)
     p = which_p[n]
     md = [m - 1 for m in Z['modes'][p]]
+    coo = coo_of(Z['object'][p])
+    if coo is not None:             # sparse block: sptenmat(X, n) * sptenmat(X, n)' on the host (cmtf_nvecs.m:41-42)
+        return _leading_eigvecs(_sparse_unfold_gram(*coo, md.index(n)), r)
+    eng = engine or default_engine()
     Y = _resident_gram(eng, Z, p, md.index(n), int(Z['size'][n]))
     if Y is None:
         Y = eng.unfold_gram(np.asarray(Z['object'][p], dtype=np.float64), md.index(n))
@@ -249,7 +255,11 @@ def _make_options(alg_options):
 
 
 def build_model(eng, Z, precision='f64'):
-    """Describe the struct Z to the engine and upload Z.object (cmtf_AOADMM.m:23-41,124-156)."""
+    """Describe the struct Z to the engine and upload Z.object (cmtf_AOADMM.m:23-41,124-156).
+
+    Z.object{p} of a CP block may be dense, an `sptensor`, or (2-way blocks) any object with `.tocoo()` such as a
+    scipy.sparse matrix; sparse blocks go up as coalesced COO nonzeros (`aoadmm_tensor_upload_coo`) and stay fp64
+    whatever `precision` says (it applies to dense blocks only)."""
     lib = eng.lib
     nb_modes = len(Z['size'])
     which_p = _which_p(Z)
@@ -317,6 +327,16 @@ def build_model(eng, Z, precision='f64'):
     for p in range(P):
         if Z['model'][p] == 'CP':
             obj = Z['object'][p]
+            coo = None if isinstance(obj, dict) else coo_of(obj)
+            if coo is not None:
+                subs, vals, shape = coo
+                md = [m - 1 for m in Z['modes'][p]]
+                if tuple(shape) != tuple(int(Z['size'][m]) for m in md):
+                    raise ValueError('Z.object{%d} has size %s, Z.size says %s' % (p + 1, tuple(shape), [Z['size'][m] for m in md]))
+                if miss[p] is not None:                                              # cmtf_AOADMM.m:77-79
+                    raise ValueError('Missing data (Z.miss) not supported for sptensor objects. Convert to tensor first.')
+                eng.upload_coo(p, subs, vals)
+                continue
             if isinstance(obj, dict) and obj.get('synthetic'):
                 capi.check(lib.aoadmm_tensor_synth(eng.h, p, int(obj['rank']), int(obj['seed']), float(obj['noise']), prec))
             else:

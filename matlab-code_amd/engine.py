@@ -109,6 +109,33 @@ class Engine:
         """Bring-up/test transport: engines driven by threads of this process form group `key` (see aoadmm_hip.h)."""
         capi.check(self.lib.aoadmm_comm_init_local(self.h, int(key), int(rank), int(world)))
 
+    # ---- data -----------------------------------------------------------------------
+    def upload_coo(self, p, subs, vals):
+        """Z.object{p} of a CP block as COO nonzeros (`aoadmm_tensor_upload_coo`): subs nnz x N, 0-based; vals nnz.
+        Duplicates are summed on the device; the sizes are those of the model."""
+        subs = np.asarray(subs, dtype=np.int64)
+        vals = np.ascontiguousarray(np.asarray(vals, dtype=np.float64).reshape(-1))
+        if subs.ndim != 2 or subs.shape[0] != vals.shape[0]:
+            raise ValueError('upload_coo: subs must be nnz x N with nnz = len(vals)')
+        subs = np.asfortranarray(subs)                # column-major nnz x N (the layout of sptensor.subs)
+        capi.check(self.lib.aoadmm_tensor_upload_coo(self.h, int(p), int(vals.shape[0]),
+                                                     subs.ctypes.data_as(C.POINTER(C.c_int64)), capi.dptr(vals)))
+
+    def resident_mttkrp(self, p, tensor_mode, rows, R):
+        """One MTTKRP of the resident block p against the current factors (`aoadmm_resident_mttkrp`): rows x R."""
+        out = np.zeros((rows, R), order='F')
+        ms = C.c_float(0)
+        capi.check(self.lib.aoadmm_resident_mttkrp(self.h, int(p), int(tensor_mode), capi.dptr(out), C.byref(ms)))
+        return out
+
+    def kernel_stats(self, which, reset=False):
+        """(ms, launches, bytes, flops) of a kernel class since the last reset (`aoadmm_kernel_stats`); which = 3:
+        MTTKRPs of sparse blocks."""
+        ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
+        capi.check(self.lib.aoadmm_kernel_stats(self.h, int(which), int(bool(reset)), C.byref(ms), C.byref(n),
+                                                C.byref(by), C.byref(fl)))
+        return ms.value, n.value, by.value, fl.value
+
     # ---- op level -----------------------------------------------------------------
     def mttkrp(self, X, U, n, precision='f64'):
         """`mttkrp(X,U,n)` with 0-based n (cmtf_fun_AOADMM.m:97)."""

@@ -87,13 +87,65 @@ int constraint_id(const std::string& n) {
   return 0;
 }
 
-// dense numeric data of a Tensor Toolbox `tensor` (field .data) or a plain array
+// dense numeric data of a Tensor Toolbox `tensor` (field .data) or a plain array.  Anything else (single, logical,
+// integer, complex sparse, a sparse logical matrix, an sptensor with non-double or complex values) is routed back to
+// the MATLAB path (cmtf:hip:unsupported, caught by cmtf_fun_AOADMM_hip.m).
 const mxArray* dense_data(const mxArray* obj) {
-  if (mxIsDouble(obj)) return obj;
+  if (mxIsDouble(obj) && !mxIsSparse(obj)) return obj;
   const mxArray* d = mxIsClass(obj, "tensor") ? mxGetProperty(obj, 0, "data") : nullptr;
   if (!d || !mxIsDouble(d))
-    mexErrMsgIdAndTxt("cmtf:hip:unsupported", "Z.object must be a dense double array or a dense tensor (sptensor stays on the MATLAB path)");
+    mexErrMsgIdAndTxt("cmtf:hip:unsupported", "Z.object is not a double array, a dense tensor, a real double sptensor or a "
+                                              "real sparse double matrix: it stays on the MATLAB path");
   return d;
+}
+
+// an sptensor, or a real sparse double matrix (a complex or logical sparse matrix goes through dense_data's fallback)
+bool is_sparse_object(const mxArray* obj) {
+  return mxIsClass(obj, "sptensor") || (mxIsDouble(obj) && mxIsSparse(obj) && !mxIsComplex(obj));
+}
+
+// Z.object{p} as an sptensor (subs 1-based doubles nnz x N, vals nnz x 1, size) or a MATLAB sparse double matrix
+// (compressed columns: ir / jc / values) -> 0-based int64 COO, column-major nnz x N, through aoadmm_tensor_upload_coo.
+// The sizes must be those of Z.size for the block's modes (`md`).
+void upload_sparse(int p, const mxArray* obj, const mxArray* sz, const std::vector<int>& md) {
+  const int N = (int)md.size();
+  std::vector<int64_t> subs;
+  std::vector<double> vals;
+  std::vector<double> shape;
+  if (mxIsClass(obj, "sptensor")) {
+    mxArray* s = mxGetProperty(obj, 0, "subs");
+    mxArray* v = mxGetProperty(obj, 0, "vals");
+    mxArray* z = mxGetProperty(obj, 0, "size");
+    if (!s || !v || !z || !mxIsDouble(s) || !mxIsDouble(z))
+      mexErrMsgIdAndTxt("cmtf:hip:invalid", "Z.object{%d}: sptensor without double subs / size", p + 1);
+    if (!mxIsDouble(v) || mxIsComplex(v))
+      mexErrMsgIdAndTxt("cmtf:hip:unsupported", "Z.object{%d}: sptensor values are not real doubles: it stays on the MATLAB path", p + 1);
+    shape.assign(mxGetDoubles(z), mxGetDoubles(z) + mxGetNumberOfElements(z));
+    const size_t nnz = mxGetNumberOfElements(v);
+    if (nnz > 0 && (mxGetM(s) != nnz || (int)mxGetN(s) != N))
+      mexErrMsgIdAndTxt("cmtf:hip:invalid", "Z.object{%d}: sptensor subs is not nnz x %d", p + 1, N);
+    subs.resize(nnz * N);
+    const double* sd = nnz ? mxGetDoubles(s) : nullptr;
+    for (size_t i = 0; i < nnz * N; ++i) subs[i] = (int64_t)sd[i] - 1;
+    vals.assign(mxGetDoubles(v), mxGetDoubles(v) + nnz);
+    mxDestroyArray(s);                                    // the property copies: no second copy of subs held further on
+    mxDestroyArray(v);
+    mxDestroyArray(z);
+  } else {
+    const size_t M = mxGetM(obj), C = mxGetN(obj);
+    const mwIndex* jc = mxGetJc(obj);
+    const mwIndex* ir = mxGetIr(obj);
+    const size_t nnz = jc[C];
+    shape = {(double)M, (double)C};
+    subs.resize(nnz * 2);
+    for (size_t j = 0; j < C; ++j)
+      for (mwIndex k = jc[j]; k < jc[j + 1]; ++k) { subs[k] = (int64_t)ir[k]; subs[nnz + k] = (int64_t)j; }
+    vals.assign(mxGetDoubles(obj), mxGetDoubles(obj) + nnz);
+  }
+  bool same = (int)shape.size() == N;
+  for (int i = 0; same && i < N; ++i) same = shape[i] == mxGetScalar(mxGetCell(sz, md[i]));
+  if (!same) mexErrMsgIdAndTxt("cmtf:hip:invalid", "Z.object{%d}: size does not match Z.size of its modes", p + 1);
+  check(aoadmm_tensor_upload_coo(g_ctx, p, (int64_t)vals.size(), subs.data(), vals.data()));
 }
 
 void put_state(int field_id, int index, int slab, const mxArray* a) {
@@ -289,6 +341,11 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         packed.insert(packed.end(), mxGetDoubles(xk), mxGetDoubles(xk) + mxGetNumberOfElements(xk));
       }
       check(aoadmm_par2_slab_upload(g_ctx, p, AOADMM_ALL_SLABS, packed.data()));
+    } else if (is_sparse_object(obj)) {
+      const mxArray* mp = mxGetCell(modes, p);
+      std::vector<int> md(mxGetNumberOfElements(mp));
+      for (size_t i = 0; i < md.size(); ++i) md[i] = (int)mxGetDoubles(mp)[i] - 1;
+      upload_sparse(p, obj, sz, md);                     // values stay fp64 whatever options.hip.precision says
     } else {
       check(aoadmm_tensor_upload(g_ctx, p, mxGetDoubles(dense_data(obj)), precision));
     }
@@ -296,6 +353,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     const mxArray* mk = (miss && !mxIsEmpty(miss) && (mwSize)p < mxGetNumberOfElements(miss)) ? mxGetCell(miss, p) : nullptr;
     if (mk && !mxIsEmpty(mk)) {
       has_missing = true;
+      if (is_sparse_object(obj))                          // cmtf_AOADMM.m:77-79
+        mexErrMsgIdAndTxt("cmtf:missingData:sptensor", "Missing data (Z.miss) not supported for sptensor objects. Convert to tensor first.");
       if (mxIsCell(obj)) {
         if (!mxIsCell(mk) || mxGetNumberOfElements(mk) != mxGetNumberOfElements(obj))
           mexErrMsgIdAndTxt("cmtf:missingData:PAR2maskNotCell", "Z.miss{%d} must be a cell array of length %d for PAR2.", p + 1,

@@ -11,16 +11,17 @@ function [G,out] = cmtf_fun_AOADMM_hip(Z,Znorm_const,G,fh,gh,lscalar,uscalar,opt
 % MATLAB process, precision = 'f64' | 'f32', par2_slab_sharding, no_permuted_copy).
 %
 % Function handles cannot cross to the GPU, so Z.prox_operators / Z.reg_func (cmtf_AOADMM.m:30-32) are
-% dropped and the MEX gateway re-reads the constraint descriptors Z.constraints{m}. Models the device
-% path does not cover ('custom' constraints, KL/IS/beta losses, sptensor data) raise cmtf:hip:unsupported, which is caught here and
-% handed to the original MATLAB implementation, so every example script keeps running.
+% dropped and the MEX gateway re-reads the constraint descriptors Z.constraints{m}. Sparse CP blocks (an
+% sptensor, or a sparse double matrix for a 2-way block) go to the device as they are, as COO nonzeros in fp64.
+% Models the device path does not cover ('custom' constraints, KL/IS/beta losses) raise cmtf:hip:unsupported,
+% which is caught here and handed to the original MATLAB implementation, so every example script keeps running.
 % Znorm_const, fh, gh, lscalar, uscalar are only needed by that fallback.
 
     Zs = Z;
     if isfield(Zs,'prox_operators'), Zs = rmfield(Zs,'prox_operators'); end
     if isfield(Zs,'reg_func'),       Zs = rmfield(Zs,'reg_func');       end
-    for p = 1:numel(Zs.object)           % Tensor Toolbox objects -> plain double arrays
-        if isa(Zs.object{p},'tensor')
+    for p = 1:numel(Zs.object)           % dense Tensor Toolbox objects -> plain double arrays; sptensor and
+        if isa(Zs.object{p},'tensor')    % sparse matrices are read by the gateway as they are (no densifying)
             Zs.object{p} = double(Zs.object{p});
         end
     end

@@ -7,8 +7,8 @@ function U = cmtf_nvecs_hip(Z,n,r)
     for p = 1:P
         i = find(Z.modes{p} == n);
         if isempty(i), continue; end
-        if isa(Z.object{p},'sptensor')
-            U = cmtf_nvecs(Z,n,r);          % sparse data stay on the MATLAB path
+        if isa(Z.object{p},'sptensor') || issparse(Z.object{p})
+            U = cmtf_nvecs(Z,n,r);          % sparse unfolding: its Gram matrix on the host (sptenmat, cmtf_nvecs.m:41-42)
             return
         end
         Y = aoadmm_mex('unfold_gram', double(Z.object{p}), i(1));

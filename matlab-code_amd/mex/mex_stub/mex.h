@@ -36,6 +36,11 @@ mwSize mxGetNumberOfDimensions(const mxArray*);
 bool mxIsChar(const mxArray*);
 void* mxGetData(const mxArray*);
 bool mxIsUint8(const mxArray*);
+bool mxIsSparse(const mxArray*);
+bool mxIsComplex(const mxArray*);
+void mxDestroyArray(mxArray*);
+mwIndex* mxGetIr(const mxArray*);
+mwIndex* mxGetJc(const mxArray*);
 mxArray* mxCreateDoubleMatrix(mwSize, mwSize, mxComplexity);
 mxArray* mxCreateDoubleScalar(double);
 mxArray* mxCreateCellMatrix(mwSize, mwSize);

@@ -1,0 +1,100 @@
+"""A small Tensor Toolbox `sptensor` (cmtf_AOADMM.m:77-79, :132): coordinate storage of a sparse CP block.
+
+    X = sptensor(subs, vals, shape)
+
+`subs` is nnz x N with 0-based subscripts (MATLAB's `X.subs` minus 1), `vals` has nnz entries.  Duplicate
+subscripts are summed on construction (sptensor's constructor rule) and the nonzeros are kept in column-major
+linear order.  `build_model` uploads it through `aoadmm_tensor_upload_coo`; the values stay fp64 on the device.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+
+class sptensor:
+    def __init__(self, subs, vals, shape):
+        shape = tuple(int(s) for s in shape)
+        if len(shape) < 2:
+            raise ValueError('sptensor: at least 2 modes, got shape %s' % (shape,))
+        if any(s < 1 for s in shape):
+            raise ValueError('sptensor: every size must be positive, got %s' % (shape,))
+        subs = np.asarray(subs)
+        vals = np.asarray(vals, dtype=np.float64).reshape(-1)
+        if subs.size == 0:
+            subs = np.zeros((0, len(shape)), dtype=np.int64)
+        if subs.ndim != 2 or subs.shape[1] != len(shape):
+            raise ValueError('sptensor: subs must be nnz x %d, got %s' % (len(shape), subs.shape))
+        if subs.shape[0] != vals.shape[0]:
+            raise ValueError('sptensor: %d subscripts but %d values' % (subs.shape[0], vals.shape[0]))
+        if not np.issubdtype(subs.dtype, np.integer):
+            if not np.all(np.asarray(subs) == np.floor(subs)):
+                raise ValueError('sptensor: subscripts must be integers')
+        subs = subs.astype(np.int64)
+        if subs.size and (subs.min() < 0 or np.any(subs.max(axis=0) >= np.asarray(shape))):
+            bad = np.argwhere((subs < 0) | (subs >= np.asarray(shape)[None, :]))[0]
+            raise ValueError('sptensor: subscript %d of nonzero %d in mode %d is outside [0, %d)'
+                             % (subs[bad[0], bad[1]], bad[0], bad[1], shape[bad[1]]))
+        # column-major linear order; duplicates summed in the order given
+        order = np.lexsort(subs.T) if subs.shape[0] else np.zeros(0, dtype=np.int64)
+        subs, vals = subs[order], vals[order]
+        if subs.shape[0]:
+            new = np.ones(subs.shape[0], dtype=bool)
+            new[1:] = np.any(subs[1:] != subs[:-1], axis=1)
+            starts = np.flatnonzero(new)
+            vals = np.add.reduceat(vals, starts)
+            subs = subs[starts]
+        self.subs = np.ascontiguousarray(subs)
+        self.vals = np.ascontiguousarray(vals)
+        self.shape = shape
+
+    @property
+    def ndim(self):
+        return len(self.shape)
+
+    @property
+    def nnz(self):
+        return int(self.vals.shape[0])
+
+    def full(self):
+        """Dense numpy array (column-major), for tests and small blocks."""
+        X = np.zeros(self.shape, order='F')
+        if self.nnz:
+            np.add.at(X, tuple(self.subs.T), self.vals)
+        return X
+
+    def norm(self):
+        return float(np.sqrt(np.sum(self.vals * self.vals)))
+
+    def __repr__(self):
+        return 'sptensor(shape=%s, nnz=%d)' % (self.shape, self.nnz)
+
+
+def coo_of(obj):
+    """(subs int64 nnz x N, vals float64, shape) of an sptensor or of any object with .tocoo() (a scipy.sparse
+    matrix); None for anything else."""
+    if isinstance(obj, sptensor):
+        return obj.subs, obj.vals, obj.shape
+    if hasattr(obj, 'tocoo') and not isinstance(obj, np.ndarray):
+        c = obj.tocoo()
+        subs = np.stack([np.asarray(c.row, dtype=np.int64), np.asarray(c.col, dtype=np.int64)], axis=1)
+        return subs, np.asarray(c.data, dtype=np.float64), tuple(int(s) for s in c.shape)
+    return None
+
+
+def unfold_gram(subs, vals, shape, n):
+    """Y = X_(n) X_(n)' of a sparse tensor (cmtf_nvecs.m:41-42, `double(sptenmat(X, n))`) without densifying the
+    tensor: the unfolding is a scipy.sparse matrix (columns = linear index of the other modes, column-major)."""
+    import scipy.sparse as sps            # only on this path
+    subs = np.asarray(subs, dtype=np.int64)
+    others = [m for m in range(len(shape)) if m != n]
+    col = np.zeros(subs.shape[0], dtype=np.int64)
+    stride = 1
+    for m in others:
+        col += subs[:, m] * stride
+        stride *= int(shape[m])
+    if stride >= 2 ** 63:
+        raise ValueError('sptensor: the mode-%d unfolding has too many columns for 64-bit indices' % (n + 1))
+    # column ids compressed to the ones that occur (same product A*A')
+    ucol, cidx = np.unique(col, return_inverse=True)
+    A = sps.csr_matrix((np.asarray(vals, dtype=np.float64), (subs[:, n], cidx)), shape=(int(shape[n]), max(len(ucol), 1)))
+    return np.asfortranarray((A @ A.T).toarray())

@@ -1,0 +1,160 @@
+"""Per-mode time of the sparse (COO) MTTKRP (csrc/sparse.hip) on one GPU, next to a torch index_add_ MTTKRP of the same
+data on the same GPU.
+
+    python3 tools/time_sparse.py [--dims 1000000,100000,10000] [--nnz 100000000] [--R 20] [--skew] [--reps 5]
+
+Prints one JSON line per (layout, mode) and a summary line.  Layouts: 'colmajor' gathers from the column-major factors
+(what aoadmm_resident_mttkrp sees before any solve), 'rowmajor' after one outer iteration, when the Gram kernel has left
+the row-major copies the solver's own MTTKRPs gather from.  Bytes are algorithmic (nonzeros streamed + factor rows
+gathered + output written, aoadmm_kernel_stats(3)); the HBM peak taken for the share is 8 TB/s.
+--skew draws every subscript as floor(size * u^4), u uniform: a power law, row 0 of the first mode then owns ~3 %
+of all nonzeros.  Subscripts go up unsorted and uncoalesced: the device sorts and sums duplicates.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+pkg = importlib.import_module('matlab-code_amd')
+capi = importlib.import_module('matlab-code_amd._capi')
+
+PEAK = 8.0e12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--dims', default='1000000,100000,10000')
+    ap.add_argument('--nnz', type=float, default=1e8)
+    ap.add_argument('--R', type=int, default=20)
+    ap.add_argument('--skew', action='store_true')
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--no-torch', action='store_true')
+    ap.add_argument('--seed', type=int, default=0)
+    a = ap.parse_args()
+    if not a.no_torch:
+        # torch (and the HIP runtime it ships) first, as bench.py does: loaded after the library, the process aborted in
+        # its exit-time destructors
+        import torch
+        torch.cuda.init()
+    dims = [int(float(v)) for v in a.dims.split(',')]
+    N, R, nnz = len(dims), a.R, int(a.nnz)
+    rng = np.random.default_rng(a.seed)
+    t0 = time.time()
+    subs = np.empty((nnz, N), dtype=np.int64, order='F')
+    for m, s in enumerate(dims):
+        if a.skew:
+            subs[:, m] = np.minimum((s * rng.random(nnz) ** 4).astype(np.int64), s - 1)
+        else:
+            subs[:, m] = rng.integers(0, s, nnz)
+    vals = rng.random(nnz)
+    t_gen = time.time() - t0
+    eng = pkg.Engine(0)
+    try:
+        run(a, eng, dims, N, R, nnz, subs, vals, t_gen)
+    finally:
+        eng.close()
+
+
+def run(a, eng, dims, N, R, nnz, subs, vals, t_gen):
+    rng = np.random.default_rng(a.seed + 1)
+    lib, h = eng.lib, eng.h
+    capi.check(lib.aoadmm_model_begin(h, N, 1, 0))
+    for m, s in enumerate(dims):
+        capi.check(lib.aoadmm_model_set_mode(h, m, s, R))
+    modes = (C.c_int * N)(*range(N))
+    capi.check(lib.aoadmm_model_add_cp(h, 0, N, modes, 1.0))
+    for m in range(N):
+        capi.check(lib.aoadmm_model_set_coupling(h, m, -1, None, 0, 0, None, 0, 0))
+    capi.check(lib.aoadmm_model_end(h))
+    t0 = time.time()
+    eng.upload_coo(0, subs, vals)
+    eng.synchronize()
+    t_up = time.time() - t0
+    normsq = C.c_double(0)
+    capi.check(lib.aoadmm_tensor_normsq(h, 0, C.byref(normsq)))
+    U = [rng.random((s, R)) for s in dims]
+    for m in range(N):
+        Um = np.asfortranarray(U[m])
+        capi.check(lib.aoadmm_state_set(h, capi.F_FAC, m, 0, capi.dptr(Um), dims[m], R))
+    print(json.dumps({'what': 'setup', 'dims': dims, 'nnz_given': nnz, 'R': R, 'skew': a.skew, 'gen_s': round(t_gen, 2),
+                      'upload_s': round(t_up, 2), 'normsq': normsq.value}), flush=True)
+    rows = []
+
+    def time_modes(layout):
+        for n in range(N):
+            out = np.zeros((dims[n], R), order='F')
+            ms = C.c_float(0)
+            capi.check(lib.aoadmm_resident_mttkrp(h, 0, n, None, C.byref(ms)))          # warm-up
+            eng.kernel_stats(3, reset=True)
+            ev = []
+            for _ in range(a.reps):
+                capi.check(lib.aoadmm_resident_mttkrp(h, 0, n, None, C.byref(ms)))
+                ev.append(ms.value)
+            kms, launches, by, fl = eng.kernel_stats(3, reset=True)
+            per = kms / launches
+            bpl = by / launches
+            r = {'what': 'mttkrp_coo', 'layout': layout, 'mode': n + 1, 'ms': round(per, 4),
+                 'ms_events_min': round(min(ev), 4), 'GB': round(bpl / 1e9, 3), 'TBps': round(bpl / per / 1e9, 3),
+                 'hbm_share': round(bpl / (per * 1e-3) / PEAK, 3), 'GFLOPs': round(fl / launches / per / 1e6, 1)}
+            if n == 0:
+                capi.check(lib.aoadmm_resident_mttkrp(h, 0, n, capi.dptr(out), C.byref(ms)))
+                r['checksum'] = float(out.sum())
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+
+    time_modes('colmajor')
+    # one outer iteration (unconstrained, no couplings): the Gram kernels leave the row-major factor copies behind
+    o = capi.Options()
+    o.MaxOuterIters, o.MaxInnerIters, o.use_dimtree = 1, 1, 1
+    res = capi.Result()
+    capi.check(lib.aoadmm_solve(h, C.byref(o), C.byref(res)))
+    time_modes('rowmajor')
+    if not a.no_torch:
+        import torch
+        dev = torch.device('cuda:0')
+        # the coalesced data the library holds would differ only in a few duplicates; the reference takes the raw COO
+        ts = torch.from_numpy(np.ascontiguousarray(subs.T)).to(dev)
+        tv = torch.from_numpy(vals).to(dev)
+        Uf = []
+        for m in range(N):
+            Um = np.zeros((dims[m], R), order='F')
+            capi.check(lib.aoadmm_state_get(h, capi.F_FAC, m, 0, capi.dptr(Um), dims[m], R))
+            Uf.append(torch.from_numpy(np.ascontiguousarray(Um)).to(dev))
+        for n in range(N):
+            def torch_mttkrp():
+                p = tv[:, None].clone()
+                for m in range(N):
+                    if m != n:
+                        p = p * Uf[m].index_select(0, ts[m])
+                o_ = torch.zeros(dims[n], R, dtype=torch.float64, device=dev)
+                o_.index_add_(0, ts[n], p)
+                return o_
+            torch_mttkrp()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.reps):
+                torch_mttkrp()
+            e1.record()
+            torch.cuda.synchronize()
+            per = e0.elapsed_time(e1) / a.reps
+            ours = [r for r in rows if r.get('layout') == 'rowmajor' and r['mode'] == n + 1][0]
+            r = {'what': 'torch_index_add', 'mode': n + 1, 'ms': round(per, 4), 'speedup_of_coo': round(per / ours['ms'], 2)}
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+    rm = [r for r in rows if r.get('layout') == 'rowmajor']
+    print(json.dumps({'what': 'summary', 'skew': a.skew, 'rowmajor_ms_sum': round(sum(r['ms'] for r in rm), 3),
+                      'rowmajor_TBps_mean': round(float(np.mean([r['TBps'] for r in rm])), 3)}), flush=True)
+
+
+if __name__ == '__main__':
+    main()
