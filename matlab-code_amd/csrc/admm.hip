@@ -1361,8 +1361,7 @@ static void tv_fast_launch(const ColArgs& a, const double* warm, int64_t ldw, co
   if (a.rows > kTvParMax) {
     AO_REQUIRE(a.ws != nullptr && a.rows < (int64_t(1) << 24), "TV prox: %lld rows need the global workspace (below 2^24 rows)",
                (long long)a.rows);
-    static const bool all_global = getenv("AOADMM_TV_ALL_GLOBAL") != nullptr;   // development switch (tools/time_tv_long*.py)
-    if (a.rows <= kTvHybridMax && !all_global) {
+    if (a.rows <= kTvHybridMax) {
       ensure_dynamic_lds(reinterpret_cast<const void*>(prox_tv_fast_k<1024, 2>), (int)tv_hybrid_lds(kTvHybridMax));
       prox_tv_fast_k<1024, 2><<<a.R, 1024, tv_hybrid_lds(a.rows), s>>>(a, warm, ldw, fz, ctl);
     } else {
@@ -1401,8 +1400,7 @@ void prox_apply(const ProxSpec& ps, const double* V, int64_t ldv, double* Zout, 
       prox_simplex_col_k<<<R, 256, 0, s>>>(a, ctl);
       break;
     case AOADMM_C_TV: {
-      static const bool seq_long = getenv("AOADMM_TV_SEQ_LONG") != nullptr;     // development switch: one-thread scan beyond 4096 rows
-      if (rows <= kTvParMax || (!seq_long && ws != nullptr && rows < (int64_t(1) << 24))) {   // LDS-resident, or the same in the workspace
+      if (rows <= kTvParMax || (ws != nullptr && rows < (int64_t(1) << 24))) {   // LDS-resident, or the same in the workspace
         tv_fast_launch(a, warm, ldw, TvFused(), ctl, s);
         break;
       }
@@ -1745,8 +1743,7 @@ size_t admm_loop_wg_lds(int rmax, int nt, int64_t rows, bool gram) {
 }
 
 bool admm_loop_wg_ok(int64_t rows, int R, int ptype, int max_inner) {
-  static const bool off = getenv("AOADMM_NO_WG_LOOP") != nullptr;          // development switch
-  if (off || max_inner < 1) return false;
+  if (max_inner < 1) return false;
   if (!(prox_is_fusable(ptype) || prox_is_colnorm(ptype))) return false;
   return rows <= kWgLoopRows && R <= 16;
 }

@@ -104,13 +104,14 @@ __device__ __forceinline__ float quarter_sum4(float a, float b, float c, float d
 // L2 (NT = 1 only, i.e. R <= 20: the headline rank): two-level accumulation.  The MFMA adds into an fp32 accumulator;
 // a run of 500 dependent adds (2000 columns) leaves a relative error of ~13 * 2^-24 in an entry of T, which after the
 // reductions and 25 outer iterations showed as 2e-8..6e-8 in the factors against the fp64 tensor mode -- outside the
-// 1e-8 of north_star.  With L2 the fp32 accumulators are flushed every `flush_every` loop rounds (default 3 = 72
+// 1e-8 of north_star.  With L2 the fp32 accumulators are flushed every `flush_every` loop rounds (kFlushEvery = 3: 72
 // columns = 18 adds) into fp64 sums and cleared: the 32 MFMA accumulators of a lane into the wave's own 16 KB slice of
 // LDS ([acc index][lane] doubles, conflict-free), the 32 packed-FMA accumulators of the leftover columns are first added over the four k-quarters
 // of the wave (quarter_sum4) and then into 8 fp64 registers (the VGPR budget at two waves per SIMD, 256, has no room
 // for 64 more register pairs: the kernel uses 202).
 // What is left is the rounding of the finished sum to the fp32 entry of T (2^-25 relative, independent per entry).
 // The flush is ~130 VALU/LDS instructions per 144 MFMAs of a wave and overlaps with the other wave's matrix work.
+constexpr int kFlushEvery = 3;
 template <int NT, bool EX, bool L2 = false>
 __global__ __launch_bounds__(256, NT <= 2 ? 2 : 1) void contract16_f32(KArgs a) {
   static_assert(!L2 || NT == 1, "two-level accumulation exists for one 16-column tile (R <= 20)");
@@ -860,17 +861,12 @@ void launch_contract(const void* X, int prec, const ContractPlan& pl, const doub
     pack_frag16_f32<<<(unsigned)cdiv(total, 256), 256, 0, s>>>(F, ldF, pl.C, pl.R, nt16, ex ? 1 : 0, Cg, (float*)frag_ws);
     AO_KERNEL_CHECK();
     size_t tsh = (size_t)4 * kTileRows * pl.R * sizeof(float);   // T tile of each of the four waves
-    // two-level accumulation for R <= 20 (see the kernel); AOADMM_CONTRACT_FLUSH = rounds of 24 columns between
-    // flushes (development switch; 0 = single-level fp32 accumulation as in rounds 1-2)
-    static const int flush_every = [] { const char* e = getenv("AOADMM_CONTRACT_FLUSH"); return e ? atoi(e) : 3; }();
-    a.flush_every = flush_every;
-    const bool l2 = nt16 == 1 && flush_every > 0;
-    if (l2) tsh = (size_t)4 * 16384;
+    // two-level accumulation for R <= 20 (see the kernel)
+    a.flush_every = kFlushEvery;
+    if (nt16 == 1) tsh = (size_t)4 * 16384;
 #define AO_GO(K) { if (tsh > 65536) ensure_dynamic_lds(reinterpret_cast<const void*>(K), (int)tsh); if (ev0) AO_HIP(hipEventRecord(ev0, s)); K<<<grid, 256, tsh, s>>>(a); }
-    if (l2 && !ex) AO_GO((contract16_f32<1, false, true>))
-    else if (l2) AO_GO((contract16_f32<1, true, true>))
-    else if (nt16 == 1 && !ex) AO_GO((contract16_f32<1, false>))
-    else if (nt16 == 1) AO_GO((contract16_f32<1, true>))
+    if (nt16 == 1 && !ex) AO_GO((contract16_f32<1, false, true>))
+    else if (nt16 == 1) AO_GO((contract16_f32<1, true, true>))
     else if (nt16 == 2 && !ex) AO_GO((contract16_f32<2, false>))
     else if (nt16 == 2) AO_GO((contract16_f32<2, true>))
     else if (nt16 == 3 && !ex) AO_GO((contract16_f32<3, false>))

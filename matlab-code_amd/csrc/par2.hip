@@ -588,8 +588,7 @@ __device__ __forceinline__ void par2_b_slab_regs_dev(const P2BArgs& a, const P2D
 constexpr int kP2RegsMaxR = 4;
 // rows per lane of the register form for a block whose longest slab has Jmax rows (0: not applicable)
 static int par2_regs_rows(const P2Dims& d) {
-  static const bool off = getenv("AOADMM_NO_PAR2_REGS") != nullptr;           // development switch
-  if (off || d.R > kP2RegsMaxR) return 0;
+  if (d.R > kP2RegsMaxR) return 0;
   return d.Jmax <= 64 ? 1 : (d.Jmax <= 128 ? 2 : (d.Jmax <= 256 ? 4 : 0));
 }
 template <int NR>
@@ -827,8 +826,7 @@ __global__ __launch_bounds__(kP2Threads) void par2_b_close_k(P2BArgs a, P2Dims d
 }
 
 bool par2_b_loop_folded_ok(const P2Dims& d, bool constrained, bool sharded) {
-  static const bool off = getenv("AOADMM_NO_PAR2_FOLD") != nullptr;           // development switch
-  return !off && !constrained && !sharded && d.R <= 8;
+  return !constrained && !sharded && d.R <= 8;
 }
 
 void par2_b_loop_folded(const P2BArgs& a0, const P2Dims& d, AdmmCtl* ctl, int max_inner, double tpc, double tpz, double tdc,

@@ -859,8 +859,7 @@ void Engine::em_pass_enqueue(int p, int update, bool fuse_next_pass) {
   int fused_c = -1;
   ContractPlan fpl;
   FactorRef facs[8];
-  static const bool no_fuse = getenv("AOADMM_NO_EM_FUSE") != nullptr;       // development switch (tools/time_em.py)
-  if (fuse_next_pass && update && b.nd == 3 && !no_fuse && em_cp_can_fuse(a, b.X.prec) && b.dims[1] <= 65535 &&
+  if (fuse_next_pass && update && b.nd == 3 && em_cp_can_fuse(a, b.X.prec) && b.dims[1] <= 65535 &&
       b.dims[2] <= 65535 && !small_direct(b, a.R)) {
     for (int i = 0; i < t.nmodes; ++i) facs[i] = factor_ref(modes_[t.modes[i]]);
     const std::vector<int> seq = update_sequence(p);
@@ -1042,7 +1041,7 @@ void Engine::timed_contract(const void* X, int prec, const ContractPlan& pl, con
                             void* frag, void* T) {
   KernelStats& ks = kstats_[pl.lead ? 1 : 0];
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  static const bool no_events = getenv("AOADMM_NO_PASS_EVENTS") != nullptr;   // development switch (tools/gap_analysis.py)
+  static const bool no_events = getenv("AOADMM_NO_PASS_EVENTS") != nullptr;   // measurement only (tools/gap_analysis.py)
   // Every 4th pass is bracketed by events (the three kinds of pass alternate with period 3, so the sample cycles through
   // them): the records cost ~4 us of launch gap on each side of a pass -- nothing at 2000^3, 1 % of an iteration at one
   // rank's share of 8 GPUs.  kernel_stats() returns the mean of the timed launches times the launch count.
@@ -1127,8 +1126,7 @@ static bool room_for(size_t bytes) {
 // Mode-3 sharding of the mode-1 pass's copy: every rank must reach the same verdict (the collectives that follow the
 // pass differ: own rows of mode 3 instead of partial sums).
 bool Engine::want_ksharded_xp(const CpBlock& b, int64_t K, int64_t* k0, int64_t* kloc) const {
-  static const bool off = getenv("AOADMM_NO_KSHARD") != nullptr;            // development switch
-  if (!sharded() || world_ <= 1 || !allow_xp_ || b.has_mask || b.nd != 3 || off) return false;
+  if (!sharded() || world_ <= 1 || !allow_xp_ || b.has_mask || b.nd != 3) return false;
   const int64_t per = cdiv(K, world_);
   if (per * (world_ - 1) >= K) return false;          // some rank would own no slab
   *k0 = per * rank_;
@@ -1234,10 +1232,8 @@ void Engine::ensure_contraction(CpBlock& b, int pos, const FactorRef* facs, int 
   int c = -1, best = -1;
   for (int cand = 2; cand >= 0; --cand) {
     if (cand == pos) continue;
-    static const bool force_lead = getenv("AOADMM_FORCE_LEAD") != nullptr;   // development switch (tools/perf_mttkrp.py)
     // contracting mode 1 needs the permuted copy (any precision) or the LDS-transposed kernel (fp32 only)
-    if (cand == 0 && !((use_cache || force_lead) && (prec == AOADMM_PREC_F32 || ensure_permuted_copy(b)))) continue;
-    if (cand != 0 && force_lead && prec == AOADMM_PREC_F32 && pos != 0) continue;
+    if (cand == 0 && !(use_cache && (prec == AOADMM_PREC_F32 || ensure_permuted_copy(b)))) continue;
     const int dist = next_update_distance(pos, cand, update_seq, nseq);
     if (dist > best) { best = dist; c = cand; }
   }
@@ -1265,8 +1261,7 @@ void Engine::ensure_contraction(CpBlock& b, int pos, const FactorRef* facs, int 
     }
   } else {
     Fc = facs[0].p + (sharded() ? b.row0 : 0);
-    static const bool force_ldskernel = getenv("AOADMM_LEAD_KERNEL") != nullptr;   // development switch
-    if (!force_ldskernel && ensure_permuted_copy(b)) {
+    if (ensure_permuted_copy(b)) {
       // Xp: rows (j, k), columns i -> the register-streaming contraction.  With a communicator the copy holds this
       // rank's slab of mode 3 and ALL of mode 1 (CpBlock::xp_ksharded): a complete T of 1/N the size
       if (b.xp_ksharded) { pl = blocked_plan(b.Jp * b.xp_kloc, b.full0); Fc = facs[0].p; }
@@ -1594,10 +1589,9 @@ void Engine::prepare_mode_system(int m, int nrho, const aoadmm_options& opt) {
   if (cty == 2) sb.Madd = mi.HHt.d();
   // The system needs the Gram matrices only: it rides in the launch of the reduction that finishes the MTTKRP (one
   // extra workgroup) when that path is taken, else it gets its own launch behind the MTTKRP.
-  static const bool no_rider = getenv("AOADMM_NO_SYS_RIDER") != nullptr;       // development switch
   bool rode = false;
   block_mttkrp(t.blk, mi.pos, facs, mi.R, t.weight, mi.A.d(), mi.rows, opt.use_dimtree != 0, seq.data(), (int)seq.size(), true,
-               false, no_rider ? nullptr : &sb, &rode);
+               false, &sb, &rode);
   if (!rode) sys_build(sb, stream_);
   if (cty == 1 || cty == 5) {                       // B = V diag(mu) V' for the Sylvester solve of the inner loop
     mi.eV.ensure((size_t)mi.R * mi.R * sizeof(double)); mi.eMu.ensure((size_t)mi.R * sizeof(double));
@@ -1615,8 +1609,6 @@ void Engine::prepare_mode_system(int m, int nrho, const aoadmm_options& opt) {
 
 // see the end of the outer loop in solve(): the first uncoupled CP mode of the next iteration, prepared ahead
 void Engine::prepare_next_first_mode(const aoadmm_options& opt) {
-  static const bool off = getenv("AOADMM_NO_PREPARE_AHEAD") != nullptr;      // development switch
-  if (off) return;
   for (int p = 0; p < n_tensors_; ++p)
     for (int m = 0; m < n_modes_; ++m) {
       const ModeInfo& mi = modes_[m];
@@ -2611,34 +2603,35 @@ void Engine::coupled_admm(int c, const aoadmm_options& opt) {
     const size_t nimg = (size_t)std::max(mi.rows * mi.R, mi.img_rows * mi.img_cols) * sizeof(double);
     mi.TD.ensure(nimg); mi.TF.ensure(nimg); mi.tmp.ensure(nimg); mi.W1.ensure(nimg); mi.W2.ensure(nimg);
   }
-  // the one-launch registers loop (couple_loop_wg_regs_k) opens the loop and forms rho_j / sum rho itself
-  bool regs_path = false;
-  {
-    static const bool off = getenv("AOADMM_GENERIC_COUPLING") != nullptr, no_wg = getenv("AOADMM_NO_WG_LOOP") != nullptr;
-    int rmax = (int)ci.cols;
-    bool local_prox = true, pc = false;
-    for (int j = 0; j < n; ++j) {
-      const ModeInfo& mi = modes_[ci.modes[j]];
-      rmax = std::max(rmax, mi.R);
-      local_prox = local_prox && (!mi.constrained || prox_is_fusable(mi.prox.type));
-      pc = pc || (tensors_[mi.tensor].par2 && mi.pos == 2);
-    }
-    regs_path = (ty == 0 || ty == 4) && !pc && !off && !no_wg && local_prox && n <= 3 && ci.rows <= 256 && rmax <= 8;
-  }
-  // reset the loop control (the per-mode sys_build calls reset their own blocks); types 0-2: in coupling_coefs_k below
-  if (!(ty == 0 || ty == 1 || ty == 2) && !regs_path) ctl_reset(ctl, stream_);
   // per-outer-iteration constants
   std::vector<const double*> hp(n);
-  bool any_pc = false;                                // a PARAFAC2 C mode in this coupling (types 0 and 1 only)
   auto pc_block = [&](const ModeInfo& mi) -> Par2Block* {
     return (tensors_[mi.tensor].par2 && mi.pos == 2) ? &tensors_[mi.tensor].p2 : nullptr;
   };
+  int rmax = (int)ci.cols;                            // largest rank, cols(Delta) included
+  bool any_pc = false;                                // a PARAFAC2 C mode in this coupling (types 0 and 1 only)
+  bool local_prox = true;                             // every constrained mode's prox runs inside the loop kernels
   for (int j = 0; j < n; ++j) {
     const ModeInfo& mj = modes_[ci.modes[j]];
     Par2Block* pb = pc_block(mj);
     hp[j] = pb ? pb->rhosum.d() : mj.rho.d();         // type 1 weighs a C mode with sum(rho) (:736)
     any_pc = any_pc || pb != nullptr;
+    rmax = std::max(rmax, mj.R);
+    local_prox = local_prox && (!mj.constrained || prox_is_fusable(mj.prox.type));
   }
+  // Which form runs the inner loop.  Row-local forms: types 0 and 4, ranks and cols(Delta) up to 16, no PARAFAC2 C
+  // mode.  Small problems among them whose proxes all run inside the kernels take the whole loop in one launch of one
+  // workgroup: one row per thread with the state in registers (couple_loop_wg_regs_k, which opens the loop and forms
+  // rho_j / sum rho itself) or the LDS form (couple_loop_wg_k).  The others launch row kernels per step; everything
+  // else takes the generic loop.
+  enum class Path { Regs, Wg, RowSteps, Generic };
+  Path path = Path::Generic;
+  if ((ty == 0 || ty == 4) && !any_pc && rmax <= 16) {
+    if (n <= 4 && ci.rows <= 2048 && local_prox) path = ci.rows <= 256 && rmax <= 8 && n <= 3 ? Path::Regs : Path::Wg;
+    else path = Path::RowSteps;
+  }
+  // reset the loop control (the per-mode sys_build calls reset their own blocks); types 0-2: in coupling_coefs_k below
+  if (!(ty == 0 || ty == 1 || ty == 2) && path != Path::Regs) ctl_reset(ctl, stream_);
   DevBuf& rho_ptrs = ci.rho_ptrs;                     // pointers never change once the work buffers exist
   if (ci.rho_ptrs_host != hp) {
     rho_ptrs.ensure(8 * sizeof(double*));
@@ -2648,7 +2641,7 @@ void Engine::coupled_admm(int c, const aoadmm_options& opt) {
   }
   const double* rho_last = modes_[ci.modes[n - 1]].rho.d();   // type 5: rhoC = mean(rho{mm}) with the stale loop variable (:1032)
   if (ty == 0 || ty == 1 || ty == 2) {
-    if (!regs_path) {
+    if (path != Path::Regs) {
       coupling_coefs_k<<<1, 64, 0, stream_>>>(ci.coef.d(), rho_ptrs.as<const double*>(), n, ctl);
       AO_KERNEL_CHECK();
     }
@@ -2671,116 +2664,102 @@ void Engine::coupled_admm(int c, const aoadmm_options& opt) {
     } else
     chol_only(ci.LAA.d(), ci.AA.d(), (int)ci.cols, ctl, stream_);
   }
-  // ---- row-local fast path (types 0 and 4, ranks and cols(Delta) up to 16, no PARAFAC2 C mode)
-  {
-    int rmax = (int)ci.cols;
-    for (int j = 0; j < n; ++j) rmax = std::max(rmax, modes_[ci.modes[j]].R);
-    static const bool off = getenv("AOADMM_GENERIC_COUPLING") != nullptr;      // development switch
-    if ((ty == 0 || ty == 4) && !any_pc && rmax <= 16 && !off) {
-      const int q = (int)ci.cols;
-      const int64_t rows = ci.rows;
-      const unsigned rb = (unsigned)cdiv(rows, 64);
-      int64_t nr = cdiv(rows, 2048);
-      if (nr > 64) nr = 64;
-      RowCouple rc[8];
-      RowDelta rd;
-      rd.n = n;
-      size_t lds_delta = (size_t)q * q;
-      for (int j = 0; j < n; ++j) {
-        ModeInfo& mi = modes_[ci.modes[j]];
-        rc[j].Aeff = mi.Aeff; rc[j].L = mi.L.d(); rc[j].rho = mi.rho.d(); rc[j].H = ty == 4 ? mi.H.d() : nullptr;
-        rc[j].fac = mi.fac.d(); rc[j].muD = mi.muD.d(); rc[j].Z = mi.Z.d(); rc[j].mu = mi.mu.d();
-        rc[j].R = mi.R; rc[j].constrained = mi.constrained ? 1 : 0;
-        rd.fac[j] = mi.fac.d(); rd.muD[j] = mi.muD.d(); rd.rho[j] = mi.rho.d(); rd.H[j] = rc[j].H; rd.R[j] = mi.R;
-        lds_delta += (size_t)q * mi.R;
-      }
-      auto by_rmax = [&](auto&& launch) {
-        if (rmax <= 4) launch(std::integral_constant<int, 4>());
-        else if (rmax <= 8) launch(std::integral_constant<int, 8>());
-        else launch(std::integral_constant<int, 16>());
-      };
-      // small problems: the whole loop in one launch of one workgroup (couple_loop_wg_k)
-      bool local_prox = true;
-      for (int j = 0; j < n; ++j) {
-        const ModeInfo& mi = modes_[ci.modes[j]];
-        local_prox = local_prox && (!mi.constrained || prox_is_fusable(mi.prox.type));
-      }
-      static const bool no_wg = getenv("AOADMM_NO_WG_LOOP") != nullptr;           // development switch
-      if (n <= 4 && rows <= 2048 && local_prox && !no_wg) {
-        WgLoopArgs wa;
-        wa.n = n; wa.q = q; wa.type = ty; wa.max_inner = opt.MaxInnerIters; wa.rows = rows;
-        wa.Delta = ci.Delta.d(); wa.DeltaOld = ci.DeltaOld.d(); wa.dD = ci.dD.d(); wa.coefs = ci.coef.d(); wa.LAA = ci.LAA.d();
-        wa.tol_pr_coupl = opt.innerRelPrTol_coupl; wa.tol_pr_constr = opt.innerRelPrTol_constr;
-        wa.tol_du_coupl = opt.innerRelDualTol_coupl; wa.tol_du_constr = opt.innerRelDualTol_constr;
-        wa.ctl = ctl;
-        size_t lds = (size_t)q * q;
-        for (int j = 0; j < n; ++j) {
-          ModeInfo& mi = modes_[ci.modes[j]];
-          WgLoopMode& wm = wa.m[j];
-          wm.Aeff = mi.Aeff; wm.L = mi.L.d(); wm.rho = mi.rho.d(); wm.H = ty == 4 ? mi.H.d() : nullptr;
-          wm.fac = mi.fac.d(); wm.muD = mi.muD.d(); wm.Z = mi.Z.d(); wm.mu = mi.mu.d(); wm.Zold = mi.Zold.d();
-          wm.slots = resid + (int64_t)ci.modes[j] * kResidPerMode;
-          wm.R = mi.R; wm.constrained = mi.constrained ? 1 : 0; wm.ptype = mi.prox.type; wm.p0 = mi.prox.p0; wm.p1 = mi.prox.p1;
-          lds += (size_t)mi.R * mi.R + (size_t)q * mi.R;
-        }
-        AO_REQUIRE(regs_path == (rows <= 256 && rmax <= 8 && n <= 3), "coupled loop: path prediction and launch disagree");
-        if (rows <= 256 && rmax <= 8 && n <= 3) {     // one row per thread: the state stays in registers
-          wa.self_start = 1;
+  const int q = (int)ci.cols;
+  const int64_t rows = ci.rows;
+  auto by_rmax = [&](auto&& launch) {
+    if (rmax <= 4) launch(std::integral_constant<int, 4>());
+    else if (rmax <= 8) launch(std::integral_constant<int, 8>());
+    else launch(std::integral_constant<int, 16>());
+  };
+  if (path == Path::Regs || path == Path::Wg) {
+    WgLoopArgs wa;
+    wa.n = n; wa.q = q; wa.type = ty; wa.max_inner = opt.MaxInnerIters; wa.rows = rows;
+    wa.Delta = ci.Delta.d(); wa.DeltaOld = ci.DeltaOld.d(); wa.dD = ci.dD.d(); wa.coefs = ci.coef.d(); wa.LAA = ci.LAA.d();
+    wa.tol_pr_coupl = opt.innerRelPrTol_coupl; wa.tol_pr_constr = opt.innerRelPrTol_constr;
+    wa.tol_du_coupl = opt.innerRelDualTol_coupl; wa.tol_du_constr = opt.innerRelDualTol_constr;
+    wa.ctl = ctl;
+    size_t lds = (size_t)q * q;
+    for (int j = 0; j < n; ++j) {
+      ModeInfo& mi = modes_[ci.modes[j]];
+      WgLoopMode& wm = wa.m[j];
+      wm.Aeff = mi.Aeff; wm.L = mi.L.d(); wm.rho = mi.rho.d(); wm.H = ty == 4 ? mi.H.d() : nullptr;
+      wm.fac = mi.fac.d(); wm.muD = mi.muD.d(); wm.Z = mi.Z.d(); wm.mu = mi.mu.d(); wm.Zold = mi.Zold.d();
+      wm.slots = resid + (int64_t)ci.modes[j] * kResidPerMode;
+      wm.R = mi.R; wm.constrained = mi.constrained ? 1 : 0; wm.ptype = mi.prox.type; wm.p0 = mi.prox.p0; wm.p1 = mi.prox.p1;
+      lds += (size_t)mi.R * mi.R + (size_t)q * mi.R;
+    }
+    if (path == Path::Regs) {
+      wa.self_start = 1;
 #define AO_WGR(RM, NMM) { if (ty == 4) couple_loop_wg_regs_k<RM, NMM, true><<<1, 256, 0, stream_>>>(wa); \
                           else couple_loop_wg_regs_k<RM, NMM, false><<<1, 256, 0, stream_>>>(wa); }
-          if (rmax <= 4) { if (n == 1) AO_WGR(4, 1) else if (n == 2) AO_WGR(4, 2) else AO_WGR(4, 3) }
-          else { if (n == 1) AO_WGR(8, 1) else if (n == 2) AO_WGR(8, 2) else AO_WGR(8, 3) }
+      if (rmax <= 4) { if (n == 1) AO_WGR(4, 1) else if (n == 2) AO_WGR(4, 2) else AO_WGR(4, 3) }
+      else { if (n == 1) AO_WGR(8, 1) else if (n == 2) AO_WGR(8, 2) else AO_WGR(8, 3) }
 #undef AO_WGR
-        } else {
-          by_rmax([&](auto tag) { couple_loop_wg_k<decltype(tag)::value><<<1, 256, lds * sizeof(double), stream_>>>(wa); });
-        }
-        AO_KERNEL_CHECK();
-        return;
-      }
-      for (int it = 0; it < opt.MaxInnerIters; ++it) {
-        for (int j = 0; j < n; ++j) {                 // primal: Sd(Delta), right-hand side and row solve in one kernel
-          const size_t lds = ((size_t)rc[j].R * rc[j].R + (size_t)q * rc[j].R) * sizeof(double);
-          by_rmax([&](auto tag) {
-            couple_primal_rows_k<decltype(tag)::value><<<rb, 64, lds, stream_>>>(rc[j], ci.Delta.d(), rows, q, ty, ctl);
-          });
-          AO_KERNEL_CHECK();
-        }
-        by_rmax([&](auto tag) {                       // Delta_old, Delta, dD
-          couple_delta_rows_k<decltype(tag)::value><<<rb, 64, lds_delta * sizeof(double), stream_>>>(
-              rd, ci.Delta.d(), ci.DeltaOld.d(), ci.dD.d(), ci.coef.d(), ci.LAA.d(), rows, q, ty, ctl);
+    } else {
+      by_rmax([&](auto tag) { couple_loop_wg_k<decltype(tag)::value><<<1, 256, lds * sizeof(double), stream_>>>(wa); });
+    }
+    AO_KERNEL_CHECK();
+    return;
+  }
+  if (path == Path::RowSteps) {
+    const unsigned rb = (unsigned)cdiv(rows, 64);
+    int64_t nr = cdiv(rows, 2048);
+    if (nr > 64) nr = 64;
+    RowCouple rc[8];
+    RowDelta rd;
+    rd.n = n;
+    size_t lds_delta = (size_t)q * q;
+    for (int j = 0; j < n; ++j) {
+      ModeInfo& mi = modes_[ci.modes[j]];
+      rc[j].Aeff = mi.Aeff; rc[j].L = mi.L.d(); rc[j].rho = mi.rho.d(); rc[j].H = ty == 4 ? mi.H.d() : nullptr;
+      rc[j].fac = mi.fac.d(); rc[j].muD = mi.muD.d(); rc[j].Z = mi.Z.d(); rc[j].mu = mi.mu.d();
+      rc[j].R = mi.R; rc[j].constrained = mi.constrained ? 1 : 0;
+      rd.fac[j] = mi.fac.d(); rd.muD[j] = mi.muD.d(); rd.rho[j] = mi.rho.d(); rd.H[j] = rc[j].H; rd.R[j] = mi.R;
+      lds_delta += (size_t)q * mi.R;
+    }
+    for (int it = 0; it < opt.MaxInnerIters; ++it) {
+      for (int j = 0; j < n; ++j) {                   // primal: Sd(Delta), right-hand side and row solve in one kernel
+        const size_t lds = ((size_t)rc[j].R * rc[j].R + (size_t)q * rc[j].R) * sizeof(double);
+        by_rmax([&](auto tag) {
+          couple_primal_rows_k<decltype(tag)::value><<<rb, 64, lds, stream_>>>(rc[j], ci.Delta.d(), rows, q, ty, ctl);
         });
         AO_KERNEL_CHECK();
-        FinalizeArgs fa;
-        fa.nmodes = n;
-        fa.max_inner = opt.MaxInnerIters;
-        fa.tol_pr_coupl = opt.innerRelPrTol_coupl; fa.tol_pr_constr = opt.innerRelPrTol_constr;
-        fa.tol_du_coupl = opt.innerRelDualTol_coupl; fa.tol_du_constr = opt.innerRelDualTol_constr;
-        for (int j = 0; j < n; ++j) {                 // duals, constraints, residual sums
-          const int m = ci.modes[j];
-          ModeInfo& mi = modes_[m];
-          double* sl = resid + (int64_t)m * kResidPerMode;
-          by_rmax([&](auto tag) {
-            couple_dual_rows_k<decltype(tag)::value><<<(unsigned)nr, 256, (size_t)q * mi.R * sizeof(double), stream_>>>(
-                rc[j], ci.Delta.d(), ci.dD.d(), rows, q, ty, sl + 4, redws_.d(), ctl);
-          });
-          AO_KERNEL_CHECK();
-          if (nr > 1) {
-            couple_dual_fin_k<<<1, 64, 0, stream_>>>(sl + 4, redws_.d(), (int)nr, ctl);
-            AO_KERNEL_CHECK();
-          }
-          if (mi.constrained)
-            constraint_update(mi.prox, mi.fac.d(), mi.Z.d(), mi.mu.d(), mi.Zold.d(), mi.V.d(), mi.rows, mi.R, mi.rho.d(), 1.0,
-                              mi.proxws.d(), sl, redws_.d(), ctl, stream_);
-          else
-            sumsq_diff(sl + 1, mi.fac.d(), nullptr, mi.rows * mi.R, redws_.d(), ctl, stream_);
-          fa.slots[j] = sl;
-          fa.constrained[j] = mi.constrained ? 1 : 0;
-          fa.coupled[j] = 1;
-        }
-        admm_finalize_generic(fa, ctl, stream_);
       }
-      return;
+      by_rmax([&](auto tag) {                         // Delta_old, Delta, dD
+        couple_delta_rows_k<decltype(tag)::value><<<rb, 64, lds_delta * sizeof(double), stream_>>>(
+            rd, ci.Delta.d(), ci.DeltaOld.d(), ci.dD.d(), ci.coef.d(), ci.LAA.d(), rows, q, ty, ctl);
+      });
+      AO_KERNEL_CHECK();
+      FinalizeArgs fa;
+      fa.nmodes = n;
+      fa.max_inner = opt.MaxInnerIters;
+      fa.tol_pr_coupl = opt.innerRelPrTol_coupl; fa.tol_pr_constr = opt.innerRelPrTol_constr;
+      fa.tol_du_coupl = opt.innerRelDualTol_coupl; fa.tol_du_constr = opt.innerRelDualTol_constr;
+      for (int j = 0; j < n; ++j) {                   // duals, constraints, residual sums
+        const int m = ci.modes[j];
+        ModeInfo& mi = modes_[m];
+        double* sl = resid + (int64_t)m * kResidPerMode;
+        by_rmax([&](auto tag) {
+          couple_dual_rows_k<decltype(tag)::value><<<(unsigned)nr, 256, (size_t)q * mi.R * sizeof(double), stream_>>>(
+              rc[j], ci.Delta.d(), ci.dD.d(), rows, q, ty, sl + 4, redws_.d(), ctl);
+        });
+        AO_KERNEL_CHECK();
+        if (nr > 1) {
+          couple_dual_fin_k<<<1, 64, 0, stream_>>>(sl + 4, redws_.d(), (int)nr, ctl);
+          AO_KERNEL_CHECK();
+        }
+        if (mi.constrained)
+          constraint_update(mi.prox, mi.fac.d(), mi.Z.d(), mi.mu.d(), mi.Zold.d(), mi.V.d(), mi.rows, mi.R, mi.rho.d(), 1.0,
+                            mi.proxws.d(), sl, redws_.d(), ctl, stream_);
+        else
+          sumsq_diff(sl + 1, mi.fac.d(), nullptr, mi.rows * mi.R, redws_.d(), ctl, stream_);
+        fa.slots[j] = sl;
+        fa.constrained[j] = mi.constrained ? 1 : 0;
+        fa.coupled[j] = 1;
+      }
+      admm_finalize_generic(fa, ctl, stream_);
     }
+    return;
   }
   for (int it = 0; it < opt.MaxInnerIters; ++it) {
     // ---- primal updates (:635-658, :713-730, :783-800, :853-870, :913-936, :1004-1020)

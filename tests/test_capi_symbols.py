@@ -77,6 +77,21 @@ def test_host_layer_rejects_what_the_device_path_does_not_cover(pkg):
     assert pkg.row_block(2000, 8, 7) == (1750, 250) and pkg.row_block(10, 4, 3) == (9, 1)
 
 
+def test_library_reads_only_the_kept_environment_names():
+    """The library picks its kernels from the inputs.  The environment names it reads are test hooks the suite sets
+    and two measurement switches that change no result and no kernel."""
+    csrc = os.path.join(ROOT, 'matlab-code_amd', 'csrc')
+    names = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(('.hip', '.h')):
+            src = open(os.path.join(csrc, f)).read()
+            found = re.findall(r'getenv\s*\(\s*"(\w+)"\s*\)', src)
+            assert len(found) == len(re.findall(r'getenv\s*\(', src)), f     # every read names its variable literally
+            names.update(found)
+    assert names == {'AOADMM_NO_SMALL_MTTKRP', 'AOADMM_EM_FUSE_SECOND_MODE', 'AOADMM_FAULT_INJECT', 'AOADMM_RELEASE_NATURAL',
+                     'AOADMM_NO_PASS_EVENTS', 'AOADMM_PASS_EVENT_EVERY'}
+
+
 def test_header_is_plain_c_and_the_c_example_links(tmp_path):
     """The boundary is a C ABI: include/aoadmm_hip.h must compile as C99 (no C++ leaks) and a plain-C caller
     (examples/solve_cp.c, the call sequence of a MEX gateway) must link against the library.  Compute needs a GPU."""

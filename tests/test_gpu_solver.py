@@ -264,14 +264,23 @@ def test_early_stop_matches(pkg, eng):
         assert rel_fro(b, a) < 1e-6
 
 
-def test_fp32_tensor_mode(pkg, eng):
+@pytest.mark.parametrize('no_permuted_copy', [0, 1], ids=['default', 'no_permuted_copy'])
+def test_fp32_tensor_mode(pkg, eng, no_permuted_copy):
     """Throughput mode (fp32 tensor, f32 MFMA, fp64 elsewhere): stated tolerance 1e-4 on the factors
-    after 10 outer iterations (input rounding 6e-8 amplified by the iteration)."""
+    after 10 outer iterations (input rounding 6e-8 amplified by the iteration).  options.hip.no_permuted_copy=1 keeps
+    no permuted copies, so the tensor passes that contract the leading mode run contract_lead16_f32: the same tolerance
+    against the oracle and against the default run."""
     rng = np.random.default_rng(8)
     Z, io, _ = cp_model((40, 50, 60), 3, rng, [('non-negativity',)] * 3)
-    Fo, oo, Fg, og = run_both(pkg, eng, Z, io, options(MaxOuterIters=10), precision='f32')
-    for a, b in zip(Fo['fac'], Fg['fac']):
-        assert rel_fro(b, a) < 1e-4
+    G = OA.init_coupled_AOADMM_CMTF({**Z, 'prox_operators': None}, io, rng=np.random.default_rng(7))
+    _, Fo, _, _ = OA.cmtf_AOADMM(Z, alg_options=options(MaxOuterIters=10), init=copy.deepcopy(G))
+    Fg = []
+    for flag in sorted({0, no_permuted_copy}):                # the default run first
+        opt = options(MaxOuterIters=10, hip=dict(no_permuted_copy=flag))
+        Fg.append(pkg.cmtf_AOADMM(Z, alg_options=opt, init=copy.deepcopy(G), engine=eng, precision='f32')[1])
+    for F in Fg:
+        for a, b, c in zip(Fo['fac'], Fg[0]['fac'], F['fac']):
+            assert rel_fro(c, a) < 1e-4 and rel_fro(c, b) < 1e-4
 
 
 def compare_par2(Fo, oo, Fg, og, tol=TOL):

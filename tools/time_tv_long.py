@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Development timing of the TV and GL-smoothness prox on columns beyond the LDS-resident 4096 rows (run under rocprofv3 --kernel-trace
---stats; with AOADMM_TV_SEQ_LONG=1 the one-thread scan it replaced)."""
+--stats)."""
 import importlib, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
