@@ -233,6 +233,16 @@ int aoadmm_tensor_synth(aoadmm_ctx* ctx, int p, int rank, uint64_t seed, double 
  * aoadmm_tensor_normsq, aoadmm_resident_mttkrp and aoadmm_solve work as for dense data.  With a communicator
  * every rank holds all nonzeros and computes the complete MTTKRP (no collective for the block). */
 int aoadmm_tensor_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* vals);
+/* Z.object{p}{k} of a PARAFAC2 block as sparse matrices, all K slabs in one call: nnz nonzeros, subs column-major
+ * nnz x 3, 0-based (i, j within the slab, k); vals nnz doubles.  Duplicates are summed, explicit zeros are allowed,
+ * nnz = 0 is valid; a subscript out of range (j >= J_k included) or nnz < 0 is AOADMM_ERR_INVALID and leaves the block
+ * as it was.  Values stay fp64.  No array of size I x sum(J_k) or K x I x R exists for such a block.  A later
+ * aoadmm_par2_slab_upload(..., AOADMM_ALL_SLABS, ...) replaces the sparse form and this call replaces a dense one.
+ * On a block with sparse slabs aoadmm_par2_slab_mask_upload and a single-slab aoadmm_par2_slab_upload return
+ * AOADMM_ERR_INVALID and aoadmm_resident_unfold_gram AOADMM_ERR_UNSUPPORTED; aoadmm_tensor_normsq and aoadmm_solve
+ * work as for dense slabs.  With a communicator every rank holds all nonzeros, the block issues no collective and
+ * aoadmm_options.par2_slab_sharding is ignored for it. */
+int aoadmm_par2_slab_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* vals);
 /* Znorm_const{p} (cmtf_AOADMM.m:130-156) */
 int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out);
 
@@ -250,13 +260,18 @@ int aoadmm_solve(aoadmm_ctx* ctx, const aoadmm_options* opt, aoadmm_result* out)
  * result stays on the device; elapsed device time of the kernels is returned */
 int aoadmm_resident_mttkrp(aoadmm_ctx* ctx, int p, int tensor_mode, double* out_host_or_null,
                            float* elapsed_ms);
+/* PARAFAC2 block with sparse slabs: the UNWEIGHTED right-hand side of tensor mode 0 (I x R: sum_k X_k B_k D_k),
+ * 1 (sum(J_k) x R, the slabs back to back as in the state fields: X_k' A D_k) or 2 (K x R: diag(A' X_k B_k)) against
+ * the current factors, column-major; every call runs its pass over the nonzeros (operator tests, timing). */
+int aoadmm_resident_par2_rhs(aoadmm_ctx* ctx, int p, int tensor_mode, double* out_host_or_null, float* elapsed_ms);
 /* device time (ms, HIP events on the library's stream around the kernel only), launch count, algorithmic
  * bytes and flops of a tensor-pass kernel since the last reset.  which = 0: register-streaming contraction
  * (contract_f32/f64, trailing modes); which = 1: LDS-transposed leading-mode contraction (contract_lead_f32);
  * which = 2: the reductions over the partial contraction T that finish an MTTKRP (bytes = size of T per reduction;
  * timed only from the first call with which = 2 on, two more events per reduction); which = 3: the MTTKRPs of
  * sparse blocks (launches = MTTKRPs, each the streaming kernel plus its carry passes; bytes = nonzeros streamed +
- * factor rows gathered + output written; flops = nnz * R * N) */
+ * factor rows gathered + output written; flops = nnz * R * N) and the passes over the nonzeros of PARAFAC2 blocks
+ * with sparse slabs (one launch per pass, counted as the MTTKRP of the I x sum(J_k) matrix it is) */
 int aoadmm_kernel_stats(aoadmm_ctx* ctx, int which, int reset, double* contract_ms, int64_t* contract_launches,
                         double* contract_bytes, double* contract_flops);
 

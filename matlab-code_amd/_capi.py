@@ -28,8 +28,8 @@ SYMBOLS = [
     'aoadmm_model_begin', 'aoadmm_model_set_mode', 'aoadmm_model_set_mode_slabs', 'aoadmm_model_add_cp',
     'aoadmm_model_add_par2', 'aoadmm_model_set_constraint', 'aoadmm_model_set_coupling',
     'aoadmm_model_set_coupling_type', 'aoadmm_model_set_ridge', 'aoadmm_model_end', 'aoadmm_tensor_upload',
-    'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_par2_slab_upload', 'aoadmm_tensor_mask_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq',
-    'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_kernel_stats',
+    'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq',
+    'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_resident_par2_rhs', 'aoadmm_kernel_stats',
     'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
 ]
 
@@ -116,6 +116,7 @@ def load_library():
     lib.aoadmm_tensor_upload_rows.argtypes = [vp, C.c_int, dp, i64, i64, C.c_int]
     lib.aoadmm_tensor_upload_coo.argtypes = [vp, C.c_int, i64, C.POINTER(i64), dp]
     lib.aoadmm_par2_slab_upload.argtypes = [vp, C.c_int, C.c_int, dp]
+    lib.aoadmm_par2_slab_upload_coo.argtypes = [vp, C.c_int, i64, C.POINTER(i64), dp]
     lib.aoadmm_tensor_mask_upload.argtypes = [vp, C.c_int, C.POINTER(C.c_uint8)]
     lib.aoadmm_par2_slab_mask_upload.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
     lib.aoadmm_tensor_synth.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.c_double, C.c_int]
@@ -124,6 +125,7 @@ def load_library():
     lib.aoadmm_state_get.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, i64, i64]
     lib.aoadmm_solve.argtypes = [vp, C.POINTER(Options), C.POINTER(Result)]
     lib.aoadmm_resident_mttkrp.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_float)]
+    lib.aoadmm_resident_par2_rhs.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_float)]
     lib.aoadmm_kernel_stats.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(i64), dp, dp]
     lib.aoadmm_op_mttkrp.argtypes = [vp, dp, C.c_int, C.POINTER(i64), C.POINTER(dp), C.c_int, C.c_int, C.c_int, dp]
     lib.aoadmm_op_unfold_gram.argtypes = [vp, dp, C.c_int, C.POINTER(i64), C.c_int, C.c_int, dp]

@@ -417,6 +417,14 @@ int aoadmm_tensor_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t*
     on_engines(ctx, [&](Engine& e, int) { e.tensor_upload_coo(p, nnz, subs, vals); });   // replicated on every engine
   });
 }
+int aoadmm_par2_slab_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* vals) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    AO_REQUIRE(nnz >= 0, "nnz = %lld < 0", (long long)nnz);
+    AO_REQUIRE(nnz == 0 || (subs != nullptr && vals != nullptr), "null subs / vals");
+    on_engines(ctx, [&](Engine& e, int) { e.par2_slab_upload_coo(p, nnz, subs, vals); });   // replicated on every engine
+  });
+}
 int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out) {
   CTX_OR_FAIL(ctx);
   return guarded([&] {
@@ -456,6 +464,12 @@ int aoadmm_resident_mttkrp(aoadmm_ctx* ctx, int p, int tensor_mode, double* out_
   CTX_OR_FAIL(ctx);
   return guarded([&] {
     on_engines(ctx, [&](Engine& e, int r) { e.resident_mttkrp(p, tensor_mode, r == 0 ? out_host_or_null : nullptr, r == 0 ? elapsed_ms : nullptr); });
+  });
+}
+int aoadmm_resident_par2_rhs(aoadmm_ctx* ctx, int p, int tensor_mode, double* out_host_or_null, float* elapsed_ms) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    on_engines(ctx, [&](Engine& e, int r) { e.resident_par2_rhs(p, tensor_mode, r == 0 ? out_host_or_null : nullptr, r == 0 ? elapsed_ms : nullptr); });
   });
 }
 int aoadmm_kernel_stats(aoadmm_ctx* ctx, int which, int reset, double* contract_ms, int64_t* contract_launches,

@@ -75,6 +75,13 @@ void par2_b_finalize(const double* norms, const P2Dims& d, int use_constr, AdmmC
 void par2_c_system(const double* A, const double* T1, const double* GA, const double* GB, double w, double ridge,
                    double bsum_half, int nrho, int raw, const P2Dims& d, const double* Cfac, double* a, double* rho,
                    double* L, AdmmCtl* ctl, hipStream_t s, const double* Madd = nullptr);
+// Sparse slabs (par2_sparse.h): the data never enters these kernels.
+// Csys alone -- the half of par2_modeA_combine that needs no data (:164)
+void par2_modeA_csys(const double* Cfac, const double* GB, const P2Dims& d, double* Csys, hipStream_t s);
+// par2_c_system with the data term given: a(k,r) = w * sv(k,r) + bsum_half * C(k,r), sv(k,r) = (A' X_k B_k)(r,r) (K x R)
+void par2_c_system_pre(const double* sv, const double* GA, const double* GB, double w, double ridge, double bsum_half,
+                       int nrho, int raw, const P2Dims& d, const double* Cfac, double* a, double* rho, double* L,
+                       AdmmCtl* ctl, hipStream_t s, const double* Madd = nullptr);
 // rhomax = max_k rho_k (:1424); separate because a slab-sharded block gathers rho first
 void par2_rho_max(const double* rho, int K, double* rhomax, hipStream_t s, double* rhomean = nullptr,
                   double* rhosum = nullptr);

@@ -110,6 +110,15 @@ void par2_modeA_combine(const double* T1, const double* Cfac, const double* GB, 
   par2_modeA_combine_k<<<nb, kKsumThreads, 0, s>>>(T1, Cfac, GB, d, Amt, Csys, ew);
   AO_KERNEL_CHECK();
 }
+// the same kernel over an A part of no rows: every tile is a Csys tile, T1 and Amt are never touched
+void par2_modeA_csys(const double* Cfac, const double* GB, const P2Dims& d, double* Csys, hipStream_t s) {
+  P2Dims d0 = d;
+  d0.I = 0;
+  const int64_t nC = (int64_t)d.R * d.R;
+  const int ew = ksum_tile_width(nC);
+  par2_modeA_combine_k<<<(unsigned)cdiv(nC, ew), kKsumThreads, 0, s>>>(nullptr, Cfac, GB, d0, nullptr, Csys, ew);
+  AO_KERNEL_CHECK();
+}
 
 __global__ void par2_xta_k(const double* X, const double* A, const double* Cfac, double w, P2Dims d, double* Ak) {
   const int k = d.k0 + blockIdx.x;
@@ -1039,6 +1048,8 @@ void par2_b_finalize(const double* norms, const P2Dims& d, int use_constr, AdmmC
 // ---------------------------------------------------------------------------
 // C mode
 // ---------------------------------------------------------------------------
+// PRE: T1 is the K x R array sv(k,r) = sum_i A(i,r) (X_k B_k)(i,r) already reduced (sparse slabs), A is not read
+template <bool PRE>
 __global__ void par2_c_system_k(const double* A, const double* T1, const double* GA, const double* GB, double w,
                                 double ridge, double bsum_half, int nrho, int raw, const double* Madd, P2Dims d,
                                 const double* Cfac, double* a, double* rho, double* L, AdmmCtl* ctl) {
@@ -1047,7 +1058,9 @@ __global__ void par2_c_system_k(const double* A, const double* T1, const double*
   const int k = d.k0 + blockIdx.x, R = d.R, I = d.I;
   for (int r = threadIdx.x; r < R; r += blockDim.x) {
     double acc = 0.0;
-    for (int i = 0; i < I; ++i) acc += A[i + I * r] * T1[(int64_t)k * I * R + i + I * r];
+    if (PRE) acc = T1[k + d.K * r];
+    else
+      for (int i = 0; i < I; ++i) acc += A[i + I * r] * T1[(int64_t)k * I * R + i + I * r];
     a[k + d.K * r] = w * acc + bsum_half * Cfac[k + d.K * r];          // w*diag(A' X_k B_k) (:221), bsum (:231)
   }
   for (int e = threadIdx.x; e < R * R; e += blockDim.x) sh[e] = GA[e] * GB[(int64_t)k * R * R + e];   // :222
@@ -1088,8 +1101,15 @@ __global__ __launch_bounds__(64) void par2_max_k(const double* x, int n, double*
 void par2_c_system(const double* A, const double* T1, const double* GA, const double* GB, double w, double ridge,
                    double bsum_half, int nrho, int raw, const P2Dims& d, const double* Cfac, double* a, double* rho,
                    double* L, AdmmCtl* ctl, hipStream_t s, const double* Madd) {
-  par2_c_system_k<<<d.k1 - d.k0, kP2Threads, (size_t)d.R * d.R * sizeof(double), s>>>(A, T1, GA, GB, w, ridge, bsum_half,
-                                                                            nrho, raw, Madd, d, Cfac, a, rho, L, ctl);
+  par2_c_system_k<false><<<d.k1 - d.k0, kP2Threads, (size_t)d.R * d.R * sizeof(double), s>>>(
+      A, T1, GA, GB, w, ridge, bsum_half, nrho, raw, Madd, d, Cfac, a, rho, L, ctl);
+  AO_KERNEL_CHECK();
+}
+void par2_c_system_pre(const double* sv, const double* GA, const double* GB, double w, double ridge, double bsum_half,
+                       int nrho, int raw, const P2Dims& d, const double* Cfac, double* a, double* rho, double* L,
+                       AdmmCtl* ctl, hipStream_t s, const double* Madd) {
+  par2_c_system_k<true><<<d.k1 - d.k0, kP2Threads, (size_t)d.R * d.R * sizeof(double), s>>>(
+      nullptr, sv, GA, GB, w, ridge, bsum_half, nrho, raw, Madd, d, Cfac, a, rho, L, ctl);
   AO_KERNEL_CHECK();
 }
 void par2_rho_max(const double* rho, int K, double* rhomax, hipStream_t s, double* rhomean, double* rhosum) {

@@ -13,6 +13,7 @@
 #include "contract.h"
 #include "misc.h"
 #include "par2.h"
+#include "par2_sparse.h"
 #include "small.h"
 #include "sparse.h"
 
@@ -120,6 +121,10 @@ struct Par2Block {
   DevBuf mask;                    // Z.miss{p}{k}: one byte per entry, same layout, 1 = observed
   bool has_mask = false;
   std::vector<char> have_slab;
+  // sparse slabs (aoadmm_par2_slab_upload_coo): X, mask and T1 do not exist; every rank of a communicator holds all
+  // nonzeros, the block is never slab-sharded and issues no collective
+  bool sparse = false;
+  Par2Sparse sp;
   DevBuf DeltaB, DeltaBold, P, Pold, muDB;        // state (G.DeltaB, G.P, G.mu_DeltaB)
   bool has_DeltaB = false;
   std::vector<char> have_P, have_mu;
@@ -200,6 +205,7 @@ class Engine {
   void tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const double* vals);
   void tensor_synth(int p, int rank, uint64_t seed, double noise, int prec);
   void par2_slab_upload(int p, int k, const double* Xk);
+  void par2_slab_upload_coo(int p, int64_t nnz, const int64_t* subs, const double* vals);
   void tensor_mask_upload(int p, const uint8_t* mask);
   void par2_slab_mask_upload(int p, int k, const uint8_t* mask);
   double tensor_normsq(int p);
@@ -212,6 +218,7 @@ class Engine {
   void solve(const aoadmm_options& opt, aoadmm_result* out);
   void resident_mttkrp(int p, int pos, double* out_host, float* ms);
   void resident_unfold_gram(int p, int pos, int slab, double* out_host);
+  void resident_par2_rhs(int p, int pos, double* out_host, float* ms);
   void kernel_stats(int which, int reset, double* ms, int64_t* launches, double* bytes, double* flops);
 
   // communicator
@@ -285,6 +292,10 @@ class Engine {
   void par2_update_C(int m, const aoadmm_options& opt);
   void par2_prepare_C_coupled(int m, int ctype, const aoadmm_options& opt);
   void par2_objective_enqueue(TensorInfo& t);
+  // sparse slabs: one pass over the nonzeros (pos 0: the row-sorted copy, 1: the column-sorted copy), counted in kstats_[3]
+  void par2s_pass(Par2Block& b, int pos, const CooFactor& f, double* out, int64_t ldOut);
+  void par2s_rhs_A(TensorInfo& t, double* out);     // out (I x R) = sum_nnz x * B(g,:) .* C(k(g),:)
+  void par2s_ensure_Y(TensorInfo& t);               // Y = Xcat' * A for the current A (cached by its version)
   double* resid_slots(int m);
   std::vector<int> update_sequence(int p) const;
 
@@ -311,7 +322,7 @@ class Engine {
   std::vector<hipEvent_t> event_pool_;   // timing events are recycled: creating two per tensor pass cost host time in the loop
   hipEvent_t take_event();
   void fold_finished(KernelStats& ks);
-  KernelStats kstats_[4];   // [0] streaming contraction, [1] leading-mode contraction, [2] reductions over T, [3] sparse MTTKRP
+  KernelStats kstats_[4];   // [0] streaming contraction, [1] leading-mode contraction, [2] reductions over T, [3] sparse MTTKRP and the passes over sparse PARAFAC2 slabs
   int prepared_mode_ = -1;  // mode whose MTTKRP + system build were enqueued ahead (prepare_next_first_mode)
   bool profile_ = true;
   bool profile_reductions_ = false;   // switched on by the first kernel_stats(2, ...) call: two more events per reduction

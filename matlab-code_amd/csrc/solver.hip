@@ -622,7 +622,7 @@ void Engine::tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const do
   AO_REQUIRE(model_done_, "call aoadmm_model_end first");
   AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
   TensorInfo& t = tensors_[p];
-  AO_REQUIRE(!t.par2, "tensor %d is PARAFAC2: sparse slabs are not supported", p);
+  AO_REQUIRE(!t.par2, "tensor %d is PARAFAC2: sparse slabs go through aoadmm_par2_slab_upload_coo", p);
   AO_REQUIRE(t.nmodes >= 2 && t.nmodes <= kCooMaxModes, "tensor %d: order %d unsupported for sparse data", p, t.nmodes);
   int64_t dims[8];
   for (int i = 0; i < t.nmodes; ++i) dims[i] = modes_[t.modes[i]].rows;
@@ -673,7 +673,9 @@ double Engine::tensor_normsq(int p) {
       t.normsq_valid = true;
       return t.normsq;
     }
-    if (t.par2) {   // sum_k ||X_k||_F^2  (cmtf_AOADMM.m:145-155)
+    if (t.par2 && t.p2.sparse) {   // the coalesced values of all slabs; every rank holds all of them
+      tensor_sumsq(slot, t.p2.sp.coo.mode[0].val.p, AOADMM_PREC_F64, t.p2.sp.coo.nnz, ws.d(), stream_);
+    } else if (t.par2) {   // sum_k ||X_k||_F^2  (cmtf_AOADMM.m:145-155)
       tensor_sumsq(slot, t.p2.X.p, AOADMM_PREC_F64, (int64_t)t.p2.I * t.p2.Jtot, ws.d(), stream_);
     } else if (t.blk.sparse) {     // norm(sptensor)^2 (:132): the coalesced values; every rank holds all of them
       tensor_sumsq(slot, t.blk.coo.mode[0].val.p, AOADMM_PREC_F64, t.blk.coo.nnz, ws.d(), stream_);
@@ -3098,7 +3100,7 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
     {
       // slabs over the ranks or every slab on every rank (aoadmm_options.par2_slab_sharding)
       const ModeInfo& mB = modes_[t.modes[1]];
-      const bool can = sharded() && world_ > 1 && !b.has_mask && !(mB.constrained && mB.prox.type == AOADMM_C_TPARAFAC2) &&
+      const bool can = sharded() && world_ > 1 && !b.has_mask && !b.sparse && !(mB.constrained && mB.prox.type == AOADMM_C_TPARAFAC2) &&
                        modes_[t.modes[2]].coupling < 0;     // a coupled C mode needs every row system on every rank
       const bool want = opt.par2_slab_sharding > 0 || (opt.par2_slab_sharding == 0 && b.K / world_ >= 1024);
       const int per = (int)cdiv(b.K, world_);
@@ -3373,6 +3375,8 @@ void Engine::resident_unfold_gram(int p, int pos, int slab, double* out_host) {
     const Par2Block& b = t.p2;
     AO_REQUIRE(pos == 0 || pos == 1, "PARAFAC2 block: mode 1 (all slabs) or mode 2 (one slab)");
     for (int k = 0; k < b.K; ++k) AO_REQUIRE(b.have_slab[k], "slab %d of tensor %d has no data", k, p);
+    if (b.sparse)
+      throw Error(AOADMM_ERR_UNSUPPORTED, fmt("resident unfold_gram: tensor %d holds sparse slabs (their Gram matrices are built on the host)", p));
     if (pos == 0) { a.X = b.X.p; a.n = b.I; a.sa = 1; a.n1 = b.Jtot; a.s1 = b.I; a.n2 = 1; a.s2 = 0; }
     else {
       AO_REQUIRE(slab >= 0 && slab < b.K, "slab %d out of range", slab);

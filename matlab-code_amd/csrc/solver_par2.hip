@@ -46,7 +46,7 @@ void Engine::add_par2(int p, const int* modes3, double weight) {
   b.off_d.alloc((size_t)(b.K + 1) * sizeof(int64_t));
   AO_HIP(hipMemcpyAsync(b.off_d.p, b.off_h.data(), (size_t)(b.K + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
   AO_HIP(hipStreamSynchronize(stream_));
-  b.X.alloc((size_t)b.I * b.Jtot * sizeof(double));
+  // b.X (I x sum J_k doubles) is allocated by the first dense upload: a block with sparse slabs never has one
   b.have_slab.assign(b.K, 0);
   b.have_P.assign(b.K, 0);
   b.have_mu.assign(b.K, 0);
@@ -60,6 +60,12 @@ void Engine::par2_slab_upload(int p, int k, const double* Xk) {
   Par2Block& b = tensors_[p].p2;
   AO_REQUIRE(k == AOADMM_ALL_SLABS || (k >= 0 && k < b.K), "slab %d out of range", k);
   const bool all = k == AOADMM_ALL_SLABS;                  // I x sum(J_k): the slabs back to back
+  AO_REQUIRE(all || !b.sparse, "tensor %d holds sparse slabs: one dense slab cannot replace part of them (upload all slabs)", p);
+  b.X.ensure((size_t)b.I * b.Jtot * sizeof(double));
+  if (b.sparse) {                                          // a dense upload of every slab replaces the sparse form
+    b.sp.clear();
+    b.sparse = false;
+  }
   const int64_t o = all ? 0 : b.off_h[k];
   const int64_t Jk = all ? b.Jtot : b.off_h[k + 1] - b.off_h[k];
   AO_HIP(hipMemcpyAsync(b.X.d() + (int64_t)b.I * o, Xk, (size_t)b.I * Jk * sizeof(double), hipMemcpyHostToDevice, stream_));
@@ -75,6 +81,7 @@ void Engine::par2_slab_mask_upload(int p, int k, const uint8_t* mask) {
   AO_REQUIRE(mask != nullptr, "null mask");
   AO_HIP(hipSetDevice(device_));
   Par2Block& b = tensors_[p].p2;
+  AO_REQUIRE(!b.sparse, "Missing data (Z.miss) not supported for sparse PARAFAC2 slabs. Convert to full slabs first. (Z.object{%d})", p + 1);
   AO_REQUIRE(k == AOADMM_ALL_SLABS || (k >= 0 && k < b.K), "slab %d out of range", k);
   if (!b.has_mask) {
     b.mask.alloc((size_t)b.I * b.Jtot);
@@ -88,12 +95,129 @@ void Engine::par2_slab_mask_upload(int p, int k, const uint8_t* mask) {
   tensors_[p].normsq_valid = false;
 }
 
+// Z.object{p}{k} as sparse matrices (par2_sparse.h): all slabs in one call; drops the dense slabs and their mask.
+void Engine::par2_slab_upload_coo(int p, int64_t nnz, const int64_t* subs, const double* vals) {
+  require_usable();
+  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
+  AO_REQUIRE(p >= 0 && p < n_tensors_ && tensors_[p].par2, "tensor %d is not a PARAFAC2 block", p);
+  AO_HIP(hipSetDevice(device_));
+  Par2Block& b = tensors_[p].p2;
+  Par2Sparse sp;
+  par2s_build(sp, b.dims_all(), nnz, subs, vals, stream_);        // validates before anything of the old form is dropped
+  b.X.release(); b.mask.release(); b.T1.release();
+  b.has_mask = false;
+  b.sp = std::move(sp);
+  b.sparse = true;
+  b.have_slab.assign(b.K, 1);
+  tensors_[p].blk.has_data = true;
+  tensors_[p].normsq_valid = false;
+}
+
+void Engine::par2s_pass(Par2Block& b, int pos, const CooFactor& f, double* out, int64_t ldOut) {
+  KernelStats& ks = kstats_[3];
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (profile_) {
+    if (ks.pending.size() >= 512) fold_finished(ks);
+    if (ks.pending.size() < 4096) {
+      e0 = take_event();
+      e1 = take_event();
+      AO_HIP(hipEventRecord(e0, stream_));
+    }
+  }
+  coo_mttkrp(b.sp.coo, pos, &f, b.R, 1.0, out, ldOut, stream_);
+  if (e0) {
+    AO_HIP(hipEventRecord(e1, stream_));
+    ks.pending.emplace_back(e0, e1);
+    ks.timed++;
+  }
+  ks.launches++;
+  ks.bytes += coo_mttkrp_bytes(b.sp.coo, pos, b.R);
+  ks.flops += coo_mttkrp_flops(b.sp.coo, b.R);
+}
+
+void Engine::par2s_rhs_A(TensorInfo& t, double* out) {
+  Par2Block& b = t.p2;
+  const P2Dims d = b.dims_all();
+  b.sp.BC.ensure((size_t)b.Jtot * b.R * sizeof(double));
+  par2s_scale_b(modes_[t.modes[1]].fac.d(), modes_[t.modes[2]].fac.d(), d, b.sp.kofg.as<int>(), b.sp.BC.d(), stream_);
+  par2s_pass(b, 0, CooFactor{b.sp.BC.d(), (int64_t)b.R, 1}, out, b.I);
+}
+
+void Engine::par2s_ensure_Y(TensorInfo& t) {
+  Par2Block& b = t.p2;
+  const ModeInfo& mA = modes_[t.modes[0]];
+  if (b.sp.y_valid && b.sp.y_version == mA.version) return;
+  b.sp.Y.ensure((size_t)b.Jtot * b.R * sizeof(double));
+  b.sp.s.ensure((size_t)b.K * b.R * sizeof(double));
+  const CooFactor f = mA.facT_version == mA.version ? CooFactor{mA.facT.d(), (int64_t)b.R, 1}
+                                                    : CooFactor{mA.fac.d(), 1, mA.rows};
+  par2s_pass(b, 1, f, b.sp.Y.d(), b.Jtot);
+  b.sp.y_valid = true;
+  b.sp.y_version = mA.version;
+}
+
+// The unweighted right-hand side of one tensor mode of a block with sparse slabs against the current factors
+// (operator-level tests and timing): 0: I x R, 1: Jtot x R in the slab layout, 2: K x R.
+void Engine::resident_par2_rhs(int p, int pos, double* out_host, float* ms) {
+  require_usable();
+  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
+  AO_REQUIRE(p >= 0 && p < n_tensors_ && tensors_[p].par2, "tensor %d is not a PARAFAC2 block", p);
+  AO_REQUIRE(pos >= 0 && pos < 3, "tensor mode %d out of range", pos);
+  AO_HIP(hipSetDevice(device_));
+  TensorInfo& t = tensors_[p];
+  Par2Block& b = t.p2;
+  AO_REQUIRE(b.sparse, "tensor %d does not hold sparse slabs (aoadmm_par2_slab_upload_coo)", p);
+  for (int i = 0; i < 3; ++i) AO_REQUIRE(modes_[t.modes[i]].has_fac, "G.fac{%d} missing", t.modes[i] + 1);
+  ModeInfo& mA = modes_[t.modes[0]];
+  ModeInfo& mB = modes_[t.modes[1]];
+  ModeInfo& mC = modes_[t.modes[2]];
+  ensure_mode_work(mA);
+  b.Ak.ensure((size_t)b.Jtot * b.R * sizeof(double));
+  const P2Dims d = b.dims_all();
+  // events from the engine's pool, handed back on every path (the timing tool calls this in a loop)
+  struct Pair {
+    std::vector<hipEvent_t>& pool;
+    hipEvent_t e0, e1;
+    ~Pair() { pool.push_back(e0); pool.push_back(e1); }
+  };
+  hipEvent_t ev0 = take_event();
+  hipEvent_t ev1 = nullptr;
+  try { ev1 = take_event(); } catch (...) { event_pool_.push_back(ev0); throw; }
+  Pair ev{event_pool_, ev0, ev1};
+  AO_HIP(hipEventRecord(ev.e0, stream_));
+  const double* res = nullptr;
+  int64_t n = 0;
+  if (pos == 0) {
+    par2s_rhs_A(t, mA.tmp.d());
+    res = mA.tmp.d(); n = (int64_t)b.I * b.R;
+  } else {
+    b.sp.y_valid = false;                               // a full evaluation: the pass over the nonzeros included
+    par2s_ensure_Y(t);
+    if (pos == 1) {
+      par2s_ak(b.sp.Y.d(), mC.fac.d(), 1.0, d, b.sp.kofg.as<int>(), b.Ak.d(), stream_);
+      res = b.Ak.d(); n = b.Jtot * b.R;
+    } else {
+      par2s_slab_sums(mB.fac.d(), b.sp.Y.d(), d, b.sp.s.d(), nullptr, nullptr, nullptr, nullptr, nullptr, stream_);
+      res = b.sp.s.d(); n = (int64_t)b.K * b.R;
+    }
+  }
+  AO_HIP(hipEventRecord(ev.e1, stream_));
+  AO_HIP(hipEventSynchronize(ev.e1));
+  float tms = 0.f;
+  AO_HIP(hipEventElapsedTime(&tms, ev.e0, ev.e1));
+  if (ms) *ms = tms;
+  if (out_host) {
+    AO_HIP(hipMemcpyAsync(out_host, res, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    AO_HIP(hipStreamSynchronize(stream_));
+  }
+}
+
 void Engine::par2_ensure_work(TensorInfo& t) {
   Par2Block& b = t.p2;
   const size_t RR = (size_t)b.R * b.R * sizeof(double);
   const size_t cat = (size_t)b.Jtot * b.R * sizeof(double);
   b.DeltaBold.ensure(RR); b.Pold.ensure(cat); b.W.ensure(cat); b.Ak.ensure(cat);
-  b.T1.ensure((size_t)b.K * b.I * b.R * sizeof(double));
+  if (!b.sparse) b.T1.ensure((size_t)b.K * b.I * b.R * sizeof(double));     // X_k B_k: sparse slabs never form it
   b.GB.ensure((size_t)b.K * RR); b.Lk.ensure((size_t)b.K * RR); b.Lc.ensure((size_t)b.K * RR);
   b.rhok.ensure((size_t)b.K * 8); b.rhoc.ensure((size_t)b.K * 8); b.rhomax.ensure(64);
   b.part.ensure((size_t)b.K * RR); b.norms.ensure((size_t)b.K * 8 * 8);
@@ -116,8 +240,13 @@ void Engine::par2_prepare_modeA(int m, int nrho, const aoadmm_options& opt) {
   const P2Dims d = b.dims();
   ModeInfo& mB = modes_[t.modes[1]];
   ModeInfo& mC = modes_[t.modes[2]];
-  par2_xkb(b.X.d(), mB.fac.d(), d, b.T1.d(), stream_);
-  par2_modeA_combine(b.T1.d(), mC.fac.d(), b.GB.d(), d, mi.tmp.d(), b.Csys.d(), stream_);
+  if (b.sparse) {                                     // one pass over the row-sorted nonzeros; Csys needs no data
+    par2s_rhs_A(t, mi.tmp.d());
+    par2_modeA_csys(mC.fac.d(), b.GB.d(), d, b.Csys.d(), stream_);
+  } else {
+    par2_xkb(b.X.d(), mB.fac.d(), d, b.T1.d(), stream_);
+    par2_modeA_combine(b.T1.d(), mC.fac.d(), b.GB.d(), d, mi.tmp.d(), b.Csys.d(), stream_);
+  }
   if (b.slab_sharded) {                               // sums over this rank's slabs -> sums over all slabs
     allreduce(mi.tmp.d(), mi.rows * mi.R);
     allreduce(b.Csys.d(), (int64_t)b.R * b.R);
@@ -160,7 +289,12 @@ void Engine::par2_update_B(int m, const aoadmm_options& opt, int iter) {
   ModeInfo& mC = modes_[t.modes[2]];
   AdmmCtl* ctl = ctl_of_mode(m);
   const bool constr = mi.constrained && iter >= opt.iter_start_PAR2Bkconstraint;        // :209, :527
-  par2_xta(b.X.d(), mA.fac.d(), mC.fac.d(), t.weight, d, b.Ak.d(), stream_);
+  if (b.sparse) {                                     // Y = Xcat' A: a pass over the column-sorted nonzeros if A moved
+    par2s_ensure_Y(t);
+    par2s_ak(b.sp.Y.d(), mC.fac.d(), t.weight, d, b.sp.kofg.as<int>(), b.Ak.d(), stream_);
+  } else {
+    par2_xta(b.X.d(), mA.fac.d(), mC.fac.d(), t.weight, d, b.Ak.d(), stream_);
+  }
   par2_b_system(mA.gram.d(), mC.fac.d(), t.weight, has_ridge_ ? mi.ridge : 0.0, opt.bsum ? opt.bsum_weight / 2 : 0.0,
                 opt.has_increase_factor_rhoBk ? opt.increase_factor_rhoBk : 1.0, 1 + (constr ? 1 : 0), d, b.rhok.d(),
                 b.Lk.d(), ctl, stream_);
@@ -210,16 +344,26 @@ void Engine::par2_update_C(int m, const aoadmm_options& opt) {
   ModeInfo& mA = modes_[t.modes[0]];
   ModeInfo& mB = modes_[t.modes[1]];
   AdmmCtl* ctl = ctl_of_mode(m);
-  par2_xkb(b.X.d(), mB.fac.d(), d, b.T1.d(), stream_);
+  if (b.sparse) {                                     // diag(A' X_k B_k) from Y: no pass while A has not moved
+    par2s_ensure_Y(t);
+    par2s_slab_sums(mB.fac.d(), b.sp.Y.d(), d, b.sp.s.d(), nullptr, nullptr, nullptr, nullptr, nullptr, stream_);
+  } else {
+    par2_xkb(b.X.d(), mB.fac.d(), d, b.T1.d(), stream_);
+  }
   const size_t RR = (size_t)b.R * b.R;
   if (b.slab_sharded) {                               // rows of the other ranks arrive through the all-reduce
     AO_HIP(hipMemsetAsync(b.ac.p, 0, (size_t)b.K * b.R * 8, stream_));
     AO_HIP(hipMemsetAsync(b.rhoc.p, 0, (size_t)b.K * 8, stream_));
     AO_HIP(hipMemsetAsync(b.Lc.p, 0, (size_t)b.K * RR * 8, stream_));
   }
-  par2_c_system(mA.fac.d(), b.T1.d(), mA.gram.d(), b.GB.d(), t.weight, has_ridge_ ? mi.ridge : 0.0,
-                opt.bsum ? opt.bsum_weight / 2 : 0.0, mi.constrained ? 1 : 0, 0, d, mi.fac.d(), b.ac.d(), b.rhoc.d(),
-                b.Lc.d(), ctl, stream_);
+  if (b.sparse)
+    par2_c_system_pre(b.sp.s.d(), mA.gram.d(), b.GB.d(), t.weight, has_ridge_ ? mi.ridge : 0.0,
+                      opt.bsum ? opt.bsum_weight / 2 : 0.0, mi.constrained ? 1 : 0, 0, d, mi.fac.d(), b.ac.d(),
+                      b.rhoc.d(), b.Lc.d(), ctl, stream_);
+  else
+    par2_c_system(mA.fac.d(), b.T1.d(), mA.gram.d(), b.GB.d(), t.weight, has_ridge_ ? mi.ridge : 0.0,
+                  opt.bsum ? opt.bsum_weight / 2 : 0.0, mi.constrained ? 1 : 0, 0, d, mi.fac.d(), b.ac.d(), b.rhoc.d(),
+                  b.Lc.d(), ctl, stream_);
   if (b.slab_sharded) {
     allreduce(b.ac.d(), (int64_t)b.K * b.R);
     allreduce(b.rhoc.d(), b.K);
@@ -279,10 +423,18 @@ void Engine::par2_prepare_C_coupled(int m, int ctype, const aoadmm_options& opt)
   const int con = mi.constrained ? 1 : 0;
   const bool big = ctype == 1 || ctype == 5;          // H*C = ...: one (K*R) x (K*R) system instead of K row systems
   b.rhosum.ensure(64);
-  par2_xkb(b.X.d(), mB.fac.d(), d, b.T1.d(), stream_);
-  par2_c_system(mA.fac.d(), b.T1.d(), mA.gram.d(), b.GB.d(), t.weight, has_ridge_ ? mi.ridge : 0.0,
-                opt.bsum ? opt.bsum_weight / 2 : 0.0, big ? 0 : (ctype == 2 ? con : 1 + con), big ? 1 : 0, d,
-                mi.fac.d(), b.ac.d(), b.rhoc.d(), b.Lc.d(), ctl, stream_, ctype == 2 ? mi.HHt.d() : nullptr);
+  if (b.sparse) {
+    par2s_ensure_Y(t);
+    par2s_slab_sums(mB.fac.d(), b.sp.Y.d(), d, b.sp.s.d(), nullptr, nullptr, nullptr, nullptr, nullptr, stream_);
+    par2_c_system_pre(b.sp.s.d(), mA.gram.d(), b.GB.d(), t.weight, has_ridge_ ? mi.ridge : 0.0,
+                      opt.bsum ? opt.bsum_weight / 2 : 0.0, big ? 0 : (ctype == 2 ? con : 1 + con), big ? 1 : 0, d,
+                      mi.fac.d(), b.ac.d(), b.rhoc.d(), b.Lc.d(), ctl, stream_, ctype == 2 ? mi.HHt.d() : nullptr);
+  } else {
+    par2_xkb(b.X.d(), mB.fac.d(), d, b.T1.d(), stream_);
+    par2_c_system(mA.fac.d(), b.T1.d(), mA.gram.d(), b.GB.d(), t.weight, has_ridge_ ? mi.ridge : 0.0,
+                  opt.bsum ? opt.bsum_weight / 2 : 0.0, big ? 0 : (ctype == 2 ? con : 1 + con), big ? 1 : 0, d,
+                  mi.fac.d(), b.ac.d(), b.rhoc.d(), b.Lc.d(), ctl, stream_, ctype == 2 ? mi.HHt.d() : nullptr);
+  }
   // max(rho) for the prox (:1424); mean(rho) takes the place of the scalar rho of a CP mode (:284, :712), sum(rho)
   // weighs this mode in the Delta update (:736)
   par2_rho_max(b.rhoc.d(), b.K, b.rhomax.d(), stream_, mi.rho.d(), b.rhosum.d());
@@ -342,7 +494,14 @@ void Engine::par2_objective_enqueue(TensorInfo& t) {
     AO_HIP(hipMemsetAsync(b.q.p, 0, (size_t)b.K * 4 * 8, stream_));
     if (regs) AO_HIP(hipMemsetAsync(b.regv.p, 0, (size_t)b.K * 8, stream_));
   }
-  par2_residual(b.X.d(), mA.fac.d(), mB.fac.d(), mC.fac.d(), d, b.res.d(), stream_);
+  if (b.sparse) {
+    // ||X_k - A D_k B_k'||^2 = ||X_k||^2 - 2 sum_r C(k,r) s(k,r) + <GA, (c_k c_k') .* GB_k>, s from Y (the CP blocks'
+    // move): no pass of its own unless A moved since Y was formed, and then the next B_k update reuses Y
+    par2s_ensure_Y(t);
+    par2s_slab_sums(mB.fac.d(), b.sp.Y.d(), d, b.sp.s.d(), b.sp.xn.d(), mC.fac.d(), mA.gram.d(), b.GB.d(), b.res.d(), stream_);
+  } else {
+    par2_residual(b.X.d(), mA.fac.d(), mB.fac.d(), mC.fac.d(), d, b.res.d(), stream_);
+  }
   par2_b_gaps(mB.fac.d(), b.P.d(), b.DeltaB.d(), mB.constrained ? mB.Z.d() : nullptr, d, b.q.d(), stream_);
   if (regs) par2_reg_values(mB.fac.d(), mB.prox.type, mB.prox.p0, d, b.regv.d(), stream_);
   if (b.slab_sharded) {

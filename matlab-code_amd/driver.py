@@ -25,7 +25,8 @@ import numpy as np
 
 from . import _capi as capi
 from .engine import Engine, constraint_descriptor, default_engine
-from .sptensor import coo_of
+from .sptensor import coo_of, pack_par2_slabs
+from .sptensor import slab_gram as _sparse_slab_gram
 from .sptensor import unfold_gram as _sparse_unfold_gram
 
 
@@ -114,6 +115,14 @@ def _resident_gram(eng, Z, p, pos, n, slab=0):
         return None
 
 
+def _par2_sparse(slabs, p):
+    """True when every slab of a PARAFAC2 block is sparse (sptensor / .tocoo()), False when every slab is dense."""
+    kinds = [coo_of(Xk) is not None for Xk in slabs]
+    if any(kinds) and not all(kinds):
+        raise ValueError('Z.object{%d}: the slabs of a PARAFAC2 block must be all sparse or all dense' % (p + 1))
+    return bool(kinds) and all(kinds)
+
+
 def init_coupled_AOADMM_CMTF(Z, init_options, Delta=None, rng=None, engine=None):
     """functions/init_coupled_AOADMM_CMTF.m:1-174: random initialisation (`nvecs = 0`) or SVD-based (`nvecs = 1`,
     :50-73), the latter with the unfolding Gram matrices computed on the device."""
@@ -146,7 +155,10 @@ def init_coupled_AOADMM_CMTF(Z, init_options, Delta=None, rng=None, engine=None)
                 if Z['model'][p] == 'CP':
                     A['fac'][n] = cmtf_nvecs(Z, n, R, eng_nv)
                 elif md.index(n) == 0:
-                    Y = _resident_gram(eng_nv, Z, p, 0, int(sz[n]))
+                    if _par2_sparse(Z['object'][p], p):     # sum_k X_k X_k' on the host, no densified slab
+                        Y = sum(_sparse_slab_gram(Xk, 0) for Xk in Z['object'][p])
+                    else:
+                        Y = _resident_gram(eng_nv, Z, p, 0, int(sz[n]))
                     if Y is None:
                         M = np.hstack([np.asarray(Xk, dtype=np.float64) for Xk in Z['object'][p]])
                         Y = eng_nv.unfold_gram(M, 0)
@@ -156,8 +168,12 @@ def init_coupled_AOADMM_CMTF(Z, init_options, Delta=None, rng=None, engine=None)
                     A['fac'][n] = []
                     A['P'][p] = []
                     A['mu_DeltaB'][p] = []
+                    sparse_slabs = _par2_sparse(Z['object'][p], p)
                     for k in range(len(sz[n])):
-                        Y = _resident_gram(eng_nv, Z, p, 1, int(sz[n][k]), k)
+                        if sparse_slabs:
+                            Y = _sparse_slab_gram(Z['object'][p][k], 1)
+                        else:
+                            Y = _resident_gram(eng_nv, Z, p, 1, int(sz[n][k]), k)
                         if Y is None:
                             Y = eng_nv.unfold_gram(np.asarray(Z['object'][p][k], dtype=np.float64), 1)
                         A['fac'][n].append(_leading_eigvecs(Y, R))
@@ -259,7 +275,8 @@ def build_model(eng, Z, precision='f64'):
 
     Z.object{p} of a CP block may be dense, an `sptensor`, or (2-way blocks) any object with `.tocoo()` such as a
     scipy.sparse matrix; sparse blocks go up as coalesced COO nonzeros (`aoadmm_tensor_upload_coo`) and stay fp64
-    whatever `precision` says (it applies to dense blocks only)."""
+    whatever `precision` says (it applies to dense blocks only).  The slabs of a PAR2 block may likewise be 2-way
+    `sptensor`s or objects with `.tocoo()`, all of them or none (`aoadmm_par2_slab_upload_coo`)."""
     lib = eng.lib
     nb_modes = len(Z['size'])
     which_p = _which_p(Z)
@@ -353,6 +370,16 @@ def build_model(eng, Z, precision='f64'):
                     raise ValueError('Z.miss{%d} size does not match Z.object{%d}.' % (p + 1, p + 1))
                 mk = np.asfortranarray(mk != 0, dtype=np.uint8)
                 capi.check(lib.aoadmm_tensor_mask_upload(eng.h, p, mk.ctypes.data_as(C.POINTER(C.c_uint8))))
+        elif _par2_sparse(Z['object'][p], p):
+            # sparse slabs: the nonzeros of all slabs as (i, j, k) in one transfer; fp64 whatever `precision` says
+            md = [m - 1 for m in Z['modes'][p]]
+            Jk = [int(v) for v in Z['size'][md[1]]]
+            if len(Z['object'][p]) != len(Jk):
+                raise ValueError('Z.object{%d} has %d slabs, Z.size says %d' % (p + 1, len(Z['object'][p]), len(Jk)))
+            subs, vals = pack_par2_slabs(Z['object'][p], int(Z['size'][md[0]]), Jk, p)
+            if miss[p] is not None:
+                raise ValueError('Missing data (Z.miss) not supported for sparse PARAFAC2 slabs. Convert to full slabs first.')
+            eng.upload_par2_coo(p, subs, vals)
         else:
             # the slabs back to back (each I x J_k, column-major) in one transfer
             Xall = np.concatenate([np.asarray(Xk, dtype=np.float64).ravel(order='F') for Xk in Z['object'][p]])

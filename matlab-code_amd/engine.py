@@ -121,6 +121,28 @@ class Engine:
         capi.check(self.lib.aoadmm_tensor_upload_coo(self.h, int(p), int(vals.shape[0]),
                                                      subs.ctypes.data_as(C.POINTER(C.c_int64)), capi.dptr(vals)))
 
+    def upload_par2_coo(self, p, subs, vals):
+        """The slabs of a PARAFAC2 block as COO nonzeros (`aoadmm_par2_slab_upload_coo`): subs nnz x 3, 0-based
+        (i, j within the slab, k), all slabs in one call; vals nnz.  Duplicates are summed on the device."""
+        subs = np.asarray(subs, dtype=np.int64)
+        vals = np.ascontiguousarray(np.asarray(vals, dtype=np.float64).reshape(-1))
+        if subs.size == 0:
+            subs = np.zeros((0, 3), dtype=np.int64)
+        if subs.ndim != 2 or subs.shape[1] != 3 or subs.shape[0] != vals.shape[0]:
+            raise ValueError('upload_par2_coo: subs must be nnz x 3 with nnz = len(vals)')
+        subs = np.asfortranarray(subs)
+        capi.check(self.lib.aoadmm_par2_slab_upload_coo(self.h, int(p), int(vals.shape[0]),
+                                                        subs.ctypes.data_as(C.POINTER(C.c_int64)), capi.dptr(vals)))
+
+    def resident_par2_rhs(self, p, tensor_mode, rows, R, with_ms=False):
+        """Unweighted right-hand side of tensor mode 0 (I x R), 1 (sum J_k x R, slabs back to back, each J_k x R
+        column-major) or 2 (K x R) of a PARAFAC2 block with sparse slabs (`aoadmm_resident_par2_rhs`).  Mode 1 comes
+        back as the packed vector of the state fields; with_ms: (result, device ms)."""
+        out = np.zeros(rows * R) if tensor_mode == 1 else np.zeros((rows, R), order='F')
+        ms = C.c_float(0)
+        capi.check(self.lib.aoadmm_resident_par2_rhs(self.h, int(p), int(tensor_mode), capi.dptr(out), C.byref(ms)))
+        return (out, ms.value) if with_ms else out
+
     def resident_mttkrp(self, p, tensor_mode, rows, R):
         """One MTTKRP of the resident block p against the current factors (`aoadmm_resident_mttkrp`): rows x R."""
         out = np.zeros((rows, R), order='F')
@@ -130,7 +152,7 @@ class Engine:
 
     def kernel_stats(self, which, reset=False):
         """(ms, launches, bytes, flops) of a kernel class since the last reset (`aoadmm_kernel_stats`); which = 3:
-        MTTKRPs of sparse blocks."""
+        MTTKRPs of sparse blocks and passes over the nonzeros of PARAFAC2 blocks with sparse slabs."""
         ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         capi.check(self.lib.aoadmm_kernel_stats(self.h, int(which), int(bool(reset)), C.byref(ms), C.byref(n),
                                                 C.byref(by), C.byref(fl)))

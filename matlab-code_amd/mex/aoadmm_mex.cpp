@@ -334,7 +334,51 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   // ---- data: Z.object{p}
   for (int p = 0; p < P; ++p) {
     const mxArray* obj = mxGetCell(object, p);
-    if (mxIsCell(obj)) {
+    bool sparse_slabs = false;
+    if (mxIsCell(obj)) {                                  // PARAFAC2 slabs: all sparse matrices or all full ones
+      mwSize nsp = 0;
+      for (mwSize k = 0; k < mxGetNumberOfElements(obj); ++k) nsp += mxIsSparse(mxGetCell(obj, k)) ? 1 : 0;
+      if (nsp != 0 && nsp != mxGetNumberOfElements(obj))
+        mexErrMsgIdAndTxt("aoadmm:mixedSlabs", "Z.object{%d}: the slabs of a PARAFAC2 block must be all sparse or all full.", p + 1);
+      sparse_slabs = nsp != 0;
+    }
+    if (sparse_slabs) {
+      // compressed columns (ir / jc / values) of every slab -> 0-based (i, j, k), column-major nnz x 3, one transfer;
+      // values stay fp64 whatever options.hip.precision says
+      std::vector<int64_t> si, sj, sk;
+      std::vector<double> vals;
+      // shapes against Z.size, as the Python layer does: a slab with fewer rows or columns, or a surplus cell, would
+      // otherwise go up silently as a differently shaped model
+      const mxArray* mp = mxGetCell(modes, p);
+      const int mA = (int)mxGetDoubles(mp)[0] - 1, mB = (int)mxGetDoubles(mp)[1] - 1;
+      const mxArray* szB = mxGetCell(sz, mB);
+      if (mxGetNumberOfElements(obj) != mxGetNumberOfElements(szB))
+        mexErrMsgIdAndTxt("aoadmm:slabCount", "Z.object{%d} has %d slabs, Z.size says %d.", p + 1,
+                          (int)mxGetNumberOfElements(obj), (int)mxGetNumberOfElements(szB));
+      const double rowsA = mxGetScalar(mxGetCell(sz, mA));
+      for (mwSize k = 0; k < mxGetNumberOfElements(obj); ++k) {
+        const mxArray* xk = mxGetCell(obj, k);
+        if (!mxIsDouble(xk) || mxIsComplex(xk))
+          mexErrMsgIdAndTxt("aoadmm:sparseSlabType", "Z.object{%d}{%d} must be a real sparse double matrix.", p + 1, (int)k + 1);
+        if ((double)mxGetM(xk) != rowsA || (double)mxGetN(xk) != mxGetDoubles(szB)[k])
+          mexErrMsgIdAndTxt("aoadmm:slabSize", "Z.object{%d}{%d} has size [%d %d], Z.size says [%d %d].", p + 1, (int)k + 1,
+                            (int)mxGetM(xk), (int)mxGetN(xk), (int)rowsA, (int)mxGetDoubles(szB)[k]);
+        const mwIndex* jc = mxGetJc(xk);
+        const mwIndex* ir = mxGetIr(xk);
+        const double* v = mxGetDoubles(xk);
+        for (mwSize j = 0; j < mxGetN(xk); ++j)
+          for (mwIndex q = jc[j]; q < jc[j + 1]; ++q) {
+            si.push_back((int64_t)ir[q]); sj.push_back((int64_t)j); sk.push_back((int64_t)k);
+            vals.push_back(v[q]);
+          }
+      }
+      std::vector<int64_t> subs;
+      subs.reserve(3 * vals.size());
+      subs.insert(subs.end(), si.begin(), si.end());
+      subs.insert(subs.end(), sj.begin(), sj.end());
+      subs.insert(subs.end(), sk.begin(), sk.end());
+      check(aoadmm_par2_slab_upload_coo(g_ctx, p, (int64_t)vals.size(), subs.data(), vals.data()));
+    } else if (mxIsCell(obj)) {
       std::vector<double> packed;                         // the slabs back to back, one transfer
       for (mwSize k = 0; k < mxGetNumberOfElements(obj); ++k) {
         const mxArray* xk = mxGetCell(obj, k);
@@ -355,6 +399,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       has_missing = true;
       if (is_sparse_object(obj))                          // cmtf_AOADMM.m:77-79
         mexErrMsgIdAndTxt("cmtf:missingData:sptensor", "Missing data (Z.miss) not supported for sptensor objects. Convert to tensor first.");
+      if (sparse_slabs)
+        mexErrMsgIdAndTxt("cmtf:missingData:sparseSlabs", "Missing data (Z.miss) not supported for sparse PARAFAC2 slabs. Convert to full slabs first.");
       if (mxIsCell(obj)) {
         if (!mxIsCell(mk) || mxGetNumberOfElements(mk) != mxGetNumberOfElements(obj))
           mexErrMsgIdAndTxt("cmtf:missingData:PAR2maskNotCell", "Z.miss{%d} must be a cell array of length %d for PAR2.", p + 1,

@@ -12,7 +12,8 @@ function [G,out] = cmtf_fun_AOADMM_hip(Z,Znorm_const,G,fh,gh,lscalar,uscalar,opt
 %
 % Function handles cannot cross to the GPU, so Z.prox_operators / Z.reg_func (cmtf_AOADMM.m:30-32) are
 % dropped and the MEX gateway re-reads the constraint descriptors Z.constraints{m}. Sparse CP blocks (an
-% sptensor, or a sparse double matrix for a 2-way block) go to the device as they are, as COO nonzeros in fp64.
+% sptensor, or a sparse double matrix for a 2-way block) go to the device as they are, as COO nonzeros in fp64;
+% so do the slabs of a PARAFAC2 block when every Z.object{p}{k} is a sparse double matrix.
 % Models the device path does not cover ('custom' constraints, KL/IS/beta losses) raise cmtf:hip:unsupported,
 % which is caught here and handed to the original MATLAB implementation, so every example script keeps running.
 % Znorm_const, fh, gh, lscalar, uscalar are only needed by that fallback.

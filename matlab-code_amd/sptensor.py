@@ -81,6 +81,32 @@ def coo_of(obj):
     return None
 
 
+def pack_par2_slabs(slabs, I, Jk, p=0):
+    """The sparse slabs of a PARAFAC2 block -> one COO list for `aoadmm_par2_slab_upload_coo`: subs nnz x 3, 0-based
+    (i, j within the slab, k), vals.  Every slab is an sptensor or has .tocoo(); its shape must be I x Jk[k].
+    Duplicates and explicit zeros are passed on as they are (the device sums duplicates)."""
+    subs, vals = [], []
+    for k, Xk in enumerate(slabs):
+        c = coo_of(Xk)
+        if c is None:
+            raise ValueError('Z.object{%d}: slab %d is dense, the others sparse: all slabs must be sparse or all dense' % (p + 1, k + 1))
+        sk, vk, shape = c
+        if tuple(shape) != (int(I), int(Jk[k])):
+            raise ValueError('Z.object{%d}{%d} has size %s, Z.size says %s' % (p + 1, k + 1, tuple(shape), [int(I), int(Jk[k])]))
+        sk = np.asarray(sk, dtype=np.int64).reshape(-1, 2)
+        subs.append(np.column_stack([sk, np.full(sk.shape[0], k, dtype=np.int64)]))
+        vals.append(np.asarray(vk, dtype=np.float64).reshape(-1))
+    if not subs:
+        return np.zeros((0, 3), dtype=np.int64), np.zeros(0)
+    return np.ascontiguousarray(np.vstack(subs)), np.concatenate(vals)
+
+
+def slab_gram(obj, n):
+    """Gram matrix of a sparse slab for init_options.nvecs = 1 without densifying it: X X' (n = 0) or X' X (n = 1)."""
+    subs, vals, shape = coo_of(obj)
+    return unfold_gram(subs, vals, shape, n)
+
+
 def unfold_gram(subs, vals, shape, n):
     """Y = X_(n) X_(n)' of a sparse tensor (cmtf_nvecs.m:41-42, `double(sptenmat(X, n))`) without densifying the
     tensor: the unfolding is a scipy.sparse matrix (columns = linear index of the other modes, column-major)."""
