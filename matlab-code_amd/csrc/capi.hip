@@ -504,7 +504,7 @@ int aoadmm_op_mttkrp(aoadmm_ctx* ctx, const double* X, int ndims, const int64_t*
     Engine& e = *ctx->eng;
     AO_HIP(hipSetDevice(e.device()));
     CpBlock blk;
-    e.block_upload(blk, ndims, dims, X, precision, 0, dims[0]);
+    block_upload(e.block_ctx(), blk, ndims, dims, X, precision, 0, dims[0]);
     std::vector<DevBuf> fac(ndims);
     FactorRef refs[8];
     for (int m = 0; m < ndims; ++m) {
@@ -515,7 +515,7 @@ int aoadmm_op_mttkrp(aoadmm_ctx* ctx, const double* X, int ndims, const int64_t*
     DevBuf o;
     o.alloc((size_t)dims[n] * R * sizeof(double));
     // host in / host out on ONE engine with the whole tensor: no collective, whatever communicator the engine is in
-    e.block_mttkrp(blk, n, refs, R, 1.0, o.d(), dims[n], false, nullptr, 0, false, true);
+    block_mttkrp(e.block_ctx(), blk, n, refs, R, 1.0, o.d(), dims[n], false, nullptr, 0, false, true);
     d2h(out, o, dims[n] * R, e.stream());
   });
 }
@@ -529,7 +529,7 @@ int aoadmm_op_unfold_gram(aoadmm_ctx* ctx, const double* X, int ndims, const int
     Engine& e = *ctx->eng;
     AO_HIP(hipSetDevice(e.device()));
     CpBlock blk;
-    e.block_upload(blk, ndims, dims, X, precision, 0, dims[0]);
+    block_upload(e.block_ctx(), blk, ndims, dims, X, precision, 0, dims[0]);
     const int64_t I = dims[0], Ip = blk.X.pad0, J = dims[1], K = ndims == 3 ? dims[2] : 1;
     UnfoldGramArgs a;
     a.X = blk.X.data.p;

@@ -357,7 +357,7 @@ __global__ __launch_bounds__(256, NT <= 2 ? 2 : 1) void contract16_f32(KArgs a) 
 // ---------------------------------------------------------------------------
 // f32 contraction of the LEADING (contiguous) mode:  T(m, r) = sum_i X[i + ld*m] * F(i, r)
 // ---------------------------------------------------------------------------
-// Used only when the mode-permuted second copy of the tensor (solver.h CpBlock::Xp) is unavailable.  The
+// Used only when the resident copy for the pass that contracts mode 1 (cpblock.h CpBlock::copy[0]) is unavailable.  The
 // reduction index is the contiguous one, so MFMA A operands (one unfolding row per lane) cannot be loaded
 // straight from HBM: a workgroup streams a [128 rows m] x [64 i] tile (128 segments of 256 contiguous bytes)
 // through registers into LDS (row stride 68 floats: ds_read_b128 of 16 rows at one column offset hits 16

@@ -1,0 +1,136 @@
+// One dense CP block (tensor or matrix): its resident data, the pass copies, the partial-contraction cache and the
+// MTTKRP paths over them.  Nothing here knows the model, the couplings or the outer loop; what a function needs from
+// the engine arrives in a BlockCtx.
+#pragma once
+#include "common.h"
+#include "contract.h"
+#include "sparse.h"
+
+namespace aoadmm {
+
+struct FactorRef {
+  const double* p;    // device, column-major
+  int64_t ld;
+  uint64_t version;
+  const double* pT = nullptr;   // optional row-major copy (rows x R) of the same version, written by the Gram kernel
+};
+
+struct KernelStats {
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+  double ms = 0.0, bytes = 0.0, flops = 0.0;
+  int64_t launches = 0, timed = 0;      // timed <= launches: launches bracketed by an event pair
+};
+
+// Event pool and kernel statistics of one engine.  begin()/end() bracket the launches of one MTTKRP step with an event
+// pair when the budget allows and count it in `ks` either way.
+struct LaunchTimers {
+  struct Pair { hipEvent_t e0 = nullptr, e1 = nullptr; };
+  std::vector<hipEvent_t> pool;   // timing events are recycled: creating two per tensor pass cost host time in the loop
+  KernelStats stats[4];   // [0] streaming contraction, [1] leading-mode contraction, [2] reductions over T, [3] sparse MTTKRP and the passes over sparse PARAFAC2 slabs
+  bool profile = true;
+  bool profile_reductions = false;   // switched on by the first kernel_stats(2, ...) call: two more events per reduction
+  hipEvent_t take_event();
+  void fold_finished(KernelStats& ks);   // completed pairs are added to ks.ms, their events go back to the pool
+  Pair take_pair(KernelStats& ks);       // two events, or none once ks holds 4096 unfinished pairs
+  Pair begin(KernelStats& ks, bool timed, hipStream_t s);                    // records e0 when it took a pair
+  void end(KernelStats& ks, Pair pr, hipStream_t s, double bytes, double flops);   // records e1, then count()
+  void count(KernelStats& ks, Pair pr, double bytes, double flops);
+};
+
+// What the block functions use of the engine that calls them
+struct BlockCtx {
+  hipStream_t stream;
+  LaunchTimers* timers;
+  int rank, world;
+  bool sharded;        // Engine::sharded()
+  bool allow_copies;   // options.hip.no_permuted_copy == 0
+  DevBuf* staging;     // host-to-device staging of the uploads
+  // recv = sum over the ranks of send, enqueued on `stream` (send == recv: in place): Engine::allreduce_from of `comm`
+  void (*allreduce_from)(void* comm, const double* send, double* recv, int64_t n);
+  void* comm;
+};
+
+// 3-way tensors: copy[c] is the resident copy the pass that contracts mode c streams over, so that all three passes
+// run the same register-streaming kernel (each the tensor's size again in HBM; 288 GB per GPU).  All are row-blocked
+// (misc.hip block_layout_copy): copy[0](j,k,i) = X(i,j,k), copy[1](k,i,j) = X(i,j,k) (one streaming pass instead of K
+// batches of an I x J matrix: measured 6.0 ms against 5.4-5.5 ms at 2000^3), copy[2] the rows of X itself.
+struct PassCopy {
+  DevBuf buf;
+  int64_t pad = 0;     // padded extent of the leading uncontracted mode: of J, of K, X.pad0
+  bool present = false, refused = false;   // refused is sticky: no room in HBM, or a mode too long for the copy kernels
+};
+
+// One dense CP block (tensor or matrix) and its partial-contraction cache.
+struct CpBlock {
+  DenseTensor X;       // natural layout, first dimension padded
+  DenseTensor Xt;      // matrices only: transposed copy (second mode contiguous)
+  PassCopy copy[3];
+  DevBuf emkr, emkr2;  // order > 3 with Z.miss: Khatri-Rao factor of the merged trailing modes (ping-pong)
+  // With a communicator copy[0] is sharded along mode 3 instead of mode 1:
+  // rank g holds X(:, :, K_g), contracts ALL of mode 1 and gets a complete T(j, k in K_g, r) of 1/N the size, instead
+  // of a partial sum of full size J x K from its rows of mode 1.
+  bool xp_ksharded = false;
+  int64_t xp_k0 = 0, xp_kloc = 0;
+  int nd = 0;
+  int64_t dims[8] = {0};   // local sizes (dims[0] = local rows when sharded)
+  int64_t full0 = 0;       // global size of the first mode
+  int64_t row0 = 0;        // first local row of the first mode
+  bool has_data = false;
+  // The natural-layout array is only read to build the three pass copies, for ||X||^2, the EM pass and the fallbacks; once
+  // all three copies exist (and no mask does) it can go: 4 -> 3 resident copies (maybe_release_natural)
+  bool x_released = false;
+  // dimension-tree cache: T = X x_c F_c, valid while factor c keeps `cached_version`
+  int cached_mode = -1;
+  uint64_t cached_version = 0;
+  ContractPlan plan;
+  DevBuf T, frag, scratch, ft, tmpA, tmpB;
+  // sharded MTTKRP outputs that are this rank's ROWS of the result (mode 1; mode 3 under xp_ksharded): send buffers whose
+  // other rows are zero for good (cleared once), all-reduced out of place into the caller's buffer
+  DevBuf own[2];
+  size_t own_bytes[2] = {0, 0};
+  int64_t own_row0[2] = {-1, -1};
+  // Z.miss{p}: one byte per entry in the layout of X (and of Xt for matrices), 1 = observed
+  DevBuf mask, maskT;
+  bool has_mask = false;
+  // sparse form of Z.object{p} (aoadmm_tensor_upload_coo): replaces everything above but nd / dims / has_data; every
+  // rank of a communicator holds all nonzeros and computes the complete MTTKRP (no row sharding, no collective)
+  bool sparse = false;
+  CooBlock coo;
+  // New data has arrived, dense or sparse: no copy, cached contraction or release state of the old data holds.  Frees
+  // nothing (a pass copy's buffer is reused by the next build; the sparse upload releases what it no longer needs).
+  void reset_derived() {
+    has_data = true; x_released = false; cached_mode = -1; xp_ksharded = false;
+    for (PassCopy& c : copy) c.present = c.refused = false;
+  }
+};
+
+inline int64_t pad_of(int prec, int64_t n) { return round_up(n, prec == AOADMM_PREC_F32 ? 4 : 2); }
+// distance (in updates) until tensor position `c` is updated again after position `pos`
+int next_update_distance(int pos, int c, const int* seq, int n);
+// tiny unsharded block: MTTKRP by the one-launch kernel instead of contraction pass + reduction
+inline bool small_direct(bool sharded, const CpBlock& b, int R) {
+  return !sharded && small_mttkrp_ok(b.X.elems_padded(), b.nd, b.dims, R);
+}
+
+// `full_array`: the caller's whole tensor when it holds one (lets a sharded engine take its mode-3 slab as well)
+void block_upload(const BlockCtx& cx, CpBlock& b, int nd, const int64_t* dims, const double* host, int prec, int64_t row0,
+                  int64_t local_rows, const double* full_array = nullptr);
+// builds the mode-3-sharded copy[0] from a natural-layout slab X(:, :, [k0, k0 + kloc)) already on the device
+void adopt_ksharded_xp(const BlockCtx& cx, CpBlock& b, const void* slab, int64_t k0, int64_t kloc);
+bool want_ksharded_xp(const BlockCtx& cx, const CpBlock& b, int64_t K, int64_t* k0, int64_t* kloc);
+bool ensure_pass_copy(const BlockCtx& cx, CpBlock& b, int c);   // false: the pass that contracts mode c runs on X
+void drop_pass_copies(CpBlock& b);
+void maybe_release_natural(const BlockCtx& cx, CpBlock& b, bool normsq_valid);
+// makes b.T hold a partial contraction that serves an MTTKRP for tensor position `pos` (3-way blocks)
+void ensure_contraction(const BlockCtx& cx, CpBlock& b, int pos, const FactorRef* facs, int R, bool use_cache,
+                        const int* update_seq, int nseq);
+// MTTKRP of a block against factors (device), result scale*mttkrp into out (ld = ldOut)
+// `collective` = false: the block holds the whole tensor and the result is complete on this engine (op-level
+// entry on an engine that happens to belong to a communicator)
+// `tensor_pass` = true: always the tensor-pass kernels, also for blocks small enough for the one-launch kernel
+// (the op-level entries, so that their parity tests exercise the pass kernels at every size)
+void block_mttkrp(const BlockCtx& cx, CpBlock& b, int pos, const FactorRef* facs, int R, double scale, double* out,
+                  int64_t ldOut, bool use_cache, const int* update_seq, int nseq, bool collective = true,
+                  bool tensor_pass = false, const SysBuild* sys = nullptr, bool* sys_done = nullptr);
+
+}  // namespace aoadmm

@@ -11,6 +11,7 @@
 #include "admm.h"
 #include "common.h"
 #include "contract.h"
+#include "cpblock.h"
 #include "misc.h"
 #include "par2.h"
 #include "par2_sparse.h"
@@ -20,64 +21,6 @@
 typedef struct ncclComm* ncclComm_t;
 
 namespace aoadmm {
-
-struct FactorRef {
-  const double* p;    // device, column-major
-  int64_t ld;
-  uint64_t version;
-  const double* pT = nullptr;   // optional row-major copy (rows x R) of the same version, written by the Gram kernel
-};
-
-// One dense CP block (tensor or matrix) and its partial-contraction cache.
-struct CpBlock {
-  DenseTensor X;       // natural layout, first dimension padded
-  DenseTensor Xt;      // matrices only: transposed copy (second mode contiguous)
-  // 3-way tensors: optional second copy Xp(j,k,i) = X(i,j,k) (leading dimension Jp), built on first use, so that
-  // the pass that contracts mode 1 streams like the others (the tensor's size again in HBM; 288 GB per GPU)
-  DevBuf Xp;
-  DevBuf emkr, emkr2;  // order > 3 with Z.miss: Khatri-Rao factor of the merged trailing modes (ping-pong)
-  int64_t Jp = 0;
-  bool has_xp = false, xp_refused = false;
-  // With a communicator the copy for the pass that contracts mode 1 is sharded along mode 3 instead of mode 1:
-  // rank g holds X(:, :, K_g), contracts ALL of mode 1 and gets a complete T(j, k in K_g, r) of 1/N the size, instead
-  // of a partial sum of full size J x K from its rows of mode 1.
-  bool xp_ksharded = false;
-  int64_t xp_k0 = 0, xp_kloc = 0;
-  // third copy Xq(k,i,j) = X(i,j,k) (leading dimension Kp): the pass that contracts mode 2 then streams like the
-  // other two instead of running K batches of an I x J matrix (measured 6.0 ms against 5.4-5.5 ms at 2000^3)
-  DevBuf Xq;
-  int64_t Kp = 0;
-  bool has_xq = false, xq_refused = false;
-  // and a copy for the pass that contracts mode 3: same row order as X, but row-blocked like the other two
-  // (misc.hip block_layout_copy); all three copies are stored in that layout
-  DevBuf Xc;
-  bool has_xc = false, xc_refused = false;
-  int nd = 0;
-  int64_t dims[8] = {0};   // local sizes (dims[0] = local rows when sharded)
-  int64_t full0 = 0;       // global size of the first mode
-  int64_t row0 = 0;        // first local row of the first mode
-  bool has_data = false;
-  // The natural-layout array is only read to build the three pass copies, for ||X||^2, the EM pass and the fallbacks; once
-  // all three copies exist (and no mask does) it can go: 4 -> 3 resident copies (Engine::maybe_release_natural)
-  bool x_released = false;
-  // dimension-tree cache: T = X x_c F_c, valid while factor c keeps `cached_version`
-  int cached_mode = -1;
-  uint64_t cached_version = 0;
-  ContractPlan plan;
-  DevBuf T, frag, scratch, ft, tmpA, tmpB;
-  // sharded MTTKRP outputs that are this rank's ROWS of the result (mode 1; mode 3 under xp_ksharded): send buffers whose
-  // other rows are zero for good (cleared once), all-reduced out of place into the caller's buffer
-  DevBuf own[2];
-  size_t own_bytes[2] = {0, 0};
-  int64_t own_row0[2] = {-1, -1};
-  // Z.miss{p}: one byte per entry in the layout of X (and of Xt for matrices), 1 = observed
-  DevBuf mask, maskT;
-  bool has_mask = false;
-  // sparse form of Z.object{p} (aoadmm_tensor_upload_coo): replaces everything above but nd / dims / has_data; every
-  // rank of a communicator holds all nonzeros and computes the complete MTTKRP (no row sharding, no collective)
-  bool sparse = false;
-  CooBlock coo;
-};
 
 struct ModeInfo {
   bool defined = false;
@@ -174,12 +117,6 @@ struct CouplingInfo {
   bool has_state = false;
 };
 
-struct KernelStats {
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-  double ms = 0.0, bytes = 0.0, flops = 0.0;
-  int64_t launches = 0, timed = 0;      // timed <= launches: launches bracketed by an event pair
-};
-
 struct LocalGroup;
 
 class Engine {
@@ -235,36 +172,19 @@ class Engine {
   bool sharded() const { return world_ > 1 || comm_ != nullptr || local_ != nullptr; }
   void require_usable() const;          // throws AOADMM_ERR_RCCL once comm_abort() has run (sticky)
   bool share_only() const { return share_only_; }
-  // tiny unsharded block: MTTKRP by the one-launch kernel instead of contraction pass + reduction
-  bool small_direct(const CpBlock& b, int R) const { return !sharded() && small_mttkrp_ok(b.X.elems_padded(), b.nd, b.dims, R); }
   int rank() const { return rank_; }
   int world() const { return world_; }
 
   hipStream_t stream() const { return stream_; }
   int device() const { return device_; }
 
-  // MTTKRP of a dense block against factors (device), result scale*mttkrp into out (ld = ldOut)
-  void ensure_contraction(CpBlock& b, int pos, const FactorRef* facs, int R, bool use_cache, const int* update_seq,
-                          int nseq);
-  bool ensure_permuted_copy(CpBlock& b);
-  bool ensure_permuted_copy2(CpBlock& b);
-  bool ensure_blocked_copy(CpBlock& b);
-  // builds the mode-3-sharded Xp from a natural-layout slab X(:, :, [k0, k0 + kloc)) already on the device
-  void adopt_ksharded_xp(CpBlock& b, const void* slab, int64_t k0, int64_t kloc);
-  bool want_ksharded_xp(const CpBlock& b, int64_t K, int64_t* k0, int64_t* kloc) const;
-  void drop_permuted_copies(CpBlock& b);
-  void maybe_release_natural(TensorInfo& t);
+  // what the block functions (cpblock.h) use of this engine
+  BlockCtx block_ctx() {
+    return BlockCtx{stream_, &timers_, rank_, world_, sharded(), allow_xp_, &staging_,
+                    [](void* e, const double* send, double* recv, int64_t n) { static_cast<Engine*>(e)->allreduce_from(send, recv, n); },
+                    this};
+  }
   bool prefetch_next_contraction(const aoadmm_options& opt);   // true: a tensor pass was enqueued
-  // `collective` = false: the block holds the whole tensor and the result is complete on this engine (op-level
-  // entry on an engine that happens to belong to a communicator)
-  // `tensor_pass` = true: always the tensor-pass kernels, also for blocks small enough for the one-launch kernel
-  // (the op-level entries, so that their parity tests exercise the pass kernels at every size)
-  void block_mttkrp(CpBlock& b, int pos, const FactorRef* facs, int R, double scale, double* out,
-                    int64_t ldOut, bool use_cache, const int* update_seq, int nseq, bool collective = true,
-                    bool tensor_pass = false, const SysBuild* sys = nullptr, bool* sys_done = nullptr);
-  // `full_array`: the caller's whole tensor when it holds one (lets a sharded engine take its mode-3 slab as well)
-  void block_upload(CpBlock& b, int nd, const int64_t* dims, const double* host, int prec, int64_t row0,
-                    int64_t local_rows, const double* full_array = nullptr);
   void allreduce(double* buf, int64_t n);
   void allreduce_from(const double* send, double* recv, int64_t n);   // out of place (send == recv: in place)
   double* scratch_slots() { return slots_.d(); }
@@ -292,7 +212,7 @@ class Engine {
   void par2_update_C(int m, const aoadmm_options& opt);
   void par2_prepare_C_coupled(int m, int ctype, const aoadmm_options& opt);
   void par2_objective_enqueue(TensorInfo& t);
-  // sparse slabs: one pass over the nonzeros (pos 0: the row-sorted copy, 1: the column-sorted copy), counted in kstats_[3]
+  // sparse slabs: one pass over the nonzeros (pos 0: the row-sorted copy, 1: the column-sorted copy), counted in timers_.stats[3]
   void par2s_pass(Par2Block& b, int pos, const CooFactor& f, double* out, int64_t ldOut);
   void par2s_rhs_A(TensorInfo& t, double* out);     // out (I x R) = sum_nnz x * B(g,:) .* C(k(g),:)
   void par2s_ensure_Y(TensorInfo& t);               // Y = Xcat' * A for the current A (cached by its version)
@@ -319,13 +239,8 @@ class Engine {
   bool allow_xp_ = true;  // options.hip.no_permuted_copy
   DevBuf atbws_;
   DevBuf staging_;
-  std::vector<hipEvent_t> event_pool_;   // timing events are recycled: creating two per tensor pass cost host time in the loop
-  hipEvent_t take_event();
-  void fold_finished(KernelStats& ks);
-  KernelStats kstats_[4];   // [0] streaming contraction, [1] leading-mode contraction, [2] reductions over T, [3] sparse MTTKRP and the passes over sparse PARAFAC2 slabs
+  LaunchTimers timers_;   // event pool and kernel statistics (cpblock.h)
   int prepared_mode_ = -1;  // mode whose MTTKRP + system build were enqueued ahead (prepare_next_first_mode)
-  bool profile_ = true;
-  bool profile_reductions_ = false;   // switched on by the first kernel_stats(2, ...) call: two more events per reduction
   ncclComm_t comm_ = nullptr;
   mutable std::mutex comm_mu_;          // comm_ / aborted_ against comm_abort() from another worker thread
   std::atomic<bool> aborted_{false};
@@ -338,9 +253,6 @@ class Engine {
 
   AdmmCtl* ctl_of_mode(int m) { return ctls_.as<AdmmCtl>() + m; }
   AdmmCtl* ctl_of_coupling(int c) { return ctls_.as<AdmmCtl>() + n_modes_ + c; }
-  void sparse_mttkrp(CpBlock& b, int pos, const FactorRef* facs, int R, double scale, double* out, int64_t ldOut);
-  void timed_contract(const void* X, int prec, const ContractPlan& pl, const double* F, int64_t ldF,
-                      void* frag, void* T);
 };
 
 }  // namespace aoadmm

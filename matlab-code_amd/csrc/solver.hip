@@ -50,9 +50,9 @@ Engine::Engine(int device) : device_(device) {
 
 Engine::~Engine() {
   (void)hipSetDevice(device_);
-  for (auto& ks : kstats_)
+  for (auto& ks : timers_.stats)
     for (auto& pr : ks.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  for (hipEvent_t e : event_pool_) (void)hipEventDestroy(e);
+  for (hipEvent_t e : timers_.pool) (void)hipEventDestroy(e);
   if (comm_) (void)ncclCommDestroy(comm_);
   if (side_ev_) (void)hipEventDestroy(side_ev_);
   if (side_) (void)hipStreamDestroy(side_);
@@ -511,76 +511,6 @@ void Engine::model_end() {
 // ---------------------------------------------------------------------------
 // data
 // ---------------------------------------------------------------------------
-static int64_t pad_of(int prec, int64_t n) { return round_up(n, prec == AOADMM_PREC_F32 ? 4 : 2); }
-static size_t blocked_bytes(int64_t M, int64_t C, size_t es) { return (size_t)round_up(M, kRowBlockElems) * C * es; }
-
-void Engine::block_upload(CpBlock& b, int nd, const int64_t* dims, const double* host, int prec, int64_t row0,
-                          int64_t local_rows, const double* full_array) {
-  AO_REQUIRE(nd >= 2 && nd <= 8, "tensor order %d unsupported", nd);
-  AO_REQUIRE(prec == AOADMM_PREC_F64 || prec == AOADMM_PREC_F32, "bad precision id %d", prec);
-  AO_REQUIRE(row0 >= 0 && local_rows > 0 && row0 + local_rows <= dims[0], "bad row block [%lld,+%lld) of %lld",
-             (long long)row0, (long long)local_rows, (long long)dims[0]);
-  AO_HIP(hipSetDevice(device_));
-  b.nd = nd;
-  b.full0 = dims[0];
-  b.row0 = row0;
-  b.dims[0] = local_rows;
-  int64_t ncols = 1;
-  for (int i = 1; i < nd; ++i) { b.dims[i] = dims[i]; ncols *= dims[i]; }
-  b.X.prec = prec; b.X.nd = nd;
-  for (int i = 0; i < nd; ++i) b.X.dims[i] = b.dims[i];
-  b.X.pad0 = pad_of(prec, local_rows);
-  b.X.data.alloc((size_t)b.X.elems_padded() * b.X.elem_size());
-  // host block layout: local_rows x ncols column-major (the caller extracted its rows)
-  const int64_t chunk_cols = std::max<int64_t>(1, (int64_t)(64ll << 20) / local_rows);   // ~512 MB of doubles
-  staging_.ensure((size_t)std::min(chunk_cols, ncols) * local_rows * sizeof(double));
-  for (int64_t c0 = 0; c0 < ncols; c0 += chunk_cols) {
-    const int64_t nc = std::min(chunk_cols, ncols - c0);
-    AO_HIP(hipMemcpyAsync(staging_.p, host + c0 * local_rows, (size_t)nc * local_rows * sizeof(double),
-                          hipMemcpyHostToDevice, stream_));
-    pad_convert(b.X.data.p, prec, b.X.pad0, staging_.d(), local_rows, nc, c0, stream_);
-    AO_HIP(hipStreamSynchronize(stream_));
-  }
-  if (nd == 2) {
-    // transposed copy for the second mode (matrices are small next to tensors)
-    b.Xt.prec = prec; b.Xt.nd = 2;
-    b.Xt.dims[0] = dims[1]; b.Xt.dims[1] = local_rows;
-    b.Xt.pad0 = pad_of(prec, dims[1]);
-    b.Xt.data.alloc((size_t)b.Xt.pad0 * local_rows * b.Xt.elem_size());
-    AO_REQUIRE(ncols * local_rows <= (int64_t)(1ll << 28), "matrix block too large for the transposed copy");
-    staging_.ensure((size_t)ncols * local_rows * sizeof(double));
-    AO_HIP(hipMemcpyAsync(staging_.p, host, (size_t)ncols * local_rows * sizeof(double), hipMemcpyHostToDevice, stream_));
-    transpose_convert(b.Xt.data.p, prec, b.Xt.pad0, staging_.d(), local_rows, ncols, stream_);
-    AO_HIP(hipStreamSynchronize(stream_));
-  }
-  b.has_data = true;
-  b.x_released = false;
-  b.cached_mode = -1;
-  b.has_xp = false; b.xp_refused = false; b.has_xq = false; b.xq_refused = false; b.has_xc = false; b.xc_refused = false;
-  b.xp_ksharded = false;
-  if (nd == 3 && full_array != nullptr) {             // the caller holds the whole tensor: mode-3 slab for the mode-1 pass
-    int64_t k0 = 0, kloc = 0;
-    if (want_ksharded_xp(b, dims[2], &k0, &kloc)) {
-      const int64_t I = dims[0], J = dims[1], Ipf = pad_of(prec, I);
-      DevBuf slab;
-      slab.alloc((size_t)Ipf * J * kloc * b.X.elem_size());
-      const double* src = full_array + (size_t)I * J * k0;      // X(:, :, k0 : k0+kloc) is contiguous
-      const int64_t ncs = J * kloc;
-      const int64_t cc = std::max<int64_t>(1, (int64_t)(64ll << 20) / I);
-      staging_.ensure((size_t)std::min(cc, ncs) * I * sizeof(double));
-      for (int64_t c0 = 0; c0 < ncs; c0 += cc) {
-        const int64_t nc = std::min(cc, ncs - c0);
-        AO_HIP(hipMemcpyAsync(staging_.p, src + c0 * I, (size_t)nc * I * sizeof(double), hipMemcpyHostToDevice, stream_));
-        pad_convert(slab.p, prec, Ipf, staging_.d(), I, nc, c0, stream_);
-        AO_HIP(hipStreamSynchronize(stream_));
-      }
-      adopt_ksharded_xp(b, slab.p, k0, kloc);
-      AO_HIP(hipStreamSynchronize(stream_));          // slab is a local
-    }
-  }
-  if (nd == 3) { (void)ensure_permuted_copy2(b); (void)ensure_blocked_copy(b); }   // one-off set-up cost belongs to the upload
-}
-
 void Engine::tensor_upload(int p, const double* data, int prec, int64_t row0, int64_t local_rows) {
   require_usable();
   AO_REQUIRE(model_done_, "call aoadmm_model_end first");
@@ -589,6 +519,8 @@ void Engine::tensor_upload(int p, const double* data, int prec, int64_t row0, in
   AO_REQUIRE(!t.par2, "tensor %d is PARAFAC2: use aoadmm_par2_slab_upload", p);
   AO_REQUIRE(local_rows < 0 || !t.blk.sparse, "tensor %d holds sparse data: a row block cannot replace it (use aoadmm_tensor_upload)", p);
   if (t.blk.sparse) { t.blk.coo.clear(); t.blk.sparse = false; }   // a dense upload replaces the sparse form
+  AO_HIP(hipSetDevice(device_));
+  const BlockCtx cx = block_ctx();
   int64_t dims[8];
   for (int i = 0; i < t.nmodes; ++i) dims[i] = modes_[t.modes[i]].rows;
   if (local_rows < 0) {            // full array given: every rank keeps its block of rows
@@ -600,17 +532,17 @@ void Engine::tensor_upload(int p, const double* data, int prec, int64_t row0, in
     AO_REQUIRE(per * (world_ - 1) < I, "tensor %d: first mode of %lld rows cannot be split over %d ranks (the last rank would own no rows)",
                p, (long long)I, world_);
     if (world_ == 1) {
-      block_upload(t.blk, t.nmodes, dims, data, prec, 0, I);
+      block_upload(cx, t.blk, t.nmodes, dims, data, prec, 0, I);
     } else {
       int64_t ncols = 1;
       for (int i = 1; i < t.nmodes; ++i) ncols *= dims[i];
       std::vector<double> blk((size_t)local_rows * ncols);
       for (int64_t c = 0; c < ncols; ++c)
         std::memcpy(&blk[(size_t)c * local_rows], data + c * I + row0, (size_t)local_rows * sizeof(double));
-      block_upload(t.blk, t.nmodes, dims, blk.data(), prec, row0, local_rows, data);
+      block_upload(cx, t.blk, t.nmodes, dims, blk.data(), prec, row0, local_rows, data);
     }
   } else {
-    block_upload(t.blk, t.nmodes, dims, data, prec, row0, local_rows);
+    block_upload(cx, t.blk, t.nmodes, dims, data, prec, row0, local_rows);
   }
   t.normsq_valid = false;
 }
@@ -630,7 +562,7 @@ void Engine::tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const do
   CooBlock coo;
   coo_build(coo, t.nmodes, dims, nnz, subs, vals, stream_);     // validates before anything of the old form is dropped
   CpBlock& b = t.blk;
-  drop_permuted_copies(b);
+  drop_pass_copies(b);
   b.X.data.release(); b.Xt.data.release();
   b.emkr.release(); b.emkr2.release(); b.T.release(); b.frag.release(); b.scratch.release(); b.ft.release();
   b.tmpA.release(); b.tmpB.release(); b.mask.release(); b.maskT.release();
@@ -640,10 +572,8 @@ void Engine::tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const do
   b.nd = t.nmodes;
   for (int i = 0; i < t.nmodes; ++i) b.dims[i] = dims[i];
   b.full0 = dims[0]; b.row0 = 0;
-  b.has_data = true; b.has_mask = false; b.x_released = false;
-  b.cached_mode = -1;
-  b.has_xp = b.xp_refused = b.has_xq = b.xq_refused = b.has_xc = b.xc_refused = false;
-  b.xp_ksharded = false;
+  b.has_mask = false;
+  b.reset_derived();
   t.normsq_valid = false;
 }
 
@@ -732,25 +662,21 @@ void Engine::tensor_synth(int p, int rank, uint64_t seed, double noise, int prec
   const double nsq = h[0] + 2.0 * sigma * h[2] + sigma * sigma * h[1];
   synth_write(b.X.data.p, prec, A.d(), B.d(), C.d(), a, sigma, 1.0 / std::sqrt(nsq), stream_);
   AO_HIP(hipStreamSynchronize(stream_));
-  b.has_data = true;
-  b.x_released = false;
-  b.cached_mode = -1;
-  b.has_xp = false; b.xp_refused = false; b.has_xq = false; b.xq_refused = false; b.has_xc = false; b.xc_refused = false;
-  b.xp_ksharded = false;
+  b.reset_derived();
+  const BlockCtx cx = block_ctx();
   {
     int64_t k0 = 0, kloc = 0;
-    if (want_ksharded_xp(b, K, &k0, &kloc)) {        // this rank's third-mode slab of the SAME tensor, all rows
+    if (want_ksharded_xp(cx, b, K, &k0, &kloc)) {        // this rank's third-mode slab of the SAME tensor, all rows
       SynthArgs ak = a;
       ak.I_loc = I; ak.I_pad = pad_of(prec, I); ak.row0 = 0; ak.k0 = k0; ak.K_loc = kloc;
       DevBuf slab;
       slab.alloc((size_t)ak.I_pad * J * kloc * b.X.elem_size());
       synth_write(slab.p, prec, A.d(), B.d(), C.d(), ak, sigma, 1.0 / std::sqrt(nsq), stream_);
-      adopt_ksharded_xp(b, slab.p, k0, kloc);
+      adopt_ksharded_xp(cx, b, slab.p, k0, kloc);
       AO_HIP(hipStreamSynchronize(stream_));          // slab is a local
     }
   }
-  (void)ensure_permuted_copy2(b);                    // set-up cost of the data, like the generation itself
-  (void)ensure_blocked_copy(b);
+  (void)ensure_pass_copy(cx, b, 1); (void)ensure_pass_copy(cx, b, 2);   // set-up cost of the data, like the generation itself
   AO_HIP(hipStreamSynchronize(stream_));
   t.normsq_valid = false;
 }
@@ -795,7 +721,7 @@ void Engine::tensor_mask_upload(int p, const uint8_t* mask) {
   }
   AO_HIP(hipStreamSynchronize(stream_));
   b.has_mask = true;
-  drop_permuted_copies(b);                           // the imputation would have to update them too
+  drop_pass_copies(b);                               // the imputation would have to update them too
   t.normsq_valid = false;
 }
 
@@ -808,8 +734,6 @@ bool Engine::has_missing() const {
 double* Engine::em_slot(int p) const {
   return slots_.d() + n_modes_ * (kSlotsPerMode + kResidPerMode) + 2 * n_tensors_ + 16 + 4 * p;
 }
-
-static int next_update_distance(int pos, int c, const int* seq, int n);
 
 // One EM pass over tensor p with the current factors: {num, den, obs_res, obs_x2} -> em_slot(p), all-reduced
 // over the row shards; update = 1 also overwrites the missing entries with the model (:416-435).
@@ -862,7 +786,7 @@ void Engine::em_pass_enqueue(int p, int update, bool fuse_next_pass) {
   ContractPlan fpl;
   FactorRef facs[8];
   if (fuse_next_pass && update && b.nd == 3 && em_cp_can_fuse(a, b.X.prec) && b.dims[1] <= 65535 &&
-      b.dims[2] <= 65535 && !small_direct(b, a.R)) {
+      b.dims[2] <= 65535 && !small_direct(sharded(), b, a.R)) {
     for (int i = 0; i < t.nmodes; ++i) facs[i] = factor_ref(modes_[t.modes[i]]);
     const std::vector<int> seq = update_sequence(p);
     const int pos0 = seq.empty() ? 0 : seq[0];
@@ -1026,72 +950,18 @@ void Engine::state_get(int field, int index, int slab, double* host, int64_t row
 // ---------------------------------------------------------------------------
 // MTTKRP engine
 // ---------------------------------------------------------------------------
-hipEvent_t Engine::take_event() {
-  if (event_pool_.empty()) {
-    for (int i = 0; i < 64; ++i) {
-      hipEvent_t e = nullptr;
-      AO_HIP(hipEventCreate(&e));
-      event_pool_.push_back(e);
-    }
-  }
-  hipEvent_t e = event_pool_.back();
-  event_pool_.pop_back();
-  return e;
-}
-
-void Engine::timed_contract(const void* X, int prec, const ContractPlan& pl, const double* F, int64_t ldF,
-                            void* frag, void* T) {
-  KernelStats& ks = kstats_[pl.lead ? 1 : 0];
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  static const bool no_events = getenv("AOADMM_NO_PASS_EVENTS") != nullptr;   // measurement only (tools/gap_analysis.py)
-  // Every 4th pass is bracketed by events (the three kinds of pass alternate with period 3, so the sample cycles through
-  // them): the records cost ~4 us of launch gap on each side of a pass -- nothing at 2000^3, 1 % of an iteration at one
-  // rank's share of 8 GPUs.  kernel_stats() returns the mean of the timed launches times the launch count.
-  // AOADMM_PASS_EVENT_EVERY=1 times every pass (the profile tools).
-  static const int every = [] { const char* e = getenv("AOADMM_PASS_EVENT_EVERY"); const int v = e ? atoi(e) : 4; return v < 1 ? 1 : v; }();
-  if (profile_ && !no_events && ks.launches % every == 0) {
-    if (ks.pending.size() >= 512) fold_finished(ks);     // a long solve never holds more than a few hundred events
-    if (ks.pending.size() < 4096) {
-      e0 = take_event();
-      e1 = take_event();
-    }
-  }
-  launch_contract(X, prec, pl, F, ldF, frag, T, stream_, e0, e1);
-  if (e0) { ks.pending.emplace_back(e0, e1); ks.timed++; }
-  ks.launches++;
-  ks.bytes += pl.algorithmic_bytes(prec);
-  ks.flops += pl.flops();
-}
-
-// pairs whose second event has completed are added to ks.ms and their events go back to the pool (no synchronisation)
-void Engine::fold_finished(KernelStats& ks) {
-  size_t keep = 0;
-  for (size_t i = 0; i < ks.pending.size(); ++i) {
-    auto& pr = ks.pending[i];
-    float t = 0.f;
-    if (hipEventQuery(pr.second) == hipSuccess && hipEventElapsedTime(&t, pr.first, pr.second) == hipSuccess) {
-      ks.ms += t;
-      event_pool_.push_back(pr.first);
-      event_pool_.push_back(pr.second);
-    } else {
-      ks.pending[keep++] = pr;
-    }
-  }
-  ks.pending.resize(keep);
-}
-
 void Engine::kernel_stats(int which, int reset, double* ms, int64_t* launches, double* bytes, double* flops) {
   AO_REQUIRE(which >= 0 && which <= 3, "kernel_stats: which must be 0, 1, 2 or 3");
-  if (which == 2) profile_reductions_ = true;
+  if (which == 2) timers_.profile_reductions = true;
   AO_HIP(hipSetDevice(device_));
   AO_HIP(hipStreamSynchronize(stream_));
-  KernelStats& ks = kstats_[which];
+  KernelStats& ks = timers_.stats[which];
   for (auto& pr : ks.pending) {
     float t = 0.f;
     AO_HIP(hipEventElapsedTime(&t, pr.first, pr.second));
     ks.ms += t;
-    event_pool_.push_back(pr.first);
-    event_pool_.push_back(pr.second);
+    timers_.pool.push_back(pr.first);
+    timers_.pool.push_back(pr.second);
   }
   ks.pending.clear();
   // launches that went untimed (event budget exhausted) count at the mean of the timed ones, so ms / launches stays
@@ -1101,182 +971,6 @@ void Engine::kernel_stats(int which, int reset, double* ms, int64_t* launches, d
   if (bytes) *bytes = ks.bytes;
   if (flops) *flops = ks.flops;
   if (reset) { ks.ms = 0; ks.launches = 0; ks.timed = 0; ks.bytes = 0; ks.flops = 0; }
-}
-
-// distance (in updates) until tensor position `c` is updated again after position `pos`
-static int next_update_distance(int pos, int c, const int* seq, int n) {
-  if (!seq || n <= 0) return c;            // no information: prefer the last mode
-  int at = -1;
-  for (int i = 0; i < n; ++i)
-    if (seq[i] == pos) at = i;
-  if (at < 0) return c;
-  for (int d = 1; d <= n; ++d)
-    if (seq[(at + d) % n] == c) return d;
-  return n + 1;                              // never updated
-}
-
-// Tensor pass for a 3-way block: makes b.T hold the partial contraction that serves an MTTKRP for tensor
-// position `pos` (a cached one is reused while its factor is unchanged).
-// Second resident copy with the first mode last (see CpBlock::Xp).  Built lazily; refused when the mask of an EM
-// problem would have to be kept in sync, when the caller opted out, or when HBM cannot hold it.
-
-static bool room_for(size_t bytes) {
-  size_t free_b = 0, total_b = 0;
-  return hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= bytes + (size_t)(4ull << 30);
-}
-
-// Mode-3 sharding of the mode-1 pass's copy: every rank must reach the same verdict (the collectives that follow the
-// pass differ: own rows of mode 3 instead of partial sums).
-bool Engine::want_ksharded_xp(const CpBlock& b, int64_t K, int64_t* k0, int64_t* kloc) const {
-  if (!sharded() || world_ <= 1 || !allow_xp_ || b.has_mask || b.nd != 3) return false;
-  const int64_t per = cdiv(K, world_);
-  if (per * (world_ - 1) >= K) return false;          // some rank would own no slab
-  *k0 = per * rank_;
-  *kloc = std::min<int64_t>(K, *k0 + per) - *k0;
-  return true;
-}
-void Engine::adopt_ksharded_xp(CpBlock& b, const void* slab, int64_t k0, int64_t kloc) {
-  const int64_t Ifull = b.full0, J = b.dims[1];
-  const int prec = b.X.prec;
-  const int64_t Ipf = round_up(Ifull, prec == AOADMM_PREC_F32 ? 4 : 2);
-  const int64_t Jp = round_up(J, prec == AOADMM_PREC_F32 ? 4 : 2);
-  b.Xp.alloc(blocked_bytes(Jp * kloc, Ifull, b.X.elem_size()));
-  b.Jp = Jp;
-  AO_REQUIRE(block_layout_copy(slab, b.Xp.p, 1, prec, Ifull, Ipf, J, kloc, Jp, stream_), "tensor mode too long for the copy kernels");
-  b.has_xp = true; b.xp_ksharded = true; b.xp_k0 = k0; b.xp_kloc = kloc;
-}
-
-bool Engine::ensure_permuted_copy(CpBlock& b) {
-  if (b.has_xp) return true;
-  if (b.xp_refused || !allow_xp_ || b.has_mask || b.nd != 3) return false;
-  const int64_t I = b.dims[0], J = b.dims[1], K = b.dims[2];
-  const int64_t Jp = round_up(J, b.X.prec == AOADMM_PREC_F32 ? 4 : 2);
-  const size_t bytes = blocked_bytes(Jp * K, I, b.X.elem_size());
-  if (!room_for(bytes)) { b.xp_refused = true; return false; }
-  b.Xp.alloc(bytes);
-  b.Jp = Jp;
-  if (!block_layout_copy(b.X.data.p, b.Xp.p, 1, b.X.prec, I, b.X.pad0, J, K, Jp, stream_)) {
-    b.Xp.release(); b.xp_refused = true; return false;
-  }
-  b.has_xp = true;
-  return true;
-}
-
-// Xq: rows (k, i), columns j -- built from X directly
-bool Engine::ensure_permuted_copy2(CpBlock& b) {
-  if (b.has_xq) return true;
-  if (b.xq_refused || !ensure_permuted_copy(b)) return false;
-  const int64_t I = b.dims[0], J = b.dims[1], K = b.dims[2];
-  const int64_t Kp = round_up(K, b.X.prec == AOADMM_PREC_F32 ? 4 : 2);
-  const size_t bytes = blocked_bytes(Kp * I, J, b.X.elem_size());
-  if (!room_for(bytes)) { b.xq_refused = true; return false; }
-  b.Xq.alloc(bytes);
-  b.Kp = Kp;
-  if (!block_layout_copy(b.X.data.p, b.Xq.p, 2, b.X.prec, I, b.X.pad0, J, K, Kp, stream_)) {
-    b.Xq.release(); b.xq_refused = true; return false;
-  }
-  b.has_xq = true;
-  return true;
-}
-
-// Xc: the rows of X itself, row-blocked (the pass that contracts mode 3)
-bool Engine::ensure_blocked_copy(CpBlock& b) {
-  if (b.has_xc) return true;
-  if (b.xc_refused || !allow_xp_ || b.has_mask || b.nd != 3) return false;
-  const int64_t I = b.dims[0], J = b.dims[1], K = b.dims[2];
-  const size_t bytes = blocked_bytes(b.X.pad0 * J, K, b.X.elem_size());
-  if (!room_for(bytes)) { b.xc_refused = true; return false; }
-  b.Xc.alloc(bytes);
-  if (!block_layout_copy(b.X.data.p, b.Xc.p, 0, b.X.prec, I, b.X.pad0, J, K, 0, stream_)) {
-    b.Xc.release(); b.xc_refused = true; return false;
-  }
-  b.has_xc = true;
-  return true;
-}
-// Releases Z.object{p} in its natural layout once every tensor pass has its own resident copy.  A 2000^3 double array is
-// 64 GB: with the natural array and three copies a MATLAB caller sat at 256 of 288 GB before any workspace.  Policy:
-// AOADMM_RELEASE_NATURAL=1 always, =0 never, default: when less HBM is free than the array itself occupies.  Afterwards
-// Z.miss cannot be attached without uploading the data again, and aoadmm_resident_unfold_gram answers
-// AOADMM_ERR_UNSUPPORTED (the caller falls back to the host-array form).
-void Engine::maybe_release_natural(TensorInfo& t) {
-  CpBlock& b = t.blk;
-  if (b.sparse || b.x_released || b.nd != 3 || !(b.has_xc && b.has_xp && b.has_xq) || b.has_mask || !t.normsq_valid || !b.X.data.p) return;
-  const char* pe = getenv("AOADMM_RELEASE_NATURAL");   // read per solve (the test suite switches it inside one process)
-  const int policy = pe ? (atoi(pe) != 0 ? 1 : -1) : 0;
-  if (policy < 0) return;
-  if (policy == 0) {
-    size_t free_b = 0, total_b = 0;
-    const size_t mine = (size_t)b.X.elems_padded() * b.X.elem_size();
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b >= mine) return;
-  }
-  AO_HIP(hipStreamSynchronize(stream_));             // the copies were built from it on this stream
-  b.X.data.release();
-  b.x_released = true;
-}
-
-void Engine::drop_permuted_copies(CpBlock& b) {
-  if (b.has_xp) { b.Xp.release(); b.has_xp = false; b.xp_ksharded = false; b.cached_mode = -1; }
-  if (b.has_xq) { b.Xq.release(); b.has_xq = false; b.cached_mode = -1; }
-  if (b.has_xc) { b.Xc.release(); b.has_xc = false; b.cached_mode = -1; }
-}
-
-void Engine::ensure_contraction(CpBlock& b, int pos, const FactorRef* facs, int R, bool use_cache,
-                                const int* update_seq, int nseq) {
-  const int prec = b.X.prec;
-  const int64_t I = b.dims[0], Ip = b.X.pad0, J = b.dims[1], K = b.dims[2];
-  if (b.x_released) use_cache = true;                  // only the pass copies are resident (maybe_release_natural)
-  const bool hit = use_cache && b.cached_mode >= 0 && b.cached_mode != pos &&
-                   facs[b.cached_mode].version == b.cached_version;
-  if (hit) return;
-  // which mode to contract: any mode but `pos`; prefer the one whose factor stays unchanged longest so
-  // that the partial contraction also serves the next update (cycle 3->{1,2}, 2->{3,1}, 1->{2,3}:
-  // 1.5 tensor reads per outer iteration).  The leading mode needs the LDS-transposed kernel (fp32 only).
-  int c = -1, best = -1;
-  for (int cand = 2; cand >= 0; --cand) {
-    if (cand == pos) continue;
-    // contracting mode 1 needs the permuted copy (any precision) or the LDS-transposed kernel (fp32 only)
-    if (cand == 0 && !(use_cache && (prec == AOADMM_PREC_F32 || ensure_permuted_copy(b)))) continue;
-    const int dist = next_update_distance(pos, cand, update_seq, nseq);
-    if (dist > best) { best = dist; c = cand; }
-  }
-  ContractPlan pl;
-  const double* Fc = facs[c].p;
-  // a pass on a row-blocked copy: one "batch" per row block, each a contiguous MB x C matrix
-  auto blocked_plan = [&](int64_t M, int64_t C) {
-    const int64_t MB = kRowBlockElems;
-    return make_plan(round_up(M, MB) / MB, MB * C, MB, MB, C, R, prec);
-  };
-  if (c == 2) {
-    if (use_cache && ensure_blocked_copy(b)) {
-      pl = blocked_plan(Ip * J, K);
-      pl.on_xc = true;
-    } else {
-      pl = make_plan(1, 0, Ip * J, Ip * J, K, R, prec);
-    }
-  } else if (c == 1) {
-    if (use_cache && ensure_permuted_copy2(b)) {
-      // Xq: rows (k, i), columns j -> one streaming pass instead of K batches of an I x J matrix
-      pl = blocked_plan(b.Kp * I, J);
-      pl.on_xq = true;
-    } else {
-      pl = make_plan(K, Ip * J, Ip, Ip, J, R, prec);
-    }
-  } else {
-    Fc = facs[0].p + (sharded() ? b.row0 : 0);
-    if (ensure_permuted_copy(b)) {
-      // Xp: rows (j, k), columns i -> the register-streaming contraction.  With a communicator the copy holds this
-      // rank's slab of mode 3 and ALL of mode 1 (CpBlock::xp_ksharded): a complete T of 1/N the size
-      if (b.xp_ksharded) { pl = blocked_plan(b.Jp * b.xp_kloc, b.full0); Fc = facs[0].p; }
-      else pl = blocked_plan(b.Jp * K, I);
-      pl.on_xp = true;
-    } else {
-      pl = make_lead_plan(J * K, Ip, I, R);
-    }
-  }
-  b.T.ensure(pl.t_bytes()); b.frag.ensure(pl.frag_bytes(prec));
-  timed_contract(pl.on_xp ? b.Xp.p : (pl.on_xq ? b.Xq.p : (pl.on_xc ? b.Xc.p : b.X.data.p)), prec, pl, Fc, facs[c].ld, b.frag.p,
-                 b.T.p);
-  b.cached_mode = c; b.cached_version = facs[c].version; b.plan = pl;
 }
 
 // The first tensor pass of the next outer iteration does not depend on the host's stopping decision, so
@@ -1289,240 +983,20 @@ bool Engine::prefetch_next_contraction(const aoadmm_options& opt) {
         const ModeInfo& mi = modes_[m];
         if (mi.coupling != cid || mi.tensor != p) continue;
         TensorInfo& t = tensors_[p];                      // first mode the next iteration updates
-        if (t.par2 || t.blk.sparse || t.blk.nd != 3 || small_direct(t.blk, mi.R)) return false;
+        if (t.par2 || t.blk.sparse || t.blk.nd != 3 || small_direct(sharded(), t.blk, mi.R)) return false;
         FactorRef facs[8];
         for (int i = 0; i < t.nmodes; ++i) {
           const ModeInfo& o = modes_[t.modes[i]];
           facs[i] = factor_ref(o);
         }
         std::vector<int> seq = update_sequence(p);
-        const int64_t before = kstats_[0].launches + kstats_[1].launches;
-        ensure_contraction(t.blk, mi.pos, facs, mi.R, true, seq.data(), (int)seq.size());
-        return kstats_[0].launches + kstats_[1].launches > before;     // false: the cached pass still serves
+        const KernelStats* ks = timers_.stats;
+        const int64_t before = ks[0].launches + ks[1].launches;
+        ensure_contraction(block_ctx(), t.blk, mi.pos, facs, mi.R, true, seq.data(), (int)seq.size());
+        return ks[0].launches + ks[1].launches > before;     // false: the cached pass still serves
       }
   }
   return false;
-}
-
-void Engine::block_mttkrp(CpBlock& b, int pos, const FactorRef* facs, int R, double scale, double* out,
-                          int64_t ldOut, bool use_cache, const int* update_seq, int nseq, bool collective,
-                          bool tensor_pass, const SysBuild* sys, bool* sys_done) {
-  if (sys_done) *sys_done = false;
-  AO_REQUIRE(b.has_data, "tensor has no data");
-  AO_REQUIRE(pos >= 0 && pos < b.nd, "mttkrp: mode %d out of range", pos);
-  if (b.sparse) {                  // complete on every rank: no own-rows buffer, no collective, no cache, no rider
-    sparse_mttkrp(b, pos, facs, R, scale, out, ldOut);
-    return;
-  }
-  const int prec = b.X.prec;
-  const int64_t I = b.dims[0], Ip = b.X.pad0;
-  const bool sharded = collective && this->sharded();
-  double* out_local = out;
-  const int64_t out_rows_full = (pos == 0) ? b.full0 : b.dims[pos];
-  // "Every rank fills its own rows of a zeroed buffer; the all-reduce is the all-gather": the zeroed buffer is a send
-  // buffer of the block that is cleared ONCE -- the rows of other ranks are never written, the own rows are overwritten
-  // by every MTTKRP -- and the all-reduce goes from it into `out` (a fill in front of every such MTTKRP was 5 us on the
-  // critical path, two per outer iteration).
-  const double* send = nullptr;
-  int64_t ld_local = ldOut;
-  auto own_rows_buffer = [&](int which, int64_t rows_full, int64_t row_first) {
-    DevBuf& ob = b.own[which];
-    const size_t need = (size_t)rows_full * R * sizeof(double);
-    if (b.own_bytes[which] != need || b.own_row0[which] != row_first) {    // (another rank's rows would stay behind)
-      if (b.own_bytes[which] != need) ob.alloc(need);
-      AO_HIP(hipMemsetAsync(ob.p, 0, need, stream_));
-      b.own_bytes[which] = need;
-      b.own_row0[which] = row_first;
-    }
-    send = ob.d();
-    ld_local = rows_full;
-    out_local = ob.d() + row_first;
-  };
-  if (sharded && pos == 0) own_rows_buffer(0, out_rows_full, b.row0);
-  const double* F0 = facs[0].p + (sharded ? b.row0 : 0);     // local rows of the first factor
-
-  if (!tensor_pass && small_direct(b, R)) {
-    // tiny block: the whole MTTKRP in one launch (contract.hip small_mttkrp_k), no partial-contraction cache
-    const int64_t J = b.dims[1], K = b.nd == 3 ? b.dims[2] : 1;
-    const int64_t st[3] = {1, Ip, Ip * J};
-    const int64_t ext[3] = {I, J, K};
-    int ia = pos == 0 ? 1 : 0, ib = pos == 2 ? 1 : 2;
-    SmallMttkrp sm;
-    sm.X = b.X.data.p;
-    sm.sn = st[pos]; sm.sa = st[ia]; sm.Na = (int)ext[ia];
-    sm.Fa = facs[ia].p; sm.lda = facs[ia].ld;
-    if (b.nd == 3) { sm.sb = st[ib]; sm.Nb = (int)ext[ib]; sm.Fb = facs[ib].p; sm.ldb = facs[ib].ld; }
-    else { sm.sb = 0; sm.Nb = 1; sm.Fb = nullptr; sm.ldb = 0; }
-    sm.R = R; sm.scale = scale; sm.out = out; sm.ldOut = ldOut;
-    const bool rode = small_mttkrp(sm, prec, ext[pos], stream_, sys);
-    if (sys_done) *sys_done = rode;
-    return;
-  }
-  if (b.nd == 2) {
-    const int64_t J = b.dims[1];
-    if (pos == 0) {
-      ContractPlan pl = make_plan(1, 0, Ip, Ip, J, R, prec);
-      b.T.ensure(pl.t_bytes()); b.frag.ensure(pl.frag_bytes(prec));
-      timed_contract(b.X.data.p, prec, pl, facs[1].p, facs[1].ld, b.frag.p, b.T.p);
-      launch_t_to_colmajor(b.T.p, pl.tprec, pl.nchunk, pl.trows(), I, R, scale, out_local, ld_local, stream_);
-    } else {
-      const int64_t Jp = b.Xt.pad0;
-      ContractPlan pl = make_plan(1, 0, Jp, Jp, I, R, prec);
-      b.T.ensure(pl.t_bytes()); b.frag.ensure(pl.frag_bytes(prec));
-      timed_contract(b.Xt.data.p, prec, pl, F0, facs[0].ld, b.frag.p, b.T.p);
-      launch_t_to_colmajor(b.T.p, pl.tprec, pl.nchunk, pl.trows(), J, R, scale, out_local, ld_local, stream_);
-    }
-    b.cached_mode = -1;
-  } else if (b.nd == 3) {
-    const int64_t J = b.dims[1], K = b.dims[2];
-    ensure_contraction(b, pos, facs, R, use_cache, update_seq, nseq);
-    const int c = b.cached_mode;
-    const ContractPlan& pl = b.plan;
-    // the mode-1 pass on a copy sharded along mode 3: T(j, k in K_g, r) is complete; mode 3's output is this rank's rows
-    const bool ksh = sharded && pl.on_xp && b.xp_ksharded;
-    // T rows are (a + Apad*bb) with (a, bb) the two uncontracted modes in the order the pass's copy stores them:
-    // tensor order on X and Xp, (k, i) on Xq
-    int ia = c == 0 ? 1 : 0, ib = c == 2 ? 1 : 2;
-    if (pl.on_xq) { ia = 2; ib = 0; }
-    const int64_t ext[3] = {I, J, ksh ? b.xp_kloc : K};
-    const int64_t An = ext[ia], Bn = ext[ib];
-    const int64_t Apad = pl.on_xq ? b.Kp : (ia == 0 ? Ip : (pl.on_xp ? b.Jp : J));
-    // factor of a mode: the first mode's factor is addressed at this rank's rows (the third mode's too under `ksh`)
-    auto fac_p = [&](int m) { return m == 0 ? F0 : (m == 2 && ksh ? facs[2].p + b.xp_k0 : facs[m].p); };
-    auto fac_pT = [&](int m) -> const double* {
-      if (!facs[m].pT) return nullptr;
-      if (m == 2 && ksh) return facs[2].pT + b.xp_k0 * R;
-      return facs[m].pT + ((m == 0 && sharded) ? b.row0 * R : 0);
-    };
-    if (ksh && pos == 2) own_rows_buffer(1, K, b.xp_k0);   // own rows of the zeroed send buffer; the all-reduce is the all-gather
-    // the reduction over T is timed like the passes (kernel_stats slot 2): it reads all of T once
-    KernelStats& rs = kstats_[2];
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (profile_ && profile_reductions_) {
-      if (rs.pending.size() >= 512) fold_finished(rs);
-      if (rs.pending.size() < 4096) {
-        e0 = take_event();
-        e1 = take_event();
-        AO_HIP(hipEventRecord(e0, stream_));
-      }
-    }
-    if (pos == ia) {
-      b.scratch.ensure(reduce_outer_scratch_bytes(An, Bn, R));
-      b.ft.ensure(reduce_factor_scratch_bytes(Bn, R));
-      const bool rode = launch_reduce_outer(b.T.p, pl.tprec, pl.nchunk, pl.trows(), An, Apad, Bn, R, fac_p(ib), facs[ib].ld, scale,
-                                            out_local, ld_local, b.scratch.d(), b.ft.d(), stream_, fac_pT(ib), 0, sys);
-      if (sys_done) *sys_done = rode;
-    } else {
-      AO_REQUIRE(pos == ib, "internal: cached contraction cannot serve this mode");
-      b.ft.ensure(reduce_factor_scratch_bytes(An, R));
-      const bool rode = launch_reduce_inner(b.T.p, pl.tprec, pl.nchunk, pl.trows(), An, Apad, Bn, R, fac_p(ia), facs[ia].ld, scale,
-                                            out_local, ld_local, b.ft.d(), stream_, fac_pT(ia), 0, sys);
-      if (sys_done) *sys_done = rode;
-    }
-    if (e0) {
-      AO_HIP(hipEventRecord(e1, stream_));
-      rs.pending.emplace_back(e0, e1);
-      rs.timed++;
-    }
-    rs.launches++;
-    rs.bytes += (double)pl.t_bytes();
-  } else {
-    // N-way (N > 3): contract the last mode (the one before it when pos is last) on the matrix cores with all
-    // leading modes merged into the unfolding row, then fold the remaining modes one at a time over T: trailing
-    // modes with reduce_outer (down to pos), leading modes with reduce_inner (up to pos), each fold leaving a
-    // smaller T in the same [row][r] layout (fp64).  No partial-contraction reuse for these: N passes per iteration.
-    const int N = b.nd;
-    const int c = pos == N - 1 ? N - 2 : N - 1;
-    int64_t lead = Ip;                                  // merged size of the modes before c (first one padded)
-    for (int m = 1; m < c; ++m) lead *= b.dims[m];
-    ContractPlan pl = (c == N - 1) ? make_plan(1, 0, lead, lead, b.dims[c], R, prec)
-                                   : make_plan(b.dims[N - 1], lead * b.dims[c], lead, lead, b.dims[c], R, prec);
-    b.T.ensure(pl.t_bytes()); b.frag.ensure(pl.frag_bytes(prec));
-    timed_contract(b.X.data.p, prec, pl, c == 0 ? F0 : facs[c].p, facs[c].ld, b.frag.p, b.T.p);
-    // remaining modes in memory order, with their padded extents inside T
-    int rem[8], nrem = 0;
-    int64_t ext[8];
-    for (int m = 0; m < N; ++m)
-      if (m != c) { rem[nrem] = m; ext[nrem] = m == 0 ? Ip : b.dims[m]; ++nrem; }
-    const void* Tin = b.T.p;
-    int tprec = pl.tprec, nchunk = pl.nchunk;
-    int64_t trows = pl.trows();
-    int flip = 0;
-    auto tbuf = [&](int64_t rows) {
-      DevBuf& d = flip ? b.tmpB : b.tmpA;
-      flip ^= 1;
-      d.ensure((size_t)rows * R * sizeof(double));
-      return d.d();
-    };
-    // fold trailing modes above pos (last remaining mode first)
-    while (nrem > 1 && rem[nrem - 1] != pos) {
-      const int mb = rem[nrem - 1];
-      int64_t Arows = 1;
-      for (int q = 0; q < nrem - 1; ++q) Arows *= ext[q];
-      const bool last = nrem == 2;                      // after this fold only `pos` remains (it is rem[0])
-      double* dst = last ? out_local : tbuf(Arows);
-      const int64_t An = last ? (rem[0] == 0 ? I : b.dims[rem[0]]) : Arows;
-      b.scratch.ensure(reduce_outer_scratch_bytes(An, b.dims[mb], R));
-      b.ft.ensure(reduce_factor_scratch_bytes(b.dims[mb], R));
-      launch_reduce_outer(Tin, tprec, nchunk, trows, An, Arows, b.dims[mb], R, facs[mb].p, facs[mb].ld,
-                          last ? scale : 1.0, dst, last ? ld_local : 0, b.scratch.d(), b.ft.d(), stream_, nullptr, last ? 0 : 1);
-      if (last) { nrem = 1; break; }
-      Tin = dst; tprec = AOADMM_PREC_F64; nchunk = 1; trows = Arows;
-      --nrem;
-    }
-    // fold leading modes below pos (first remaining mode first)
-    while (nrem > 1) {
-      const int ma = rem[0];
-      int64_t Brows = 1;
-      for (int q = 1; q < nrem; ++q) Brows *= ext[q];
-      const bool last = nrem == 2;                      // after this fold only `pos` remains (it is rem[1])
-      double* dst = last ? out_local : tbuf(Brows);
-      const int64_t An = ma == 0 ? I : b.dims[ma];
-      b.ft.ensure(reduce_factor_scratch_bytes(An, R));
-      launch_reduce_inner(Tin, tprec, nchunk, trows, An, ext[0], Brows, R, ma == 0 ? F0 : facs[ma].p, facs[ma].ld,
-                          last ? scale : 1.0, dst, last ? ld_local : 0, b.ft.d(), stream_, nullptr, last ? 0 : 1);
-      Tin = dst; tprec = AOADMM_PREC_F64; nchunk = 1; trows = Brows;
-      for (int q = 0; q + 1 < nrem; ++q) { rem[q] = rem[q + 1]; ext[q] = ext[q + 1]; }
-      --nrem;
-    }
-    b.cached_mode = -1;
-  }
-  if (sharded) {
-    if (send) {                                        // from the block's own-rows send buffer (ld = rows) into `out`
-      if (ldOut == out_rows_full) allreduce_from(send, out, out_rows_full * R);
-      else for (int r = 0; r < R; ++r) allreduce_from(send + out_rows_full * r, out + ldOut * r, out_rows_full);
-    } else if (ldOut == out_rows_full) allreduce(out, out_rows_full * R);
-    else for (int r = 0; r < R; ++r) allreduce(out + ldOut * r, out_rows_full);
-  }
-}
-
-// MTTKRP of a sparse block (sparse.hip): factors gathered through their row-major copy when it is current
-void Engine::sparse_mttkrp(CpBlock& b, int pos, const FactorRef* facs, int R, double scale, double* out, int64_t ldOut) {
-  CooFactor f[kCooMaxModes];
-  int k = 0;
-  for (int m = 0; m < b.nd; ++m) {
-    if (m == pos) continue;
-    f[k++] = facs[m].pT ? CooFactor{facs[m].pT, (int64_t)R, 1} : CooFactor{facs[m].p, 1, facs[m].ld};
-  }
-  KernelStats& ks = kstats_[3];
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (profile_) {
-    if (ks.pending.size() >= 512) fold_finished(ks);
-    if (ks.pending.size() < 4096) {
-      e0 = take_event();
-      e1 = take_event();
-      AO_HIP(hipEventRecord(e0, stream_));
-    }
-  }
-  coo_mttkrp(b.coo, pos, f, R, scale, out, ldOut, stream_);
-  if (e0) {
-    AO_HIP(hipEventRecord(e1, stream_));
-    ks.pending.emplace_back(e0, e1);
-    ks.timed++;
-  }
-  ks.launches++;
-  ks.bytes += coo_mttkrp_bytes(b.coo, pos, R);
-  ks.flops += coo_mttkrp_flops(b.coo, R);
 }
 
 std::vector<int> Engine::update_sequence(int p) const {
@@ -1592,7 +1066,7 @@ void Engine::prepare_mode_system(int m, int nrho, const aoadmm_options& opt) {
   // The system needs the Gram matrices only: it rides in the launch of the reduction that finishes the MTTKRP (one
   // extra workgroup) when that path is taken, else it gets its own launch behind the MTTKRP.
   bool rode = false;
-  block_mttkrp(t.blk, mi.pos, facs, mi.R, t.weight, mi.A.d(), mi.rows, opt.use_dimtree != 0, seq.data(), (int)seq.size(), true,
+  block_mttkrp(block_ctx(), t.blk, mi.pos, facs, mi.R, t.weight, mi.A.d(), mi.rows, opt.use_dimtree != 0, seq.data(), (int)seq.size(), true,
                false, &sb, &rode);
   if (!rode) sys_build(sb, stream_);
   if (cty == 1 || cty == 5) {                       // B = V diag(mu) V' for the Sylvester solve of the inner loop
@@ -2996,7 +2470,7 @@ void Engine::eval_objective_enqueue(bool first) {
         facs[i] = factor_ref(o);
       }
       std::vector<int> seq = update_sequence(p);
-      block_mttkrp(t.blk, 0, facs, m0.R, t.weight, m0.A.d(), m0.rows, true, seq.data(), (int)seq.size());
+      block_mttkrp(block_ctx(), t.blk, 0, facs, m0.R, t.weight, m0.A.d(), m0.rows, true, seq.data(), (int)seq.size());
       SysBuild sb;
       sb.ngram = 0;
       for (int i = 1; i < t.nmodes; ++i) sb.grams[sb.ngram++] = modes_[t.modes[i]].gram.d();
@@ -3066,7 +2540,7 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
   allow_xp_ = opt.no_permuted_copy == 0;
   if (!allow_xp_)
     for (int p = 0; p < n_tensors_; ++p)
-      drop_permuted_copies(tensors_[p].blk);
+      drop_pass_copies(tensors_[p].blk);
   for (int p = 0; p < n_tensors_; ++p) {
     AO_REQUIRE(tensors_[p].blk.has_data, "tensor %d has no data (Z.object{%d})", p, p + 1);
   }
@@ -3253,7 +2727,7 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
     for (ModeInfo& mq : modes_) mq.quad.dirty = true;   // rho moves once per outer iteration ('quadratic regularization', non-symmetric L)
     if (iter == 3)                                      // by now every pass of the schedule has run once: all copies exist
       for (int p = 0; p < n_tensors_; ++p)
-        if (!tensors_[p].par2) maybe_release_natural(tensors_[p]);
+        if (!tensors_[p].par2) maybe_release_natural(block_ctx(), tensors_[p].blk, tensors_[p].normsq_valid);
     for (int cid = -1; cid < n_couplings_; ++cid) {                            // :89 (0 = uncoupled first)
       std::vector<int> cm;
       for (int m = 0; m < n_modes_; ++m)
@@ -3428,7 +2902,7 @@ void Engine::resident_mttkrp(int p, int pos, double* out_host, float* ms) {
   AO_HIP(hipEventCreate(&e0)); AO_HIP(hipEventCreate(&e1));
   AO_HIP(hipEventRecord(e0, stream_));
   t.blk.cached_mode = -1;                              // a full MTTKRP: tensor pass + reduction, on the pass's resident copy
-  block_mttkrp(t.blk, pos, facs, mi.R, 1.0, mi.A.d(), mi.rows, true, nullptr, 0, true, true);
+  block_mttkrp(block_ctx(), t.blk, pos, facs, mi.R, 1.0, mi.A.d(), mi.rows, true, nullptr, 0, true, true);
   t.blk.cached_mode = -1;                              // the solver's own factors may differ from what this pass used
   AO_HIP(hipEventRecord(e1, stream_));
   AO_HIP(hipEventSynchronize(e1));

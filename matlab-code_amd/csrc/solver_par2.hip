@@ -114,25 +114,10 @@ void Engine::par2_slab_upload_coo(int p, int64_t nnz, const int64_t* subs, const
 }
 
 void Engine::par2s_pass(Par2Block& b, int pos, const CooFactor& f, double* out, int64_t ldOut) {
-  KernelStats& ks = kstats_[3];
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (profile_) {
-    if (ks.pending.size() >= 512) fold_finished(ks);
-    if (ks.pending.size() < 4096) {
-      e0 = take_event();
-      e1 = take_event();
-      AO_HIP(hipEventRecord(e0, stream_));
-    }
-  }
+  KernelStats& ks = timers_.stats[3];
+  const LaunchTimers::Pair pr = timers_.begin(ks, timers_.profile, stream_);
   coo_mttkrp(b.sp.coo, pos, &f, b.R, 1.0, out, ldOut, stream_);
-  if (e0) {
-    AO_HIP(hipEventRecord(e1, stream_));
-    ks.pending.emplace_back(e0, e1);
-    ks.timed++;
-  }
-  ks.launches++;
-  ks.bytes += coo_mttkrp_bytes(b.sp.coo, pos, b.R);
-  ks.flops += coo_mttkrp_flops(b.sp.coo, b.R);
+  timers_.end(ks, pr, stream_, coo_mttkrp_bytes(b.sp.coo, pos, b.R), coo_mttkrp_flops(b.sp.coo, b.R));
 }
 
 void Engine::par2s_rhs_A(TensorInfo& t, double* out) {
@@ -180,10 +165,10 @@ void Engine::resident_par2_rhs(int p, int pos, double* out_host, float* ms) {
     hipEvent_t e0, e1;
     ~Pair() { pool.push_back(e0); pool.push_back(e1); }
   };
-  hipEvent_t ev0 = take_event();
+  hipEvent_t ev0 = timers_.take_event();
   hipEvent_t ev1 = nullptr;
-  try { ev1 = take_event(); } catch (...) { event_pool_.push_back(ev0); throw; }
-  Pair ev{event_pool_, ev0, ev1};
+  try { ev1 = timers_.take_event(); } catch (...) { timers_.pool.push_back(ev0); throw; }
+  Pair ev{timers_.pool, ev0, ev1};
   AO_HIP(hipEventRecord(ev.e0, stream_));
   const double* res = nullptr;
   int64_t n = 0;

@@ -1,7 +1,7 @@
 """CPU, world_size 2 over gloo: the N > 1 path's algorithm.
 
 The multi-GPU engine row-shards the tensor's first mode, keeps factor matrices replicated and
-all-reduces each MTTKRP output (csrc/solver.hip block_mttkrp + Engine::allreduce); the copy for the
+all-reduces each MTTKRP output (csrc/cpblock.hip block_mttkrp + Engine::allreduce); the copy for the
 pass that contracts mode 1 is sharded along mode 3 instead (CpBlock::xp_ksharded), so MTTKRPs of
 modes 2 and 3 come from either partition depending on which pass serves them.  Here the same
 partitions (`row_block`, product code) and the same collective pattern are run with the oracle as

@@ -1,8 +1,8 @@
 """The N > 1 data path with world > 1 on ONE GPU: every rank is a thread of this process with its own engine and
 stream, joined by the library's process-local group (aoadmm_comm_init_local: host-staged, rank-ordered sums in
 place of ncclAllReduce -- RCCL refuses two ranks on one device).  Everything else is the code the RCCL ranks run:
-mode-1 row blocks (csrc/solver.hip tensor_upload), zero-filled own-rows MTTKRP buffers, all-reduced partial
-objective sums, replicated ADMM.  Bars: all ranks bit-identical; factors within 1e-8 of the oracle (fp64)."""
+mode-1 row blocks (csrc/solver.hip tensor_upload), zero-filled own-rows MTTKRP buffers (csrc/cpblock.hip
+block_mttkrp), all-reduced partial objective sums, replicated ADMM.  Bars: all ranks bit-identical; factors within 1e-8 of the oracle (fp64)."""
 import copy
 import itertools
 import threading

@@ -359,7 +359,7 @@ def test_tparafac2_temporal_smoothness(pkg, eng):
 
 def test_rccl_one_rank_communicator(pkg):
     """The N > 1 data path (zero-filled own-rows buffer + ncclAllReduce of every MTTKRP output on the
-    library's stream, csrc/solver.hip block_mttkrp/allreduce) with a ONE-rank RCCL communicator: the
+    library's stream, csrc/cpblock.hip block_mttkrp, csrc/solver.hip allreduce) with a ONE-rank RCCL communicator: the
     only form of the RCCL path a one-GPU box can run.  Same factors as the oracle."""
     rng = np.random.default_rng(21)
     Z, io, _ = cp_model((37, 14, 12), 3, rng, [('TV regularization', 0.01), ('non-negativity',), ('non-negativity',)])
