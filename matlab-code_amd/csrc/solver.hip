@@ -231,6 +231,7 @@ void Engine::model_begin(int n_modes, int n_tensors, int n_couplings) {
   modes_.resize(n_modes); tensors_.resize(n_tensors); couplings_.resize(n_couplings);
   model_done_ = false;
   has_ridge_ = false;
+  allow_xp_ = true;                                   // options.hip.no_permuted_copy of an earlier solve does not outlive its model
 }
 
 void Engine::set_mode(int mode, int64_t rows, int rank) {

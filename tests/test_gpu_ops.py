@@ -14,7 +14,15 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize('dims,R', [((40, 50, 60), 3), ((20, 30, 40), 3), ((50, 30, 40), 4), ((33, 17, 29), 5),
                                     ((130, 7, 9), 10), ((7, 5, 300), 20), ((64, 64, 64), 20), ((3, 2, 2), 1),
-                                    ((50, 70), 3), ((71, 33), 4), ((257, 129), 17), ((5, 6, 7, 8), 3) ])
+                                    ((50, 70), 3), ((71, 33), 4), ((257, 129), 17), ((5, 6, 7, 8), 3),
+                                    # the rank classes above R = 20: three and four 16-column tiles, with and without
+                                    # leftover columns, and the epilogue of more than 64 KB of LDS (R > 32)
+                                    ((33, 17, 29), 32), ((33, 17, 29), 36), ((33, 17, 29), 37), ((33, 17, 29), 48),
+                                    ((33, 17, 29), 52), ((33, 17, 29), 53), ((33, 17, 29), 64),
+                                    # 20 chunks on X with an empty last one; reduce_inner over B >= 1024 rows
+                                    ((6, 10, 2565), 20), ((6, 10, 2565), 37), ((6, 1030, 10), 52),
+                                    # matrices: launch_t_to_colmajor over 20 chunks, and at the largest rank
+                                    ((2565, 12), 20), ((2565, 12), 49), ((71, 33), 64)])
 @pytest.mark.parametrize('prec,tol', [('f64', 1e-12), ('f32', 2e-6)])
 def test_mttkrp_matches_oracle(eng, dims, R, prec, tol):
     """mttkrp(X,U,n) (cmtf_fun_AOADMM.m:97).  fp64 path: 1e-12 relative Frobenius (summation order only);
@@ -332,13 +340,13 @@ def test_nvecs_initialisation_from_resident_data(pkg):
         assert w[R] < 1e-10 * w[0]
 
 
-@pytest.mark.parametrize('dims', [(9, 7, 6, 5), (13, 4, 6, 3, 5), (34, 3, 2, 17)])
+@pytest.mark.parametrize('dims,R', [((9, 7, 6, 5), 4), ((13, 4, 6, 3, 5), 4), ((34, 3, 2, 17), 4), ((5, 6, 7, 8), 37)],
+                         ids=['dims0', 'dims1', 'dims2', 'dims3'])       # the ids the cases had before R was a parameter
 @pytest.mark.parametrize('prec,tol', [('f64', 1e-12), ('f32', 3e-6)])
-def test_mttkrp_nway(pkg, eng, dims, prec, tol):
+def test_mttkrp_nway(pkg, eng, dims, R, prec, tol):
     """Tensors of order > 3 (the toolbox mttkrp is N-way): one matrix-core contraction + successive folds over T."""
     rng = np.random.default_rng(len(dims) + sum(dims))
     X = rng.standard_normal(dims)
-    R = 4
     U = [rng.standard_normal((n, R)) for n in dims]
     for n in range(len(dims)):
         ref = o_mttkrp(X, U, n)
