@@ -306,6 +306,26 @@ int aoadmm_op_admm_constrained(aoadmm_ctx* ctx, const double* A, const double* B
                                const double* Lmat, int64_t rows, int R, int max_inner,
                                double tol_pr, double tol_du, double* fac, double* Z, double* mu,
                                int* inner_iters);
+/* Kernel family that ran an ADMM_constrained_only loop (reported by aoadmm_op_admm_mode).  The library picks it
+ * from the shape, the constraint and max_inner alone. */
+enum {
+  AOADMM_PATH_WG = 0,             /* whole loop in one workgroup: rows <= 256, R <= 16 */
+  AOADMM_PATH_MFMA = 1,           /* element-wise prox, two launches on the matrix cores */
+  AOADMM_PATH_ROWS_FUSED = 2,     /* one launch per inner iteration, element-/row-wise prox inside */
+  AOADMM_PATH_ROWS_COLPROX = 3,   /* primal kernel, column/matrix prox, dual kernel per inner iteration */
+  AOADMM_PATH_ROWS_TV = 4,        /* primal kernel, TV prox with the dual update inside */
+  AOADMM_PATH_ROWL = 5            /* triangular solves per row (aoadmm_op_admm_constrained only) */
+};
+/* The same loop as one constrained CP mode of aoadmm_solve runs it: C is the Hadamard product of the other modes'
+ * Gram matrices (R x R); rho = trace(C)/R, L = chol(C + rho/2*I) and inv(L*L') are built on the device
+ * (cmtf_fun_AOADMM.m:98-127,141-142 with weight 1), and the kernels are the ones the solver picks for this shape.
+ * fac/Z/mu are updated in place.  Also returned (each may be NULL): the inner iteration count, res[0] / res[1] =
+ * relative primal / dual residual of the last iteration (:1079-1096), gram = fac'*fac (R x R, :148),
+ * fac_rowmajor = the row-major copy of fac the next tensor pass reads (rows x R), path = AOADMM_PATH_*. */
+int aoadmm_op_admm_mode(aoadmm_ctx* ctx, const double* A, const double* C, int constraint,
+                        const double* params, int n_params, const double* Lmat, int64_t rows, int R,
+                        int max_inner, double tol_pr, double tol_du, double* fac, double* Z, double* mu,
+                        int* inner_iters, double* res, double* gram, double* fac_rowmajor, int* path);
 
 #ifdef __cplusplus
 }

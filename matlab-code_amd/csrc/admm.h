@@ -69,9 +69,11 @@ void prox_apply(const ProxSpec& ps, const double* V, int64_t ldv, double* Zout, 
 // `warm`: optional previous value of the prox output (same shape); only a speed hint (TV warm start)
 
 // The whole ADMM_constrained_only loop (:596-622) for a CP mode, enqueued without host synchronisation:
-//   fusable prox : one row-parallel kernel per inner iteration (fac, Z, mu, residual partial sums);
-//   other prox   : primal kernel -> column/matrix prox kernel -> dual kernel per inner iteration.
-// The loop condition is evaluated on the device at the head of each iteration (admm.hip admm_continue).
+//   element-wise prox, up to 4096 rows and 10 inner iterations : two launches for the whole loop (admm_rows_mfma_k);
+//   other fusable prox : one row-parallel kernel per inner iteration (fac, Z, mu, residual partial sums);
+//   other prox         : primal kernel -> column/matrix prox kernel -> dual kernel per inner iteration.
+// In the per-iteration forms the loop condition is evaluated on the device at the head of each iteration (admm.hip
+// admm_continue).  admm_path() below is the one place that chooses.
 // `part` holds admm_partials(rows) * 4 doubles; `V`,`Znew` are rows*R scratch (non-fusable only).
 struct AdmmMode {
   const double* A;      // MTTKRP (+bsum term)            rows x R
@@ -94,6 +96,21 @@ struct GramFold {
   double* At = nullptr;
   int nb = 0;
 };
+// Which kernels run the loop of one constrained CP mode.  Decided from the inputs alone, in one place: the solver,
+// admm_constrained_loop and the op-level entry (capi.hip aoadmm_op_admm_mode) all branch on admm_path().  The values
+// are part of the C ABI (include/aoadmm_hip.h AOADMM_PATH_*).
+enum AdmmPath {
+  kAdmmPathWg = 0,          // admm_loop_wg_k: the whole loop in one workgroup (caller runs admm_loop_wg)
+  kAdmmPathMfma = 1,        // admm_rows_mfma_k: the two-launch speculative loop
+  kAdmmPathRowsFused = 2,   // admm_rows_k with the element-/row-wise prox inside
+  kAdmmPathRowsColProx = 3, // admm_rows_k -> prox_apply -> dual_update_k
+  kAdmmPathRowsTv = 4,      // admm_rows_k -> TV prox with the dual update inside
+  kAdmmPathRowL = 5         // admm_rowL_k: triangular solves, for callers without inv(L*L')
+};
+// `have_binv`: inv(L*L') is available (the solver always has it for a constrained mode); `have_prox_ws`: a prox
+// workspace of prox_ws_bytes() is passed.
+AdmmPath admm_path(int64_t rows, int R, int ptype, int max_inner, bool have_binv, bool have_prox_ws);
+// Runs every path but kAdmmPathWg (that one has its own entry below and leaves Gram matrix and row-major copy itself).
 void admm_constrained_loop(const AdmmMode& m, double* part, double* V, double* Znew, double* prox_ws,
                            AdmmCtl* ctl, int max_inner, double tol_pr, double tol_du, hipStream_t s,
                            LoopEnd* deferred_end = nullptr, GramFold* gf = nullptr);

@@ -1764,9 +1764,32 @@ void admm_loop_wg(const WgLoopU& a, hipStream_t s) {
   AO_KERNEL_CHECK();
 }
 
+// TV prox with the dual update inside: LDS-resident columns, or the same arrays in the prox workspace
+static bool tv_fusable(int ptype, int64_t rows, bool have_prox_ws) {
+  return ptype == AOADMM_C_TV && (rows <= kTvParMax || (have_prox_ws && rows < (int64_t(1) << 24)));
+}
+
+AdmmPath admm_path(int64_t rows, int R, int ptype, int max_inner, bool have_binv, bool have_prox_ws) {
+  if (!have_binv) return kAdmmPathRowL;
+  if (admm_loop_wg_ok(rows, R, ptype, max_inner)) return kAdmmPathWg;
+  if (prox_is_fusable(ptype)) {
+    // element-wise prox: the whole loop in two launches (admm_rows_mfma_k).  One wave per 16 rows; pass 2 adds the
+    // partial sums of an iteration with kSpecPartJ loads per lane (tiles <= 256) and pass 1 leaves max_inner * tiles of
+    // them in `part` (2 * kMaxParts slots); the simplex projection needs the whole row in one thread.
+    const int64_t tiles = cdiv(rows, 16);
+    if (ptype != AOADMM_C_SIMPLEX_ROW && R <= 32 && tiles <= 64 * kSpecPartJ && max_inner <= kSpecMaxInner &&
+        (int64_t)max_inner * tiles <= 2 * kMaxParts)
+      return kAdmmPathMfma;
+    return kAdmmPathRowsFused;
+  }
+  return tv_fusable(ptype, rows, have_prox_ws) ? kAdmmPathRowsTv : kAdmmPathRowsColProx;
+}
+
 void admm_constrained_loop(const AdmmMode& m, double* part, double* V, double* Znew, double* prox_ws,
                            AdmmCtl* ctl, int max_inner, double tol_pr, double tol_du, hipStream_t s,
                            LoopEnd* deferred_end, GramFold* gf) {
+  const AdmmPath path = admm_path(m.rows, m.R, m.prox.type, max_inner, m.Binv != nullptr, prox_ws != nullptr);
+  AO_REQUIRE(path != kAdmmPathWg, "admm_constrained_loop: this mode belongs to the one-workgroup loop (admm_loop_wg)");
   FusedArgs a;
   a.A = m.A; a.L = m.L; a.Binv = m.Binv; a.rho = m.rho; a.fac = m.fac; a.Z = m.Z; a.mu = m.mu; a.V = V; a.part = part;
   a.ctl = ctl;
@@ -1779,10 +1802,8 @@ void admm_constrained_loop(const AdmmMode& m, double* part, double* V, double* Z
   const int64_t n = m.rows * m.R;
   int64_t nbd = cdiv(n, 1024);
   if (nbd > 64) nbd = 64;
-  // element-wise prox: the whole loop in two launches (admm_rows_mfma_k)
-  const int64_t tiles = cdiv(m.rows, 16);            // one wave per 16 rows
-  if (a.fused && a.ptype != AOADMM_C_SIMPLEX_ROW && a.Binv && a.R <= 32 && tiles <= 64 * kSpecPartJ &&
-      max_inner <= kSpecMaxInner && (int64_t)max_inner * tiles <= 2 * kMaxParts) {
+  if (path == kAdmmPathMfma) {
+    const int64_t tiles = cdiv(m.rows, 16);            // one wave per 16 rows
     SpecExtra ex{nullptr, nullptr};
     launch_rows_mfma_any(a, ex, false, (unsigned)tiles, s);
     AO_KERNEL_CHECK();
@@ -1792,8 +1813,8 @@ void admm_constrained_loop(const AdmmMode& m, double* part, double* V, double* Z
     if (deferred_end) *deferred_end = LoopEnd();    // the loop is closed: pass 2 recorded iters / residuals
     return;
   }
-  const bool tv_fused = !a.fused && m.prox.type == AOADMM_C_TV &&                        // prox + dual in one kernel
-                        (m.rows <= kTvParMax || (prox_ws != nullptr && m.rows < (int64_t(1) << 24)));
+  // prox + dual in one kernel (without inv(L*L') the primal kernel differs, the rest of the chain does not)
+  const bool tv_fused = path == kAdmmPathRowsTv || (path == kAdmmPathRowL && tv_fusable(m.prox.type, m.rows, prox_ws != nullptr));
   const int nparts = a.fused ? (int)blocks : (tv_fused ? m.R : (int)nbd);
   for (int it = 0; it < max_inner; ++it) {
     a.it = it;

@@ -661,4 +661,76 @@ int aoadmm_op_admm_constrained(aoadmm_ctx* ctx, const double* A, const double* B
   });
 }
 
+// One mode's ADMM update as Engine::update_uncoupled_cp_mode runs it for a constrained mode: the system from sys_build
+// (rho, L, inv(L*L')), the path from admm_path(), the Gram matrix and row-major copy from whichever kernel the solver
+// takes them from on that path.
+int aoadmm_op_admm_mode(aoadmm_ctx* ctx, const double* A, const double* Cmat, int constraint, const double* params,
+                        int n_params, const double* Lmat, int64_t rows, int R, int max_inner, double tol_pr,
+                        double tol_du, double* fac, double* Z, double* mu, int* inner_iters, double* res,
+                        double* gram, double* fac_rowmajor, int* path) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    AO_REQUIRE(A && Cmat && fac && Z && mu && rows > 0 && R > 0 && R <= kMaxRank && max_inner >= 1, "bad arguments");
+    AO_REQUIRE(constraint != AOADMM_C_QUADRATIC || Lmat != nullptr, "quadratic regularization needs its matrix");
+    Engine& e = *ctx->eng;
+    hipStream_t s = e.stream();
+    AO_HIP(hipSetDevice(e.device()));
+    const int64_t nR = rows * R, RR = (int64_t)R * R;
+    DevBuf a, cpre, cd, bs, l, bi, rh, f, z, m, part, V, Zn, ws, ctl, g, ft, aws;
+    h2d(a, A, nR, s); h2d(cpre, Cmat, RR, s);
+    h2d(f, fac, nR, s); h2d(z, Z, nR, s); h2d(m, mu, nR, s);
+    cd.alloc((size_t)RR * 8); bs.alloc((size_t)RR * 8); l.alloc((size_t)RR * 8); bi.alloc((size_t)RR * 8); rh.alloc(64);
+    part.alloc((size_t)admm_partials(rows) * 4 * 8);
+    V.alloc((size_t)nR * 8); Zn.alloc((size_t)nR * 8);
+    ws.alloc(prox_ws_bytes(constraint, rows, R));
+    g.alloc((size_t)RR * 8); ft.alloc((size_t)nR * 8);
+    const size_t fold = (size_t)cdiv(rows, 16) * RR * 8, atb = atb_ws_bytes(rows, R, R);
+    aws.alloc(fold > atb ? fold : atb);
+    ctl.alloc(sizeof(AdmmCtl));
+    AO_HIP(hipMemsetAsync(ctl.p, 0, sizeof(AdmmCtl), s));
+    AdmmCtl* c = ctl.as<AdmmCtl>();
+    SysBuild sb;                                     // prepare_mode_system with the Hadamard product given
+    sb.ngram = 0; sb.Cpre = cpre.d(); sb.w = 1.0; sb.ridge = 0.0; sb.bsum_half = 0.0; sb.rho_scale = 1.0;
+    sb.nrho = 1; sb.R = R;
+    sb.C = cd.d(); sb.rho = rh.d(); sb.Bsys = bs.d(); sb.L = l.d(); sb.Binv = bi.d(); sb.ctl = c;
+    sys_build(sb, s);
+    ProxSpec ps = make_spec(constraint, params, n_params);
+    QuadPrep qp;
+    if (constraint == AOADMM_C_QUADRATIC) { qp.build(Lmat, rows, s); qp.attach(ps); }
+    const AdmmPath ap = admm_path(rows, R, constraint, max_inner, true, ws.d() != nullptr);
+    if (ap == kAdmmPathWg) {
+      WgLoopU wa;
+      wa.A = a.d(); wa.Binv = bi.d(); wa.L = l.d(); wa.rho = rh.d(); wa.rho_prox = rh.d();
+      wa.fac = f.d(); wa.Z = z.d(); wa.mu = m.d();
+      wa.rows = rows; wa.R = R; wa.per_row = 0;
+      wa.ptype = ps.type; wa.p0 = ps.p0; wa.p1 = ps.p1;
+      wa.max_inner = max_inner; wa.tol_pr = tol_pr; wa.tol_du = tol_du;
+      wa.ctl = c;
+      wa.gram = g.d(); wa.facT = ft.d();
+      admm_loop_wg(wa, s);
+    } else {
+      AdmmMode am;
+      am.A = a.d(); am.L = l.d(); am.Binv = bi.d(); am.rho = rh.d();
+      am.fac = f.d(); am.Z = z.d(); am.mu = m.d();
+      am.rows = rows; am.R = R; am.prox = ps;
+      LoopEnd le;
+      GramFold gf;
+      gf.ws = aws.d(); gf.At = ft.d();
+      admm_constrained_loop(am, part.d(), V.d(), Zn.d(), ws.d(), c, max_inner, tol_pr, tol_du, s, &le, &gf);
+      if (gf.nb > 0) atb_fin(g.d(), aws.d(), gf.nb, R * R, nullptr, s);
+      else atb_small(g.d(), f.d(), rows, f.d(), rows, rows, R, R, aws.d(), nullptr, s, ft.d(), le.ctl ? &le : nullptr);
+    }
+    AdmmCtl h;
+    AO_HIP(hipMemcpyAsync(&h, ctl.p, sizeof h, hipMemcpyDeviceToHost, s));
+    AO_HIP(hipStreamSynchronize(s));
+    if (h.notpd) throw Error(AOADMM_ERR_NOT_PD, "Matrix must be positive definite.");
+    if (inner_iters) *inner_iters = h.iters;
+    if (res) { res[0] = h.res[1]; res[1] = h.res[3]; }
+    if (path) *path = (int)ap;
+    d2h(fac, f, nR, s); d2h(Z, z, nR, s); d2h(mu, m, nR, s);
+    if (gram) d2h(gram, g, RR, s);
+    if (fac_rowmajor) d2h(fac_rowmajor, ft, nR, s);
+  });
+}
+
 }  // extern "C"

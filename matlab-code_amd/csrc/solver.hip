@@ -1107,7 +1107,7 @@ void Engine::update_uncoupled_cp_mode(int m, const aoadmm_options& opt) {
   if (!mi.constrained) {
     // G.fac{m} = A{m}/B{m}  (:134): B is symmetric positive definite -> Cholesky solve
     row_solve(mi.fac.d(), mi.rows, mi.Aeff, mi.rows, mi.L.d(), mi.rows, mi.R, nullptr, stream_);
-  } else if (admm_loop_wg_ok(mi.rows, mi.R, mi.prox.type, opt.MaxInnerIters)) {
+  } else if (admm_path(mi.rows, mi.R, mi.prox.type, opt.MaxInnerIters, true, mi.proxws.d() != nullptr) == kAdmmPathWg) {
     // short mode: loop, Gram matrix and row-major copy in one launch of one workgroup
     WgLoopU wa;
     wa.A = mi.Aeff; wa.Binv = mi.Binv.d(); wa.L = mi.L.d(); wa.rho = mi.rho.d(); wa.rho_prox = mi.rho.d();

@@ -223,6 +223,30 @@ class Engine:
             float(tol_pr), float(tol_du), capi.dptr(fac), capi.dptr(Z), capi.dptr(mu), C.byref(it)))
         return fac, Z, mu, it.value
 
+    def admm_mode(self, A, Cmat, constraint, fac, Z, mu, max_inner, tol_pr, tol_du):
+        """The ADMM update of one constrained CP mode as the solver runs it (`aoadmm_op_admm_mode`): system and
+        kernels chosen by the library from `Cmat` (Hadamard product of the other modes' Gram matrices) and the shape.
+        Returns a dict: fac, Z, mu, inner_iters, pr, du (residuals of the last iteration), gram (fac'*fac), facT (the
+        row-major copy of fac as a rows x R C-ordered array) and path (one of capi.PATH_*)."""
+        cid, params, Lmat = constraint_descriptor(constraint)
+        A = capi.as_f(A)
+        Cmat = capi.as_f(Cmat)
+        rows, R = A.shape
+        fac = capi.as_f(fac).copy(order='F')
+        Z = capi.as_f(Z).copy(order='F')
+        mu = capi.as_f(mu).copy(order='F')
+        it, path = C.c_int(0), C.c_int(-1)
+        res = np.zeros(2)
+        gram = np.zeros((R, R), order='F')
+        facT = np.zeros((rows, R), order='C')
+        capi.check(self.lib.aoadmm_op_admm_mode(
+            self.h, capi.dptr(A), capi.dptr(Cmat), cid, capi.dptr(params) if params.size else None, params.size,
+            capi.dptr(Lmat) if Lmat is not None else None, rows, R, int(max_inner), float(tol_pr), float(tol_du),
+            capi.dptr(fac), capi.dptr(Z), capi.dptr(mu), C.byref(it), capi.dptr(res), capi.dptr(gram), capi.dptr(facT),
+            C.byref(path)))
+        return dict(fac=fac, Z=Z, mu=mu, inner_iters=it.value, pr=float(res[0]), du=float(res[1]), gram=gram,
+                    facT=facT, path=path.value)
+
 
 _default = None
 
