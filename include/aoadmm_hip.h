@@ -326,6 +326,32 @@ int aoadmm_op_admm_mode(aoadmm_ctx* ctx, const double* A, const double* C, int c
                         const double* params, int n_params, const double* Lmat, int64_t rows, int R,
                         int max_inner, double tol_pr, double tol_du, double* fac, double* Z, double* mu,
                         int* inner_iters, double* res, double* gram, double* fac_rowmajor, int* path);
+/* Kernels that run the B_k loop of a PARAFAC2 block (reported by aoadmm_op_par2_b_loop).  The library picks them from
+ * R, the longest slab and whether the B_k constraint is active. */
+enum {
+  AOADMM_P2SLAB_REGS1 = 0,        /* slab in registers, one row per lane: R <= 4, max J_k <= 64 */
+  AOADMM_P2SLAB_REGS2 = 1,        /* two rows per lane: max J_k <= 128 */
+  AOADMM_P2SLAB_REGS4 = 2,        /* four rows per lane: max J_k <= 256 */
+  AOADMM_P2SLAB_LDS4 = 3,         /* slab through LDS / global memory: R <= 4, longer slabs */
+  AOADMM_P2SLAB_LDS8 = 4,         /* R in 5..8 */
+  AOADMM_P2SLAB_LDS16 = 5,        /* R in 9..16 */
+  AOADMM_P2SLAB_LDS64 = 6         /* R in 17..64 */
+};
+/* Mode B of a PARAFAC2 block as aoadmm_solve runs it from the right-hand side on (cmtf_fun_AOADMM.m:194-218 with
+ * ADMM_B_Parafac2 :509-589), on K slabs of rows_k[k] rows: Ak = the slabs' right-hand sides w*X_k'*A*D_k back to back
+ * (each rows_k[k] x R, column-major), GA = A'*A (R x R), C (K x R).  rho_k = rho_scale*trace(D_k GA D_k)/R and
+ * L_k = chol(weight*D_k GA D_k + rho_k/2*(1 + constrained)*I) are built on the device; AOADMM_ERR_NOT_PD when one fails.
+ * constraint = AOADMM_C_NONE: no B_k constraint (Z, muZ ignored, may be NULL).  tol = the four inner tolerances
+ * {pr_coupl, pr_constr, du_coupl, du_constr}.  P, mu_DeltaB (slabs back to back), DeltaB (R x R) and, when constrained,
+ * Z and muZ are updated in place; B receives the new B_k.  Also returned (each may be NULL): rho (K), L and
+ * GB = B_k'*B_k ([K][R*R]), the inner iteration count, res[0..3] = the four residual means of the last iteration in
+ * the order of tol, path[0..3] = {two-launch folded loop (1) or four launches (0), AOADMM_P2SLAB_*, slab staged in
+ * LDS (1) or rotated in global memory (0), class of the folded dual kernel (16 / 64, 0 when not folded)}. */
+int aoadmm_op_par2_b_loop(aoadmm_ctx* ctx, int K, const int64_t* rows_k, int R, const double* Ak, const double* GA,
+                          const double* C, double weight, double rho_scale, int constraint, const double* params,
+                          int n_params, int max_inner, const double* tol, double* P, double* mu_DeltaB,
+                          double* DeltaB, double* Z, double* muZ, double* B, double* rho, double* L, double* GB,
+                          int* inner_iters, double* res, int* path);
 
 #ifdef __cplusplus
 }

@@ -733,4 +733,84 @@ int aoadmm_op_admm_mode(aoadmm_ctx* ctx, const double* A, const double* Cmat, in
   });
 }
 
+// Mode B of a PARAFAC2 block from the right-hand side on, as Engine::par2_update_B runs it: par2_b_loop (slab systems,
+// ADMM_B_Parafac2 on the path par2_b_path() names, Gram matrices) on uploaded buffers, no model.
+int aoadmm_op_par2_b_loop(aoadmm_ctx* ctx, int K, const int64_t* rows_k, int R, const double* Ak, const double* GA,
+                          const double* Cmat, double weight, double rho_scale, int constraint, const double* params,
+                          int n_params, int max_inner, const double* tol, double* P, double* mu_DeltaB, double* DeltaB,
+                          double* Z, double* muZ, double* B, double* rho, double* L, double* GB, int* inner_iters,
+                          double* res, int* path) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    AO_REQUIRE(K >= 1 && rows_k && R > 0 && R <= kMaxRank && max_inner >= 1 && tol, "bad arguments");
+    AO_REQUIRE(Ak && GA && Cmat && P && mu_DeltaB && DeltaB && B, "bad arguments");
+    AO_REQUIRE(constraint >= AOADMM_C_NONE && constraint <= AOADMM_C_TPARAFAC2 && constraint != AOADMM_C_QUADRATIC,
+               "constraint id %d is not available here", constraint);
+    const bool constr = constraint != AOADMM_C_NONE;
+    AO_REQUIRE(!constr || (Z && muZ), "a constrained B_k loop needs Z and muZ");
+    std::vector<int64_t> off((size_t)K + 1, 0);
+    int64_t jmax = 0;
+    for (int k = 0; k < K; ++k) {
+      AO_REQUIRE(rows_k[k] >= 1 && rows_k[k] < ((int64_t)1 << 31) / R, "slab %d: bad row count", k);
+      off[k + 1] = off[k] + rows_k[k];
+      jmax = std::max(jmax, rows_k[k]);
+    }
+    if (constraint == AOADMM_C_TPARAFAC2) {
+      AO_REQUIRE(K <= kTsmoothMaxK, "tPARAFAC2 on the device supports up to %d slabs", kTsmoothMaxK);
+      for (int k = 1; k < K; ++k)
+        AO_REQUIRE(rows_k[k] == rows_k[0], "tPARAFAC2 needs slabs of equal size (t_smoothness_prox.m adds B_k matrices)");
+    }
+    Engine& e = *ctx->eng;
+    hipStream_t s = e.stream();
+    AO_HIP(hipSetDevice(e.device()));
+    const int64_t RR = (int64_t)R * R, n = off[K] * R;
+    DevBuf offd, ak, ga, cf, rh, l, b, p, pold, mu, w, db, dbo, part, norms, jrot, z, mz, zold, v, ws, gb, ctl;
+    offd.alloc((size_t)(K + 1) * sizeof(int64_t));
+    AO_HIP(hipMemcpyAsync(offd.p, off.data(), (size_t)(K + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    h2d(ak, Ak, n, s); h2d(ga, GA, RR, s); h2d(cf, Cmat, (int64_t)K * R, s);
+    h2d(p, P, n, s); h2d(mu, mu_DeltaB, n, s); h2d(db, DeltaB, RR, s);
+    rh.alloc((size_t)K * 8); l.alloc((size_t)K * RR * 8); gb.alloc((size_t)K * RR * 8);
+    b.alloc((size_t)n * 8); pold.alloc((size_t)n * 8); w.alloc((size_t)n * 8);
+    dbo.alloc((size_t)RR * 8); part.alloc((size_t)K * RR * 8); norms.alloc((size_t)K * 8 * 8); jrot.alloc((size_t)K * RR * 8);
+    AO_HIP(hipMemsetAsync(b.p, 0, (size_t)n * 8, s));
+    AO_HIP(hipMemsetAsync(l.p, 0, (size_t)K * RR * 8, s));
+    if (constr) {
+      h2d(z, Z, n, s); h2d(mz, muZ, n, s);
+      zold.alloc((size_t)n * 8); v.alloc((size_t)n * 8);
+      ws.alloc(prox_ws_bytes(constraint, jmax, R));
+    }
+    ctl.alloc(sizeof(AdmmCtl));
+    AO_HIP(hipMemsetAsync(ctl.p, 0, sizeof(AdmmCtl), s));
+    P2Dims d;
+    d.K = K; d.I = 0; d.R = R; d.off = offd.as<int64_t>(); d.off_h = off.data();
+    d.Jtot = off[K]; d.Jmax = (int)jmax; d.k0 = 0; d.k1 = K;
+    P2BLoop g;
+    g.GA = ga.d(); g.Cfac = cf.d();
+    g.w = weight; g.ridge = 0.0; g.bsum = false; g.bsum_half = 0.0; g.rho_scale = rho_scale;
+    g.Ak = ak.d(); g.rho = rh.d(); g.L = l.d();
+    g.a.B = b.d(); g.a.P = p.d(); g.a.Pold = pold.d(); g.a.mu = mu.d(); g.a.W = w.d();
+    g.a.DeltaB = db.d(); g.a.DeltaBold = dbo.d(); g.a.part = part.d(); g.a.norms = norms.d(); g.a.Jrot = jrot.d();
+    g.constrained = constr;
+    g.prox = make_spec(constraint, params, n_params);
+    g.Z = z.d(); g.muZ = mz.d(); g.Zold = zold.d(); g.V = v.d(); g.prox_ws = ws.d();
+    g.max_inner = max_inner;
+    g.tol_pr_coupl = tol[0]; g.tol_pr_constr = tol[1]; g.tol_du_coupl = tol[2]; g.tol_du_constr = tol[3];
+    g.GB = gb.d();
+    const P2BPath bp = par2_b_path(d, constr, false);
+    par2_b_loop(g, d, ctl.as<AdmmCtl>(), s);
+    AdmmCtl h;
+    AO_HIP(hipMemcpyAsync(&h, ctl.p, sizeof h, hipMemcpyDeviceToHost, s));
+    AO_HIP(hipStreamSynchronize(s));
+    if (h.notpd) throw Error(AOADMM_ERR_NOT_PD, "Matrix must be positive definite.");
+    if (inner_iters) *inner_iters = h.iters;
+    if (res) for (int i = 0; i < 4; ++i) res[i] = h.res[i];
+    if (path) { path[0] = bp.folded; path[1] = bp.slab; path[2] = bp.in_lds; path[3] = bp.dual_fold; }
+    d2h(B, b, n, s); d2h(P, p, n, s); d2h(mu_DeltaB, mu, n, s); d2h(DeltaB, db, RR, s);
+    if (constr) { d2h(Z, z, n, s); d2h(muZ, mz, n, s); }
+    if (rho) d2h(rho, rh, K, s);
+    if (L) d2h(L, l, (int64_t)K * RR, s);
+    if (GB) d2h(GB, gb, (int64_t)K * RR, s);
+  });
+}
+
 }  // extern "C"

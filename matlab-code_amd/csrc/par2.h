@@ -51,15 +51,35 @@ struct P2BArgs {
   double* Jrot = nullptr;
   int jrot_valid = 0;                  // 0: Jrot holds nothing yet (first inner iteration): cold start, then store
 };
+// Which kernels run the B_k loop of a block.  Decided from the inputs alone, in one place: par2_b_loop_folded,
+// par2_b_iteration and the op-level entry (capi.hip aoadmm_op_par2_b_loop) all branch on par2_b_path().  The values are
+// part of the C ABI (include/aoadmm_hip.h AOADMM_P2SLAB_*).
+enum P2SlabKernel {
+  kP2SlabRegs1 = 0,   // par2_b_slab_regs_k<1> / par2_b_slab_fold_regs_k<1>: R <= 4, Jmax <= 64
+  kP2SlabRegs2 = 1,   // <2>: R <= 4, Jmax <= 128
+  kP2SlabRegs4 = 2,   // <4>: R <= 4, Jmax <= 256
+  kP2SlabLds4 = 3,    // par2_b_slab_k<4> / par2_b_slab_fold_k<4>: R <= 4, Jmax > 256
+  kP2SlabLds8 = 4,    // <8>: R in 5..8
+  kP2SlabLds16 = 5,   // par2_b_slab_k<16>: R in 9..16
+  kP2SlabLds64 = 6    // par2_b_slab_k<kMaxRank>: R >= 17
+};
+struct P2BPath {
+  int folded;      // 1: two launches per inner iteration (par2_b_loop_folded); 0: four (par2_b_iteration, ...)
+  int slab;        // P2SlabKernel
+  int in_lds;      // LDS forms: 1 when W_k is staged in LDS, 0 when it is rotated in place (no warm start then)
+  int dual_fold;   // folded: the par2_b_dual_fold_k class, 16 or 64; else 0
+};
+P2BPath par2_b_path(const P2Dims& d, bool constrained, bool sharded);
 // one inner iteration of ADMM_B_Parafac2 up to (not including) the constraint update   (:525-547, :582-585)
 // psum (R*R+1 doubles) != nullptr: slabs are sharded, DeltaB's sums go through `allreduce`
 void par2_b_iteration(const P2BArgs& a, const P2Dims& d, const AdmmCtl* ctl, hipStream_t s, double* psum,
                       const P2AllReduce& allreduce);
-// The whole loop without B_k constraints on unsharded slabs, R <= 8: two launches per inner iteration (the sum over the
-// slabs and the while test ride at the head of the next kernel) and one closing launch; ctl must have been reset.
-bool par2_b_loop_folded_ok(const P2Dims& d, bool constrained, bool sharded);
+// The whole loop without B_k constraints on unsharded slabs, R <= 8 (par2_b_path().folded): two launches per inner
+// iteration (the sum over the slabs and the while test ride at the head of the next kernel) and one closing launch; ctl
+// must have been reset.
 void par2_b_loop_folded(const P2BArgs& a, const P2Dims& d, AdmmCtl* ctl, int max_inner, double tol_pr_coupl,
                         double tol_pr_constr, double tol_du_coupl, double tol_du_constr, hipStream_t s);
+constexpr int kTsmoothMaxK = 64;       // tPARAFAC2: each thread keeps the eliminated diagonal of the K x K system
 // Z_k = prox(B_k + muZ_k, rho_k) ; muZ_k += B_k - Z_k ; norms[k][4..6] = ||B-Z||^2, ||muZ||^2, ||Z-Zold||^2   (:566-579)
 void par2_b_constraint(const ProxSpec& ps, const double* B, double* Z, double* muZ, double* Zold, double* V,
                        const double* rho, const P2Dims& d, double* prox_ws, double* norms, const AdmmCtl* ctl,
@@ -68,6 +88,27 @@ void par2_b_constraint(const ProxSpec& ps, const double* B, double* Z, double* m
 void par2_b_finalize(const double* norms, const P2Dims& d, int use_constr, AdmmCtl* ctl, int max_inner,
                      double tol_pr_coupl, double tol_pr_constr, double tol_du_coupl, double tol_du_constr, hipStream_t s,
                      double* part4, const P2AllReduce& allreduce);
+
+// Mode B from the right-hand side on (:194-218): the slab systems (par2_b_system, which opens the loop in ctl), the bsum
+// term of the right-hand side (:204-207), ADMM_B_Parafac2 on the path par2_b_path() names, and the Gram matrices of the
+// new B_k.  Engine::par2_update_B and aoadmm_op_par2_b_loop both run exactly this.
+struct P2BLoop {
+  const double *GA, *Cfac;                  // A'A (R x R), C (K x R)
+  double w, ridge, bsum_half, rho_scale;    // block weight, ridge, bsum_weight/2 (0 without bsum), increase_factor_rhoBk
+  bool bsum = false;
+  double* Ak;                               // w X_k' A D_k; with bsum: += bsum_half * B (:204-207)
+  double *rho, *L;                          // out: rho_k [K], chol factors [K][R*R]
+  P2BArgs a;                                // B, P, Pold, mu, W, DeltaB, DeltaBold, part, norms, Jrot (the rest is filled in)
+  bool constrained = false;                 // B_k constraint active in this outer iteration (:209, :527)
+  ProxSpec prox;
+  double *Z = nullptr, *muZ = nullptr, *Zold = nullptr, *V = nullptr, *prox_ws = nullptr;
+  int max_inner;
+  double tol_pr_coupl, tol_pr_constr, tol_du_coupl, tol_du_constr;
+  double* GB;                               // out: B_k' B_k [K][R*R]
+  double *psum = nullptr, *part4 = nullptr; // slabs sharded over ranks: R*R+1 sums of DeltaB, four residual means
+  P2AllReduce allreduce;
+};
+void par2_b_loop(const P2BLoop& g, const P2Dims& d, AdmmCtl* ctl, hipStream_t s);
 
 // mode C: a(k,r) = w * sum_i A(i,r) T1[k](i,r) ; C_k = GA .* GB[k] ; rho_k ; B_k (+rho_k/2 I if constrained) ; chol  (:221-240)
 // nrho = how many rho_k/2*I terms the system gets (constraint, exact coupling :262-264); Madd (R x R, optional) enters

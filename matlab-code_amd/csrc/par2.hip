@@ -834,19 +834,38 @@ __global__ __launch_bounds__(kP2Threads) void par2_b_close_k(P2BArgs a, P2Dims d
   }
 }
 
-bool par2_b_loop_folded_ok(const P2Dims& d, bool constrained, bool sharded) {
-  return !constrained && !sharded && d.R <= 8;
+P2BPath par2_b_path(const P2Dims& d, bool constrained, bool sharded) {
+  P2BPath p;
+  p.folded = (!constrained && !sharded && d.R <= 8) ? 1 : 0;
+  const int nr = par2_regs_rows(d);
+  if (nr == 1) p.slab = kP2SlabRegs1;
+  else if (nr == 2) p.slab = kP2SlabRegs2;
+  else if (nr == 4) p.slab = kP2SlabRegs4;
+  else if (d.R <= 4) p.slab = kP2SlabLds4;
+  else if (d.R <= 8) p.slab = kP2SlabLds8;
+  else if (d.R <= 16) p.slab = kP2SlabLds16;
+  else p.slab = kP2SlabLds64;
+  const size_t rr = (size_t)d.R * d.R * sizeof(double);
+  const size_t wl = (size_t)d.Jmax * d.R * sizeof(double);
+  p.in_lds = rr + wl <= 48 * 1024 ? 1 : 0;
+  p.dual_fold = p.folded ? (d.R * d.R <= 16 ? 16 : 64) : 0;
+  return p;
+}
+// dynamic LDS of the LDS forms of the slab kernel: max(2*R*R, R*R + Jmax*R [in_lds], 64) doubles
+static size_t par2_b_slab_lds(const P2Dims& d, const P2BPath& p) {
+  const size_t rr = (size_t)d.R * d.R * sizeof(double);
+  const size_t wl = (size_t)d.Jmax * d.R * sizeof(double);
+  return std::max<size_t>(std::max<size_t>(2 * rr, rr + (p.in_lds ? wl : 0)), 64 * sizeof(double));
 }
 
 void par2_b_loop_folded(const P2BArgs& a0, const P2Dims& d, AdmmCtl* ctl, int max_inner, double tpc, double tpz, double tdc,
                         double tdz, hipStream_t s) {
-  AO_REQUIRE(par2_b_loop_folded_ok(d, a0.use_constr != 0, false), "par2_b_loop_folded: not applicable");
+  const P2BPath p = par2_b_path(d, a0.use_constr != 0, false);
+  AO_REQUIRE(p.folded, "par2_b_loop_folded: not applicable");
   const int RR = d.R * d.R;
-  const size_t rr = (size_t)RR * sizeof(double);
   const unsigned nk = (unsigned)(d.k1 - d.k0);
-  const size_t wl = (size_t)d.Jmax * d.R * sizeof(double);
-  const int in_lds = rr + wl <= 48 * 1024;
-  const size_t lds = std::max<size_t>(std::max<size_t>(2 * rr, rr + (in_lds ? wl : 0)), 64 * sizeof(double));
+  const int in_lds = p.in_lds;
+  const size_t lds = par2_b_slab_lds(d, p);
   const size_t lds2 = (size_t)(2 * RR + kP2Threads * (RR + 1)) * sizeof(double);
   P2Fold f{0, max_inner, tpc, tpz, tdc, tdz};
   for (int it = 0; it < max_inner; ++it) {
@@ -855,14 +874,15 @@ void par2_b_loop_folded(const P2BArgs& a0, const P2Dims& d, AdmmCtl* ctl, int ma
     a.DeltaBold = (it & 1) ? a0.DeltaB : a0.DeltaBold;
     a.jrot_valid = it >= 1 ? 1 : 0;                  // the first inner iteration of every loop starts cold
     f.it = it;
-    const int nr = par2_regs_rows(d);
-    if (nr == 1) par2_b_slab_fold_regs_k<1><<<nk, kP2Threads, 0, s>>>(a, d, ctl, f);
-    else if (nr == 2) par2_b_slab_fold_regs_k<2><<<nk, kP2Threads, 0, s>>>(a, d, ctl, f);
-    else if (nr == 4) par2_b_slab_fold_regs_k<4><<<nk, kP2Threads, 0, s>>>(a, d, ctl, f);
-    else if (d.R <= 4) par2_b_slab_fold_k<4><<<nk, kP2Threads, lds, s>>>(a, d, ctl, in_lds, f);
-    else par2_b_slab_fold_k<8><<<nk, kP2Threads, lds, s>>>(a, d, ctl, in_lds, f);
+    switch (p.slab) {
+      case kP2SlabRegs1: par2_b_slab_fold_regs_k<1><<<nk, kP2Threads, 0, s>>>(a, d, ctl, f); break;
+      case kP2SlabRegs2: par2_b_slab_fold_regs_k<2><<<nk, kP2Threads, 0, s>>>(a, d, ctl, f); break;
+      case kP2SlabRegs4: par2_b_slab_fold_regs_k<4><<<nk, kP2Threads, 0, s>>>(a, d, ctl, f); break;
+      case kP2SlabLds4: par2_b_slab_fold_k<4><<<nk, kP2Threads, lds, s>>>(a, d, ctl, in_lds, f); break;
+      default: par2_b_slab_fold_k<8><<<nk, kP2Threads, lds, s>>>(a, d, ctl, in_lds, f); break;   // folded: R <= 8
+    }
     AO_KERNEL_CHECK();
-    if (RR <= 16) par2_b_dual_fold_k<16><<<nk, kP2Threads, lds2, s>>>(a, d, ctl);
+    if (p.dual_fold == 16) par2_b_dual_fold_k<16><<<nk, kP2Threads, lds2, s>>>(a, d, ctl);
     else par2_b_dual_fold_k<64><<<nk, kP2Threads, lds2, s>>>(a, d, ctl);
     AO_KERNEL_CHECK();
   }
@@ -875,17 +895,18 @@ void par2_b_iteration(const P2BArgs& a, const P2Dims& d, const AdmmCtl* ctl, hip
                       const P2AllReduce& allreduce) {
   const size_t rr = (size_t)d.R * d.R * sizeof(double);
   const unsigned nk = (unsigned)(d.k1 - d.k0);
-  const size_t wl = (size_t)d.Jmax * d.R * sizeof(double);
-  const int in_lds = rr + wl <= 48 * 1024;
-  const size_t lds = std::max<size_t>(std::max<size_t>(2 * rr, rr + (in_lds ? wl : 0)), 64 * sizeof(double));
-  const int nr = par2_regs_rows(d);
-  if (nr == 1) par2_b_slab_regs_k<1><<<nk, kP2Threads, 0, s>>>(a, d, ctl);
-  else if (nr == 2) par2_b_slab_regs_k<2><<<nk, kP2Threads, 0, s>>>(a, d, ctl);
-  else if (nr == 4) par2_b_slab_regs_k<4><<<nk, kP2Threads, 0, s>>>(a, d, ctl);
-  else if (d.R <= 4) par2_b_slab_k<4><<<nk, kP2Threads, lds, s>>>(a, d, ctl, in_lds);
-  else if (d.R <= 8) par2_b_slab_k<8><<<nk, kP2Threads, lds, s>>>(a, d, ctl, in_lds);
-  else if (d.R <= 16) par2_b_slab_k<16><<<nk, kP2Threads, lds, s>>>(a, d, ctl, in_lds);
-  else par2_b_slab_k<kMaxRank><<<nk, kP2Threads, lds, s>>>(a, d, ctl, in_lds);
+  const P2BPath p = par2_b_path(d, a.use_constr != 0, psum != nullptr);   // the slab kernel does not depend on the last two
+  const int in_lds = p.in_lds;
+  const size_t lds = par2_b_slab_lds(d, p);
+  switch (p.slab) {
+    case kP2SlabRegs1: par2_b_slab_regs_k<1><<<nk, kP2Threads, 0, s>>>(a, d, ctl); break;
+    case kP2SlabRegs2: par2_b_slab_regs_k<2><<<nk, kP2Threads, 0, s>>>(a, d, ctl); break;
+    case kP2SlabRegs4: par2_b_slab_regs_k<4><<<nk, kP2Threads, 0, s>>>(a, d, ctl); break;
+    case kP2SlabLds4: par2_b_slab_k<4><<<nk, kP2Threads, lds, s>>>(a, d, ctl, in_lds); break;
+    case kP2SlabLds8: par2_b_slab_k<8><<<nk, kP2Threads, lds, s>>>(a, d, ctl, in_lds); break;
+    case kP2SlabLds16: par2_b_slab_k<16><<<nk, kP2Threads, lds, s>>>(a, d, ctl, in_lds); break;
+    default: par2_b_slab_k<kMaxRank><<<nk, kP2Threads, lds, s>>>(a, d, ctl, in_lds); break;
+  }
   AO_KERNEL_CHECK();
   const int ew = ksum_tile_width((int64_t)d.R * d.R);
   par2_deltab_combine_k<<<(unsigned)cdiv((int64_t)d.R * d.R, ew), kKsumThreads, 0, s>>>(a, d, ctl, ew, psum);
@@ -934,7 +955,6 @@ __global__ __launch_bounds__(kP2Threads) void par2_bz_post_k(const double* B, co
 //   diag_k = 4*eta + rho_k (2*eta + rho_k at both ends), off-diagonals c = -2*eta, rhs_k = rho_k*V_k(j,r),
 // solved by the same Gaussian elimination (no pivoting, :42-46) and back substitution (:49-56) as the
 // reference.  The eliminated diagonal is the same for every entry; each thread keeps it in a local array.
-constexpr int kTsmoothMaxK = 64;
 __global__ void par2_tsmooth_k(const double* V, double* Z, const double* rho, double eta, P2Dims d, const AdmmCtl* ctl) {
   CTL_GUARD(ctl);
   const int64_t n = d.off[1] * d.R;                    // entries per slab (all slabs equal)
@@ -1043,6 +1063,34 @@ void par2_b_finalize(const double* norms, const P2Dims& d, int use_constr, AdmmC
                                              tol_du_constr);
     AO_KERNEL_CHECK();
   }
+}
+
+// mode B from the right-hand side on (:194-218) -- see par2.h
+void par2_b_loop(const P2BLoop& g, const P2Dims& d, AdmmCtl* ctl, hipStream_t s) {
+  const bool constr = g.constrained;
+  par2_b_system(g.GA, g.Cfac, g.w, g.ridge, g.bsum_half, g.rho_scale, 1 + (constr ? 1 : 0), d, g.rho, g.L, ctl, s);
+  if (g.bsum) {                                                                          // :204-207
+    Coef c[2] = {coef(1.0), coef(g.bsum_half)};
+    const double* x[2] = {g.Ak, g.a.B};
+    ew_lincomb(g.Ak, d.Jtot * d.R, 2, c, x, nullptr, s);
+  }
+  P2BArgs a = g.a;                                                                       // par2_b_system opened the loop (ctl)
+  a.Ak = g.Ak; a.L = g.L; a.rho = g.rho;
+  a.Z = constr ? g.Z : nullptr; a.muZ = constr ? g.muZ : nullptr;
+  a.use_constr = constr ? 1 : 0;
+  const bool sharded = g.psum != nullptr;
+  if (par2_b_path(d, constr, sharded).folded) {
+    par2_b_loop_folded(a, d, ctl, g.max_inner, g.tol_pr_coupl, g.tol_pr_constr, g.tol_du_coupl, g.tol_du_constr, s);
+    par2_gram(a.B, d, g.GB, s);                                                          // :216-218
+    return;
+  }
+  for (int it = 0; it < g.max_inner; ++it) {
+    par2_b_iteration(a, d, ctl, s, g.psum, g.allreduce);
+    if (constr) par2_b_constraint(g.prox, a.B, g.Z, g.muZ, g.Zold, g.V, g.rho, d, g.prox_ws, a.norms, ctl, s);
+    par2_b_finalize(a.norms, d, constr ? 1 : 0, ctl, g.max_inner, g.tol_pr_coupl, g.tol_pr_constr, g.tol_du_coupl,
+                    g.tol_du_constr, s, g.part4, g.allreduce);
+  }
+  par2_gram(a.B, d, g.GB, s);                                                            // :216-218
 }
 
 // ---------------------------------------------------------------------------

@@ -280,43 +280,29 @@ void Engine::par2_update_B(int m, const aoadmm_options& opt, int iter) {
   } else {
     par2_xta(b.X.d(), mA.fac.d(), mC.fac.d(), t.weight, d, b.Ak.d(), stream_);
   }
-  par2_b_system(mA.gram.d(), mC.fac.d(), t.weight, has_ridge_ ? mi.ridge : 0.0, opt.bsum ? opt.bsum_weight / 2 : 0.0,
-                opt.has_increase_factor_rhoBk ? opt.increase_factor_rhoBk : 1.0, 1 + (constr ? 1 : 0), d, b.rhok.d(),
-                b.Lk.d(), ctl, stream_);
-  if (opt.bsum) {                                                                        // :204-207
-    Coef c[2] = {coef(1.0), coef(opt.bsum_weight / 2)};
-    const double* x[2] = {b.Ak.d(), mi.fac.d()};
-    ew_lincomb(b.Ak.d(), b.Jtot * b.R, 2, c, x, nullptr, stream_);
-  }
-  t.last_pos = 1;                                                                        // last_m(p) = 2; par2_b_system opened the loop (ctl)
-  P2BArgs a;
-  a.Ak = b.Ak.d(); a.L = b.Lk.d(); a.rho = b.rhok.d();
-  a.B = mi.fac.d(); a.P = b.P.d(); a.Pold = b.Pold.d(); a.mu = b.muDB.d(); a.W = b.W.d();
-  a.DeltaB = b.DeltaB.d(); a.DeltaBold = b.DeltaBold.d(); a.part = b.part.d();
-  a.Z = constr ? mi.Z.d() : nullptr; a.muZ = constr ? mi.mu.d() : nullptr;
-  a.norms = b.norms.d();
-  a.use_constr = constr ? 1 : 0;
+  t.last_pos = 1;                                                                        // last_m(p) = 2
+  P2BLoop g;
+  g.GA = mA.gram.d(); g.Cfac = mC.fac.d();
+  g.w = t.weight; g.ridge = has_ridge_ ? mi.ridge : 0.0;
+  g.bsum = opt.bsum != 0; g.bsum_half = opt.bsum ? opt.bsum_weight / 2 : 0.0;
+  g.rho_scale = opt.has_increase_factor_rhoBk ? opt.increase_factor_rhoBk : 1.0;
+  g.Ak = b.Ak.d(); g.rho = b.rhok.d(); g.L = b.Lk.d();
+  g.a.B = mi.fac.d(); g.a.P = b.P.d(); g.a.Pold = b.Pold.d(); g.a.mu = b.muDB.d(); g.a.W = b.W.d();
+  g.a.DeltaB = b.DeltaB.d(); g.a.DeltaBold = b.DeltaBold.d(); g.a.part = b.part.d();
+  g.a.norms = b.norms.d();
   b.Jrot.ensure((size_t)b.K * b.R * b.R * sizeof(double));
-  a.Jrot = b.Jrot.d();
-  const P2AllReduce ar = [this](double* buf, int64_t n) { allreduce(buf, n); };
-  double* psum = b.slab_sharded ? b.psum.d() : nullptr;
-  double* part4 = b.slab_sharded ? b.psum.d() + (int64_t)b.R * b.R + 8 : nullptr;
-  if (par2_b_loop_folded_ok(d, constr, b.slab_sharded)) {
-    par2_b_loop_folded(a, d, ctl, opt.MaxInnerIters, opt.innerRelPrTol_coupl, opt.innerRelPrTol_constr,
-                       opt.innerRelDualTol_coupl, opt.innerRelDualTol_constr, stream_);
-    par2_gram(mi.fac.d(), d, b.GB.d(), stream_);                                         // :216-218
-    mi.version++;
-    return;
-  }
-  for (int it = 0; it < opt.MaxInnerIters; ++it) {
-    par2_b_iteration(a, d, ctl, stream_, psum, ar);
-    if (constr)
-      par2_b_constraint(mi.prox, mi.fac.d(), mi.Z.d(), mi.mu.d(), mi.Zold.d(), mi.V.d(), b.rhok.d(), d, mi.proxws.d(),
-                        b.norms.d(), ctl, stream_);
-    par2_b_finalize(b.norms.d(), d, constr ? 1 : 0, ctl, opt.MaxInnerIters, opt.innerRelPrTol_coupl,
-                    opt.innerRelPrTol_constr, opt.innerRelDualTol_coupl, opt.innerRelDualTol_constr, stream_, part4, ar);
-  }
-  par2_gram(mi.fac.d(), d, b.GB.d(), stream_);                                           // :216-218
+  g.a.Jrot = b.Jrot.d();
+  g.constrained = constr;
+  g.prox = mi.prox;
+  g.Z = mi.Z.d(); g.muZ = mi.mu.d(); g.Zold = mi.Zold.d(); g.V = mi.V.d(); g.prox_ws = mi.proxws.d();
+  g.max_inner = opt.MaxInnerIters;
+  g.tol_pr_coupl = opt.innerRelPrTol_coupl; g.tol_pr_constr = opt.innerRelPrTol_constr;
+  g.tol_du_coupl = opt.innerRelDualTol_coupl; g.tol_du_constr = opt.innerRelDualTol_constr;
+  g.GB = b.GB.d();
+  g.psum = b.slab_sharded ? b.psum.d() : nullptr;
+  g.part4 = b.slab_sharded ? b.psum.d() + (int64_t)b.R * b.R + 8 : nullptr;
+  g.allreduce = [this](double* buf, int64_t n) { allreduce(buf, n); };
+  par2_b_loop(g, d, ctl, stream_);                    // systems, ADMM_B_Parafac2, Gram matrices of the new B_k (:194-218)
   mi.version++;
 }
 

@@ -247,6 +247,59 @@ class Engine:
         return dict(fac=fac, Z=Z, mu=mu, inner_iters=it.value, pr=float(res[0]), du=float(res[1]), gram=gram,
                     facT=facT, path=path.value)
 
+    def par2_b_loop(self, rows_k, R, Ak, GA, Cmat, weight, rho_scale, constraint, max_inner, tol, P, mu_DeltaB, DeltaB,
+                    Z=None, muZ=None):
+        """Mode B of a PARAFAC2 block from the right-hand side on, as the solver runs it (`aoadmm_op_par2_b_loop`):
+        slab systems, ADMM_B_Parafac2 with the kernels the library picks for (R, max J_k, constrained), Gram matrices.
+        Ak, P, mu_DeltaB, Z, muZ: lists of K arrays J_k x R; GA R x R; Cmat K x R; constraint: a `Z.constraints` cell
+        or None; tol: (pr_coupl, pr_constr, du_coupl, du_constr).  Returns a dict: B, P, mu, Z, muZ (lists; Z, muZ
+        None when unconstrained), DeltaB, rho (K), L and GB (K x R x R, [k] = the slab's matrix), inner_iters,
+        res (4, order of tol) and path = (folded, slab class capi.P2SLAB_*, in_lds, dual_fold class)."""
+        rows = [int(j) for j in rows_k]
+        K, R = len(rows), int(R)
+        if constraint is None:
+            cid, params = 0, np.zeros(0)
+        else:
+            cid, params, Lmat = constraint_descriptor(constraint)
+            if Lmat is not None:
+                raise ValueError('par2_b_loop: quadratic regularization is not available here')
+
+        def pack(xs):
+            xs = [np.asarray(x, dtype=np.float64).reshape(j, R) for x, j in zip(xs, rows)]
+            if len(xs) != K:
+                raise ValueError('par2_b_loop: one array per slab')
+            return np.concatenate([x.ravel(order='F') for x in xs])
+
+        def unpack(v):
+            off = np.concatenate([[0], np.cumsum(rows)]) * R
+            return [v[off[k]:off[k + 1]].reshape(rows[k], R, order='F').copy() for k in range(K)]
+
+        ak, p, mu = pack(Ak), pack(P), pack(mu_DeltaB)
+        z = pack(Z) if cid else None
+        mz = pack(muZ) if cid else None
+        ga, cm = capi.as_f(GA), capi.as_f(Cmat)
+        if ga.shape != (R, R) or cm.shape != (K, R):
+            raise ValueError('par2_b_loop: GA must be R x R and C K x R')
+        db = capi.as_f(DeltaB).copy(order='F')
+        n = ak.size
+        b = np.zeros(n)
+        rho, L, GB = np.zeros(K), np.zeros(K * R * R), np.zeros(K * R * R)
+        it = C.c_int(0)
+        res = np.zeros(4)
+        path = (C.c_int * 4)(-1, -1, -1, -1)
+        tolv = np.asarray(tol, dtype=np.float64).reshape(4).copy()
+        rk = (C.c_int64 * K)(*rows)
+        capi.check(self.lib.aoadmm_op_par2_b_loop(
+            self.h, K, rk, R, capi.dptr(ak), capi.dptr(ga), capi.dptr(cm), float(weight), float(rho_scale), cid,
+            capi.dptr(params) if params.size else None, params.size, int(max_inner), capi.dptr(tolv), capi.dptr(p),
+            capi.dptr(mu), capi.dptr(db), capi.dptr(z), capi.dptr(mz), capi.dptr(b), capi.dptr(rho), capi.dptr(L),
+            capi.dptr(GB), C.byref(it), capi.dptr(res), path))
+        mats = lambda v: np.stack([v[k * R * R:(k + 1) * R * R].reshape(R, R, order='F') for k in range(K)])
+        return dict(B=unpack(b), P=unpack(p), mu=unpack(mu), Z=unpack(z) if cid else None,
+                    muZ=unpack(mz) if cid else None, DeltaB=db, rho=rho, L=mats(L), GB=mats(GB), inner_iters=it.value,
+                    res=res, path=tuple(path))
+
+
 
 _default = None
 

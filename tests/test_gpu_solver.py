@@ -321,6 +321,39 @@ def test_parafac2_larger_ranks(pkg, eng, R, K):
     compare_par2(*run_both(pkg, eng, Z, io, options(MaxOuterIters=6)))
 
 
+@pytest.mark.parametrize('R,Jk', [
+    pytest.param(3, [64, 33, 40, 17], id='regs1'),            # longest slab <= 64: one row per lane, folded loop
+    pytest.param(3, [129, 256, 200, 131], id='regs4'),        # 129..256: four rows per lane
+    pytest.param(3, [257, 300, 90], id='lds4'),               # R <= 4 with a slab above 256 rows
+    pytest.param(17, [40, 61, 50, 37], id='lds64'),           # R >= 17, four launches
+    pytest.param(3, [2100, 70, 35], id='nolds'),              # the slab does not fit the LDS stage: rotated in place
+    pytest.param(3, [50], id='K1'),                           # one slab
+])
+def test_parafac2_Bk_kernel_classes(pkg, eng, R, Jk):
+    """Short solves at shapes whose B_k loop takes the kernel classes no other solve reaches (par2.hip par2_b_path;
+    each class alone against fp64: tests/test_gpu_par2_bloop.py)."""
+    from helpers import par2_slabs
+    rng = np.random.default_rng(17)
+    I, K = 20, len(Jk)
+    X, _ = par2_slabs(I, Jk, R, rng, 0.2)
+    Z = dict(loss_function=['Frobenius'], model=['PAR2'], modes=[[1, 2, 3]], size=[I, Jk, K],
+             coupling=dict(lin_coupled_modes=[0, 0, 0], coupling_type=[], coupl_trafo_matrices=[None] * 3),
+             constrained_modes=[0, 0, 1], constraints=[None, None, ('non-negativity',)], weights=[1.0], object=[X])
+    distr = [lambda a, b: rng.standard_normal((a, b)), lambda a, b: rng.standard_normal((a, b)),
+             lambda a, b: rng.random((a, b)) + 0.1]
+    io = dict(lambdas_init=[[1] * R], nvecs=0, distr=distr, normalize=1)
+    Fo, oo, Fg, og = run_both(pkg, eng, Z, io, options(MaxOuterIters=4))
+    if K == 1:
+        # One slab: P_1 spans the columns of B_1 + mu_1 and DeltaB = P_1'(B_1 + mu_1), so mu_1 + B_1 - P_1 DeltaB is zero
+        # in exact arithmetic and mu_1 is rounding noise in the oracle too (1e-16 of ||B_1||).  It is compared on the scale
+        # of what it is the difference of; everything else as in every other case.
+        (mo,), (mg,), (Bo,) = Fo['mu_DeltaB'][0], Fg['mu_DeltaB'][0], Fo['fac'][1]
+        assert np.linalg.norm(mo) < 1e-13 * np.linalg.norm(Bo)
+        assert np.linalg.norm(mg - mo) < TOL * np.linalg.norm(Bo)
+        Fo = dict(Fo, mu_DeltaB=None)
+    compare_par2(Fo, oo, Fg, og)
+
+
 def test_parafac2_constrained_Bk(pkg, eng):
     """B_k constrained (example_script9 family: unimodality on the B_k columns, delayed start, rho factor)."""
     from helpers import script4_model
