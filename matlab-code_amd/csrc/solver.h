@@ -1,7 +1,8 @@
 // Host-side engine: model (struct Z), state (struct G) and the AO-ADMM outer loop
 // (functions/cmtf_fun_AOADMM.m:87-476) driving the HIP kernels.  Everything stays
 // resident in HBM; the host synchronises once per outer iteration to read the
-// objective values and the inner-iteration counters.
+// objective values and the inner-iteration counters.  The members are defined in solver.hip (model, data, outer loop,
+// objective), solver_par2.hip (PARAFAC2 blocks) and solver_coupled.hip (coupled ADMM loop).
 #pragma once
 #include <atomic>
 #include <memory>
@@ -11,6 +12,7 @@
 #include "admm.h"
 #include "common.h"
 #include "contract.h"
+#include "couple.h"
 #include "cpblock.h"
 #include "misc.h"
 #include "par2.h"
@@ -119,6 +121,18 @@ struct CouplingInfo {
 
 struct LocalGroup;
 
+constexpr int kSlotsPerMode = 8;      // objective slots
+constexpr int kResidPerMode = 8;      // ADMM residual slots
+
+// coupling images (solver_coupled.hip): Sd(D), Tf(F) and Tf'(Y) for mode `mi` of coupling `ci`; each returns its input
+// where the map is the identity and `dst` otherwise
+const double* image_d(double* dst, const CouplingInfo& ci, const double* D, const ModeInfo& mi, const AdmmCtl* ctl,
+                      hipStream_t s);
+const double* image_f(double* dst, const CouplingInfo& ci, const double* F, const ModeInfo& mi, const AdmmCtl* ctl,
+                      hipStream_t s);
+const double* adjoint_f(double* dst, const CouplingInfo& ci, const double* Y, const ModeInfo& mi, const AdmmCtl* ctl,
+                        hipStream_t s);
+
 class Engine {
  public:
   explicit Engine(int device);
@@ -198,13 +212,22 @@ class Engine {
   }
   void update_uncoupled_cp_mode(int m, const aoadmm_options& opt);
   void prepare_mode_system(int m, int nrho, const aoadmm_options& opt);
-  void coupled_admm(int c, const aoadmm_options& opt);
   void eval_objective_enqueue(bool first);
   bool has_missing() const;
   void em_pass_enqueue(int p, int update, bool fuse_next_pass = false);
   void prepare_next_first_mode(const aoadmm_options& opt);         // statistics of tensor p into its EM slots (+ imputation)
   double* em_slot(int p) const;
   void ensure_mode_work(ModeInfo& mi);
+  // coupled ADMM loop (solver_coupled.hip): coupled_admm prepares it and runs one of the three forms
+  void coupled_admm(int c, const aoadmm_options& opt);
+  void coupled_one_launch(CouplingInfo& ci, AdmmCtl* ctl, const aoadmm_options& opt, CouplePath path, int rmax);
+  void coupled_row_steps(CouplingInfo& ci, AdmmCtl* ctl, const aoadmm_options& opt, int rmax);
+  void coupled_generic(CouplingInfo& ci, AdmmCtl* ctl, const aoadmm_options& opt, bool any_pc);
+  void coupled_generic_primal(CouplingInfo& ci, ModeInfo& mi, AdmmCtl* ctl, bool first);
+  void coupled_generic_delta(CouplingInfo& ci, AdmmCtl* ctl, bool any_pc);
+  void coupled_generic_dual(CouplingInfo& ci, int m, AdmmCtl* ctl);
+  FinalizeArgs coupled_finalize_args(const CouplingInfo& ci, const aoadmm_options& opt);
+  Par2Block* par2_c_block(const ModeInfo& mi);
   // PARAFAC2 (solver_par2.hip)
   void par2_ensure_work(TensorInfo& t);
   void par2_prepare_modeA(int m, int nrho, const aoadmm_options& opt);

@@ -1,11 +1,9 @@
 // Engine implementation: see solver.h.  Reference control flow:
-// functions/cmtf_fun_AOADMM.m:87-476 (outer loop), :625-695 / :904-983 (coupled ADMM
-// cases 0 and 4), :1213-1363 (objective), functions/evaluate_stopping_conditions.m.
+// functions/cmtf_fun_AOADMM.m:87-476 (outer loop), :1213-1363 (objective),
+// functions/evaluate_stopping_conditions.m.  This file launches no kernel of its own.
 #include "solver.h"
-#include "device_utils.h"
 #include "em.h"
 #include "hosteig.h"
-#include "prox_dev.h"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -28,9 +26,6 @@ namespace aoadmm {
     if (r__ != ncclSuccess)                                                                    \
       throw Error(AOADMM_ERR_RCCL, fmt("%s failed: %s", #expr, ncclGetErrorString(r__)));      \
   } while (0)
-
-static constexpr int kSlotsPerMode = 8;      // objective slots
-static constexpr int kResidPerMode = 8;      // ADMM residual slots
 
 Engine::Engine(int device) : device_(device) {
   int n = 0;
@@ -1139,1298 +1134,6 @@ void Engine::update_uncoupled_cp_mode(int m, const aoadmm_options& opt) {
     mi.facT_version = mi.version;
   } else {
     compute_gram(mi, le.ctl ? &le : nullptr);                                 // :148
-  }
-}
-
-// The six linear couplings (cmtf_fun_AOADMM.m:625-1075) in one form:  Tf_m(C_m) = Sd_m(Delta)
-//   type 0: C = Delta | 1: H*C = Delta | 2: C*H = Delta | 3: C = H*Delta | 4: C = Delta*H | 5: H*C = Delta*H2
-// Sd: the Delta-side image for mode m (shape img_rows x img_cols)
-static const double* image_d(double* dst, const CouplingInfo& ci, const double* D, const ModeInfo& mi,
-                             const AdmmCtl* ctl, hipStream_t s) {
-  switch (ci.type) {
-    case 3: gemm_small(dst, mi.rows, mi.H.d(), mi.hr, D, ci.rows, mi.rows, (int)ci.rows, mi.R, 0, coef(1.0), 0.0, ctl, s); return dst;
-    case 4: gemm_small(dst, mi.rows, D, ci.rows, mi.H.d(), mi.hr, ci.rows, (int)ci.cols, mi.R, 0, coef(1.0), 0.0, ctl, s); return dst;
-    case 5: gemm_small(dst, ci.rows, D, ci.rows, mi.H2.d(), mi.h2r, ci.rows, (int)ci.cols, mi.R, 0, coef(1.0), 0.0, ctl, s); return dst;
-    default: return D;                               // types 0, 1, 2: Sd is the identity
-  }
-}
-// Tf: the factor-side image (same shape); types 0, 3, 4 are the identity and return F itself
-static const double* image_f(double* dst, const CouplingInfo& ci, const double* F, const ModeInfo& mi,
-                             const AdmmCtl* ctl, hipStream_t s) {
-  if (ci.type == 1 || ci.type == 5) {
-    gemm_small(dst, mi.hr, mi.H.d(), mi.hr, F, mi.rows, mi.hr, (int)mi.rows, mi.R, 0, coef(1.0), 0.0, ctl, s);
-    return dst;
-  }
-  if (ci.type == 2) {
-    gemm_small(dst, mi.rows, F, mi.rows, mi.H.d(), mi.hr, mi.rows, mi.R, (int)mi.hc, 0, coef(1.0), 0.0, ctl, s);
-    return dst;
-  }
-  return F;
-}
-// Tf': adjoint of the factor-side map applied to Y (img shape) -> rows x R ; identity for types 0, 3, 4
-static const double* adjoint_f(double* dst, const CouplingInfo& ci, const double* Y, const ModeInfo& mi,
-                               const AdmmCtl* ctl, hipStream_t s) {
-  if (ci.type == 1 || ci.type == 5) {               // H' * Y
-    gemm_small(dst, mi.rows, mi.Ht.d(), mi.hc, Y, mi.img_rows, mi.rows, (int)mi.hr, mi.R, 0, coef(1.0), 0.0, ctl, s);
-    return dst;
-  }
-  if (ci.type == 2) {                                // Y * H'
-    gemm_small(dst, mi.rows, Y, mi.rows, mi.H.d(), mi.hr, mi.rows, (int)mi.hc, mi.R, 1, coef(1.0), 0.0, ctl, s);
-    return dst;
-  }
-  return Y;
-}
-
-__global__ void coupling_coefs_k(double* coef, const double* const* rhos, int n, AdmmCtl* ctl) {
-  // coef[j] = rho_j / sum rho  (:661-675); also opens the coupled loop (what ctl_reset does: one launch fewer)
-  if (threadIdx.x == 1) {
-    ctl->active = 1;
-    ctl->iters = 0;
-    ctl->res[0] = ctl->res[1] = ctl->res[2] = ctl->res[3] = 0.0;
-  }
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int j = 0; j < n; ++j) s += rhos[j][0];
-    for (int j = 0; j < n; ++j) coef[j] = 1.0 / s * rhos[j][0];
-    coef[n] = s;
-  }
-}
-
-// mu_Delta += Tf(C) - Sd(Delta) (:679 and the same line of every case) with the sums the coupling residuals need in
-// the same pass: out[0] = ||Tf(C) - Sd(Delta)||^2, out[1] = ||mu_Delta||^2, out[3] = ||den||^2 (den = Tf(C) or C,
-// :1099-1210); out[2] (the dual numerator) is filled by the caller.  One workgroup for n <= 2048, else per-block
-// partial sums added in block order by coupling_dual_fin_k.
-__global__ __launch_bounds__(256) void coupling_dual_k(double* muD, const double* tf, const double* td, int64_t ni,
-                                                       const double* den, int64_t nden, double* out, double* ws,
-                                                       const AdmmCtl* ctl) {
-  if (ctl != nullptr && ctl->active == 0) return;
-  __shared__ double sh4[4];
-  double s0 = 0, s1 = 0, s2 = 0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (int64_t i = first; i < ni; i += stride) {
-    const double g = tf[i] - td[i];
-    const double m = muD[i] + g;
-    muD[i] = m;
-    s0 += g * g; s1 += m * m;
-  }
-  for (int64_t i = first; i < nden; i += stride) s2 += den[i] * den[i];
-  s0 = block256_sum(s0, sh4); s1 = block256_sum(s1, sh4); s2 = block256_sum(s2, sh4);
-  if (threadIdx.x == 0) {
-    if (gridDim.x == 1) { out[0] = s0; out[1] = s1; out[3] = s2; }
-    else { double* w = ws + 3 * (int64_t)blockIdx.x; w[0] = s0; w[1] = s1; w[2] = s2; }
-  }
-}
-__global__ void coupling_dual_fin_k(double* out, const double* ws, int nb, const AdmmCtl* ctl) {
-  if (ctl != nullptr && ctl->active == 0) return;
-  if (threadIdx.x >= 3) return;
-  double t = 0.0;
-  for (int b = 0; b < nb; ++b) t += ws[3 * b + threadIdx.x];
-  out[threadIdx.x == 2 ? 3 : threadIdx.x] = t;
-}
-
-// Delta(k,:) = sum_j rho_j(k) * (C_j + mu_j)(k,:) / sum_j rho_j(k)   (:661-675): rho_j is a K-vector for a PARAFAC2
-// C mode (vec[j] = 1) and a scalar otherwise
-struct RowMeanArgs { const double* fac[8]; const double* mu[8]; const double* rho[8]; int vec[8]; int n; int64_t rows; int cols; };
-__global__ void coupling_rowmean_k(double* Delta, RowMeanArgs a, const AdmmCtl* ctl) {
-  if (ctl != nullptr && ctl->active == 0) return;
-  const int64_t tot = a.rows * a.cols;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < tot; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t k = e % a.rows;
-    double acc = 0.0, sr = 0.0;
-    for (int j = 0; j < a.n; ++j) {
-      const double rj = a.vec[j] ? a.rho[j][k] : a.rho[j][0];
-      acc += rj * (a.fac[j][e] + a.mu[j][e]);
-      sr += rj;
-    }
-    Delta[e] = 1.0 / sr * acc;
-  }
-}
-
-// out(k,c) = rho_k * in(k,c)  (rows of a K x cols matrix scaled by the rho vector of a PARAFAC2 C mode)
-__global__ void rows_scale_k(double* out, const double* in, const double* rho, int64_t rows, int64_t cols,
-                             const AdmmCtl* ctl) {
-  if (ctl != nullptr && ctl->active == 0) return;
-  const int64_t tot = rows * cols;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < tot; e += (int64_t)gridDim.x * blockDim.x)
-    out[e] = rho[e % rows] * in[e];
-}
-static void rows_scale(double* out, const double* in, const double* rho, int64_t rows, int64_t cols, const AdmmCtl* ctl,
-                       hipStream_t s) {
-  int64_t nb = cdiv(rows * cols, 256);
-  if (nb > 1024) nb = 1024;
-  rows_scale_k<<<(unsigned)nb, 256, 0, s>>>(out, in, rho, rows, cols, ctl);
-  AO_KERNEL_CHECK();
-}
-// Delta(k,:) = BB(k,:) / (AA + rho_k*AAA)   (:957-961): one workgroup per row, q x q system in LDS
-__global__ void delta_rowwise_solve_k(double* Delta, const double* BB, int64_t rows, int q, const double* AA,
-                                      const double* AAA, const double* rho, AdmmCtl* ctl) {
-  if (ctl->active == 0) return;
-  extern __shared__ double sh[];                      // q*q matrix, then q right-hand side
-  double* M = sh;
-  double* x = sh + q * q;
-  const int64_t k = blockIdx.x;
-  for (int e = threadIdx.x; e < q * q; e += blockDim.x) M[e] = AA[e] + rho[k] * AAA[e];
-  for (int c = threadIdx.x; c < q; c += blockDim.x) x[c] = BB[k + rows * c];
-  __syncthreads();
-  const bool ok = chol_lds(M, q);
-  if (!ok) { if (threadIdx.x == 0) ctl->notpd = 1; return; }
-  if (threadIdx.x == 0) {                             // x * inv(L*L'): forward with L, backward with L'
-    for (int c = 0; c < q; ++c) {
-      double v = x[c];
-      for (int p = 0; p < c; ++p) v -= M[c + q * p] * x[p];
-      x[c] = v / M[c + q * c];
-    }
-    for (int c = q - 1; c >= 0; --c) {
-      double v = x[c];
-      for (int p = c + 1; p < q; ++p) v -= M[p + q * c] * x[p];
-      x[c] = v / M[c + q * c];
-    }
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < q; c += blockDim.x) Delta[k + rows * c] = x[c];
-}
-
-struct AAArgs { const double* H[8]; const double* rho[8]; int R[8]; int n; int Rc; };
-__global__ void coupling_AA_k(double* AA, AAArgs a) {
-  // AA = sum_j rho_j * H_j * H_j'   (:941-954 ; :1033-1047 with H2 and the common rhoC)
-  const int Rc = a.Rc;
-  for (int e = threadIdx.x; e < Rc * Rc; e += blockDim.x) {
-    const int i = e % Rc, k = e / Rc;
-    double acc = 0.0;
-    for (int j = 0; j < a.n; ++j) {
-      double t = 0.0;
-      for (int q = 0; q < a.R[j]; ++q) t += a.H[j][i + Rc * q] * a.H[j][k + Rc * q];
-      acc += a.rho[j][0] * t;
-    }
-    AA[e] = acc;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Couplings of type 0 (C = Delta) and 4 (C = Delta*H) are row-local: row i of every coupled factor, of Delta and of
-// the duals only ever meets row i.  One thread per row then does a whole step in registers, which turns the
-// 27 launches of an inner iteration (two modes, generic path below) into 11.  RMAX bounds both R and cols(Delta).
-struct RowCouple {
-  // per mode
-  const double* Aeff; const double* L; const double* rho; const double* H;   // H: q x R (type 4), unused for type 0
-  double* fac; double* muD; const double* Z; const double* mu;
-  int R, constrained;
-};
-template <int RMAX>
-__global__ __launch_bounds__(64) void couple_primal_rows_k(RowCouple m, const double* Delta, int64_t rows, int q, int type,
-                                                           const AdmmCtl* ctl) {
-  if (ctl != nullptr && ctl->active == 0) return;
-  extern __shared__ double sh[];                      // L (R*R), H (q*R)
-  const int R = m.R;
-  double* Lsh = sh;
-  double* Hsh = sh + R * R;
-  for (int e = threadIdx.x; e < R * R; e += blockDim.x) Lsh[e] = m.L[e];
-  if (type == 4)
-    for (int e = threadIdx.x; e < q * R; e += blockDim.x) Hsh[e] = m.H[e];
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows) return;
-  const double rh = m.rho[0] / 2;
-  double d[RMAX], x[RMAX];
-#pragma unroll
-  for (int c = 0; c < RMAX; ++c) d[c] = c < q ? Delta[i + rows * c] : 0.0;
-#pragma unroll
-  for (int r = 0; r < RMAX; ++r) {
-    x[r] = 0.0;
-    if (r < R) {
-      double td;
-      if (type == 4) {                                // (Delta*H)(i,r)  (:925)
-        td = 0.0;
-#pragma unroll
-        for (int c = 0; c < RMAX; ++c)
-          if (c < q) td += d[c] * Hsh[c + q * r];
-      } else {
-        td = d[r];                                    // :647
-      }
-      double v = m.Aeff[i + rows * r] + rh * (td - m.muD[i + rows * r]);
-      if (m.constrained) v += rh * (m.Z[i + rows * r] - m.mu[i + rows * r]);
-      x[r] = v;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < RMAX; ++r)                      // x * inv(L*L')  (:651, :929)
-    if (r < R) {
-      double v = x[r];
-#pragma unroll
-      for (int p = 0; p < RMAX; ++p)
-        if (p < r) v -= Lsh[r + R * p] * x[p];
-      x[r] = v / Lsh[r + R * r];
-    }
-#pragma unroll
-  for (int r = RMAX - 1; r >= 0; --r)
-    if (r < R) {
-      double v = x[r];
-#pragma unroll
-      for (int p = 0; p < RMAX; ++p)
-        if (p > r && p < R) v -= Lsh[p + R * r] * x[p];
-      x[r] = v / Lsh[r + R * r];
-    }
-#pragma unroll
-  for (int r = 0; r < RMAX; ++r)
-    if (r < R) m.fac[i + rows * r] = x[r];
-}
-
-struct RowDelta {
-  const double* fac[8]; const double* muD[8]; const double* rho[8]; const double* H[8];
-  int R[8];
-  int n;
-};
-// Delta_old = Delta ; Delta = weighted mean (type 0, :661-675) or BB / AA (type 4, :939-963) ; dD = Delta - Delta_old
-template <int RMAX>
-__global__ __launch_bounds__(64) void couple_delta_rows_k(RowDelta a, double* Delta, double* DeltaOld, double* dD,
-                                                          const double* coefs, const double* LAA, int64_t rows, int q,
-                                                          int type, const AdmmCtl* ctl) {
-  if (ctl != nullptr && ctl->active == 0) return;
-  extern __shared__ double sh[];                      // LAA (q*q), then H_j (q*R_j) back to back
-  double* Lsh = sh;
-  if (type == 4) {
-    for (int e = threadIdx.x; e < q * q; e += blockDim.x) Lsh[e] = LAA[e];
-    int off = q * q;
-    for (int j = 0; j < a.n; ++j) {
-      for (int e = threadIdx.x; e < q * a.R[j]; e += blockDim.x) sh[off + e] = a.H[j][e];
-      off += q * a.R[j];
-    }
-  }
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows) return;
-  double bb[RMAX];
-#pragma unroll
-  for (int c = 0; c < RMAX; ++c) bb[c] = 0.0;
-  int off = q * q;
-  for (int j = 0; j < a.n; ++j) {
-    if (type == 4) {
-      const double rj = a.rho[j][0];
-      double t[RMAX];
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r) t[r] = r < a.R[j] ? a.fac[j][i + rows * r] + a.muD[j][i + rows * r] : 0.0;
-      const double* Hj = sh + off;
-#pragma unroll
-      for (int c = 0; c < RMAX; ++c)
-        if (c < q) {
-          double acc = 0.0;
-#pragma unroll
-          for (int r = 0; r < RMAX; ++r)
-            if (r < a.R[j]) acc += t[r] * Hj[c + q * r];
-          bb[c] = (j == 0 ? 0.0 : bb[c]) + rj * acc;                               // :955, same order as the gemm path
-        }
-      off += q * a.R[j];
-    } else {
-      const double cj = coefs[j];                     // rho_j / sum rho
-#pragma unroll
-      for (int c = 0; c < RMAX; ++c)
-        if (c < q) {
-          const double v = cj * a.fac[j][i + rows * c] + cj * a.muD[j][i + rows * c];
-          bb[c] = j == 0 ? v : bb[c] + v;
-        }
-    }
-  }
-  if (type == 4) {                                    // Delta(i,:) = bb * inv(LAA*LAA')
-#pragma unroll
-    for (int c = 0; c < RMAX; ++c)
-      if (c < q) {
-        double v = bb[c];
-#pragma unroll
-        for (int p = 0; p < RMAX; ++p)
-          if (p < c) v -= Lsh[c + q * p] * bb[p];
-        bb[c] = v / Lsh[c + q * c];
-      }
-#pragma unroll
-    for (int c = RMAX - 1; c >= 0; --c)
-      if (c < q) {
-        double v = bb[c];
-#pragma unroll
-        for (int p = 0; p < RMAX; ++p)
-          if (p > c && p < q) v -= Lsh[p + q * c] * bb[p];
-        bb[c] = v / Lsh[c + q * c];
-      }
-  }
-#pragma unroll
-  for (int c = 0; c < RMAX; ++c)
-    if (c < q) {
-      const double old = Delta[i + rows * c];
-      DeltaOld[i + rows * c] = old;
-      Delta[i + rows * c] = bb[c];
-      dD[i + rows * c] = bb[c] - old;
-    }
-}
-
-// mu_Delta += C - Sd(Delta) and the four sums of the coupling residuals (:1099-1115, :1175-1191) for one mode:
-// out[0] = ||C - Sd(Delta)||^2, out[1] = ||mu_Delta||^2, out[2] = ||Sd(dD)||^2, out[3] = ||C||^2
-template <int RMAX>
-__global__ __launch_bounds__(256) void couple_dual_rows_k(RowCouple m, const double* Delta, const double* dD, int64_t rows,
-                                                          int q, int type, double* out, double* ws, const AdmmCtl* ctl) {
-  if (ctl != nullptr && ctl->active == 0) return;
-  extern __shared__ double sh[];                      // H (q*R)
-  __shared__ double sh4[4];
-  const int R = m.R;
-  if (type == 4)
-    for (int e = threadIdx.x; e < q * R; e += blockDim.x) sh[e] = m.H[e];
-  __syncthreads();
-  double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (int64_t)gridDim.x * blockDim.x) {
-    double d[RMAX], dd[RMAX];
-#pragma unroll
-    for (int c = 0; c < RMAX; ++c) { d[c] = c < q ? Delta[i + rows * c] : 0.0; dd[c] = c < q ? dD[i + rows * c] : 0.0; }
-#pragma unroll
-    for (int r = 0; r < RMAX; ++r)
-      if (r < R) {
-        double td, tdd;
-        if (type == 4) {
-          td = 0.0; tdd = 0.0;
-#pragma unroll
-          for (int c = 0; c < RMAX; ++c)
-            if (c < q) { td += d[c] * sh[c + q * r]; tdd += dd[c] * sh[c + q * r]; }
-        } else { td = d[r]; tdd = dd[r]; }
-        const double f = m.fac[i + rows * r];
-        const double g = f - td;
-        const double mm = m.muD[i + rows * r] + g;                                  // :679, :967
-        m.muD[i + rows * r] = mm;
-        s0 += g * g; s1 += mm * mm; s2 += tdd * tdd; s3 += f * f;
-      }
-  }
-  s0 = block256_sum(s0, sh4); s1 = block256_sum(s1, sh4); s2 = block256_sum(s2, sh4); s3 = block256_sum(s3, sh4);
-  if (threadIdx.x == 0) {
-    double* o = gridDim.x == 1 ? out : ws + 4 * (int64_t)blockIdx.x;
-    o[0] = s0; o[1] = s1; o[2] = s2; o[3] = s3;
-  }
-}
-__global__ void couple_dual_fin_k(double* out, const double* ws, int nb, const AdmmCtl* ctl) {
-  if (ctl != nullptr && ctl->active == 0) return;
-  if (threadIdx.x >= 4) return;
-  double t = 0.0;
-  for (int b = 0; b < nb; ++b) t += ws[4 * b + threadIdx.x];
-  out[threadIdx.x] = t;
-}
-
-// ---------------------------------------------------------------------------
-// The whole inner loop of a row-local coupling (types 0 and 4) in ONE launch, for the sizes the example scripts use
-// (rows of Delta up to a few thousand, ranks up to 16).  For these couplings every step of an inner iteration --
-// the primal solves of all coupled modes (:647-651, :925-929), the Delta update (:661-675, :939-963), the coupling
-// duals (:679, :967) and, with an element-/row-wise prox, update_constraint (:1420-1429) -- touches row i of every
-// matrix only, so thread i carries row i through the iteration without meeting another thread; the workgroup meets
-// once per iteration to add up the residual sums (:1099-1115, :1175-1191, :1079-1096) and to evaluate the while
-// condition (:630).  The launch-per-step form (couple_primal / couple_delta / couple_dual + constraint_update +
-// finalize: 12 launches per inner iteration for two constrained modes) is kept for larger problems.
-struct WgLoopMode {
-  const double* Aeff; const double* L; const double* rho; const double* H;
-  double *fac, *muD, *Z, *mu, *Zold;
-  double* slots;        // 8 residual sums of this mode (see FinalizeArgs)
-  int R, constrained, ptype;
-  double p0, p1;
-};
-struct WgLoopArgs {
-  WgLoopMode m[4];
-  int n, q, type, max_inner;
-  int64_t rows;
-  double *Delta, *DeltaOld, *dD;
-  const double* coefs;
-  const double* LAA;
-  double tol_pr_coupl, tol_pr_constr, tol_du_coupl, tol_du_constr;
-  AdmmCtl* ctl;
-  int self_start = 0;       // registers kernel: opens the loop itself and takes rho_j / sum rho from the modes' rho
-                            // (no ctl_reset / coupling_coefs_k launch in front of it)
-};
-template <int RMAX>
-__global__ __launch_bounds__(256) void couple_loop_wg_k(WgLoopArgs a) {
-  extern __shared__ double sh[];                      // LAA (q*q) | per mode: L (R*R), H (q*R)
-  __shared__ double red[4][32];
-  __shared__ int go;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int q = a.q, type = a.type;
-  const int64_t rows = a.rows;
-  int offL[4], offH[4];
-  {
-    int off = q * q;
-    for (int j = 0; j < a.n; ++j) { offL[j] = off; off += a.m[j].R * a.m[j].R; offH[j] = off; off += q * a.m[j].R; }
-    if (type == 4)
-      for (int e = t; e < q * q; e += 256) sh[e] = a.LAA[e];
-    for (int j = 0; j < a.n; ++j) {
-      const int R = a.m[j].R;
-      for (int e = t; e < R * R; e += 256) sh[offL[j] + e] = a.m[j].L[e];
-      if (type == 4)
-        for (int e = t; e < q * R; e += 256) sh[offH[j] + e] = a.m[j].H[e];
-    }
-  }
-  if (t == 0) go = a.ctl->active;
-  __syncthreads();
-  int it = 0;
-  while (go) {
-    double sums[4][8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) sums[j][k] = 0.0;
-    for (int64_t i = t; i < rows; i += 256) {
-      double d[RMAX];
-#pragma unroll
-      for (int c = 0; c < RMAX; ++c) d[c] = c < q ? a.Delta[i + rows * c] : 0.0;
-      // ---- primal updates
-      for (int j = 0; j < a.n; ++j) {
-        const WgLoopMode& m = a.m[j];
-        const int R = m.R;
-        const double* Lsh = sh + offL[j];
-        const double* Hsh = sh + offH[j];
-        const double rh = m.rho[0] / 2;
-        double x[RMAX];
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r) {
-          x[r] = 0.0;
-          if (r < R) {
-            double td;
-            if (type == 4) {                          // (Delta*H)(i,r)  (:925)
-              td = 0.0;
-#pragma unroll
-              for (int c = 0; c < RMAX; ++c)
-                if (c < q) td += d[c] * Hsh[c + q * r];
-            } else {
-              td = d[r];                              // :647
-            }
-            double v = m.Aeff[i + rows * r] + rh * (td - m.muD[i + rows * r]);
-            if (m.constrained) v += rh * (m.Z[i + rows * r] - m.mu[i + rows * r]);
-            x[r] = v;
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r)                // x * inv(L*L')  (:651, :929)
-          if (r < R) {
-            double v = x[r];
-#pragma unroll
-            for (int p = 0; p < RMAX; ++p)
-              if (p < r) v -= Lsh[r + R * p] * x[p];
-            x[r] = v / Lsh[r + R * r];
-          }
-#pragma unroll
-        for (int r = RMAX - 1; r >= 0; --r)
-          if (r < R) {
-            double v = x[r];
-#pragma unroll
-            for (int p = 0; p < RMAX; ++p)
-              if (p > r && p < R) v -= Lsh[p + R * r] * x[p];
-            x[r] = v / Lsh[r + R * r];
-          }
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r)
-          if (r < R) m.fac[i + rows * r] = x[r];
-      }
-      // ---- Delta
-      double bb[RMAX];
-#pragma unroll
-      for (int c = 0; c < RMAX; ++c) bb[c] = 0.0;
-      for (int j = 0; j < a.n; ++j) {
-        const WgLoopMode& m = a.m[j];
-        if (type == 4) {
-          const double rj = m.rho[0];
-          double tt[RMAX];
-#pragma unroll
-          for (int r = 0; r < RMAX; ++r) tt[r] = r < m.R ? m.fac[i + rows * r] + m.muD[i + rows * r] : 0.0;
-          const double* Hj = sh + offH[j];
-#pragma unroll
-          for (int c = 0; c < RMAX; ++c)
-            if (c < q) {
-              double acc = 0.0;
-#pragma unroll
-              for (int r = 0; r < RMAX; ++r)
-                if (r < m.R) acc += tt[r] * Hj[c + q * r];
-              bb[c] = (j == 0 ? 0.0 : bb[c]) + rj * acc;                           // :955
-            }
-        } else {
-          const double cj = a.coefs[j];               // rho_j / sum rho
-#pragma unroll
-          for (int c = 0; c < RMAX; ++c)
-            if (c < q) {
-              const double v = cj * m.fac[i + rows * c] + cj * m.muD[i + rows * c];
-              bb[c] = j == 0 ? v : bb[c] + v;
-            }
-        }
-      }
-      if (type == 4) {                                // Delta(i,:) = bb * inv(LAA*LAA')
-        const double* Lsh = sh;
-#pragma unroll
-        for (int c = 0; c < RMAX; ++c)
-          if (c < q) {
-            double v = bb[c];
-#pragma unroll
-            for (int p = 0; p < RMAX; ++p)
-              if (p < c) v -= Lsh[c + q * p] * bb[p];
-            bb[c] = v / Lsh[c + q * c];
-          }
-#pragma unroll
-        for (int c = RMAX - 1; c >= 0; --c)
-          if (c < q) {
-            double v = bb[c];
-#pragma unroll
-            for (int p = 0; p < RMAX; ++p)
-              if (p > c && p < q) v -= Lsh[p + q * c] * bb[p];
-            bb[c] = v / Lsh[c + q * c];
-          }
-      }
-      double dd[RMAX];
-#pragma unroll
-      for (int c = 0; c < RMAX; ++c) {
-        dd[c] = 0.0;
-        if (c < q) {
-          a.DeltaOld[i + rows * c] = d[c];
-          a.Delta[i + rows * c] = bb[c];
-          dd[c] = bb[c] - d[c];
-          a.dD[i + rows * c] = dd[c];
-        }
-      }
-      // ---- coupling duals, constraints, residual sums
-      for (int j = 0; j < a.n; ++j) {
-        const WgLoopMode& m = a.m[j];
-        const int R = m.R;
-        const double* Hsh = sh + offH[j];
-        double f[RMAX];
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r) {
-          f[r] = 0.0;
-          if (r < R) {
-            double td, tdd;
-            if (type == 4) {
-              td = 0.0; tdd = 0.0;
-#pragma unroll
-              for (int c = 0; c < RMAX; ++c)
-                if (c < q) { td += bb[c] * Hsh[c + q * r]; tdd += dd[c] * Hsh[c + q * r]; }
-            } else { td = bb[r]; tdd = dd[r]; }
-            f[r] = m.fac[i + rows * r];
-            const double g = f[r] - td;
-            const double mm = m.muD[i + rows * r] + g;                              // :679, :967
-            m.muD[i + rows * r] = mm;
-            sums[j][4] += g * g; sums[j][5] += mm * mm; sums[j][6] += tdd * tdd; sums[j][7] += f[r] * f[r];
-          }
-        }
-        if (m.constrained) {                          // update_constraint (:1420-1429)
-          const double rho = m.rho[0];
-          double zo[RMAX], mu[RMAX], z[RMAX];
-#pragma unroll
-          for (int r = 0; r < RMAX; ++r) {
-            zo[r] = r < R ? m.Z[i + rows * r] : 0.0;
-            mu[r] = r < R ? m.mu[i + rows * r] : 0.0;
-            z[r] = f[r] + mu[r];
-          }
-          if (m.ptype == AOADMM_C_SIMPLEX_ROW) {
-            simplex_regs<RMAX>(z, R, m.p0);
-          } else {
-#pragma unroll
-            for (int r = 0; r < RMAX; ++r) z[r] = prox_elem(m.ptype, z[r], m.p0, m.p1, rho);
-          }
-#pragma unroll
-          for (int r = 0; r < RMAX; ++r)
-            if (r < R) {
-              const double mn = mu[r] + f[r] - z[r];
-              m.Zold[i + rows * r] = zo[r];
-              m.Z[i + rows * r] = z[r];
-              m.mu[i + rows * r] = mn;
-              const double dz = z[r] - zo[r];
-              sums[j][0] += (f[r] - z[r]) * (f[r] - z[r]); sums[j][1] += f[r] * f[r]; sums[j][2] += mn * mn; sums[j][3] += dz * dz;
-            }
-        } else {
-#pragma unroll
-          for (int r = 0; r < RMAX; ++r) sums[j][1] += f[r] * f[r];
-        }
-      }
-    }
-    // ---- the workgroup's sums (fixed order: lanes by DPP tree, then the four waves in order)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const double v = wave_sum(sums[j][k]);
-        if (lane == 0) red[w][j * 8 + k] = v;
-      }
-    __syncthreads();
-    if (t < 32) {
-      const double tot = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-      red[0][t] = tot;
-      const int j = t >> 3;
-      if (j < a.n) a.m[j].slots[t & 7] = tot;
-    }
-    __syncthreads();
-    if (t == 0) {                                     // eval_res_ADMM_coupl_case0/4 + eval_res_ADMM_constr, while condition
-      double prc = 0, duc = 0, prz = 0, duz = 0;
-      int nz = 0;
-      for (int j = 0; j < a.n; ++j) {
-        const double* sj = &red[0][j * 8];
-        prc += sqrt(sj[4]) / sqrt(sj[7]);
-        const double sc = sqrt(sj[5]);
-        duc += sc > 0 ? sqrt(sj[6]) / sc : sqrt(sj[6]);
-        if (a.m[j].constrained) {
-          prz += sqrt(sj[0]) / sqrt(sj[1]);
-          const double sz = sqrt(sj[2]);
-          duz += sz > 0 ? sqrt(sj[3]) / sz : sqrt(sj[3]);
-          ++nz;
-        }
-      }
-      prc /= a.n; duc /= a.n;
-      if (nz) { prz /= nz; duz /= nz; }
-      ++it;
-      a.ctl->res[0] = prc; a.ctl->res[1] = prz; a.ctl->res[2] = duc; a.ctl->res[3] = duz;
-      a.ctl->iters = it;
-      const int cont = (it < a.max_inner && (prc > a.tol_pr_coupl || prz > a.tol_pr_constr || duc > a.tol_du_coupl ||
-                                             duz > a.tol_du_constr)) ? 1 : 0;
-      a.ctl->active = cont;
-      go = cont;
-    }
-    __syncthreads();
-  }
-}
-
-// Register-resident form of couple_loop_wg_k for rows <= 256 (one row per thread) and NM coupled modes: the rows of A,
-// fac, mu_Delta, Z, mu of every coupled mode and the row of Delta are loaded once, live in registers for the whole
-// loop and are stored once.  An inner iteration is then arithmetic plus one workgroup reduction, with no memory round
-// trip (the global-memory form re-reads its own stores from L2 several times per iteration: 25 us per iteration
-// against a few us here at 50 rows x 4 columns).
-// Everything is padded to RMAX with zeros -- the small matrices in LDS (L_j, H_j, L_AA as RMAX x RMAX blocks), the
-// reciprocal diagonals (0 beyond the rank) and the register rows -- so the loop body is straight-line code: a padded
-// column contributes exact zeros to every sum and is never stored.  (The first version tested `r < R` and `c < q` at
-// every step: ~5000 instructions, 700 of them branches, 10 us per inner iteration; PMC: 15 cycles per instruction on
-// the one wave per SIMD.)  T4: coupling type 4 (C = Delta*H), else type 0 (C = Delta).
-template <int RMAX, int NM, bool T4>
-__global__ __launch_bounds__(256) void couple_loop_wg_regs_k(WgLoopArgs a) {
-  constexpr int RR = RMAX * RMAX;
-  __shared__ double Lsh[NM][RR];                      // L_j, column-major with leading dimension RMAX
-  __shared__ double Hsh[NM][RR];                      // H_j(c, r) at c + RMAX*r
-  __shared__ double LAAsh[RR];
-  __shared__ double red[4][8 * NM];
-  __shared__ double invd[NM + 1][RMAX];               // reciprocal diagonals of L_j and of LAA: the substitutions multiply
-  __shared__ int go;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int q = a.q;
-  const int64_t rows = a.rows;
-  const int64_t i = t;
-  const bool have = i < rows;
-  const int64_t ic = have ? i : rows - 1;             // clamped: padding threads compute on a valid row, store nothing
-  for (int e = t; e < RR; e += 256) {
-    const int r = e % RMAX, c = e / RMAX;
-    LAAsh[e] = (T4 && r < q && c < q) ? a.LAA[r + q * c] : 0.0;
-#pragma unroll
-    for (int j = 0; j < NM; ++j) {
-      const int R = a.m[j].R;
-      Lsh[j][e] = (r < R && c < R) ? a.m[j].L[r + R * c] : 0.0;
-      Hsh[j][e] = (T4 && r < q && c < R) ? a.m[j].H[r + q * c] : 0.0;
-    }
-  }
-  __syncthreads();
-  if (t < RMAX) {
-#pragma unroll
-    for (int j = 0; j < NM; ++j) invd[j][t] = t < a.m[j].R ? 1.0 / Lsh[j][t + RMAX * t] : 0.0;
-    invd[NM][t] = (T4 && t < q) ? 1.0 / LAAsh[t + RMAX * t] : 0.0;
-  }
-  double d[RMAX], av[NM][RMAX], f[NM][RMAX], md[NM][RMAX], z[NM][RMAX], mu[NM][RMAX], zo[NM][RMAX], rh[NM], rho[NM], cj[NM];
-  ElemProx ep[NM];
-#pragma unroll
-  for (int c = 0; c < RMAX; ++c) d[c] = c < q ? a.Delta[ic + rows * c] : 0.0;
-#pragma unroll
-  for (int j = 0; j < NM; ++j) {
-    const WgLoopMode& m = a.m[j];
-    rho[j] = m.rho[0];
-    rh[j] = rho[j] / 2;
-    cj[j] = (T4 || a.self_start) ? 0.0 : a.coefs[j];  // rho_j / sum rho
-    ep[j] = elem_prox_of(m.ptype, m.p0, m.p1, rho[j]);
-#pragma unroll
-    for (int r = 0; r < RMAX; ++r) {
-      const bool ok = r < m.R;
-      const int64_t o = ic + rows * (ok ? r : 0);
-      av[j][r] = ok ? m.Aeff[o] : 0.0;
-      f[j][r] = ok ? m.fac[o] : 0.0;
-      md[j][r] = ok ? m.muD[o] : 0.0;
-      z[j][r] = (ok && m.constrained) ? m.Z[o] : 0.0;
-      mu[j][r] = (ok && m.constrained) ? m.mu[o] : 0.0;
-      zo[j][r] = z[j][r];
-    }
-  }
-  if (!T4 && a.self_start) {                          // coupling_coefs_k's arithmetic: 1 / sum(rho) * rho_j, modes in order
-    double srho = 0.0;
-#pragma unroll
-    for (int j = 0; j < NM; ++j) srho += rho[j];
-#pragma unroll
-    for (int j = 0; j < NM; ++j) cj[j] = 1.0 / srho * rho[j];
-  }
-  double dold[RMAX], dd[RMAX];
-#pragma unroll
-  for (int c = 0; c < RMAX; ++c) { dold[c] = d[c]; dd[c] = 0.0; }
-  if (t == 0) go = a.self_start ? 1 : a.ctl->active;
-  __syncthreads();
-  int it = 0;
-  bool ran = false;
-  while (go) {
-    ran = true;
-    double sums[NM][8];
-#pragma unroll
-    for (int j = 0; j < NM; ++j)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) sums[j][k] = 0.0;
-    // ---- primal updates
-#pragma unroll
-    for (int j = 0; j < NM; ++j) {
-      const WgLoopMode& m = a.m[j];
-      double x[RMAX];
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r) {
-        double td;
-        if (T4) {                                     // (Delta*H)(i,r)  (:925)
-          td = 0.0;
-#pragma unroll
-          for (int c = 0; c < RMAX; ++c) td += d[c] * Hsh[j][c + RMAX * r];
-        } else {
-          td = d[r];                                  // :647
-        }
-        double v = av[j][r] + rh[j] * (td - md[j][r]);
-        if (m.constrained) v += rh[j] * (z[j][r] - mu[j][r]);
-        x[r] = v;
-      }
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r) {                // x * inv(L*L')  (:651, :929)
-        double v = x[r];
-#pragma unroll
-        for (int p = 0; p < r; ++p) v -= Lsh[j][r + RMAX * p] * x[p];
-        x[r] = v * invd[j][r];
-      }
-#pragma unroll
-      for (int r = RMAX - 1; r >= 0; --r) {
-        double v = x[r];
-#pragma unroll
-        for (int p = r + 1; p < RMAX; ++p) v -= Lsh[j][p + RMAX * r] * x[p];
-        x[r] = v * invd[j][r];
-      }
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r) f[j][r] = x[r];
-    }
-    // ---- Delta
-    double bb[RMAX];
-#pragma unroll
-    for (int c = 0; c < RMAX; ++c) bb[c] = 0.0;
-#pragma unroll
-    for (int j = 0; j < NM; ++j) {
-      if (T4) {
-#pragma unroll
-        for (int c = 0; c < RMAX; ++c) {
-          double acc = 0.0;
-#pragma unroll
-          for (int r = 0; r < RMAX; ++r) acc += (f[j][r] + md[j][r]) * Hsh[j][c + RMAX * r];
-          bb[c] = (j == 0 ? 0.0 : bb[c]) + rho[j] * acc;                           // :955
-        }
-      } else {
-#pragma unroll
-        for (int c = 0; c < RMAX; ++c) {
-          const double v = cj[j] * f[j][c] + cj[j] * md[j][c];
-          bb[c] = j == 0 ? v : bb[c] + v;
-        }
-      }
-    }
-    if (T4) {                                         // Delta(i,:) = bb * inv(LAA*LAA')
-#pragma unroll
-      for (int c = 0; c < RMAX; ++c) {
-        double v = bb[c];
-#pragma unroll
-        for (int p = 0; p < c; ++p) v -= LAAsh[c + RMAX * p] * bb[p];
-        bb[c] = v * invd[NM][c];
-      }
-#pragma unroll
-      for (int c = RMAX - 1; c >= 0; --c) {
-        double v = bb[c];
-#pragma unroll
-        for (int p = c + 1; p < RMAX; ++p) v -= LAAsh[p + RMAX * c] * bb[p];
-        bb[c] = v * invd[NM][c];
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < RMAX; ++c) {
-      const double nv = (T4 || c < q) ? bb[c] : 0.0;  // type 0: columns beyond q carry nothing
-      dold[c] = d[c];
-      dd[c] = nv - d[c];
-      d[c] = nv;
-    }
-    // ---- coupling duals, constraints, residual sums
-#pragma unroll
-    for (int j = 0; j < NM; ++j) {
-      const WgLoopMode& m = a.m[j];
-      const int R = m.R;
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r) {
-        double td, tdd;
-        if (T4) {
-          td = 0.0; tdd = 0.0;
-#pragma unroll
-          for (int c = 0; c < RMAX; ++c) { td += d[c] * Hsh[j][c + RMAX * r]; tdd += dd[c] * Hsh[j][c + RMAX * r]; }
-        } else { td = r < R ? d[r] : 0.0; tdd = r < R ? dd[r] : 0.0; }
-        const double g = f[j][r] - td;
-        const double mm = md[j][r] + g;                                             // :679, :967
-        md[j][r] = mm;
-        if (have) { sums[j][4] += g * g; sums[j][5] += mm * mm; sums[j][6] += tdd * tdd; sums[j][7] += f[j][r] * f[j][r]; }
-      }
-      if (m.constrained) {                            // update_constraint (:1420-1429)
-        double zn[RMAX];
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r) { zo[j][r] = z[j][r]; zn[r] = f[j][r] + mu[j][r]; }
-        if (m.ptype == AOADMM_C_SIMPLEX_ROW) {
-          simplex_regs<RMAX>(zn, R, m.p0);
-        } else {
-#pragma unroll
-          for (int r = 0; r < RMAX; ++r) zn[r] = r < R ? elem_prox(ep[j], zn[r]) : 0.0;
-        }
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r) {
-          const double mn = mu[j][r] + f[j][r] - zn[r];
-          const double dz = zn[r] - zo[j][r];
-          if (have) {
-            sums[j][0] += (f[j][r] - zn[r]) * (f[j][r] - zn[r]); sums[j][1] += f[j][r] * f[j][r]; sums[j][2] += mn * mn;
-            sums[j][3] += dz * dz;
-          }
-          z[j][r] = zn[r];
-          mu[j][r] = mn;
-        }
-      } else if (have) {
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r) sums[j][1] += f[j][r] * f[j][r];
-      }
-    }
-    // ---- the workgroup's sums (fixed order: lanes by DPP tree, then the four waves in order)
-#pragma unroll
-    for (int j = 0; j < NM; ++j)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const double v = wave_sum(sums[j][k]);
-        if (lane == 0) red[w][j * 8 + k] = v;
-      }
-    __syncthreads();
-    if (t < 8 * NM) {
-      const double tot = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-      red[0][t] = tot;
-      a.m[t >> 3].slots[t & 7] = tot;
-    }
-    __syncthreads();
-    // eval_res_ADMM_coupl_case0/4 + eval_res_ADMM_constr: the 4*NM ratios (two square roots and a division each, ~100
-    // dependent fp64 instructions) on 4*NM lanes side by side, then one lane adds them in mode order and decides --
-    // the whole workgroup waits for this
-    if (t < 4 * NM) {
-      const int j = t >> 2, which = t & 3;            // 0: primal coupling, 1: dual coupling, 2: primal constr., 3: dual constr.
-      const double* sj = &red[0][j * 8];
-      double v;
-      if (which == 0) v = sqrt(sj[4]) / sqrt(sj[7]);
-      else if (which == 2) v = sqrt(sj[0]) / sqrt(sj[1]);
-      else {
-        const double num = sqrt(which == 1 ? sj[6] : sj[3]), sc = sqrt(which == 1 ? sj[5] : sj[2]);
-        v = sc > 0 ? num / sc : num;
-      }
-      red[1][t] = v;
-    }
-    __syncthreads();
-    if (t == 0) {                                     // while condition
-      double prc = 0, duc = 0, prz = 0, duz = 0;
-      int nz = 0;
-      for (int j = 0; j < NM; ++j) {
-        prc += red[1][4 * j];
-        duc += red[1][4 * j + 1];
-        if (a.m[j].constrained) {
-          prz += red[1][4 * j + 2];
-          duz += red[1][4 * j + 3];
-          ++nz;
-        }
-      }
-      prc /= NM; duc /= NM;
-      if (nz) { prz /= nz; duz /= nz; }
-      ++it;
-      a.ctl->res[0] = prc; a.ctl->res[1] = prz; a.ctl->res[2] = duc; a.ctl->res[3] = duz;
-      a.ctl->iters = it;
-      const int cont = (it < a.max_inner && (prc > a.tol_pr_coupl || prz > a.tol_pr_constr || duc > a.tol_du_coupl ||
-                                             duz > a.tol_du_constr)) ? 1 : 0;
-      a.ctl->active = cont;
-      go = cont;
-    }
-    __syncthreads();
-  }
-  if (!ran || !have) return;
-#pragma unroll
-  for (int c = 0; c < RMAX; ++c)
-    if (c < q) { a.Delta[i + rows * c] = d[c]; a.DeltaOld[i + rows * c] = dold[c]; a.dD[i + rows * c] = dd[c]; }
-#pragma unroll
-  for (int j = 0; j < NM; ++j) {
-    const WgLoopMode& m = a.m[j];
-#pragma unroll
-    for (int r = 0; r < RMAX; ++r)
-      if (r < m.R) {
-        const int64_t o = i + rows * r;
-        m.fac[o] = f[j][r];
-        m.muD[o] = md[j][r];
-        if (m.constrained) { m.Z[o] = z[j][r]; m.mu[o] = mu[j][r]; m.Zold[o] = zo[j][r]; }
-      }
-  }
-}
-
-void Engine::coupled_admm(int c, const aoadmm_options& opt) {
-  CouplingInfo& ci = couplings_[c];
-  AdmmCtl* ctl = ctl_of_coupling(c);
-  const int n = (int)ci.modes.size();
-  const int ty = ci.type;
-  const int64_t nD = ci.rows * ci.cols;
-  ci.DeltaOld.ensure(nD * 8); ci.BB.ensure(nD * 8); ci.dD.ensure(nD * 8); ci.tmp.ensure(nD * 8);
-  ci.coef.ensure(64 * 8);
-  const int64_t qa = ty == 3 ? ci.rows : ci.cols;    // order of the Delta normal equations (types 3 / 4, 5)
-  ci.AA.ensure((size_t)qa * qa * 8); ci.LAA.ensure((size_t)qa * qa * 8);
-  double* resid = slots_.d() + n_modes_ * kSlotsPerMode + 2 * n_tensors_;
-  for (int j = 0; j < n; ++j) {                       // image-shaped work buffers
-    ModeInfo& mi = modes_[ci.modes[j]];
-    const size_t nimg = (size_t)std::max(mi.rows * mi.R, mi.img_rows * mi.img_cols) * sizeof(double);
-    mi.TD.ensure(nimg); mi.TF.ensure(nimg); mi.tmp.ensure(nimg); mi.W1.ensure(nimg); mi.W2.ensure(nimg);
-  }
-  // per-outer-iteration constants
-  std::vector<const double*> hp(n);
-  auto pc_block = [&](const ModeInfo& mi) -> Par2Block* {
-    return (tensors_[mi.tensor].par2 && mi.pos == 2) ? &tensors_[mi.tensor].p2 : nullptr;
-  };
-  int rmax = (int)ci.cols;                            // largest rank, cols(Delta) included
-  bool any_pc = false;                                // a PARAFAC2 C mode in this coupling (types 0 and 1 only)
-  bool local_prox = true;                             // every constrained mode's prox runs inside the loop kernels
-  for (int j = 0; j < n; ++j) {
-    const ModeInfo& mj = modes_[ci.modes[j]];
-    Par2Block* pb = pc_block(mj);
-    hp[j] = pb ? pb->rhosum.d() : mj.rho.d();         // type 1 weighs a C mode with sum(rho) (:736)
-    any_pc = any_pc || pb != nullptr;
-    rmax = std::max(rmax, mj.R);
-    local_prox = local_prox && (!mj.constrained || prox_is_fusable(mj.prox.type));
-  }
-  // Which form runs the inner loop.  Row-local forms: types 0 and 4, ranks and cols(Delta) up to 16, no PARAFAC2 C
-  // mode.  Small problems among them whose proxes all run inside the kernels take the whole loop in one launch of one
-  // workgroup: one row per thread with the state in registers (couple_loop_wg_regs_k, which opens the loop and forms
-  // rho_j / sum rho itself) or the LDS form (couple_loop_wg_k).  The others launch row kernels per step; everything
-  // else takes the generic loop.
-  enum class Path { Regs, Wg, RowSteps, Generic };
-  Path path = Path::Generic;
-  if ((ty == 0 || ty == 4) && !any_pc && rmax <= 16) {
-    if (n <= 4 && ci.rows <= 2048 && local_prox) path = ci.rows <= 256 && rmax <= 8 && n <= 3 ? Path::Regs : Path::Wg;
-    else path = Path::RowSteps;
-  }
-  // reset the loop control (the per-mode sys_build calls reset their own blocks); types 0-2: in coupling_coefs_k below
-  if (!(ty == 0 || ty == 1 || ty == 2) && path != Path::Regs) ctl_reset(ctl, stream_);
-  DevBuf& rho_ptrs = ci.rho_ptrs;                     // pointers never change once the work buffers exist
-  if (ci.rho_ptrs_host != hp) {
-    rho_ptrs.ensure(8 * sizeof(double*));
-    AO_HIP(hipMemcpyAsync(rho_ptrs.p, hp.data(), n * sizeof(double*), hipMemcpyHostToDevice, stream_));
-    AO_HIP(hipStreamSynchronize(stream_));            // hp is a local
-    ci.rho_ptrs_host = hp;
-  }
-  const double* rho_last = modes_[ci.modes[n - 1]].rho.d();   // type 5: rhoC = mean(rho{mm}) with the stale loop variable (:1032)
-  if (ty == 0 || ty == 1 || ty == 2) {
-    if (path != Path::Regs) {
-      coupling_coefs_k<<<1, 64, 0, stream_>>>(ci.coef.d(), rho_ptrs.as<const double*>(), n, ctl);
-      AO_KERNEL_CHECK();
-    }
-  } else if (ty == 4 || ty == 5) {
-    AAArgs aa, aaa;                                   // aaa: the PARAFAC2 C mode's H*H' kept apart (:946-948)
-    aa.n = 0; aa.Rc = (int)ci.cols; aaa.n = 0; aaa.Rc = (int)ci.cols;
-    for (int j = 0; j < n; ++j) {
-      const ModeInfo& mj = modes_[ci.modes[j]];
-      AAArgs& dst = pc_block(mj) ? aaa : aa;
-      dst.H[dst.n] = ty == 4 ? mj.H.d() : mj.H2.d();
-      dst.rho[dst.n] = (&dst == &aaa) ? ones_.d() : (ty == 4 ? hp[j] : rho_last);
-      dst.R[dst.n] = mj.R;
-      dst.n++;
-    }
-    coupling_AA_k<<<1, 256, 0, stream_>>>(ci.AA.d(), aa);
-    AO_KERNEL_CHECK();
-    if (aaa.n > 0) {                                  // LAA holds AAA; the per-row systems are factored in the Delta step
-      coupling_AA_k<<<1, 256, 0, stream_>>>(ci.LAA.d(), aaa);
-      AO_KERNEL_CHECK();
-    } else
-    chol_only(ci.LAA.d(), ci.AA.d(), (int)ci.cols, ctl, stream_);
-  }
-  const int q = (int)ci.cols;
-  const int64_t rows = ci.rows;
-  auto by_rmax = [&](auto&& launch) {
-    if (rmax <= 4) launch(std::integral_constant<int, 4>());
-    else if (rmax <= 8) launch(std::integral_constant<int, 8>());
-    else launch(std::integral_constant<int, 16>());
-  };
-  if (path == Path::Regs || path == Path::Wg) {
-    WgLoopArgs wa;
-    wa.n = n; wa.q = q; wa.type = ty; wa.max_inner = opt.MaxInnerIters; wa.rows = rows;
-    wa.Delta = ci.Delta.d(); wa.DeltaOld = ci.DeltaOld.d(); wa.dD = ci.dD.d(); wa.coefs = ci.coef.d(); wa.LAA = ci.LAA.d();
-    wa.tol_pr_coupl = opt.innerRelPrTol_coupl; wa.tol_pr_constr = opt.innerRelPrTol_constr;
-    wa.tol_du_coupl = opt.innerRelDualTol_coupl; wa.tol_du_constr = opt.innerRelDualTol_constr;
-    wa.ctl = ctl;
-    size_t lds = (size_t)q * q;
-    for (int j = 0; j < n; ++j) {
-      ModeInfo& mi = modes_[ci.modes[j]];
-      WgLoopMode& wm = wa.m[j];
-      wm.Aeff = mi.Aeff; wm.L = mi.L.d(); wm.rho = mi.rho.d(); wm.H = ty == 4 ? mi.H.d() : nullptr;
-      wm.fac = mi.fac.d(); wm.muD = mi.muD.d(); wm.Z = mi.Z.d(); wm.mu = mi.mu.d(); wm.Zold = mi.Zold.d();
-      wm.slots = resid + (int64_t)ci.modes[j] * kResidPerMode;
-      wm.R = mi.R; wm.constrained = mi.constrained ? 1 : 0; wm.ptype = mi.prox.type; wm.p0 = mi.prox.p0; wm.p1 = mi.prox.p1;
-      lds += (size_t)mi.R * mi.R + (size_t)q * mi.R;
-    }
-    if (path == Path::Regs) {
-      wa.self_start = 1;
-#define AO_WGR(RM, NMM) { if (ty == 4) couple_loop_wg_regs_k<RM, NMM, true><<<1, 256, 0, stream_>>>(wa); \
-                          else couple_loop_wg_regs_k<RM, NMM, false><<<1, 256, 0, stream_>>>(wa); }
-      if (rmax <= 4) { if (n == 1) AO_WGR(4, 1) else if (n == 2) AO_WGR(4, 2) else AO_WGR(4, 3) }
-      else { if (n == 1) AO_WGR(8, 1) else if (n == 2) AO_WGR(8, 2) else AO_WGR(8, 3) }
-#undef AO_WGR
-    } else {
-      by_rmax([&](auto tag) { couple_loop_wg_k<decltype(tag)::value><<<1, 256, lds * sizeof(double), stream_>>>(wa); });
-    }
-    AO_KERNEL_CHECK();
-    return;
-  }
-  if (path == Path::RowSteps) {
-    const unsigned rb = (unsigned)cdiv(rows, 64);
-    int64_t nr = cdiv(rows, 2048);
-    if (nr > 64) nr = 64;
-    RowCouple rc[8];
-    RowDelta rd;
-    rd.n = n;
-    size_t lds_delta = (size_t)q * q;
-    for (int j = 0; j < n; ++j) {
-      ModeInfo& mi = modes_[ci.modes[j]];
-      rc[j].Aeff = mi.Aeff; rc[j].L = mi.L.d(); rc[j].rho = mi.rho.d(); rc[j].H = ty == 4 ? mi.H.d() : nullptr;
-      rc[j].fac = mi.fac.d(); rc[j].muD = mi.muD.d(); rc[j].Z = mi.Z.d(); rc[j].mu = mi.mu.d();
-      rc[j].R = mi.R; rc[j].constrained = mi.constrained ? 1 : 0;
-      rd.fac[j] = mi.fac.d(); rd.muD[j] = mi.muD.d(); rd.rho[j] = mi.rho.d(); rd.H[j] = rc[j].H; rd.R[j] = mi.R;
-      lds_delta += (size_t)q * mi.R;
-    }
-    for (int it = 0; it < opt.MaxInnerIters; ++it) {
-      for (int j = 0; j < n; ++j) {                   // primal: Sd(Delta), right-hand side and row solve in one kernel
-        const size_t lds = ((size_t)rc[j].R * rc[j].R + (size_t)q * rc[j].R) * sizeof(double);
-        by_rmax([&](auto tag) {
-          couple_primal_rows_k<decltype(tag)::value><<<rb, 64, lds, stream_>>>(rc[j], ci.Delta.d(), rows, q, ty, ctl);
-        });
-        AO_KERNEL_CHECK();
-      }
-      by_rmax([&](auto tag) {                         // Delta_old, Delta, dD
-        couple_delta_rows_k<decltype(tag)::value><<<rb, 64, lds_delta * sizeof(double), stream_>>>(
-            rd, ci.Delta.d(), ci.DeltaOld.d(), ci.dD.d(), ci.coef.d(), ci.LAA.d(), rows, q, ty, ctl);
-      });
-      AO_KERNEL_CHECK();
-      FinalizeArgs fa;
-      fa.nmodes = n;
-      fa.max_inner = opt.MaxInnerIters;
-      fa.tol_pr_coupl = opt.innerRelPrTol_coupl; fa.tol_pr_constr = opt.innerRelPrTol_constr;
-      fa.tol_du_coupl = opt.innerRelDualTol_coupl; fa.tol_du_constr = opt.innerRelDualTol_constr;
-      for (int j = 0; j < n; ++j) {                   // duals, constraints, residual sums
-        const int m = ci.modes[j];
-        ModeInfo& mi = modes_[m];
-        double* sl = resid + (int64_t)m * kResidPerMode;
-        by_rmax([&](auto tag) {
-          couple_dual_rows_k<decltype(tag)::value><<<(unsigned)nr, 256, (size_t)q * mi.R * sizeof(double), stream_>>>(
-              rc[j], ci.Delta.d(), ci.dD.d(), rows, q, ty, sl + 4, redws_.d(), ctl);
-        });
-        AO_KERNEL_CHECK();
-        if (nr > 1) {
-          couple_dual_fin_k<<<1, 64, 0, stream_>>>(sl + 4, redws_.d(), (int)nr, ctl);
-          AO_KERNEL_CHECK();
-        }
-        if (mi.constrained)
-          constraint_update(mi.prox, mi.fac.d(), mi.Z.d(), mi.mu.d(), mi.Zold.d(), mi.V.d(), mi.rows, mi.R, mi.rho.d(), 1.0,
-                            mi.proxws.d(), sl, redws_.d(), ctl, stream_);
-        else
-          sumsq_diff(sl + 1, mi.fac.d(), nullptr, mi.rows * mi.R, redws_.d(), ctl, stream_);
-        fa.slots[j] = sl;
-        fa.constrained[j] = mi.constrained ? 1 : 0;
-        fa.coupled[j] = 1;
-      }
-      admm_finalize_generic(fa, ctl, stream_);
-    }
-    return;
-  }
-  for (int it = 0; it < opt.MaxInnerIters; ++it) {
-    // ---- primal updates (:635-658, :713-730, :783-800, :853-870, :913-936, :1004-1020)
-    for (int j = 0; j < n; ++j) {
-      ModeInfo& mi = modes_[ci.modes[j]];
-      const int64_t nm = mi.rows * mi.R, ni = mi.img_rows * mi.img_cols;
-      // Sd(Delta): after the first inner iteration the image computed in the dual step below is still current
-      const double* TD = (it == 0 || ty == 0 || ty == 1 || ty == 2) ? image_d(mi.TD.d(), ci, ci.Delta.d(), mi, ctl, stream_)
-                                                                     : mi.TD.d();
-      Par2Block* pb = pc_block(mi);
-      if (pb && ty != 1 && ty != 5) {
-        // row k: A_inner = a_k + rho_k/2*Tf'(Sd(Delta) - mu_Delta)(k,:) [+ rho_k/2*(Z - mu)(k,:)], solved with L_k
-        // (:638-645, :785-792, :850-857, :916-923); Tf' is the identity except for type 2 (right-multiplication by H')
-        if (ty == 2) {
-          Coef c2[2] = {coef(1.0), coef(-1.0)};
-          const double* x2[2] = {TD, mi.muD.d()};
-          ew_lincomb(mi.tmp.d(), ni, 2, c2, x2, ctl, stream_);
-          const double* adj = adjoint_f(mi.TF.d(), ci, mi.tmp.d(), mi, ctl, stream_);
-          Coef cf[3] = {coef(1.0), coef(1.0), coef(-1.0)};
-          const double* x[3] = {adj, mi.Z.d(), mi.mu.d()};
-          ew_lincomb(mi.RHS.d(), nm, mi.constrained ? 3 : 1, cf, x, ctl, stream_);
-        } else {
-          Coef cf[4] = {coef(1.0), coef(-1.0), coef(1.0), coef(-1.0)};
-          const double* x[4] = {TD, mi.muD.d(), mi.Z.d(), mi.mu.d()};
-          ew_lincomb(mi.RHS.d(), nm, mi.constrained ? 4 : 2, cf, x, ctl, stream_);
-        }
-        par2_c_rowsolve(pb->ac.d(), pb->rhoc.d(), pb->Lc.d(), mi.RHS.d(), nullptr, 1, pb->dims_all(), mi.fac.d(), ctl, stream_);
-        continue;
-      }
-      if (ty == 0 || ty == 3 || ty == 4) {
-        Coef cf[5] = {coef(1.0), coef(mi.rho.d(), 0.5), coef(mi.rho.d(), -0.5), coef(mi.rho.d(), 0.5), coef(mi.rho.d(), -0.5)};
-        const double* x[5] = {mi.Aeff, TD, mi.muD.d(), mi.Z.d(), mi.mu.d()};
-        ew_lincomb(mi.RHS.d(), nm, mi.constrained ? 5 : 3, cf, x, ctl, stream_);
-      } else {
-        Coef c2[2] = {coef(1.0), coef(-1.0)};
-        const double* x2[2] = {TD, mi.muD.d()};
-        ew_lincomb(mi.tmp.d(), ni, 2, c2, x2, ctl, stream_);                   // Sd(Delta) - mu_Delta
-        const double* adj = adjoint_f(mi.TF.d(), ci, mi.tmp.d(), mi, ctl, stream_);
-        Coef cf[4] = {coef(1.0), coef(mi.rho.d(), 0.5), coef(mi.rho.d(), 0.5), coef(mi.rho.d(), -0.5)};
-        const double* x[4] = {mi.Aeff, adj, mi.Z.d(), mi.mu.d()};
-        ew_lincomb(mi.RHS.d(), nm, mi.constrained ? 4 : 2, cf, x, ctl, stream_);
-      }
-      if (pb && (ty == 1 || ty == 5)) {
-        // vec(C') = (blkdiag(B_k) + rhoC/2*kron(H'H,I) [+ rhoC/2*I]) \ vec(A_inner') (:714-722); mi.rho holds rhoC
-        if (pb->hth_diag)                             // H'H diagonal: the system is K row systems (solver_par2.hip)
-          par2_c_rowsolve(mi.RHS.d(), pb->rhoc.d(), pb->Lc.d(), nullptr, nullptr, 0, pb->dims_all(), mi.fac.d(), ctl, stream_);
-        else
-          dense_symv_rows(pb->Minv.d(), mi.RHS.d(), mi.fac.d(), pb->K, pb->R, ctl, stream_);
-      } else if (ty == 1 || ty == 5) {
-        // sylvester(B2, B, A_inner) (:707, :1016) with B2 = rho/2*H'H (+ rho/2*I if constrained) = U (..) U',
-        // B = V diag(mu) V':  X = U * ((U' A_inner V) ./ (beta_i + mu_j)) * V'
-        gemm_small(mi.W1.d(), mi.rows, mi.eUt.d(), mi.rows, mi.RHS.d(), mi.rows, mi.rows, (int)mi.rows, mi.R, 0, coef(1.0), 0.0, ctl, stream_);
-        gemm_small(mi.W2.d(), mi.rows, mi.W1.d(), mi.rows, mi.eV.d(), mi.R, mi.rows, mi.R, mi.R, 0, coef(1.0), 0.0, ctl, stream_);
-        sylv_scale(mi.W2.d(), mi.rows, mi.R, mi.eLam.d(), mi.eMu.d(), mi.rho.d(), 1.0, mi.constrained ? 1.0 : 0.0, ctl, stream_);
-        gemm_small(mi.W1.d(), mi.rows, mi.W2.d(), mi.rows, mi.eV.d(), mi.R, mi.rows, mi.R, mi.R, 1, coef(1.0), 0.0, ctl, stream_);
-        gemm_small(mi.fac.d(), mi.rows, mi.eU.d(), mi.rows, mi.W1.d(), mi.rows, mi.rows, (int)mi.rows, mi.R, 0, coef(1.0), 0.0, ctl, stream_);
-      } else {
-        row_solve(mi.fac.d(), mi.rows, mi.RHS.d(), mi.rows, mi.L.d(), mi.rows, mi.R, ctl, stream_);
-      }
-    }
-    // ---- Delta update
-    {
-      Coef c1[1] = {coef(1.0)};
-      const double* x1[1] = {ci.Delta.d()};
-      ew_lincomb(ci.DeltaOld.d(), nD, 1, c1, x1, ctl, stream_);
-    }
-    if ((ty == 0 || ty == 2) && any_pc) {             // per-row weights rho_j(k) (:666-675, :805-811)
-      RowMeanArgs ra;
-      ra.n = n; ra.rows = ci.rows; ra.cols = (int)ci.cols;
-      for (int j = 0; j < n; ++j) {
-        ModeInfo& mi = modes_[ci.modes[j]];
-        Par2Block* pb = pc_block(mi);
-        ra.fac[j] = image_f(mi.TF.d(), ci, mi.fac.d(), mi, ctl, stream_); ra.mu[j] = mi.muD.d();
-        ra.rho[j] = pb ? pb->rhoc.d() : mi.rho.d();
-        ra.vec[j] = pb ? 1 : 0;
-      }
-      int64_t nb = cdiv(nD, 256);
-      if (nb > 1024) nb = 1024;
-      coupling_rowmean_k<<<(unsigned)nb, 256, 0, stream_>>>(ci.Delta.d(), ra, ctl);
-      AO_KERNEL_CHECK();
-    } else if (ty == 0 || ty == 1 || ty == 2) {       // weighted mean of Tf(C_j) + mu_j (:661-675, :735-741, :805-811)
-      for (int j = 0; j < n; ++j) {
-        ModeInfo& mi = modes_[ci.modes[j]];
-        const double* tf = image_f(mi.TF.d(), ci, mi.fac.d(), mi, ctl, stream_);
-        if (j == 0) {
-          Coef cf[2] = {coef(ci.coef.d() + j, 1.0), coef(ci.coef.d() + j, 1.0)};
-          const double* x[2] = {tf, mi.muD.d()};
-          ew_lincomb(ci.Delta.d(), nD, 2, cf, x, ctl, stream_);
-        } else {
-          Coef cf[3] = {coef(1.0), coef(ci.coef.d() + j, 1.0), coef(ci.coef.d() + j, 1.0)};
-          const double* x[3] = {ci.Delta.d(), tf, mi.muD.d()};
-          ew_lincomb(ci.Delta.d(), nD, 3, cf, x, ctl, stream_);
-        }
-      }
-    } else if (ty == 3) {                             // Delta = AA \ BB (:875-885)
-      for (int j = 0; j < n; ++j) {
-        ModeInfo& mi = modes_[ci.modes[j]];
-        Coef cf[2] = {coef(1.0), coef(1.0)};
-        const double* x[2] = {mi.fac.d(), mi.muD.d()};
-        ew_lincomb(mi.tmp.d(), mi.rows * mi.R, 2, cf, x, ctl, stream_);
-        if (Par2Block* pb = pc_block(mi)) {           // rows weighted by rho_k: H'*diag(rho)*H and H'*diag(rho)*(C + mu)
-          pb->Hs.ensure((size_t)mi.hr * mi.hc * 8);
-          rows_scale(pb->Hs.d(), mi.H.d(), pb->rhoc.d(), mi.hr, mi.hc, ctl, stream_);
-          rows_scale(mi.tmp.d(), mi.tmp.d(), pb->rhoc.d(), mi.rows, mi.R, ctl, stream_);
-          gemm_small(ci.AA.d(), ci.rows, mi.Ht.d(), mi.hc, pb->Hs.d(), mi.hr, ci.rows, (int)mi.rows, (int)ci.rows, 0,
-                     coef(1.0), j == 0 ? 0.0 : 1.0, ctl, stream_);
-          gemm_small(ci.BB.d(), ci.rows, mi.Ht.d(), mi.hc, mi.tmp.d(), mi.rows, ci.rows, (int)mi.rows, mi.R, 0,
-                     coef(1.0), j == 0 ? 0.0 : 1.0, ctl, stream_);
-          continue;
-        }
-        gemm_small(ci.AA.d(), ci.rows, mi.Ht.d(), mi.hc, mi.H.d(), mi.hr, ci.rows, (int)mi.rows, (int)ci.rows, 0,
-                   coef(mi.rho.d(), 1.0), j == 0 ? 0.0 : 1.0, ctl, stream_);
-        gemm_small(ci.BB.d(), ci.rows, mi.Ht.d(), mi.hc, mi.tmp.d(), mi.rows, ci.rows, (int)mi.rows, mi.R, 0,
-                   coef(mi.rho.d(), 1.0), j == 0 ? 0.0 : 1.0, ctl, stream_);
-      }
-      spd_solve_left(ci.AA.d(), ci.rows, ci.BB.d(), (int)ci.cols, ctl, stream_);
-      Coef c1[1] = {coef(1.0)};
-      const double* x1[1] = {ci.BB.d()};
-      ew_lincomb(ci.Delta.d(), nD, 1, c1, x1, ctl, stream_);
-    } else {                                          // types 4, 5: Delta = BB / AA (:939-963, :1026-1054)
-      for (int j = 0; j < n; ++j) {
-        ModeInfo& mi = modes_[ci.modes[j]];
-        const double* tf = image_f(mi.TF.d(), ci, mi.fac.d(), mi, ctl, stream_);
-        Coef cf[2] = {coef(1.0), coef(1.0)};
-        const double* x[2] = {tf, mi.muD.d()};
-        ew_lincomb(mi.tmp.d(), mi.img_rows * mi.img_cols, 2, cf, x, ctl, stream_);
-        // BB += rho_j * (Tf(C_j) + mu_j) * H_j'   (:955 ; :1048 with H2 and rhoC)
-        if (ty == 4 && pc_block(mi)) {                // rows weighted by rho_k (:955)
-          rows_scale(mi.tmp.d(), mi.tmp.d(), pc_block(mi)->rhoc.d(), mi.rows, mi.R, ctl, stream_);
-          gemm_small(ci.BB.d(), ci.rows, mi.tmp.d(), mi.rows, mi.H.d(), mi.hr, ci.rows, mi.R, (int)ci.cols, 1,
-                     coef(1.0), j == 0 ? 0.0 : 1.0, ctl, stream_);
-        } else if (ty == 4)
-          gemm_small(ci.BB.d(), ci.rows, mi.tmp.d(), mi.rows, mi.H.d(), mi.hr, ci.rows, mi.R, (int)ci.cols, 1,
-                     coef(mi.rho.d(), 1.0), j == 0 ? 0.0 : 1.0, ctl, stream_);
-        else
-          gemm_small(ci.BB.d(), ci.rows, mi.tmp.d(), mi.img_rows, mi.H2.d(), mi.h2r, ci.rows, mi.R, (int)ci.cols, 1,
-                     coef(rho_last, 1.0), j == 0 ? 0.0 : 1.0, ctl, stream_);
-      }
-      if (any_pc) {                                   // Delta(k,:) = BB(k,:) / (AA + rho_k*AAA)  (:957-961, :1049-1052)
-        const Par2Block* pb = nullptr;
-        for (int j = 0; j < n; ++j)
-          if (Par2Block* q = pc_block(modes_[ci.modes[j]])) pb = q;
-        const int q = (int)ci.cols;
-        delta_rowwise_solve_k<<<(unsigned)ci.rows, 64, (size_t)(q * q + q) * sizeof(double), stream_>>>(
-            ci.Delta.d(), ci.BB.d(), ci.rows, q, ci.AA.d(), ci.LAA.d(), pb->rhoc.d(), ctl);
-        AO_KERNEL_CHECK();
-      } else
-      row_solve(ci.Delta.d(), ci.rows, ci.BB.d(), ci.rows, ci.LAA.d(), ci.rows, (int)ci.cols, ctl, stream_);
-    }
-    {
-      Coef cf[2] = {coef(1.0), coef(-1.0)};
-      const double* x[2] = {ci.Delta.d(), ci.DeltaOld.d()};
-      ew_lincomb(ci.dD.d(), nD, 2, cf, x, ctl, stream_);
-    }
-    // ---- duals, constraints, residual pieces (:678-692 and the same block of every case)
-    FinalizeArgs fa;
-    fa.nmodes = n;
-    fa.max_inner = opt.MaxInnerIters;
-    fa.tol_pr_coupl = opt.innerRelPrTol_coupl; fa.tol_pr_constr = opt.innerRelPrTol_constr;
-    fa.tol_du_coupl = opt.innerRelDualTol_coupl; fa.tol_du_constr = opt.innerRelDualTol_constr;
-    for (int j = 0; j < n; ++j) {
-      const int m = ci.modes[j];
-      ModeInfo& mi = modes_[m];
-      double* sl = resid + (int64_t)m * kResidPerMode;
-      const int64_t nm = mi.rows * mi.R, ni = mi.img_rows * mi.img_cols;
-      const double* TD = image_d(mi.TD.d(), ci, ci.Delta.d(), mi, ctl, stream_);
-      const double* tf = image_f(mi.TF.d(), ci, mi.fac.d(), mi, ctl, stream_);
-      {
-        // mu_Delta += Tf(C) - Sd(Delta); sl[4] = ||Tf(C) - Sd(Delta)||^2, sl[5] = ||mu_Delta||^2, sl[7] = ||den||^2 with
-        // den = H*C (:1125) / C*H (:1143) for types 1, 2, else C
-        const bool img_den = ty == 1 || ty == 2;
-        int64_t nr = cdiv(std::max(ni, nm), 2048);
-        if (nr > 64) nr = 64;
-        coupling_dual_k<<<(unsigned)nr, 256, 0, stream_>>>(mi.muD.d(), tf, TD, ni, img_den ? tf : mi.fac.d(), img_den ? ni : nm,
-                                                           sl + 4, redws_.d(), ctl);
-        AO_KERNEL_CHECK();
-        if (nr > 1) {
-          coupling_dual_fin_k<<<1, 64, 0, stream_>>>(sl + 4, redws_.d(), (int)nr, ctl);
-          AO_KERNEL_CHECK();
-        }
-      }
-      if (mi.constrained) {
-        Par2Block* pb = pc_block(mi);                 // a C mode's prox gets max(rho) (:1423-1424)
-        constraint_update(mi.prox, mi.fac.d(), mi.Z.d(), mi.mu.d(), mi.Zold.d(), mi.V.d(), mi.rows, mi.R,
-                          pb ? pb->rhomax.d() : mi.rho.d(), 1.0, mi.proxws.d(), sl, redws_.d(), ctl, stream_);
-      } else
-        sumsq_diff(sl + 1, mi.fac.d(), nullptr, nm, redws_.d(), ctl, stream_);
-      const double* dimg = image_d(mi.tmp.d(), ci, ci.dD.d(), mi, ctl, stream_);
-      sumsq_diff(sl + 6, dimg, nullptr, ni, redws_.d(), ctl, stream_);
-      fa.slots[j] = sl;
-      fa.constrained[j] = mi.constrained ? 1 : 0;
-      fa.coupled[j] = 1;
-    }
-    admm_finalize_generic(fa, ctl, stream_);
   }
 }
 

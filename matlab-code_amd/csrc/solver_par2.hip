@@ -6,9 +6,6 @@
 
 namespace aoadmm {
 
-static constexpr int kSlotsPerMode = 8;
-static constexpr int kResidPerMode = 8;
-
 double* Engine::resid_slots(int m) {
   return slots_.d() + n_modes_ * kSlotsPerMode + 2 * n_tensors_ + (int64_t)m * kResidPerMode;
 }

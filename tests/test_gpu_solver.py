@@ -228,14 +228,18 @@ def test_three_blocks_share_a_factor(pkg, eng, rows):
     compare(*run_both(pkg, eng, Z, io, options(MaxOuterIters=8)))
 
 
-@pytest.mark.parametrize('rows', [300, 2500])
+@pytest.mark.parametrize('rows,R', [(300, None), (2500, None), (300, 7), (2500, 7), (300, 12), (2500, 12)],
+                         ids=['300', '2500', '300-R7', '2500-R7', '300-R12', '2500-R12'])
 @pytest.mark.parametrize('ctype', [0, 4])
-def test_row_local_coupling_loop_forms(pkg, eng, rows, ctype):
-    """The three forms of the row-local coupled loop (csrc/solver.hip): register-resident one-workgroup kernel (rows
-    <= 256: the script-sized tests above), global-memory one-workgroup kernel (300 rows here), one launch per step
-    (2500 rows), for the exact (type 0) and the partial (type 4) coupling."""
+def test_row_local_coupling_loop_forms(pkg, eng, rows, ctype, R):
+    """The three forms of the row-local coupled loop (kernels and launchers in csrc/couple.hip, chosen by couple_path,
+    driven from csrc/solver_coupled.hip): register-resident one-workgroup kernel (rows <= 256: the script-sized tests
+    above), global-memory one-workgroup kernel (300 rows here), one launch per step (2500 rows), for the exact (type 0)
+    and the partial (type 4) coupling.  The launchers instantiate the kernels for ranks up to 4, 8 and 16: the models'
+    default ranks (3 and 4) take the first class, R = 7 the second, R = 12 the third."""
     rng = np.random.default_rng(40 + ctype)
-    Z, io = (cp_cp_exact_model(rng, rows=rows) if ctype == 0 else script3_model(rng, rows=rows))
+    kw = {} if R is None else dict(R=R)
+    Z, io = (cp_cp_exact_model(rng, rows=rows, **kw) if ctype == 0 else script3_model(rng, rows=rows, **kw))
     compare(*run_both(pkg, eng, Z, io, options(MaxOuterIters=6)))
 
 
