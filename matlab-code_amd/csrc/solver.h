@@ -1,8 +1,9 @@
 // Host-side engine: model (struct Z), state (struct G) and the AO-ADMM outer loop
 // (functions/cmtf_fun_AOADMM.m:87-476) driving the HIP kernels.  Everything stays
 // resident in HBM; the host synchronises once per outer iteration to read the
-// objective values and the inner-iteration counters.  The members are defined in solver.hip (model, data, outer loop,
-// objective), solver_par2.hip (PARAFAC2 blocks) and solver_coupled.hip (coupled ADMM loop).
+// objective values and the inner-iteration counters (readback.h).  The members are defined in solver.hip (model, data,
+// state), solver_solve.hip (outer loop), solver_objective.hip (objective, device and host half), solver_par2.hip
+// (PARAFAC2 blocks), solver_coupled.hip (coupled ADMM loop) and solver_comm.hip (communicator).
 #pragma once
 #include <atomic>
 #include <memory>
@@ -17,6 +18,7 @@
 #include "misc.h"
 #include "par2.h"
 #include "par2_sparse.h"
+#include "readback.h"
 #include "small.h"
 #include "sparse.h"
 
@@ -108,6 +110,7 @@ struct TensorInfo {
   bool normsq_valid = false;
   int last_pos = -1;
   bool eval_shortcut = false;   // PARAFAC2: the enqueued objective evaluation took the last_mttkrp shortcut (:1254-1260)
+  bool masked() const { return par2 ? p2.has_mask : blk.has_mask; }   // Z.miss{p} given
 };
 
 struct CouplingInfo {
@@ -120,9 +123,7 @@ struct CouplingInfo {
 };
 
 struct LocalGroup;
-
-constexpr int kSlotsPerMode = 8;      // objective slots
-constexpr int kResidPerMode = 8;      // ADMM residual slots
+struct SolveRun;                      // what one solve carries from step to step (solver_solve.hip)
 
 // coupling images (solver_coupled.hip): Sd(D), Tf(F) and Tf'(Y) for mode `mi` of coupling `ci`; each returns its input
 // where the map is the identity and `dst` otherwise
@@ -201,23 +202,42 @@ class Engine {
   bool prefetch_next_contraction(const aoadmm_options& opt);   // true: a tensor pass was enqueued
   void allreduce(double* buf, int64_t n);
   void allreduce_from(const double* send, double* recv, int64_t n);   // out of place (send == recv: in place)
-  double* scratch_slots() { return slots_.d(); }
-  double* red_ws() { return redws_.d(); }
 
  private:
   void check_mode(int m) const;
+  // model_end, paragraph by paragraph
+  void check_model() const;
+  void shape_coupling(int c);              // modes, shapes and checks of one coupling
+  void precompute_coupling(int c);         // H*H' / the eigendecomposition of H'*H, once per model
+  void alloc_readback();
+  void comm_release();                     // destroys the RCCL communicator, if any (solver_comm.hip)
+  bool has_missing() const;
+  void em_pass_enqueue(int p, int update, bool fuse_next_pass = false);   // statistics of tensor p into its EM slots (+ imputation)
   void compute_gram(ModeInfo& mi, const LoopEnd* close = nullptr);
   FactorRef factor_ref(const ModeInfo& o) const {
     return FactorRef{o.fac.d(), o.rows, o.version, o.facT_version == o.version ? o.facT.d() : nullptr};
   }
+  void factor_refs(const TensorInfo& t, FactorRef facs[8]) const {
+    for (int i = 0; i < t.nmodes; ++i) facs[i] = factor_ref(modes_[t.modes[i]]);
+  }
+  // outer loop, step by step (solver_solve.hip)
+  void solve_setup(const aoadmm_options& opt);
+  void decide_slab_sharding(TensorInfo& t, const aoadmm_options& opt);
+  void outer_updates(const aoadmm_options& opt, int iter, bool has_miss);
+  void update_mode(int m, int cid, const aoadmm_options& opt, int iter);
+  void enqueue_readback(SolveRun& r);
+  void enqueue_objective(SolveRun& r, int iter);
+  void finish_objective(SolveRun& r);
+  void record_iteration(SolveRun& r, int iter);
   void update_uncoupled_cp_mode(int m, const aoadmm_options& opt);
   void prepare_mode_system(int m, int nrho, const aoadmm_options& opt);
-  void eval_objective_enqueue(bool first);
-  bool has_missing() const;
-  void em_pass_enqueue(int p, int update, bool fuse_next_pass = false);
-  void prepare_next_first_mode(const aoadmm_options& opt);         // statistics of tensor p into its EM slots (+ imputation)
-  double* em_slot(int p) const;
+  void prepare_next_first_mode(const aoadmm_options& opt);
   void ensure_mode_work(ModeInfo& mi);
+  // objective (solver_objective.hip): the device half fills the arena, the host half reads its pinned copy
+  void eval_objective_enqueue(bool first);
+  void check_not_pd(const ArenaView& h) const;
+  void objective_from_host(const ArenaView& h, double f[4]) const;
+  double rel_missing_from_host(const ArenaView& h) const;
   // coupled ADMM loop (solver_coupled.hip): coupled_admm prepares it and runs one of the three forms
   void coupled_admm(int c, const aoadmm_options& opt);
   void coupled_one_launch(CouplingInfo& ci, AdmmCtl* ctl, const aoadmm_options& opt, CouplePath path, int rmax);
@@ -239,7 +259,6 @@ class Engine {
   void par2s_pass(Par2Block& b, int pos, const CooFactor& f, double* out, int64_t ldOut);
   void par2s_rhs_A(TensorInfo& t, double* out);     // out (I x R) = sum_nnz x * B(g,:) .* C(k(g),:)
   void par2s_ensure_Y(TensorInfo& t);               // Y = Xcat' * A for the current A (cached by its version)
-  double* resid_slots(int m);
   std::vector<int> update_sequence(int p) const;
 
   int device_ = 0;
@@ -252,10 +271,10 @@ class Engine {
   std::vector<ModeInfo> modes_;
   std::vector<TensorInfo> tensors_;
   std::vector<CouplingInfo> couplings_;
-  DevBuf readback_;      // everything the host reads once per outer iteration, in one piece (one copy): slots_ | ctls_ |
-                         // per PARAFAC2 block res (K + 1), q (4 K), regv (K); the three below are views into it
-  DevBuf ctls_;          // AdmmCtl[n_modes + n_couplings]
-  DevBuf slots_;         // objective scalars
+  DevBuf readback_;      // everything the host reads once per outer iteration, in one piece (one copy); a PARAFAC2
+                         // block's res, q and regv are views into it
+  ArenaLayout arena_;    // its layout (readback.h)
+  ArenaView dev_;        // typed pointers into readback_
   DevBuf redws_;         // reduction workspace
   DevBuf ones_;          // a device 1.0 (unit weight where a kernel expects a rho pointer)
   DevBuf emws_;          // EM pass partial sums
@@ -267,15 +286,16 @@ class Engine {
   ncclComm_t comm_ = nullptr;
   mutable std::mutex comm_mu_;          // comm_ / aborted_ against comm_abort() from another worker thread
   std::atomic<bool> aborted_{false};
-  std::shared_ptr<LocalGroup> local_;   // process-local group (threads of one process), see solver.hip
+  std::shared_ptr<LocalGroup> local_;   // process-local group (threads of one process), see solver_comm.hip
   int rank_ = 0, world_ = 1;
   bool share_only_ = false;             // aoadmm_comm_init_rank_share: rank_/world_ of an N-rank job on a one-rank communicator
   aoadmm_progress_fn progress_fn_ = nullptr;   // options.Display = 'iter'
   void* progress_user_ = nullptr;
   int progress_every_ = 0;
 
-  AdmmCtl* ctl_of_mode(int m) { return ctls_.as<AdmmCtl>() + m; }
-  AdmmCtl* ctl_of_coupling(int c) { return ctls_.as<AdmmCtl>() + n_modes_ + c; }
+  AdmmCtl* ctl_of_mode(int m) const { return dev_.ctl(m); }
+  AdmmCtl* ctl_of_coupling(int c) const { return dev_.ctl(n_modes_ + c); }
+  double* resid_slots(int m) const { return dev_.resid(m); }
 };
 
 }  // namespace aoadmm

@@ -1,31 +1,15 @@
-// Engine implementation: see solver.h.  Reference control flow:
-// functions/cmtf_fun_AOADMM.m:87-476 (outer loop), :1213-1363 (objective),
-// functions/evaluate_stopping_conditions.m.  This file launches no kernel of its own.
+// Engine implementation: see solver.h.  Constructor and destructor, model definition, data upload / synthesis /
+// masks / EM pass, state get/set, kernel statistics and the resident_* entries.  This file launches no kernel of its own.
 #include "solver.h"
 #include "em.h"
 #include "hosteig.h"
 
-#include <rccl/rccl.h>
-#include <dlfcn.h>
-
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
-#include <condition_variable>
 #include <cstring>
-#include <map>
-#include <mutex>
-#include <set>
 
 namespace aoadmm {
-
-#define AO_NCCL(expr)                                                                          \
-  do {                                                                                         \
-    ncclResult_t r__ = (expr);                                                                 \
-    if (r__ != ncclSuccess)                                                                    \
-      throw Error(AOADMM_ERR_RCCL, fmt("%s failed: %s", #expr, ncclGetErrorString(r__)));      \
-  } while (0)
 
 Engine::Engine(int device) : device_(device) {
   int n = 0;
@@ -48,167 +32,10 @@ Engine::~Engine() {
   for (auto& ks : timers_.stats)
     for (auto& pr : ks.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (hipEvent_t e : timers_.pool) (void)hipEventDestroy(e);
-  if (comm_) (void)ncclCommDestroy(comm_);
+  comm_release();
   if (side_ev_) (void)hipEventDestroy(side_ev_);
   if (side_) (void)hipStreamDestroy(side_);
   if (stream_) (void)hipStreamDestroy(stream_);
-}
-
-// ---------------------------------------------------------------------------
-// communicator
-// ---------------------------------------------------------------------------
-void Engine::comm_init(const char id[128], int rank, int world, bool share_only) {
-  AO_REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad rank/world %d/%d", rank, world);
-  AO_REQUIRE(id != nullptr || world == 1, "a communicator of %d ranks needs the id from aoadmm_comm_unique_id", world);
-  AO_HIP(hipSetDevice(device_));
-  if (comm_) { (void)ncclCommDestroy(comm_); comm_ = nullptr; }
-  local_.reset();
-  if (id != nullptr) {               // world == 1 with an id: one-rank communicator (exercises the RCCL path on one GPU)
-    ncclUniqueId uid;
-    static_assert(sizeof(uid) <= 128, "unique id larger than the ABI buffer");
-    std::memcpy(&uid, id, sizeof(uid));
-    // share_only (aoadmm_comm_init_rank_share): this engine takes rank `rank` of `world` in every sharding decision
-    // but its communicator has ONE rank, so the collectives run (ncclAllReduce on the library's stream) without
-    // peers: one rank's share of an N-GPU job, timed on a one-GPU box.  The sums are this rank's partial sums only.
-    if (share_only) AO_NCCL(ncclCommInitRank(&comm_, 1, uid, 0));
-    else AO_NCCL(ncclCommInitRank(&comm_, world, uid, rank));
-  }
-  rank_ = rank;
-  world_ = world;
-  share_only_ = share_only;
-  aborted_ = false;
-}
-
-// Process-local group: engines driven by threads of ONE process (on one device or several) meet at a
-// mutex/condvar barrier and add their buffers through host staging, in rank order, so every rank gets the same
-// bits.  It exists so the sharded data path (row blocks, own-rows buffers, objective partial sums) can be run with
-// world > 1 on a one-GPU box, where RCCL refuses two ranks on one device.  Not a transport for production: the
-// data crosses PCIe twice per collective.
-struct LocalGroup {
-  std::mutex m;
-  std::condition_variable cv;
-  int world = 0, arrived = 0, joined = 0;
-  uint64_t gen = 0;
-  bool aborted = false;                       // a rank failed outside the collectives: nobody waits for it any more
-  std::vector<std::vector<double>> stage;     // one host buffer per rank
-  void barrier() {
-    std::unique_lock<std::mutex> lk(m);
-    if (aborted) throw Error(AOADMM_ERR_RCCL, "local group: aborted after a failure on another rank");
-    const uint64_t g = gen;
-    if (++arrived == world) {
-      arrived = 0;
-      ++gen;
-      cv.notify_all();
-      return;
-    }
-    if (!cv.wait_for(lk, std::chrono::seconds(120), [&] { return gen != g || aborted; }))
-      throw Error(AOADMM_ERR_RCCL, "local group: a rank did not reach the collective within 120 s");
-    if (gen == g) throw Error(AOADMM_ERR_RCCL, "local group: aborted after a failure on another rank");
-  }
-  void abort() {
-    std::lock_guard<std::mutex> lk(m);
-    aborted = true;
-    cv.notify_all();
-  }
-};
-static std::mutex g_groups_mutex;
-static std::map<int, std::shared_ptr<LocalGroup>> g_groups;
-
-void Engine::comm_init_local(int key, int rank, int world) {
-  AO_REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad rank/world %d/%d", rank, world);
-  if (comm_) { (void)ncclCommDestroy(comm_); comm_ = nullptr; }
-  std::lock_guard<std::mutex> lk(g_groups_mutex);
-  std::shared_ptr<LocalGroup>& g = g_groups[key];
-  if (!g || g->joined == g->world) {           // first rank of a new (or re-used) key
-    g = std::make_shared<LocalGroup>();
-    g->world = world;
-    g->stage.resize(world);
-  }
-  AO_REQUIRE(g->world == world, "local group %d was created for %d ranks, not %d", key, g->world, world);
-  g->joined++;
-  local_ = g;
-  rank_ = rank;
-  world_ = world;
-  aborted_ = false;
-}
-
-void Engine::comm_abort() {
-  aborted_ = true;                              // sticky: every later collective, solve or upload of this engine throws
-  if (local_) local_->abort();
-  ncclComm_t c = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(comm_mu_);
-    c = comm_;
-    comm_ = nullptr;
-  }
-  // outside the lock: the owner thread may sit inside ncclAllReduce's enqueue with a copy of the handle
-  if (c) (void)ncclCommAbort(c);                // the collective kernels of this rank see the flag and exit
-}
-
-void Engine::require_usable() const {
-  if (aborted_) throw Error(AOADMM_ERR_RCCL, "context unusable: its communicator was aborted after a failure on another rank");
-}
-
-void Engine::comm_info(int* nccl_version, int* comm_ranks, char* lib_path, int cap) const {
-  if (nccl_version) {
-    int v = 0;
-    AO_NCCL(ncclGetVersion(&v));
-    *nccl_version = v;
-  }
-  if (comm_ranks) {
-    int n = local_ ? world_ : 0;
-    std::lock_guard<std::mutex> lk(comm_mu_);
-    if (comm_) AO_NCCL(ncclCommCount(comm_, &n));
-    *comm_ranks = n;
-  }
-  if (lib_path && cap > 0) {
-    lib_path[0] = 0;
-    Dl_info di;
-    if (dladdr(reinterpret_cast<const void*>(&ncclGetVersion), &di) && di.dli_fname) {
-      std::strncpy(lib_path, di.dli_fname, (size_t)cap - 1);
-      lib_path[cap - 1] = 0;
-    }
-  }
-}
-
-void Engine::allreduce(double* buf, int64_t n) { allreduce_from(buf, buf, n); }
-
-// recv = sum over ranks of send (send == recv: in place)
-void Engine::allreduce_from(const double* send, double* buf, int64_t n) {
-  if (n <= 0) return;
-  if (aborted_) throw Error(AOADMM_ERR_RCCL, "communicator aborted after a failure on another rank");
-  if (local_) {
-    LocalGroup& g = *local_;
-    std::vector<double>& mine = g.stage[rank_];
-    mine.resize((size_t)n);
-    AO_HIP(hipMemcpyAsync(mine.data(), send, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    AO_HIP(hipStreamSynchronize(stream_));
-    g.barrier();                                // every rank has staged its contribution
-    std::vector<double> tot((size_t)n, 0.0);
-    for (int r = 0; r < g.world; ++r) {
-      AO_REQUIRE((int64_t)g.stage[r].size() == n, "local group: rank %d brought %lld values, rank %d brought %lld", r,
-                 (long long)g.stage[r].size(), rank_, (long long)n);
-      for (int64_t i = 0; i < n; ++i) tot[i] += g.stage[r][i];
-    }
-    g.barrier();                                // every rank has read all contributions
-    AO_HIP(hipMemcpyAsync(buf, tot.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream_));
-    AO_HIP(hipStreamSynchronize(stream_));
-    return;
-  }
-  ncclComm_t c = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(comm_mu_);
-    if (aborted_) throw Error(AOADMM_ERR_RCCL, "communicator aborted after a failure on another rank");
-    c = comm_;
-  }
-  if (!c) {
-    // a sharded engine without a transport would go on with its partial sums: never silently
-    if (world_ > 1) throw Error(AOADMM_ERR_RCCL, fmt("rank %d of %d has no communicator", rank_, world_));
-    if (send != buf) AO_HIP(hipMemcpyAsync(buf, send, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
-    return;
-  }
-  // enqueued outside the lock so that comm_abort() from the caller's thread never waits behind a stuck enqueue
-  AO_NCCL(ncclAllReduce(send, buf, (size_t)n, ncclDouble, ncclSum, c, stream_));
 }
 
 // ---------------------------------------------------------------------------
@@ -337,7 +164,7 @@ void Engine::set_ridge(const double* ridge) {
   for (int m = 0; m < n_modes_; ++m) modes_[m].ridge = ridge ? ridge[m] : 0.0;
 }
 
-void Engine::model_end() {
+void Engine::check_model() const {
   for (int m = 0; m < n_modes_; ++m) {
     AO_REQUIRE(modes_[m].defined, "mode %d has no size", m);
     AO_REQUIRE(modes_[m].tensor >= 0, "mode %d belongs to no tensor (Mismatch between size and modes inputs)", m);
@@ -356,150 +183,158 @@ void Engine::model_end() {
       AO_REQUIRE(mi.coupling < 0, "Coupling in 2. mode (the varying mode) of Parafac2 decomposition not supported.");
     }
   }
+}
+
+void Engine::shape_coupling(int c) {
+  CouplingInfo& ci = couplings_[c];
+  AO_REQUIRE(ci.type >= 0, "coupling %d has no type (Mismatch between number of couplings and coupling types)", c);
+  ci.modes.clear();
+  for (int m = 0; m < n_modes_; ++m)
+    if (modes_[m].coupling == c) ci.modes.push_back(m);
+  AO_REQUIRE(!ci.modes.empty(), "coupling %d couples no mode", c);
+  AO_REQUIRE(ci.modes.size() <= 8, "more than 8 modes in one coupling");
+  for (int m : ci.modes)
+    if (tensors_[modes_[m].tensor].par2 && modes_[m].pos == 2 && ci.type == 5)
+      AO_REQUIRE(modes_[m].hr <= modes_[m].rows, "coupling type 5 of a PARAFAC2 C mode: Delta has more rows than the mode (cmtf_fun_AOADMM.m:1049-1051 indexes rho by Delta's row)");
+  if (ci.type == 4 || ci.type == 5) {       // :945-961, :1034-1052 keep one PARAFAC2 term apart (AAA); two would overwrite each other
+    int npc = 0;
+    for (int m : ci.modes) npc += (tensors_[modes_[m].tensor].par2 && modes_[m].pos == 2) ? 1 : 0;
+    if (npc > 1) throw Error(AOADMM_ERR_UNSUPPORTED, fmt("coupling type %d with more than one PARAFAC2 C mode is not supported", ci.type));
+  }
+  const ModeInfo& m0 = modes_[ci.modes[0]];
+  auto need_H = [&](int m) { AO_REQUIRE(modes_[m].hr > 0, "Coupling matrix for mode %d is missing.", m + 1); };
+  switch (ci.type) {
+    case 0:                                   // C = Delta  (check_data_input.m:48-61)
+      ci.rows = m0.rows; ci.cols = m0.R;
+      for (int m : ci.modes) {
+        AO_REQUIRE(modes_[m].rows == m0.rows, "Coupled factor matrices of mode %d and mode %d need to have same number of rows.", ci.modes[0] + 1, m + 1);
+        AO_REQUIRE(modes_[m].R == m0.R, "Coupled factor matrices of mode %d and mode %d need to have same number of components/columns.", ci.modes[0] + 1, m + 1);
+        modes_[m].img_rows = modes_[m].rows; modes_[m].img_cols = modes_[m].R;
+      }
+      break;
+    case 1:                                   // H*C = Delta : H is (rows_Delta x rows_m)  (:62-80)
+      need_H(ci.modes[0]);
+      ci.rows = m0.hr; ci.cols = m0.R;
+      for (int m : ci.modes) {
+        need_H(m);
+        AO_REQUIRE(modes_[m].hc == modes_[m].rows, "Mismatch between sz and number of columns of coupling matrix for mode %d.", m + 1);
+        AO_REQUIRE(modes_[m].hr == ci.rows, "Coupling transformation matrices need to have same number of rows for mode %d and mode %d.", ci.modes[0] + 1, m + 1);
+        AO_REQUIRE(modes_[m].R == m0.R, "Coupled factor matrices of mode %d and mode %d need to have same number of components/columns.", ci.modes[0] + 1, m + 1);
+        modes_[m].img_rows = ci.rows; modes_[m].img_cols = modes_[m].R;
+      }
+      break;
+    case 2:                                   // C*H = Delta : H is (R_m x cols_Delta)  (:81-98)
+      need_H(ci.modes[0]);
+      ci.rows = m0.rows; ci.cols = m0.hc;
+      for (int m : ci.modes) {
+        need_H(m);
+        AO_REQUIRE(modes_[m].hr == modes_[m].R, "Mismatch between number of components and number of rows of coupling matrix for mode %d.", m + 1);
+        AO_REQUIRE(modes_[m].hc == ci.cols, "Coupling transformation matrices need to have same number of columns for mode %d and mode %d.", ci.modes[0] + 1, m + 1);
+        AO_REQUIRE(modes_[m].rows == ci.rows, "Coupled factor matrices of mode %d and mode %d need to have same number of rows.", ci.modes[0] + 1, m + 1);
+        modes_[m].img_rows = ci.rows; modes_[m].img_cols = ci.cols;
+      }
+      AO_REQUIRE(ci.cols <= kMaxRank, "coupling type 2: Delta has more than %d columns", kMaxRank);
+      break;
+    case 3:                                   // C = H*Delta : H is (rows_m x rows_Delta)  (:99-114)
+      need_H(ci.modes[0]);
+      ci.rows = m0.hc; ci.cols = m0.R;
+      for (int m : ci.modes) {
+        need_H(m);
+        AO_REQUIRE(modes_[m].hr == modes_[m].rows, "Mismatch between sz and number of rows of coupling matrix for mode %d.", m + 1);
+        AO_REQUIRE(modes_[m].hc == ci.rows, "Coupling transformation matrices need to have same number of columns for mode %d and mode %d.", ci.modes[0] + 1, m + 1);
+        AO_REQUIRE(modes_[m].R == m0.R, "Coupled factor matrices of mode %d and mode %d need to have same number of components/columns.", ci.modes[0] + 1, m + 1);
+        modes_[m].img_rows = modes_[m].rows; modes_[m].img_cols = modes_[m].R;
+      }
+      break;
+    case 4:                                   // C = Delta*H : H is (cols_Delta x R_m)
+      need_H(ci.modes[0]);
+      ci.rows = m0.rows; ci.cols = m0.hr;
+      for (int m : ci.modes) {
+        need_H(m);
+        AO_REQUIRE(modes_[m].rows == ci.rows && modes_[m].hr == ci.cols && modes_[m].hc == modes_[m].R,
+                   "coupling type 4: transformation matrix of mode %d has the wrong shape", m + 1);
+        modes_[m].img_rows = modes_[m].rows; modes_[m].img_cols = modes_[m].R;
+      }
+      AO_REQUIRE(ci.cols <= kMaxRank, "coupling type 4: Delta has more than %d columns", kMaxRank);
+      break;
+    default:                                  // 5: H*C = Delta*H2 : H (rows_Delta x rows_m), H2 (cols_Delta x R_m)  (:125-140)
+      need_H(ci.modes[0]);
+      AO_REQUIRE(m0.h2r > 0, "Coupling matrix H2 for mode %d is missing.", ci.modes[0] + 1);
+      ci.rows = m0.hr; ci.cols = m0.h2r;
+      for (int m : ci.modes) {
+        need_H(m);
+        AO_REQUIRE(modes_[m].h2r > 0, "Coupling matrix H2 for mode %d is missing.", m + 1);
+        AO_REQUIRE(modes_[m].hc == modes_[m].rows && modes_[m].hr == ci.rows && modes_[m].h2r == ci.cols &&
+                   modes_[m].h2c == modes_[m].R, "coupling type 5: transformation matrices of mode %d have the wrong shape", m + 1);
+        modes_[m].img_rows = ci.rows; modes_[m].img_cols = modes_[m].R;
+      }
+      AO_REQUIRE(ci.cols <= kMaxRank, "coupling type 5: Delta has more than %d columns", kMaxRank);
+      break;
+  }
+}
+
+void Engine::precompute_coupling(int c) {
+  const CouplingInfo& ci = couplings_[c];
+  for (int m : ci.modes) {
+    ModeInfo& mi = modes_[m];
+    if (ci.type == 2) {                       // H*H' (R x R) for the system matrix (:314)
+      std::vector<double> hh((size_t)mi.R * mi.R, 0.0);
+      for (int a = 0; a < mi.R; ++a)
+        for (int b2 = 0; b2 < mi.R; ++b2) {
+          double acc = 0.0;
+          for (int64_t c2 = 0; c2 < mi.hc; ++c2) acc += mi.H_host[(size_t)a + (size_t)mi.hr * c2] * mi.H_host[(size_t)b2 + (size_t)mi.hr * c2];
+          hh[(size_t)a + (size_t)mi.R * b2] = acc;
+        }
+      upload_small(mi.HHt, hh.data(), (int64_t)mi.R * mi.R, stream_);
+    }
+    if (ci.type == 1 || ci.type == 5) {       // H'*H = U diag(lam) U' once: the Sylvester solves reuse it (:288, :377)
+      const int64_t n = mi.rows;
+      if (n > 4096) throw Error(AOADMM_ERR_UNSUPPORTED, "coupling types 1/5: modes beyond 4096 rows are not diagonalised on the host");
+      std::vector<double> hth((size_t)n * n, 0.0), lam, U;
+      for (int64_t a = 0; a < n; ++a)
+        for (int64_t b2 = a; b2 < n; ++b2) {
+          double acc = 0.0;
+          for (int64_t q = 0; q < mi.hr; ++q) acc += mi.H_host[(size_t)q + (size_t)mi.hr * a] * mi.H_host[(size_t)q + (size_t)mi.hr * b2];
+          hth[(size_t)a + (size_t)n * b2] = acc; hth[(size_t)b2 + (size_t)n * a] = acc;
+        }
+      AO_REQUIRE(host_sym_eig(n, hth, lam, U) >= 0, "eigendecomposition of H'*H (mode %d) did not converge", m + 1);
+      std::vector<double> Ut((size_t)n * n);
+      for (int64_t j = 0; j < n; ++j)
+        for (int64_t i = 0; i < n; ++i) Ut[(size_t)j + (size_t)n * i] = U[(size_t)i + (size_t)n * j];
+      upload_small(mi.eU, U.data(), n * n, stream_);
+      upload_small(mi.eUt, Ut.data(), n * n, stream_);
+      upload_small(mi.eLam, lam.data(), n, stream_);
+    }
+  }
+}
+
+// one arena for what the host reads back per outer iteration, so that one copy fetches it
+void Engine::alloc_readback() {
+  std::vector<int> slabs(n_tensors_, 0);
+  for (int p = 0; p < n_tensors_; ++p)
+    if (tensors_[p].par2) slabs[p] = tensors_[p].p2.K;
+  arena_.build(n_modes_, n_tensors_, n_couplings_, slabs);
+  for (int p = 0; p < n_tensors_; ++p)            // views of the previous arena go before it does
+    if (tensors_[p].par2) { tensors_[p].p2.res.release(); tensors_[p].p2.q.release(); tensors_[p].p2.regv.release(); }
+  readback_.alloc(arena_.bytes);
+  AO_HIP(hipMemsetAsync(readback_.p, 0, readback_.bytes, stream_));
+  dev_ = arena_.at(readback_.p);
+  for (int p = 0; p < n_tensors_; ++p) {
+    if (!tensors_[p].par2) continue;
+    Par2Block& b = tensors_[p].p2;
+    b.res.view(dev_.p2_res(p), (size_t)(b.K + 1) * 8);
+    b.q.view(dev_.p2_q(p), (size_t)b.K * kSlabSums * 8);
+    b.regv.view(dev_.p2_regv(p), (size_t)b.K * 8);
+  }
+}
+
+void Engine::model_end() {
+  check_model();
   for (int c = 0; c < n_couplings_; ++c) {
-    CouplingInfo& ci = couplings_[c];
-    AO_REQUIRE(ci.type >= 0, "coupling %d has no type (Mismatch between number of couplings and coupling types)", c);
-    ci.modes.clear();
-    for (int m = 0; m < n_modes_; ++m)
-      if (modes_[m].coupling == c) ci.modes.push_back(m);
-    AO_REQUIRE(!ci.modes.empty(), "coupling %d couples no mode", c);
-    AO_REQUIRE(ci.modes.size() <= 8, "more than 8 modes in one coupling");
-    for (int m : ci.modes)
-      if (tensors_[modes_[m].tensor].par2 && modes_[m].pos == 2 && ci.type == 5)
-        AO_REQUIRE(modes_[m].hr <= modes_[m].rows, "coupling type 5 of a PARAFAC2 C mode: Delta has more rows than the mode (cmtf_fun_AOADMM.m:1049-1051 indexes rho by Delta's row)");
-    if (ci.type == 4 || ci.type == 5) {       // :945-961, :1034-1052 keep one PARAFAC2 term apart (AAA); two would overwrite each other
-      int npc = 0;
-      for (int m : ci.modes) npc += (tensors_[modes_[m].tensor].par2 && modes_[m].pos == 2) ? 1 : 0;
-      if (npc > 1) throw Error(AOADMM_ERR_UNSUPPORTED, fmt("coupling type %d with more than one PARAFAC2 C mode is not supported", ci.type));
-    }
-    const ModeInfo& m0 = modes_[ci.modes[0]];
-    auto need_H = [&](int m) { AO_REQUIRE(modes_[m].hr > 0, "Coupling matrix for mode %d is missing.", m + 1); };
-    switch (ci.type) {
-      case 0:                                   // C = Delta  (check_data_input.m:48-61)
-        ci.rows = m0.rows; ci.cols = m0.R;
-        for (int m : ci.modes) {
-          AO_REQUIRE(modes_[m].rows == m0.rows, "Coupled factor matrices of mode %d and mode %d need to have same number of rows.", ci.modes[0] + 1, m + 1);
-          AO_REQUIRE(modes_[m].R == m0.R, "Coupled factor matrices of mode %d and mode %d need to have same number of components/columns.", ci.modes[0] + 1, m + 1);
-          modes_[m].img_rows = modes_[m].rows; modes_[m].img_cols = modes_[m].R;
-        }
-        break;
-      case 1:                                   // H*C = Delta : H is (rows_Delta x rows_m)  (:62-80)
-        need_H(ci.modes[0]);
-        ci.rows = m0.hr; ci.cols = m0.R;
-        for (int m : ci.modes) {
-          need_H(m);
-          AO_REQUIRE(modes_[m].hc == modes_[m].rows, "Mismatch between sz and number of columns of coupling matrix for mode %d.", m + 1);
-          AO_REQUIRE(modes_[m].hr == ci.rows, "Coupling transformation matrices need to have same number of rows for mode %d and mode %d.", ci.modes[0] + 1, m + 1);
-          AO_REQUIRE(modes_[m].R == m0.R, "Coupled factor matrices of mode %d and mode %d need to have same number of components/columns.", ci.modes[0] + 1, m + 1);
-          modes_[m].img_rows = ci.rows; modes_[m].img_cols = modes_[m].R;
-        }
-        break;
-      case 2:                                   // C*H = Delta : H is (R_m x cols_Delta)  (:81-98)
-        need_H(ci.modes[0]);
-        ci.rows = m0.rows; ci.cols = m0.hc;
-        for (int m : ci.modes) {
-          need_H(m);
-          AO_REQUIRE(modes_[m].hr == modes_[m].R, "Mismatch between number of components and number of rows of coupling matrix for mode %d.", m + 1);
-          AO_REQUIRE(modes_[m].hc == ci.cols, "Coupling transformation matrices need to have same number of columns for mode %d and mode %d.", ci.modes[0] + 1, m + 1);
-          AO_REQUIRE(modes_[m].rows == ci.rows, "Coupled factor matrices of mode %d and mode %d need to have same number of rows.", ci.modes[0] + 1, m + 1);
-          modes_[m].img_rows = ci.rows; modes_[m].img_cols = ci.cols;
-        }
-        AO_REQUIRE(ci.cols <= kMaxRank, "coupling type 2: Delta has more than %d columns", kMaxRank);
-        break;
-      case 3:                                   // C = H*Delta : H is (rows_m x rows_Delta)  (:99-114)
-        need_H(ci.modes[0]);
-        ci.rows = m0.hc; ci.cols = m0.R;
-        for (int m : ci.modes) {
-          need_H(m);
-          AO_REQUIRE(modes_[m].hr == modes_[m].rows, "Mismatch between sz and number of rows of coupling matrix for mode %d.", m + 1);
-          AO_REQUIRE(modes_[m].hc == ci.rows, "Coupling transformation matrices need to have same number of columns for mode %d and mode %d.", ci.modes[0] + 1, m + 1);
-          AO_REQUIRE(modes_[m].R == m0.R, "Coupled factor matrices of mode %d and mode %d need to have same number of components/columns.", ci.modes[0] + 1, m + 1);
-          modes_[m].img_rows = modes_[m].rows; modes_[m].img_cols = modes_[m].R;
-        }
-        break;
-      case 4:                                   // C = Delta*H : H is (cols_Delta x R_m)
-        need_H(ci.modes[0]);
-        ci.rows = m0.rows; ci.cols = m0.hr;
-        for (int m : ci.modes) {
-          need_H(m);
-          AO_REQUIRE(modes_[m].rows == ci.rows && modes_[m].hr == ci.cols && modes_[m].hc == modes_[m].R,
-                     "coupling type 4: transformation matrix of mode %d has the wrong shape", m + 1);
-          modes_[m].img_rows = modes_[m].rows; modes_[m].img_cols = modes_[m].R;
-        }
-        AO_REQUIRE(ci.cols <= kMaxRank, "coupling type 4: Delta has more than %d columns", kMaxRank);
-        break;
-      default:                                  // 5: H*C = Delta*H2 : H (rows_Delta x rows_m), H2 (cols_Delta x R_m)  (:125-140)
-        need_H(ci.modes[0]);
-        AO_REQUIRE(m0.h2r > 0, "Coupling matrix H2 for mode %d is missing.", ci.modes[0] + 1);
-        ci.rows = m0.hr; ci.cols = m0.h2r;
-        for (int m : ci.modes) {
-          need_H(m);
-          AO_REQUIRE(modes_[m].h2r > 0, "Coupling matrix H2 for mode %d is missing.", m + 1);
-          AO_REQUIRE(modes_[m].hc == modes_[m].rows && modes_[m].hr == ci.rows && modes_[m].h2r == ci.cols &&
-                     modes_[m].h2c == modes_[m].R, "coupling type 5: transformation matrices of mode %d have the wrong shape", m + 1);
-          modes_[m].img_rows = ci.rows; modes_[m].img_cols = modes_[m].R;
-        }
-        AO_REQUIRE(ci.cols <= kMaxRank, "coupling type 5: Delta has more than %d columns", kMaxRank);
-        break;
-    }
-    for (int m : ci.modes) {
-      ModeInfo& mi = modes_[m];
-      if (ci.type == 2) {                       // H*H' (R x R) for the system matrix (:314)
-        std::vector<double> hh((size_t)mi.R * mi.R, 0.0);
-        for (int a = 0; a < mi.R; ++a)
-          for (int b2 = 0; b2 < mi.R; ++b2) {
-            double acc = 0.0;
-            for (int64_t c2 = 0; c2 < mi.hc; ++c2) acc += mi.H_host[(size_t)a + (size_t)mi.hr * c2] * mi.H_host[(size_t)b2 + (size_t)mi.hr * c2];
-            hh[(size_t)a + (size_t)mi.R * b2] = acc;
-          }
-        upload_small(mi.HHt, hh.data(), (int64_t)mi.R * mi.R, stream_);
-      }
-      if (ci.type == 1 || ci.type == 5) {       // H'*H = U diag(lam) U' once: the Sylvester solves reuse it (:288, :377)
-        const int64_t n = mi.rows;
-        if (n > 4096) throw Error(AOADMM_ERR_UNSUPPORTED, "coupling types 1/5: modes beyond 4096 rows are not diagonalised on the host");
-        std::vector<double> hth((size_t)n * n, 0.0), lam, U;
-        for (int64_t a = 0; a < n; ++a)
-          for (int64_t b2 = a; b2 < n; ++b2) {
-            double acc = 0.0;
-            for (int64_t q = 0; q < mi.hr; ++q) acc += mi.H_host[(size_t)q + (size_t)mi.hr * a] * mi.H_host[(size_t)q + (size_t)mi.hr * b2];
-            hth[(size_t)a + (size_t)n * b2] = acc; hth[(size_t)b2 + (size_t)n * a] = acc;
-          }
-        AO_REQUIRE(host_sym_eig(n, hth, lam, U) >= 0, "eigendecomposition of H'*H (mode %d) did not converge", m + 1);
-        std::vector<double> Ut((size_t)n * n);
-        for (int64_t j = 0; j < n; ++j)
-          for (int64_t i = 0; i < n; ++i) Ut[(size_t)j + (size_t)n * i] = U[(size_t)i + (size_t)n * j];
-        upload_small(mi.eU, U.data(), n * n, stream_);
-        upload_small(mi.eUt, Ut.data(), n * n, stream_);
-        upload_small(mi.eLam, lam.data(), n, stream_);
-      }
-    }
+    shape_coupling(c);
+    precompute_coupling(c);
   }
-  {
-    // one arena for what the host reads back per outer iteration, so that one copy fetches it
-    const size_t nsl = (size_t)(n_modes_ * (kSlotsPerMode + kResidPerMode) + 2 * n_tensors_ + 16 + 4 * n_tensors_) * sizeof(double);
-    const size_t nct = (size_t)(n_modes_ + n_couplings_ + 1) * sizeof(AdmmCtl);
-    const size_t off_ctl = (size_t)round_up((int64_t)nsl, 64);
-    size_t tot = (size_t)round_up((int64_t)(off_ctl + nct), 64);
-    std::vector<size_t> off_p2(n_tensors_, 0);
-    for (int p = 0; p < n_tensors_; ++p)
-      if (tensors_[p].par2) { off_p2[p] = tot; tot += ((size_t)6 * tensors_[p].p2.K + 1) * sizeof(double); }
-    for (int p = 0; p < n_tensors_; ++p)            // views of the previous arena go before it does
-      if (tensors_[p].par2) { tensors_[p].p2.res.release(); tensors_[p].p2.q.release(); tensors_[p].p2.regv.release(); }
-    ctls_.release(); slots_.release();
-    readback_.alloc(tot);
-    AO_HIP(hipMemsetAsync(readback_.p, 0, readback_.bytes, stream_));
-    char* base = readback_.as<char>();
-    slots_.view(base, nsl);
-    ctls_.view(base + off_ctl, nct);
-    for (int p = 0; p < n_tensors_; ++p) {
-      if (!tensors_[p].par2) continue;
-      Par2Block& b = tensors_[p].p2;
-      char* q = base + off_p2[p];
-      b.res.view(q, (size_t)(b.K + 1) * 8);
-      b.q.view(q + (size_t)(b.K + 1) * 8, (size_t)b.K * 4 * 8);
-      b.regv.view(q + (size_t)(5 * b.K + 1) * 8, (size_t)b.K * 8);
-    }
-  }
+  alloc_readback();
   AO_HIP(hipStreamSynchronize(stream_));
   model_done_ = true;
 }
@@ -587,15 +422,15 @@ double Engine::tensor_normsq(int p) {
     AO_HIP(hipSetDevice(device_));
     DevBuf ws;
     ws.alloc(1024 * sizeof(double) + 64);
-    double* slot = slots_.d() + n_modes_ * (kSlotsPerMode + kResidPerMode) + 2 * n_tensors_;
-    if (t.par2 ? t.p2.has_mask : t.blk.has_mask) {
+    double* slot = dev_.scratch();
+    if (t.masked()) {
       // ||miss .* X||^2 (cmtf_AOADMM.m:133-148): the observed-entry sum of squares of a statistics-only EM pass
       // (needs factors on the device: solve() calls this after the state checks)
       em_pass_enqueue(p, 0);
-      double h4[4];
-      AO_HIP(hipMemcpyAsync(h4, em_slot(p), sizeof h4, hipMemcpyDeviceToHost, stream_));
+      double h4[kEmStats];
+      AO_HIP(hipMemcpyAsync(h4, dev_.em(p), sizeof h4, hipMemcpyDeviceToHost, stream_));
       AO_HIP(hipStreamSynchronize(stream_));
-      t.normsq = h4[3];
+      t.normsq = h4[kEmObsX2];
       t.normsq_valid = true;
       return t.normsq;
     }
@@ -647,7 +482,7 @@ void Engine::tensor_synth(int p, int rank, uint64_t seed, double noise, int prec
   SynthArgs a;
   a.I_loc = loc; a.I_pad = b.X.pad0; a.J = J; a.K = K; a.row0 = row0; a.I_full = I; a.R = rank; a.seed = seed;
   synth_factors(A.d(), B.d(), C.d(), a, stream_);
-  double* slot = slots_.d() + n_modes_ * (kSlotsPerMode + kResidPerMode) + 2 * n_tensors_;
+  double* slot = dev_.scratch();
   synth_norms(slot, A.d(), B.d(), C.d(), a, ws.d(), stream_);
   allreduce(slot, 3);
   double h[3];
@@ -723,15 +558,11 @@ void Engine::tensor_mask_upload(int p, const uint8_t* mask) {
 
 bool Engine::has_missing() const {
   for (int p = 0; p < n_tensors_; ++p)
-    if (tensors_[p].par2 ? tensors_[p].p2.has_mask : tensors_[p].blk.has_mask) return true;
+    if (tensors_[p].masked()) return true;
   return false;
 }
 
-double* Engine::em_slot(int p) const {
-  return slots_.d() + n_modes_ * (kSlotsPerMode + kResidPerMode) + 2 * n_tensors_ + 16 + 4 * p;
-}
-
-// One EM pass over tensor p with the current factors: {num, den, obs_res, obs_x2} -> em_slot(p), all-reduced
+// One EM pass over tensor p with the current factors: {num, den, obs_res, obs_x2} -> its EM slots, all-reduced
 // over the row shards; update = 1 also overwrites the missing entries with the model (:416-435).
 void Engine::em_pass_enqueue(int p, int update, bool fuse_next_pass) {
   TensorInfo& t = tensors_[p];
@@ -742,7 +573,7 @@ void Engine::em_pass_enqueue(int p, int update, bool fuse_next_pass) {
     a.A = modes_[t.modes[0]].fac.d(); a.B = modes_[t.modes[1]].fac.d(); a.C = modes_[t.modes[2]].fac.d();
     a.off = b.off_d.as<int64_t>(); a.K = b.K; a.I = b.I; a.R = b.R; a.update = update;
     emws_.ensure((size_t)b.K * 4 * sizeof(double));
-    em_par2_pass(a, emws_.d(), em_slot(p), stream_);
+    em_par2_pass(a, emws_.d(), dev_.em(p), stream_);
     return;
   }
   CpBlock& b = t.blk;
@@ -783,7 +614,7 @@ void Engine::em_pass_enqueue(int p, int update, bool fuse_next_pass) {
   FactorRef facs[8];
   if (fuse_next_pass && update && b.nd == 3 && em_cp_can_fuse(a, b.X.prec) && b.dims[1] <= 65535 &&
       b.dims[2] <= 65535 && !small_direct(sharded(), b, a.R)) {
-    for (int i = 0; i < t.nmodes; ++i) facs[i] = factor_ref(modes_[t.modes[i]]);
+    factor_refs(t, facs);
     const std::vector<int> seq = update_sequence(p);
     const int pos0 = seq.empty() ? 0 : seq[0];
     int best = -1;
@@ -804,7 +635,7 @@ void Engine::em_pass_enqueue(int p, int update, bool fuse_next_pass) {
     a.T = b.T.p;
     a.t_chunk_stride = fpl.trows() * a.R;
   }
-  em_cp_pass(a, b.X.prec, emws_.d(), em_slot(p), stream_);
+  em_cp_pass(a, b.X.prec, emws_.d(), dev_.em(p), stream_);
   if (b.nd == 2 && update) {
     // same imputation on the transposed copy (roles of the two factors swapped); its statistics are discarded
     EmCpArgs at = a;
@@ -815,7 +646,7 @@ void Engine::em_pass_enqueue(int p, int update, bool fuse_next_pass) {
     emws_.ensure(wsb + 64);
     em_cp_pass(at, b.Xt.prec, emws_.d(), emws_.d() + wsb / sizeof(double), stream_);   // statistics to a scratch tail
   }
-  allreduce(em_slot(p), 4);
+  allreduce(dev_.em(p), kEmStats);
   if (update) b.cached_mode = -1;                    // the data changed: cached partial contractions are stale
   if (fused_c >= 0) { b.cached_mode = fused_c; b.cached_version = facs[fused_c].version; b.plan = fpl; }
 }
@@ -969,572 +800,6 @@ void Engine::kernel_stats(int which, int reset, double* ms, int64_t* launches, d
   if (reset) { ks.ms = 0; ks.launches = 0; ks.timed = 0; ks.bytes = 0; ks.flops = 0; }
 }
 
-// The first tensor pass of the next outer iteration does not depend on the host's stopping decision, so
-// it is enqueued before the host waits for the objective values: the round trip hides behind it.
-bool Engine::prefetch_next_contraction(const aoadmm_options& opt) {
-  if (!opt.use_dimtree) return false;
-  for (int cid = -1; cid < n_couplings_; ++cid) {
-    for (int p = 0; p < n_tensors_; ++p)
-      for (int m = 0; m < n_modes_; ++m) {
-        const ModeInfo& mi = modes_[m];
-        if (mi.coupling != cid || mi.tensor != p) continue;
-        TensorInfo& t = tensors_[p];                      // first mode the next iteration updates
-        if (t.par2 || t.blk.sparse || t.blk.nd != 3 || small_direct(sharded(), t.blk, mi.R)) return false;
-        FactorRef facs[8];
-        for (int i = 0; i < t.nmodes; ++i) {
-          const ModeInfo& o = modes_[t.modes[i]];
-          facs[i] = factor_ref(o);
-        }
-        std::vector<int> seq = update_sequence(p);
-        const KernelStats* ks = timers_.stats;
-        const int64_t before = ks[0].launches + ks[1].launches;
-        ensure_contraction(block_ctx(), t.blk, mi.pos, facs, mi.R, true, seq.data(), (int)seq.size());
-        return ks[0].launches + ks[1].launches > before;     // false: the cached pass still serves
-      }
-  }
-  return false;
-}
-
-std::vector<int> Engine::update_sequence(int p) const {
-  // order in which the positions of tensor p are updated inside one outer iteration:
-  // uncoupled modes first, then coupling ids ascending (cmtf_fun_AOADMM.m:10,89-93)
-  std::vector<int> seq;
-  const TensorInfo& t = tensors_[p];
-  for (int cid = -1; cid < n_couplings_; ++cid)
-    for (int i = 0; i < t.nmodes; ++i)
-      if (modes_[t.modes[i]].coupling == cid) seq.push_back(i);
-  return seq;
-}
-
-// ---------------------------------------------------------------------------
-// per-mode pieces of the outer loop
-// ---------------------------------------------------------------------------
-void Engine::ensure_mode_work(ModeInfo& mi) {
-  const size_t nR = (size_t)mi.rows * mi.R * sizeof(double), RR = (size_t)mi.R * mi.R * sizeof(double);
-  mi.A.ensure(nR); mi.Ab.ensure(nR);
-  mi.gram.ensure(RR); mi.C.ensure(RR); mi.Bsys.ensure(RR); mi.L.ensure(RR); mi.Binv.ensure(RR);
-  mi.rho.ensure(64);
-  mi.Zold.ensure(nR); mi.V.ensure(nR); mi.Znew.ensure(nR); mi.RHS.ensure(nR); mi.TD.ensure(nR); mi.tmp.ensure(nR);
-  mi.part.ensure((size_t)admm_partials(mi.rows) * 4 * sizeof(double));
-  if (mi.constrained) mi.proxws.ensure(prox_ws_bytes(mi.prox.type, mi.rows, mi.R));
-  atbws_.ensure(atb_ws_bytes(mi.rows, mi.R, mi.R));
-}
-
-// Gram of the current factor (:66, :148); the same kernel leaves a row-major copy of the factor for the T
-// reductions and closes the ADMM loop that produced the factor.  Call BEFORE bumping mi.version.
-void Engine::compute_gram(ModeInfo& mi, const LoopEnd* close) {
-  mi.facT.ensure((size_t)mi.rows * mi.R * sizeof(double));
-  atb_small(mi.gram.d(), mi.fac.d(), mi.rows, mi.fac.d(), mi.rows, mi.rows, mi.R, mi.R, atbws_.d(), nullptr, stream_,
-            mi.facT.d(), close);
-  mi.facT_version = mi.version;
-}
-
-void Engine::prepare_mode_system(int m, int nrho, const aoadmm_options& opt) {
-  ModeInfo& mi = modes_[m];
-  TensorInfo& t = tensors_[mi.tensor];
-  if (t.par2) {                      // first PARAFAC2 mode: same system, different A and C (:159-178)
-    AO_REQUIRE(mi.pos == 0, "internal: only the first PARAFAC2 mode goes through the CP-style system");
-    par2_prepare_modeA(m, nrho, opt);
-    return;
-  }
-  FactorRef facs[8];
-  for (int i = 0; i < t.nmodes; ++i) {
-    const ModeInfo& o = modes_[t.modes[i]];
-    facs[i] = factor_ref(o);
-  }
-  std::vector<int> seq = update_sequence(mi.tensor);
-  SysBuild sb;
-  sb.ngram = 0;
-  for (int i = 0; i < t.nmodes; ++i)
-    if (i != mi.pos) sb.grams[sb.ngram++] = modes_[t.modes[i]].gram.d();     // :98-103, :109,:112
-  sb.Cpre = nullptr;
-  sb.w = t.weight;
-  sb.ridge = has_ridge_ ? mi.ridge : 0.0;
-  sb.bsum_half = opt.bsum ? opt.bsum_weight / 2 : 0.0;
-  sb.rho_scale = 1.0;
-  sb.nrho = nrho;
-  sb.R = mi.R;
-  sb.C = mi.C.d(); sb.rho = mi.rho.d(); sb.Bsys = mi.Bsys.d(); sb.L = mi.L.d();
-  sb.Binv = nrho > 0 ? mi.Binv.d() : nullptr;
-  sb.ctl = ctl_of_mode(m);
-  const int cty = mi.coupling >= 0 ? couplings_[mi.coupling].type : -1;
-  if (cty == 2) sb.Madd = mi.HHt.d();
-  // The system needs the Gram matrices only: it rides in the launch of the reduction that finishes the MTTKRP (one
-  // extra workgroup) when that path is taken, else it gets its own launch behind the MTTKRP.
-  bool rode = false;
-  block_mttkrp(block_ctx(), t.blk, mi.pos, facs, mi.R, t.weight, mi.A.d(), mi.rows, opt.use_dimtree != 0, seq.data(), (int)seq.size(), true,
-               false, &sb, &rode);
-  if (!rode) sys_build(sb, stream_);
-  if (cty == 1 || cty == 5) {                       // B = V diag(mu) V' for the Sylvester solve of the inner loop
-    mi.eV.ensure((size_t)mi.R * mi.R * sizeof(double)); mi.eMu.ensure((size_t)mi.R * sizeof(double));
-    sym_eig_small(mi.Bsys.d(), mi.R, mi.eMu.d(), mi.eV.d(), stream_);
-  }
-  t.last_pos = mi.pos;                                                        // :121-123
-  mi.Aeff = mi.A.d();
-  if (opt.bsum) {                                                             // :124-127
-    Coef c[2] = {coef(1.0), coef(opt.bsum_weight / 2)};
-    const double* x[2] = {mi.A.d(), mi.fac.d()};
-    ew_lincomb(mi.Ab.d(), mi.rows * mi.R, 2, c, x, nullptr, stream_);
-    mi.Aeff = mi.Ab.d();
-  }
-}
-
-// see the end of the outer loop in solve(): the first uncoupled CP mode of the next iteration, prepared ahead
-void Engine::prepare_next_first_mode(const aoadmm_options& opt) {
-  for (int p = 0; p < n_tensors_; ++p)
-    for (int m = 0; m < n_modes_; ++m) {
-      const ModeInfo& mi = modes_[m];
-      if (mi.coupling != -1 || mi.tensor != p) continue;
-      if (tensors_[p].par2 && mi.pos != 0) return;  // a PARAFAC2 B_k or C mode comes first: nothing ahead
-      prepare_mode_system(m, mi.constrained ? 1 : 0, opt);   // (the first PARAFAC2 mode goes through the same call, :159-178)
-      prepared_mode_ = m;
-      return;
-    }
-}
-
-void Engine::update_uncoupled_cp_mode(int m, const aoadmm_options& opt) {
-  ModeInfo& mi = modes_[m];
-  if (prepared_mode_ == m) prepared_mode_ = -1;     // MTTKRP and system were enqueued at the end of the last iteration
-  else prepare_mode_system(m, mi.constrained ? 1 : 0, opt);
-  AdmmCtl* ctl = ctl_of_mode(m);
-  LoopEnd le;
-  GramFold gf;
-  if (!mi.constrained) {
-    // G.fac{m} = A{m}/B{m}  (:134): B is symmetric positive definite -> Cholesky solve
-    row_solve(mi.fac.d(), mi.rows, mi.Aeff, mi.rows, mi.L.d(), mi.rows, mi.R, nullptr, stream_);
-  } else if (admm_path(mi.rows, mi.R, mi.prox.type, opt.MaxInnerIters, true, mi.proxws.d() != nullptr) == kAdmmPathWg) {
-    // short mode: loop, Gram matrix and row-major copy in one launch of one workgroup
-    WgLoopU wa;
-    wa.A = mi.Aeff; wa.Binv = mi.Binv.d(); wa.L = mi.L.d(); wa.rho = mi.rho.d(); wa.rho_prox = mi.rho.d();
-    wa.fac = mi.fac.d(); wa.Z = mi.Z.d(); wa.mu = mi.mu.d();
-    wa.rows = mi.rows; wa.R = mi.R; wa.per_row = 0;
-    wa.ptype = mi.prox.type; wa.p0 = mi.prox.p0; wa.p1 = mi.prox.p1;
-    wa.max_inner = opt.MaxInnerIters; wa.tol_pr = opt.innerRelPrTol_constr; wa.tol_du = opt.innerRelDualTol_constr;
-    wa.ctl = ctl;
-    mi.facT.ensure((size_t)mi.rows * mi.R * sizeof(double));
-    wa.gram = mi.gram.d(); wa.facT = mi.facT.d();
-    admm_loop_wg(wa, stream_);
-    mi.version++;
-    mi.facT_version = mi.version;
-    return;
-  } else {
-    AdmmMode am;
-    am.A = mi.Aeff; am.L = mi.L.d(); am.Binv = mi.Binv.d(); am.rho = mi.rho.d();
-    am.fac = mi.fac.d(); am.Z = mi.Z.d(); am.mu = mi.mu.d();
-    am.rows = mi.rows; am.R = mi.R; am.prox = mi.prox;
-    mi.facT.ensure((size_t)mi.rows * mi.R * sizeof(double));
-    atbws_.ensure((size_t)cdiv(mi.rows, 16) * mi.R * mi.R * sizeof(double));
-    gf.ws = atbws_.d(); gf.At = mi.facT.d();
-    admm_constrained_loop(am, mi.part.d(), mi.V.d(), mi.Znew.d(), mi.proxws.d(), ctl, opt.MaxInnerIters,
-                          opt.innerRelPrTol_constr, opt.innerRelDualTol_constr, stream_, &le, &gf);
-  }
-  mi.version++;
-  if (gf.nb > 0) {                                                            // :148, partials left by the loop's last launch
-    atb_fin(mi.gram.d(), atbws_.d(), gf.nb, mi.R * mi.R, nullptr, stream_);
-    mi.facT_version = mi.version;
-  } else {
-    compute_gram(mi, le.ctl ? &le : nullptr);                                 // :148
-  }
-}
-
-// ---------------------------------------------------------------------------
-// objective (CMTF_AOADMM_func_eval, :1213-1363)
-// ---------------------------------------------------------------------------
-void Engine::eval_objective_enqueue(bool first) {
-  double* S = slots_.d();
-  ReduceBatch rb;                                  // every plain reduction of this evaluation in one launch
-  auto add = [&](int kind, double* slot, const double* x, const double* y, int64_t n) {
-    ReduceTask k;
-    k.kind = kind; k.slot = slot; k.x = x; k.y = y; k.n = n;
-    rb.add(k);
-  };
-  for (int p = 0; p < n_tensors_; ++p) {
-    TensorInfo& t = tensors_[p];
-    const bool masked = t.par2 ? t.p2.has_mask : t.blk.has_mask;
-    if (masked && first) em_pass_enqueue(p, 0);  // observed-entry residual (:1224-1226, :1249-1252); later
-                                                 // evaluations reuse the statistics of the EM update pass
-    if (t.par2) {
-      par2_objective_enqueue(t);                 // direct residual (:1262-1264) + internal-coupling gaps (:1355)
-      t.eval_shortcut = !masked && !first && t.last_pos == 0;   // remembered for finish_eval: last_pos may move on before
-      if (t.eval_shortcut) {                                // shortcut through last_mttkrp / last_had (:1254-1260)
-        ModeInfo& lm = modes_[t.modes[0]];
-        double* sp = S + n_modes_ * kSlotsPerMode + 2 * p;
-        add(RT_DOT, sp + 0, lm.A.d(), lm.fac.d(), lm.rows * lm.R);
-        add(RT_DOT, sp + 1, lm.C.d(), lm.gram.d(), (int64_t)lm.R * lm.R);
-      }
-      continue;
-    }
-    if (masked) continue;
-    if (first) {
-      // cp_func.m:47-55 / pca_func.m:29-39: same formula with the first mode's MTTKRP
-      ModeInfo& m0 = modes_[t.modes[0]];
-      FactorRef facs[8];
-      for (int i = 0; i < t.nmodes; ++i) {
-        const ModeInfo& o = modes_[t.modes[i]];
-        facs[i] = factor_ref(o);
-      }
-      std::vector<int> seq = update_sequence(p);
-      block_mttkrp(block_ctx(), t.blk, 0, facs, m0.R, t.weight, m0.A.d(), m0.rows, true, seq.data(), (int)seq.size());
-      SysBuild sb;
-      sb.ngram = 0;
-      for (int i = 1; i < t.nmodes; ++i) sb.grams[sb.ngram++] = modes_[t.modes[i]].gram.d();
-      sb.Cpre = nullptr; sb.w = t.weight; sb.ridge = 0; sb.bsum_half = 0; sb.rho_scale = 1; sb.nrho = 1; sb.R = m0.R;
-      sb.C = m0.C.d(); sb.rho = m0.rho.d(); sb.Bsys = m0.Bsys.d(); sb.L = m0.L.d(); sb.ctl = nullptr;
-      sys_build(sb, stream_);
-      t.last_pos = 0;
-    }
-    ModeInfo& lm = modes_[t.modes[t.last_pos]];
-    double* sp = S + n_modes_ * kSlotsPerMode + 2 * p;
-    add(RT_DOT, sp + 0, lm.A.d(), lm.fac.d(), lm.rows * lm.R);                 // f_2 * w
-    add(RT_DOT, sp + 1, lm.C.d(), lm.gram.d(), (int64_t)lm.R * lm.R);          // f_3
-  }
-  for (int m = 0; m < n_modes_; ++m) {
-    ModeInfo& mi = modes_[m];
-    if (mi.slabs) continue;                      // per-slab ratios come from par2_b_gaps
-    double* sm = S + (int64_t)m * kSlotsPerMode;
-    const int64_t nm = mi.rows * mi.R;
-    add(RT_SUMSQ_DIFF, sm + 0, mi.fac.d(), nullptr, nm);
-    if (mi.constrained) {
-      add(RT_SUMSQ_DIFF, sm + 1, mi.fac.d(), mi.Z.d(), nm);
-      const int ty = mi.prox.type;
-      if (ty == AOADMM_C_L2_REG) {
-        reg_value(sm + 3, ty, mi.prox.p0, mi.fac.d(), mi.rows, mi.R, redws_.d(), stream_);
-      } else if (ty == AOADMM_C_QUADRATIC) {       // eta*trace(x'*L*x) (:67): L*x into the prox workspace, then <x, L*x>
-        gemm_small(mi.proxws.d(), mi.rows, mi.prox.Lmat, mi.rows, mi.fac.d(), mi.rows, mi.rows, (int)mi.rows, mi.R, 0,
-                   coef(1.0), 0.0, nullptr, stream_);
-        ReduceTask k;
-        k.kind = RT_DOT; k.slot = sm + 3; k.x = mi.fac.d(); k.y = mi.proxws.d(); k.n = nm; k.scale = mi.prox.p0;
-        rb.add(k);
-      } else if (ty == AOADMM_C_L1_REG || ty == AOADMM_C_L0_REG || ty == AOADMM_C_RIDGE || ty == AOADMM_C_GL_SMOOTH ||
-                 ty == AOADMM_C_TV) {
-        ReduceTask k;
-        k.kind = RT_REG; k.aux = ty; k.slot = sm + 3; k.x = mi.fac.d(); k.rows = mi.rows; k.R = mi.R; k.scale = mi.prox.p0;
-        rb.add(k);
-      }
-    }
-    if (mi.coupling >= 0) {                        // :1303-1329
-      CouplingInfo& ci = couplings_[mi.coupling];
-      const size_t nimg = (size_t)std::max(nm, mi.img_rows * mi.img_cols) * sizeof(double);
-      mi.TD.ensure(nimg); mi.TF.ensure(nimg);
-      const double* td = image_d(mi.TD.d(), ci, ci.Delta.d(), mi, nullptr, stream_);
-      const double* tf = image_f(mi.TF.d(), ci, mi.fac.d(), mi, nullptr, stream_);
-      add(RT_SUMSQ_DIFF, sm + 2, tf, td, mi.img_rows * mi.img_cols);
-      if (tf != mi.fac.d()) add(RT_SUMSQ_DIFF, sm + 4, tf, nullptr, mi.img_rows * mi.img_cols);   // ||H*C|| / ||C*H||
-    }
-    if (rb.n >= kReduceBatchMax - 4) {           // many modes: flush and start the next batch
-      reduce_batch(rb, redws_.d(), stream_);
-      rb = ReduceBatch();
-    }
-  }
-  reduce_batch(rb, redws_.d(), stream_);
-}
-
-static bool stop_one(double f, double fo, const aoadmm_options& o) {
-  const double rel = fo > 0 ? std::fabs(fo - f) / fo : std::fabs(fo - f);    // evaluate_stopping_conditions.m:8-15
-  return f < o.AbsFuncTol || rel < o.OuterRelTol;
-}
-
-void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
-  require_usable();
-  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
-  AO_REQUIRE(out != nullptr, "null result");
-  AO_REQUIRE(opt.MaxOuterIters >= 0 && opt.MaxInnerIters >= 1, "bad iteration limits");
-  AO_HIP(hipSetDevice(device_));
-  prepared_mode_ = -1;                                // nothing prepared ahead by an earlier solve is valid for this state
-  allow_xp_ = opt.no_permuted_copy == 0;
-  if (!allow_xp_)
-    for (int p = 0; p < n_tensors_; ++p)
-      drop_pass_copies(tensors_[p].blk);
-  for (int p = 0; p < n_tensors_; ++p) {
-    AO_REQUIRE(tensors_[p].blk.has_data, "tensor %d has no data (Z.object{%d})", p, p + 1);
-  }
-  for (int m = 0; m < n_modes_; ++m) {
-    ModeInfo& mi = modes_[m];
-    AO_REQUIRE(mi.has_fac, "G.fac{%d} missing", m + 1);
-    if (mi.constrained) AO_REQUIRE(mi.has_Z && mi.has_mu, "G.constraint_fac{%d} / constraint_dual_fac{%d} missing", m + 1, m + 1);
-    if (mi.coupling >= 0) {
-      AO_REQUIRE(mi.has_muD && mi.muD_rows == mi.img_rows && mi.muD_cols == mi.img_cols, "G.coupling_dual_fac{%d} missing or mis-sized", m + 1);
-      AO_REQUIRE(couplings_[mi.coupling].has_state, "G.coupling_fac{%d} missing", mi.coupling + 1);
-    }
-    ensure_mode_work(mi);
-    if (!mi.slabs) compute_gram(mi);                                         // :62-81
-  }
-  for (int p = 0; p < n_tensors_; ++p) {
-    TensorInfo& t = tensors_[p];
-    if (t.par2) {
-      for (int k = 0; k < t.p2.K; ++k)
-        AO_REQUIRE(t.p2.have_P[k] && t.p2.have_mu[k], "G.P{%d}{%d} / G.mu_DeltaB{%d}{%d} missing", p + 1, k + 1, p + 1, k + 1);
-    }
-    (void)tensor_normsq(p);          // Znorm_const{p}; a masked block needs the factors (statistics-only EM pass)
-  }
-  const bool has_miss = has_missing();
-  for (int p = 0; p < n_tensors_; ++p) {
-    TensorInfo& t = tensors_[p];
-    if (!t.par2) continue;
-    Par2Block& b = t.p2;
-    AO_REQUIRE(b.has_DeltaB, "G.DeltaB{%d} missing", p + 1);
-    for (int k = 0; k < b.K; ++k) AO_REQUIRE(b.have_P[k] && b.have_mu[k], "G.P{%d}{%d} / G.mu_DeltaB{%d}{%d} missing", p + 1, k + 1, p + 1, k + 1);
-    par2_ensure_work(t);
-    {
-      // slabs over the ranks or every slab on every rank (aoadmm_options.par2_slab_sharding)
-      const ModeInfo& mB = modes_[t.modes[1]];
-      const bool can = sharded() && world_ > 1 && !b.has_mask && !b.sparse && !(mB.constrained && mB.prox.type == AOADMM_C_TPARAFAC2) &&
-                       modes_[t.modes[2]].coupling < 0;     // a coupled C mode needs every row system on every rank
-      const bool want = opt.par2_slab_sharding > 0 || (opt.par2_slab_sharding == 0 && b.K / world_ >= 1024);
-      const int per = (int)cdiv(b.K, world_);
-      // every rank must own a slab, and every rank must reach the same verdict: otherwise repeat the block
-      b.slab_sharded = can && want && (int64_t)per * (world_ - 1) < b.K;
-      b.k0 = std::min(b.K, per * rank_);
-      b.k1 = std::min(b.K, b.k0 + per);
-    }
-    par2_gram(modes_[t.modes[1]].fac.d(), b.dims(), b.GB.d(), stream_);      // :71-73
-    t.last_pos = 2;
-  }
-  const int nctl = n_modes_ + n_couplings_;
-  const int nslots = n_modes_ * kSlotsPerMode + 2 * n_tensors_;
-  // pinned landing area + event: the host waits for the objective values only, not for work enqueued
-  // behind them (prefetch_next_contraction)
-  struct Pinned {
-    void* p = nullptr; hipEvent_t ev = nullptr;
-    ~Pinned() { if (p) (void)hipHostFree(p); if (ev) (void)hipEventDestroy(ev); }
-  } pin;
-  // per PARAFAC2 block: K + 1 slab residuals (+ the not-PD flag of sharded slabs), 4 K gap sums, K regulariser values --
-  // read back with everything else behind ONE event (three more copies into pageable memory with a stream
-  // synchronisation each left the GPU idle for ~60 us per outer iteration of config 4)
-  const char* rb_base = readback_.as<char>();
-  auto in_arena = [&](const DevBuf& d) {
-    return !d.owned && static_cast<const char*>(d.p) >= rb_base && static_cast<const char*>(d.p) + d.bytes <= rb_base + readback_.bytes;
-  };
-  AO_REQUIRE(in_arena(slots_) && in_arena(ctls_), "read-back arena: slots / loop-control blocks are not views of it");
-  AO_HIP(hipHostMalloc(&pin.p, readback_.bytes, hipHostMallocDefault));
-  AO_HIP(hipEventCreateWithFlags(&pin.ev, hipEventDisableTiming));
-  char* hb = static_cast<char*>(pin.p);
-  double* hs = reinterpret_cast<double*>(hb + (slots_.as<char>() - rb_base));
-  double* hem = hs + (em_slot(0) - slots_.d());                                // EM statistics, 4 per tensor
-  AdmmCtl* hctl = reinterpret_cast<AdmmCtl*>(hb + (ctls_.as<char>() - rb_base));
-  std::vector<double*> hp2v(n_tensors_, nullptr);                              // PARAFAC2 per-slab values: res | q | regv
-  for (int p = 0; p < n_tensors_; ++p) {
-    if (!tensors_[p].par2) continue;
-    Par2Block& b = tensors_[p].p2;
-    AO_REQUIRE(in_arena(b.res) && in_arena(b.q) && in_arena(b.regv) && b.q.d() == b.res.d() + b.K + 1 &&
-               b.regv.d() == b.res.d() + 5 * b.K + 1, "read-back arena: PARAFAC2 block %d keeps its sums elsewhere", p);
-    hp2v[p] = reinterpret_cast<double*>(hb + (b.res.as<char>() - rb_base));
-  }
-  (void)nslots;
-
-  auto enqueue_readback = [&]() {
-    AO_HIP(hipMemcpyAsync(hb, readback_.p, readback_.bytes, hipMemcpyDeviceToHost, stream_));
-    AO_HIP(hipEventRecord(pin.ev, stream_));
-  };
-  auto finish_eval = [&](double f[4]) {
-    AO_HIP(hipEventSynchronize(pin.ev));
-    for (int i = 0; i < nctl; ++i)
-      if (hctl[i].notpd)
-        throw Error(AOADMM_ERR_NOT_PD, "Cholesky failed: system matrix is not positive definite (chol in cmtf_fun_AOADMM.m:142/273/362)");
-    double ft = 0.0, fpar = 0.0, fcon = 0.0;
-    int ncon = 0;
-    for (int p = 0; p < n_tensors_; ++p) {
-      TensorInfo& t = tensors_[p];
-      const double* sp = hs + n_modes_ * kSlotsPerMode + 2 * p;
-      const bool masked = t.par2 ? t.p2.has_mask : t.blk.has_mask;
-      if (t.par2) {
-        Par2Block& b = t.p2;
-        const double* res = hp2v[p];
-        const double* q = res + b.K + 1;
-        if (b.slab_sharded && res[b.K] > 0)         // some rank's slabs hit a non-positive-definite system (the slot is only written then)
-          throw Error(AOADMM_ERR_NOT_PD, "Cholesky failed in a PARAFAC2 slab system on another rank (chol in cmtf_fun_AOADMM.m:212/240)");
-        double fp = 0.0;
-        if (masked) fp = hem[4 * p + 2];                                                        // :1249-1252
-        else if (t.eval_shortcut) fp = t.normsq - 2.0 * (sp[0] / t.weight) + sp[1];               // :1254-1260
-        else for (int k = 0; k < b.K; ++k) fp += res[k];                                        // :1262-1264
-        ft += t.weight * fp;                                                                    // :1267
-        const ModeInfo& mB = modes_[t.modes[1]];
-        double gp = 0.0, gz = 0.0, nb2 = 0.0;
-        for (int k = 0; k < b.K; ++k) {
-          const double nb = std::sqrt(q[4 * k + 1]);
-          gp += std::sqrt(q[4 * k]) / nb;                                                       // :1355
-          gz += std::sqrt(q[4 * k + 2]) / nb;                                                   // :1337
-          nb2 += q[4 * k + 1];
-        }
-        fpar += gp;
-        if (mB.constrained && mB.prox.type == AOADMM_C_TPARAFAC2) {        // t_smoothness_penalty.m via reg_func (:1276-1277)
-          double pen = 0.0;
-          for (int k = 1; k < b.K; ++k) pen += q[4 * k + 3];
-          ft += mB.prox.p0 * pen;
-        }
-        if (mB.constrained && prox_has_reg_value(mB.prox.type)) {          // sum_k reg_func(B_k) (:1279-1281)
-          const double* rv = res + 5 * b.K + 1;
-          for (int k = 0; k < b.K; ++k) ft += rv[k];
-        }
-        if (mB.constrained) {
-          const double g = gz / b.K;                                                            // :1339
-          fcon += g;
-          if (g != 0.0) ++ncon;
-          if (has_ridge_) ft += mB.ridge * nb2;                                                 // :1292-1295 (quirk: only if constrained)
-        }
-      } else if (masked) {
-        ft += t.weight * hem[4 * p + 2];                                       // :1224-1226 = w * ||miss.*(X - M)||^2
-      } else {
-        const double f2 = sp[0] / t.weight;                                   // last_mttkrp = A*1/w (:121)
-        ft += t.weight * (t.normsq - 2.0 * f2 + sp[1]);                        // :1235-1241
-      }
-    }
-    if (fpar > 0) {                                                            // :1360-1362 (quirk: K of the LAST tensor)
-      const TensorInfo& tl = tensors_[n_tensors_ - 1];
-      fpar /= tl.par2 ? tl.p2.K : 1;
-    }
-    std::vector<double> cp(n_couplings_, 0.0);
-    for (int m = 0; m < n_modes_; ++m) {
-      const ModeInfo& mi = modes_[m];
-      if (mi.slabs) continue;
-      const double* sm = hs + (int64_t)m * kSlotsPerMode;
-      const double nf = std::sqrt(sm[0]);
-      if (mi.constrained) {
-        const int ty = mi.prox.type;
-        if (prox_has_reg_value(ty)) ft += sm[3];                               // reg_func (:1272-1288)
-        const double g = std::sqrt(sm[1]) / nf;                               // :1341
-        fcon += g;
-        if (g != 0.0) ++ncon;
-      }
-      if (has_ridge_) ft += mi.ridge * sm[0];                                  // :1297
-      if (mi.coupling >= 0) {                                                  // :1309-1323
-        const int cty = couplings_[mi.coupling].type;
-        const double den = (cty == 1 || cty == 2 || cty == 5) ? std::sqrt(sm[4]) : nf;
-        cp[mi.coupling] += std::sqrt(sm[2]) / den;
-      }
-    }
-    double fc = 0.0; int nc = 0;
-    for (double v : cp) { fc += v; if (v != 0.0) ++nc; }
-    if (fc > 0) fc /= nc;                                                      // :1327-1329
-    if (fcon > 0) fcon /= ncon;                                                // :1346-1348
-    f[0] = ft; f[1] = fc; f[2] = fcon; f[3] = fpar;
-  };
-
-  double f[4], fo[4];
-  eval_objective_enqueue(true);                                                // :32
-  enqueue_readback();
-  finish_eval(f);
-  if (out->func_val_conv) out->func_val_conv[0] = f[0];
-  if (out->func_coupl_conv) out->func_coupl_conv[0] = f[1];
-  if (out->func_constr_conv) out->func_constr_conv[0] = f[2];
-  if (out->func_PAR2_coupl) out->func_PAR2_coupl[0] = f[3];
-  if (out->time_at_it) out->time_at_it[0] = 0.0;
-  double f_rel_missing = std::nan("");                                          // :30
-  if (out->func_rel_missing) out->func_rel_missing[0] = f_rel_missing;
-  const bool report = progress_fn_ != nullptr && progress_every_ > 0;
-  if (report) progress_fn_(progress_user_, 0, f, f_rel_missing);               // :53-59
-  const auto t0 = std::chrono::steady_clock::now();
-
-  int iter = 1;
-  bool stop = false;
-  while (iter <= opt.MaxOuterIters && !stop) {                                 // :87
-    for (ModeInfo& mq : modes_) mq.quad.dirty = true;   // rho moves once per outer iteration ('quadratic regularization', non-symmetric L)
-    if (iter == 3)                                      // by now every pass of the schedule has run once: all copies exist
-      for (int p = 0; p < n_tensors_; ++p)
-        if (!tensors_[p].par2) maybe_release_natural(block_ctx(), tensors_[p].blk, tensors_[p].normsq_valid);
-    for (int cid = -1; cid < n_couplings_; ++cid) {                            // :89 (0 = uncoupled first)
-      std::vector<int> cm;
-      for (int m = 0; m < n_modes_; ++m)
-        if (modes_[m].coupling == cid) cm.push_back(m);
-      if (cm.empty()) continue;
-      std::set<int> ps;
-      for (int m : cm) ps.insert(modes_[m].tensor);
-      for (int p : ps)                                                         // :91
-        for (int m : cm)                                                       // :93
-          if (modes_[m].tensor == p) {
-            const bool par2 = tensors_[p].par2;
-            if (par2 && modes_[m].pos == 1) par2_update_B(m, opt, iter);             // :191-218
-            else if (par2 && modes_[m].pos == 2 && cid < 0) par2_update_C(m, opt);   // :219-248
-            else if (par2 && modes_[m].pos == 2) par2_prepare_C_coupled(m, couplings_[cid].type, opt);
-            else if (cid < 0) update_uncoupled_cp_mode(m, opt);
-            else {
-              // system of a coupled mode: +rho/2*I (types 0, 3, 4: :269, :336, :358), +rho/2*H*H' (type 2, :314),
-              // nothing for the Sylvester types 1, 5 (:288-293, :377-382); +rho/2*I more if constrained
-              const int cty = couplings_[cid].type;
-              const int con = modes_[m].constrained ? 1 : 0;
-              prepare_mode_system(m, (cty == 0 || cty == 3 || cty == 4) ? 1 + con : (cty == 2 ? con : 0), opt);
-            }
-          }
-      if (cid >= 0) {
-        coupled_admm(cid, opt);                                                // :277 / :366
-        for (int m : cm) { modes_[m].version++; compute_gram(modes_[m]); }      // :393-403
-      }
-    }
-    if (has_miss)                                                              // EM imputation (:408-441)
-      for (int p = 0; p < n_tensors_; ++p)
-        if (tensors_[p].par2 ? tensors_[p].p2.has_mask : tensors_[p].blk.has_mask)
-          em_pass_enqueue(p, 1, opt.use_dimtree != 0 && iter < opt.MaxOuterIters);
-    for (int i = 0; i < 4; ++i) fo[i] = f[i];
-    if (iter < opt.MaxOuterIters) {
-      // The objective needs nothing the first tensor pass of the next iteration writes (frag, T), and that pass does
-      // not depend on the stopping decision: the pass goes onto the main stream, the objective kernels and their
-      // read-back onto the side stream behind an event, and the main stream takes up its small kernels again only
-      // when the objective is through (they overwrite what it reads).  ~50 us per iteration off the critical path.
-      // (Only when a pass is actually launched: the cross-stream wait alone costs ~40 us.)
-      AO_HIP(hipEventRecord(side_ev_, stream_));
-      if (prefetch_next_contraction(opt)) {
-        AO_HIP(hipStreamWaitEvent(side_, side_ev_, 0));
-        std::swap(stream_, side_);
-        try {
-          eval_objective_enqueue(false);                                       // :447
-          enqueue_readback();
-        } catch (...) { std::swap(stream_, side_); throw; }
-        std::swap(stream_, side_);
-        AO_HIP(hipStreamWaitEvent(stream_, pin.ev, 0));
-      } else {
-        eval_objective_enqueue(false);                                         // :447
-        enqueue_readback();
-        // No pass to hide behind: the host now waits ~45 us for the read-back before it can enqueue anything, and the
-        // GPU would sit idle.  The MTTKRP (reductions over the cached T) and the system build of the next iteration's
-        // first mode depend on no stopping decision and write only that mode's scratch (A, C, rho, B, L, inv, ctl --
-        // behind the read-back of this iteration's loop counters in stream order): enqueue them now.
-        if (!has_miss) prepare_next_first_mode(opt);
-      }
-    } else {
-      eval_objective_enqueue(false);                                           // :447
-      enqueue_readback();
-    }
-    finish_eval(f);
-    if (out->func_val_conv) out->func_val_conv[iter] = f[0];
-    if (out->func_coupl_conv) out->func_coupl_conv[iter] = f[1];
-    if (out->func_constr_conv) out->func_constr_conv[iter] = f[2];
-    if (out->func_PAR2_coupl) out->func_PAR2_coupl[iter] = f[3];
-    if (out->time_at_it)
-      out->time_at_it[iter] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (out->innerIters) {
-      for (int m = 0; m < n_modes_; ++m) {
-        const ModeInfo& mi = modes_[m];
-        double v;
-        if (mi.coupling >= 0) v = hctl[n_modes_ + mi.coupling].iters;          // :392
-        else if (mi.slabs) v = hctl[m].iters;                                  // :215
-        else if (mi.constrained) v = hctl[m].iters;                            // :146
-        else v = 1;                                                            // :138
-        out->innerIters[(int64_t)(iter - 1) * n_modes_ + m] = v;
-      }
-    }
-    stop = stop_one(f[0], fo[0], opt) && stop_one(f[1], fo[1], opt) && stop_one(f[2], fo[2], opt) &&
-           stop_one(f[3], fo[3], opt);                                         // :456
-    if (has_miss) {
-      double num = 0.0, den = 0.0;
-      for (int p = 0; p < n_tensors_; ++p)
-        if (tensors_[p].par2 ? tensors_[p].p2.has_mask : tensors_[p].blk.has_mask) { num += hem[4 * p]; den += hem[4 * p + 1]; }
-      f_rel_missing = den > 0 ? std::sqrt(num / den) : std::sqrt(num);        // :436-440
-      if (out->func_rel_missing) out->func_rel_missing[iter] = f_rel_missing;
-      stop = stop && (f_rel_missing < opt.OuterRelTol);                        // :457-459
-    }
-    if (report && iter % progress_every_ == 0) progress_fn_(progress_user_, iter, f, f_rel_missing);   // :462-468
-    ++iter;
-  }
-  out->f_tensors = f[0]; out->f_couplings = f[1]; out->f_constraints = f[2]; out->f_PAR2_couplings = f[3];
-  out->f_rel_missing = f_rel_missing;
-  for (int p = 0; p < n_tensors_; ++p)
-    if (tensors_[p].par2) par2_gather_slabs(tensors_[p]);
-  AO_HIP(hipStreamSynchronize(stream_));
-  out->OuterIterations = iter - 1;
-  out->exit_code = iter > opt.MaxOuterIters ? 0 : 1;                           // make_exit_flag.m:4-5
-  for (int i = 0; i < 4; ++i) out->exit_abs[i] = f[i] < opt.AbsFuncTol ? 1 : 0;
-}
-
 // Y = X_(n) X_(n)' of the RESIDENT data of tensor p (cmtf_nvecs.m:31-56, init_coupled_AOADMM_CMTF.m:50-73): the Gram
 // matrix whose leading eigenvectors initialise mode `pos` with init_options.nvecs = 1, without another transfer of the
 // tensor.  CP blocks (matrices, 3-way): any mode; PARAFAC2 blocks: pos 0 = [X_1 ... X_K] X_k' summed, pos 1 = X_k' X_k
@@ -1594,12 +859,9 @@ void Engine::resident_mttkrp(int p, int pos, double* out_host, float* ms) {
   AO_HIP(hipSetDevice(device_));
   TensorInfo& t = tensors_[p];
   AO_REQUIRE(pos >= 0 && pos < t.nmodes, "tensor mode %d out of range", pos);
+  for (int i = 0; i < t.nmodes; ++i) AO_REQUIRE(modes_[t.modes[i]].has_fac, "G.fac{%d} missing", t.modes[i] + 1);
   FactorRef facs[8];
-  for (int i = 0; i < t.nmodes; ++i) {
-    ModeInfo& o = modes_[t.modes[i]];
-    AO_REQUIRE(o.has_fac, "G.fac{%d} missing", t.modes[i] + 1);
-    facs[i] = factor_ref(o);
-  }
+  factor_refs(t, facs);
   ModeInfo& mi = modes_[t.modes[pos]];
   ensure_mode_work(mi);
   hipEvent_t e0, e1;

@@ -6,10 +6,6 @@
 
 namespace aoadmm {
 
-double* Engine::resid_slots(int m) {
-  return slots_.d() + n_modes_ * kSlotsPerMode + 2 * n_tensors_ + (int64_t)m * kResidPerMode;
-}
-
 void Engine::add_par2(int p, const int* modes3, double weight) {
   AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
   TensorInfo& t = tensors_[p];
@@ -474,7 +470,7 @@ void Engine::par2_objective_enqueue(TensorInfo& t) {
   if (regs) par2_reg_values(mB.fac.d(), mB.prox.type, mB.prox.p0, d, b.regv.d(), stream_);
   if (b.slab_sharded) {
     // res[K] carries the not-positive-definite flags of this block's modes, so that a Cholesky failure in one
-    // rank's slabs stops every rank (finish_eval) instead of leaving the others waiting in a collective
+    // rank's slabs stops every rank (check_not_pd) instead of leaving the others waiting in a collective
     par2_collect_notpd(ctl_of_mode(t.modes[0]), ctl_of_mode(t.modes[1]), ctl_of_mode(t.modes[2]), b.res.d() + b.K, stream_);
     allreduce(b.res.d(), b.K + 1);
     allreduce(b.q.d(), (int64_t)b.K * 4);

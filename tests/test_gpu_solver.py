@@ -493,6 +493,58 @@ def test_em_missing_cp_parafac2_script12(pkg, eng):
     _compare_em(oo, og)
 
 
+def _three_block_model(order, rng):
+    """Three uncoupled blocks, R = 3, weights 0.3 / 0.5 / 0.2: a CP block 11 x 9 x 7 (non-negative modes) and two PARAFAC2
+    blocks with I = 10, K = 5 then K = 9 and ragged J_k = 8 + (3k) % 5 (A, B_k free, C non-negative), 5 % noise."""
+    from helpers import cp_data, par2_slabs
+    R, Ks = 3, [5, 9]
+    size, modes, constraints, objects, distr = [], [], [], [], []
+    for model in order:
+        modes.append([len(size) + 1, len(size) + 2, len(size) + 3])
+        if model == 'CP':
+            X, _ = cp_data((11, 9, 7), R, rng, 0.05)
+            size += [11, 9, 7]
+            constraints += [('non-negativity',)] * 3
+            distr += [lambda a, b: rng.random((a, b))] * 3
+        else:
+            K = Ks.pop(0)
+            Jk = [8 + (3 * k) % 5 for k in range(K)]
+            X, _ = par2_slabs(10, Jk, R, rng, 0.05)
+            size += [10, Jk, K]
+            constraints += [None, None, ('non-negativity',)]
+            distr += [lambda a, b: rng.standard_normal((a, b)), lambda a, b: rng.standard_normal((a, b)),
+                      lambda a, b: rng.random((a, b)) + 0.1]
+        objects.append(X)
+    n = len(size)
+    Z = dict(loss_function=['Frobenius'] * 3, model=list(order), modes=modes, size=size,
+             coupling=dict(lin_coupled_modes=[0] * n, coupling_type=[], coupl_trafo_matrices=[None] * n),
+             constrained_modes=[0 if c is None else 1 for c in constraints], constraints=constraints,
+             weights=[0.3, 0.5, 0.2], object=objects)
+    io = dict(lambdas_init=[[1] * R] * 3, nvecs=0, distr=distr, normalize=1)
+    return Z, io
+
+
+@pytest.mark.parametrize('masked', [False, True], ids=['full', 'missing'])
+@pytest.mark.parametrize('order', [('PAR2', 'CP', 'PAR2'), ('PAR2', 'PAR2', 'CP')], ids=['par2-last', 'cp-last'])
+def test_two_parafac2_blocks_and_a_cp_block(pkg, eng, order, masked):
+    """Two PARAFAC2 blocks in one model, with a CP block between or behind them: the second block's place in the
+    read-back arena, the per-tensor and EM slots of tensors behind a PARAFAC2 block, a block without missing data
+    (the first) beside masked ones, and both sides of the quirk that divides f_PAR2_couplings by the K of the LAST
+    tensor (cmtf_fun_AOADMM.m:1360-1362: by 9, or by 1 where the CP block is last)."""
+    rng = np.random.default_rng(5)
+    Z, io = _three_block_model(order, rng)
+    if masked:
+        full = Z['object'][0]
+        Z = _with_mask(Z, rng)
+        Z['object'][0] = full
+        Z['miss'][0] = None
+    Fo, oo, Fg, og = run_both(pkg, eng, Z, io, options(MaxOuterIters=6))
+    assert np.all(np.isfinite(oo['func_val_conv'])) and oo['func_PAR2_coupl'][0] > 0
+    compare_par2(Fo, oo, Fg, og)
+    if masked:
+        _compare_em(oo, og)
+
+
 def test_em_missing_fp32_tensor(pkg, eng):
     """fp32-resident tensor: imputation and statistics in fp32/fp64 mix, stated tolerance 1e-4."""
     rng = np.random.default_rng(34)
