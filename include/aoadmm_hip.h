@@ -229,7 +229,8 @@ int aoadmm_tensor_synth(aoadmm_ctx* ctx, int p, int rank, uint64_t seed, double 
  * Sizes come from aoadmm_model_set_mode (each below 2^31); a subscript out of range or nnz < 0 is
  * AOADMM_ERR_INVALID, nnz = 0 is valid.  A later aoadmm_tensor_upload replaces the sparse form and this call
  * replaces a dense one.  On a sparse block aoadmm_tensor_mask_upload, aoadmm_tensor_upload_rows and
- * aoadmm_tensor_synth return AOADMM_ERR_INVALID and aoadmm_resident_unfold_gram AOADMM_ERR_UNSUPPORTED;
+ * aoadmm_tensor_synth return AOADMM_ERR_INVALID and aoadmm_resident_unfold_gram AOADMM_ERR_UNSUPPORTED
+ * (aoadmm_resident_nvecs gives the leading eigenvectors instead);
  * aoadmm_tensor_normsq, aoadmm_resident_mttkrp and aoadmm_solve work as for dense data.  With a communicator
  * every rank holds all nonzeros and computes the complete MTTKRP (no collective for the block). */
 int aoadmm_tensor_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* vals);
@@ -291,6 +292,26 @@ int aoadmm_op_unfold_gram(aoadmm_ctx* ctx, const double* X, int ndims, const int
  * the partial sums of the row blocks are all-reduced; the first mode of a row-sharded block has no local answer:
  * AOADMM_ERR_UNSUPPORTED (use aoadmm_op_unfold_gram with the host array). */
 int aoadmm_resident_unfold_gram(aoadmm_ctx* ctx, int p, int tensor_mode, int slab, double* out);
+/* The r leading eigenvectors of X_(n) X_(n)' for the RESIDENT SPARSE data of tensor p: the start that
+ * init_options.nvecs = 1 asks for (cmtf_nvecs.m:54-56) without the I_n x I_n Gram matrix, by block subspace iteration
+ * with Rayleigh-Ritz on the nonzeros (two passes over them per iteration).
+ *   Accepted: a sparse CP block (aoadmm_tensor_upload_coo), any tensor_mode, order 2..8; a PARAFAC2 block with sparse
+ *   slabs (aoadmm_par2_slab_upload_coo), tensor_mode 0 (sum_k X_k X_k').  Dense data and tensor_mode 1, 2 of a
+ *   PARAFAC2 block: AOADMM_ERR_UNSUPPORTED (dense data have aoadmm_resident_unfold_gram).  A block without nonzeros,
+ *   r outside 1..min(I_n, 64) or ldU < I_n: AOADMM_ERR_INVALID.  Work arrays that do not fit the free device memory:
+ *   AOADMM_ERR_NOMEM, before anything is launched.
+ *   Options (null or zeros = defaults): oversample (8): the iterated block has b = min(I_n, 64, max(r, min(F, r +
+ *   oversample))) columns, F the number of non-empty mode-n fibers, so the oversampling shrinks for r > 64 - oversample;
+ *   max_iters (500); tol (1e-10) on the residual ||Y Q_r - V Q_r Theta_r||_F / theta_1 of the first r Ritz pairs;
+ *   seed of the counter-based generator of the start block (deterministic, matches no host generator).
+ *   U: I_n x r column-major with leading dimension ldU, columns by descending eigenvalue, each with its entry of
+ *   largest magnitude positive (the first such entry on a tie); eigvals (optional): the r eigenvalues.  Not converged
+ *   within max_iters is not an error: AOADMM_OK with info->converged = 0 and the last iterate.  Bitwise reproducible
+ *   for a given seed.  With a communicator the block is replicated: every rank computes the same bits, no collective. */
+typedef struct { int oversample; int max_iters; double tol; uint64_t seed; } aoadmm_nvecs_options;
+typedef struct { int iterations; int converged; int block; double residual; int64_t fibers; } aoadmm_nvecs_info;
+int aoadmm_resident_nvecs(aoadmm_ctx* ctx, int p, int tensor_mode, int r, const aoadmm_nvecs_options* opt_or_null,
+                          double* U, int64_t ldU, double* eigvals_or_null, aoadmm_nvecs_info* info_or_null);
 /* G'*G : cmtf_fun_AOADMM.m:66,148 */
 int aoadmm_op_gram(aoadmm_ctx* ctx, const double* F, int64_t rows, int R, double* out);
 /* L = chol(B','lower') : cmtf_fun_AOADMM.m:142 ; AOADMM_ERR_NOT_PD on failure */

@@ -32,7 +32,7 @@ SYMBOLS = [
     'aoadmm_model_set_coupling_type', 'aoadmm_model_set_ridge', 'aoadmm_model_end', 'aoadmm_tensor_upload',
     'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq',
     'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_resident_par2_rhs', 'aoadmm_kernel_stats',
-    'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
+    'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_resident_nvecs', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
     'aoadmm_op_admm_mode', 'aoadmm_op_par2_b_loop',
 ]
 
@@ -74,6 +74,15 @@ class Result(C.Structure):
         ('time_at_it', C.POINTER(C.c_double)), ('innerIters', C.POINTER(C.c_double)),
         ('f_rel_missing', C.c_double), ('func_rel_missing', C.POINTER(C.c_double)),
     ]
+
+
+class NvecsOptions(C.Structure):                  # aoadmm_nvecs_options (zeros = defaults)
+    _fields_ = [('oversample', C.c_int), ('max_iters', C.c_int), ('tol', C.c_double), ('seed', C.c_uint64)]
+
+
+class NvecsInfo(C.Structure):                     # aoadmm_nvecs_info
+    _fields_ = [('iterations', C.c_int), ('converged', C.c_int), ('block', C.c_int), ('residual', C.c_double),
+                ('fibers', C.c_int64)]
 
 
 _lib = None
@@ -133,6 +142,8 @@ def load_library():
     lib.aoadmm_op_mttkrp.argtypes = [vp, dp, C.c_int, C.POINTER(i64), C.POINTER(dp), C.c_int, C.c_int, C.c_int, dp]
     lib.aoadmm_op_unfold_gram.argtypes = [vp, dp, C.c_int, C.POINTER(i64), C.c_int, C.c_int, dp]
     lib.aoadmm_resident_unfold_gram.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
+    lib.aoadmm_resident_nvecs.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(NvecsOptions), dp, i64, dp,
+                                          C.POINTER(NvecsInfo)]
     lib.aoadmm_op_gram.argtypes = [vp, dp, i64, C.c_int, dp]
     lib.aoadmm_op_chol.argtypes = [vp, dp, C.c_int, dp]
     lib.aoadmm_op_prox.argtypes = [vp, C.c_int, dp, C.c_int, dp, dp, i64, C.c_int, C.c_double, dp]

@@ -553,6 +553,18 @@ int aoadmm_resident_unfold_gram(aoadmm_ctx* ctx, int p, int tensor_mode, int sla
   });
 }
 
+int aoadmm_resident_nvecs(aoadmm_ctx* ctx, int p, int tensor_mode, int r, const aoadmm_nvecs_options* opt, double* U,
+                          int64_t ldU, double* eigvals, aoadmm_nvecs_info* info) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    AO_REQUIRE(U != nullptr, "null pointer");
+    // the block is replicated: every engine of a multi-device context computes the same bits, rank 0 reports
+    on_engines(ctx, [&](Engine& e, int rk) {
+      e.resident_nvecs(p, tensor_mode, r, opt, rk == 0 ? U : nullptr, ldU, rk == 0 ? eigvals : nullptr, rk == 0 ? info : nullptr);
+    });
+  });
+}
+
 int aoadmm_op_gram(aoadmm_ctx* ctx, const double* F, int64_t rows, int R, double* out) {
   CTX_OR_FAIL(ctx);
   return guarded([&] {

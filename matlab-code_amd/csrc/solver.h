@@ -170,6 +170,8 @@ class Engine {
   void solve(const aoadmm_options& opt, aoadmm_result* out);
   void resident_mttkrp(int p, int pos, double* out_host, float* ms);
   void resident_unfold_gram(int p, int pos, int slab, double* out_host);
+  void resident_nvecs(int p, int pos, int r, const aoadmm_nvecs_options* opt, double* U_host, int64_t ldU, double* eig_host,
+                      aoadmm_nvecs_info* info);
   void resident_par2_rhs(int p, int pos, double* out_host, float* ms);
   void kernel_stats(int which, int reset, double* ms, int64_t* launches, double* bytes, double* flops);
 

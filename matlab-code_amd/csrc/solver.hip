@@ -3,6 +3,7 @@
 #include "solver.h"
 #include "em.h"
 #include "hosteig.h"
+#include "sparse_nvecs.h"
 
 #include <algorithm>
 #include <cmath>
@@ -851,6 +852,45 @@ void Engine::resident_unfold_gram(int p, int pos, int slab, double* out_host) {
   if (reduce) allreduce(y.d(), a.n * a.n);
   if (out_host) AO_HIP(hipMemcpyAsync(out_host, y.p, (size_t)a.n * a.n * sizeof(double), hipMemcpyDeviceToHost, stream_));
   AO_HIP(hipStreamSynchronize(stream_));
+}
+
+// The r leading eigenvectors of X_(n) X_(n)' for the RESIDENT sparse data of tensor p (the nvecs start of
+// cmtf_nvecs.m:54-56 without the I_n x I_n Gram matrix): block subspace iteration on the nonzeros, sparse_nvecs.h.
+// Sparse CP blocks: any mode; PARAFAC2 blocks with sparse slabs: pos 0 (sum_k X_k X_k' = Xcat Xcat',
+// init_coupled_AOADMM_CMTF.m first-mode branch).  Every rank of a communicator holds all nonzeros and computes the
+// same bits: no collective.
+void Engine::resident_nvecs(int p, int pos, int r, const aoadmm_nvecs_options* opt, double* U_host, int64_t ldU,
+                            double* eig_host, aoadmm_nvecs_info* info) {
+  require_usable();
+  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
+  AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
+  AO_HIP(hipSetDevice(device_));
+  TensorInfo& t = tensors_[p];
+  AO_REQUIRE(pos >= 0 && pos < t.nmodes, "tensor mode %d out of range", pos);
+  CooBlock* coo = nullptr;
+  if (t.par2) {
+    Par2Block& b = t.p2;
+    for (int k = 0; k < b.K; ++k) AO_REQUIRE(b.have_slab[k], "slab %d of tensor %d has no data", k, p);
+    if (!b.sparse)
+      throw Error(AOADMM_ERR_UNSUPPORTED, fmt("resident nvecs: tensor %d holds dense slabs (use aoadmm_resident_unfold_gram)", p));
+    if (pos != 0)
+      throw Error(AOADMM_ERR_UNSUPPORTED, "resident nvecs: only the first mode of a PARAFAC2 block (the B_k and C modes start on the host)");
+    coo = &b.sp.coo;
+  } else {
+    CpBlock& b = t.blk;
+    AO_REQUIRE(b.has_data, "tensor %d has no data", p);
+    if (!b.sparse)
+      throw Error(AOADMM_ERR_UNSUPPORTED, fmt("resident nvecs: tensor %d is dense (use aoadmm_resident_unfold_gram)", p));
+    coo = &b.coo;
+  }
+  AO_REQUIRE(coo->nnz >= 1, "resident nvecs: tensor %d has no nonzeros", p);
+  AO_REQUIRE(r >= 1 && r <= std::min<int64_t>(coo->dims[pos], kMaxRank), "resident nvecs: r = %d outside 1..%lld", r,
+             (long long)std::min<int64_t>(coo->dims[pos], kMaxRank));
+  AO_REQUIRE(U_host == nullptr || ldU >= coo->dims[pos], "resident nvecs: ldU %lld < %lld rows", (long long)ldU,
+             (long long)coo->dims[pos]);
+  NvecsLists lists;                                    // freed on return
+  nvecs_build_lists(lists, *coo, pos, stream_);
+  sparse_nvecs(lists, r, opt, U_host, ldU, eig_host, info, coo->slot_row, coo->slot_val, &timers_, stream_);
 }
 
 void Engine::resident_mttkrp(int p, int pos, double* out_host, float* ms) {

@@ -45,6 +45,28 @@ void coo_build(CooBlock& b, int nd, const int64_t* dims, int64_t nnz, const int6
 void coo_mttkrp(CooBlock& b, int pos, const CooFactor* f, int R, double scale, double* out, int64_t ldOut,
                 hipStream_t s);
 
+// A list of n entries sorted by `key` (int32, 0 <= key < rows); entry e carries the index gidx[e] and the value val[e]
+struct CooList {
+  const int* key;
+  const int* gidx;
+  const double* val;
+  int64_t n, rows;
+};
+// out(k, 0:R-1) = sum over the entries e with key[e] = k of val[e] * src(gidx[e], 0:R-1), src and out ROW-major with R
+// doubles per row (out: l.rows rows, all of them written).  The MTTKRP's team kernel and carry levels with one gathered
+// factor: no float atomics, bitwise reproducible.  slot_row / slot_val: two carry buffers each (ping-pong per level).
+void coo_list_pass(const CooList& l, const double* src, int R, double* out, DevBuf* slot_row, DevBuf* slot_val,
+                   hipStream_t s);
+
+// Pieces of coo_build that the fiber lists of sparse_nvecs.hip use as well.
+struct CooSortWork { DevBuf permA, permB, keyA, keyB, tmp, stride; };
+// w.permA = the order of the n entries by column-major linear index over the nd index arrays idx[m * n + e]
+// (0 <= idx < dims[m]); stable LSD radix sorts over groups of modes whose linear index fits in 64 bits
+void coo_sort_linear(CooSortWork& w, const int* idx, int64_t n, int nd, const int64_t* dims, hipStream_t s);
+// head[i] = 1 where sorted entry i differs from entry i - 1 in any index, seg = inclusive scan of head (the 1-based run
+// of every sorted entry); returns the number of runs (one host read)
+int64_t coo_runs_scan(CooSortWork& w, DevBuf& head, DevBuf& seg, const int* idx, int64_t n, int nd, hipStream_t s);
+
 // algorithmic bytes (nonzeros streamed + factor rows gathered + output written) and flops of one coo_mttkrp
 double coo_mttkrp_bytes(const CooBlock& b, int pos, int R);
 double coo_mttkrp_flops(const CooBlock& b, int R);

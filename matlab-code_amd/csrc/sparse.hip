@@ -55,8 +55,8 @@ __global__ void coo_runs_k(int* cidx, double* vs, int64_t nc, const int* head, i
   for (int m = 0; m < nd; ++m) cidx[m * nc + s] = idx[m * nnz + q];
 }
 
-static void carry_passes(const int* rin, const double* vin, int64_t n, int R, double scale, double* out, int64_t ldOut,
-                         DevBuf* srow, DevBuf* sval, int next, hipStream_t s);
+static void carry_passes(const int* rin, const double* vin, int64_t n, int R, double scale, double* out, int64_t oI,
+                         int64_t oR, DevBuf* srow, DevBuf* sval, int next, hipStream_t s);
 
 // the copy of mode n: other modes' indices and values in the order of perm (row indices are the sort's keys)
 __global__ void coo_gather_k(int* oidx, double* oval, const int* perm, const int* cidx, const double* cval, int64_t nc,
@@ -87,6 +87,54 @@ static void radix_sort(DevBuf& tmp, const K* kin, K* kout, const int* vin, int* 
   AO_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need, kin, kout, vin, vout, (int)n, 0, bits, s));
   tmp.ensure(need);
   AO_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, need, kin, kout, vin, vout, (int)n, 0, bits, s));
+}
+
+void coo_sort_linear(CooSortWork& w, const int* idx, int64_t nnz, int nd, const int64_t* dims, hipStream_t s) {
+  w.permA.alloc((size_t)nnz * sizeof(int)); w.permB.alloc((size_t)nnz * sizeof(int));
+  w.keyA.alloc((size_t)nnz * sizeof(uint64_t)); w.keyB.alloc((size_t)nnz * sizeof(uint64_t));
+  iota_k<<<blocks_for(nnz), 256, 0, s>>>(w.permA.as<int>(), nnz);
+  AO_KERNEL_CHECK();
+  // Column-major linear order by stable LSD radix sorts over groups of consecutive modes whose linear index fits in
+  // 64 bits (one group, i.e. one 64-bit sort, unless the product of the sizes reaches 2^64)
+  std::vector<int64_t> hstride(nd, 1);
+  std::vector<std::pair<int, int>> groups;
+  for (int m0 = 0; m0 < nd;) {
+    uint64_t prod = 1;
+    int m1 = m0;
+    while (m1 < nd && prod <= UINT64_MAX / (uint64_t)dims[m1]) { hstride[m1] = (int64_t)prod; prod *= (uint64_t)dims[m1]; ++m1; }
+    groups.emplace_back(m0, m1);
+    m0 = m1;
+  }
+  w.stride.alloc(nd * sizeof(int64_t));
+  AO_HIP(hipMemcpyAsync(w.stride.p, hstride.data(), nd * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  for (const auto& g : groups) {
+    uint64_t prod = 1;
+    for (int m = g.first; m < g.second; ++m) prod *= (uint64_t)dims[m];
+    if (prod <= 1) continue;
+    coo_key_k<<<blocks_for(nnz), 256, 0, s>>>(w.keyA.as<uint64_t>(), w.permA.as<int>(), idx, nnz, g.first, g.second,
+                                              w.stride.as<int64_t>());
+    AO_KERNEL_CHECK();
+    radix_sort<uint64_t>(w.tmp, w.keyA.as<uint64_t>(), w.keyB.as<uint64_t>(), w.permA.as<int>(), w.permB.as<int>(), nnz,
+                         bits_for(prod), s);
+    std::swap(w.permA, w.permB);
+  }
+  AO_HIP(hipStreamSynchronize(s));                   // hstride is a local
+}
+
+int64_t coo_runs_scan(CooSortWork& w, DevBuf& head, DevBuf& seg, const int* idx, int64_t nnz, int nd, hipStream_t s) {
+  head.alloc((size_t)nnz * sizeof(int)); seg.alloc((size_t)nnz * sizeof(int));
+  coo_head_k<<<blocks_for(nnz), 256, 0, s>>>(head.as<int>(), w.permA.as<int>(), idx, nnz, nd);
+  AO_KERNEL_CHECK();
+  {
+    size_t need = 0;
+    AO_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, need, head.as<int>(), seg.as<int>(), (int)nnz, s));
+    w.tmp.ensure(need);
+    AO_HIP(hipcub::DeviceScan::InclusiveSum(w.tmp.p, need, head.as<int>(), seg.as<int>(), (int)nnz, s));
+  }
+  int nc32 = 0;
+  AO_HIP(hipMemcpyAsync(&nc32, seg.as<int>() + nnz - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+  AO_HIP(hipStreamSynchronize(s));
+  return nc32;
 }
 
 void coo_build(CooBlock& b, int nd, const int64_t* dims, int64_t nnz, const int64_t* subs, const double* vals,
@@ -120,52 +168,16 @@ void coo_build(CooBlock& b, int nd, const int64_t* dims, int64_t nnz, const int6
     b = std::move(nb);
     return;
   }
-  DevBuf idx, val, permA, permB, keyA, keyB, head, seg, tmp, stride;
+  DevBuf idx, val, head, seg;
+  CooSortWork w;
+  DevBuf &permA = w.permA, &permB = w.permB, &keyA = w.keyA, &keyB = w.keyB, &tmp = w.tmp;
   idx.alloc(hidx.size() * sizeof(int));
   val.alloc((size_t)nnz * sizeof(double));
   AO_HIP(hipMemcpyAsync(idx.p, hidx.data(), hidx.size() * sizeof(int), hipMemcpyHostToDevice, s));
   AO_HIP(hipMemcpyAsync(val.p, vals, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, s));
-  permA.alloc((size_t)nnz * sizeof(int)); permB.alloc((size_t)nnz * sizeof(int));
-  keyA.alloc((size_t)nnz * sizeof(uint64_t)); keyB.alloc((size_t)nnz * sizeof(uint64_t));
-  iota_k<<<blocks_for(nnz), 256, 0, s>>>(permA.as<int>(), nnz);
-  AO_KERNEL_CHECK();
-  // Column-major linear order by stable LSD radix sorts over groups of consecutive modes whose linear index fits in
-  // 64 bits (one group, i.e. one 64-bit sort, unless the product of the sizes reaches 2^64)
-  std::vector<int64_t> hstride(nd, 1);
-  std::vector<std::pair<int, int>> groups;
-  for (int m0 = 0; m0 < nd;) {
-    uint64_t prod = 1;
-    int m1 = m0;
-    while (m1 < nd && prod <= UINT64_MAX / (uint64_t)dims[m1]) { hstride[m1] = (int64_t)prod; prod *= (uint64_t)dims[m1]; ++m1; }
-    groups.emplace_back(m0, m1);
-    m0 = m1;
-  }
-  stride.alloc(nd * sizeof(int64_t));
-  AO_HIP(hipMemcpyAsync(stride.p, hstride.data(), nd * sizeof(int64_t), hipMemcpyHostToDevice, s));
-  for (const auto& g : groups) {
-    uint64_t prod = 1;
-    for (int m = g.first; m < g.second; ++m) prod *= (uint64_t)dims[m];
-    if (prod <= 1) continue;
-    coo_key_k<<<blocks_for(nnz), 256, 0, s>>>(keyA.as<uint64_t>(), permA.as<int>(), idx.as<int>(), nnz, g.first, g.second,
-                                              stride.as<int64_t>());
-    AO_KERNEL_CHECK();
-    radix_sort<uint64_t>(tmp, keyA.as<uint64_t>(), keyB.as<uint64_t>(), permA.as<int>(), permB.as<int>(), nnz,
-                         bits_for(prod), s);
-    std::swap(permA, permB);
-  }
+  coo_sort_linear(w, idx.as<int>(), nnz, nd, dims, s);
   // duplicates: runs of equal subscripts in the sorted order
-  head.alloc((size_t)nnz * sizeof(int)); seg.alloc((size_t)nnz * sizeof(int));
-  coo_head_k<<<blocks_for(nnz), 256, 0, s>>>(head.as<int>(), permA.as<int>(), idx.as<int>(), nnz, nd);
-  AO_KERNEL_CHECK();
-  {
-    size_t need = 0;
-    AO_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, need, head.as<int>(), seg.as<int>(), (int)nnz, s));
-    tmp.ensure(need);
-    AO_HIP(hipcub::DeviceScan::InclusiveSum(tmp.p, need, head.as<int>(), seg.as<int>(), (int)nnz, s));
-  }
-  int nc32 = 0;
-  AO_HIP(hipMemcpyAsync(&nc32, seg.as<int>() + nnz - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-  AO_HIP(hipStreamSynchronize(s));
+  const int nc32 = (int)coo_runs_scan(w, head, seg, idx.as<int>(), nnz, nd, s);
   const int64_t nc = nc32;
   DevBuf cidx, cval, crow[2], cvals[2];
   cidx.alloc((size_t)nd * nc * sizeof(int));
@@ -177,7 +189,7 @@ void coo_build(CooBlock& b, int nd, const int64_t* dims, int64_t nnz, const int6
   // duplicates summed per run with the MTTKRP's carry passes (a list sorted by run id, one value per entry): chunks of
   // 256 entries per team, chunk-boundary partials added level by level in chunk order -- bitwise reproducible, and no
   // thread walks a long run alone however many copies of one subscript the input holds
-  carry_passes(seg.as<int>(), vs, nnz, 1, 1.0, cval.d(), nc, crow, cvals, 0, s);
+  carry_passes(seg.as<int>(), vs, nnz, 1, 1.0, cval.d(), 1, nc, crow, cvals, 0, s);
   idx.release(); val.release(); keyA.release(); keyB.release(); head.release(); seg.release();
   nb.nnz = nc;
   // one copy per mode, stably sorted by that mode's index (32-bit keys)
@@ -213,7 +225,7 @@ struct SegAcc {
   int r, R;
   double scale;
   double* out;
-  int64_t ldOut;
+  int64_t oI, oR;    // element (row, r) of the result at out[row * oI + r * oR]
   int* slot_row;
   double* slot_val;
   int cur = -1;
@@ -224,7 +236,7 @@ struct SegAcc {
     const bool cl = first && start > 0 && rows[start - 1] == cur;
     const bool cr = last && end < n && rows[end] == cur;
     if (!cl && !cr) {
-      if (r < R) out[cur + ldOut * r] = scale * acc;
+      if (r < R) out[cur * oI + oR * r] = scale * acc;
     } else {
       const int64_t sl = 2 * team + (cl ? 0 : 1);
       if (r < R) slot_val[sl * R + r] = acc;
@@ -265,7 +277,7 @@ struct CooArgs {
   int R;
   double scale;
   double* out;
-  int64_t ldOut;
+  int64_t oI, oR;
   int* slot_row;
   double* slot_val;
 };
@@ -284,7 +296,7 @@ __global__ __launch_bounds__(256) void mttkrp_coo_k(CooArgs a) {
   const int rr = r < a.R ? r : a.R - 1;            // lanes beyond R read column R - 1 and store nothing
   SegAcc sa;
   sa.rows = a.row; sa.n = a.nnz; sa.start = start; sa.end = end; sa.team = team;
-  sa.r = r; sa.R = a.R; sa.scale = a.scale; sa.out = a.out; sa.ldOut = a.ldOut;
+  sa.r = r; sa.R = a.R; sa.scale = a.scale; sa.out = a.out; sa.oI = a.oI; sa.oR = a.oR;
   sa.slot_row = a.slot_row; sa.slot_val = a.slot_val;
   for (int64_t i0 = start; i0 < end; i0 += kCooUnroll) {
     int rowu[kCooUnroll];
@@ -314,7 +326,7 @@ __global__ __launch_bounds__(256) void mttkrp_coo_k(CooArgs a) {
 // kCooChunk per team, same rules; rout / vout receive this level's slots (null when one team covers the list)
 template <int G>
 __global__ __launch_bounds__(256) void coo_carry_k(const int* rin, const double* vin, int64_t n, int R, double scale,
-                                                   double* out, int64_t ldOut, int* rout, double* vout) {
+                                                   double* out, int64_t oI, int64_t oR, int* rout, double* vout) {
   const int64_t team = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
   const int r = (int)(threadIdx.x % G);
   const int64_t start = team * kCooChunk;
@@ -323,7 +335,7 @@ __global__ __launch_bounds__(256) void coo_carry_k(const int* rin, const double*
   const int rr = r < R ? r : R - 1;
   SegAcc sa;
   sa.rows = rin; sa.n = n; sa.start = start; sa.end = end; sa.team = team;
-  sa.r = r; sa.R = R; sa.scale = scale; sa.out = out; sa.ldOut = ldOut;
+  sa.r = r; sa.R = R; sa.scale = scale; sa.out = out; sa.oI = oI; sa.oR = oR;
   sa.slot_row = rout; sa.slot_val = vout;
   for (int64_t i0 = start; i0 < end; i0 += kCooUnroll) {
     int rowu[kCooUnroll];
@@ -354,17 +366,17 @@ static void launch_coo(const CooArgs& a, int64_t nteams, hipStream_t s) {
 }
 
 template <int G>
-static void launch_carry(const int* rin, const double* vin, int64_t n, int R, double scale, double* out, int64_t ldOut,
-                         int* rout, double* vout, hipStream_t s) {
-  coo_carry_k<G><<<blocks_for(cdiv(n, kCooChunk) * G), 256, 0, s>>>(rin, vin, n, R, scale, out, ldOut, rout, vout);
+static void launch_carry(const int* rin, const double* vin, int64_t n, int R, double scale, double* out, int64_t oI,
+                         int64_t oR, int* rout, double* vout, hipStream_t s) {
+  coo_carry_k<G><<<blocks_for(cdiv(n, kCooChunk) * G), 256, 0, s>>>(rin, vin, n, R, scale, out, oI, oR, rout, vout);
   AO_KERNEL_CHECK();
 }
 
 // Sums a list sorted by row (rows rin, R-vectors vin, n entries; row -1 = empty) into out, level by level until one team
 // covers the list (a level shrinks the list kCooChunk / 2 = 128 times).  Level outputs alternate between srow/sval[next]
 // and [next ^ 1], never the buffer the level reads.
-static void carry_passes(const int* rin, const double* vin, int64_t n, int R, double scale, double* out, int64_t ldOut,
-                         DevBuf* srow, DevBuf* sval, int next, hipStream_t s) {
+static void carry_passes(const int* rin, const double* vin, int64_t n, int R, double scale, double* out, int64_t oI,
+                         int64_t oR, DevBuf* srow, DevBuf* sval, int next, hipStream_t s) {
   const int G = R <= 4 ? 4 : R <= 8 ? 8 : R <= 16 ? 16 : R <= 32 ? 32 : 64;
   for (;;) {
     const int64_t teams = cdiv(n, kCooChunk);
@@ -377,16 +389,39 @@ static void carry_passes(const int* rin, const double* vin, int64_t n, int R, do
       vout = sval[next].d();
     }
     switch (G) {
-      case 4: launch_carry<4>(rin, vin, n, R, scale, out, ldOut, rout, vout, s); break;
-      case 8: launch_carry<8>(rin, vin, n, R, scale, out, ldOut, rout, vout, s); break;
-      case 16: launch_carry<16>(rin, vin, n, R, scale, out, ldOut, rout, vout, s); break;
-      case 32: launch_carry<32>(rin, vin, n, R, scale, out, ldOut, rout, vout, s); break;
-      default: launch_carry<64>(rin, vin, n, R, scale, out, ldOut, rout, vout, s); break;
+      case 4: launch_carry<4>(rin, vin, n, R, scale, out, oI, oR, rout, vout, s); break;
+      case 8: launch_carry<8>(rin, vin, n, R, scale, out, oI, oR, rout, vout, s); break;
+      case 16: launch_carry<16>(rin, vin, n, R, scale, out, oI, oR, rout, vout, s); break;
+      case 32: launch_carry<32>(rin, vin, n, R, scale, out, oI, oR, rout, vout, s); break;
+      default: launch_carry<64>(rin, vin, n, R, scale, out, oI, oR, rout, vout, s); break;
     }
     if (teams <= 1) break;
     rin = rout; vin = vout; n = 2 * teams;
     next ^= 1;
   }
+}
+
+// the team kernel and the carry levels over one list sorted by a.row; `out` has been cleared by the caller
+static void run_list(CooArgs a, DevBuf* slot_row, DevBuf* slot_val, hipStream_t s) {
+  const int R = a.R;
+  const int64_t nteams = cdiv(a.nnz, kCooChunk);
+  // level-0 slots: two per team (carry_passes sizes the later levels)
+  if (nteams > 1) {
+    const size_t n0 = (size_t)2 * nteams;
+    slot_row[0].ensure(n0 * sizeof(int)); slot_val[0].ensure(n0 * R * sizeof(double));
+  }
+  a.slot_row = nteams > 1 ? slot_row[0].as<int>() : nullptr;
+  a.slot_val = nteams > 1 ? slot_val[0].d() : nullptr;
+  const int G = R <= 4 ? 4 : R <= 8 ? 8 : R <= 16 ? 16 : R <= 32 ? 32 : 64;
+  switch (G) {
+    case 4: launch_coo<4>(a, nteams, s); break;
+    case 8: launch_coo<8>(a, nteams, s); break;
+    case 16: launch_coo<16>(a, nteams, s); break;
+    case 32: launch_coo<32>(a, nteams, s); break;
+    default: launch_coo<64>(a, nteams, s); break;
+  }
+  if (nteams > 1)
+    carry_passes(slot_row[0].as<int>(), slot_val[0].d(), 2 * nteams, R, a.scale, a.out, a.oI, a.oR, slot_row, slot_val, 1, s);
 }
 
 void coo_mttkrp(CooBlock& b, int pos, const CooFactor* f, int R, double scale, double* out, int64_t ldOut,
@@ -399,29 +434,25 @@ void coo_mttkrp(CooBlock& b, int pos, const CooFactor* f, int R, double scale, d
   AO_HIP(hipMemset2DAsync(out, (size_t)ldOut * sizeof(double), 0, (size_t)rows * sizeof(double), (size_t)R, s));
   if (b.nnz == 0) return;
   const CooMode& cm = b.mode[pos];
-  const int64_t nteams = cdiv(b.nnz, kCooChunk);
-  // level-0 slots: two per team (carry_passes sizes the later levels)
-  if (nteams > 1) {
-    const size_t n0 = (size_t)2 * nteams;
-    b.slot_row[0].ensure(n0 * sizeof(int)); b.slot_val[0].ensure(n0 * R * sizeof(double));
-  }
   CooArgs a;
   a.row = cm.row.as<int>(); a.oidx = cm.oidx.as<int>(); a.val = cm.val.d(); a.nnz = b.nnz;
   a.no = b.nd - 1;
   for (int k = 0; k < a.no; ++k) a.f[k] = f[k];
-  a.R = R; a.scale = scale; a.out = out; a.ldOut = ldOut;
-  a.slot_row = nteams > 1 ? b.slot_row[0].as<int>() : nullptr;
-  a.slot_val = nteams > 1 ? b.slot_val[0].d() : nullptr;
-  const int G = R <= 4 ? 4 : R <= 8 ? 8 : R <= 16 ? 16 : R <= 32 ? 32 : 64;
-  switch (G) {
-    case 4: launch_coo<4>(a, nteams, s); break;
-    case 8: launch_coo<8>(a, nteams, s); break;
-    case 16: launch_coo<16>(a, nteams, s); break;
-    case 32: launch_coo<32>(a, nteams, s); break;
-    default: launch_coo<64>(a, nteams, s); break;
-  }
-  if (nteams > 1)
-    carry_passes(b.slot_row[0].as<int>(), b.slot_val[0].d(), 2 * nteams, R, scale, out, ldOut, b.slot_row, b.slot_val, 1, s);
+  a.R = R; a.scale = scale; a.out = out; a.oI = 1; a.oR = ldOut;
+  run_list(a, b.slot_row, b.slot_val, s);
+}
+
+void coo_list_pass(const CooList& l, const double* src, int R, double* out, DevBuf* slot_row, DevBuf* slot_val,
+                   hipStream_t s) {
+  AO_REQUIRE(R >= 1 && R <= kMaxRank, "sparse list pass: width %d outside 1..%d", R, kMaxRank);
+  AO_REQUIRE(l.n >= 1 && l.rows >= 1, "sparse list pass: empty list");
+  AO_HIP(hipMemsetAsync(out, 0, (size_t)l.rows * R * sizeof(double), s));
+  CooArgs a;
+  a.row = l.key; a.oidx = l.gidx; a.val = l.val; a.nnz = l.n;
+  a.no = 1;
+  a.f[0] = CooFactor{src, (int64_t)R, 1};
+  a.R = R; a.scale = 1.0; a.out = out; a.oI = R; a.oR = 1;
+  run_list(a, slot_row, slot_val, s);
 }
 
 double coo_mttkrp_bytes(const CooBlock& b, int pos, int R) {

@@ -85,15 +85,68 @@ def _leading_eigvecs(Y, r):
     return np.asfortranarray(V[:, idx])
 
 
-def cmtf_nvecs(Z, n, r, engine=None):
+NVECS_ITERATIVE_ROWS = 16384     # a sparse mode with more rows than this starts on the device unless told otherwise
+
+
+def _nvecs_method(method, sparse, rows):
+    """`init_options.nvecs_method` -> 'gram' (Gram matrix of the unfolding + LAPACK) or 'iterative' (subspace iteration
+    on the nonzeros, `aoadmm_resident_nvecs`; sparse blocks only).  None: 'iterative' for a sparse block whose mode
+    has more than NVECS_ITERATIVE_ROWS rows, 'gram' otherwise."""
+    if method is None:
+        return 'iterative' if sparse and rows > NVECS_ITERATIVE_ROWS else 'gram'
+    if method not in ('gram', 'iterative'):
+        raise ValueError("init_options.nvecs_method must be 'gram' or 'iterative', got %r" % (method,))
+    if method == 'iterative' and not sparse:
+        raise ValueError("nvecs_method 'iterative' handles sparse blocks only (dense blocks take 'gram')")
+    return method
+
+
+def _iterative_nvecs(eng, Z, p, pos, r, state):
+    """The r leading left singular vectors of tensor mode `pos` of the sparse block p by `Engine.resident_nvecs`.
+    The init runs before build_model, so the block goes up as a scratch one-block model of its own modes with rank r:
+    once per block (`state['p']` remembers which block the engine holds), whatever the number of modes asked for."""
+    import warnings
+    md = [m - 1 for m in Z['modes'][p]]
+    if state.get('p') != p:
+        n = len(md)
+        Zs = dict(loss_function=['Frobenius'], model=[Z['model'][p]], modes=[list(range(1, n + 1))],
+                  size=[Z['size'][m] for m in md], weights=[1.0], object=[Z['object'][p]],
+                  coupling=dict(lin_coupled_modes=[0] * n, coupling_type=[], coupl_trafo_matrices=[None] * n),
+                  constrained_modes=[0] * n, constraints=[None] * n, _ranks=[int(r)] * n)
+        state['p'] = None
+        build_model(eng, Zs)
+        eng._resident_model = None          # a scratch model: not the caller's Z
+        state['p'] = p
+    U, _, info = eng.resident_nvecs(0, pos, int(Z['size'][md[pos]]), int(r))
+    if not info['converged']:
+        warnings.warn('nvecs of mode %d: subspace iteration stopped after %d iterations with residual %.3e'
+                      % (md[pos] + 1, info['iterations'], info['residual']), RuntimeWarning, stacklevel=3)
+    return U
+
+
+def cmtf_nvecs(Z, n, r, engine=None, method=None, _state=None):
     """functions/cmtf_nvecs.m:1-58 for a CP block: first r left singular vectors of the mode-n unfolding (0-based n)
-    of the data set that owns mode n.  The I_n x I_n Gram matrix of the unfolding comes from the device
-    (`aoadmm_op_unfold_gram`), or for a sparse block from scipy.sparse on the host (no densified tensor); the r
-    leading eigenvectors from LAPACK on the host."""
+    of the data set that owns mode n.  method 'gram': the I_n x I_n Gram matrix of the unfolding comes from the device
+    (`aoadmm_op_unfold_gram`), or for a sparse block from scipy.sparse on the host (no densified tensor), the r
+    leading eigenvectors from LAPACK on the host.  method 'iterative' (sparse blocks): subspace iteration on the
+    nonzeros on the device, no Gram matrix (`aoadmm_resident_nvecs`).  None: see `_nvecs_method`."""
     which_p = _which_p(Z)
     p = which_p[n]
     md = [m - 1 for m in Z['modes'][p]]
     coo = coo_of(Z['object'][p])
+    how = _nvecs_method(method, coo is not None, int(Z['size'][n]))
+    if how == 'iterative':
+        # `_state` (init_coupled_AOADMM_CMTF): while block p is on the device, every mode it owns that takes this path
+        # is computed, so a block coupled with others still goes up once however the modes interleave
+        st = {} if _state is None else _state
+        cache = st.setdefault('U', {})
+        if (n, r) not in cache:
+            eng = engine or default_engine()
+            for m in md:
+                if m == n or (_state is not None and which_p[m] == p and (m, r) not in cache
+                              and _nvecs_method(method, True, int(Z['size'][m])) == 'iterative'):
+                    cache[(m, r)] = _iterative_nvecs(eng, Z, p, md.index(m), r, st)
+        return cache[(n, r)]
     if coo is not None:             # sparse block: sptenmat(X, n) * sptenmat(X, n)' on the host (cmtf_nvecs.m:41-42)
         return _leading_eigvecs(_sparse_unfold_gram(*coo, md.index(n)), r)
     eng = engine or default_engine()
@@ -130,6 +183,8 @@ def init_coupled_AOADMM_CMTF(Z, init_options, Delta=None, rng=None, engine=None)
         rng = np.random.default_rng()
     nvecs = bool(init_options.get('nvecs', 0))
     eng_nv = (engine or default_engine()) if nvecs else None
+    nv_method = init_options.get('nvecs_method')     # None: automatic (see _nvecs_method)
+    nv_state = {}                                    # which block the engine holds as a scratch model ('iterative')
     sz = Z['size']
     lambdas = init_options['lambdas_init']
     distr = init_options['distr']
@@ -153,9 +208,13 @@ def init_coupled_AOADMM_CMTF(Z, init_options, Delta=None, rng=None, engine=None)
         for n in md:
             if nvecs:                                                           # :50-73
                 if Z['model'][p] == 'CP':
-                    A['fac'][n] = cmtf_nvecs(Z, n, R, eng_nv)
+                    A['fac'][n] = cmtf_nvecs(Z, n, R, eng_nv, nv_method, nv_state)
                 elif md.index(n) == 0:
-                    if _par2_sparse(Z['object'][p], p):     # sum_k X_k X_k' on the host, no densified slab
+                    sparse_slabs = _par2_sparse(Z['object'][p], p)
+                    if _nvecs_method(nv_method, sparse_slabs, int(sz[n])) == 'iterative':   # Xcat Xcat' on the device
+                        A['fac'][n] = _iterative_nvecs(eng_nv, Z, p, 0, R, nv_state)
+                        continue
+                    if sparse_slabs:                        # sum_k X_k X_k' on the host, no densified slab
                         Y = sum(_sparse_slab_gram(Xk, 0) for Xk in Z['object'][p])
                     else:
                         Y = _resident_gram(eng_nv, Z, p, 0, int(sz[n]))

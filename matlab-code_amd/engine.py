@@ -186,6 +186,20 @@ class Engine:
         capi.check(self.lib.aoadmm_resident_unfold_gram(self.h, int(p), int(tensor_mode), int(slab), capi.dptr(out)))
         return out
 
+    def resident_nvecs(self, p, tensor_mode, n, r, oversample=0, max_iters=0, tol=0.0, seed=0):
+        """The r leading eigenvectors of X_(n) X_(n)' from the SPARSE data of tensor p already on the device
+        (`aoadmm_resident_nvecs`): block subspace iteration on the nonzeros, no n x n Gram matrix.  n = I_n; zeros =
+        the library's defaults (oversample 8, max_iters 500, tol 1e-10).  Returns (U n x r, eigvals r, info) with
+        info = dict(iterations, converged, block, residual, fibers); not converged is reported, not raised."""
+        U = np.zeros((int(n), int(r)), order='F')
+        ev = np.zeros(int(r))
+        opt = capi.NvecsOptions(int(oversample), int(max_iters), float(tol), int(seed))
+        info = capi.NvecsInfo()
+        capi.check(self.lib.aoadmm_resident_nvecs(self.h, int(p), int(tensor_mode), int(r), C.byref(opt), capi.dptr(U),
+                                                  max(int(n), 1), capi.dptr(ev), C.byref(info)))
+        return U, ev, dict(iterations=info.iterations, converged=info.converged, block=info.block,
+                           residual=info.residual, fibers=info.fibers)
+
     def gram(self, F):
         F = capi.as_f(F)
         out = np.zeros((F.shape[1], F.shape[1]), order='F')

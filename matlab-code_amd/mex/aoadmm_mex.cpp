@@ -107,11 +107,9 @@ bool is_sparse_object(const mxArray* obj) {
 // Z.object{p} as an sptensor (subs 1-based doubles nnz x N, vals nnz x 1, size) or a MATLAB sparse double matrix
 // (compressed columns: ir / jc / values) -> 0-based int64 COO, column-major nnz x N, through aoadmm_tensor_upload_coo.
 // The sizes must be those of Z.size for the block's modes (`md`).
-void upload_sparse(int p, const mxArray* obj, const mxArray* sz, const std::vector<int>& md) {
-  const int N = (int)md.size();
-  std::vector<int64_t> subs;
-  std::vector<double> vals;
-  std::vector<double> shape;
+// the conversion alone; N < 0: whatever order the sptensor has
+void read_sparse(int p, const mxArray* obj, int N, std::vector<int64_t>& subs, std::vector<double>& vals,
+                 std::vector<double>& shape) {
   if (mxIsClass(obj, "sptensor")) {
     mxArray* s = mxGetProperty(obj, 0, "subs");
     mxArray* v = mxGetProperty(obj, 0, "vals");
@@ -121,6 +119,7 @@ void upload_sparse(int p, const mxArray* obj, const mxArray* sz, const std::vect
     if (!mxIsDouble(v) || mxIsComplex(v))
       mexErrMsgIdAndTxt("cmtf:hip:unsupported", "Z.object{%d}: sptensor values are not real doubles: it stays on the MATLAB path", p + 1);
     shape.assign(mxGetDoubles(z), mxGetDoubles(z) + mxGetNumberOfElements(z));
+    if (N < 0) N = (int)shape.size();
     const size_t nnz = mxGetNumberOfElements(v);
     if (nnz > 0 && (mxGetM(s) != nnz || (int)mxGetN(s) != N))
       mexErrMsgIdAndTxt("cmtf:hip:invalid", "Z.object{%d}: sptensor subs is not nnz x %d", p + 1, N);
@@ -142,6 +141,14 @@ void upload_sparse(int p, const mxArray* obj, const mxArray* sz, const std::vect
       for (mwIndex k = jc[j]; k < jc[j + 1]; ++k) { subs[k] = (int64_t)ir[k]; subs[nnz + k] = (int64_t)j; }
     vals.assign(mxGetDoubles(obj), mxGetDoubles(obj) + nnz);
   }
+}
+
+void upload_sparse(int p, const mxArray* obj, const mxArray* sz, const std::vector<int>& md) {
+  const int N = (int)md.size();
+  std::vector<int64_t> subs;
+  std::vector<double> vals;
+  std::vector<double> shape;
+  read_sparse(p, obj, N, subs, vals, shape);
   bool same = (int)shape.size() == N;
   for (int i = 0; same && i < N; ++i) same = shape[i] == mxGetScalar(mxGetCell(sz, md[i]));
   if (!same) mexErrMsgIdAndTxt("cmtf:hip:invalid", "Z.object{%d}: size does not match Z.size of its modes", p + 1);
@@ -230,6 +237,42 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (nd < 2 || nd > 3 || n < 0 || n >= nd) mexErrMsgIdAndTxt("cmtf:hip:unsupported", "unfold_gram handles matrices and 3-way tensors");
     plhs[0] = mxCreateDoubleMatrix((mwSize)dims[n], (mwSize)dims[n], mxREAL);
     check(aoadmm_op_unfold_gram(g_ctx, mxGetDoubles(X), nd, dims, n, AOADMM_PREC_F64, mxGetDoubles(plhs[0])));
+    return;
+  }
+  // U = aoadmm_mex('nvecs', X, n, r): the r leading left singular vectors of the mode-n unfolding (n 1-based) of an
+  // sptensor or a sparse double matrix by subspace iteration on the device (aoadmm_resident_nvecs): no I_n x I_n
+  // Gram matrix.  X goes up as a scratch one-block model, which replaces whatever model the context held.
+  if (nrhs == 4 && mxIsChar(prhs[0])) {
+    if (str(prhs[0]) != "nvecs") mexErrMsgIdAndTxt("cmtf:hip:usage", "unknown operation '%s'", str(prhs[0]).c_str());
+    if (!is_sparse_object(prhs[1])) mexErrMsgIdAndTxt("cmtf:hip:unsupported", "nvecs handles sptensors and sparse double matrices (dense data: 'unfold_gram')");
+    if (!g_ctx) {
+      check(aoadmm_create(&g_ctx, 0));
+      g_devices.assign(1, 0);
+      if (!g_at_exit) { mexAtExit(at_exit); g_at_exit = true; }
+    }
+    std::vector<int64_t> subs;
+    std::vector<double> vals, shape;
+    read_sparse(0, prhs[1], -1, subs, vals, shape);
+    const int N = (int)shape.size();
+    const int n = (int)mxGetScalar(prhs[2]) - 1, r = (int)mxGetScalar(prhs[3]);
+    if (N < 2 || N > 8 || n < 0 || n >= N) mexErrMsgIdAndTxt("cmtf:hip:invalid", "nvecs: mode %d of an order-%d object", n + 1, N);
+    check(aoadmm_model_begin(g_ctx, N, 1, 0));
+    std::vector<int> md(N);
+    for (int m = 0; m < N; ++m) {
+      md[m] = m;
+      check(aoadmm_model_set_mode(g_ctx, m, (int64_t)shape[m], r));
+    }
+    check(aoadmm_model_add_cp(g_ctx, 0, N, md.data(), 1.0));
+    for (int m = 0; m < N; ++m) check(aoadmm_model_set_coupling(g_ctx, m, -1, nullptr, 0, 0, nullptr, 0, 0));
+    check(aoadmm_model_end(g_ctx));
+    check(aoadmm_tensor_upload_coo(g_ctx, 0, (int64_t)vals.size(), subs.data(), vals.data()));
+    const int64_t In = (int64_t)shape[n];
+    plhs[0] = mxCreateDoubleMatrix((mwSize)In, (mwSize)r, mxREAL);
+    aoadmm_nvecs_info info;
+    check(aoadmm_resident_nvecs(g_ctx, 0, n, r, nullptr, mxGetDoubles(plhs[0]), In, nullptr, &info));
+    if (!info.converged)
+      mexWarnMsgIdAndTxt("cmtf:hip:nvecs", "nvecs of mode %d: subspace iteration stopped after %d iterations with residual %.3e",
+                         n + 1, info.iterations, info.residual);
     return;
   }
   if (nrhs != 3 || nlhs > 2) mexErrMsgIdAndTxt("cmtf:hip:usage", "usage: [Fac,out] = aoadmm_mex(Z, G, options)");

@@ -48,6 +48,7 @@ mxArray* mxCreateStructMatrix(mwSize, mwSize, int, const char**);
 mxArray* mxCreateString(const char*);
 mxArray* mxDuplicateArray(const mxArray*);
 void mexErrMsgIdAndTxt(const char*, const char*, ...);
+void mexWarnMsgIdAndTxt(const char*, const char*, ...);
 int mexAtExit(void (*)(void));
 int mexPrintf(const char*, ...);
 int mexEvalString(const char*);

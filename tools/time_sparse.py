@@ -2,6 +2,7 @@
 data on the same GPU.
 
     python3 tools/time_sparse.py [--dims 1000000,100000,10000] [--nnz 100000000] [--R 20] [--skew] [--reps 5]
+    python3 tools/time_sparse.py --nvecs [--nvecs-iters 20] [--host-gram] ...
 
 Prints one JSON line per (layout, mode) and a summary line.  Layouts: 'colmajor' gathers from the column-major factors
 (what aoadmm_resident_mttkrp sees before any solve), 'rowmajor' after one outer iteration, when the Gram kernel has left
@@ -9,6 +10,12 @@ the row-major copies the solver's own MTTKRPs gather from.  Bytes are algorithmi
 gathered + output written, aoadmm_kernel_stats(3)); the HBM peak taken for the share is 8 TB/s.
 --skew draws every subscript as floor(size * u^4), u uniform: a power law, row 0 of the first mode then owns ~3 %
 of all nonzeros.  Subscripts go up unsorted and uncoalesced: the device sorts and sums duplicates.
+--nvecs times the nvecs start of every mode instead (aoadmm_resident_nvecs, r = R, block b = R + 8): the model takes
+rank b, so that the block's own MTTKRP of the mode at rank b stands next to it.  Per mode: F, the mean time of one
+pass over the nonzeros (HIP events, aoadmm_kernel_stats(3); an iteration runs two), the wall time of an iteration with
+its dense part (difference of a run of --nvecs-iters iterations and a run of one) and of the list build (what is left
+of the one-iteration run), the iterations run and whether the tolerance was reached within --nvecs-iters.
+--host-gram adds the wall time of the host path (sptensor.unfold_gram + eigh) for modes of at most 16384 rows.
 """
 from __future__ import annotations
 
@@ -39,6 +46,9 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--no-torch', action='store_true')
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--nvecs', action='store_true')
+    ap.add_argument('--nvecs-iters', type=int, default=20)
+    ap.add_argument('--host-gram', action='store_true')
     a = ap.parse_args()
     if not a.no_torch:
         # torch (and the HIP runtime it ships) first, as bench.py does: loaded after the library, the process aborted in
@@ -47,6 +57,8 @@ def main():
         torch.cuda.init()
     dims = [int(float(v)) for v in a.dims.split(',')]
     N, R, nnz = len(dims), a.R, int(a.nnz)
+    if a.nvecs:
+        a.no_torch = True
     rng = np.random.default_rng(a.seed)
     t0 = time.time()
     subs = np.empty((nnz, N), dtype=np.int64, order='F')
@@ -59,9 +71,60 @@ def main():
     t_gen = time.time() - t0
     eng = pkg.Engine(0)
     try:
-        run(a, eng, dims, N, R, nnz, subs, vals, t_gen)
+        (run_nvecs if a.nvecs else run)(a, eng, dims, N, R, nnz, subs, vals, t_gen)
     finally:
         eng.close()
+
+
+def run_nvecs(a, eng, dims, N, R, nnz, subs, vals, t_gen):
+    rng = np.random.default_rng(a.seed + 1)
+    lib, h = eng.lib, eng.h
+    b = min(64, R + 8)
+    capi.check(lib.aoadmm_model_begin(h, N, 1, 0))
+    for m, s in enumerate(dims):
+        capi.check(lib.aoadmm_model_set_mode(h, m, s, b))
+    capi.check(lib.aoadmm_model_add_cp(h, 0, N, (C.c_int * N)(*range(N)), 1.0))
+    for m in range(N):
+        capi.check(lib.aoadmm_model_set_coupling(h, m, -1, None, 0, 0, None, 0, 0))
+    capi.check(lib.aoadmm_model_end(h))
+    t0 = time.time()
+    eng.upload_coo(0, subs, vals)
+    eng.synchronize()
+    print(json.dumps({'what': 'setup', 'dims': dims, 'nnz_given': nnz, 'r': R, 'b': b, 'skew': a.skew,
+                      'gen_s': round(t_gen, 2), 'upload_s': round(time.time() - t0, 2)}), flush=True)
+    for m in range(N):
+        Um = np.asfortranarray(rng.random((dims[m], b)))
+        capi.check(lib.aoadmm_state_set(h, capi.F_FAC, m, 0, capi.dptr(Um), dims[m], b))
+    for n in range(N):
+        rmax = min(R, dims[n])
+        ms = C.c_float(0)
+        capi.check(lib.aoadmm_resident_mttkrp(h, 0, n, None, C.byref(ms)))              # warm-up
+        ev = []
+        for _ in range(a.reps):
+            capi.check(lib.aoadmm_resident_mttkrp(h, 0, n, None, C.byref(ms)))
+            ev.append(ms.value)
+        eng.resident_nvecs(0, n, dims[n], rmax, max_iters=1)                             # warm-up
+        t0 = time.time()
+        _, _, i1 = eng.resident_nvecs(0, n, dims[n], rmax, max_iters=1)
+        w1 = (time.time() - t0) * 1e3
+        eng.kernel_stats(3, reset=True)
+        t0 = time.time()
+        _, _, ik = eng.resident_nvecs(0, n, dims[n], rmax, max_iters=a.nvecs_iters)
+        wk = (time.time() - t0) * 1e3
+        kms, launches, by, _ = eng.kernel_stats(3, reset=True)
+        it_ms = (wk - w1) / (ik['iterations'] - 1) if ik['iterations'] > 1 else float('nan')
+        r = {'what': 'nvecs', 'mode': n + 1, 'rows': dims[n], 'r': rmax, 'b': ik['block'], 'F': ik['fibers'],
+             'pass_ms': round(kms / launches, 4), 'pass_TBps': round(by / launches / (kms / launches) / 1e9, 3),
+             'iter_ms_wall': round(it_ms, 3), 'build_ms_wall': round(w1 - it_ms, 3) if it_ms == it_ms else None,
+             'iterations': ik['iterations'], 'converged': ik['converged'], 'residual': ik['residual'],
+             'mttkrp_rank_b_ms': round(float(np.median(ev)), 4),
+             'passes_over_two_mttkrps': round(2 * kms / launches / (2 * float(np.median(ev))), 3)}
+        if a.host_gram and dims[n] <= 16384:
+            sp = importlib.import_module('matlab-code_amd.sptensor')
+            t0 = time.time()
+            w, V = np.linalg.eigh(sp.unfold_gram(subs, vals, dims, n))
+            r['host_gram_ms'] = round((time.time() - t0) * 1e3, 1)
+        print(json.dumps(r), flush=True)
 
 
 def run(a, eng, dims, N, R, nnz, subs, vals, t_gen):
