@@ -91,8 +91,28 @@ enum {
 /* storage / arithmetic of the big tensor passes */
 enum {
   AOADMM_PREC_F64 = 0, /* tensor stored fp64, v_mfma_f64_16x16x4_f64 (parity mode)        */
-  AOADMM_PREC_F32 = 1  /* tensor stored fp32, v_mfma_f32_16x16x4_f32 (+ packed-fp32 VALU for 1-4 leftover columns),
+  AOADMM_PREC_F32 = 1, /* tensor stored fp32, v_mfma_f32_16x16x4_f32 (+ packed-fp32 VALU for 1-4 leftover columns),
                           fp64 everywhere else */
+  AOADMM_PREC_F16 = 2  /* dense 3-way CP blocks only: entries stored fp16 with one power-of-two scale per block,
+                          v_mfma_f32_16x16x32_f16 with fp32 accumulation; everything else as AOADMM_PREC_F32.
+                          The rule, which a host can reproduce bit for bit:
+                            1. round the entries to fp32 (as AOADMM_PREC_F32 does);
+                            2. a = max |x| over those fp32 values = m * 2^E with m in [0.5, 1)  (frexp);
+                            3. s = 2^(15 - E), the exponent clamped to [-126, 127] so that s is a normal fp32 number:
+                               a * s lies in [2^14, 2^15);  an all-zero block has s = 1;
+                            4. a non-finite entry makes the upload fail with AOADMM_ERR_INVALID;
+                            5. stored: q = fp16(x_fp32 * s), round to nearest even, subnormals kept;
+                            6. the block's data IS q / s: aoadmm_tensor_normsq is the fp64 sum of (q / s)^2 and the
+                               model is fitted to q / s.
+                          Resident: three fp16 pass copies (6 bytes per entry; 10 at the peak of the upload); the
+                          natural-layout array is released at once, so aoadmm_tensor_mask_upload on such a block is
+                          AOADMM_ERR_INVALID and aoadmm_resident_unfold_gram AOADMM_ERR_UNSUPPORTED, and aoadmm_solve
+                          with options.no_permuted_copy = 1 is AOADMM_ERR_INVALID (the copies are the data).
+                          AOADMM_ERR_UNSUPPORTED, the block left as it was: a block that is not 3-way,
+                          aoadmm_tensor_upload_rows, aoadmm_op_mttkrp / aoadmm_op_unfold_gram, and any engine of a
+                          communicator or of an aoadmm_create_multi context.  A copy that cannot be built fails the
+                          upload (AOADMM_ERR_NOMEM: no room in device memory; AOADMM_ERR_UNSUPPORTED: a mode too
+                          long for the copy kernels) and leaves the block without data. */
 };
 
 typedef struct aoadmm_ctx aoadmm_ctx;
@@ -246,6 +266,11 @@ int aoadmm_tensor_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t*
 int aoadmm_par2_slab_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* vals);
 /* Znorm_const{p} (cmtf_AOADMM.m:130-156) */
 int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out);
+/* How tensor p is stored on the device (each output may be NULL): *precision = the AOADMM_PREC_* its passes stream
+ * (AOADMM_PREC_F64 for sparse and PARAFAC2 data), *scale = the power-of-two scale s of an AOADMM_PREC_F16 block (1.0
+ * otherwise), *resident_bytes = what a dense CP block holds now: natural-layout array, pass copies, transposed copy and
+ * mask (0 for sparse and PARAFAC2 data).  No device work. */
+int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes);
 
 /* ---- state (the struct G) ---------------------------------------------- */
 /* slab = k for cell-valued fields (PARAFAC2 B mode, P, mu_DeltaB), else 0.  slab = AOADMM_ALL_SLABS moves

@@ -15,7 +15,30 @@ LIB_PATH = os.environ.get('AOADMM_LIB_PATH') or os.path.join(_HERE, 'libaoadmm_h
 
 # status codes (include/aoadmm_hip.h)
 OK, ERR_INVALID, ERR_HIP, ERR_NOT_PD, ERR_RCCL, ERR_UNSUPPORTED, ERR_NOMEM = range(7)
-PREC_F64, PREC_F32 = 0, 1
+PREC_F64, PREC_F32, PREC_F16 = 0, 1, 2
+PRECISIONS = {'f64': PREC_F64, 'f32': PREC_F32, 'f16': PREC_F16}
+
+
+def precision_id(precision):
+    """'f64' | 'f32' | 'f16' -> AOADMM_PREC_*; anything else is a ValueError."""
+    try:
+        return PRECISIONS[precision]
+    except (KeyError, TypeError):
+        raise ValueError("precision must be one of 'f64', 'f32', 'f16', got %r" % (precision,)) from None
+
+
+def quantize_f16(X):
+    """The AOADMM_PREC_F16 storage rule of include/aoadmm_hip.h on the host: (q, s) with q the float16 array the device
+    stores and s its power-of-two scale; the block's data is q / s.  A non-finite entry is a ValueError."""
+    x = np.asarray(X, dtype=np.float64).astype(np.float32)
+    if not np.all(np.isfinite(x)):
+        raise ValueError('quantize_f16: the tensor holds an entry that is not finite')
+    a = float(np.abs(x).max()) if x.size else 0.0
+    s = 1.0
+    if a > 0.0:
+        _, E = np.frexp(a)
+        s = float(np.ldexp(1.0, min(127, max(-126, 15 - int(E)))))
+    return (x * np.float32(s)).astype(np.float16), s
 (F_FAC, F_CONSTRAINT_FAC, F_CONSTRAINT_DUAL, F_COUPLING_FAC, F_COUPLING_DUAL, F_DELTAB, F_P,
  F_MU_DELTAB) = range(8)
 ALL_SLABS = -1            # AOADMM_ALL_SLABS
@@ -30,7 +53,7 @@ SYMBOLS = [
     'aoadmm_model_begin', 'aoadmm_model_set_mode', 'aoadmm_model_set_mode_slabs', 'aoadmm_model_add_cp',
     'aoadmm_model_add_par2', 'aoadmm_model_set_constraint', 'aoadmm_model_set_coupling',
     'aoadmm_model_set_coupling_type', 'aoadmm_model_set_ridge', 'aoadmm_model_end', 'aoadmm_tensor_upload',
-    'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq',
+    'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq', 'aoadmm_tensor_storage_info',
     'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_resident_par2_rhs', 'aoadmm_kernel_stats',
     'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_resident_nvecs', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
     'aoadmm_op_admm_mode', 'aoadmm_op_par2_b_loop',
@@ -133,6 +156,7 @@ def load_library():
     lib.aoadmm_par2_slab_mask_upload.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
     lib.aoadmm_tensor_synth.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.c_double, C.c_int]
     lib.aoadmm_tensor_normsq.argtypes = [vp, C.c_int, dp]
+    lib.aoadmm_tensor_storage_info.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp, C.POINTER(i64)]
     lib.aoadmm_state_set.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, i64, i64]
     lib.aoadmm_state_get.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, i64, i64]
     lib.aoadmm_solve.argtypes = [vp, C.POINTER(Options), C.POINTER(Result)]

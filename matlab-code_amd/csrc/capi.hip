@@ -425,6 +425,11 @@ int aoadmm_par2_slab_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64
     on_engines(ctx, [&](Engine& e, int) { e.par2_slab_upload_coo(p, nnz, subs, vals); });   // replicated on every engine
   });
 }
+int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes) {
+  CTX_OR_FAIL(ctx);
+  // no collective and no device work: rank 0's engine answers for a multi-device context (every rank holds the same form)
+  return guarded([&] { ctx->eng->tensor_storage_info(p, precision, scale, resident_bytes); });
+}
 int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out) {
   CTX_OR_FAIL(ctx);
   return guarded([&] {
@@ -501,6 +506,8 @@ int aoadmm_op_mttkrp(aoadmm_ctx* ctx, const double* X, int ndims, const int64_t*
   return guarded([&] {
     AO_REQUIRE(X && dims && U && out, "null pointer");
     AO_REQUIRE(ndims >= 2 && ndims <= 8 && n >= 0 && n < ndims, "bad order/mode");
+    if (precision == AOADMM_PREC_F16)
+      throw Error(AOADMM_ERR_UNSUPPORTED, "aoadmm_op_mttkrp runs on a natural-layout array: AOADMM_PREC_F16 exists for resident blocks only (aoadmm_tensor_upload)");
     Engine& e = *ctx->eng;
     AO_HIP(hipSetDevice(e.device()));
     CpBlock blk;
@@ -526,6 +533,8 @@ int aoadmm_op_unfold_gram(aoadmm_ctx* ctx, const double* X, int ndims, const int
   return guarded([&] {
     AO_REQUIRE(X && dims && out, "null pointer");
     AO_REQUIRE((ndims == 2 || ndims == 3) && n >= 0 && n < ndims, "unfold_gram handles matrices and 3-way tensors");
+    if (precision == AOADMM_PREC_F16)
+      throw Error(AOADMM_ERR_UNSUPPORTED, "aoadmm_op_unfold_gram runs on a natural-layout array: AOADMM_PREC_F16 exists for resident blocks only (aoadmm_tensor_upload)");
     Engine& e = *ctx->eng;
     AO_HIP(hipSetDevice(e.device()));
     CpBlock blk;

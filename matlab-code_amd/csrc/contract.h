@@ -21,6 +21,9 @@ struct DenseTensor {
   size_t elem_size() const { return prec == AOADMM_PREC_F32 ? 4 : 8; }
 };
 
+// bytes of one stored tensor entry in precision `prec` (AOADMM_PREC_*)
+inline double prec_bytes(int prec) { return prec == AOADMM_PREC_F16 ? 2.0 : (prec == AOADMM_PREC_F32 ? 4.0 : 8.0); }
+
 // Description of one batched "contiguous-M" contraction
 //   T[b][m][r] = sum_{c<C} X[b*batch_stride + m + ld*c] * F[c][r]
 // (m contiguous in memory).  T is row-major [nchunk][nbatch*M][R] in the tensor's own precision: an
@@ -33,22 +36,26 @@ struct ContractPlan {
   int nchunk;          // split of the reduction (bounds f32 accumulation length)
   bool lead = false;   // true: the contracted mode is the contiguous one (X[c + ld*m]), LDS-transposed kernel
   bool on_copy = false;   // the pass runs on the contracted mode's row-blocked resident copy (cpblock.h CpBlock::copy)
+  double xscale = 1.0;    // AOADMM_PREC_F16 operands: the block's power-of-two scale s (the copy holds fp16(x * s))
   int64_t trows() const { return nbatch * M; }
   size_t t_bytes() const { return (size_t)nchunk * trows() * R * (tprec == AOADMM_PREC_F32 ? 4 : 8); }
   size_t frag_bytes(int prec) const;
   double algorithmic_bytes(int prec) const {   // tensor read once + T written once
-    return (double)nbatch * M * C * (prec == AOADMM_PREC_F32 ? 4.0 : 8.0) + (double)t_bytes();
+    return (double)nbatch * M * C * prec_bytes(prec) + (double)t_bytes();
   }
   double flops() const { return 2.0 * nbatch * M * C * R; }
 };
 
+// prec = AOADMM_PREC_F16: a pass on a half pass copy (misc.h half_layout_copy): M = ld = kRowBlockElems, one batch per
+// row block, T in fp32 (tprec = AOADMM_PREC_F32) in the layout of the fp32 pass on a copy.
 ContractPlan make_plan(int64_t nbatch, int64_t batch_stride, int64_t M, int64_t ld, int64_t C, int R,
                        int prec);
 
 // T(m,r) = sum_c X[c + ld*m] * F(c,r): contraction of the leading (contiguous) mode, fp32 tensors
 ContractPlan make_lead_plan(int64_t M, int64_t ld, int64_t C, int R);
 
-// F: device fp64, column-major (C x R) with leading dimension ldF.
+// F: device fp64, column-major (C x R) with leading dimension ldF.  `prec` is the precision of the operand X; the plan's
+// tprec equals it except for half operands, whose T is fp32.
 void launch_contract(const void* X, int prec, const ContractPlan& pl, const double* F, int64_t ldF,
                      void* frag_ws, void* T, hipStream_t s, hipEvent_t ev0 = nullptr,
                      hipEvent_t ev1 = nullptr);   // events bracket the contraction kernel only

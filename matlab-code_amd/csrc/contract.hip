@@ -750,15 +750,194 @@ __global__ __launch_bounds__(256, NT <= 2 ? 2 : 1) void contract_f64(KArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// fp16 contraction (AOADMM_PREC_F16 storage): v_mfma_f32_16x16x32_f16 on a half pass copy
+// ---------------------------------------------------------------------------
+// The copy (misc.hip half_layout_copy) holds q = fp16(x * s) in 512-row blocks whose columns are grouped by 32: element
+// (m, c) of a block sits at (c / 32) * 512 * 32 + (m % 512) * 32 + c % 32 halves, columns padded with zeros to a multiple
+// of 32.  A row of a group is 64 bytes, so lane l's 16-byte load at row (l & 15), byte (l >> 4) * 16 is exactly the A
+// operand of the MFMA: A[row l&15][k = 8(l>>4) + j], j = 0..7; a 16-row tile of a group is 1 KB contiguous, a wave's 128
+// rows 8 KB.  B: lane l holds F[k = 8(l>>4) + j][col l&15].  C/D: col = lane&15, row = 4(lane>>4) + reg.
+//   The factor keeps ~22 bits: column r is scaled by a power of two t_r (its largest entry lands in [2^14, 2^15)) and
+//   split into hi = fp16(F t_r) and lo = fp16(F t_r - hi); both fragments are multiplied into the SAME fp32 accumulator.
+//   t_r is found on the device (frag16_scales_k), nothing is read back.  The epilogue multiplies by 1/t_r and 1/s (powers
+//   of two: exact) and leaves T in fp32 in the layout of contract16_f32 on a copy, so every reduction runs unchanged.
+//   NT = ceil(R / 16) column tiles, no vector-pipe leftovers: a wave issues 16 NT MFMAs of 16 cycles per 8 KB it loads.
+//   Register ring of three 32-column stages, the next stages' loads issued between the MFMA groups (as contract16_f32).
+// frag workspace: [0, 512) double t_r[64]; [512, 768) float 1/t_r[64]; from byte 1024 on
+//   frag[g][nt][f][lane] f16x8, element j = (f ? lo : hi) of F[32g + 8(lane>>4) + j][16nt + (lane&15)] * t_r
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+static constexpr int kGroup16 = 32;                 // reduction columns per MFMA and per pipeline stage
+static constexpr int64_t kGroupHalves = kGroup16 * 512;   // halves of one column group of a 512-row block
+static constexpr int kFragHeader16 = 1024;          // bytes in front of the fragments
+static constexpr int kScaleExp16 = 15;              // largest scaled magnitude in [2^14, 2^15)
+
+__global__ __launch_bounds__(256) void frag16_scales_k(const double* __restrict__ F, int64_t ldF, int64_t C, double* __restrict__ tsc,
+                                                      float* __restrict__ tinv) {
+  __shared__ double sh[256];
+  const int r = blockIdx.x;
+  double mx = 0.0;
+  for (int64_t c = threadIdx.x; c < C; c += 256) mx = fmax(mx, fabs(F[c + ldF * r]));
+  sh[threadIdx.x] = mx;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + st]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    mx = sh[0];
+    int e = 0;
+    if (mx > 0.0 && mx <= 1.7976931348623157e308) {   // a zero (or non-finite) column keeps t_r = 1
+      int ex;
+      (void)frexp(mx, &ex);
+      e = kScaleExp16 - ex;
+      e = e > 110 ? 110 : (e < -110 ? -110 : e);       // 1 / t_r stays a normal fp32 number
+    }
+    tsc[r] = ldexp(1.0, e);
+    tinv[r] = (float)ldexp(1.0, -e);
+  }
+}
+
+__global__ void pack_frag16_f16(const double* __restrict__ F, int64_t ldF, int64_t C, int R, int NT, int64_t Cg,
+                                const double* __restrict__ tsc, f16x8* __restrict__ frag) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= Cg * NT * 128) return;
+  const int lane = idx & 63, f = (idx >> 6) & 1;
+  const int nt = (int)((idx >> 7) % NT);
+  const int64_t g = (idx >> 7) / NT;
+  const int r = 16 * nt + (lane & 15);
+  const double t = r < R ? tsc[r] : 1.0;
+  f16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int64_t c = kGroup16 * g + 8 * (lane >> 4) + j;
+    const double v = (c < C && r < R) ? F[c + ldF * r] * t : 0.0;
+    const _Float16 hi = (_Float16)v;
+    o[j] = f ? (_Float16)(v - (double)hi) : hi;
+  }
+  frag[idx] = o;
+}
+
+struct KArgs16 {
+  const _Float16* X;
+  const void* frag;
+  float* T;            // [nchunk][trows][R]
+  int64_t ntiles, Cg, trows;
+  int groups_per_chunk, R;
+  float inv_s;         // 1 / s of the block
+};
+
+template <int NT>
+__global__ __launch_bounds__(256, NT <= 2 ? 2 : 1) void contract16_f16(KArgs16 a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wt = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wt >= a.ntiles) return;                        // wave-uniform
+  const int chunk = blockIdx.y;
+  const int64_t blk = wt >> 2;                        // four 128-row wave tiles per 512-row block
+  const int m0 = (int)(wt & 3) * kTileRows;
+  const int r16 = lane & 15, q = lane >> 4;
+  const int64_t g0 = (int64_t)chunk * a.groups_per_chunk;
+  int64_t g1 = g0 + a.groups_per_chunk;
+  if (g1 > a.Cg) g1 = a.Cg;
+  const int64_t ng = g1 > g0 ? g1 - g0 : 0;           // every group is whole: the copy pads its columns with zeros
+  const _Float16* xp = a.X + (blk * a.Cg + g0) * kGroupHalves + (m0 + r16) * kGroup16 + 8 * q;
+  const f16x8* fp = reinterpret_cast<const f16x8*>(reinterpret_cast<const char*>(a.frag) + kFragHeader16) + g0 * (NT * 128) + lane;
+
+  f32x4 acc[NT][8];                                   // [nt][16-row tile]
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+    for (int t = 0; t < 8; ++t) acc[nt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  f16x8 x0[8], x1[8], x2[8];
+  f16x8 f0[NT][2], f1[NT][2], f2[NT][2];
+#define AO_LOAD1(XS, GI, TL) XS[TL] = __builtin_nontemporal_load(reinterpret_cast<const f16x8*>(xp + (GI) * kGroupHalves + (TL) * (16 * kGroup16)));
+#define AO_LOADF(FS, GI)                                                                             \
+  {                                                                                                  \
+    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                                              \
+      FS[nt][0] = fp[(GI) * (NT * 128) + nt * 128];                                                  \
+      FS[nt][1] = fp[(GI) * (NT * 128) + nt * 128 + 64];                                             \
+    }                                                                                                \
+  }
+#define AO_LOAD_STAGE(XS, FS, GI)                                                                    \
+  { _Pragma("unroll") for (int tl_ = 0; tl_ < 8; ++tl_) AO_LOAD1(XS, GI, tl_) AO_LOADF(FS, GI) }
+#define AO_FMA_T(XS, FS, TL)                                                                         \
+  {                                                                                                  \
+    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                                              \
+      acc[nt][TL] = __builtin_amdgcn_mfma_f32_16x16x32_f16(XS[TL], FS[nt][0], acc[nt][TL], 0, 0, 0); \
+      acc[nt][TL] = __builtin_amdgcn_mfma_f32_16x16x32_f16(XS[TL], FS[nt][1], acc[nt][TL], 0, 0, 0); \
+    }                                                                                                \
+  }
+#define AO_COMPUTE_STAGE(XS, FS) { _Pragma("unroll") for (int tl_ = 0; tl_ < 8; ++tl_) AO_FMA_T(XS, FS, tl_) }
+  // consume stage (XC, FC) while fetching stage GI into (XL, FL): one load between MFMA groups
+#define AO_MIX_STAGE(XC, FC, XL, FL, GI)                                                             \
+  {                                                                                                  \
+    _Pragma("unroll") for (int tl_ = 0; tl_ < 8; ++tl_) {                                            \
+      AO_FMA_T(XC, FC, tl_) AO_LOAD1(XL, GI, tl_)                                                    \
+      if (tl_ == 7) AO_LOADF(FL, GI)                                                                 \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+    }                                                                                                \
+  }
+  if (ng > 0) AO_LOAD_STAGE(x0, f0, 0)
+  if (ng > 1) AO_LOAD_STAGE(x1, f1, 1)
+  int64_t g = 0;
+  for (; g + 5 <= ng; g += 3) {                      // steady state: every prefetch is in range
+    AO_MIX_STAGE(x0, f0, x2, f2, g + 2)
+    AO_MIX_STAGE(x1, f1, x0, f0, g + 3)
+    AO_MIX_STAGE(x2, f2, x1, f1, g + 4)
+  }
+  for (; g + 3 <= ng; g += 3) {                      // at most one drained round
+    if (g + 2 < ng) AO_LOAD_STAGE(x2, f2, g + 2)
+    AO_COMPUTE_STAGE(x0, f0)
+    if (g + 3 < ng) AO_LOAD_STAGE(x0, f0, g + 3)
+    AO_COMPUTE_STAGE(x1, f1)
+    if (g + 4 < ng) AO_LOAD_STAGE(x1, f1, g + 4)
+    AO_COMPUTE_STAGE(x2, f2)
+  }
+  if (g < ng) AO_COMPUTE_STAGE(x0, f0)
+  if (g + 1 < ng) AO_COMPUTE_STAGE(x1, f1)
+#undef AO_LOAD1
+#undef AO_LOADF
+#undef AO_LOAD_STAGE
+#undef AO_FMA_T
+#undef AO_COMPUTE_STAGE
+#undef AO_MIX_STAGE
+  // epilogue: tile t row j = 4q + reg is row m0 + 16t + j of the block; descaled by 1/t_r and 1/s (exact), assembled in
+  // the wave's LDS slice and stored as whole lines (see contract16_f32)
+  extern __shared__ __attribute__((aligned(16))) float t_lds[];
+  float* tl = t_lds + (threadIdx.x >> 6) * (kTileRows * a.R);
+  const float* tinv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.frag) + 512);
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int r = 16 * nt + r16;
+    if (r < a.R) {
+      const float ti = tinv[r];
+#pragma unroll
+      for (int t = 0; t < 8; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) tl[(16 * t + 4 * q + i) * a.R + r] = acc[nt][t][i] * ti * a.inv_s;
+    }
+  }
+  // a wave's LDS operations complete in order: its own writes are visible to its reads without a barrier
+  {
+    const int n16 = kTileRows * a.R / 4;
+    f32x4* dst = reinterpret_cast<f32x4*>(a.T + ((int64_t)chunk * a.trows + blk * 512 + m0) * a.R);
+    const f32x4* src = reinterpret_cast<const f32x4*>(tl);
+    for (int c = lane; c < n16; c += 64) __builtin_nontemporal_store(src[c], dst + c);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
 static int nt_of(int R, int prec) {
-  const int w = prec == AOADMM_PREC_F32 ? 32 : 16;
+  const int w = prec == AOADMM_PREC_F32 ? 32 : 16;   // (fp16: 16-column tiles)
   return (R + w - 1) / w;
 }
-static int tile_rows(int prec) { return prec == AOADMM_PREC_F32 ? kTileRows : kTileRows64; }
+static int tile_rows(int prec) { return prec == AOADMM_PREC_F64 ? kTileRows64 : kTileRows; }
 
 size_t ContractPlan::frag_bytes(int prec) const {
+  if (prec == AOADMM_PREC_F16)                        // header + hi and lo fragments of every 32-column group
+    return (size_t)kFragHeader16 + (size_t)cdiv(C, kGroup16) * nt_of(R, prec) * 2048;
   const int64_t Cg = cdiv(C, kGroup);
   // f32: the 32-column layout needs nt32*1024 B per group, the 16-column layout nt16*512 + 128 (extras)
   return (size_t)(nt_of(R, prec) * 1024 + 1152) * Cg + 8192;
@@ -767,18 +946,21 @@ size_t ContractPlan::frag_bytes(int prec) const {
 ContractPlan make_plan(int64_t nbatch, int64_t batch_stride, int64_t M, int64_t ld, int64_t C, int R,
                        int prec) {
   ContractPlan p;
-  p.tprec = prec;
+  const bool half = prec == AOADMM_PREC_F16;
+  p.tprec = half ? AOADMM_PREC_F32 : prec;            // a half operand accumulates in fp32 inside the MFMA: T is fp32
   p.nbatch = nbatch; p.batch_stride = batch_stride; p.M = M; p.ld = ld; p.C = C; p.R = R;
-  const int64_t Cg = cdiv(C, kGroup);
+  const int gcols = half ? kGroup16 : kGroup;         // columns per group
+  const int64_t Cg = cdiv(C, gcols);
   const int64_t ntiles = nbatch * cdiv(M, tile_rows(prec));
   int64_t nchunk = 1;
-  // f32 accumulates in fp32 inside the MFMA: keep one accumulation run <= 2048 terms;
+  // f32 (and f16) accumulate in fp32 inside the MFMA: keep one accumulation run <= 2048 terms;
   // partial sums of different chunks are added in fp64 by the reduce kernels.
-  if (prec == AOADMM_PREC_F32) nchunk = cdiv(Cg, 256);
+  if (prec != AOADMM_PREC_F64) nchunk = cdiv(Cg, 2048 / gcols);
   // few row tiles (short mode): split the reduction to fill the 256 CUs
   if (ntiles < 2048) {
     int64_t want = cdiv(2048, ntiles);
-    int64_t maxc = Cg / 16 > 0 ? Cg / 16 : 1;       // keep >= 128 columns per chunk
+    const int64_t gmin = 128 / gcols;
+    int64_t maxc = Cg / gmin > 0 ? Cg / gmin : 1;   // keep >= 128 columns per chunk
     if (want > maxc) want = maxc;
     if (want > nchunk) nchunk = want;
   }
@@ -830,10 +1012,51 @@ static void launch_contract_lead(const void* X, const ContractPlan& pl, const do
   AO_KERNEL_CHECK();
 }
 
+// pass on a half pass copy: scales, fragments, contract16_f16
+static void launch_contract_half(const void* X, const ContractPlan& pl, const double* F, int64_t ldF, void* frag_ws,
+                                 void* T, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+  AO_REQUIRE(pl.on_copy && !pl.lead && pl.M == 512 && pl.ld == 512 && pl.tprec == AOADMM_PREC_F32,
+             "internal: a half operand is streamed from its pass copies only");
+  const int64_t Cg = cdiv(pl.C, kGroup16);
+  AO_REQUIRE(pl.batch_stride == 512 * kGroup16 * Cg && pl.nbatch > 0 && pl.C > 0, "internal: half pass copy and plan disagree");
+  const int NT = nt_of(pl.R, AOADMM_PREC_F16);
+  char* ws = reinterpret_cast<char*>(frag_ws);
+  double* tsc = reinterpret_cast<double*>(ws);
+  float* tinv = reinterpret_cast<float*>(ws + 512);
+  frag16_scales_k<<<(unsigned)pl.R, 256, 0, s>>>(F, ldF, pl.C, tsc, tinv);
+  AO_KERNEL_CHECK();
+  pack_frag16_f16<<<(unsigned)cdiv(Cg * NT * 128, 256), 256, 0, s>>>(F, ldF, pl.C, pl.R, NT, Cg, tsc,
+                                                                    reinterpret_cast<f16x8*>(ws + kFragHeader16));
+  AO_KERNEL_CHECK();
+  KArgs16 a;
+  a.X = reinterpret_cast<const _Float16*>(X); a.frag = frag_ws; a.T = reinterpret_cast<float*>(T);
+  a.ntiles = pl.nbatch * 4; a.Cg = Cg; a.trows = pl.trows();
+  a.groups_per_chunk = (int)cdiv(Cg, pl.nchunk);
+  a.R = pl.R;
+  a.inv_s = (float)(1.0 / pl.xscale);                 // s is a normal fp32 power of two: exact
+  AO_REQUIRE(pl.nbatch < (int64_t)2147483647, "tensor too large for one launch");
+  const dim3 grid((unsigned)pl.nbatch, (unsigned)pl.nchunk);
+  const size_t tsh = (size_t)4 * kTileRows * pl.R * sizeof(float);   // T tile of each of the four waves
+#define AO_GO(K) { if (tsh > 65536) ensure_dynamic_lds(reinterpret_cast<const void*>(K), (int)tsh); if (ev0) AO_HIP(hipEventRecord(ev0, s)); K<<<grid, 256, tsh, s>>>(a); }
+  if (NT == 1) AO_GO(contract16_f16<1>)
+  else if (NT == 2) AO_GO(contract16_f16<2>)
+  else if (NT == 3) AO_GO(contract16_f16<3>)
+  else if (NT == 4) AO_GO(contract16_f16<4>)
+  else throw Error(AOADMM_ERR_UNSUPPORTED, "rank > 64 not supported");
+#undef AO_GO
+  if (ev1) AO_HIP(hipEventRecord(ev1, s));
+  AO_KERNEL_CHECK();
+}
+
 void launch_contract(const void* X, int prec, const ContractPlan& pl, const double* F, int64_t ldF,
                      void* frag_ws, void* T, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-  AO_REQUIRE(pl.tprec == prec, "contraction plan and tensor precision disagree");
   AO_REQUIRE(pl.R >= 1 && pl.R <= kMaxRank, "rank %d outside [1,%d]", pl.R, kMaxRank);
+  if (prec == AOADMM_PREC_F16) {                      // half operand, fp32 T
+    launch_contract_half(X, pl, F, ldF, frag_ws, T, s, ev0, ev1);
+    return;
+  }
+  AO_REQUIRE(prec == AOADMM_PREC_F32 || prec == AOADMM_PREC_F64, "bad precision id %d", prec);
+  AO_REQUIRE(pl.tprec == prec, "contraction plan and tensor precision disagree");
   if (pl.lead) {
     AO_REQUIRE(prec == AOADMM_PREC_F32, "leading-mode contraction exists for fp32 tensors only");
     launch_contract_lead(X, pl, F, ldF, frag_ws, T, s, ev0, ev1);

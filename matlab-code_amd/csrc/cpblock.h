@@ -79,6 +79,10 @@ struct CpBlock {
   // The natural-layout array is only read to build the three pass copies, for ||X||^2, the EM pass and the fallbacks; once
   // all three copies exist (and no mask does) it can go: 4 -> 3 resident copies (maybe_release_natural)
   bool x_released = false;
+  // AOADMM_PREC_F16 storage (3-way blocks, block_make_half): the three pass copies hold q = fp16_rn(x * scale), `scale`
+  // a power of two, and ARE the data (q / scale); the fp32 natural array they were rounded from is gone (x_released)
+  bool half = false;
+  double scale = 1.0;
   // dimension-tree cache: T = X x_c F_c, valid while factor c keeps `cached_version`
   int cached_mode = -1;
   uint64_t cached_version = 0;
@@ -99,7 +103,7 @@ struct CpBlock {
   // New data has arrived, dense or sparse: no copy, cached contraction or release state of the old data holds.  Frees
   // nothing (a pass copy's buffer is reused by the next build; the sparse upload releases what it no longer needs).
   void reset_derived() {
-    has_data = true; x_released = false; cached_mode = -1; xp_ksharded = false;
+    has_data = true; x_released = false; cached_mode = -1; xp_ksharded = false; half = false; scale = 1.0;
     for (PassCopy& c : copy) c.present = c.refused = false;
   }
 };
@@ -109,12 +113,17 @@ inline int64_t pad_of(int prec, int64_t n) { return round_up(n, prec == AOADMM_P
 int next_update_distance(int pos, int c, const int* seq, int n);
 // tiny unsharded block: MTTKRP by the one-launch kernel instead of contraction pass + reduction
 inline bool small_direct(bool sharded, const CpBlock& b, int R) {
-  return !sharded && small_mttkrp_ok(b.X.elems_padded(), b.nd, b.dims, R);
+  return !sharded && !b.half && small_mttkrp_ok(b.X.elems_padded(), b.nd, b.dims, R);
 }
 
 // `full_array`: the caller's whole tensor when it holds one (lets a sharded engine take its mode-3 slab as well)
 void block_upload(const BlockCtx& cx, CpBlock& b, int nd, const int64_t* dims, const double* host, int prec, int64_t row0,
                   int64_t local_rows, const double* full_array = nullptr);
+// Turns a freshly uploaded fp32 3-way block into its half form (include/aoadmm_hip.h, AOADMM_PREC_F16): scale from the
+// largest magnitude, three half pass copies built one at a time, natural array released.  Throws AOADMM_ERR_INVALID for
+// a non-finite entry, AOADMM_ERR_NOMEM / AOADMM_ERR_UNSUPPORTED when a copy cannot be built; the block is then left
+// without data.
+void block_make_half(const BlockCtx& cx, CpBlock& b);
 // builds the mode-3-sharded copy[0] from a natural-layout slab X(:, :, [k0, k0 + kloc)) already on the device
 void adopt_ksharded_xp(const BlockCtx& cx, CpBlock& b, const void* slab, int64_t k0, int64_t kloc);
 bool want_ksharded_xp(const BlockCtx& cx, const CpBlock& b, int64_t K, int64_t* k0, int64_t* kloc);

@@ -3,7 +3,9 @@
 #include "misc.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
 
 namespace aoadmm {
 
@@ -100,6 +102,12 @@ static void upload_padded(const BlockCtx& cx, void* dst, int prec, int64_t pad, 
 void block_upload(const BlockCtx& cx, CpBlock& b, int nd, const int64_t* dims, const double* host, int prec, int64_t row0,
                   int64_t local_rows, const double* full_array) {
   AO_REQUIRE(nd >= 2 && nd <= 8, "tensor order %d unsupported", nd);
+  // AOADMM_PREC_F16: the entries are rounded to fp32 exactly as for AOADMM_PREC_F32, then block_make_half takes over
+  const bool half = prec == AOADMM_PREC_F16;
+  if (half) {
+    AO_REQUIRE(nd == 3 && !cx.sharded, "internal: half storage is for unsharded 3-way blocks (the callers refuse the rest)");
+    prec = AOADMM_PREC_F32;
+  }
   AO_REQUIRE(prec == AOADMM_PREC_F64 || prec == AOADMM_PREC_F32, "bad precision id %d", prec);
   AO_REQUIRE(row0 >= 0 && local_rows > 0 && row0 + local_rows <= dims[0], "bad row block [%lld,+%lld) of %lld",
              (long long)row0, (long long)local_rows, (long long)dims[0]);
@@ -130,6 +138,7 @@ void block_upload(const BlockCtx& cx, CpBlock& b, int nd, const int64_t* dims, c
     AO_HIP(hipStreamSynchronize(s));
   }
   b.reset_derived();
+  if (half) { block_make_half(cx, b); return; }       // no fp32 copy is ever built: peak 4 + 3 * 2 bytes per entry
   if (nd == 3 && full_array != nullptr) {             // the caller holds the whole tensor: mode-3 slab for the mode-1 pass
     int64_t k0 = 0, kloc = 0;
     if (want_ksharded_xp(cx, b, dims[2], &k0, &kloc)) {
@@ -142,6 +151,54 @@ void block_upload(const BlockCtx& cx, CpBlock& b, int nd, const int64_t* dims, c
     }
   }
   if (nd == 3) { (void)ensure_pass_copy(cx, b, 1); (void)ensure_pass_copy(cx, b, 2); }   // one-off set-up cost belongs to the upload
+}
+
+// ---- half storage ----------------------------------------------------------
+static bool room_for(size_t bytes);
+
+void block_make_half(const BlockCtx& cx, CpBlock& b) {
+  AO_REQUIRE(b.nd == 3 && b.X.prec == AOADMM_PREC_F32 && b.X.data.p && !b.has_mask && !cx.sharded,
+             "internal: half storage is built from an unsharded, unmasked fp32 3-way block");
+  hipStream_t s = cx.stream;
+  auto fail = [&](int code, const std::string& msg) {  // the fp32 array is not the data: nothing valid is left
+    drop_pass_copies(b);
+    b.X.data.release();
+    b.has_data = false; b.half = false; b.scale = 1.0; b.x_released = false; b.cached_mode = -1;
+    throw Error(code, msg);
+  };
+  drop_pass_copies(b);
+  for (PassCopy& c : b.copy) c.refused = false;
+  // scale: a = max |x| = m * 2^E, m in [0.5, 1)  ->  s = 2^(15 - E), kept a normal fp32 number; all zeros: s = 1
+  DevBuf stat;
+  stat.alloc(2 * sizeof(uint32_t));
+  tensor_absmax_f32(stat.as<uint32_t>(), b.X.data.as<float>(), b.X.elems_padded(), s);
+  uint32_t h2[2] = {0, 0};
+  AO_HIP(hipMemcpyAsync(h2, stat.p, sizeof h2, hipMemcpyDeviceToHost, s));
+  AO_HIP(hipStreamSynchronize(s));
+  if (h2[1]) fail(AOADMM_ERR_INVALID, "half-precision storage: the tensor holds an entry that is not finite");
+  float amax;
+  std::memcpy(&amax, &h2[0], sizeof amax);
+  double scale = 1.0;
+  if (amax > 0.f) {
+    int E;
+    (void)std::frexp((double)amax, &E);
+    scale = std::ldexp(1.0, std::min(127, std::max(-126, 15 - E)));
+  }
+  const int64_t I = b.dims[0], J = b.dims[1], K = b.dims[2];
+  for (int c = 0; c < 3; ++c) {
+    PassCopy& pc = b.copy[c];
+    const int64_t pad = pad_of(AOADMM_PREC_F32, b.dims[(c + 1) % 3]);
+    const size_t bytes = (size_t)half_copy_elems(pad * b.dims[(c + 2) % 3], b.dims[c]) * 2;
+    if (!room_for(bytes)) fail(AOADMM_ERR_NOMEM, fmt("half-precision storage: no room in device memory for the pass copy of mode %d (%zu bytes)", c + 1, bytes));
+    pc.buf.alloc(bytes);
+    pc.pad = pad;
+    if (!half_layout_copy(b.X.data.p, pc.buf.p, c, I, b.X.pad0, J, K, pad, (float)scale, s))
+      fail(AOADMM_ERR_UNSUPPORTED, fmt("half-precision storage: a mode of the tensor is too long for the copy kernels (pass copy of mode %d)", c + 1));
+    pc.present = true;
+  }
+  AO_HIP(hipStreamSynchronize(s));                     // the copies were built from it on this stream
+  b.X.data.release();                                  // whatever AOADMM_RELEASE_NATURAL says: the fp32 array is not the data
+  b.x_released = true; b.half = true; b.scale = scale; b.cached_mode = -1;
 }
 
 // ---- pass copies -----------------------------------------------------------
@@ -257,6 +314,17 @@ void ensure_contraction(const BlockCtx& cx, CpBlock& b, int pos, const FactorRef
   }
   ContractPlan pl;
   const double* Fc = c == 0 ? facs[0].p + (cx.sharded ? b.row0 : 0) : facs[c].p;
+  if (b.half) {                                        // the half copies are the data: always a pass on copy c
+    AO_REQUIRE(b.copy[c].present, "internal: half block without its pass copy of mode %d", c + 1);
+    const int64_t M = b.copy[c].pad * b.dims[(c + 2) % 3], C = b.dims[c], MB = kRowBlockElems;
+    pl = make_plan(round_up(M, MB) / MB, MB * round_up(C, kHalfGroupCols), MB, MB, C, R, AOADMM_PREC_F16);
+    pl.on_copy = true;
+    pl.xscale = b.scale;
+    b.T.ensure(pl.t_bytes()); b.frag.ensure(pl.frag_bytes(AOADMM_PREC_F16));
+    timed_contract(cx, b.copy[c].buf.p, AOADMM_PREC_F16, pl, Fc, facs[c].ld, b.frag.p, b.T.p);
+    b.cached_mode = c; b.cached_version = facs[c].version; b.plan = pl;
+    return;
+  }
   if (use_cache && ensure_pass_copy(cx, b, c)) {       // (mode 1 is only ever chosen with use_cache)
     // a pass on a row-blocked copy: one "batch" per row block, each a contiguous MB x C matrix.  With a communicator
     // copy 0 holds this rank's slab of mode 3 and ALL of mode 1 (CpBlock::xp_ksharded): a complete T of 1/N the size

@@ -44,6 +44,20 @@ void reg_value(double* slot, int type, double p0, const double* X, int64_t rows,
 constexpr int64_t kRowBlockElems = 512;
 bool block_layout_copy(const void* X, void* D, int which, int prec, int64_t I, int64_t Ip, int64_t J, int64_t K,
                        int64_t Tp, hipStream_t s);
+// Half (AOADMM_PREC_F16) form of the same copies, written from the fp32 natural array X (first dimension padded to Ip):
+// the copy for the pass that contracts mode c holds q = fp16_rn(x * s) with rows m = a + Apad * b (a, b: the modes
+// (c + 1) % 3 and (c + 2) % 3, Apad = a's extent padded to a multiple of 4) in blocks of kRowBlockElems rows, the columns
+// of a block grouped by kHalfGroupCols:
+//     element (m, c)  ->  (m / MB) * MB * Cp  +  (c / 32) * MB * 32  +  (m % MB) * 32  +  c % 32      (in halves),
+// Cp = C padded to a multiple of 32; padding rows and padding columns are zeros.  D holds half_copy_elems() halves.
+// false: a mode is too long for one launch.
+constexpr int64_t kHalfGroupCols = 32;
+inline int64_t half_copy_elems(int64_t rows, int64_t C) { return round_up(rows, kRowBlockElems) * round_up(C, kHalfGroupCols); }
+bool half_layout_copy(const void* X, void* D, int c, int64_t I, int64_t Ip, int64_t J, int64_t K, int64_t Apad, float s,
+                      hipStream_t st);
+// out2[0] = bit pattern of max |x| over the finite entries of an fp32 array, out2[1] != 0 when an entry is not finite
+void tensor_absmax_f32(uint32_t* out2, const float* X, int64_t n, hipStream_t s);
+
 // Y = X_(n) X_(n)' of a resident dense block (cmtf_nvecs.m:56): row a of the unfolding at X + a*sa, reduction
 // over t1 < n1 (stride s1) x t2 < n2 (stride s2); Y is n x n column-major fp64.
 struct UnfoldGramArgs {

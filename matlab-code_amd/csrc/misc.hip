@@ -112,10 +112,41 @@ __global__ void sum_ws_k(double* slot, const double* ws, int nb, int stride, int
   }
 }
 void tensor_sumsq(double* slot, const void* X, int prec, int64_t n, double* ws, hipStream_t s) {
-  if (prec == AOADMM_PREC_F32) tensor_sumsq_k<float><<<kNormBlocks, 256, 0, s>>>(ws, (const float*)X, n);
+  if (prec == AOADMM_PREC_F16) tensor_sumsq_k<_Float16><<<kNormBlocks, 256, 0, s>>>(ws, (const _Float16*)X, n);
+  else if (prec == AOADMM_PREC_F32) tensor_sumsq_k<float><<<kNormBlocks, 256, 0, s>>>(ws, (const float*)X, n);
   else tensor_sumsq_k<double><<<kNormBlocks, 256, 0, s>>>(ws, (const double*)X, n);
   AO_KERNEL_CHECK();
   sum_ws_k<<<1, 64, 0, s>>>(slot, ws, kNormBlocks, 1, 1);
+  AO_KERNEL_CHECK();
+}
+
+// max |x| and "an entry is not finite" in one pass (the half upload's scale, cpblock.hip block_make_half).  Positive
+// floats order like their bit patterns, and a maximum does not depend on the order it is taken in.
+__global__ void tensor_absmax_f32_k(uint32_t* out2, const float* __restrict__ X, int64_t n) {
+  __shared__ uint32_t shm[256], shf[256];
+  uint32_t mx = 0, bad = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t u = __float_as_uint(X[i]) & 0x7fffffffu;
+    if (u >= 0x7f800000u) bad = 1;                    // inf or NaN
+    else if (u > mx) mx = u;
+  }
+  shm[threadIdx.x] = mx; shf[threadIdx.x] = bad;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st) {
+      if (shm[threadIdx.x + st] > shm[threadIdx.x]) shm[threadIdx.x] = shm[threadIdx.x + st];
+      shf[threadIdx.x] |= shf[threadIdx.x + st];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    atomicMax(out2, shm[0]);
+    if (shf[0]) atomicOr(out2 + 1, 1u);
+  }
+}
+void tensor_absmax_f32(uint32_t* out2, const float* X, int64_t n, hipStream_t s) {
+  AO_HIP(hipMemsetAsync(out2, 0, 2 * sizeof(uint32_t), s));
+  tensor_absmax_f32_k<<<kNormBlocks, 256, 0, s>>>(out2, X, n);
   AO_KERNEL_CHECK();
 }
 
@@ -325,6 +356,63 @@ bool block_layout_copy(const void* X, void* D, int which, int prec, int64_t I, i
   if (prec == AOADMM_PREC_F32) { if (which == 1) AO_BP(float, 1); else AO_BP(float, 2); }
   else { if (which == 1) AO_BP(double, 1); else AO_BP(double, 2); }
 #undef AO_BP
+  AO_KERNEL_CHECK();
+  return true;
+}
+
+// Half pass copies (misc.h): a workgroup moves a 16 (a) x 16 (b) x 32 (c) box of X through LDS, reading along whichever
+// of the three indices is contiguous in X (U) and writing 32 halves = one 64-byte row of a column group at a time; the
+// 16 rows of one b are 1 KB contiguous.  The value is rounded once: fp16_rn(x * s), s a power of two.
+struct HalfCopyArgs {
+  const float* X;
+  _Float16* D;
+  int64_t A, Apad, B, C, Cg;     // extents of a (valid, padded), b, c; column groups
+  int64_t sa, sb, sc;            // element strides of a, b, c in X
+  float s;
+};
+template <int U>
+__global__ __launch_bounds__(256) void half_copy_k(HalfCopyArgs h) {
+  __shared__ _Float16 tile[16][16][34];               // [b][a][c]
+  const int64_t cg = blockIdx.x, a0 = (int64_t)blockIdx.y * 16, b0 = (int64_t)blockIdx.z * 16;
+  for (int e = threadIdx.x; e < 8192; e += 256) {
+    int ia, ib, ic;
+    if (U == 0) { ia = e & 15; ic = (e >> 4) & 31; ib = e >> 9; }
+    else if (U == 1) { ib = e & 15; ic = (e >> 4) & 31; ia = e >> 9; }
+    else { ic = e & 31; ia = (e >> 5) & 15; ib = e >> 9; }
+    const int64_t a = a0 + ia, b = b0 + ib, c = kHalfGroupCols * cg + ic;
+    const float v = (a < h.A && b < h.B && c < h.C) ? h.X[a * h.sa + b * h.sb + c * h.sc] : 0.f;
+    tile[ib][ia][ic] = (_Float16)(v * h.s);
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < 8192; e += 256) {
+    const int ic = e & 31, ia = (e >> 5) & 15, ib = e >> 9;
+    const int64_t a = a0 + ia, b = b0 + ib;
+    if (a < h.Apad && b < h.B) {                      // a >= A, c >= C: zeros from the load guard
+      const int64_t m = a + h.Apad * b;
+      h.D[(m / kRowBlockElems) * (kRowBlockElems * kHalfGroupCols * h.Cg) + cg * (kRowBlockElems * kHalfGroupCols) +
+          (m % kRowBlockElems) * kHalfGroupCols + ic] = tile[ib][ia][ic];
+    }
+  }
+}
+bool half_layout_copy(const void* X, void* D, int c, int64_t I, int64_t Ip, int64_t J, int64_t K, int64_t Apad, float s,
+                      hipStream_t st) {
+  const int64_t ext[3] = {I, J, K}, stride[3] = {1, Ip, Ip * J};
+  const int ma = (c + 1) % 3, mb = (c + 2) % 3;
+  HalfCopyArgs h;
+  h.X = (const float*)X; h.D = (_Float16*)D;
+  h.A = ext[ma]; h.Apad = Apad; h.B = ext[mb]; h.C = ext[c]; h.Cg = cdiv(ext[c], kHalfGroupCols);
+  h.sa = stride[ma]; h.sb = stride[mb]; h.sc = stride[c];
+  h.s = s;
+  if (Apad < h.A || cdiv(Apad, 16) > 65535 || cdiv(h.B, 16) > 65535 || h.Cg > 2147483647) return false;
+  const int64_t M = Apad * h.B, Mpad = round_up(M, kRowBlockElems);
+  if (Mpad > M) {                                     // rows of the last block beyond the data
+    const size_t blk = (size_t)kRowBlockElems * kHalfGroupCols * h.Cg * sizeof(_Float16);
+    AO_HIP(hipMemsetAsync((char*)D + (size_t)(Mpad / kRowBlockElems - 1) * blk, 0, blk, st));
+  }
+  const dim3 grid((unsigned)h.Cg, (unsigned)cdiv(Apad, 16), (unsigned)cdiv(h.B, 16));
+  if (c == 2) half_copy_k<0><<<grid, 256, 0, st>>>(h);        // a = mode 1 is the contiguous one
+  else if (c == 1) half_copy_k<1><<<grid, 256, 0, st>>>(h);   // b = mode 1
+  else half_copy_k<2><<<grid, 256, 0, st>>>(h);               // c = mode 1
   AO_KERNEL_CHECK();
   return true;
 }

@@ -161,6 +161,9 @@ class Engine {
   void tensor_mask_upload(int p, const uint8_t* mask);
   void par2_slab_mask_upload(int p, int k, const uint8_t* mask);
   double tensor_normsq(int p);
+  // what tensor p keeps on the device: the precision its passes stream, the power-of-two scale of a half block (else 1)
+  // and the bytes of its natural array, pass copies, transposed copy and mask (dense CP blocks; 0 for the others)
+  void tensor_storage_info(int p, int* precision, double* scale, int64_t* resident_bytes);
 
   // state
   void state_set(int field, int index, int slab, const double* host, int64_t rows, int64_t cols);
@@ -187,6 +190,7 @@ class Engine {
   void par2_gather_slabs(TensorInfo& t);
   // (world_ > 1 stays true after an abort took the communicator away: the engine must not fall back to unsharded work)
   bool sharded() const { return world_ > 1 || comm_ != nullptr || local_ != nullptr; }
+  void require_half_ok(const TensorInfo& t, int p, bool row_block) const;   // AOADMM_ERR_UNSUPPORTED where AOADMM_PREC_F16 is not available
   void require_usable() const;          // throws AOADMM_ERR_RCCL once comm_abort() has run (sticky)
   bool share_only() const { return share_only_; }
   int rank() const { return rank_; }

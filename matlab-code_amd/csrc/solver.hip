@@ -343,6 +343,36 @@ void Engine::model_end() {
 // ---------------------------------------------------------------------------
 // data
 // ---------------------------------------------------------------------------
+// AOADMM_PREC_F16 is for unsharded dense 3-way CP blocks given whole.  The verdict depends on the model and on
+// sharded() only, so every rank of a communicator reaches the same one.
+void Engine::require_half_ok(const TensorInfo& t, int p, bool row_block) const {
+  if (row_block)
+    throw Error(AOADMM_ERR_UNSUPPORTED, "AOADMM_PREC_F16 is not available in aoadmm_tensor_upload_rows: the block's scale comes from the whole tensor");
+  if (sharded())
+    throw Error(AOADMM_ERR_UNSUPPORTED, "AOADMM_PREC_F16 is not available on an engine that belongs to a communicator or to a multi-device context (the scale would have to be the same on every rank)");
+  if (t.nmodes != 3)
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("AOADMM_PREC_F16 is for 3-way CP blocks: tensor %d has %d modes", p, t.nmodes));
+}
+
+void Engine::tensor_storage_info(int p, int* precision, double* scale, int64_t* resident_bytes) {
+  require_usable();
+  AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
+  const TensorInfo& t = tensors_[p];
+  const CpBlock& b = t.blk;
+  const bool dense_cp = !t.par2 && !b.sparse;
+  AO_REQUIRE(t.par2 || b.has_data, "tensor %d has no data", p);
+  if (precision) *precision = !dense_cp ? AOADMM_PREC_F64 : (b.half ? AOADMM_PREC_F16 : b.X.prec);
+  if (scale) *scale = dense_cp && b.half ? b.scale : 1.0;
+  if (resident_bytes) {
+    int64_t n = 0;
+    if (dense_cp) {
+      for (const DevBuf* d : {&b.X.data, &b.Xt.data, &b.copy[0].buf, &b.copy[1].buf, &b.copy[2].buf, &b.mask, &b.maskT})
+        if (d->p) n += (int64_t)d->bytes;
+    }
+    *resident_bytes = n;
+  }
+}
+
 void Engine::tensor_upload(int p, const double* data, int prec, int64_t row0, int64_t local_rows) {
   require_usable();
   AO_REQUIRE(model_done_, "call aoadmm_model_end first");
@@ -350,6 +380,7 @@ void Engine::tensor_upload(int p, const double* data, int prec, int64_t row0, in
   TensorInfo& t = tensors_[p];
   AO_REQUIRE(!t.par2, "tensor %d is PARAFAC2: use aoadmm_par2_slab_upload", p);
   AO_REQUIRE(local_rows < 0 || !t.blk.sparse, "tensor %d holds sparse data: a row block cannot replace it (use aoadmm_tensor_upload)", p);
+  if (prec == AOADMM_PREC_F16) require_half_ok(t, p, local_rows >= 0);   // refused before anything of the block changes
   if (t.blk.sparse) { t.blk.coo.clear(); t.blk.sparse = false; }   // a dense upload replaces the sparse form
   AO_HIP(hipSetDevice(device_));
   const BlockCtx cx = block_ctx();
@@ -441,6 +472,9 @@ double Engine::tensor_normsq(int p) {
       tensor_sumsq(slot, t.p2.X.p, AOADMM_PREC_F64, (int64_t)t.p2.I * t.p2.Jtot, ws.d(), stream_);
     } else if (t.blk.sparse) {     // norm(sptensor)^2 (:132): the coalesced values; every rank holds all of them
       tensor_sumsq(slot, t.blk.coo.mode[0].val.p, AOADMM_PREC_F64, t.blk.coo.nnz, ws.d(), stream_);
+    } else if (t.blk.half) {       // sum of q^2 over a pass copy (its padding is zero); the data is q / s
+      const CpBlock& b = t.blk;
+      tensor_sumsq(slot, b.copy[2].buf.p, AOADMM_PREC_F16, half_copy_elems(b.copy[2].pad * b.dims[1], b.dims[2]), ws.d(), stream_);
     } else {
       AO_REQUIRE(!t.blk.x_released, "internal: ||X||^2 of tensor %d asked for after its natural-layout array was released", p);
       tensor_sumsq(slot, t.blk.X.data.p, t.blk.X.prec, t.blk.X.elems_padded(), ws.d(), stream_);
@@ -449,6 +483,7 @@ double Engine::tensor_normsq(int p) {
     double v = 0;
     AO_HIP(hipMemcpyAsync(&v, slot, sizeof(double), hipMemcpyDeviceToHost, stream_));
     AO_HIP(hipStreamSynchronize(stream_));
+    if (!t.par2 && !t.blk.sparse && t.blk.half) v = v / t.blk.scale / t.blk.scale;   // powers of two: exact
     t.normsq = v;
     t.normsq_valid = true;
   }
@@ -463,6 +498,9 @@ void Engine::tensor_synth(int p, int rank, uint64_t seed, double noise, int prec
   AO_REQUIRE(!t.par2 && t.nmodes == 3, "synthetic generator handles 3-way CP blocks");
   AO_REQUIRE(!t.blk.sparse, "tensor %d holds sparse data: the synthetic generator writes dense blocks (upload dense data first)", p);
   AO_REQUIRE(rank > 0 && rank <= kMaxRank, "bad rank");
+  const bool half = prec == AOADMM_PREC_F16;           // generated as for AOADMM_PREC_F32, then rounded like an upload
+  if (half) { require_half_ok(t, p, false); prec = AOADMM_PREC_F32; }
+  AO_REQUIRE(prec == AOADMM_PREC_F64 || prec == AOADMM_PREC_F32, "bad precision id %d", prec);
   AO_HIP(hipSetDevice(device_));
   const int64_t I = modes_[t.modes[0]].rows, J = modes_[t.modes[1]].rows, K = modes_[t.modes[2]].rows;
   const int64_t per = cdiv(I, world_);
@@ -496,6 +534,8 @@ void Engine::tensor_synth(int p, int rank, uint64_t seed, double noise, int prec
   AO_HIP(hipStreamSynchronize(stream_));
   b.reset_derived();
   const BlockCtx cx = block_ctx();
+  t.normsq_valid = false;
+  if (half) { block_make_half(cx, b); return; }
   {
     int64_t k0 = 0, kloc = 0;
     if (want_ksharded_xp(cx, b, K, &k0, &kloc)) {        // this rank's third-mode slab of the SAME tensor, all rows

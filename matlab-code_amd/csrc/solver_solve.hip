@@ -210,6 +210,10 @@ struct SolveRun {
 // Znorm_const, the PARAFAC2 blocks' sharding and their B_k Gram matrices.
 void Engine::solve_setup(const aoadmm_options& opt) {
   prepared_mode_ = -1;                                // nothing prepared ahead by an earlier solve is valid for this state
+  if (opt.no_permuted_copy != 0)
+    for (int p = 0; p < n_tensors_; ++p)
+      AO_REQUIRE(tensors_[p].par2 || !tensors_[p].blk.half,
+                 "options.hip.no_permuted_copy = 1 cannot be honoured: tensor %d is stored in half precision and its pass copies are the data", p);
   allow_xp_ = opt.no_permuted_copy == 0;
   if (!allow_xp_)
     for (int p = 0; p < n_tensors_; ++p)

@@ -334,8 +334,11 @@ def build_model(eng, Z, precision='f64'):
 
     Z.object{p} of a CP block may be dense, an `sptensor`, or (2-way blocks) any object with `.tocoo()` such as a
     scipy.sparse matrix; sparse blocks go up as coalesced COO nonzeros (`aoadmm_tensor_upload_coo`) and stay fp64
-    whatever `precision` says (it applies to dense blocks only).  The slabs of a PAR2 block may likewise be 2-way
+    whatever `precision` says (it applies to dense blocks only).  `precision` is 'f64', 'f32' or 'f16'; with 'f16'
+    every dense 3-way CP block without Z.miss is stored as fp16 with one power-of-two scale (AOADMM_PREC_F16,
+    `capi.quantize_f16` is the rule) and every other dense block as fp32.  The slabs of a PAR2 block may likewise be 2-way
     `sptensor`s or objects with `.tocoo()`, all of them or none (`aoadmm_par2_slab_upload_coo`)."""
+    prec = capi.precision_id(precision)                # an unknown string fails before the engine is touched
     lib = eng.lib
     nb_modes = len(Z['size'])
     which_p = _which_p(Z)
@@ -399,10 +402,14 @@ def build_model(eng, Z, precision='f64'):
         r = np.asarray(Z['ridge'], dtype=np.float64)
         capi.check(lib.aoadmm_model_set_ridge(eng.h, capi.dptr(r)))
     capi.check(lib.aoadmm_model_end(eng.h))
-    prec = capi.PREC_F32 if precision == 'f32' else capi.PREC_F64
+    model_prec = prec
     for p in range(P):
         if Z['model'][p] == 'CP':
             obj = Z['object'][p]
+            # 'f16': dense 3-way blocks without a mask; matrices, order > 3 and masked blocks go up as fp32
+            prec = model_prec
+            if prec == capi.PREC_F16 and (len(Z['modes'][p]) != 3 or miss[p] is not None):
+                prec = capi.PREC_F32
             coo = None if isinstance(obj, dict) else coo_of(obj)
             if coo is not None:
                 subs, vals, shape = coo

@@ -150,6 +150,14 @@ class Engine:
         capi.check(self.lib.aoadmm_resident_mttkrp(self.h, int(p), int(tensor_mode), capi.dptr(out), C.byref(ms)))
         return out
 
+    def tensor_storage_info(self, p):
+        """(precision id capi.PREC_*, scale, resident bytes) of tensor p (`aoadmm_tensor_storage_info`): the precision
+        its passes stream, the power-of-two scale of an 'f16' block (1.0 otherwise) and the bytes a dense CP block
+        holds on the device now."""
+        prec, scale, nbytes = C.c_int(0), C.c_double(0), C.c_int64(0)
+        capi.check(self.lib.aoadmm_tensor_storage_info(self.h, int(p), C.byref(prec), C.byref(scale), C.byref(nbytes)))
+        return prec.value, scale.value, nbytes.value
+
     def kernel_stats(self, which, reset=False):
         """(ms, launches, bytes, flops) of a kernel class since the last reset (`aoadmm_kernel_stats`); which = 3:
         MTTKRPs of sparse blocks and passes over the nonzeros of PARAFAC2 blocks with sparse slabs."""
@@ -160,14 +168,15 @@ class Engine:
 
     # ---- op level -----------------------------------------------------------------
     def mttkrp(self, X, U, n, precision='f64'):
-        """`mttkrp(X,U,n)` with 0-based n (cmtf_fun_AOADMM.m:97)."""
+        """`mttkrp(X,U,n)` with 0-based n (cmtf_fun_AOADMM.m:97).  'f16' exists for resident blocks only: the library
+        answers it with `UnsupportedOnDevice` here."""
         X = capi.as_f(X)
         dims = (C.c_int64 * X.ndim)(*X.shape)
         Us = [capi.as_f(u) for u in U]
         R = Us[0].shape[1]
         arr = (C.POINTER(C.c_double) * X.ndim)(*[capi.dptr(u) for u in Us])
         out = np.zeros((X.shape[n], R), order='F')
-        prec = capi.PREC_F32 if precision == 'f32' else capi.PREC_F64
+        prec = capi.precision_id(precision)
         capi.check(self.lib.aoadmm_op_mttkrp(self.h, capi.dptr(X), X.ndim, dims, arr, R, int(n), prec, capi.dptr(out)))
         return out
 
@@ -176,7 +185,7 @@ class Engine:
         X = capi.as_f(X)
         dims = (C.c_int64 * X.ndim)(*X.shape)
         out = np.zeros((X.shape[n], X.shape[n]), order='F')
-        prec = capi.PREC_F32 if precision == 'f32' else capi.PREC_F64
+        prec = capi.precision_id(precision)
         capi.check(self.lib.aoadmm_op_unfold_gram(self.h, capi.dptr(X), X.ndim, dims, int(n), prec, capi.dptr(out)))
         return out
 

@@ -288,7 +288,13 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       for (mwSize i = 0; i < mxGetNumberOfElements(d); ++i) devices.push_back((int)mxGetDoubles(d)[i]);
       if (devices.empty()) devices.assign(1, 0);
     }
-    if (const mxArray* p = field(hip, "precision", false)) precision = str(p) == "f32" ? AOADMM_PREC_F32 : AOADMM_PREC_F64;
+    if (const mxArray* p = field(hip, "precision", false)) {
+      const std::string ps = str(p);
+      if (ps == "f64") precision = AOADMM_PREC_F64;
+      else if (ps == "f32") precision = AOADMM_PREC_F32;
+      else if (ps == "f16") precision = AOADMM_PREC_F16;
+      else mexErrMsgIdAndTxt("aoadmm:precision", "options.hip.precision must be 'f64', 'f32' or 'f16', got '%s'", ps.c_str());
+    }
   }
   if (g_ctx && devices != g_devices) {               // another device list: start over
     aoadmm_destroy(g_ctx);
@@ -434,7 +440,13 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       for (size_t i = 0; i < md.size(); ++i) md[i] = (int)mxGetDoubles(mp)[i] - 1;
       upload_sparse(p, obj, sz, md);                     // values stay fp64 whatever options.hip.precision says
     } else {
-      check(aoadmm_tensor_upload(g_ctx, p, mxGetDoubles(dense_data(obj)), precision));
+      // 'f16': dense 3-way blocks without Z.miss are stored fp16 (AOADMM_PREC_F16), every other dense block fp32
+      int prec_p = precision;
+      if (precision == AOADMM_PREC_F16) {
+        const mxArray* mkp = (miss && !mxIsEmpty(miss) && (mwSize)p < mxGetNumberOfElements(miss)) ? mxGetCell(miss, p) : nullptr;
+        if (mxGetNumberOfElements(mxGetCell(modes, p)) != 3 || (mkp && !mxIsEmpty(mkp))) prec_p = AOADMM_PREC_F32;
+      }
+      check(aoadmm_tensor_upload(g_ctx, p, mxGetDoubles(dense_data(obj)), prec_p));
     }
     // Z.miss{p} (cmtf_AOADMM.m:68-121): same shape as the data, uint8
     const mxArray* mk = (miss && !mxIsEmpty(miss) && (mwSize)p < mxGetNumberOfElements(miss)) ? mxGetCell(miss, p) : nullptr;
