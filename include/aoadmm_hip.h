@@ -108,10 +108,23 @@ enum {
                           natural-layout array is released at once, so aoadmm_tensor_mask_upload on such a block is
                           AOADMM_ERR_INVALID and aoadmm_resident_unfold_gram AOADMM_ERR_UNSUPPORTED, and aoadmm_solve
                           with options.no_permuted_copy = 1 is AOADMM_ERR_INVALID (the copies are the data).
+                          On an engine that belongs to a communicator (aoadmm_comm_init_rank, aoadmm_comm_init_local,
+                          aoadmm_comm_init_rank_share, also one of a single rank) aoadmm_tensor_upload with the whole
+                          array and aoadmm_tensor_synth are COLLECTIVE for this precision: every rank must make the
+                          call.  Each rank takes max |x| and "not finite" over everything it holds (its rows of mode 1
+                          and, where every rank owns one, its slab of mode 3 for the mode-1 pass), one sum all-reduce
+                          of world + 1 doubles carries them round, and steps 2-4 apply to the maximum of the WHOLE
+                          tensor: s is the same on every rank, and a non-finite entry anywhere fails the call on
+                          EVERY rank (after the exchange, so no rank is left alone in a later collective).
+                          aoadmm_tensor_normsq is all-reduced over the ranks' rows before the division by s^2;
+                          aoadmm_tensor_storage_info reports the rank's own resident bytes and the common s.
                           AOADMM_ERR_UNSUPPORTED, the block left as it was: a block that is not 3-way,
-                          aoadmm_tensor_upload_rows, aoadmm_op_mttkrp / aoadmm_op_unfold_gram, and any engine of a
-                          communicator or of an aoadmm_create_multi context.  A copy that cannot be built fails the
-                          upload (AOADMM_ERR_NOMEM: no room in device memory; AOADMM_ERR_UNSUPPORTED: a mode too
+                          aoadmm_tensor_upload_rows (the scale comes from the whole tensor),
+                          aoadmm_op_mttkrp / aoadmm_op_unfold_gram (they run on a natural-layout array), and a
+                          multi-device context (aoadmm_create_multi with more than one device: one caller, one array
+                          for all engines; one context per rank and a communicator serve the same job).  A copy that
+                          cannot be built fails the upload on that rank alone (AOADMM_ERR_NOMEM: no room in device
+                          memory; AOADMM_ERR_UNSUPPORTED: a mode too
                           long for the copy kernels) and leaves the block without data. */
 };
 

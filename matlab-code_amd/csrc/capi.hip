@@ -219,6 +219,7 @@ int aoadmm_create_multi(aoadmm_ctx** ctx, int n_devices, const int* devices) {
     for (int a = 0; a < n; ++a)
       for (int b = a + 1; b < n; ++b) distinct = distinct && devices[a] != devices[b];
     if (n > 1) {
+      for (int r = 0; r < n; ++r) mc->eng[r]->set_multi_member();
       if (distinct) {                                 // RCCL over xGMI, one rank per device
         ncclUniqueId uid;
         ncclResult_t r = ncclGetUniqueId(&uid);

@@ -6,6 +6,8 @@
 #include "contract.h"
 #include "sparse.h"
 
+#include <functional>
+
 namespace aoadmm {
 
 struct FactorRef {
@@ -80,7 +82,8 @@ struct CpBlock {
   // all three copies exist (and no mask does) it can go: 4 -> 3 resident copies (maybe_release_natural)
   bool x_released = false;
   // AOADMM_PREC_F16 storage (3-way blocks, block_make_half): the three pass copies hold q = fp16_rn(x * scale), `scale`
-  // a power of two, and ARE the data (q / scale); the fp32 natural array they were rounded from is gone (x_released)
+  // a power of two, and ARE the data (q / scale); the fp32 natural array they were rounded from is gone (x_released).
+  // With a communicator `scale` comes from the WHOLE tensor (the same on every rank) and copy[0] may be xp_ksharded.
   bool half = false;
   double scale = 1.0;
   // dimension-tree cache: T = X x_c F_c, valid while factor c keeps `cached_version`
@@ -119,11 +122,17 @@ inline bool small_direct(bool sharded, const CpBlock& b, int R) {
 // `full_array`: the caller's whole tensor when it holds one (lets a sharded engine take its mode-3 slab as well)
 void block_upload(const BlockCtx& cx, CpBlock& b, int nd, const int64_t* dims, const double* host, int prec, int64_t row0,
                   int64_t local_rows, const double* full_array = nullptr);
+// Fills `slab` with X(:, :, [k0, k0 + kloc)) of the WHOLE tensor in the natural fp32 layout (all full0 rows, padded to
+// pad_of(AOADMM_PREC_F32, full0)): the caller's way to the mode-3 slab of a sharded half block (upload or generator)
+using SlabSource = std::function<void(DevBuf& slab, int64_t k0, int64_t kloc)>;
 // Turns a freshly uploaded fp32 3-way block into its half form (include/aoadmm_hip.h, AOADMM_PREC_F16): scale from the
-// largest magnitude, three half pass copies built one at a time, natural array released.  Throws AOADMM_ERR_INVALID for
-// a non-finite entry, AOADMM_ERR_NOMEM / AOADMM_ERR_UNSUPPORTED when a copy cannot be built; the block is then left
-// without data.
-void block_make_half(const BlockCtx& cx, CpBlock& b);
+// largest magnitude, three half pass copies built one at a time, natural array released.  On a sharded engine the call
+// is COLLECTIVE: the largest magnitude and the "not finite" flag of every rank's data (its rows and, with `slab_source`
+// where want_ksharded_xp agrees, its mode-3 slab, which becomes the xp_ksharded copy[0]) meet in one all-reduce, so every
+// rank gets the same scale and the same verdict.  Throws AOADMM_ERR_INVALID for a non-finite entry anywhere (on every
+// rank, after the exchange), AOADMM_ERR_NOMEM / AOADMM_ERR_UNSUPPORTED when a copy cannot be built (this rank alone); the
+// block is then left without data.
+void block_make_half(const BlockCtx& cx, CpBlock& b, const SlabSource* slab_source = nullptr);
 // builds the mode-3-sharded copy[0] from a natural-layout slab X(:, :, [k0, k0 + kloc)) already on the device
 void adopt_ksharded_xp(const BlockCtx& cx, CpBlock& b, const void* slab, int64_t k0, int64_t kloc);
 bool want_ksharded_xp(const BlockCtx& cx, const CpBlock& b, int64_t K, int64_t* k0, int64_t* kloc);

@@ -105,7 +105,7 @@ void block_upload(const BlockCtx& cx, CpBlock& b, int nd, const int64_t* dims, c
   // AOADMM_PREC_F16: the entries are rounded to fp32 exactly as for AOADMM_PREC_F32, then block_make_half takes over
   const bool half = prec == AOADMM_PREC_F16;
   if (half) {
-    AO_REQUIRE(nd == 3 && !cx.sharded, "internal: half storage is for unsharded 3-way blocks (the callers refuse the rest)");
+    AO_REQUIRE(nd == 3, "internal: half storage is for 3-way blocks (the callers refuse the rest)");
     prec = AOADMM_PREC_F32;
   }
   AO_REQUIRE(prec == AOADMM_PREC_F64 || prec == AOADMM_PREC_F32, "bad precision id %d", prec);
@@ -138,7 +138,15 @@ void block_upload(const BlockCtx& cx, CpBlock& b, int nd, const int64_t* dims, c
     AO_HIP(hipStreamSynchronize(s));
   }
   b.reset_derived();
-  if (half) { block_make_half(cx, b); return; }       // no fp32 copy is ever built: peak 4 + 3 * 2 bytes per entry
+  if (half) {                                         // no fp32 copy is ever built: peak 4 + 3 * 2 bytes per entry
+    const SlabSource from_host = [&](DevBuf& slab, int64_t k0, int64_t kloc) {
+      const int64_t I = dims[0], J = dims[1], Ipf = pad_of(AOADMM_PREC_F32, I);
+      slab.alloc((size_t)Ipf * J * kloc * sizeof(float));
+      upload_padded(cx, slab.p, AOADMM_PREC_F32, Ipf, full_array + (size_t)I * J * k0, I, J * kloc);   // contiguous in the caller's array
+    };
+    block_make_half(cx, b, full_array != nullptr ? &from_host : nullptr);
+    return;
+  }
   if (nd == 3 && full_array != nullptr) {             // the caller holds the whole tensor: mode-3 slab for the mode-1 pass
     int64_t k0 = 0, kloc = 0;
     if (want_ksharded_xp(cx, b, dims[2], &k0, &kloc)) {
@@ -156,45 +164,88 @@ void block_upload(const BlockCtx& cx, CpBlock& b, int nd, const int64_t* dims, c
 // ---- half storage ----------------------------------------------------------
 static bool room_for(size_t bytes);
 
-void block_make_half(const BlockCtx& cx, CpBlock& b) {
-  AO_REQUIRE(b.nd == 3 && b.X.prec == AOADMM_PREC_F32 && b.X.data.p && !b.has_mask && !cx.sharded,
-             "internal: half storage is built from an unsharded, unmasked fp32 3-way block");
+void block_make_half(const BlockCtx& cx, CpBlock& b, const SlabSource* slab_source) {
+  AO_REQUIRE(b.nd == 3 && b.X.prec == AOADMM_PREC_F32 && b.X.data.p && !b.has_mask,
+             "internal: half storage is built from an unmasked fp32 3-way block");
   hipStream_t s = cx.stream;
-  auto fail = [&](int code, const std::string& msg) {  // the fp32 array is not the data: nothing valid is left
+  auto drop = [&] {                                    // the fp32 array is not the data: nothing valid is left
     drop_pass_copies(b);
     b.X.data.release();
     b.has_data = false; b.half = false; b.scale = 1.0; b.x_released = false; b.cached_mode = -1;
-    throw Error(code, msg);
   };
+  auto fail = [&](int code, const std::string& msg) { drop(); throw Error(code, msg); };
   drop_pass_copies(b);
   for (PassCopy& c : b.copy) c.refused = false;
-  // scale: a = max |x| = m * 2^E, m in [0.5, 1)  ->  s = 2^(15 - E), kept a normal fp32 number; all zeros: s = 1
-  DevBuf stat;
-  stat.alloc(2 * sizeof(uint32_t));
-  tensor_absmax_f32(stat.as<uint32_t>(), b.X.data.as<float>(), b.X.elems_padded(), s);
+  // largest magnitude and "not finite" over everything this rank holds: its rows, then its mode-3 slab (rows of other
+  // ranks: they keep the values of a lone rank-share engine finite too, which learns nothing from peers)
+  DevBuf stat, slab;
+  int64_t k0 = 0, kloc = 0;
+  bool ksh = false;
   uint32_t h2[2] = {0, 0};
-  AO_HIP(hipMemcpyAsync(h2, stat.p, sizeof h2, hipMemcpyDeviceToHost, s));
-  AO_HIP(hipStreamSynchronize(s));
-  if (h2[1]) fail(AOADMM_ERR_INVALID, "half-precision storage: the tensor holds an entry that is not finite");
+  try {
+    stat.alloc(2 * sizeof(uint32_t));
+    tensor_absmax_f32(stat.as<uint32_t>(), b.X.data.as<float>(), b.X.elems_padded(), s);
+    if (slab_source) {
+      BlockCtx with_copies = cx;                       // the copies are the data: options.hip.no_permuted_copy has no say
+      with_copies.allow_copies = true;
+      ksh = want_ksharded_xp(with_copies, b, b.dims[2], &k0, &kloc);
+    }
+    if (ksh) {
+      (*slab_source)(slab, k0, kloc);
+      tensor_absmax_f32(stat.as<uint32_t>(), slab.as<float>(), pad_of(AOADMM_PREC_F32, b.full0) * b.dims[1] * kloc, s, true);
+    }
+    AO_HIP(hipMemcpyAsync(h2, stat.p, sizeof h2, hipMemcpyDeviceToHost, s));
+    AO_HIP(hipStreamSynchronize(s));
+  } catch (...) { drop(); throw; }                     // (a lone failure, like any out-of-memory in front of a collective)
   float amax;
   std::memcpy(&amax, &h2[0], sizeof amax);
+  double gmax = (double)amax;
+  bool bad = h2[1] != 0;
+  if (cx.sharded) {
+    // One sum all-reduce of world + 1 doubles: slot g holds rank g's maximum (zero from everyone else), the last slot
+    // counts the ranks that saw a non-finite entry.  Every sum has one nonzero term or is a small integer: exact, and the
+    // same bits on every rank.  Nothing above fails for a reason the data gives, so every rank gets here.
+    std::vector<double> v((size_t)cx.world + 1, 0.0);
+    v[(size_t)cx.rank] = gmax;
+    v[(size_t)cx.world] = bad ? 1.0 : 0.0;
+    try {
+      DevBuf ex;
+      ex.alloc(v.size() * sizeof(double));
+      AO_HIP(hipMemcpyAsync(ex.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, s));
+      cx.allreduce_from(cx.comm, ex.d(), ex.d(), (int64_t)v.size());
+      AO_HIP(hipMemcpyAsync(v.data(), ex.p, v.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+      AO_HIP(hipStreamSynchronize(s));
+    } catch (...) { drop(); throw; }
+    gmax = *std::max_element(v.begin(), v.begin() + cx.world);
+    bad = v[(size_t)cx.world] != 0.0;
+  }
+  if (bad) fail(AOADMM_ERR_INVALID, "half-precision storage: the tensor holds an entry that is not finite");
+  // scale: a = max |x| = m * 2^E, m in [0.5, 1)  ->  s = 2^(15 - E), kept a normal fp32 number; all zeros: s = 1
   double scale = 1.0;
-  if (amax > 0.f) {
+  if (gmax > 0.0) {
     int E;
-    (void)std::frexp((double)amax, &E);
+    (void)std::frexp(gmax, &E);
     scale = std::ldexp(1.0, std::min(127, std::max(-126, 15 - E)));
   }
   const int64_t I = b.dims[0], J = b.dims[1], K = b.dims[2];
   for (int c = 0; c < 3; ++c) {
     PassCopy& pc = b.copy[c];
+    const bool from_slab = c == 0 && ksh;              // rank g's X(:, :, K_g) with ALL of mode 1 (CpBlock::xp_ksharded)
     const int64_t pad = pad_of(AOADMM_PREC_F32, b.dims[(c + 1) % 3]);
-    const size_t bytes = (size_t)half_copy_elems(pad * b.dims[(c + 2) % 3], b.dims[c]) * 2;
+    const size_t bytes = (size_t)(from_slab ? half_copy_elems(pad * kloc, b.full0) : half_copy_elems(pad * b.dims[(c + 2) % 3], b.dims[c])) * 2;
     if (!room_for(bytes)) fail(AOADMM_ERR_NOMEM, fmt("half-precision storage: no room in device memory for the pass copy of mode %d (%zu bytes)", c + 1, bytes));
-    pc.buf.alloc(bytes);
+    try { pc.buf.alloc(bytes); } catch (...) { drop(); throw; }
     pc.pad = pad;
-    if (!half_layout_copy(b.X.data.p, pc.buf.p, c, I, b.X.pad0, J, K, pad, (float)scale, s))
+    const bool ok = from_slab ? half_layout_copy(slab.p, pc.buf.p, 0, b.full0, pad_of(AOADMM_PREC_F32, b.full0), J, kloc, pad, (float)scale, s)
+                              : half_layout_copy(b.X.data.p, pc.buf.p, c, I, b.X.pad0, J, K, pad, (float)scale, s);
+    if (!ok)
       fail(AOADMM_ERR_UNSUPPORTED, fmt("half-precision storage: a mode of the tensor is too long for the copy kernels (pass copy of mode %d)", c + 1));
     pc.present = true;
+    if (from_slab) {
+      b.xp_ksharded = true; b.xp_k0 = k0; b.xp_kloc = kloc;
+      AO_HIP(hipStreamSynchronize(s));                 // the copy was built from it on this stream
+      slab.release();                                  // before the two other copies are allocated
+    }
   }
   AO_HIP(hipStreamSynchronize(s));                     // the copies were built from it on this stream
   b.X.data.release();                                  // whatever AOADMM_RELEASE_NATURAL says: the fp32 array is not the data
@@ -316,10 +367,13 @@ void ensure_contraction(const BlockCtx& cx, CpBlock& b, int pos, const FactorRef
   const double* Fc = c == 0 ? facs[0].p + (cx.sharded ? b.row0 : 0) : facs[c].p;
   if (b.half) {                                        // the half copies are the data: always a pass on copy c
     AO_REQUIRE(b.copy[c].present, "internal: half block without its pass copy of mode %d", c + 1);
-    const int64_t M = b.copy[c].pad * b.dims[(c + 2) % 3], C = b.dims[c], MB = kRowBlockElems;
+    const bool ksh = c == 0 && b.xp_ksharded;          // this rank's slab of mode 3 and ALL of mode 1, as below
+    const int64_t M = b.copy[c].pad * (ksh ? b.xp_kloc : b.dims[(c + 2) % 3]), C = ksh ? b.full0 : b.dims[c];
+    const int64_t MB = kRowBlockElems;
     pl = make_plan(round_up(M, MB) / MB, MB * round_up(C, kHalfGroupCols), MB, MB, C, R, AOADMM_PREC_F16);
     pl.on_copy = true;
     pl.xscale = b.scale;
+    if (ksh) Fc = facs[0].p;
     b.T.ensure(pl.t_bytes()); b.frag.ensure(pl.frag_bytes(AOADMM_PREC_F16));
     timed_contract(cx, b.copy[c].buf.p, AOADMM_PREC_F16, pl, Fc, facs[c].ld, b.frag.p, b.T.p);
     b.cached_mode = c; b.cached_version = facs[c].version; b.plan = pl;

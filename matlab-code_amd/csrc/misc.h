@@ -55,8 +55,9 @@ constexpr int64_t kHalfGroupCols = 32;
 inline int64_t half_copy_elems(int64_t rows, int64_t C) { return round_up(rows, kRowBlockElems) * round_up(C, kHalfGroupCols); }
 bool half_layout_copy(const void* X, void* D, int c, int64_t I, int64_t Ip, int64_t J, int64_t K, int64_t Apad, float s,
                       hipStream_t st);
-// out2[0] = bit pattern of max |x| over the finite entries of an fp32 array, out2[1] != 0 when an entry is not finite
-void tensor_absmax_f32(uint32_t* out2, const float* X, int64_t n, hipStream_t s);
+// out2[0] = bit pattern of max |x| over the finite entries of an fp32 array, out2[1] != 0 when an entry is not finite;
+// `accumulate`: out2 already holds the result of an earlier call and the two arrays are taken together
+void tensor_absmax_f32(uint32_t* out2, const float* X, int64_t n, hipStream_t s, bool accumulate = false);
 
 // Y = X_(n) X_(n)' of a resident dense block (cmtf_nvecs.m:56): row a of the unfolding at X + a*sa, reduction
 // over t1 < n1 (stride s1) x t2 < n2 (stride s2); Y is n x n column-major fp64.

@@ -144,8 +144,8 @@ __global__ void tensor_absmax_f32_k(uint32_t* out2, const float* __restrict__ X,
     if (shf[0]) atomicOr(out2 + 1, 1u);
   }
 }
-void tensor_absmax_f32(uint32_t* out2, const float* X, int64_t n, hipStream_t s) {
-  AO_HIP(hipMemsetAsync(out2, 0, 2 * sizeof(uint32_t), s));
+void tensor_absmax_f32(uint32_t* out2, const float* X, int64_t n, hipStream_t s, bool accumulate) {
+  if (!accumulate) AO_HIP(hipMemsetAsync(out2, 0, 2 * sizeof(uint32_t), s));
   tensor_absmax_f32_k<<<kNormBlocks, 256, 0, s>>>(out2, X, n);
   AO_KERNEL_CHECK();
 }

@@ -193,6 +193,9 @@ class Engine {
   void require_half_ok(const TensorInfo& t, int p, bool row_block) const;   // AOADMM_ERR_UNSUPPORTED where AOADMM_PREC_F16 is not available
   void require_usable() const;          // throws AOADMM_ERR_RCCL once comm_abort() has run (sticky)
   bool share_only() const { return share_only_; }
+  // One of the engines of a multi-device context (aoadmm_create_multi with more than one device): its data calls fan out
+  // from one caller, and AOADMM_PREC_F16 stays refused there (require_half_ok)
+  void set_multi_member() { multi_member_ = true; }
   int rank() const { return rank_; }
   int world() const { return world_; }
 
@@ -294,6 +297,7 @@ class Engine {
   std::atomic<bool> aborted_{false};
   std::shared_ptr<LocalGroup> local_;   // process-local group (threads of one process), see solver_comm.hip
   int rank_ = 0, world_ = 1;
+  bool multi_member_ = false;           // set_multi_member()
   bool share_only_ = false;             // aoadmm_comm_init_rank_share: rank_/world_ of an N-rank job on a one-rank communicator
   aoadmm_progress_fn progress_fn_ = nullptr;   // options.Display = 'iter'
   void* progress_user_ = nullptr;

@@ -343,13 +343,14 @@ void Engine::model_end() {
 // ---------------------------------------------------------------------------
 // data
 // ---------------------------------------------------------------------------
-// AOADMM_PREC_F16 is for unsharded dense 3-way CP blocks given whole.  The verdict depends on the model and on
-// sharded() only, so every rank of a communicator reaches the same one.
+// AOADMM_PREC_F16 is for dense 3-way CP blocks given whole, on one engine or on the ranks of a communicator (where the
+// upload is a collective: block_make_half).  The verdict depends on the model and on how the context was made only, so
+// every rank of a communicator reaches the same one.
 void Engine::require_half_ok(const TensorInfo& t, int p, bool row_block) const {
   if (row_block)
     throw Error(AOADMM_ERR_UNSUPPORTED, "AOADMM_PREC_F16 is not available in aoadmm_tensor_upload_rows: the block's scale comes from the whole tensor");
-  if (sharded())
-    throw Error(AOADMM_ERR_UNSUPPORTED, "AOADMM_PREC_F16 is not available on an engine that belongs to a communicator or to a multi-device context (the scale would have to be the same on every rank)");
+  if (multi_member_)
+    throw Error(AOADMM_ERR_UNSUPPORTED, "AOADMM_PREC_F16 is not available on a multi-device context (aoadmm_create_multi): use one context per rank and a communicator");
   if (t.nmodes != 3)
     throw Error(AOADMM_ERR_UNSUPPORTED, fmt("AOADMM_PREC_F16 is for 3-way CP blocks: tensor %d has %d modes", p, t.nmodes));
 }
@@ -473,8 +474,9 @@ double Engine::tensor_normsq(int p) {
     } else if (t.blk.sparse) {     // norm(sptensor)^2 (:132): the coalesced values; every rank holds all of them
       tensor_sumsq(slot, t.blk.coo.mode[0].val.p, AOADMM_PREC_F64, t.blk.coo.nnz, ws.d(), stream_);
     } else if (t.blk.half) {       // sum of q^2 over a pass copy (its padding is zero); the data is q / s
-      const CpBlock& b = t.blk;
+      const CpBlock& b = t.blk;      // copy[2] holds this rank's rows, and s is the same on every rank
       tensor_sumsq(slot, b.copy[2].buf.p, AOADMM_PREC_F16, half_copy_elems(b.copy[2].pad * b.dims[1], b.dims[2]), ws.d(), stream_);
+      allreduce(slot, 1);
     } else {
       AO_REQUIRE(!t.blk.x_released, "internal: ||X||^2 of tensor %d asked for after its natural-layout array was released", p);
       tensor_sumsq(slot, t.blk.X.data.p, t.blk.X.prec, t.blk.X.elems_padded(), ws.d(), stream_);
@@ -535,7 +537,16 @@ void Engine::tensor_synth(int p, int rank, uint64_t seed, double noise, int prec
   b.reset_derived();
   const BlockCtx cx = block_ctx();
   t.normsq_valid = false;
-  if (half) { block_make_half(cx, b); return; }
+  if (half) {                                          // collective on a sharded engine, like the norms above
+    const SlabSource generate = [&](DevBuf& slab, int64_t k0, int64_t kloc) {   // the same tensor's third-mode slab, all rows
+      SynthArgs ak = a;
+      ak.I_loc = I; ak.I_pad = pad_of(prec, I); ak.row0 = 0; ak.k0 = k0; ak.K_loc = kloc;
+      slab.alloc((size_t)ak.I_pad * J * kloc * b.X.elem_size());
+      synth_write(slab.p, prec, A.d(), B.d(), C.d(), ak, sigma, 1.0 / std::sqrt(nsq), stream_);
+    };
+    block_make_half(cx, b, &generate);
+    return;
+  }
   {
     int64_t k0 = 0, kloc = 0;
     if (want_ksharded_xp(cx, b, K, &k0, &kloc)) {        // this rank's third-mode slab of the SAME tensor, all rows

@@ -336,7 +336,11 @@ def build_model(eng, Z, precision='f64'):
     scipy.sparse matrix; sparse blocks go up as coalesced COO nonzeros (`aoadmm_tensor_upload_coo`) and stay fp64
     whatever `precision` says (it applies to dense blocks only).  `precision` is 'f64', 'f32' or 'f16'; with 'f16'
     every dense 3-way CP block without Z.miss is stored as fp16 with one power-of-two scale (AOADMM_PREC_F16,
-    `capi.quantize_f16` is the rule) and every other dense block as fp32.  The slabs of a PAR2 block may likewise be 2-way
+    `capi.quantize_f16` is the rule) and every other dense block as fp32.  On an engine that belongs to a communicator
+    (`Engine.comm_init_*`) the 'f16' upload of such a block is a COLLECTIVE: every rank calls `build_model` with the same
+    whole array, keeps its rows (and its mode-3 slab) as fp16 and gets the scale of the WHOLE tensor; a non-finite entry
+    anywhere raises `AoadmmError` (ERR_INVALID) on every rank.  A multi-device engine (`Engine([0, 1, ...])`) answers 'f16'
+    with `UnsupportedOnDevice`.  The slabs of a PAR2 block may likewise be 2-way
     `sptensor`s or objects with `.tocoo()`, all of them or none (`aoadmm_par2_slab_upload_coo`)."""
     prec = capi.precision_id(precision)                # an unknown string fails before the engine is touched
     lib = eng.lib

@@ -86,10 +86,13 @@ class Engine:
         return buf.raw
 
     def comm_init_rank(self, uid, rank, world):
+        """Rank `rank` of a `world`-rank RCCL communicator (`aoadmm_comm_init_rank`).  Afterwards `build_model` shards
+        dense CP blocks by rows, and with 'f16' it is a collective whose scale comes from the whole tensor."""
         capi.check(self.lib.aoadmm_comm_init_rank(self.h, uid, int(rank), int(world)))
 
     def comm_init_rank_share(self, uid, rank, world):
-        """Measurement hook: rank `rank` of `world` in every sharding decision, on a ONE-rank RCCL communicator."""
+        """Measurement hook: rank `rank` of `world` in every sharding decision, on a ONE-rank RCCL communicator.  Nothing
+        is learnt from peers: sums are partial, and an 'f16' block takes its scale from this rank's rows and mode-3 slab."""
         capi.check(self.lib.aoadmm_comm_init_rank_share(self.h, uid, int(rank), int(world)))
 
     def comm_rank(self):
@@ -106,7 +109,8 @@ class Engine:
         return {'rccl_version': v.value, 'comm_ranks': n.value, 'librccl': buf.value.decode('utf-8', 'replace')}
 
     def comm_init_local(self, key, rank, world):
-        """Bring-up/test transport: engines driven by threads of this process form group `key` (see aoadmm_hip.h)."""
+        """Bring-up/test transport: engines driven by threads of this process form group `key` (see aoadmm_hip.h).  As on
+        RCCL ranks, an 'f16' `build_model` is a collective here: all ranks of the group must make it together."""
         capi.check(self.lib.aoadmm_comm_init_local(self.h, int(key), int(rank), int(world)))
 
     # ---- data -----------------------------------------------------------------------
@@ -153,7 +157,8 @@ class Engine:
     def tensor_storage_info(self, p):
         """(precision id capi.PREC_*, scale, resident bytes) of tensor p (`aoadmm_tensor_storage_info`): the precision
         its passes stream, the power-of-two scale of an 'f16' block (1.0 otherwise) and the bytes a dense CP block
-        holds on the device now."""
+        holds on the device now.  On a rank of a communicator: the scale common to all ranks (that of the whole tensor)
+        and this rank's own bytes."""
         prec, scale, nbytes = C.c_int(0), C.c_double(0), C.c_int64(0)
         capi.check(self.lib.aoadmm_tensor_storage_info(self.h, int(p), C.byref(prec), C.byref(scale), C.byref(nbytes)))
         return prec.value, scale.value, nbytes.value

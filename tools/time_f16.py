@@ -13,6 +13,11 @@ and per round of --steps outer iterations (host clock around a solve that ends w
   iter_ms            time per outer iteration
   pass_ms, pass_TBs  mean tensor-pass time and algorithmic bytes over it, from aoadmm_kernel_stats(0) with every pass
                      bracketed by events (AOADMM_PASS_EVENT_EVERY=1)
+--as-rank R --of N measures ONE RANK'S SHARE of an N-GPU job instead (bench.py's option of the same name): both engines
+join a one-rank communicator through aoadmm_comm_init_rank_share before the model is built, hold rank R's rows and its
+mode-3 slab, and run every collective without peers.  Such a run is a measurement, not a solve: its sums are partial.
+After the timed rounds one more round per mode runs with the reductions over T timed as well (aoadmm_kernel_stats(2)),
+so that a share whose iteration falls short of the pass ratio shows where the rest of the time goes.
 Raw lines go to --out (JSON lines), a summary to stdout."""
 import argparse
 import copy
@@ -36,8 +41,13 @@ def main():
     ap.add_argument('--steps', type=int, default=10, help='outer iterations per timed round')
     ap.add_argument('--rounds', type=int, default=5, help='timed rounds per mode, alternating')
     ap.add_argument('--gap-iters', type=int, default=25)
+    ap.add_argument('--as-rank', type=int, default=-1, help="measure rank R's share of an N-GPU job (needs --of)")
+    ap.add_argument('--of', type=int, default=0, help='number of ranks of the job whose share is measured')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'f16_time_%s.jsonl' % time.strftime('%Y%m%d_%H%M%S')))
     args = ap.parse_args()
+    share = args.as_rank >= 0
+    if share and not (args.of > 1 and args.as_rank < args.of):
+        raise SystemExit('time_f16.py: --as-rank R needs --of N with 0 <= R < N, N > 1')
     pkg = importlib.import_module('matlab-code_amd')
     N, R = args.size, args.rank
     Z = dict(loss_function=['Frobenius'], model=['CP'], modes=[[1, 2, 3]], size=[N, N, N],
@@ -65,12 +75,15 @@ def main():
     eng, fac = {}, {}
     for m in modes:
         eng[m] = pkg.Engine(0)
+        if share:
+            eng[m].comm_init_rank_share(eng[m].comm_unique_id(), args.as_rank, args.of)
         t0 = time.perf_counter()
         pkg.build_model(eng[m], Z, m)
         eng[m].synchronize()
         up = time.perf_counter() - t0
         prec, scale, nbytes = eng[m].tensor_storage_info(0)
-        emit(kind='storage', mode=m, size=N, rank=R, upload_s=up, precision=prec, scale=scale, resident_bytes=nbytes,
+        emit(kind='storage', mode=m, size=N, rank=R, as_rank=args.as_rank, of=args.of, upload_s=up, precision=prec,
+             scale=scale, resident_bytes=nbytes,
              bytes_per_entry=nbytes / float(N) ** 3)
         pkg.upload_state(eng[m], Z, copy.deepcopy(G0))
     # the factor gap, which is also the warm-up of every kernel the timed rounds use
@@ -101,7 +114,22 @@ def main():
             emit(**row)
     med = {m: {k: float(np.median([r[k] for r in rows[m]])) for k in ('iter_ms', 'pass_ms', 'pass_TBs', 'pass_bytes')}
            for m in modes}
-    emit(kind='summary', size=N, rank=R, median=med, pass_ratio_f16_over_f32=med['f16']['pass_ms'] / med['f32']['pass_ms'],
+    # where an iteration's time goes: passes (class 0) and reductions over T (class 2), every launch timed
+    for m in modes:
+        e = eng[m]
+        e.kernel_stats(2, reset=True)                     # switches the reductions' events on
+        e.kernel_stats(0, reset=True)
+        e.synchronize()
+        t0 = time.perf_counter()
+        pkg.run_solver(e, opts(args.steps), 3)
+        e.synchronize()
+        dt = time.perf_counter() - t0
+        p_ms, p_n = e.kernel_stats(0)[:2]
+        r_ms, r_n = e.kernel_stats(2)[:2]
+        emit(kind='kernel_stats', mode=m, steps=args.steps, iter_ms=dt / args.steps * 1e3, pass_ms_per_iter=p_ms / args.steps,
+             passes=p_n, reduction_ms_per_iter=r_ms / args.steps, reductions=r_n)
+    emit(kind='summary', size=N, rank=R, as_rank=args.as_rank, of=args.of, median=med,
+         pass_ratio_f16_over_f32=med['f16']['pass_ms'] / med['f32']['pass_ms'],
          iter_ratio_f16_over_f32=med['f16']['iter_ms'] / med['f32']['iter_ms'])
     for m in modes:
         eng[m].close()
