@@ -265,8 +265,29 @@ int aoadmm_tensor_synth(aoadmm_ctx* ctx, int p, int rank, uint64_t seed, double 
  * aoadmm_tensor_synth return AOADMM_ERR_INVALID and aoadmm_resident_unfold_gram AOADMM_ERR_UNSUPPORTED
  * (aoadmm_resident_nvecs gives the leading eigenvectors instead);
  * aoadmm_tensor_normsq, aoadmm_resident_mttkrp and aoadmm_solve work as for dense data.  With a communicator
- * every rank holds all nonzeros and computes the complete MTTKRP (no collective for the block). */
+ * every rank holds all nonzeros and computes the complete MTTKRP (no collective for the block): N (4 N + 8) bytes
+ * per coalesced nonzero on every rank, and no rank's MTTKRP gets shorter with more ranks.
+ * aoadmm_tensor_upload_coo_sharded is the form that divides both. */
 int aoadmm_tensor_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* vals);
+/* The same block with its nonzeros SHARDED over the ranks of the communicator.  Arguments and validation are those of
+ * aoadmm_tensor_upload_coo; every rank passes the WHOLE list and all ranks make the call together.  The list is
+ * coalesced as a whole first (duplicates summed before anything is cut: the same model), then with nnz coalesced
+ * nonzeros rank g of `world` keeps the entries [floor(g nnz / world), floor((g + 1) nnz / world)) of EVERY mode's
+ * sorted copy: the same numeric cut applied to each mode's own order.  A copy is sorted by its mode's row, so a rank's
+ * share of mode n is a contiguous row span that overlaps its neighbours in at most the boundary rows, and a row with
+ * many nonzeros is spread over as many ranks as its length asks for (the balance does not depend on skew).  A share
+ * may be empty (nnz < world).  Resident afterwards: N (4 N + 8) bytes per KEPT nonzero; the peak during the call is
+ * that of aoadmm_tensor_upload_coo (the full copies are built, cut and freed; an upload that hands each rank only a
+ * part of the list does not exist).  Without a communicator, or with world = 1, the call IS
+ * aoadmm_tensor_upload_coo, bit for bit.  A multi-device context shards over its engines.
+ *   On a sharded block: aoadmm_tensor_normsq is the all-reduced sum of squares of the mode-0 shares;
+ *   aoadmm_resident_mttkrp and every MTTKRP inside aoadmm_solve are COLLECTIVES (each rank writes its partial sums into
+ *   its row span of a zeroed send buffer of I_n x R doubles, one all-reduce returns the complete result on every rank;
+ *   every rank takes part, with an empty share too; no float atomics, two runs return the same bits);
+ *   aoadmm_resident_nvecs returns AOADMM_ERR_UNSUPPORTED (its fiber lists need all nonzeros); the refusals of a sparse
+ *   block above stay.  A block whose share was cut for another (rank, world) than the context has now answers
+ *   AOADMM_ERR_INVALID ("upload again") to these calls.  The next upload of either kind replaces the block. */
+int aoadmm_tensor_upload_coo_sharded(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* vals);
 /* Z.object{p}{k} of a PARAFAC2 block as sparse matrices, all K slabs in one call: nnz nonzeros, subs column-major
  * nnz x 3, 0-based (i, j within the slab, k); vals nnz doubles.  Duplicates are summed, explicit zeros are allowed,
  * nnz = 0 is valid; a subscript out of range (j >= J_k included) or nnz < 0 is AOADMM_ERR_INVALID and leaves the block
@@ -281,8 +302,10 @@ int aoadmm_par2_slab_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64
 int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out);
 /* How tensor p is stored on the device (each output may be NULL): *precision = the AOADMM_PREC_* its passes stream
  * (AOADMM_PREC_F64 for sparse and PARAFAC2 data), *scale = the power-of-two scale s of an AOADMM_PREC_F16 block (1.0
- * otherwise), *resident_bytes = what a dense CP block holds now: natural-layout array, pass copies, transposed copy and
- * mask (0 for sparse and PARAFAC2 data).  No device work. */
+ * otherwise), *resident_bytes = what a CP block holds now: natural-layout array, pass copies, transposed copy and
+ * mask of a dense block; the per-mode copies of the nonzeros of a sparse block, N (4 N + 8) bytes per nonzero this
+ * rank holds (all of them, or its share of a sharded block; a multi-device context reports rank 0's); 0 for PARAFAC2
+ * data.  No device work. */
 int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes);
 
 /* ---- state (the struct G) ---------------------------------------------- */
@@ -310,7 +333,9 @@ int aoadmm_resident_par2_rhs(aoadmm_ctx* ctx, int p, int tensor_mode, double* ou
  * timed only from the first call with which = 2 on, two more events per reduction); which = 3: the MTTKRPs of
  * sparse blocks (launches = MTTKRPs, each the streaming kernel plus its carry passes; bytes = nonzeros streamed +
  * factor rows gathered + output written; flops = nnz * R * N) and the passes over the nonzeros of PARAFAC2 blocks
- * with sparse slabs (one launch per pass, counted as the MTTKRP of the I x sum(J_k) matrix it is) */
+ * with sparse slabs (one launch per pass, counted as the MTTKRP of the I x sum(J_k) matrix it is).  Of a sharded
+ * sparse block: this rank's share (its nonzeros, and the rows of its span as the output written); the all-reduce is
+ * outside the events */
 int aoadmm_kernel_stats(aoadmm_ctx* ctx, int which, int reset, double* contract_ms, int64_t* contract_launches,
                         double* contract_bytes, double* contract_flops);
 
@@ -345,7 +370,8 @@ int aoadmm_resident_unfold_gram(aoadmm_ctx* ctx, int p, int tensor_mode, int sla
  *   U: I_n x r column-major with leading dimension ldU, columns by descending eigenvalue, each with its entry of
  *   largest magnitude positive (the first such entry on a tie); eigvals (optional): the r eigenvalues.  Not converged
  *   within max_iters is not an error: AOADMM_OK with info->converged = 0 and the last iterate.  Bitwise reproducible
- *   for a given seed.  With a communicator the block is replicated: every rank computes the same bits, no collective. */
+ *   for a given seed.  With a communicator the block is replicated: every rank computes the same bits, no collective
+ *   (a block uploaded with aoadmm_tensor_upload_coo_sharded: AOADMM_ERR_UNSUPPORTED). */
 typedef struct { int oversample; int max_iters; double tol; uint64_t seed; } aoadmm_nvecs_options;
 typedef struct { int iterations; int converged; int block; double residual; int64_t fibers; } aoadmm_nvecs_info;
 int aoadmm_resident_nvecs(aoadmm_ctx* ctx, int p, int tensor_mode, int r, const aoadmm_nvecs_options* opt_or_null,

@@ -39,6 +39,17 @@ def quantize_f16(X):
         _, E = np.frexp(a)
         s = float(np.ldexp(1.0, min(127, max(-126, 15 - int(E)))))
     return (x * np.float32(s)).astype(np.float16), s
+
+
+def coo_share(nnz, rank, world):
+    """(first, end) of rank `rank`'s share of `nnz` coalesced nonzeros under `aoadmm_tensor_upload_coo_sharded`: the
+    entries [floor(rank nnz / world), floor((rank + 1) nnz / world)) of every mode's sorted copy."""
+    nnz, rank, world = int(nnz), int(rank), int(world)
+    if nnz < 0 or world < 1 or not 0 <= rank < world:
+        raise ValueError('coo_share: need nnz >= 0 and 0 <= rank < world, got %d, %d, %d' % (nnz, rank, world))
+    return rank * nnz // world, (rank + 1) * nnz // world
+
+
 (F_FAC, F_CONSTRAINT_FAC, F_CONSTRAINT_DUAL, F_COUPLING_FAC, F_COUPLING_DUAL, F_DELTAB, F_P,
  F_MU_DELTAB) = range(8)
 ALL_SLABS = -1            # AOADMM_ALL_SLABS
@@ -53,7 +64,7 @@ SYMBOLS = [
     'aoadmm_model_begin', 'aoadmm_model_set_mode', 'aoadmm_model_set_mode_slabs', 'aoadmm_model_add_cp',
     'aoadmm_model_add_par2', 'aoadmm_model_set_constraint', 'aoadmm_model_set_coupling',
     'aoadmm_model_set_coupling_type', 'aoadmm_model_set_ridge', 'aoadmm_model_end', 'aoadmm_tensor_upload',
-    'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq', 'aoadmm_tensor_storage_info',
+    'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_tensor_upload_coo_sharded', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq', 'aoadmm_tensor_storage_info',
     'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_resident_par2_rhs', 'aoadmm_kernel_stats',
     'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_resident_nvecs', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
     'aoadmm_op_admm_mode', 'aoadmm_op_par2_b_loop',
@@ -150,6 +161,7 @@ def load_library():
     lib.aoadmm_tensor_upload.argtypes = [vp, C.c_int, dp, C.c_int]
     lib.aoadmm_tensor_upload_rows.argtypes = [vp, C.c_int, dp, i64, i64, C.c_int]
     lib.aoadmm_tensor_upload_coo.argtypes = [vp, C.c_int, i64, C.POINTER(i64), dp]
+    lib.aoadmm_tensor_upload_coo_sharded.argtypes = [vp, C.c_int, i64, C.POINTER(i64), dp]
     lib.aoadmm_par2_slab_upload.argtypes = [vp, C.c_int, C.c_int, dp]
     lib.aoadmm_par2_slab_upload_coo.argtypes = [vp, C.c_int, i64, C.POINTER(i64), dp]
     lib.aoadmm_tensor_mask_upload.argtypes = [vp, C.c_int, C.POINTER(C.c_uint8)]

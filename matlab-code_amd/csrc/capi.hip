@@ -418,6 +418,14 @@ int aoadmm_tensor_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t*
     on_engines(ctx, [&](Engine& e, int) { e.tensor_upload_coo(p, nnz, subs, vals); });   // replicated on every engine
   });
 }
+int aoadmm_tensor_upload_coo_sharded(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* vals) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    AO_REQUIRE(nnz >= 0, "nnz = %lld < 0", (long long)nnz);
+    AO_REQUIRE(nnz == 0 || (subs != nullptr && vals != nullptr), "null subs / vals");
+    on_engines(ctx, [&](Engine& e, int) { e.tensor_upload_coo(p, nnz, subs, vals, true); });   // every engine keeps its share
+  });
+}
 int aoadmm_par2_slab_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* vals) {
   CTX_OR_FAIL(ctx);
   return guarded([&] {
@@ -428,7 +436,8 @@ int aoadmm_par2_slab_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64
 }
 int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes) {
   CTX_OR_FAIL(ctx);
-  // no collective and no device work: rank 0's engine answers for a multi-device context (every rank holds the same form)
+  // no collective and no device work: rank 0's engine answers for a multi-device context (every rank holds the same
+  // form; of a sharded sparse block rank 0's share)
   return guarded([&] { ctx->eng->tensor_storage_info(p, precision, scale, resident_bytes); });
 }
 int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out) {

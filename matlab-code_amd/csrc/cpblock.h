@@ -99,8 +99,10 @@ struct CpBlock {
   // Z.miss{p}: one byte per entry in the layout of X (and of Xt for matrices), 1 = observed
   DevBuf mask, maskT;
   bool has_mask = false;
-  // sparse form of Z.object{p} (aoadmm_tensor_upload_coo): replaces everything above but nd / dims / has_data; every
-  // rank of a communicator holds all nonzeros and computes the complete MTTKRP (no row sharding, no collective)
+  // sparse form of Z.object{p}: replaces everything above but nd / dims / has_data.  aoadmm_tensor_upload_coo: every
+  // rank of a communicator holds all nonzeros and computes the complete MTTKRP (no collective);
+  // aoadmm_tensor_upload_coo_sharded: every rank holds its share of the nonzeros (coo.sharded) and the MTTKRP is an
+  // all-reduce of the shares' partial sums, from the block's per-mode send buffers (CooBlock::send)
   bool sparse = false;
   CooBlock coo;
   // New data has arrived, dense or sparse: no copy, cached contraction or release state of the old data holds.  Frees

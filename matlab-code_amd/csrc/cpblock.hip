@@ -569,9 +569,10 @@ static void mttkrp_nway(const BlockCtx& cx, CpBlock& b, int pos, const FactorRef
   b.cached_mode = -1;
 }
 
-// MTTKRP of a sparse block (sparse.hip): factors gathered through their row-major copy when it is current
+// MTTKRP of a sparse block (sparse.hip): factors gathered through their row-major copy when it is current.
+// span_only: the share of a sharded block, into the rows of its span alone
 static void sparse_mttkrp(const BlockCtx& cx, CpBlock& b, int pos, const FactorRef* facs, int R, double scale, double* out,
-                          int64_t ldOut) {
+                          int64_t ldOut, bool span_only) {
   CooFactor f[kCooMaxModes];
   int k = 0;
   for (int m = 0; m < b.nd; ++m) {
@@ -580,8 +581,39 @@ static void sparse_mttkrp(const BlockCtx& cx, CpBlock& b, int pos, const FactorR
   }
   LaunchTimers& tm = *cx.timers;
   const LaunchTimers::Pair pr = tm.begin(tm.stats[3], tm.profile, cx.stream);
-  coo_mttkrp(b.coo, pos, f, R, scale, out, ldOut, cx.stream);
+  coo_mttkrp(b.coo, pos, f, R, scale, out, ldOut, cx.stream, span_only);
   tm.end(tm.stats[3], pr, cx.stream, coo_mttkrp_bytes(b.coo, pos, R), coo_mttkrp_flops(b.coo, R));
+}
+
+// The send buffer of mode `pos` of a sharded sparse block (dims[pos] x R, leading dimension dims[pos]).  Invariant of
+// every all-reduce from it: the rows outside the share's span are zero.  The span is fixed for the life of the CooBlock
+// (a new upload, a new cut or a new model makes a new block without buffers), coo_mttkrp's span form writes inside the
+// span only, and a buffer made for another R is made and cleared again here.
+static double* sparse_send_buffer(const BlockCtx& cx, CooBlock& c, int pos, int R) {
+  DevBuf& sb = c.send[pos];
+  if (c.send_R[pos] != R || !sb.p) {
+    const size_t need = (size_t)c.dims[pos] * R * sizeof(double);
+    c.send_R[pos] = 0;
+    sb.alloc(need);
+    AO_HIP(hipMemsetAsync(sb.p, 0, need, cx.stream));
+    c.send_R[pos] = R;
+  }
+  return sb.d();
+}
+
+// Sharded sparse block: this rank's partial MTTKRP into its span of the send buffer, all-reduced into `out` (the
+// own-rows pattern of the dense path; neighbouring spans may share their boundary rows, which the sum completes).
+// Every rank comes here for every MTTKRP, with an empty share too.
+static void sparse_mttkrp_sharded(const BlockCtx& cx, CpBlock& b, int pos, const FactorRef* facs, int R, double scale,
+                                  double* out, int64_t ldOut, bool collective) {
+  CooBlock& c = b.coo;
+  AO_REQUIRE(collective, "internal: a sharded sparse block has no MTTKRP outside a collective");
+  AO_REQUIRE(c.cut_rank == cx.rank && c.cut_world == cx.world,
+             "sparse block was cut for rank %d of %d, the engine is now rank %d of %d: upload again", c.cut_rank, c.cut_world,
+             cx.rank, cx.world);
+  double* send = sparse_send_buffer(cx, c, pos, R);
+  sparse_mttkrp(cx, b, pos, facs, R, scale, send, c.dims[pos], true);
+  mttkrp_allreduce(cx, send, out, ldOut, c.dims[pos], R);
 }
 
 void block_mttkrp(const BlockCtx& cx, CpBlock& b, int pos, const FactorRef* facs, int R, double scale, double* out,
@@ -590,8 +622,9 @@ void block_mttkrp(const BlockCtx& cx, CpBlock& b, int pos, const FactorRef* facs
   if (sys_done) *sys_done = false;
   AO_REQUIRE(b.has_data, "tensor has no data");
   AO_REQUIRE(pos >= 0 && pos < b.nd, "mttkrp: mode %d out of range", pos);
-  if (b.sparse) {                  // complete on every rank: no own-rows buffer, no collective, no cache, no rider
-    sparse_mttkrp(cx, b, pos, facs, R, scale, out, ldOut);
+  if (b.sparse) {                  // no cache, no rider; replicated: complete on every rank, no collective
+    if (b.coo.sharded) sparse_mttkrp_sharded(cx, b, pos, facs, R, scale, out, ldOut, collective);
+    else sparse_mttkrp(cx, b, pos, facs, R, scale, out, ldOut, false);
     return;
   }
   const bool sharded = collective && cx.sharded;

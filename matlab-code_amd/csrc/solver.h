@@ -154,7 +154,7 @@ class Engine {
 
   // data
   void tensor_upload(int p, const double* data, int prec, int64_t row0, int64_t local_rows);
-  void tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const double* vals);
+  void tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const double* vals, bool shard = false);
   void tensor_synth(int p, int rank, uint64_t seed, double noise, int prec);
   void par2_slab_upload(int p, int k, const double* Xk);
   void par2_slab_upload_coo(int p, int64_t nnz, const int64_t* subs, const double* vals);
@@ -162,7 +162,8 @@ class Engine {
   void par2_slab_mask_upload(int p, int k, const uint8_t* mask);
   double tensor_normsq(int p);
   // what tensor p keeps on the device: the precision its passes stream, the power-of-two scale of a half block (else 1)
-  // and the bytes of its natural array, pass copies, transposed copy and mask (dense CP blocks; 0 for the others)
+  // and the bytes of its natural array, pass copies, transposed copy and mask (dense CP blocks), of the per-mode copies
+  // of the nonzeros this rank holds (sparse CP blocks); 0 for PARAFAC2 blocks
   void tensor_storage_info(int p, int* precision, double* scale, int64_t* resident_bytes);
 
   // state

@@ -369,6 +369,10 @@ void Engine::tensor_storage_info(int p, int* precision, double* scale, int64_t* 
     if (dense_cp) {
       for (const DevBuf* d : {&b.X.data, &b.Xt.data, &b.copy[0].buf, &b.copy[1].buf, &b.copy[2].buf, &b.mask, &b.maskT})
         if (d->p) n += (int64_t)d->bytes;
+    } else if (!t.par2) {            // the per-mode copies of the nonzeros this rank holds: N (4 N + 8) bytes each
+      for (int m = 0; m < b.coo.nd; ++m)
+        for (const DevBuf* d : {&b.coo.mode[m].row, &b.coo.mode[m].oidx, &b.coo.mode[m].val})
+          if (d->p) n += (int64_t)d->bytes;
     }
     *resident_bytes = n;
   }
@@ -412,8 +416,10 @@ void Engine::tensor_upload(int p, const double* data, int prec, int64_t row0, in
 }
 
 // Z.object{p} as a sptensor / sparse matrix (sparse.h): the block keeps the coalesced nonzeros, one sorted copy per
-// mode, and drops whatever dense form it had.  Replicated on every rank of a communicator.
-void Engine::tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const double* vals) {
+// mode, and drops whatever dense form it had.  Replicated on every rank of a communicator, or with `shard` cut over the
+// ranks (coo_keep_share: the whole list is coalesced first, so the sharded model is the same model; every rank passes
+// the whole list and reaches the same verdict on it).  shard without peers is the replicated upload.
+void Engine::tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const double* vals, bool shard) {
   require_usable();
   AO_REQUIRE(model_done_, "call aoadmm_model_end first");
   AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
@@ -425,6 +431,7 @@ void Engine::tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const do
   AO_HIP(hipSetDevice(device_));
   CooBlock coo;
   coo_build(coo, t.nmodes, dims, nnz, subs, vals, stream_);     // validates before anything of the old form is dropped
+  if (shard && world_ > 1) coo_keep_share(coo, rank_, world_, stream_);
   CpBlock& b = t.blk;
   drop_pass_copies(b);
   b.X.data.release(); b.Xt.data.release();
@@ -471,8 +478,13 @@ double Engine::tensor_normsq(int p) {
       tensor_sumsq(slot, t.p2.sp.coo.mode[0].val.p, AOADMM_PREC_F64, t.p2.sp.coo.nnz, ws.d(), stream_);
     } else if (t.par2) {   // sum_k ||X_k||_F^2  (cmtf_AOADMM.m:145-155)
       tensor_sumsq(slot, t.p2.X.p, AOADMM_PREC_F64, (int64_t)t.p2.I * t.p2.Jtot, ws.d(), stream_);
-    } else if (t.blk.sparse) {     // norm(sptensor)^2 (:132): the coalesced values; every rank holds all of them
-      tensor_sumsq(slot, t.blk.coo.mode[0].val.p, AOADMM_PREC_F64, t.blk.coo.nnz, ws.d(), stream_);
+    } else if (t.blk.sparse) {     // norm(sptensor)^2 (:132): the coalesced values
+      const CooBlock& c = t.blk.coo; // replicated: every rank holds all of them; sharded: the mode-0 shares cover them once
+      AO_REQUIRE(!c.sharded || (c.cut_rank == rank_ && c.cut_world == world_),
+                 "sparse tensor %d was cut for rank %d of %d, the engine is now rank %d of %d: upload again", p, c.cut_rank,
+                 c.cut_world, rank_, world_);
+      tensor_sumsq(slot, c.mode[0].val.p, AOADMM_PREC_F64, c.nnz, ws.d(), stream_);
+      if (c.sharded) allreduce(slot, 1);
     } else if (t.blk.half) {       // sum of q^2 over a pass copy (its padding is zero); the data is q / s
       const CpBlock& b = t.blk;      // copy[2] holds this rank's rows, and s is the same on every rank
       tensor_sumsq(slot, b.copy[2].buf.p, AOADMM_PREC_F16, half_copy_elems(b.copy[2].pad * b.dims[1], b.dims[2]), ws.d(), stream_);
@@ -932,6 +944,8 @@ void Engine::resident_nvecs(int p, int pos, int r, const aoadmm_nvecs_options* o
     AO_REQUIRE(b.has_data, "tensor %d has no data", p);
     if (!b.sparse)
       throw Error(AOADMM_ERR_UNSUPPORTED, fmt("resident nvecs: tensor %d is dense (use aoadmm_resident_unfold_gram)", p));
+    if (b.coo.sharded)
+      throw Error(AOADMM_ERR_UNSUPPORTED, fmt("resident nvecs: the nonzeros of tensor %d are sharded over the ranks (the fiber lists need all of them: upload with aoadmm_tensor_upload_coo)", p));
     coo = &b.coo;
   }
   AO_REQUIRE(coo->nnz >= 1, "resident nvecs: tensor %d has no nonzeros", p);

@@ -19,9 +19,21 @@ struct CooMode {
 struct CooBlock {
   int nd = 0;
   int64_t dims[kCooMaxModes] = {0};
-  int64_t nnz = 0;               // after coalescing
+  int64_t nnz = 0;               // entries of every mode's copy: all coalesced nonzeros, or this rank's share of them
   CooMode mode[kCooMaxModes];
   DevBuf slot_row[2], slot_val[2];   // carries of the chunks that share a row with a neighbour (ping-pong per level)
+  // Sharded over the ranks of a communicator (coo_keep_share): every mode's copy holds the entries
+  // [coo_share_begin(nnz_full, rank, world), coo_share_begin(nnz_full, rank + 1, world)) of that mode's sorted order,
+  // so a rank's part of mode n lies in the rows [span0[n], span1[n]] (span0 = -1: an empty share)
+  bool sharded = false;
+  int cut_rank = 0, cut_world = 1;
+  int64_t nnz_full = 0;          // coalesced nonzeros of the whole tensor
+  int64_t span0[kCooMaxModes] = {0}, span1[kCooMaxModes] = {0};
+  // send[n]: dims[n] x send_R[n] doubles, the sharded MTTKRP of mode n in front of its all-reduce.  Rows outside the
+  // span are zero: cleared when the buffer is made, never written afterwards (the span belongs to the block and a new
+  // upload makes a new block, so no buffer outlives its cut)
+  DevBuf send[kCooMaxModes];
+  int send_R[kCooMaxModes] = {0};
   void clear() { *this = CooBlock(); }
   CooBlock() = default;
   CooBlock(CooBlock&&) = default;
@@ -40,10 +52,19 @@ struct CooFactor {
 void coo_build(CooBlock& b, int nd, const int64_t* dims, int64_t nnz, const int64_t* subs, const double* vals,
                hipStream_t s);
 
+// first entry of rank g's share of nnz sorted entries: floor(g * nnz / world) (nnz < 2^31: the product fits)
+inline int64_t coo_share_begin(int64_t nnz, int g, int world) { return nnz * g / world; }
+// Keeps rank `rank`'s share of every mode's copy in buffers of the share's size (oidx strided by the share's count) and
+// frees the full copies, one mode at a time: N (4 N + 8) bytes per kept nonzero stay resident.  The peak is that of
+// coo_build.  Call once, on a freshly built block.
+void coo_keep_share(CooBlock& b, int rank, int world, hipStream_t s);
+
 // out(:, 0:R-1) (column-major, leading dimension ldOut, dims[pos] rows) = scale * mttkrp of the block for mode pos.
 // f[k] are the factors of the other modes in mode order.  Bitwise reproducible (no atomics).
+// span_only (sharded blocks): clears and writes the rows [span0[pos], span1[pos]] of `out` alone -- this rank's partial
+// sums, complete after the sum over the ranks; an empty share touches nothing.
 void coo_mttkrp(CooBlock& b, int pos, const CooFactor* f, int R, double scale, double* out, int64_t ldOut,
-                hipStream_t s);
+                hipStream_t s, bool span_only = false);
 
 // A list of n entries sorted by `key` (int32, 0 <= key < rows); entry e carries the index gidx[e] and the value val[e]
 struct CooList {
@@ -67,7 +88,8 @@ void coo_sort_linear(CooSortWork& w, const int* idx, int64_t n, int nd, const in
 // of every sorted entry); returns the number of runs (one host read)
 int64_t coo_runs_scan(CooSortWork& w, DevBuf& head, DevBuf& seg, const int* idx, int64_t n, int nd, hipStream_t s);
 
-// algorithmic bytes (nonzeros streamed + factor rows gathered + output written) and flops of one coo_mttkrp
+// algorithmic bytes (nonzeros streamed + factor rows gathered + output written: all rows, or the span of a sharded
+// block) and flops of one coo_mttkrp, from the entries this rank holds
 double coo_mttkrp_bytes(const CooBlock& b, int pos, int R);
 double coo_mttkrp_flops(const CooBlock& b, int R);
 

@@ -164,7 +164,7 @@ void coo_build(CooBlock& b, int nd, const int64_t* dims, int64_t nnz, const int6
   nb.nd = nd;
   for (int m = 0; m < nd; ++m) nb.dims[m] = dims[m];
   if (nnz == 0) {
-    nb.nnz = 0;
+    nb.nnz = nb.nnz_full = 0;
     b = std::move(nb);
     return;
   }
@@ -191,7 +191,7 @@ void coo_build(CooBlock& b, int nd, const int64_t* dims, int64_t nnz, const int6
   // thread walks a long run alone however many copies of one subscript the input holds
   carry_passes(seg.as<int>(), vs, nnz, 1, 1.0, cval.d(), 1, nc, crow, cvals, 0, s);
   idx.release(); val.release(); keyA.release(); keyB.release(); head.release(); seg.release();
-  nb.nnz = nc;
+  nb.nnz = nb.nnz_full = nc;
   // one copy per mode, stably sorted by that mode's index (32-bit keys)
   iota_k<<<blocks_for(nc), 256, 0, s>>>(permA.as<int>(), nc);
   AO_KERNEL_CHECK();
@@ -208,6 +208,39 @@ void coo_build(CooBlock& b, int nd, const int64_t* dims, int64_t nnz, const int6
   }
   AO_HIP(hipStreamSynchronize(s));                   // the locals above are freed on return
   b = std::move(nb);
+}
+
+void coo_keep_share(CooBlock& b, int rank, int world, hipStream_t s) {
+  AO_REQUIRE(world >= 1 && rank >= 0 && rank < world, "sparse block: bad rank/world %d/%d", rank, world);
+  AO_REQUIRE(!b.sharded && b.nnz == b.nnz_full, "internal: coo_keep_share on a block that was cut before");
+  const int64_t full = b.nnz_full;
+  const int64_t lo = coo_share_begin(full, rank, world), hi = coo_share_begin(full, rank + 1, world), cnt = hi - lo;
+  const int no = b.nd - 1;
+  for (int n = 0; n < b.nd; ++n) {
+    CooMode& cm = b.mode[n];
+    CooMode keep;                                      // stays without buffers for an empty share
+    b.span0[n] = b.span1[n] = -1;
+    if (cnt > 0) {
+      keep.row.alloc((size_t)cnt * sizeof(int));
+      keep.oidx.alloc((size_t)no * cnt * sizeof(int));
+      keep.val.alloc((size_t)cnt * sizeof(double));
+      AO_HIP(hipMemcpyAsync(keep.row.p, cm.row.as<int>() + lo, (size_t)cnt * sizeof(int), hipMemcpyDeviceToDevice, s));
+      for (int k = 0; k < no; ++k)
+        AO_HIP(hipMemcpyAsync(keep.oidx.as<int>() + (size_t)k * cnt, cm.oidx.as<int>() + (size_t)k * full + lo,
+                              (size_t)cnt * sizeof(int), hipMemcpyDeviceToDevice, s));
+      AO_HIP(hipMemcpyAsync(keep.val.p, cm.val.d() + lo, (size_t)cnt * sizeof(double), hipMemcpyDeviceToDevice, s));
+      int ends[2] = {-1, -1};
+      AO_HIP(hipMemcpyAsync(&ends[0], cm.row.as<int>() + lo, sizeof(int), hipMemcpyDeviceToHost, s));
+      AO_HIP(hipMemcpyAsync(&ends[1], cm.row.as<int>() + hi - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+      AO_HIP(hipStreamSynchronize(s));                 // the copies are done before the full arrays go
+      AO_REQUIRE(ends[0] >= 0 && ends[0] <= ends[1] && ends[1] < b.dims[n], "internal: mode %d of a sparse block is not sorted by row", n);
+      b.span0[n] = ends[0]; b.span1[n] = ends[1];
+    }
+    cm = std::move(keep);                              // frees this mode's full copy
+  }
+  for (int i = 0; i < 2; ++i) { b.slot_row[i].release(); b.slot_val[i].release(); }   // sized for the full list by the build
+  b.nnz = cnt;
+  b.sharded = true; b.cut_rank = rank; b.cut_world = world;
 }
 
 // ---------------------------------------------------------------------------
@@ -425,13 +458,19 @@ static void run_list(CooArgs a, DevBuf* slot_row, DevBuf* slot_val, hipStream_t 
 }
 
 void coo_mttkrp(CooBlock& b, int pos, const CooFactor* f, int R, double scale, double* out, int64_t ldOut,
-                hipStream_t s) {
+                hipStream_t s, bool span_only) {
   AO_REQUIRE(pos >= 0 && pos < b.nd, "sparse mttkrp: mode %d out of range", pos);
   AO_REQUIRE(R >= 1 && R <= kMaxRank, "sparse mttkrp: rank %d outside 1..%d", R, kMaxRank);
   const int64_t rows = b.dims[pos];
   AO_REQUIRE(ldOut >= rows, "sparse mttkrp: ldOut %lld < %lld rows", (long long)ldOut, (long long)rows);
-  // rows without nonzeros are exact zeros; every other row is stored exactly once below
-  AO_HIP(hipMemset2DAsync(out, (size_t)ldOut * sizeof(double), 0, (size_t)rows * sizeof(double), (size_t)R, s));
+  AO_REQUIRE(!span_only || b.sharded, "internal: span form of the sparse mttkrp on a block that is not sharded");
+  if (span_only && b.nnz == 0) return;
+  // rows without nonzeros are exact zeros; every other row is stored exactly once below (every entry of a share has
+  // its row inside the share's span)
+  const int64_t r0 = span_only ? b.span0[pos] : 0, nr = span_only ? b.span1[pos] - b.span0[pos] + 1 : rows;
+  AO_REQUIRE(r0 >= 0 && nr >= 1 && r0 + nr <= rows, "internal: span [%lld, %lld] of mode %d outside its %lld rows", (long long)r0,
+             (long long)(r0 + nr - 1), pos, (long long)rows);
+  AO_HIP(hipMemset2DAsync(out + r0, (size_t)ldOut * sizeof(double), 0, (size_t)nr * sizeof(double), (size_t)R, s));
   if (b.nnz == 0) return;
   const CooMode& cm = b.mode[pos];
   CooArgs a;
@@ -457,7 +496,8 @@ void coo_list_pass(const CooList& l, const double* src, int R, double* out, DevB
 
 double coo_mttkrp_bytes(const CooBlock& b, int pos, int R) {
   const double nz = (double)b.nnz, no = (double)(b.nd - 1);
-  return nz * (4.0 + 4.0 * no + 8.0) + nz * no * R * 8.0 + (double)b.dims[pos] * R * 8.0;
+  const double rows = !b.sharded ? (double)b.dims[pos] : b.nnz == 0 ? 0.0 : (double)(b.span1[pos] - b.span0[pos] + 1);
+  return nz * (4.0 + 4.0 * no + 8.0) + nz * no * R * 8.0 + rows * R * 8.0;
 }
 
 double coo_mttkrp_flops(const CooBlock& b, int R) { return (double)b.nnz * R * b.nd; }

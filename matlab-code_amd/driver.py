@@ -329,7 +329,7 @@ def _make_options(alg_options):
     return o
 
 
-def build_model(eng, Z, precision='f64'):
+def build_model(eng, Z, precision='f64', sparse_sharding=False):
     """Describe the struct Z to the engine and upload Z.object (cmtf_AOADMM.m:23-41,124-156).
 
     Z.object{p} of a CP block may be dense, an `sptensor`, or (2-way blocks) any object with `.tocoo()` such as a
@@ -341,7 +341,11 @@ def build_model(eng, Z, precision='f64'):
     whole array, keeps its rows (and its mode-3 slab) as fp16 and gets the scale of the WHOLE tensor; a non-finite entry
     anywhere raises `AoadmmError` (ERR_INVALID) on every rank.  A multi-device engine (`Engine([0, 1, ...])`) answers 'f16'
     with `UnsupportedOnDevice`.  The slabs of a PAR2 block may likewise be 2-way
-    `sptensor`s or objects with `.tocoo()`, all of them or none (`aoadmm_par2_slab_upload_coo`)."""
+    `sptensor`s or objects with `.tocoo()`, all of them or none (`aoadmm_par2_slab_upload_coo`).
+    sparse_sharding: sparse CP blocks go up through `aoadmm_tensor_upload_coo_sharded`, so that every rank of the
+    engine's communicator (or every engine of a multi-device one) keeps its share of the nonzeros and the block's
+    MTTKRPs become all-reduces; every rank calls `build_model` with the same Z.  PAR2 blocks with sparse slabs stay
+    replicated."""
     prec = capi.precision_id(precision)                # an unknown string fails before the engine is touched
     lib = eng.lib
     nb_modes = len(Z['size'])
@@ -422,7 +426,10 @@ def build_model(eng, Z, precision='f64'):
                     raise ValueError('Z.object{%d} has size %s, Z.size says %s' % (p + 1, tuple(shape), [Z['size'][m] for m in md]))
                 if miss[p] is not None:                                              # cmtf_AOADMM.m:77-79
                     raise ValueError('Missing data (Z.miss) not supported for sptensor objects. Convert to tensor first.')
-                eng.upload_coo(p, subs, vals)
+                if sparse_sharding:
+                    eng.upload_coo(p, subs, vals, sharded=True)
+                else:
+                    eng.upload_coo(p, subs, vals)
                 continue
             if isinstance(obj, dict) and obj.get('synthetic'):
                 capi.check(lib.aoadmm_tensor_synth(eng.h, p, int(obj['rank']), int(obj['seed']), float(obj['noise']), prec))
@@ -652,7 +659,9 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
                 if jk < ranks[md[0]]:
                     raise ValueError('Number of components for PARAFAC2 is larger than size of slice %d of data tensor %d.' % (k + 1, p + 1))
     Z['_ranks'] = ranks
-    build_model(eng, Z, precision)
+    # alg_options['hip']['sparse_sharding'] (default 0: replicated): sparse CP blocks sharded over the ranks
+    hip = alg_options.get('hip', {}) if isinstance(alg_options, dict) else {}
+    build_model(eng, Z, precision, sparse_sharding=bool(int(hip.get('sparse_sharding', 0))))
     upload_state(eng, Z, G)
     out = run_solver(eng, alg_options, nb_modes,
                      has_missing=Z.get('miss') is not None and any(m is not None for m in Z['miss']))

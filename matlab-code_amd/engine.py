@@ -114,16 +114,19 @@ class Engine:
         capi.check(self.lib.aoadmm_comm_init_local(self.h, int(key), int(rank), int(world)))
 
     # ---- data -----------------------------------------------------------------------
-    def upload_coo(self, p, subs, vals):
+    def upload_coo(self, p, subs, vals, sharded=False):
         """Z.object{p} of a CP block as COO nonzeros (`aoadmm_tensor_upload_coo`): subs nnz x N, 0-based; vals nnz.
-        Duplicates are summed on the device; the sizes are those of the model."""
+        Duplicates are summed on the device; the sizes are those of the model.  sharded
+        (`aoadmm_tensor_upload_coo_sharded`): every rank of the communicator makes the call with the whole list and keeps
+        its share of the coalesced nonzeros (`capi.coo_share`); the block's MTTKRPs are collectives afterwards.  Without
+        a communicator it is the plain upload."""
         subs = np.asarray(subs, dtype=np.int64)
         vals = np.ascontiguousarray(np.asarray(vals, dtype=np.float64).reshape(-1))
         if subs.ndim != 2 or subs.shape[0] != vals.shape[0]:
             raise ValueError('upload_coo: subs must be nnz x N with nnz = len(vals)')
         subs = np.asfortranarray(subs)                # column-major nnz x N (the layout of sptensor.subs)
-        capi.check(self.lib.aoadmm_tensor_upload_coo(self.h, int(p), int(vals.shape[0]),
-                                                     subs.ctypes.data_as(C.POINTER(C.c_int64)), capi.dptr(vals)))
+        upload = self.lib.aoadmm_tensor_upload_coo_sharded if sharded else self.lib.aoadmm_tensor_upload_coo
+        capi.check(upload(self.h, int(p), int(vals.shape[0]), subs.ctypes.data_as(C.POINTER(C.c_int64)), capi.dptr(vals)))
 
     def upload_par2_coo(self, p, subs, vals):
         """The slabs of a PARAFAC2 block as COO nonzeros (`aoadmm_par2_slab_upload_coo`): subs nnz x 3, 0-based
@@ -156,16 +159,17 @@ class Engine:
 
     def tensor_storage_info(self, p):
         """(precision id capi.PREC_*, scale, resident bytes) of tensor p (`aoadmm_tensor_storage_info`): the precision
-        its passes stream, the power-of-two scale of an 'f16' block (1.0 otherwise) and the bytes a dense CP block
-        holds on the device now.  On a rank of a communicator: the scale common to all ranks (that of the whole tensor)
-        and this rank's own bytes."""
+        its passes stream, the power-of-two scale of an 'f16' block (1.0 otherwise) and the bytes a CP block holds on
+        the device now (a sparse block: N (4 N + 8) per nonzero held).  On a rank of a communicator: the scale common to
+        all ranks (that of the whole tensor) and this rank's own bytes."""
         prec, scale, nbytes = C.c_int(0), C.c_double(0), C.c_int64(0)
         capi.check(self.lib.aoadmm_tensor_storage_info(self.h, int(p), C.byref(prec), C.byref(scale), C.byref(nbytes)))
         return prec.value, scale.value, nbytes.value
 
     def kernel_stats(self, which, reset=False):
         """(ms, launches, bytes, flops) of a kernel class since the last reset (`aoadmm_kernel_stats`); which = 3:
-        MTTKRPs of sparse blocks and passes over the nonzeros of PARAFAC2 blocks with sparse slabs."""
+        MTTKRPs of sparse blocks (of a sharded block: this rank's share) and passes over the nonzeros of PARAFAC2
+        blocks with sparse slabs."""
         ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         capi.check(self.lib.aoadmm_kernel_stats(self.h, int(which), int(bool(reset)), C.byref(ms), C.byref(n),
                                                 C.byref(by), C.byref(fl)))

@@ -143,7 +143,7 @@ void read_sparse(int p, const mxArray* obj, int N, std::vector<int64_t>& subs, s
   }
 }
 
-void upload_sparse(int p, const mxArray* obj, const mxArray* sz, const std::vector<int>& md) {
+void upload_sparse(int p, const mxArray* obj, const mxArray* sz, const std::vector<int>& md, bool sharded) {
   const int N = (int)md.size();
   std::vector<int64_t> subs;
   std::vector<double> vals;
@@ -152,7 +152,9 @@ void upload_sparse(int p, const mxArray* obj, const mxArray* sz, const std::vect
   bool same = (int)shape.size() == N;
   for (int i = 0; same && i < N; ++i) same = shape[i] == mxGetScalar(mxGetCell(sz, md[i]));
   if (!same) mexErrMsgIdAndTxt("cmtf:hip:invalid", "Z.object{%d}: size does not match Z.size of its modes", p + 1);
-  check(aoadmm_tensor_upload_coo(g_ctx, p, (int64_t)vals.size(), subs.data(), vals.data()));
+  // options.hip.sparse_sharding: the engines of a multi-device context (options.hip.devices) keep one share each
+  check((sharded ? aoadmm_tensor_upload_coo_sharded : aoadmm_tensor_upload_coo)(g_ctx, p, (int64_t)vals.size(), subs.data(),
+                                                                                vals.data()));
 }
 
 void put_state(int field_id, int index, int slab, const mxArray* a) {
@@ -281,7 +283,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   // aoadmm_create_multi, one engine + host thread per device inside the library, RCCL between them)
   std::vector<int> devices(1, 0);
   int precision = AOADMM_PREC_F64;
+  bool sparse_sharding = false;                      // options.hip.sparse_sharding (default 0: sparse CP blocks replicated)
   if (const mxArray* hip = field(opt, "hip", false)) {
+    if (const mxArray* f = field(hip, "sparse_sharding", false)) sparse_sharding = mxGetScalar(f) != 0;
     if (const mxArray* d = field(hip, "device", false)) devices.assign(1, (int)mxGetScalar(d));
     if (const mxArray* d = field(hip, "devices", false)) {
       devices.clear();
@@ -438,7 +442,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       const mxArray* mp = mxGetCell(modes, p);
       std::vector<int> md(mxGetNumberOfElements(mp));
       for (size_t i = 0; i < md.size(); ++i) md[i] = (int)mxGetDoubles(mp)[i] - 1;
-      upload_sparse(p, obj, sz, md);                     // values stay fp64 whatever options.hip.precision says
+      upload_sparse(p, obj, sz, md, sparse_sharding);    // values stay fp64 whatever options.hip.precision says
     } else {
       // 'f16': dense 3-way blocks without Z.miss are stored fp16 (AOADMM_PREC_F16), every other dense block fp32
       int prec_p = precision;

@@ -3,6 +3,7 @@ data on the same GPU.
 
     python3 tools/time_sparse.py [--dims 1000000,100000,10000] [--nnz 100000000] [--R 20] [--skew] [--reps 5]
     python3 tools/time_sparse.py --nvecs [--nvecs-iters 20] [--host-gram] ...
+    python3 tools/time_sparse.py --as-rank 0 --of 8 [--skew] ...
 
 Prints one JSON line per (layout, mode) and a summary line.  Layouts: 'colmajor' gathers from the column-major factors
 (what aoadmm_resident_mttkrp sees before any solve), 'rowmajor' after one outer iteration, when the Gram kernel has left
@@ -16,6 +17,15 @@ pass over the nonzeros (HIP events, aoadmm_kernel_stats(3); an iteration runs tw
 its dense part (difference of a run of --nvecs-iters iterations and a run of one) and of the list build (what is left
 of the one-iteration run), the iterations run and whether the tolerance was reached within --nvecs-iters.
 --host-gram adds the wall time of the host path (sptensor.unfold_gram + eigh) for modes of at most 16384 rows.
+--as-rank R --of N times one rank's share of a block sharded over N ranks (aoadmm_tensor_upload_coo_sharded) next to the
+replicated block, in one process: the replicated upload and its per-mode MTTKRP first (row-major gathers, after one outer
+iteration) on one engine, and on a second engine aoadmm_comm_init_rank_share(R, N), the sharded upload of the same list and
+the same factors; the MTTKRPs of the two engines alternate.  Per mode: the median (and min, max) over --reps of both kernel
+times (HIP events around the MTTKRP kernels, aoadmm_kernel_stats(3)), the ratio of the medians next to 1/N, the share's
+nonzeros and row span.  --of takes a list (2,4,8); R is taken modulo each N, so --as-rank -1 is the last rank.  The
+communicator has ONE rank: `allreduce_1rank_ms` is what is left of aoadmm_resident_mttkrp's own events after the
+kernels, i.e. a one-rank ncclAllReduce of I_n x R doubles on one GPU.  It says nothing about the all-reduce between
+GPUs, which this tool cannot time.
 """
 from __future__ import annotations
 
@@ -49,6 +59,8 @@ def main():
     ap.add_argument('--nvecs', action='store_true')
     ap.add_argument('--nvecs-iters', type=int, default=20)
     ap.add_argument('--host-gram', action='store_true')
+    ap.add_argument('--as-rank', type=int, default=None)
+    ap.add_argument('--of', default=None)
     a = ap.parse_args()
     if not a.no_torch:
         # torch (and the HIP runtime it ships) first, as bench.py does: loaded after the library, the process aborted in
@@ -57,7 +69,9 @@ def main():
         torch.cuda.init()
     dims = [int(float(v)) for v in a.dims.split(',')]
     N, R, nnz = len(dims), a.R, int(a.nnz)
-    if a.nvecs:
+    if (a.as_rank is None) != (a.of is None):
+        ap.error('--as-rank and --of go together')
+    if a.nvecs or a.of is not None:
         a.no_torch = True
     rng = np.random.default_rng(a.seed)
     t0 = time.time()
@@ -71,7 +85,7 @@ def main():
     t_gen = time.time() - t0
     eng = pkg.Engine(0)
     try:
-        (run_nvecs if a.nvecs else run)(a, eng, dims, N, R, nnz, subs, vals, t_gen)
+        (run_nvecs if a.nvecs else run_share if a.of is not None else run)(a, eng, dims, N, R, nnz, subs, vals, t_gen)
     finally:
         eng.close()
 
@@ -125,6 +139,86 @@ def run_nvecs(a, eng, dims, N, R, nnz, subs, vals, t_gen):
             w, V = np.linalg.eigh(sp.unfold_gram(subs, vals, dims, n))
             r['host_gram_ms'] = round((time.time() - t0) * 1e3, 1)
         print(json.dumps(r), flush=True)
+
+
+def run_share(a, eng, dims, N, R, nnz, subs, vals, t_gen):
+    lib = eng.lib
+    worlds = [int(v) for v in a.of.split(',')]
+    o = capi.Options()
+    o.MaxOuterIters, o.MaxInnerIters, o.use_dimtree = 1, 1, 1
+
+    def prepare(e):
+        """The replicated block, the same factors on every engine, and one outer iteration (unconstrained, no
+        couplings; deterministic) so that the Gram kernels leave the row-major factor copies behind."""
+        rng = np.random.default_rng(a.seed + 1)
+        h = e.h
+        capi.check(lib.aoadmm_model_begin(h, N, 1, 0))
+        for m, s in enumerate(dims):
+            capi.check(lib.aoadmm_model_set_mode(h, m, s, R))
+        capi.check(lib.aoadmm_model_add_cp(h, 0, N, (C.c_int * N)(*range(N)), 1.0))
+        for m in range(N):
+            capi.check(lib.aoadmm_model_set_coupling(h, m, -1, None, 0, 0, None, 0, 0))
+        capi.check(lib.aoadmm_model_end(h))
+        t0 = time.time()
+        e.upload_coo(0, subs, vals)
+        e.synchronize()
+        t_up = time.time() - t0
+        for m in range(N):
+            Um = np.asfortranarray(rng.random((dims[m], R)))
+            capi.check(lib.aoadmm_state_set(h, capi.F_FAC, m, 0, capi.dptr(Um), dims[m], R))
+        res = capi.Result()
+        capi.check(lib.aoadmm_solve(h, C.byref(o), C.byref(res)))
+        return t_up
+
+    def once(e, n):
+        """(kernel ms, ms of aoadmm_resident_mttkrp's own events, algorithmic bytes) of one MTTKRP of mode n"""
+        ms = C.c_float(0)
+        e.kernel_stats(3, reset=True)
+        capi.check(lib.aoadmm_resident_mttkrp(e.h, 0, n, None, C.byref(ms)))
+        kms, launches, by, _ = e.kernel_stats(3, reset=True)
+        assert launches == 1
+        return kms, ms.value, by
+
+    share_eng = pkg.Engine(0)                 # the replicated block stays on `eng`, the share goes here: same process
+    try:
+        t_up = prepare(eng)
+        prepare(share_eng)
+        full_bytes = eng.tensor_storage_info(0)[2]
+        nnz_c = full_bytes // (N * (4 * N + 8))
+        print(json.dumps({'what': 'setup', 'dims': dims, 'nnz_given': nnz, 'nnz_coalesced': int(nnz_c), 'R': R,
+                          'skew': a.skew, 'reps': a.reps, 'gen_s': round(t_gen, 2), 'upload_s': round(t_up, 2),
+                          'resident_bytes': int(full_bytes)}), flush=True)
+        for world in worlds:
+            rank = a.as_rank % world
+            capi.check(lib.aoadmm_comm_init_rank_share(share_eng.h, share_eng.comm_unique_id(), rank, world))
+            t0 = time.time()
+            share_eng.upload_coo(0, subs, vals, sharded=True)
+            share_eng.synchronize()
+            t_cut = time.time() - t0
+            share_bytes = share_eng.tensor_storage_info(0)[2]
+            lo, hi = capi.coo_share(nnz_c, rank, world)
+            assert share_bytes == N * (4 * N + 8) * (hi - lo), (share_bytes, lo, hi)
+            for n in range(N):
+                once(eng, n), once(share_eng, n)                             # warm-up
+                rep, sh = [], []
+                for _ in range(a.reps):                                      # alternating, same process, same factors
+                    rep.append(once(eng, n))
+                    sh.append(once(share_eng, n))
+                rk, sk = [v[0] for v in rep], [v[0] for v in sh]
+                # output rows of the span: what is left of the algorithmic bytes after the nonzeros and the gathers
+                span_rows = (sh[0][2] - (hi - lo) * (4 * N + 8 + (N - 1) * R * 8)) / (R * 8)
+                print(json.dumps({
+                    'what': 'share', 'as_rank': rank, 'of': world, 'skew': a.skew, 'mode': n + 1, 'reps': a.reps,
+                    'share_nnz': int(hi - lo), 'span_rows': int(round(span_rows)), 'rows': dims[n],
+                    'share_ms': round(float(np.median(sk)), 4), 'share_ms_min_max': [round(min(sk), 4), round(max(sk), 4)],
+                    'replicated_ms': round(float(np.median(rk)), 4),
+                    'replicated_ms_min_max': [round(min(rk), 4), round(max(rk), 4)],
+                    'ratio': round(float(np.median(sk)) / float(np.median(rk)), 4), 'one_over_N': round(1.0 / world, 4),
+                    'allreduce_1rank_ms': round(float(np.median([v[1] - v[0] for v in sh])), 4),
+                    'allreduce_MB': round(dims[n] * R * 8 / 1e6, 2), 'upload_s': round(t_cut, 2),
+                    'resident_bytes': int(share_bytes)}), flush=True)
+    finally:
+        share_eng.close()
 
 
 def run(a, eng, dims, N, R, nnz, subs, vals, t_gen):
