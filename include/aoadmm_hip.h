@@ -437,6 +437,32 @@ int aoadmm_op_par2_b_loop(aoadmm_ctx* ctx, int K, const int64_t* rows_k, int R, 
                           int n_params, int max_inner, const double* tol, double* P, double* mu_DeltaB,
                           double* DeltaB, double* Z, double* muZ, double* B, double* rho, double* L, double* GB,
                           int* inner_iters, double* res, int* path);
+/* Form of the coupled ADMM loop (cmtf_fun_AOADMM.m:625-1075; reported by aoadmm_op_coupled_loop).  The library picks
+ * it from the coupling type, the number of coupled modes, the rows and columns of Delta, the ranks and the constraints. */
+enum {
+  AOADMM_CPATH_REGS = 0,          /* types 0/4, whole loop in one workgroup, a row per thread in registers */
+  AOADMM_CPATH_WG = 1,            /* types 0/4, whole loop in one workgroup through LDS / global memory */
+  AOADMM_CPATH_ROWSTEPS = 2,      /* types 0/4, row kernels launched per step */
+  AOADMM_CPATH_GENERIC = 3        /* any type: images, small products and solves launched per step */
+};
+/* The inner loop of coupling `coupling` of the current model as aoadmm_solve runs it once the MTTKRPs of its modes are
+ * there (cmtf_fun_AOADMM.m:253-404 with ADMM_coupled :625-1075).  The model is declared with aoadmm_model_*; no tensor
+ * data is needed.  A[j] (rows_j x R_j) is the MTTKRP and C[j] (R_j x R_j) the Hadamard product of the other modes' Gram
+ * matrices, block weight applied, of the coupling's j-th mode (modes in ascending order).  Per mode rho = trace(C)/R and
+ * the system matrix C [+ Z.ridge] + rho/2*(I, twice if constrained: types 0, 3, 4 | H*H' + I if constrained: type 2)
+ * with its Cholesky factor, or its eigenvectors for the Sylvester solve (types 1, 5), are built on the device;
+ * AOADMM_ERR_NOT_PD when a factorisation fails.  The state is read from and left in the context (aoadmm_state_set /
+ * aoadmm_state_get: FAC, CONSTRAINT_FAC, CONSTRAINT_DUAL, COUPLING_DUAL of the modes, COUPLING_FAC of the coupling).
+ * tol = the four inner tolerances {pr_coupl, pr_constr, du_coupl, du_constr}.  Returned (each may be NULL): the inner
+ * iteration count; res[0..3] = the four residual means of the last iteration in the order of tol; rho[j]; L[j] and
+ * gram[j] = fac'*fac (arrays of pointers, R_j x R_j each); slots[8*j..8*j+7] = the squared norms behind the residuals
+ * of mode j {|fac-Z|, |fac|, |mu|, |Z-Zold|, |Tf(C)-Sd(Delta)|, |mu_Delta|, |Sd(dDelta)|, |denominator|}; path[0] =
+ * AOADMM_CPATH_*, path[1] = rank class of the row kernels (4, 8 or 16; 0 with AOADMM_CPATH_GENERIC).
+ * AOADMM_ERR_UNSUPPORTED for a coupling that holds a mode of a PARAFAC2 block (its systems come from the block's slabs)
+ * and on a context that belongs to a communicator or drives several devices. */
+int aoadmm_op_coupled_loop(aoadmm_ctx* ctx, int coupling, const double* const* A, const double* const* C, int max_inner,
+                           const double* tol, int* inner_iters, double* res, double* rho, double* const* L,
+                           double* const* gram, double* slots, int* path);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,7 @@ def coo_share(nnz, rank, world):
  F_MU_DELTAB) = range(8)
 ALL_SLABS = -1            # AOADMM_ALL_SLABS
 (PATH_WG, PATH_MFMA, PATH_ROWS_FUSED, PATH_ROWS_COLPROX, PATH_ROWS_TV, PATH_ROWL) = range(6)   # AOADMM_PATH_*
+(CPATH_REGS, CPATH_WG, CPATH_ROWSTEPS, CPATH_GENERIC) = range(4)   # AOADMM_CPATH_*
 (P2SLAB_REGS1, P2SLAB_REGS2, P2SLAB_REGS4, P2SLAB_LDS4, P2SLAB_LDS8, P2SLAB_LDS16, P2SLAB_LDS64) = range(7)   # AOADMM_P2SLAB_*
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double)   # aoadmm_progress_fn
 
@@ -67,7 +68,7 @@ SYMBOLS = [
     'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_tensor_upload_coo_sharded', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq', 'aoadmm_tensor_storage_info',
     'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_resident_par2_rhs', 'aoadmm_kernel_stats',
     'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_resident_nvecs', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
-    'aoadmm_op_admm_mode', 'aoadmm_op_par2_b_loop',
+    'aoadmm_op_admm_mode', 'aoadmm_op_par2_b_loop', 'aoadmm_op_coupled_loop',
 ]
 
 
@@ -190,6 +191,8 @@ def load_library():
     ip = C.POINTER(C.c_int)
     lib.aoadmm_op_par2_b_loop.argtypes = [vp, C.c_int, C.POINTER(i64), C.c_int, dp, dp, dp, C.c_double, C.c_double,
                                           C.c_int, dp, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip, dp, ip]
+    dpp = C.POINTER(dp)
+    lib.aoadmm_op_coupled_loop.argtypes = [vp, C.c_int, dpp, dpp, C.c_int, dp, ip, dp, dp, dpp, dpp, dp, ip]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name != 'aoadmm_last_error':

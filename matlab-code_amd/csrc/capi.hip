@@ -844,4 +844,16 @@ int aoadmm_op_par2_b_loop(aoadmm_ctx* ctx, int K, const int64_t* rows_k, int R, 
   });
 }
 
+// The coupled loop of one coupling of the declared model as Engine::outer_updates runs it behind the MTTKRPs
+// (Engine::coupled_loop_op: the solver's own system build, coupled_admm and Gram matrices).
+int aoadmm_op_coupled_loop(aoadmm_ctx* ctx, int coupling, const double* const* A, const double* const* C, int max_inner,
+                           const double* tol, int* inner_iters, double* res, double* rho, double* const* L,
+                           double* const* gram, double* slots, int* path) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    if (ctx->multi) throw Error(AOADMM_ERR_UNSUPPORTED, "aoadmm_op_coupled_loop runs on a single-device context");
+    ctx->eng->coupled_loop_op(coupling, A, C, max_inner, tol, inner_iters, res, rho, L, gram, slots, path);
+  });
+}
+
 }  // extern "C"

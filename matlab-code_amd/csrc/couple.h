@@ -13,9 +13,16 @@ namespace aoadmm {
 // workgroup: one row per thread with the state in registers (couple_loop_wg_regs_k, which opens the loop and forms
 // rho_j / sum rho itself) or the LDS form (couple_loop_wg_k).  The others launch row kernels per step; everything
 // else takes the generic loop.
-enum class CouplePath { Regs, Wg, RowSteps, Generic };
+// The values are those of AOADMM_CPATH_* (aoadmm_op_coupled_loop reports them).
+enum class CouplePath {
+  Regs = AOADMM_CPATH_REGS, Wg = AOADMM_CPATH_WG, RowSteps = AOADMM_CPATH_ROWSTEPS, Generic = AOADMM_CPATH_GENERIC
+};
 // `rmax`: largest rank, cols(Delta) included; `local_prox`: every constrained mode's prox runs inside the loop kernels
 CouplePath couple_path(int type, int n_modes, int64_t rows, int rmax, bool any_par2_c, bool local_prox);
+// The row kernels are instantiated for ranks (and cols(Delta)) up to 4, 8 and 16: the class of `rmax` <= 16.  Every
+// launcher of a row-local form picks its instance by this (the registers kernel exists for 4 and 8 only, which is all
+// couple_path() sends it).
+int couple_rank_class(int rmax);
 
 // ---- pieces of the generic loop (any coupling type)
 // coef[j] = rho_j / sum rho, coef[n] = sum rho (:661-675); also opens the loop (what ctl_reset does: one launch fewer)

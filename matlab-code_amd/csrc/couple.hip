@@ -18,11 +18,13 @@ CouplePath couple_path(int type, int n_modes, int64_t rows, int rmax, bool any_p
   return path;
 }
 
-// the row kernels are instantiated for ranks (and cols(Delta)) up to 4, 8 and 16
+int couple_rank_class(int rmax) { return rmax <= 4 ? 4 : rmax <= 8 ? 8 : 16; }
+
 template <class F>
 static void by_rmax(int rmax, F&& launch) {
-  if (rmax <= 4) launch(std::integral_constant<int, 4>());
-  else if (rmax <= 8) launch(std::integral_constant<int, 8>());
+  const int cls = couple_rank_class(rmax);
+  if (cls == 4) launch(std::integral_constant<int, 4>());
+  else if (cls == 8) launch(std::integral_constant<int, 8>());
   else launch(std::integral_constant<int, 16>());
 }
 
@@ -942,7 +944,7 @@ static void launch_loop_regs(const WgLoopArgs& a, hipStream_t s) {
 }
 void couple_loop_one_launch(const WgLoopArgs& a, CouplePath path, int rmax, hipStream_t s) {
   if (path == CouplePath::Regs) {
-    if (rmax <= 4) launch_loop_regs<4>(a, s);
+    if (couple_rank_class(rmax) == 4) launch_loop_regs<4>(a, s);
     else launch_loop_regs<8>(a, s);
   } else {
     size_t lds = (size_t)a.q * a.q;                   // LAA | per mode: L, H

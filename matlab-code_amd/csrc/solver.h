@@ -178,6 +178,12 @@ class Engine {
                       aoadmm_nvecs_info* info);
   void resident_par2_rhs(int p, int pos, double* out_host, float* ms);
   void kernel_stats(int which, int reset, double* ms, int64_t* launches, double* bytes, double* flops);
+  // The coupled ADMM loop of coupling c as a solve runs it after the MTTKRPs (aoadmm_op_coupled_loop): A[j] (rows_j x R_j)
+  // and Cm[j] (R_j x R_j, weight applied) of the coupling's j-th mode come from the host, the state is the engine's.
+  // Every output may be null: rho (n), L / gram (n pointers, R_j x R_j each), slots (n x 8), path (2).
+  void coupled_loop_op(int c, const double* const* A, const double* const* Cm, int max_inner, const double* tol,
+                       int* inner_iters, double* res, double* rho, double* const* L, double* const* gram, double* slots,
+                       int* path);
 
   // communicator
   void comm_init(const char id[128], int rank, int world, bool share_only = false);
@@ -241,6 +247,11 @@ class Engine {
   void record_iteration(SolveRun& r, int iter);
   void update_uncoupled_cp_mode(int m, const aoadmm_options& opt);
   void prepare_mode_system(int m, int nrho, const aoadmm_options& opt);
+  // the system of a CP mode in one place for the solver and aoadmm_op_coupled_loop: how often rho/2*I enters a coupled
+  // mode's matrix, where sys_build writes, and what follows it (eigenvectors for types 1/5, Aeff)
+  int coupled_nrho(int m) const;
+  SysBuild mode_sysbuild(int m, int nrho);
+  void close_mode_system(int m, const SysBuild& sb, bool build, const double* A);
   void prepare_next_first_mode(const aoadmm_options& opt);
   void ensure_mode_work(ModeInfo& mi);
   // objective (solver_objective.hip): the device half fills the arena, the host half reads its pinned copy
@@ -249,6 +260,8 @@ class Engine {
   void objective_from_host(const ArenaView& h, double f[4]) const;
   double rel_missing_from_host(const ArenaView& h) const;
   // coupled ADMM loop (solver_coupled.hip): coupled_admm prepares it and runs one of the three forms
+  struct CoupleForm { CouplePath path; int rmax; bool any_pc; };   // rmax: largest rank, cols(Delta) included
+  CoupleForm coupled_form(const CouplingInfo& ci);
   void coupled_admm(int c, const aoadmm_options& opt);
   void coupled_one_launch(CouplingInfo& ci, AdmmCtl* ctl, const aoadmm_options& opt, CouplePath path, int rmax);
   void coupled_row_steps(CouplingInfo& ci, AdmmCtl* ctl, const aoadmm_options& opt, int rmax);

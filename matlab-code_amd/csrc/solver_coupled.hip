@@ -70,6 +70,20 @@ FinalizeArgs Engine::coupled_finalize_args(const CouplingInfo& ci, const aoadmm_
   return fa;
 }
 
+// which form runs coupling ci: couple_path() on what the model says about its modes
+Engine::CoupleForm Engine::coupled_form(const CouplingInfo& ci) {
+  int rmax = (int)ci.cols;                            // largest rank, cols(Delta) included
+  bool any_pc = false;                                // a PARAFAC2 C mode in this coupling (types 0 and 1 only)
+  bool local_prox = true;                             // every constrained mode's prox runs inside the loop kernels
+  for (int m : ci.modes) {
+    const ModeInfo& mj = modes_[m];
+    any_pc = any_pc || par2_c_block(mj) != nullptr;
+    rmax = std::max(rmax, mj.R);
+    local_prox = local_prox && (!mj.constrained || prox_is_fusable(mj.prox.type));
+  }
+  return CoupleForm{couple_path(ci.type, (int)ci.modes.size(), ci.rows, rmax, any_pc, local_prox), rmax, any_pc};
+}
+
 void Engine::coupled_admm(int c, const aoadmm_options& opt) {
   CouplingInfo& ci = couplings_[c];
   AdmmCtl* ctl = ctl_of_coupling(c);
@@ -87,18 +101,15 @@ void Engine::coupled_admm(int c, const aoadmm_options& opt) {
   }
   // per-outer-iteration constants
   std::vector<const double*> hp(n);
-  int rmax = (int)ci.cols;                            // largest rank, cols(Delta) included
-  bool any_pc = false;                                // a PARAFAC2 C mode in this coupling (types 0 and 1 only)
-  bool local_prox = true;                             // every constrained mode's prox runs inside the loop kernels
   for (int j = 0; j < n; ++j) {
     const ModeInfo& mj = modes_[ci.modes[j]];
     Par2Block* pb = par2_c_block(mj);
     hp[j] = pb ? pb->rhosum.d() : mj.rho.d();         // type 1 weighs a C mode with sum(rho) (:736)
-    any_pc = any_pc || pb != nullptr;
-    rmax = std::max(rmax, mj.R);
-    local_prox = local_prox && (!mj.constrained || prox_is_fusable(mj.prox.type));
   }
-  const CouplePath path = couple_path(ty, n, ci.rows, rmax, any_pc, local_prox);
+  const CoupleForm form = coupled_form(ci);
+  const CouplePath path = form.path;
+  const int rmax = form.rmax;
+  const bool any_pc = form.any_pc;
   // reset the loop control (the per-mode sys_build calls reset their own blocks); types 0-2: in coupling_coefs_k below
   if (!(ty == 0 || ty == 1 || ty == 2) && path != CouplePath::Regs) ctl_reset(ctl, stream_);
   DevBuf& rho_ptrs = ci.rho_ptrs;                     // pointers never change once the work buffers exist
@@ -369,6 +380,77 @@ void Engine::coupled_generic_dual(CouplingInfo& ci, int m, AdmmCtl* ctl) {
     sumsq_diff(sl + 1, mi.fac.d(), nullptr, nm, redws_.d(), ctl, stream_);
   const double* dimg = image_d(mi.tmp.d(), ci, ci.dD.d(), mi, ctl, stream_);
   sumsq_diff(sl + 6, dimg, nullptr, ni, redws_.d(), ctl, stream_);
+}
+
+// aoadmm_op_coupled_loop: per mode what update_mode -> prepare_mode_system does behind the MTTKRP (A and C given),
+// then coupled_admm and the Gram matrices, exactly as outer_updates runs them
+void Engine::coupled_loop_op(int c, const double* const* A, const double* const* Cm, int max_inner, const double* tol,
+                             int* inner_iters, double* res, double* rho, double* const* L, double* const* gram,
+                             double* slots, int* path) {
+  require_usable();
+  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
+  if (sharded() || multi_member_)
+    throw Error(AOADMM_ERR_UNSUPPORTED, "aoadmm_op_coupled_loop runs on one engine without a communicator");
+  AO_REQUIRE(c >= 0 && c < n_couplings_, "coupling %d out of range", c);
+  AO_REQUIRE(A && Cm && tol && max_inner >= 1, "bad arguments");
+  AO_HIP(hipSetDevice(device_));
+  CouplingInfo& ci = couplings_[c];
+  const int n = (int)ci.modes.size();
+  for (int j = 0; j < n; ++j) {
+    const int m = ci.modes[j];
+    const ModeInfo& mi = modes_[m];
+    if (tensors_[mi.tensor].par2)
+      throw Error(AOADMM_ERR_UNSUPPORTED, fmt("aoadmm_op_coupled_loop: mode %d belongs to a PARAFAC2 block, whose systems come from the block", m + 1));
+    AO_REQUIRE(A[j] && Cm[j], "mode %d: A or C missing", m + 1);
+    AO_REQUIRE(mi.has_fac, "G.fac{%d} missing", m + 1);
+    if (mi.constrained) AO_REQUIRE(mi.has_Z && mi.has_mu, "G.constraint_fac{%d} / constraint_dual_fac{%d} missing", m + 1, m + 1);
+    AO_REQUIRE(mi.has_muD && mi.muD_rows == mi.img_rows && mi.muD_cols == mi.img_cols, "G.coupling_dual_fac{%d} missing or mis-sized", m + 1);
+  }
+  AO_REQUIRE(ci.has_state, "G.coupling_fac{%d} missing", c + 1);
+  aoadmm_options opt{};
+  opt.MaxInnerIters = max_inner;
+  opt.innerRelPrTol_coupl = tol[0]; opt.innerRelPrTol_constr = tol[1];
+  opt.innerRelDualTol_coupl = tol[2]; opt.innerRelDualTol_constr = tol[3];
+  std::vector<DevBuf> cpre(n);
+  for (int j = 0; j < n; ++j) {
+    const int m = ci.modes[j];
+    ModeInfo& mi = modes_[m];
+    ensure_mode_work(mi);
+    mi.quad.dirty = true;                             // rho may have moved ('quadratic regularization', non-symmetric L)
+    const size_t nR = (size_t)mi.rows * mi.R * sizeof(double), RR = (size_t)mi.R * mi.R * sizeof(double);
+    cpre[j].alloc(RR);
+    AO_HIP(hipMemcpyAsync(mi.A.p, A[j], nR, hipMemcpyHostToDevice, stream_));
+    AO_HIP(hipMemcpyAsync(cpre[j].p, Cm[j], RR, hipMemcpyHostToDevice, stream_));
+    SysBuild sb = mode_sysbuild(m, coupled_nrho(m));
+    sb.Cpre = cpre[j].d();
+    close_mode_system(m, sb, true, mi.A.d());
+  }
+  AO_HIP(hipStreamSynchronize(stream_));              // the host arrays are the caller's
+  const CoupleForm form = coupled_form(ci);
+  coupled_admm(c, opt);                                                        // :277 / :366
+  for (int m : ci.modes) { modes_[m].version++; compute_gram(modes_[m]); }    // :393-403
+  std::vector<AdmmCtl> h((size_t)n + 1);
+  for (int j = 0; j < n; ++j)
+    AO_HIP(hipMemcpyAsync(&h[j], ctl_of_mode(ci.modes[j]), sizeof(AdmmCtl), hipMemcpyDeviceToHost, stream_));
+  AO_HIP(hipMemcpyAsync(&h[n], ctl_of_coupling(c), sizeof(AdmmCtl), hipMemcpyDeviceToHost, stream_));
+  AO_HIP(hipStreamSynchronize(stream_));
+  for (const AdmmCtl& k : h)
+    if (k.notpd) throw Error(AOADMM_ERR_NOT_PD, "Matrix must be positive definite.");
+  if (inner_iters) *inner_iters = h[n].iters;
+  if (res) for (int i = 0; i < 4; ++i) res[i] = h[n].res[i];
+  if (path) {
+    path[0] = (int)form.path;
+    path[1] = form.path == CouplePath::Generic ? 0 : couple_rank_class(form.rmax);
+  }
+  for (int j = 0; j < n; ++j) {
+    const ModeInfo& mi = modes_[ci.modes[j]];
+    const size_t RR = (size_t)mi.R * mi.R * sizeof(double);
+    if (rho) AO_HIP(hipMemcpyAsync(rho + j, mi.rho.p, sizeof(double), hipMemcpyDeviceToHost, stream_));
+    if (L && L[j]) AO_HIP(hipMemcpyAsync(L[j], mi.L.p, RR, hipMemcpyDeviceToHost, stream_));
+    if (gram && gram[j]) AO_HIP(hipMemcpyAsync(gram[j], mi.gram.p, RR, hipMemcpyDeviceToHost, stream_));
+    if (slots) AO_HIP(hipMemcpyAsync(slots + 8 * j, resid_slots(ci.modes[j]), 8 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  }
+  AO_HIP(hipStreamSynchronize(stream_));
 }
 
 }  // namespace aoadmm

@@ -66,6 +66,47 @@ void Engine::compute_gram(ModeInfo& mi, const LoopEnd* close) {
   mi.facT_version = mi.version;
 }
 
+// system of a coupled mode: +rho/2*I (types 0, 3, 4: :269, :336, :358), +rho/2*H*H' (type 2, :314), nothing for the
+// Sylvester types 1, 5 (:288-293, :377-382); +rho/2*I more if constrained
+int Engine::coupled_nrho(int m) const {
+  const int cty = couplings_[modes_[m].coupling].type;
+  const int con = modes_[m].constrained ? 1 : 0;
+  return (cty == 0 || cty == 3 || cty == 4) ? 1 + con : (cty == 2 ? con : 0);
+}
+
+// sys_build of CP mode m into the mode's own buffers; the caller names the source of C (grams or Cpre), w and bsum_half
+SysBuild Engine::mode_sysbuild(int m, int nrho) {
+  ModeInfo& mi = modes_[m];
+  SysBuild sb;
+  sb.ngram = 0;
+  sb.Cpre = nullptr;
+  sb.w = 1.0;
+  sb.ridge = has_ridge_ ? mi.ridge : 0.0;
+  sb.bsum_half = 0.0;
+  sb.rho_scale = 1.0;
+  sb.nrho = nrho;
+  sb.R = mi.R;
+  sb.C = mi.C.d(); sb.rho = mi.rho.d(); sb.Bsys = mi.Bsys.d(); sb.L = mi.L.d();
+  sb.Binv = nrho > 0 ? mi.Binv.d() : nullptr;
+  sb.ctl = ctl_of_mode(m);
+  const int cty = mi.coupling >= 0 ? couplings_[mi.coupling].type : -1;
+  if (cty == 2) sb.Madd = mi.HHt.d();
+  return sb;
+}
+
+// what follows the right-hand side A of mode m: the system unless it rode in the MTTKRP's launch, and for the
+// Sylvester types the eigenvectors of the system matrix
+void Engine::close_mode_system(int m, const SysBuild& sb, bool build, const double* A) {
+  ModeInfo& mi = modes_[m];
+  if (build) sys_build(sb, stream_);
+  const int cty = mi.coupling >= 0 ? couplings_[mi.coupling].type : -1;
+  if (cty == 1 || cty == 5) {                       // B = V diag(mu) V' for the Sylvester solve of the inner loop
+    mi.eV.ensure((size_t)mi.R * mi.R * sizeof(double)); mi.eMu.ensure((size_t)mi.R * sizeof(double));
+    sym_eig_small(mi.Bsys.d(), mi.R, mi.eMu.d(), mi.eV.d(), stream_);
+  }
+  mi.Aeff = A;
+}
+
 void Engine::prepare_mode_system(int m, int nrho, const aoadmm_options& opt) {
   ModeInfo& mi = modes_[m];
   TensorInfo& t = tensors_[mi.tensor];
@@ -77,34 +118,18 @@ void Engine::prepare_mode_system(int m, int nrho, const aoadmm_options& opt) {
   FactorRef facs[8];
   factor_refs(t, facs);
   std::vector<int> seq = update_sequence(mi.tensor);
-  SysBuild sb;
-  sb.ngram = 0;
+  SysBuild sb = mode_sysbuild(m, nrho);
   for (int i = 0; i < t.nmodes; ++i)
     if (i != mi.pos) sb.grams[sb.ngram++] = modes_[t.modes[i]].gram.d();     // :98-103, :109,:112
-  sb.Cpre = nullptr;
   sb.w = t.weight;
-  sb.ridge = has_ridge_ ? mi.ridge : 0.0;
   sb.bsum_half = opt.bsum ? opt.bsum_weight / 2 : 0.0;
-  sb.rho_scale = 1.0;
-  sb.nrho = nrho;
-  sb.R = mi.R;
-  sb.C = mi.C.d(); sb.rho = mi.rho.d(); sb.Bsys = mi.Bsys.d(); sb.L = mi.L.d();
-  sb.Binv = nrho > 0 ? mi.Binv.d() : nullptr;
-  sb.ctl = ctl_of_mode(m);
-  const int cty = mi.coupling >= 0 ? couplings_[mi.coupling].type : -1;
-  if (cty == 2) sb.Madd = mi.HHt.d();
   // The system needs the Gram matrices only: it rides in the launch of the reduction that finishes the MTTKRP (one
   // extra workgroup) when that path is taken, else it gets its own launch behind the MTTKRP.
   bool rode = false;
   block_mttkrp(block_ctx(), t.blk, mi.pos, facs, mi.R, t.weight, mi.A.d(), mi.rows, opt.use_dimtree != 0, seq.data(), (int)seq.size(), true,
                false, &sb, &rode);
-  if (!rode) sys_build(sb, stream_);
-  if (cty == 1 || cty == 5) {                       // B = V diag(mu) V' for the Sylvester solve of the inner loop
-    mi.eV.ensure((size_t)mi.R * mi.R * sizeof(double)); mi.eMu.ensure((size_t)mi.R * sizeof(double));
-    sym_eig_small(mi.Bsys.d(), mi.R, mi.eMu.d(), mi.eV.d(), stream_);
-  }
+  close_mode_system(m, sb, !rode, mi.A.d());
   t.last_pos = mi.pos;                                                        // :121-123
-  mi.Aeff = mi.A.d();
   if (opt.bsum) {                                                             // :124-127
     Coef c[2] = {coef(1.0), coef(opt.bsum_weight / 2)};
     const double* x[2] = {mi.A.d(), mi.fac.d()};
@@ -283,13 +308,7 @@ void Engine::update_mode(int m, int cid, const aoadmm_options& opt, int iter) {
   else if (par2 && modes_[m].pos == 2 && cid < 0) par2_update_C(m, opt);   // :219-248
   else if (par2 && modes_[m].pos == 2) par2_prepare_C_coupled(m, couplings_[cid].type, opt);
   else if (cid < 0) update_uncoupled_cp_mode(m, opt);
-  else {
-    // system of a coupled mode: +rho/2*I (types 0, 3, 4: :269, :336, :358), +rho/2*H*H' (type 2, :314),
-    // nothing for the Sylvester types 1, 5 (:288-293, :377-382); +rho/2*I more if constrained
-    const int cty = couplings_[cid].type;
-    const int con = modes_[m].constrained ? 1 : 0;
-    prepare_mode_system(m, (cty == 0 || cty == 3 || cty == 4) ? 1 + con : (cty == 2 ? con : 0), opt);
-  }
+  else prepare_mode_system(m, coupled_nrho(m), opt);
 }
 
 // One outer iteration's updates: every mode in the schedule of :89-93, the coupled ADMM loops, then the EM passes.

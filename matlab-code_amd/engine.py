@@ -331,6 +331,30 @@ class Engine:
                     muZ=unpack(mz) if cid else None, DeltaB=db, rho=rho, L=mats(L), GB=mats(GB), inner_iters=it.value,
                     res=res, path=tuple(path))
 
+    def coupled_loop(self, coupling, A, Cmat, max_inner, tol):
+        """The inner loop of coupling `coupling` (0-based) of the model this engine holds, as the solver runs it behind
+        the MTTKRPs (`aoadmm_op_coupled_loop`): systems, the form of the loop the library picks, Gram matrices.  A, Cmat:
+        one array per coupled mode in ascending mode order (rows_j x R_j: the MTTKRP; R_j x R_j: the Hadamard product
+        of the other modes' Gram matrices, weight applied); tol: (pr_coupl, pr_constr, du_coupl, du_constr).  The state
+        goes in and out through `aoadmm_state_set` / `aoadmm_state_get`.  Returns a dict: inner_iters, res (4, order of
+        tol), rho (n), L and gram (lists of R_j x R_j), slots (n x 8 squared norms behind the residuals) and path =
+        (capi.CPATH_*, rank class of the row kernels or 0)."""
+        A = [capi.as_f(a) for a in A]
+        Cmat = [capi.as_f(c) for c in Cmat]
+        n = len(A)
+        if n == 0 or len(Cmat) != n or any(a.ndim != 2 or c.shape != (a.shape[1],) * 2 for a, c in zip(A, Cmat)):
+            raise ValueError('coupled_loop: one rows x R array and one R x R array per coupled mode')
+        L = [np.zeros(c.shape, order='F') for c in Cmat]
+        gram = [np.zeros(c.shape, order='F') for c in Cmat]
+        rho, slots, res = np.zeros(n), np.zeros((n, 8)), np.zeros(4)
+        it = C.c_int(0)
+        path = (C.c_int * 2)(-1, -1)
+        tolv = np.asarray(tol, dtype=np.float64).reshape(4).copy()
+        ptrs = lambda xs: (C.POINTER(C.c_double) * n)(*[capi.dptr(x) for x in xs])
+        capi.check(self.lib.aoadmm_op_coupled_loop(
+            self.h, int(coupling), ptrs(A), ptrs(Cmat), int(max_inner), capi.dptr(tolv), C.byref(it), capi.dptr(res),
+            capi.dptr(rho), ptrs(L), ptrs(gram), capi.dptr(slots), path))
+        return dict(inner_iters=it.value, res=res, rho=rho, L=L, gram=gram, slots=slots, path=tuple(path))
 
 
 _default = None

@@ -49,6 +49,16 @@ def test_constraint_ids_match_header(pkg):
     assert len(pkg.CONSTRAINT_IDS) == 20
 
 
+def test_coupled_loop_entry_and_its_path_codes(pkg):
+    """aoadmm_op_coupled_loop is declared, bound and exported, and the AOADMM_CPATH_* values are those of the binding."""
+    capi = __import__('importlib').import_module('matlab-code_amd._capi')
+    assert 'aoadmm_op_coupled_loop' in declared_functions() and 'aoadmm_op_coupled_loop' in pkg.SYMBOLS
+    assert hasattr(pkg.load_library(), 'aoadmm_op_coupled_loop') and hasattr(pkg.Engine, 'coupled_loop')
+    text = open(HEADER).read()
+    ids = {m.group(1): int(m.group(2)) for m in re.finditer(r'AOADMM_CPATH_([A-Z]+)\s*=\s*(\d+)', text)}
+    assert ids == dict(REGS=capi.CPATH_REGS, WG=capi.CPATH_WG, ROWSTEPS=capi.CPATH_ROWSTEPS, GENERIC=capi.CPATH_GENERIC)
+
+
 def test_no_cpu_fallback(pkg):
     """Without a GPU the product path must fail loudly (never route through the oracle)."""
     lib = pkg.load_library()

@@ -255,6 +255,30 @@ def test_coupled_loop_early_exit_matches(pkg, eng):
     compare(Fo, oo, Fg, og)
 
 
+EXIT_TOLS = dict(innerRelPrTol_coupl=1e-2, innerRelDualTol_coupl=1e-2, innerRelPrTol_constr=1e-2, innerRelDualTol_constr=1e-2)
+
+
+@pytest.mark.parametrize('form', ['wg', 'rowsteps', 'generic-1', 'generic-3'])
+def test_coupled_loop_early_exit_on_the_other_forms(pkg, eng, form):
+    """The tolerances of test_coupled_loop_early_exit_matches on the forms of the coupled loop that test does not reach:
+    the LDS one-workgroup kernel (script 3 at 300 rows), the launch-per-step form (exact coupling at 2500 rows) and the
+    generic loop (coupling types 1 and 3).  innerIters and the state left behind against the oracle.  With up to 30 inner
+    iterations the oracle leaves the coupled loop early in the first outer iterations of each of these models (asserted)."""
+    from helpers import transformed_coupling_model
+    rng = np.random.default_rng(45)
+    if form == 'wg':
+        Z, io = script3_model(rng, rows=300)
+    elif form == 'rowsteps':
+        Z, io = cp_cp_exact_model(rng, rows=2500)
+    else:
+        Z, io = transformed_coupling_model(rng, int(form[-1]))
+    opt = options(MaxOuterIters=dict(wg=4, rowsteps=6).get(form, 8), MaxInnerIters=30, **EXIT_TOLS)
+    Fo, oo, Fg, og = run_both(pkg, eng, Z, io, opt)
+    assert np.array_equal(og['innerIters'], oo['innerIters'])
+    assert 1 < oo['innerIters'][0].min() < 30, 'the coupled loop of this model never leaves early: the case checks nothing'
+    compare(Fo, oo, Fg, og)
+
+
 def test_early_stop_matches(pkg, eng):
     """Non-zero tolerances: inner/outer stopping decisions taken on the device agree with the oracle."""
     rng = np.random.default_rng(6)
