@@ -288,6 +288,27 @@ int aoadmm_tensor_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t*
  *   block above stay.  A block whose share was cut for another (rank, world) than the context has now answers
  *   AOADMM_ERR_INVALID ("upload again") to these calls.  The next upload of either kind replaces the block. */
 int aoadmm_tensor_upload_coo_sharded(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* vals);
+/* Marks (on != 0) or unmarks a sparse CP block as OBSERVED-ONLY: its stored entries (after coalescing; explicit zeros
+ * are kept) are the observations, every other entry is MISSING instead of an observed zero.  aoadmm_solve then runs the
+ * reference's EM imputation (cmtf_fun_AOADMM.m:408-441) on the block as it would on the densified tensor with the mask
+ * "is stored" -- same factors, duals, innerIters, func_val_conv, func_rel_missing and stopping rule (:457-459) -- without
+ * an array of the tensor's size: the missing entries start at 0 in every solve, the MTTKRP is the sparse MTTKRP of the
+ * residuals on the stored entries plus a rank-R correction from the factor snapshot of the last EM step, and the
+ * statistics are sums over the stored entries and R x R products (no float atomics: two runs return the same bits).
+ * Resident afterwards: N (4 N + 16) bytes per nonzero plus two copies of every factor (aoadmm_tensor_storage_info).
+ * Valid on a block uploaded with aoadmm_tensor_upload_coo that holds at least one entry (none: AOADMM_ERR_INVALID);
+ * AOADMM_ERR_UNSUPPORTED for a dense block, a PARAFAC2 block and a block uploaded with
+ * aoadmm_tensor_upload_coo_sharded.  Any later upload of the block clears the mark.  aoadmm_tensor_mask_upload on
+ * sparse data stays refused.  With a communicator the block is replicated: every rank does the same work, no
+ * collective. */
+int aoadmm_tensor_set_observed_only(aoadmm_ctx* ctx, int p, int on);
+/* One EM step of an observed-only block with the current factors: the residuals x - m of the stored entries, then the
+ * snapshot of the factors.  stats = {sum over the stored entries of (x - m)^2, num, den} with num / den the squared
+ * norms of the change of the missing entries and of their old values (:436-440); the first step after the mark or a
+ * solve has den = 0 and num = the squared norm of the model outside the stored entries.  Afterwards
+ * aoadmm_resident_mttkrp on the block returns the MTTKRP of the imputed tensor as of this step (before any step: the
+ * plain sparse MTTKRP, bit for bit). */
+int aoadmm_resident_em_step(aoadmm_ctx* ctx, int p, double stats[3]);
 /* Z.object{p}{k} of a PARAFAC2 block as sparse matrices, all K slabs in one call: nnz nonzeros, subs column-major
  * nnz x 3, 0-based (i, j within the slab, k); vals nnz doubles.  Duplicates are summed, explicit zeros are allowed,
  * nnz = 0 is valid; a subscript out of range (j >= J_k included) or nnz < 0 is AOADMM_ERR_INVALID and leaves the block
@@ -304,8 +325,9 @@ int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out);
  * (AOADMM_PREC_F64 for sparse and PARAFAC2 data), *scale = the power-of-two scale s of an AOADMM_PREC_F16 block (1.0
  * otherwise), *resident_bytes = what a CP block holds now: natural-layout array, pass copies, transposed copy and
  * mask of a dense block; the per-mode copies of the nonzeros of a sparse block, N (4 N + 8) bytes per nonzero this
- * rank holds (all of them, or its share of a sharded block; a multi-device context reports rank 0's); 0 for PARAFAC2
- * data.  No device work. */
+ * rank holds (all of them, or its share of a sharded block; a multi-device context reports rank 0's), for an
+ * observed-only block N (4 N + 16) per nonzero plus the factor snapshots (2 * 8 * I_n * R bytes per mode); 0 for
+ * PARAFAC2 data.  No device work. */
 int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes);
 
 /* ---- state (the struct G) ---------------------------------------------- */
@@ -333,7 +355,10 @@ int aoadmm_resident_par2_rhs(aoadmm_ctx* ctx, int p, int tensor_mode, double* ou
  * timed only from the first call with which = 2 on, two more events per reduction); which = 3: the MTTKRPs of
  * sparse blocks (launches = MTTKRPs, each the streaming kernel plus its carry passes; bytes = nonzeros streamed +
  * factor rows gathered + output written; flops = nnz * R * N) and the passes over the nonzeros of PARAFAC2 blocks
- * with sparse slabs (one launch per pass, counted as the MTTKRP of the I x sum(J_k) matrix it is).  Of a sharded
+ * with sparse slabs (one launch per pass, counted as the MTTKRP of the I x sum(J_k) matrix it is); an EM step of an
+ * observed-only block counts as one launch with the bytes and flops of its N passes, and its MTTKRPs include the
+ * dense correction; which = 4 + n (n = 0 .. 7): the pass of those EM steps over the copy of tensor mode n alone (the
+ * residuals x - m; n = 0 also carries the statistics, and is the whole of a statistics-only step).  Of a sharded
  * sparse block: this rank's share (its nonzeros, and the rows of its span as the output written); the all-reduce is
  * outside the events */
 int aoadmm_kernel_stats(aoadmm_ctx* ctx, int which, int reset, double* contract_ms, int64_t* contract_launches,

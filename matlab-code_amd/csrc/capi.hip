@@ -434,6 +434,20 @@ int aoadmm_par2_slab_upload_coo(aoadmm_ctx* ctx, int p, int64_t nnz, const int64
     on_engines(ctx, [&](Engine& e, int) { e.par2_slab_upload_coo(p, nnz, subs, vals); });   // replicated on every engine
   });
 }
+int aoadmm_tensor_set_observed_only(aoadmm_ctx* ctx, int p, int on) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] { on_engines(ctx, [&](Engine& e, int) { e.set_observed_only(p, on != 0); }); });
+}
+int aoadmm_resident_em_step(aoadmm_ctx* ctx, int p, double stats[3]) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    AO_REQUIRE(stats != nullptr, "null stats");
+    on_engines(ctx, [&](Engine& e, int r) {          // replicated: every engine takes the same step, rank 0 answers
+      double mine[3];
+      e.resident_em_step(p, r == 0 ? stats : mine);
+    });
+  });
+}
 int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes) {
   CTX_OR_FAIL(ctx);
   // no collective and no device work: rank 0's engine answers for a multi-device context (every rank holds the same

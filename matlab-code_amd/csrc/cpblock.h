@@ -5,6 +5,7 @@
 #include "common.h"
 #include "contract.h"
 #include "sparse.h"
+#include "sparse_em.h"
 
 #include <functional>
 
@@ -17,6 +18,9 @@ struct FactorRef {
   const double* pT = nullptr;   // optional row-major copy (rows x R) of the same version, written by the Gram kernel
 };
 
+constexpr int kStatsEmPass = 4;
+constexpr int kStatsClasses = kStatsEmPass + kCooMaxModes;
+
 struct KernelStats {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
   double ms = 0.0, bytes = 0.0, flops = 0.0;
@@ -28,7 +32,10 @@ struct KernelStats {
 struct LaunchTimers {
   struct Pair { hipEvent_t e0 = nullptr, e1 = nullptr; };
   std::vector<hipEvent_t> pool;   // timing events are recycled: creating two per tensor pass cost host time in the loop
-  KernelStats stats[4];   // [0] streaming contraction, [1] leading-mode contraction, [2] reductions over T, [3] sparse MTTKRP and the passes over sparse PARAFAC2 slabs
+  // [0] streaming contraction, [1] leading-mode contraction, [2] reductions over T, [3] sparse MTTKRP, the passes over
+  // sparse PARAFAC2 slabs and the EM steps of observed-only blocks, [kStatsEmPass + n] the pass of those steps over
+  // mode n's copy
+  KernelStats stats[kStatsClasses];
   bool profile = true;
   bool profile_reductions = false;   // switched on by the first kernel_stats(2, ...) call: two more events per reduction
   hipEvent_t take_event();
@@ -105,6 +112,8 @@ struct CpBlock {
   // all-reduce of the shares' partial sums, from the block's per-mode send buffers (CooBlock::send)
   bool sparse = false;
   CooBlock coo;
+  // observed-only form of a sparse block (aoadmm_tensor_set_observed_only): the unstored entries are missing, not zero
+  SparseEm sem;
   // New data has arrived, dense or sparse: no copy, cached contraction or release state of the old data holds.  Frees
   // nothing (a pass copy's buffer is reused by the next build; the sparse upload releases what it no longer needs).
   void reset_derived() {

@@ -581,8 +581,22 @@ static void sparse_mttkrp(const BlockCtx& cx, CpBlock& b, int pos, const FactorR
   }
   LaunchTimers& tm = *cx.timers;
   const LaunchTimers::Pair pr = tm.begin(tm.stats[3], tm.profile, cx.stream);
-  coo_mttkrp(b.coo, pos, f, R, scale, out, ldOut, cx.stream, span_only);
-  tm.end(tm.stats[3], pr, cx.stream, coo_mttkrp_bytes(b.coo, pos, R), coo_mttkrp_flops(b.coo, R));
+  // observed-only block after an EM step: the imputed tensor is the residuals on the stored entries plus the snapshot's
+  // model everywhere (sparse_em.h); before the first step the missing entries are 0 and this is the plain MTTKRP
+  const bool imputed = b.sem.on && b.sem.have_snap;
+  coo_mttkrp(b.coo, pos, f, R, scale, out, ldOut, cx.stream, span_only, imputed ? b.sem.res[pos].d() : nullptr);
+  double bytes = coo_mttkrp_bytes(b.coo, pos, R), flops = coo_mttkrp_flops(b.coo, R);
+  if (imputed) {
+    AO_REQUIRE(b.sem.R == R, "observed-only block was marked for rank %d, the MTTKRP has rank %d", b.sem.R, R);
+    SemFac sf[kCooMaxModes];
+    for (int m = 0; m < b.nd; ++m) sf[m] = SemFac{facs[m].p, facs[m].ld, facs[m].pT};
+    sem_mttkrp_correct(b.sem, pos, sf, scale, out, ldOut, cx.stream);
+    for (int m = 0; m < b.nd; ++m) {                  // Fo_j'F_j of the other modes, then Fo_pos * W
+      bytes += (m == pos ? 3.0 : 2.0) * (double)b.dims[m] * R * 8.0;
+      flops += 2.0 * (double)b.dims[m] * R * R;
+    }
+  }
+  tm.end(tm.stats[3], pr, cx.stream, bytes, flops);
 }
 
 // The send buffer of mode `pos` of a sharded sparse block (dims[pos] x R, leading dimension dims[pos]).  Invariant of

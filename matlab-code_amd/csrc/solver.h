@@ -111,6 +111,8 @@ struct TensorInfo {
   int last_pos = -1;
   bool eval_shortcut = false;   // PARAFAC2: the enqueued objective evaluation took the last_mttkrp shortcut (:1254-1260)
   bool masked() const { return par2 ? p2.has_mask : blk.has_mask; }   // Z.miss{p} given
+  bool observed_only() const { return !par2 && blk.sparse && blk.sem.on; }   // sparse block whose unstored entries are missing
+  bool missing() const { return masked() || observed_only(); }        // the block takes part in the EM step
 };
 
 struct CouplingInfo {
@@ -160,6 +162,7 @@ class Engine {
   void par2_slab_upload_coo(int p, int64_t nnz, const int64_t* subs, const double* vals);
   void tensor_mask_upload(int p, const uint8_t* mask);
   void par2_slab_mask_upload(int p, int k, const uint8_t* mask);
+  void set_observed_only(int p, bool on);          // sparse CP block: unstored entries are missing (sparse_em.h)
   double tensor_normsq(int p);
   // what tensor p keeps on the device: the precision its passes stream, the power-of-two scale of a half block (else 1)
   // and the bytes of its natural array, pass copies, transposed copy and mask (dense CP blocks), of the per-mode copies
@@ -173,6 +176,7 @@ class Engine {
   // solve
   void solve(const aoadmm_options& opt, aoadmm_result* out);
   void resident_mttkrp(int p, int pos, double* out_host, float* ms);
+  void resident_em_step(int p, double stats[3]);   // one EM step of an observed-only block: {sum_Omega (x-m)^2, num, den}
   void resident_unfold_gram(int p, int pos, int slab, double* out_host);
   void resident_nvecs(int p, int pos, int r, const aoadmm_nvecs_options* opt, double* U_host, int64_t ldU, double* eig_host,
                       aoadmm_nvecs_info* info);
@@ -229,6 +233,7 @@ class Engine {
   void comm_release();                     // destroys the RCCL communicator, if any (solver_comm.hip)
   bool has_missing() const;
   void em_pass_enqueue(int p, int update, bool fuse_next_pass = false);   // statistics of tensor p into its EM slots (+ imputation)
+  void sparse_em_enqueue(int p, bool stats_only);  // EM step of an observed-only sparse block into its EM slots
   void compute_gram(ModeInfo& mi, const LoopEnd* close = nullptr);
   FactorRef factor_ref(const ModeInfo& o) const {
     return FactorRef{o.fac.d(), o.rows, o.version, o.facT_version == o.version ? o.facT.d() : nullptr};

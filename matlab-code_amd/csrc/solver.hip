@@ -373,6 +373,7 @@ void Engine::tensor_storage_info(int p, int* precision, double* scale, int64_t* 
       for (int m = 0; m < b.coo.nd; ++m)
         for (const DevBuf* d : {&b.coo.mode[m].row, &b.coo.mode[m].oidx, &b.coo.mode[m].val})
           if (d->p) n += (int64_t)d->bytes;
+      n += sem_resident_bytes(b.sem);      // observed-only: 8 more bytes per nonzero per copy and the factor snapshots
     }
     *resident_bytes = n;
   }
@@ -386,7 +387,7 @@ void Engine::tensor_upload(int p, const double* data, int prec, int64_t row0, in
   AO_REQUIRE(!t.par2, "tensor %d is PARAFAC2: use aoadmm_par2_slab_upload", p);
   AO_REQUIRE(local_rows < 0 || !t.blk.sparse, "tensor %d holds sparse data: a row block cannot replace it (use aoadmm_tensor_upload)", p);
   if (prec == AOADMM_PREC_F16) require_half_ok(t, p, local_rows >= 0);   // refused before anything of the block changes
-  if (t.blk.sparse) { t.blk.coo.clear(); t.blk.sparse = false; }   // a dense upload replaces the sparse form
+  if (t.blk.sparse) { t.blk.coo.clear(); t.blk.sem.clear(); t.blk.sparse = false; }   // a dense upload replaces the sparse form
   AO_HIP(hipSetDevice(device_));
   const BlockCtx cx = block_ctx();
   int64_t dims[8];
@@ -439,6 +440,7 @@ void Engine::tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const do
   b.tmpA.release(); b.tmpB.release(); b.mask.release(); b.maskT.release();
   for (int i = 0; i < 2; ++i) { b.own[i].release(); b.own_bytes[i] = 0; b.own_row0[i] = -1; }
   b.coo = std::move(coo);
+  b.sem.clear();                                       // a new upload is a plain block again
   b.sparse = true;
   b.nd = t.nmodes;
   for (int i = 0; i < t.nmodes; ++i) b.dims[i] = dims[i];
@@ -620,9 +622,73 @@ void Engine::tensor_mask_upload(int p, const uint8_t* mask) {
   t.normsq_valid = false;
 }
 
+// Observed-only sparse CP block (sparse_em.h): the stored entries are the observations, the others are missing and
+// start at 0 (example_script12_CP_PAR2_EM.m:115-147).  Z.miss on sparse data stays refused (tensor_mask_upload).
+void Engine::set_observed_only(int p, bool on) {
+  require_usable();
+  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
+  AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
+  TensorInfo& t = tensors_[p];
+  if (t.par2)
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("observed-only is for sparse CP blocks: tensor %d is PARAFAC2 (sparse slabs with missing entries are not supported)", p));
+  CpBlock& b = t.blk;
+  AO_REQUIRE(b.has_data, "tensor %d has no data: upload it with aoadmm_tensor_upload_coo first", p);
+  if (!b.sparse)
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("observed-only is for sparse CP blocks: tensor %d holds dense data (use Z.miss / aoadmm_tensor_mask_upload)", p));
+  if (b.coo.sharded)
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("observed-only is not available for a block uploaded with aoadmm_tensor_upload_coo_sharded (tensor %d): upload it replicated", p));
+  AO_REQUIRE(b.coo.nnz > 0, "tensor %d has no stored entry: an observed-only block needs observations", p);
+  AO_HIP(hipSetDevice(device_));
+  if (!on) { b.sem.clear(); return; }
+  sem_enable(b.sem, b.coo, modes_[t.modes[0]].R);
+}
+
+void Engine::sparse_em_enqueue(int p, bool stats_only) {
+  TensorInfo& t = tensors_[p];
+  CpBlock& b = t.blk;
+  SemFac sf[kCooMaxModes];
+  for (int i = 0; i < t.nmodes; ++i) {
+    const FactorRef fr = factor_ref(modes_[t.modes[i]]);
+    sf[i] = SemFac{fr.p, fr.ld, fr.pT};
+  }
+  const bool snap = b.sem.have_snap && !stats_only;
+  // the whole step is one launch of class 3; the pass over mode n's copy is also one of class 4 + n
+  const LaunchTimers::Pair pr = timers_.begin(timers_.stats[3], timers_.profile, stream_);
+  sem_step_begin(b.sem, b.coo, sf, stats_only, stream_);
+  double bytes = 0.0, flops = 0.0;
+  for (int pos = 0; pos < (stats_only ? 1 : t.nmodes); ++pos) {
+    KernelStats& ks = timers_.stats[kStatsEmPass + pos];
+    const LaunchTimers::Pair pp = timers_.begin(ks, timers_.profile, stream_);
+    sem_step_pass(b.sem, b.coo, sf, pos, stats_only, stream_);
+    const double pb = sem_pass_bytes(b.sem, pos == 0, snap, !stats_only), pf = sem_pass_flops(b.sem, pos == 0, snap);
+    timers_.end(ks, pp, stream_, pb, pf);
+    bytes += pb; flops += pf;
+  }
+  sem_step_finish(b.sem, sf, stats_only, dev_.em(p), stream_);
+  timers_.end(timers_.stats[3], pr, stream_, bytes, flops);
+}
+
+void Engine::resident_em_step(int p, double stats[3]) {
+  require_usable();
+  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
+  AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
+  AO_REQUIRE(stats != nullptr, "null stats");
+  TensorInfo& t = tensors_[p];
+  if (!t.observed_only())
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("tensor %d is not an observed-only sparse CP block (aoadmm_tensor_set_observed_only)", p));
+  for (int i = 0; i < t.nmodes; ++i) AO_REQUIRE(modes_[t.modes[i]].has_fac, "G.fac{%d} missing", t.modes[i] + 1);
+  AO_REQUIRE(t.blk.sem.R == modes_[t.modes[0]].R, "tensor %d was marked observed-only for rank %d", p, t.blk.sem.R);
+  AO_HIP(hipSetDevice(device_));
+  sparse_em_enqueue(p, false);
+  double h4[kEmStats];
+  AO_HIP(hipMemcpyAsync(h4, dev_.em(p), sizeof h4, hipMemcpyDeviceToHost, stream_));
+  AO_HIP(hipStreamSynchronize(stream_));
+  stats[0] = h4[kEmObsRes]; stats[1] = h4[kEmNum]; stats[2] = h4[kEmDen];
+}
+
 bool Engine::has_missing() const {
   for (int p = 0; p < n_tensors_; ++p)
-    if (tensors_[p].masked()) return true;
+    if (tensors_[p].missing()) return true;
   return false;
 }
 
@@ -842,7 +908,7 @@ void Engine::state_get(int field, int index, int slab, double* host, int64_t row
 // MTTKRP engine
 // ---------------------------------------------------------------------------
 void Engine::kernel_stats(int which, int reset, double* ms, int64_t* launches, double* bytes, double* flops) {
-  AO_REQUIRE(which >= 0 && which <= 3, "kernel_stats: which must be 0, 1, 2 or 3");
+  AO_REQUIRE(which >= 0 && which < kStatsClasses, "kernel_stats: which must be 0 .. %d", kStatsClasses - 1);
   if (which == 2) timers_.profile_reductions = true;
   AO_HIP(hipSetDevice(device_));
   AO_HIP(hipStreamSynchronize(stream_));

@@ -23,6 +23,10 @@ void Engine::eval_objective_enqueue(bool first) {
     const bool masked = t.masked();
     if (masked && first) em_pass_enqueue(p, 0);  // observed-entry residual (:1224-1226, :1249-1252); later
                                                  // evaluations reuse the statistics of the EM update pass
+    if (t.observed_only()) {                     // likewise over the stored entries of an observed-only sparse block
+      if (first) sparse_em_enqueue(p, true);
+      continue;
+    }
     if (t.par2) {
       par2_objective_enqueue(t);                 // direct residual (:1262-1264) + internal-coupling gaps (:1355)
       t.eval_shortcut = !masked && !first && t.last_pos == 0;   // remembered for objective_from_host: last_pos may move on before
@@ -116,7 +120,7 @@ void Engine::objective_from_host(const ArenaView& h, double f[4]) const {
   for (int p = 0; p < n_tensors_; ++p) {
     const TensorInfo& t = tensors_[p];
     const double* sp = h.tensor_obj(p);
-    const bool masked = t.masked();
+    const bool masked = t.missing();
     if (t.par2) {
       const Par2Block& b = t.p2;
       const double* res = h.p2_res(p);
@@ -193,7 +197,7 @@ void Engine::objective_from_host(const ArenaView& h, double f[4]) const {
 double Engine::rel_missing_from_host(const ArenaView& h) const {
   double num = 0.0, den = 0.0;
   for (int p = 0; p < n_tensors_; ++p)
-    if (tensors_[p].masked()) { num += h.em(p)[kEmNum]; den += h.em(p)[kEmDen]; }
+    if (tensors_[p].missing()) { num += h.em(p)[kEmNum]; den += h.em(p)[kEmDen]; }
   return den > 0 ? std::sqrt(num / den) : std::sqrt(num);
 }
 }  // namespace aoadmm

@@ -264,6 +264,12 @@ void Engine::solve_setup(const aoadmm_options& opt) {
         AO_REQUIRE(t.p2.have_P[k] && t.p2.have_mu[k], "G.P{%d}{%d} / G.mu_DeltaB{%d}{%d} missing", p + 1, k + 1, p + 1, k + 1);
     }
     (void)tensor_normsq(p);          // Znorm_const{p}; a masked block needs the factors (statistics-only EM pass)
+    if (t.observed_only()) {         // a solve starts with the missing entries at 0: no snapshot of an earlier one
+      const CpBlock& b = t.blk;
+      AO_REQUIRE(!b.coo.sharded && b.coo.nnz > 0 && b.sem.nnz == b.coo.nnz, "tensor %d: observed-only needs a replicated sparse block with stored entries", p);
+      AO_REQUIRE(b.sem.R == modes_[t.modes[0]].R, "tensor %d was marked observed-only for rank %d", p, b.sem.R);
+      t.blk.sem.have_snap = false;
+    }
   }
   for (int p = 0; p < n_tensors_; ++p) {
     TensorInfo& t = tensors_[p];
@@ -333,8 +339,10 @@ void Engine::outer_updates(const aoadmm_options& opt, int iter, bool has_miss) {
     }
   }
   if (has_miss)                                                              // EM imputation (:408-441)
-    for (int p = 0; p < n_tensors_; ++p)
+    for (int p = 0; p < n_tensors_; ++p) {
       if (tensors_[p].masked()) em_pass_enqueue(p, 1, opt.use_dimtree != 0 && iter < opt.MaxOuterIters);
+      else if (tensors_[p].observed_only()) sparse_em_enqueue(p, false);
+    }
 }
 
 void Engine::enqueue_readback(SolveRun& r) {

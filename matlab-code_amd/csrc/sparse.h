@@ -63,8 +63,10 @@ void coo_keep_share(CooBlock& b, int rank, int world, hipStream_t s);
 // f[k] are the factors of the other modes in mode order.  Bitwise reproducible (no atomics).
 // span_only (sharded blocks): clears and writes the rows [span0[pos], span1[pos]] of `out` alone -- this rank's partial
 // sums, complete after the sum over the ranks; an empty share touches nothing.
+// vals (optional): nnz values in the order of mode pos's copy, read instead of CooMode::val (the residuals of an
+// observed-only block, sparse_em.h)
 void coo_mttkrp(CooBlock& b, int pos, const CooFactor* f, int R, double scale, double* out, int64_t ldOut,
-                hipStream_t s, bool span_only = false);
+                hipStream_t s, bool span_only = false, const double* vals = nullptr);
 
 // A list of n entries sorted by `key` (int32, 0 <= key < rows); entry e carries the index gidx[e] and the value val[e]
 struct CooList {

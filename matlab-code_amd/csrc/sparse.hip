@@ -458,7 +458,7 @@ static void run_list(CooArgs a, DevBuf* slot_row, DevBuf* slot_val, hipStream_t 
 }
 
 void coo_mttkrp(CooBlock& b, int pos, const CooFactor* f, int R, double scale, double* out, int64_t ldOut,
-                hipStream_t s, bool span_only) {
+                hipStream_t s, bool span_only, const double* vals) {
   AO_REQUIRE(pos >= 0 && pos < b.nd, "sparse mttkrp: mode %d out of range", pos);
   AO_REQUIRE(R >= 1 && R <= kMaxRank, "sparse mttkrp: rank %d outside 1..%d", R, kMaxRank);
   const int64_t rows = b.dims[pos];
@@ -474,7 +474,7 @@ void coo_mttkrp(CooBlock& b, int pos, const CooFactor* f, int R, double scale, d
   if (b.nnz == 0) return;
   const CooMode& cm = b.mode[pos];
   CooArgs a;
-  a.row = cm.row.as<int>(); a.oidx = cm.oidx.as<int>(); a.val = cm.val.d(); a.nnz = b.nnz;
+  a.row = cm.row.as<int>(); a.oidx = cm.oidx.as<int>(); a.val = vals ? vals : cm.val.d(); a.nnz = b.nnz;
   a.no = b.nd - 1;
   for (int k = 0; k < a.no; ++k) a.f[k] = f[k];
   a.R = R; a.scale = scale; a.out = out; a.oI = 1; a.oR = ldOut;

@@ -329,7 +329,46 @@ def _make_options(alg_options):
     return o
 
 
-def build_model(eng, Z, precision='f64', sparse_sharding=False):
+def _unsupported(msg):
+    return capi.UnsupportedOnDevice(capi.ERR_UNSUPPORTED, msg)
+
+
+def observed_only_blocks(Z, observed_only, sparse_sharding=False):
+    """The 0-based blocks that `alg_options['hip']['sparse_observed_only']` marks: 0 / None / False -> none, 1 / True ->
+    every sparse CP block, a list -> those 1-based blocks, each of which must be a sparse CP block.  Raises
+    `UnsupportedOnDevice` for a dense block, a PAR2 block and for any marked block together with `sparse_sharding`."""
+    P = len(Z['object'])
+
+    def sparse_cp(p):
+        obj = Z['object'][p]
+        return Z['model'][p] == 'CP' and not isinstance(obj, dict) and coo_of(obj) is not None
+
+    if observed_only is None or isinstance(observed_only, (bool, int, np.integer)):
+        if observed_only is None or int(observed_only) == 0:
+            return []
+        if int(observed_only) != 1:
+            raise ValueError('sparse_observed_only must be 0, 1 or a list of 1-based block numbers')
+        blocks = [p for p in range(P) if sparse_cp(p)]
+    else:
+        blocks = []
+        for q in observed_only:
+            p = int(q) - 1
+            if int(q) != q or p < 0 or p >= P:
+                raise ValueError('sparse_observed_only names Z.object{%s}: the model has %d blocks' % (q, P))
+            if Z['model'][p] != 'CP':
+                raise _unsupported('sparse_observed_only: Z.object{%d} is a PARAFAC2 block (sparse slabs with missing '
+                                   'entries are not supported)' % (p + 1))
+            if not sparse_cp(p):
+                raise _unsupported('sparse_observed_only: Z.object{%d} is dense (use Z.miss for a dense block)' % (p + 1))
+            if p not in blocks:
+                blocks.append(p)
+    if blocks and sparse_sharding:
+        raise _unsupported('sparse_observed_only is not available together with sparse_sharding: an observed-only '
+                           'block is replicated')
+    return blocks
+
+
+def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0):
     """Describe the struct Z to the engine and upload Z.object (cmtf_AOADMM.m:23-41,124-156).
 
     Z.object{p} of a CP block may be dense, an `sptensor`, or (2-way blocks) any object with `.tocoo()` such as a
@@ -345,8 +384,13 @@ def build_model(eng, Z, precision='f64', sparse_sharding=False):
     sparse_sharding: sparse CP blocks go up through `aoadmm_tensor_upload_coo_sharded`, so that every rank of the
     engine's communicator (or every engine of a multi-device one) keeps its share of the nonzeros and the block's
     MTTKRPs become all-reduces; every rank calls `build_model` with the same Z.  PAR2 blocks with sparse slabs stay
-    replicated."""
+    replicated.
+    observed_only (`observed_only_blocks`: 0, 1 or a list of 1-based block numbers): the named sparse CP blocks are
+    marked observed-only after their upload (`Engine.set_observed_only`): their stored entries are the observations,
+    every other entry is missing and fitted by EM as Z.miss does for dense data.  Z.miss on a sparse block keeps
+    raising the reference's error."""
     prec = capi.precision_id(precision)                # an unknown string fails before the engine is touched
+    observed = observed_only_blocks(Z, observed_only, sparse_sharding)
     lib = eng.lib
     nb_modes = len(Z['size'])
     which_p = _which_p(Z)
@@ -430,6 +474,10 @@ def build_model(eng, Z, precision='f64', sparse_sharding=False):
                     eng.upload_coo(p, subs, vals, sharded=True)
                 else:
                     eng.upload_coo(p, subs, vals)
+                if p in observed:
+                    if len(vals) == 0:
+                        raise ValueError('sparse_observed_only: Z.object{%d} has no stored entry' % (p + 1))
+                    eng.set_observed_only(p, True)
                 continue
             if isinstance(obj, dict) and obj.get('synthetic'):
                 capi.check(lib.aoadmm_tensor_synth(eng.h, p, int(obj['rank']), int(obj['seed']), float(obj['noise']), prec))
@@ -661,10 +709,15 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
     Z['_ranks'] = ranks
     # alg_options['hip']['sparse_sharding'] (default 0: replicated): sparse CP blocks sharded over the ranks
     hip = alg_options.get('hip', {}) if isinstance(alg_options, dict) else {}
-    build_model(eng, Z, precision, sparse_sharding=bool(int(hip.get('sparse_sharding', 0))))
+    # alg_options['hip']['sparse_observed_only'] (default 0; 1: every sparse CP block; a list: 1-based block numbers):
+    # the unstored entries of those blocks are missing, not zero
+    sharding = bool(int(hip.get('sparse_sharding', 0)))
+    observed_opt = hip.get('sparse_observed_only', 0)
+    observed = observed_only_blocks(Z, observed_opt, sharding)
+    build_model(eng, Z, precision, sparse_sharding=sharding, observed_only=observed_opt)
     upload_state(eng, Z, G)
     out = run_solver(eng, alg_options, nb_modes,
-                     has_missing=Z.get('miss') is not None and any(m is not None for m in Z['miss']))
+                     has_missing=bool(observed) or (Z.get('miss') is not None and any(m is not None for m in Z['miss'])))
     Fac = download_state(eng, Z, G)
     Zhat = []
     for p in range(len(Z['object'])):                                                 # :197-206

@@ -150,6 +150,20 @@ class Engine:
         capi.check(self.lib.aoadmm_resident_par2_rhs(self.h, int(p), int(tensor_mode), capi.dptr(out), C.byref(ms)))
         return (out, ms.value) if with_ms else out
 
+    def set_observed_only(self, p, on=True):
+        """Marks the sparse CP block p observed-only (`aoadmm_tensor_set_observed_only`): its stored entries are the
+        observations and every other entry is missing, fitted by the reference's EM step without a dense array.  For a
+        block uploaded with `upload_coo` (not sharded) that holds at least one entry; any later upload clears it."""
+        capi.check(self.lib.aoadmm_tensor_set_observed_only(self.h, int(p), int(bool(on))))
+
+    def em_step(self, p):
+        """One EM step of the observed-only block p with the current factors (`aoadmm_resident_em_step`):
+        (sum over the stored entries of (x - m)^2, num, den) of `f_rel_missing`; `resident_mttkrp` then returns the
+        MTTKRP of the imputed tensor as of this step."""
+        st = np.zeros(3)
+        capi.check(self.lib.aoadmm_resident_em_step(self.h, int(p), capi.dptr(st)))
+        return float(st[0]), float(st[1]), float(st[2])
+
     def resident_mttkrp(self, p, tensor_mode, rows, R):
         """One MTTKRP of the resident block p against the current factors (`aoadmm_resident_mttkrp`): rows x R."""
         out = np.zeros((rows, R), order='F')
@@ -168,8 +182,9 @@ class Engine:
 
     def kernel_stats(self, which, reset=False):
         """(ms, launches, bytes, flops) of a kernel class since the last reset (`aoadmm_kernel_stats`); which = 3:
-        MTTKRPs of sparse blocks (of a sharded block: this rank's share) and passes over the nonzeros of PARAFAC2
-        blocks with sparse slabs."""
+        MTTKRPs of sparse blocks (of a sharded block: this rank's share), passes over the nonzeros of PARAFAC2
+        blocks with sparse slabs and EM steps of observed-only blocks; which = 4 + n: the pass of those EM steps over
+        the copy of tensor mode n."""
         ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         capi.check(self.lib.aoadmm_kernel_stats(self.h, int(which), int(bool(reset)), C.byref(ms), C.byref(n),
                                                 C.byref(by), C.byref(fl)))

@@ -284,8 +284,25 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   std::vector<int> devices(1, 0);
   int precision = AOADMM_PREC_F64;
   bool sparse_sharding = false;                      // options.hip.sparse_sharding (default 0: sparse CP blocks replicated)
+  // options.hip.sparse_observed_only: 0 (default), 1 = every sparse CP block, or a list of 1-based block numbers: the
+  // unstored entries of those blocks are missing, not zero (aoadmm_tensor_set_observed_only)
+  bool observed_all = false;
+  std::vector<int> observed_list;
   if (const mxArray* hip = field(opt, "hip", false)) {
     if (const mxArray* f = field(hip, "sparse_sharding", false)) sparse_sharding = mxGetScalar(f) != 0;
+    if (const mxArray* f = field(hip, "sparse_observed_only", false)) {
+      if (mxIsCell(f) || mxIsEmpty(f))
+        mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.sparse_observed_only must be 0, 1 or a list of block numbers");
+      const mwSize ne = mxGetNumberOfElements(f);
+      if (ne == 1 && mxGetScalar(f) <= 1) {           // the scalars 0 and 1; any other value names blocks
+        observed_all = mxGetScalar(f) == 1;
+      } else {
+        if (!mxIsDouble(f)) mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.sparse_observed_only: a list of block numbers must be double");
+        for (mwSize i = 0; i < ne; ++i) observed_list.push_back((int)mxGetDoubles(f)[i] - 1);
+      }
+    }
+    if ((observed_all || !observed_list.empty()) && sparse_sharding)
+      mexErrMsgIdAndTxt("cmtf:hip:unsupported", "options.hip.sparse_observed_only is not available together with options.hip.sparse_sharding");
     if (const mxArray* d = field(hip, "device", false)) devices.assign(1, (int)mxGetScalar(d));
     if (const mxArray* d = field(hip, "devices", false)) {
       devices.clear();
@@ -432,6 +449,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       subs.insert(subs.end(), sk.begin(), sk.end());
       check(aoadmm_par2_slab_upload_coo(g_ctx, p, (int64_t)vals.size(), subs.data(), vals.data()));
     } else if (mxIsCell(obj)) {
+      if (std::find(observed_list.begin(), observed_list.end(), p) != observed_list.end())
+        mexErrMsgIdAndTxt("cmtf:hip:unsupported", "options.hip.sparse_observed_only: Z.object{%d} is a PARAFAC2 block", p + 1);
       std::vector<double> packed;                         // the slabs back to back, one transfer
       for (mwSize k = 0; k < mxGetNumberOfElements(obj); ++k) {
         const mxArray* xk = mxGetCell(obj, k);
@@ -443,7 +462,13 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       std::vector<int> md(mxGetNumberOfElements(mp));
       for (size_t i = 0; i < md.size(); ++i) md[i] = (int)mxGetDoubles(mp)[i] - 1;
       upload_sparse(p, obj, sz, md, sparse_sharding);    // values stay fp64 whatever options.hip.precision says
+      if (observed_all || std::find(observed_list.begin(), observed_list.end(), p) != observed_list.end()) {
+        check(aoadmm_tensor_set_observed_only(g_ctx, p, 1));
+        has_missing = true;                               // out.func_rel_missing and the display column as for Z.miss
+      }
     } else {
+      if (std::find(observed_list.begin(), observed_list.end(), p) != observed_list.end())
+        mexErrMsgIdAndTxt("cmtf:hip:unsupported", "options.hip.sparse_observed_only: Z.object{%d} is dense (use Z.miss)", p + 1);
       // 'f16': dense 3-way blocks without Z.miss are stored fp16 (AOADMM_PREC_F16), every other dense block fp32
       int prec_p = precision;
       if (precision == AOADMM_PREC_F16) {

@@ -8,7 +8,10 @@ function [G,out] = cmtf_fun_AOADMM_hip(Z,Znorm_const,G,fh,gh,lscalar,uscalar,opt
 %        [Fac,out] = cmtf_fun_AOADMM_hip(Z,Znorm_const, G,fh,gh,lscalar,uscalar,options);
 % Nothing else changes: Z, the 'init' struct, init_options and options keep their fields; optional
 % engine settings live in options.hip (device = 0 or devices = [0 1 ... 7] for several GPUs from this one
-% MATLAB process, precision = 'f64' | 'f32' | 'f16', par2_slab_sharding, sparse_sharding, no_permuted_copy).
+% MATLAB process, precision = 'f64' | 'f32' | 'f16', par2_slab_sharding, sparse_sharding, sparse_observed_only,
+% no_permuted_copy).  sparse_observed_only = 1 (every sparse CP block) or a list of block numbers: the entries an
+% sptensor does not store are MISSING, not zero, and are fitted by the EM step as Z.miss does for full data (Z.miss itself
+% stays refused for an sptensor, cmtf_AOADMM.m:77-79); not together with sparse_sharding.
 % 'f16': dense 3-way CP blocks without Z.miss are stored as fp16 with one power-of-two scale per block (half the bytes
 % of every tensor pass, 6 instead of 16 resident bytes per entry; the model is fitted to the quantised data), every other
 % dense block as fp32; not with several devices, not with no_permuted_copy = 1.

@@ -4,6 +4,7 @@ data on the same GPU.
     python3 tools/time_sparse.py [--dims 1000000,100000,10000] [--nnz 100000000] [--R 20] [--skew] [--reps 5]
     python3 tools/time_sparse.py --nvecs [--nvecs-iters 20] [--host-gram] ...
     python3 tools/time_sparse.py --as-rank 0 --of 8 [--skew] ...
+    python3 tools/time_sparse.py --observed-only [--out profiles/sparse_observed_time.jsonl] ...
 
 Prints one JSON line per (layout, mode) and a summary line.  Layouts: 'colmajor' gathers from the column-major factors
 (what aoadmm_resident_mttkrp sees before any solve), 'rowmajor' after one outer iteration, when the Gram kernel has left
@@ -26,6 +27,14 @@ nonzeros and row span.  --of takes a list (2,4,8); R is taken modulo each N, so 
 communicator has ONE rank: `allreduce_1rank_ms` is what is left of aoadmm_resident_mttkrp's own events after the
 kernels, i.e. a one-rank ncclAllReduce of I_n x R doubles on one GPU.  It says nothing about the all-reduce between
 GPUs, which this tool cannot time.
+--observed-only times the block marked observed-only (aoadmm_tensor_set_observed_only, csrc/sparse_em.hip) next to the
+plain block of the same data in the same process, one engine each, after one outer iteration of both (row-major gathers,
+and the observed block holds a snapshot).  Per mode: the median (min, max) over --reps of the plain MTTKRP, of the
+imputed MTTKRP (residual values + dense correction) and of the EM step's pass over that mode's copy (HIP events,
+aoadmm_kernel_stats(3) and (4 + n); the pass over the first copy carries the statistics with the snapshot's gathers),
+and their ratio next to N / (N - 1).  Then the statistics-only pass (first step after a new mark: no snapshot, residuals
+written), the whole EM step, and the wall time of one outer iteration of both engines (difference of solves of 3 and of
+1 iterations, unconstrained modes).  Every line also goes to --out.
 """
 from __future__ import annotations
 
@@ -61,6 +70,8 @@ def main():
     ap.add_argument('--host-gram', action='store_true')
     ap.add_argument('--as-rank', type=int, default=None)
     ap.add_argument('--of', default=None)
+    ap.add_argument('--observed-only', action='store_true')
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sparse_observed_time.jsonl'))
     a = ap.parse_args()
     if not a.no_torch:
         # torch (and the HIP runtime it ships) first, as bench.py does: loaded after the library, the process aborted in
@@ -71,7 +82,7 @@ def main():
     N, R, nnz = len(dims), a.R, int(a.nnz)
     if (a.as_rank is None) != (a.of is None):
         ap.error('--as-rank and --of go together')
-    if a.nvecs or a.of is not None:
+    if a.nvecs or a.of is not None or a.observed_only:
         a.no_torch = True
     rng = np.random.default_rng(a.seed)
     t0 = time.time()
@@ -85,7 +96,8 @@ def main():
     t_gen = time.time() - t0
     eng = pkg.Engine(0)
     try:
-        (run_nvecs if a.nvecs else run_share if a.of is not None else run)(a, eng, dims, N, R, nnz, subs, vals, t_gen)
+        (run_nvecs if a.nvecs else run_share if a.of is not None else run_observed if a.observed_only else run)(
+            a, eng, dims, N, R, nnz, subs, vals, t_gen)
     finally:
         eng.close()
 
@@ -219,6 +231,125 @@ def run_share(a, eng, dims, N, R, nnz, subs, vals, t_gen):
                     'resident_bytes': int(share_bytes)}), flush=True)
     finally:
         share_eng.close()
+
+
+def run_observed(a, eng, dims, N, R, nnz, subs, vals, t_gen):
+    lib = eng.lib
+    out = open(a.out, 'a')
+
+    def emit(r):
+        line = json.dumps(r)
+        print(line, flush=True)
+        out.write(line + '\n')
+        out.flush()
+
+    def solve(e, iters):
+        o = capi.Options()
+        o.MaxOuterIters, o.MaxInnerIters, o.use_dimtree = iters, 1, 1
+        res = capi.Result()
+        e.synchronize()
+        t0 = time.time()
+        capi.check(lib.aoadmm_solve(e.h, C.byref(o), C.byref(res)))
+        e.synchronize()
+        return (time.time() - t0) * 1e3
+
+    def set_factors(e):
+        rng = np.random.default_rng(a.seed + 1)
+        for m in range(N):
+            Um = np.asfortranarray(rng.random((dims[m], R)))
+            capi.check(lib.aoadmm_state_set(e.h, capi.F_FAC, m, 0, capi.dptr(Um), dims[m], R))
+
+    def prepare(e, observed):
+        h = e.h
+        capi.check(lib.aoadmm_model_begin(h, N, 1, 0))
+        for m, s in enumerate(dims):
+            capi.check(lib.aoadmm_model_set_mode(h, m, s, R))
+        capi.check(lib.aoadmm_model_add_cp(h, 0, N, (C.c_int * N)(*range(N)), 1.0))
+        for m in range(N):
+            capi.check(lib.aoadmm_model_set_coupling(h, m, -1, None, 0, 0, None, 0, 0))
+        capi.check(lib.aoadmm_model_end(h))
+        t0 = time.time()
+        e.upload_coo(0, subs, vals)
+        if observed:
+            e.set_observed_only(0)
+        e.synchronize()
+        t_up = time.time() - t0
+        set_factors(e)
+        solve(e, 1)                                   # row-major factor copies; the observed block takes its snapshot
+        return t_up
+
+    def mttkrp_once(e, n):
+        ms = C.c_float(0)
+        e.kernel_stats(3, reset=True)
+        capi.check(lib.aoadmm_resident_mttkrp(e.h, 0, n, None, C.byref(ms)))
+        kms, launches, by, _ = e.kernel_stats(3, reset=True)
+        assert launches == 1
+        return kms, by
+
+    def step_once(e):
+        """(ms of the whole EM step, [ms of the pass over every copy], [their algorithmic bytes])"""
+        for c in [3] + [4 + n for n in range(N)]:
+            e.kernel_stats(c, reset=True)
+        e.em_step(0)
+        whole = e.kernel_stats(3, reset=True)[0]
+        per = [e.kernel_stats(4 + n, reset=True) for n in range(N)]
+        return whole, [p[0] for p in per], [p[2] for p in per]
+
+    def mmm(v):
+        return [round(float(np.median(v)), 4), round(min(v), 4), round(max(v), 4)]
+
+    obs = pkg.Engine(0)
+    try:
+        t_up = prepare(eng, False)
+        t_up_obs = prepare(obs, True)
+        plain_bytes, obs_bytes = eng.tensor_storage_info(0)[2], obs.tensor_storage_info(0)[2]
+        emit({'what': 'setup', 'dims': dims, 'nnz_given': nnz, 'nnz_coalesced': int(plain_bytes // (N * (4 * N + 8))),
+              'R': R, 'skew': a.skew, 'reps': a.reps, 'gen_s': round(t_gen, 2), 'upload_s': round(t_up, 2),
+              'upload_observed_s': round(t_up_obs, 2), 'resident_bytes': int(plain_bytes),
+              'resident_bytes_observed': int(obs_bytes)})
+        for n in range(N):
+            mttkrp_once(eng, n), mttkrp_once(obs, n)
+        step_once(obs)                                # warm-up
+        plain, imputed, steps = [[] for _ in range(N)], [[] for _ in range(N)], []
+        for _ in range(a.reps):                       # alternating, same process, same data
+            for n in range(N):
+                plain[n].append(mttkrp_once(eng, n))
+                imputed[n].append(mttkrp_once(obs, n))
+            steps.append(step_once(obs))
+        for n in range(N):
+            pk, ik = [v[0] for v in plain[n]], [v[0] for v in imputed[n]]
+            ps = [s[1][n] for s in steps]
+            emit({'what': 'observed_mode', 'mode': n + 1, 'rows': dims[n], 'carries_statistics': n == 0,
+                  'plain_mttkrp_ms': mmm(pk), 'imputed_mttkrp_ms': mmm(ik), 'em_pass_ms': mmm(ps),
+                  'em_pass_GB': round(steps[0][2][n] / 1e9, 3),
+                  'em_pass_TBps': round(steps[0][2][n] / float(np.median(ps)) / 1e9, 3),
+                  'em_pass_over_plain_mttkrp': round(float(np.median(ps)) / float(np.median(pk)), 3),
+                  'imputed_over_plain_mttkrp': round(float(np.median(ik)) / float(np.median(pk)), 3),
+                  'N_over_N_minus_1': round(N / (N - 1.0), 3)})
+        emit({'what': 'observed_step', 'em_step_ms': mmm([s[0] for s in steps]),
+              'passes_ms_sum': round(float(np.median([sum(s[1]) for s in steps])), 4)})
+        # the pass of a first step: statistics without a snapshot
+        first = []
+        for _ in range(a.reps):
+            obs.set_observed_only(0)
+            first.append(step_once(obs)[1][0])
+        emit({'what': 'observed_first_pass', 'statistics_pass_no_snapshot_ms': mmm(first)})
+        # one outer iteration, wall: solves of 3 and of 1 iterations from the same factors
+        it = {}
+        for name, e in (('plain', eng), ('observed', obs)):
+            w = []
+            for _ in range(a.reps):
+                set_factors(e)
+                t1 = solve(e, 1)
+                set_factors(e)
+                t3 = solve(e, 3)
+                w.append((t3 - t1) / 2)
+            it[name] = w
+        emit({'what': 'observed_iteration', 'plain_iter_ms_wall': mmm(it['plain']), 'observed_iter_ms_wall': mmm(it['observed']),
+              'ratio': round(float(np.median(it['observed'])) / float(np.median(it['plain'])), 3)})
+    finally:
+        obs.close()
+        out.close()
 
 
 def run(a, eng, dims, N, R, nnz, subs, vals, t_gen):
