@@ -154,7 +154,11 @@ typedef struct aoadmm_options {
                                             on every rank unless it has >= 1024 slabs per rank), 1 = shard the slabs
                                             over the ranks, -1 = never.  Blocks with Z.miss or the tPARAFAC2 constraint
                                             are always repeated */
-  int32_t reserved[5];
+  int32_t heldout_patience;              /* engine option: k > 0 stops the solve after iteration i when H_i = sum over the
+                                            blocks with a held-out list of w_p * sum (y - m)^2 has not been strictly below
+                                            its best value so far for k consecutive iterations (exit_code 2); 0 = off.
+                                            k > 0 with no list attached: AOADMM_ERR_INVALID before any work */
+  int32_t reserved[4];
 } aoadmm_options;
 
 /* `out` struct of cmtf_fun_AOADMM.m:480-494.  Arrays are caller-allocated with
@@ -163,7 +167,9 @@ typedef struct aoadmm_options {
 typedef struct aoadmm_result {
   double f_tensors, f_couplings, f_constraints, f_PAR2_couplings;
   int32_t OuterIterations;
-  int32_t exit_code;            /* 0 = 'maxIterations', 1 = stopping rule met (make_exit_flag.m) */
+  int32_t exit_code;            /* 0 = 'maxIterations', 1 = stopping rule met (make_exit_flag.m), 2 = stopped by
+                                   aoadmm_options.heldout_patience (when both rules fire in one iteration: 1;
+                                   a rule that fires in iteration MaxOuterIters reports 0, as before) */
   int32_t exit_abs[4];          /* per quantity: 1 = 'AbsFuncTol', 0 = 'RelFuncTol' */
   double *func_val_conv, *func_coupl_conv, *func_constr_conv, *func_PAR2_coupl, *time_at_it;
   double *innerIters;
@@ -330,6 +336,46 @@ int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out);
  * PARAFAC2 data.  No device work. */
 int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes);
 
+/* ---- held-out entries ---------------------------- */
+/* The model of block p for the current AOADMM_F_FAC state at n subscripts: out[e] = sum_r prod_m F_m(s_m, r) for a CP
+ * block, sum_r A(i, r) B_k(j, r) C(k, r) for a PARAFAC2 block with subscripts (i, j within slab k, k).  subs is
+ * column-major n x n_tensor_modes, 0-based, the layout aoadmm_tensor_upload_coo takes; out is n doubles on the host, in
+ * the caller's order.  Needs a finished model (aoadmm_model_end) and the factors of the block's modes
+ * (aoadmm_state_set); the block need not hold data.  A subscript out of range (j >= J_k included) or a missing factor
+ * is AOADMM_ERR_INVALID; n = 0 does nothing.  Only factors are read, so the answer is the same for dense, sparse,
+ * sharded and row-sharded blocks and on every rank of a communicator (no collective).  No array of the tensor's size
+ * exists.  Bitwise reproducible. */
+int aoadmm_resident_model_at(aoadmm_ctx* ctx, int p, int64_t n, const int64_t* subs, double* out);
+/* Attaches (n > 0) or removes (n = 0) the HELD-OUT LIST of block p: n entries (subs as above, vals n doubles) that were
+ * kept out of the fit.  Duplicates are allowed and each is scored; whether an entry is also stored in the block's data
+ * is the caller's business (documented, not checked).  A subscript out of range or a value that is not finite is
+ * AOADMM_ERR_INVALID and the previous list stays.  Resident: 4 N + 8 bytes per entry (int32 subscripts, fp64 value), in
+ * the caller's order; aoadmm_tensor_storage_info does not count them (aoadmm_heldout_info does).  The list belongs to
+ * the MODEL: aoadmm_model_begin drops it, a new upload of the block's data keeps it.  With a list attached every
+ * evaluation of the objective inside aoadmm_solve (the starting point included) also scores the list against the
+ * factors that evaluation uses; the sums travel in the solve's one read-back per outer iteration and are kept as a
+ * trace (aoadmm_heldout_trace).  Nothing else the solve computes changes: factors, duals, innerIters and the objective
+ * traces are bit for bit those of the solve without a list.  With a communicator every rank attaches the same list
+ * and does the same work (no collective, bit-identical ranks); a PARAFAC2 block with a list is never slab-sharded
+ * (aoadmm_options.par2_slab_sharding is ignored for it). */
+int aoadmm_tensor_set_heldout(aoadmm_ctx* ctx, int p, int64_t n, const int64_t* subs, const double* vals);
+/* stats = {sum (y - m)^2, sum y^2, sum m^2, n as a double} of block p's list for the current factors, outside a solve
+ * (relative error sqrt(stats[0] / stats[1]), RMSE sqrt(stats[0] / stats[3])).  AOADMM_ERR_INVALID without a list. */
+int aoadmm_resident_heldout_stats(aoadmm_ctx* ctx, int p, double stats[4]);
+/* *n = entries of block p's list (0: none), *resident_bytes = n (4 N + 8), *row_major = what the block's last held-out
+ * pass (aoadmm_resident_model_at, aoadmm_resident_heldout_stats or inside a solve) gathered from: 1 the row-major
+ * factor copies the Gram kernel leaves (current inside a solve), 0 the column-major factors (after aoadmm_state_set),
+ * -1 no pass yet.  Each output may be NULL.  No device work. */
+int aoadmm_heldout_info(aoadmm_ctx* ctx, int p, int64_t* n, int64_t* resident_bytes, int* row_major);
+/* After aoadmm_solve: out[i] = sum (y - m)^2 of block p's list at iteration i = 0 .. OuterIterations (at most cap
+ * entries are written), *len = OuterIterations + 1 (0 when the block had no list), *best_iter = the iteration at which
+ * H_i = sum over the blocks with a list of w_p * sum (y - m)^2 was smallest (the first such; -1 without a list).  The
+ * factors a solve returns are those of its LAST iteration; the solve is bit-reproducible, so a second solve from the
+ * same state with MaxOuterIters = *best_iter returns the best model (no snapshot is kept).  Each output may be NULL.
+ * aoadmm_resident_model_at, aoadmm_tensor_set_heldout and aoadmm_resident_heldout_stats answer AOADMM_ERR_UNSUPPORTED
+ * on a multi-device context (aoadmm_create_multi with more than one device). */
+int aoadmm_heldout_trace(aoadmm_ctx* ctx, int p, double* out, int cap, int* len, int* best_iter);
+
 /* ---- state (the struct G) ---------------------------------------------- */
 /* slab = k for cell-valued fields (PARAFAC2 B mode, P, mu_DeltaB), else 0.  slab = AOADMM_ALL_SLABS moves
  * all K cells at once: host holds them back to back, each J_k x R column-major, rows = sum J_k. */
@@ -360,7 +406,9 @@ int aoadmm_resident_par2_rhs(aoadmm_ctx* ctx, int p, int tensor_mode, double* ou
  * dense correction; which = 4 + n (n = 0 .. 7): the pass of those EM steps over the copy of tensor mode n alone (the
  * residuals x - m; n = 0 also carries the statistics, and is the whole of a statistics-only step).  Of a sharded
  * sparse block: this rank's share (its nonzeros, and the rows of its span as the output written); the all-reduce is
- * outside the events */
+ * outside the events; which = 12: the held-out passes (aoadmm_resident_model_at, aoadmm_resident_heldout_stats and the pass
+ * of every objective evaluation of a solve with a list attached: one launch each; bytes = subscripts and values streamed
+ * + factor rows gathered, flops = n * R * N + 8 n for the sums) */
 int aoadmm_kernel_stats(aoadmm_ctx* ctx, int which, int reset, double* contract_ms, int64_t* contract_launches,
                         double* contract_bytes, double* contract_flops);
 

@@ -448,6 +448,41 @@ int aoadmm_resident_em_step(aoadmm_ctx* ctx, int p, double stats[3]) {
     });
   });
 }
+// Held-out scoring answers on one engine (which may belong to a communicator); a multi-device context would have to
+// keep one list per engine for no gain: it is refused
+static void require_single_engine(aoadmm_ctx* ctx, const char* what) {
+  if (ctx->multi && ctx->multi->eng.size() > 1)
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("%s is not available on a multi-device context (aoadmm_create_multi with more than one device): use one context per rank and a communicator", what));
+}
+int aoadmm_resident_model_at(aoadmm_ctx* ctx, int p, int64_t n, const int64_t* subs, double* out) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_resident_model_at");
+    ctx->eng->model_at(p, n, subs, out);
+  });
+}
+int aoadmm_tensor_set_heldout(aoadmm_ctx* ctx, int p, int64_t n, const int64_t* subs, const double* vals) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_tensor_set_heldout");
+    ctx->eng->set_heldout(p, n, subs, vals);
+  });
+}
+int aoadmm_resident_heldout_stats(aoadmm_ctx* ctx, int p, double stats[4]) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_resident_heldout_stats");
+    ctx->eng->heldout_stats(p, stats);
+  });
+}
+int aoadmm_heldout_info(aoadmm_ctx* ctx, int p, int64_t* n, int64_t* resident_bytes, int* row_major) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] { ctx->eng->heldout_info(p, n, resident_bytes, row_major); });   // no device work
+}
+int aoadmm_heldout_trace(aoadmm_ctx* ctx, int p, double* out, int cap, int* len, int* best_iter) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] { ctx->eng->heldout_trace(p, out, cap, len, best_iter); });      // no device work
+}
 int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes) {
   CTX_OR_FAIL(ctx);
   // no collective and no device work: rank 0's engine answers for a multi-device context (every rank holds the same

@@ -15,6 +15,7 @@
 #include "contract.h"
 #include "couple.h"
 #include "cpblock.h"
+#include "heldout.h"
 #include "misc.h"
 #include "par2.h"
 #include "par2_sparse.h"
@@ -109,6 +110,12 @@ struct TensorInfo {
   double normsq = 0.0;
   bool normsq_valid = false;
   int last_pos = -1;
+  // held-out list (aoadmm_tensor_set_heldout): belongs to the model, not to the data; every evaluation of the objective
+  // inside a solve also scores it (heldout.h)
+  HeldoutList ho;
+  int ho_row_major = -1;        // what the block's last held-out pass gathered from: 1 the row-major factor copies, 0 the
+                                // column-major factors, -1 no pass yet
+  std::vector<double> ho_trace; // sum (y - m)^2 at iteration 0 .. OuterIterations of the last solve
   bool eval_shortcut = false;   // PARAFAC2: the enqueued objective evaluation took the last_mttkrp shortcut (:1254-1260)
   bool masked() const { return par2 ? p2.has_mask : blk.has_mask; }   // Z.miss{p} given
   bool observed_only() const { return !par2 && blk.sparse && blk.sem.on; }   // sparse block whose unstored entries are missing
@@ -177,6 +184,12 @@ class Engine {
   void solve(const aoadmm_options& opt, aoadmm_result* out);
   void resident_mttkrp(int p, int pos, double* out_host, float* ms);
   void resident_em_step(int p, double stats[3]);   // one EM step of an observed-only block: {sum_Omega (x-m)^2, num, den}
+  // held-out scoring (heldout.h)
+  void model_at(int p, int64_t n, const int64_t* subs, double* out_host);     // the model of block p at n subscripts
+  void set_heldout(int p, int64_t n, const int64_t* subs, const double* vals);   // n = 0 removes the list
+  void heldout_stats(int p, double stats[4]);      // {sum (y-m)^2, sum y^2, sum m^2, count} for the current factors
+  void heldout_info(int p, int64_t* n, int64_t* resident_bytes, int* row_major) const;
+  void heldout_trace(int p, double* out, int cap, int* len, int* best_iter) const;
   void resident_unfold_gram(int p, int pos, int slab, double* out_host);
   void resident_nvecs(int p, int pos, int r, const aoadmm_nvecs_options* opt, double* U_host, int64_t ldU, double* eig_host,
                       aoadmm_nvecs_info* info);
@@ -234,6 +247,10 @@ class Engine {
   bool has_missing() const;
   void em_pass_enqueue(int p, int update, bool fuse_next_pass = false);   // statistics of tensor p into its EM slots (+ imputation)
   void sparse_em_enqueue(int p, bool stats_only);  // EM step of an observed-only sparse block into its EM slots
+  bool has_heldout() const;
+  HeldoutFactors heldout_factors(const TensorInfo& t, bool* row_major) const;   // the current fac state of block t as the pass gathers it
+  void heldout_check_subs(const TensorInfo& t, int p, int64_t n, const int64_t* subs, std::vector<int>& idx32) const;
+  void heldout_enqueue(int p, double* sums);       // block p's list against the current factors -> sums[0..2] (device)
   void compute_gram(ModeInfo& mi, const LoopEnd* close = nullptr);
   FactorRef factor_ref(const ModeInfo& o) const {
     return FactorRef{o.fac.d(), o.rows, o.version, o.facT_version == o.version ? o.facT.d() : nullptr};
@@ -310,6 +327,7 @@ class Engine {
   DevBuf atbws_;
   DevBuf staging_;
   LaunchTimers timers_;   // event pool and kernel statistics (cpblock.h)
+  int ho_best_iter_ = -1;   // iteration of the smallest weighted held-out sum of the last solve (-1: no list was attached)
   int prepared_mode_ = -1;  // mode whose MTTKRP + system build were enqueued ahead (prepare_next_first_mode)
   ncclComm_t comm_ = nullptr;
   mutable std::mutex comm_mu_;          // comm_ / aborted_ against comm_abort() from another worker thread

@@ -18,6 +18,8 @@ void Engine::eval_objective_enqueue(bool first) {
     k.kind = kind; k.slot = slot; k.x = x; k.y = y; k.n = n;
     rb.add(k);
   };
+  for (int p = 0; p < n_tensors_; ++p)           // held-out lists: scored against the fac state this evaluation uses
+    if (tensors_[p].ho.n > 0) heldout_enqueue(p, dev_.heldout(p));
   for (int p = 0; p < n_tensors_; ++p) {
     TensorInfo& t = tensors_[p];
     const bool masked = t.masked();

@@ -228,6 +228,9 @@ struct SolveRun {
   bool has_miss = false;
   double f[4] = {0, 0, 0, 0};                       // f_tensors, f_couplings, f_constraints, f_PAR2_couplings
   double f_rel_missing = 0.0;
+  bool has_ho = false;                              // some block has a held-out list
+  double ho_best = 0.0;                             // smallest H_i = sum_p w_p sum (y - m)^2 so far ...
+  int ho_bad = 0;                                   // ... and the iterations since that were not strictly below it
   std::chrono::steady_clock::time_point t0;
 };
 
@@ -297,7 +300,8 @@ void Engine::solve_setup(const aoadmm_options& opt) {
 void Engine::decide_slab_sharding(TensorInfo& t, const aoadmm_options& opt) {
   Par2Block& b = t.p2;
   const ModeInfo& mB = modes_[t.modes[1]];
-  const bool can = sharded() && world_ > 1 && !b.has_mask && !b.sparse && !(mB.constrained && mB.prox.type == AOADMM_C_TPARAFAC2) &&
+  // (a held-out list is scored inside the solve from this rank's B_k: the block is repeated then)
+  const bool can = sharded() && world_ > 1 && !b.has_mask && !b.sparse && t.ho.n == 0 && !(mB.constrained && mB.prox.type == AOADMM_C_TPARAFAC2) &&
                    modes_[t.modes[2]].coupling < 0;     // a coupled C mode needs every row system on every rank
   const bool want = opt.par2_slab_sharding > 0 || (opt.par2_slab_sharding == 0 && b.K / world_ >= 1024);
   const int per = (int)cdiv(b.K, world_);
@@ -401,6 +405,18 @@ void Engine::record_iteration(SolveRun& r, int iter) {
   if (out->time_at_it)
     out->time_at_it[iter] = iter == 0 ? 0.0 : std::chrono::duration<double>(std::chrono::steady_clock::now() - r.t0).count();
   if (out->func_rel_missing && (iter == 0 || r.has_miss)) out->func_rel_missing[iter] = r.f_rel_missing;
+  if (r.has_ho) {                                    // the held-out sums came in the same read-back
+    double H = 0.0;
+    for (int p = 0; p < n_tensors_; ++p) {
+      TensorInfo& t = tensors_[p];
+      if (t.ho.n == 0) continue;
+      const double v = r.host.heldout(p)[kHoRes];
+      t.ho_trace.push_back(v);
+      H += t.weight * v;
+    }
+    if (iter == 0 || H < r.ho_best) { r.ho_best = H; ho_best_iter_ = iter; r.ho_bad = 0; }
+    else ++r.ho_bad;
+  }
   if (iter == 0 || !out->innerIters) return;
   for (int m = 0; m < n_modes_; ++m) {
     const ModeInfo& mi = modes_[m];
@@ -418,10 +434,16 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
   AO_REQUIRE(model_done_, "call aoadmm_model_end first");
   AO_REQUIRE(out != nullptr, "null result");
   AO_REQUIRE(opt.MaxOuterIters >= 0 && opt.MaxInnerIters >= 1, "bad iteration limits");
+  const bool has_ho = has_heldout();
+  AO_REQUIRE(opt.heldout_patience >= 0, "heldout_patience = %d < 0", opt.heldout_patience);
+  AO_REQUIRE(opt.heldout_patience == 0 || has_ho, "heldout_patience = %d needs a held-out list (aoadmm_tensor_set_heldout)", opt.heldout_patience);
   AO_HIP(hipSetDevice(device_));
+  ho_best_iter_ = -1;
+  for (TensorInfo& t : tensors_) t.ho_trace.clear();
   solve_setup(opt);
   SolveRun r{opt, out};
   r.has_miss = has_missing();
+  r.has_ho = has_ho;
   r.pin.alloc(readback_.bytes);
   r.host = arena_.at(r.pin.p);
 
@@ -437,8 +459,8 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
   const double* f = r.f;
   double fo[4];
   int iter = 1;
-  bool stop = false;
-  while (iter <= opt.MaxOuterIters && !stop) {                                 // :87
+  bool stop = false, ho_stop = false;
+  while (iter <= opt.MaxOuterIters && !stop && !ho_stop) {                     // :87
     outer_updates(opt, iter, r.has_miss);
     for (int i = 0; i < 4; ++i) fo[i] = f[i];
     enqueue_objective(r, iter);
@@ -448,6 +470,7 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
     stop = stop_one(f[0], fo[0], opt) && stop_one(f[1], fo[1], opt) && stop_one(f[2], fo[2], opt) &&
            stop_one(f[3], fo[3], opt);                                         // :456
     if (r.has_miss) stop = stop && (r.f_rel_missing < opt.OuterRelTol);        // :457-459
+    ho_stop = opt.heldout_patience > 0 && r.ho_bad >= opt.heldout_patience;    // held-out early stopping (heldout.h)
     if (report && iter % progress_every_ == 0) progress_fn_(progress_user_, iter, r.f, r.f_rel_missing);   // :462-468
     ++iter;
   }
@@ -457,7 +480,7 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
     if (tensors_[p].par2) par2_gather_slabs(tensors_[p]);
   AO_HIP(hipStreamSynchronize(stream_));
   out->OuterIterations = iter - 1;
-  out->exit_code = iter > opt.MaxOuterIters ? 0 : 1;                           // make_exit_flag.m:4-5
+  out->exit_code = iter > opt.MaxOuterIters ? 0 : stop ? 1 : 2;                // make_exit_flag.m:4-5; 2: heldout_patience
   for (int i = 0; i < 4; ++i) out->exit_abs[i] = f[i] < opt.AbsFuncTol ? 1 : 0;
 }
 }  // namespace aoadmm

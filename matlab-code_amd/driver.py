@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _capi as capi
 from .engine import Engine, constraint_descriptor, default_engine
-from .sptensor import coo_of, pack_par2_slabs
+from .sptensor import coo_of, pack_par2_slabs, sptensor
 from .sptensor import slab_gram as _sparse_slab_gram
 from .sptensor import unfold_gram as _sparse_unfold_gram
 
@@ -326,6 +326,7 @@ def _make_options(alg_options):
     o.use_dimtree = int(hip.get('use_dimtree', 1))
     o.no_permuted_copy = int(hip.get('no_permuted_copy', 0))
     o.par2_slab_sharding = int(hip.get('par2_slab_sharding', 0))
+    o.heldout_patience = int(hip.get('heldout_patience', 0))
     return o
 
 
@@ -366,6 +367,63 @@ def observed_only_blocks(Z, observed_only, sparse_sharding=False):
         raise _unsupported('sparse_observed_only is not available together with sparse_sharding: an observed-only '
                            'block is replicated')
     return blocks
+
+
+def heldout_lists(Z, heldout, patience=0):
+    """`alg_options['hip']['heldout']` -> {0-based block: (subs n x N int64 0-based, vals n float64)}, checked on the
+    host before the engine is touched.  `heldout` maps 1-based block numbers to `(subs, vals)` or to an `sptensor` of the
+    block's size (its stored entries are the list); None / {} -> no list.  For a PAR2 block the subscripts are
+    (i, j within slab k, k).  ValueError: a block the model does not have, subs that are not n x N, not integers or out
+    of range, len(vals) != n, a value that is not finite, and `patience` > 0 (or not a non-negative integer) without
+    any list."""
+    P = len(Z['object'])
+    if patience is None or isinstance(patience, bool) or int(patience) != patience or int(patience) < 0:
+        raise ValueError('heldout_patience must be a non-negative integer, got %r' % (patience,))
+    lists = {}
+    if heldout is not None and not isinstance(heldout, dict):
+        raise ValueError('heldout must be a dict {1-based block number: (subs, vals) or sptensor}')
+    for q, item in (heldout or {}).items():
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or q < 1 or q > P:
+            raise ValueError('heldout names Z.object{%s}: the model has %d blocks' % (q, P))
+        p = int(q) - 1
+        md = [m - 1 for m in Z['modes'][p]]
+        par2 = Z['model'][p] == 'PAR2'
+        shape = [int(Z['size'][md[0]]), None, int(Z['size'][md[2]])] if par2 else [int(Z['size'][m]) for m in md]
+        if isinstance(item, sptensor):
+            if par2 or tuple(item.shape) != tuple(shape):
+                raise ValueError('heldout{%d}: an sptensor must have the size of the CP block Z.object{%d}' % (q, q))
+            subs, vals = item.subs, item.vals
+        else:
+            try:
+                subs, vals = item
+            except (TypeError, ValueError):
+                raise ValueError('heldout{%d} must be (subs, vals) or an sptensor' % q) from None
+        subs = np.asarray(subs)
+        vals = np.asarray(vals, dtype=np.float64).reshape(-1)
+        if subs.ndim != 2 or subs.shape[1] != len(md):
+            raise ValueError('heldout{%d}: subs must be n x %d, got %s' % (q, len(md), subs.shape))
+        if subs.shape[0] != vals.shape[0]:
+            raise ValueError('heldout{%d}: %d subscripts but %d values' % (q, subs.shape[0], vals.shape[0]))
+        if not np.issubdtype(subs.dtype, np.integer):
+            if not (np.issubdtype(subs.dtype, np.floating) and np.all(np.isfinite(subs)) and np.all(subs == np.floor(subs))):
+                raise ValueError('heldout{%d}: subscripts must be integers' % q)
+        subs = subs.astype(np.int64)
+        if not np.all(np.isfinite(vals)):
+            raise ValueError('heldout{%d}: a value is not finite' % q)
+        for m in range(len(md)):
+            if par2 and m == 1:
+                continue
+            if subs.shape[0] and (subs[:, m].min() < 0 or subs[:, m].max() >= shape[m]):
+                raise ValueError('heldout{%d}: a subscript of mode %d is outside [0, %d)' % (q, m + 1, shape[m]))
+        if par2 and subs.shape[0]:
+            Jk = np.asarray([int(v) for v in Z['size'][md[1]]], dtype=np.int64)
+            if subs[:, 1].min() < 0 or np.any(subs[:, 1] >= Jk[subs[:, 2]]):
+                raise ValueError('heldout{%d}: a subscript of mode 2 is outside its slab' % q)
+        if subs.shape[0]:
+            lists[p] = (np.ascontiguousarray(subs), np.ascontiguousarray(vals))
+    if int(patience) > 0 and not lists:
+        raise ValueError('heldout_patience = %d needs a held-out list (alg_options.hip.heldout)' % int(patience))
+    return lists
 
 
 def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0):
@@ -670,6 +728,8 @@ def run_solver(eng, alg_options, nb_modes, has_missing=False):
     names = ['f_tensors', 'f_couplings', 'f_constraints', 'f_PAR2_couplings']
     if res.exit_code == 0:
         out['exit_flag'] = 'maxIterations'                                   # make_exit_flag.m:4-5
+    elif res.exit_code == 2:
+        out['exit_flag'] = 'heldoutPatience'                                 # alg_options.hip.heldout_patience
     else:
         out['exit_flag'] = {nm: ('AbsFuncTol' if res.exit_abs[i] else 'RelFuncTol') for i, nm in enumerate(names)}
     return out
@@ -714,10 +774,25 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
     sharding = bool(int(hip.get('sparse_sharding', 0)))
     observed_opt = hip.get('sparse_observed_only', 0)
     observed = observed_only_blocks(Z, observed_opt, sharding)
+    # alg_options['hip']['heldout'] = {1-based block: (subs, vals) | sptensor} and ['heldout_patience'] (`heldout_lists`):
+    # entries kept out of the fit, scored on the device with every evaluation of the objective
+    held = heldout_lists(Z, hip.get('heldout'), hip.get('heldout_patience', 0))
     build_model(eng, Z, precision, sparse_sharding=sharding, observed_only=observed_opt)
+    for p, (hs, hv) in sorted(held.items()):
+        eng.set_heldout(p, hs, hv)
     upload_state(eng, Z, G)
     out = run_solver(eng, alg_options, nb_modes,
                      has_missing=bool(observed) or (Z.get('miss') is not None and any(m is not None for m in Z['miss'])))
+    if held:
+        # out.func_heldout{block}: sum (y - m)^2 at iteration 0 .. OuterIterations; with heldout_sumsq = sum y^2 and
+        # heldout_count the relative error sqrt(func_heldout / heldout_sumsq) and the RMSE sqrt(func_heldout /
+        # heldout_count) follow.  The factors returned are those of the LAST iteration: a run from the same init with
+        # MaxOuterIters = heldout_best_iter returns the best model (the solve is bit-reproducible)
+        out['func_heldout'], out['heldout_sumsq'], out['heldout_count'] = {}, {}, {}
+        for p, (hs, hv) in sorted(held.items()):
+            out['func_heldout'][p + 1], out['heldout_best_iter'] = eng.heldout_trace(p)
+            out['heldout_sumsq'][p + 1] = float(np.sum(hv * hv))
+            out['heldout_count'][p + 1] = int(hv.shape[0])
     Fac = download_state(eng, Z, G)
     Zhat = []
     for p in range(len(Z['object'])):                                                 # :197-206

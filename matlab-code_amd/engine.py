@@ -164,6 +164,62 @@ class Engine:
         capi.check(self.lib.aoadmm_resident_em_step(self.h, int(p), capi.dptr(st)))
         return float(st[0]), float(st[1]), float(st[2])
 
+    # ---- held-out scoring ------------------------------------------------------------
+    @staticmethod
+    def _subs_f(subs, what):
+        subs = np.asarray(subs, dtype=np.int64)
+        if subs.ndim != 2:
+            raise ValueError('%s: subs must be n x N' % what)
+        return np.asfortranarray(subs)                # column-major n x N (the layout of sptensor.subs)
+
+    def model_at(self, p, subs):
+        """The model of block p for the current factors at the subscripts `subs` (n x N, 0-based; a PARAFAC2 block:
+        (i, j within slab k, k)), in the caller's order (`aoadmm_resident_model_at`).  Needs the model and the factor
+        state, not the block's data; no array of the tensor's size exists."""
+        subs = self._subs_f(subs, 'model_at')
+        out = np.zeros(subs.shape[0])
+        capi.check(self.lib.aoadmm_resident_model_at(self.h, int(p), int(subs.shape[0]),
+                                                     subs.ctypes.data_as(C.POINTER(C.c_int64)), capi.dptr(out)))
+        return out
+
+    def set_heldout(self, p, subs, vals):
+        """Attaches the held-out list of block p (`aoadmm_tensor_set_heldout`): subs n x N, 0-based; vals n.  An empty
+        list removes it.  Duplicates are scored once each.  The list belongs to the model: `build_model` drops it, a new
+        upload of the block's data keeps it.  A solve then scores it with every evaluation of the objective."""
+        vals = np.ascontiguousarray(np.asarray(vals, dtype=np.float64).reshape(-1))
+        if vals.shape[0] == 0:
+            capi.check(self.lib.aoadmm_tensor_set_heldout(self.h, int(p), 0, None, None))
+            return
+        subs = self._subs_f(subs, 'set_heldout')
+        if subs.shape[0] != vals.shape[0]:
+            raise ValueError('set_heldout: subs must be n x N with n = len(vals)')
+        capi.check(self.lib.aoadmm_tensor_set_heldout(self.h, int(p), int(vals.shape[0]),
+                                                      subs.ctypes.data_as(C.POINTER(C.c_int64)), capi.dptr(vals)))
+
+    def heldout_stats(self, p):
+        """(sum (y - m)^2, sum y^2, sum m^2, n) of block p's held-out list for the current factors
+        (`aoadmm_resident_heldout_stats`); `AoadmmError` (ERR_INVALID) without a list."""
+        st = np.zeros(4)
+        capi.check(self.lib.aoadmm_resident_heldout_stats(self.h, int(p), capi.dptr(st)))
+        return float(st[0]), float(st[1]), float(st[2]), int(st[3])
+
+    def heldout_info(self, p):
+        """dict(n, resident_bytes, row_major) of block p's held-out list (`aoadmm_heldout_info`): n (4 N + 8) bytes;
+        row_major: 1 when the block's last held-out pass gathered from the row-major factor copies, 0 from the
+        column-major factors, -1 before any pass."""
+        n, nb, rm = C.c_int64(0), C.c_int64(0), C.c_int(-1)
+        capi.check(self.lib.aoadmm_heldout_info(self.h, int(p), C.byref(n), C.byref(nb), C.byref(rm)))
+        return dict(n=n.value, resident_bytes=nb.value, row_major=rm.value)
+
+    def heldout_trace(self, p):
+        """(trace, best_iter) of the last solve (`aoadmm_heldout_trace`): sum (y - m)^2 of block p's list at iteration
+        0 .. OuterIterations (empty without a list) and the iteration of the smallest weighted sum over the blocks."""
+        ln, best = C.c_int(0), C.c_int(-1)
+        capi.check(self.lib.aoadmm_heldout_trace(self.h, int(p), None, 0, C.byref(ln), C.byref(best)))
+        out = np.zeros(max(ln.value, 1))
+        capi.check(self.lib.aoadmm_heldout_trace(self.h, int(p), capi.dptr(out), ln.value, C.byref(ln), C.byref(best)))
+        return out[:ln.value].copy(), best.value
+
     def resident_mttkrp(self, p, tensor_mode, rows, R):
         """One MTTKRP of the resident block p against the current factors (`aoadmm_resident_mttkrp`): rows x R."""
         out = np.zeros((rows, R), order='F')
@@ -184,7 +240,7 @@ class Engine:
         """(ms, launches, bytes, flops) of a kernel class since the last reset (`aoadmm_kernel_stats`); which = 3:
         MTTKRPs of sparse blocks (of a sharded block: this rank's share), passes over the nonzeros of PARAFAC2
         blocks with sparse slabs and EM steps of observed-only blocks; which = 4 + n: the pass of those EM steps over
-        the copy of tensor mode n."""
+        the copy of tensor mode n; which = 12: the held-out passes."""
         ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         capi.check(self.lib.aoadmm_kernel_stats(self.h, int(which), int(bool(reset)), C.byref(ms), C.byref(n),
                                                 C.byref(by), C.byref(fl)))

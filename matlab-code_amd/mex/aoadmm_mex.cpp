@@ -19,6 +19,7 @@
  * MATLAB implementation.
  */
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -504,6 +505,38 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     }
   }
 
+  // ---- options.hip.heldout: a cell per block of a struct with `subs` (n x N, 1-based as MATLAB has them; a PARAFAC2
+  // block: i, j within slab k, k) and `vals` (n): entries kept out of the fit, scored on the device with every
+  // evaluation of the objective (aoadmm_tensor_set_heldout).  Empty cells and blocks beyond the cell have no list.
+  std::vector<char> has_list(P, 0);
+  if (const mxArray* hip = field(opt, "hip", false))
+    if (const mxArray* ho = field(hip, "heldout", false)) {
+      if (!mxIsCell(ho) || mxGetNumberOfElements(ho) > (mwSize)P)
+        mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.heldout must be a cell with at most one entry per block of Z.object");
+      for (mwSize p = 0; p < mxGetNumberOfElements(ho); ++p) {
+        const mxArray* e = mxGetCell(ho, p);
+        if (!e || mxIsEmpty(e)) continue;
+        if (!mxIsStruct(e)) mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.heldout{%d} must be a struct with subs and vals", (int)p + 1);
+        const mxArray* hs = field(e, "subs");
+        const mxArray* hv = field(e, "vals");
+        const mwSize N = mxGetNumberOfElements(mxGetCell(modes, p));
+        const mwSize n = mxGetNumberOfElements(hv);
+        if (!mxIsDouble(hs) || !mxIsDouble(hv) || mxIsComplex(hv) || mxGetM(hs) != n || mxGetN(hs) != N)
+          mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.heldout{%d}: subs must be a double n x %d array and vals n real doubles",
+                            (int)p + 1, (int)N);
+        if (n == 0) continue;
+        std::vector<int64_t> s0((size_t)n * N);              // column-major n x N as subs is; 1-based -> 0-based
+        const double* sd = mxGetDoubles(hs);
+        for (size_t i = 0; i < s0.size(); ++i) {
+          if (sd[i] != std::floor(sd[i]))
+            mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.heldout{%d}: subscripts must be integers", (int)p + 1);
+          s0[i] = (int64_t)sd[i] - 1;
+        }
+        check(aoadmm_tensor_set_heldout(g_ctx, (int)p, (int64_t)n, s0.data(), mxGetDoubles(hv)));   // range and NaN: the library
+        has_list[p] = 1;
+      }
+    }
+
   // ---- state: the struct G (init_coupled_AOADMM_CMTF.m:41-45)
   for (int m = 0; m < n_modes; ++m) {
     put_state_maybe_cell(AOADMM_F_FAC, m, mxGetCell(fac, m));
@@ -544,6 +577,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (const mxArray* hip = field(opt, "hip", false)) {
     if (const mxArray* f = field(hip, "no_permuted_copy", false)) o.no_permuted_copy = (int)mxGetScalar(f);
     if (const mxArray* f = field(hip, "par2_slab_sharding", false)) o.par2_slab_sharding = (int)mxGetScalar(f);
+    if (const mxArray* f = field(hip, "heldout_patience", false)) o.heldout_patience = (int)mxGetScalar(f);
   }
 
   // ---- solve
@@ -595,10 +629,13 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
 
   // ---- out (cmtf_fun_AOADMM.m:480-494)
   if (nlhs > 1) {
-    const char* fn[] = {"f_tensors", "f_couplings", "f_constraints", "f_PAR2_couplings", "f_rel_missing", "exit_flag",
-                        "OuterIterations", "func_val_conv", "func_coupl_conv", "func_constr_conv", "func_PAR2_coupl",
-                        "time_at_it", "innerIters", "func_rel_missing"};
-    mxArray* out = mxCreateStructMatrix(1, 1, has_missing ? 14 : 13, fn);   /* func_rel_missing only with Z.miss (:490-492) */
+    std::vector<const char*> fn = {"f_tensors", "f_couplings", "f_constraints", "f_PAR2_couplings", "f_rel_missing", "exit_flag",
+                                   "OuterIterations", "func_val_conv", "func_coupl_conv", "func_constr_conv", "func_PAR2_coupl",
+                                   "time_at_it", "innerIters"};
+    if (has_missing) fn.push_back("func_rel_missing");                     /* only with Z.miss (:490-492) */
+    const bool any_list = std::find(has_list.begin(), has_list.end(), 1) != has_list.end();
+    if (any_list) { fn.push_back("func_heldout"); fn.push_back("heldout_best_iter"); }   /* only with options.hip.heldout */
+    mxArray* out = mxCreateStructMatrix(1, 1, (int)fn.size(), fn.data());
     const int it = res.OuterIterations;
     auto vec = [&](const std::vector<double>& v, int len) {
       mxArray* a = mxCreateDoubleMatrix(1, len, mxREAL);
@@ -611,8 +648,26 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxSetField(out, 0, "f_PAR2_couplings", mxCreateDoubleScalar(res.f_PAR2_couplings));
     mxSetField(out, 0, "f_rel_missing", mxCreateDoubleScalar(has_missing ? res.f_rel_missing : mxGetNaN()));
     if (has_missing) mxSetField(out, 0, "func_rel_missing", vec(frm, it + 1));
+    if (any_list) {
+      // out.func_heldout{p}: sum (y - m)^2 of block p's list at iteration 0 .. OuterIterations; out.heldout_best_iter: the
+      // iteration of the smallest weighted sum.  Fac holds the LAST iteration: run again from the same G with
+      // MaxOuterIters = heldout_best_iter for the best model (the solve is bit-reproducible)
+      mxArray* fh = mxCreateCellMatrix(1, P);
+      int best = -1;
+      for (int p = 0; p < P; ++p) {
+        if (!has_list[p]) continue;
+        std::vector<double> tr(it + 1);
+        int len = 0;
+        check(aoadmm_heldout_trace(g_ctx, p, tr.data(), it + 1, &len, &best));
+        mxSetCell(fh, p, vec(tr, len < it + 1 ? len : it + 1));
+      }
+      mxSetField(out, 0, "func_heldout", fh);
+      mxSetField(out, 0, "heldout_best_iter", mxCreateDoubleScalar(best));
+    }
     if (res.exit_code == 0) {
       mxSetField(out, 0, "exit_flag", mxCreateString("maxIterations"));      /* make_exit_flag.m:4-5 */
+    } else if (res.exit_code == 2) {
+      mxSetField(out, 0, "exit_flag", mxCreateString("heldoutPatience"));    /* options.hip.heldout_patience */
     } else {
       const char* q[] = {"f_tensors", "f_couplings", "f_constraints", "f_PAR2_couplings"};
       mxArray* ef = mxCreateStructMatrix(1, 1, 4, q);

@@ -65,6 +65,20 @@ class sptensor:
     def norm(self):
         return float(np.sqrt(np.sum(self.vals * self.vals)))
 
+    def split(self, frac, rng=None):
+        """(train, heldout): two sptensors of this shape.  `heldout` gets round(frac * nnz) of the stored entries,
+        drawn without replacement by `rng` (a numpy Generator or a seed), `train` the rest.  The cut is made after
+        coalescing, so the parts are disjoint and their union is this tensor; the same rng state gives the same cut."""
+        frac = float(frac)
+        if not 0.0 <= frac <= 1.0:
+            raise ValueError('sptensor.split: frac must lie in [0, 1], got %r' % (frac,))
+        rng = np.random.default_rng(rng)
+        k = int(round(frac * self.nnz))
+        held = np.zeros(self.nnz, dtype=bool)
+        held[rng.permutation(self.nnz)[:k]] = True
+        return (sptensor(self.subs[~held], self.vals[~held], self.shape),
+                sptensor(self.subs[held], self.vals[held], self.shape))
+
     def __repr__(self):
         return 'sptensor(shape=%s, nnz=%d)' % (self.shape, self.nnz)
 

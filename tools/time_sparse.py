@@ -5,6 +5,7 @@ data on the same GPU.
     python3 tools/time_sparse.py --nvecs [--nvecs-iters 20] [--host-gram] ...
     python3 tools/time_sparse.py --as-rank 0 --of 8 [--skew] ...
     python3 tools/time_sparse.py --observed-only [--out profiles/sparse_observed_time.jsonl] ...
+    python3 tools/time_sparse.py --heldout [FRAC] [--skew] [--reps 7] [--out profiles/sparse_heldout_time.jsonl] ...
 
 Prints one JSON line per (layout, mode) and a summary line.  Layouts: 'colmajor' gathers from the column-major factors
 (what aoadmm_resident_mttkrp sees before any solve), 'rowmajor' after one outer iteration, when the Gram kernel has left
@@ -35,6 +36,14 @@ aoadmm_kernel_stats(3) and (4 + n); the pass over the first copy carries the sta
 and their ratio next to N / (N - 1).  Then the statistics-only pass (first step after a new mark: no snapshot, residuals
 written), the whole EM step, and the wall time of one outer iteration of both engines (difference of solves of 3 and of
 1 iterations, unconstrained modes).  Every line also goes to --out.
+--heldout FRAC (default 0.1) holds FRAC of the drawn list out (its first rows: the draw is i.i.d.) and times the
+held-out pass (csrc/heldout.hip, aoadmm_resident_heldout_stats, HIP events of aoadmm_kernel_stats(12)) in one process
+with the residual passes of an observed-only block of the training entries (classes 4 + n) and with one outer iteration
+(wall, solves of 3 and of 1 iterations) of the plain and of the observed-only block, each with the list attached and
+without it, alternating.  Medians of --reps (at least 7).  `per_entry_ratio` is the pass's time per held-out entry over
+the time per nonzero of a residual pass over modes 2 and 3 (both do N gathers per entry; the held-out pass writes
+nothing).  The list is scored in the caller's order and again sorted by its first subscript on the host, which is what
+a sort at attach time would give the pass.
 """
 from __future__ import annotations
 
@@ -71,8 +80,15 @@ def main():
     ap.add_argument('--as-rank', type=int, default=None)
     ap.add_argument('--of', default=None)
     ap.add_argument('--observed-only', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sparse_observed_time.jsonl'))
+    ap.add_argument('--heldout', type=float, nargs='?', const=0.1, default=None, metavar='FRAC')
+    ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, 'profiles', 'sparse_heldout_time.jsonl' if a.heldout is not None else 'sparse_observed_time.jsonl')
+    if a.heldout is not None:
+        if not 0.0 < a.heldout < 1.0:
+            ap.error('--heldout FRAC must lie inside (0, 1)')
+        a.reps = max(a.reps, 7)
     if not a.no_torch:
         # torch (and the HIP runtime it ships) first, as bench.py does: loaded after the library, the process aborted in
         # its exit-time destructors
@@ -82,7 +98,7 @@ def main():
     N, R, nnz = len(dims), a.R, int(a.nnz)
     if (a.as_rank is None) != (a.of is None):
         ap.error('--as-rank and --of go together')
-    if a.nvecs or a.of is not None or a.observed_only:
+    if a.nvecs or a.of is not None or a.observed_only or a.heldout is not None:
         a.no_torch = True
     rng = np.random.default_rng(a.seed)
     t0 = time.time()
@@ -96,8 +112,8 @@ def main():
     t_gen = time.time() - t0
     eng = pkg.Engine(0)
     try:
-        (run_nvecs if a.nvecs else run_share if a.of is not None else run_observed if a.observed_only else run)(
-            a, eng, dims, N, R, nnz, subs, vals, t_gen)
+        (run_nvecs if a.nvecs else run_share if a.of is not None else run_observed if a.observed_only else
+         run_heldout if a.heldout is not None else run)(a, eng, dims, N, R, nnz, subs, vals, t_gen)
     finally:
         eng.close()
 
@@ -347,6 +363,123 @@ def run_observed(a, eng, dims, N, R, nnz, subs, vals, t_gen):
             it[name] = w
         emit({'what': 'observed_iteration', 'plain_iter_ms_wall': mmm(it['plain']), 'observed_iter_ms_wall': mmm(it['observed']),
               'ratio': round(float(np.median(it['observed'])) / float(np.median(it['plain'])), 3)})
+    finally:
+        obs.close()
+        out.close()
+
+
+def run_heldout(a, eng, dims, N, R, nnz, subs, vals, t_gen):
+    lib = eng.lib
+    out = open(a.out, 'a')
+
+    def emit(r):
+        line = json.dumps(r)
+        print(line, flush=True)
+        out.write(line + '\n')
+        out.flush()
+
+    def mmm(v):
+        return [round(float(np.median(v)), 4), round(min(v), 4), round(max(v), 4)]
+
+    def solve(e, iters):
+        o = capi.Options()
+        o.MaxOuterIters, o.MaxInnerIters, o.use_dimtree = iters, 1, 1
+        res = capi.Result()
+        e.synchronize()
+        t0 = time.time()
+        capi.check(lib.aoadmm_solve(e.h, C.byref(o), C.byref(res)))
+        e.synchronize()
+        return (time.time() - t0) * 1e3
+
+    def set_factors(e):
+        rng = np.random.default_rng(a.seed + 1)
+        for m in range(N):
+            Um = np.asfortranarray(rng.random((dims[m], R)))
+            capi.check(lib.aoadmm_state_set(e.h, capi.F_FAC, m, 0, capi.dptr(Um), dims[m], R))
+
+    k = int(round(a.heldout * nnz))
+    hs, hv = np.ascontiguousarray(subs[:k]), np.ascontiguousarray(vals[:k])
+    ts, tv = subs[k:], vals[k:]
+    order = np.argsort(hs[:, 0], kind='stable')
+    hs_sorted, hv_sorted = np.ascontiguousarray(hs[order]), np.ascontiguousarray(hv[order])
+
+    def prepare(e, observed):
+        h = e.h
+        capi.check(lib.aoadmm_model_begin(h, N, 1, 0))
+        for m, s in enumerate(dims):
+            capi.check(lib.aoadmm_model_set_mode(h, m, s, R))
+        capi.check(lib.aoadmm_model_add_cp(h, 0, N, (C.c_int * N)(*range(N)), 1.0))
+        for m in range(N):
+            capi.check(lib.aoadmm_model_set_coupling(h, m, -1, None, 0, 0, None, 0, 0))
+        capi.check(lib.aoadmm_model_end(h))
+        e.upload_coo(0, ts, tv)
+        if observed:
+            e.set_observed_only(0)
+        set_factors(e)
+        solve(e, 1)                                   # row-major factor copies; the observed block takes its snapshot
+
+    def pass_once(e):
+        e.kernel_stats(12, reset=True)
+        e.heldout_stats(0)
+        ms, launches, by, _ = e.kernel_stats(12, reset=True)
+        assert launches == 1
+        return ms, by
+
+    def residual_once(e):
+        for c in [3] + [4 + n for n in range(N)]:
+            e.kernel_stats(c, reset=True)
+        e.em_step(0)
+        return [e.kernel_stats(4 + n, reset=True)[0] for n in range(N)]
+
+    def iteration(e):
+        set_factors(e)
+        t1 = solve(e, 1)
+        set_factors(e)
+        t3 = solve(e, 3)
+        return (t3 - t1) / 2
+
+    obs = pkg.Engine(0)
+    try:
+        prepare(eng, False)
+        prepare(obs, True)
+        nnz_train = eng.tensor_storage_info(0)[2] // (N * (4 * N + 8))
+        t0 = time.time()
+        eng.set_heldout(0, hs, hv)
+        t_attach = time.time() - t0
+        emit({'what': 'setup', 'dims': dims, 'nnz_given': nnz, 'heldout_frac': a.heldout, 'heldout_n': k,
+              'train_nnz_coalesced': int(nnz_train), 'R': R, 'skew': a.skew, 'reps': a.reps, 'gen_s': round(t_gen, 2),
+              'attach_s': round(t_attach, 2), 'heldout_info': eng.heldout_info(0)})
+        pass_once(eng), residual_once(obs)            # warm-up
+        caller, res = [], []
+        for _ in range(a.reps):                       # alternating, same process
+            caller.append(pass_once(eng))
+            res.append(residual_once(obs))
+        eng.set_heldout(0, hs_sorted, hv_sorted)
+        pass_once(eng)
+        srt = [pass_once(eng) for _ in range(a.reps)]
+        eng.set_heldout(0, hs, hv)
+        assert eng.heldout_info(0)['row_major'] == 1
+        ho = float(np.median([v[0] for v in caller]))
+        r23 = float(np.median([(v[1] + v[2]) / 2 for v in res])) if N >= 3 else float(np.median([v[1] for v in res]))
+        emit({'what': 'heldout_pass', 'heldout_pass_ms': mmm([v[0] for v in caller]),
+              'heldout_pass_sorted_by_mode1_ms': mmm([v[0] for v in srt]), 'GB': round(caller[0][1] / 1e9, 3),
+              'TBps': round(caller[0][1] / ho / 1e9, 3),
+              'residual_pass_ms_by_mode': [mmm([v[n] for v in res]) for n in range(N)],
+              'ns_per_heldout_entry': round(ho * 1e6 / k, 5), 'ns_per_nonzero_residual_modes_2_3': round(r23 * 1e6 / nnz_train, 5),
+              'per_entry_ratio': round((ho / k) / (r23 / nnz_train), 3)})
+        it = {}
+        for name, e in (('plain', eng), ('observed', obs)):
+            w_list, w_none = [], []
+            iteration(e)                              # warm-up
+            for _ in range(a.reps):                   # alternating: list attached, list removed
+                e.set_heldout(0, hs, hv)
+                w_list.append(iteration(e))
+                e.set_heldout(0, hs[:0], hv[:0])
+                w_none.append(iteration(e))
+            it[name] = (w_list, w_none)
+            emit({'what': 'heldout_iteration', 'block': name, 'iter_ms_wall_with_list': mmm(w_list),
+                  'iter_ms_wall_no_list': mmm(w_none),
+                  'added_ms': round(float(np.median(w_list)) - float(np.median(w_none)), 4)})
     finally:
         obs.close()
         out.close()
