@@ -370,11 +370,38 @@ int aoadmm_heldout_info(aoadmm_ctx* ctx, int p, int64_t* n, int64_t* resident_by
 /* After aoadmm_solve: out[i] = sum (y - m)^2 of block p's list at iteration i = 0 .. OuterIterations (at most cap
  * entries are written), *len = OuterIterations + 1 (0 when the block had no list), *best_iter = the iteration at which
  * H_i = sum over the blocks with a list of w_p * sum (y - m)^2 was smallest (the first such; -1 without a list).  The
- * factors a solve returns are those of its LAST iteration; the solve is bit-reproducible, so a second solve from the
- * same state with MaxOuterIters = *best_iter returns the best model (no snapshot is kept).  Each output may be NULL.
+ * factors a solve returns are those of its LAST iteration; aoadmm_heldout_keep_best / aoadmm_heldout_restore_best bring
+ * the best iterate back (without them a second solve from the same state with MaxOuterIters = *best_iter returns it: the
+ * solve is bit-reproducible).  Each output may be NULL.
  * aoadmm_resident_model_at, aoadmm_tensor_set_heldout and aoadmm_resident_heldout_stats answer AOADMM_ERR_UNSUPPORTED
  * on a multi-device context (aoadmm_create_multi with more than one device). */
 int aoadmm_heldout_trace(aoadmm_ctx* ctx, int p, double* out, int cap, int* len, int* best_iter);
+/* on = 1: every later aoadmm_solve keeps, on the device, a copy of the complete solver state -- every field
+ * aoadmm_state_get can return -- of the iteration at which H_i (aoadmm_heldout_trace) was smallest so far.  Iteration
+ * 0 is the starting point and the comparison is strict: the earliest minimum wins, the rule of *best_iter.  The copy is
+ * ONE kernel launch over a table of the state arrays whenever H improved (one hipMemcpyAsync per array would cost more
+ * than a small model's outer iteration); it follows the read-back the host already waits for, so no synchronisation
+ * is added.  The solve itself does not change: its state on return, its traces, exit_code and result scalars are those
+ * of the LAST iteration, bit for bit, with the switch on or off.  on = 0 releases the copy; any other value is
+ * AOADMM_ERR_INVALID.  The switch belongs to the MODEL, as the lists do: aoadmm_model_begin clears it.  A solve with
+ * the switch on and no list attached is AOADMM_ERR_INVALID before any work.  Costs the state's bytes once more in HBM. */
+int aoadmm_heldout_keep_best(aoadmm_ctx* ctx, int on);
+/* Copies the kept state back into the engine's state and reports its iteration in *iter (may be NULL).  Afterwards the
+ * engine is where a solve of *iter iterations from the same start would have left it: what is derived from the factors
+ * (Gram matrices, row-major copies, the cached tensor pass, the B_k Gram matrices and the Y cache of sparse slabs) is
+ * invalidated as aoadmm_state_set invalidates it, and the imputed entries of a block with Z.miss are brought to the
+ * restored factors' model by one imputation pass (*iter = 0 took no EM step: the entries then stay as the last iteration
+ * left them; an observed-only block starts every solve from zeros and needs nothing).  The kept copy survives the call:
+ * a second call returns the same.  It is invalidated by the next aoadmm_solve, by any aoadmm_state_set and by
+ * aoadmm_model_begin; AOADMM_ERR_INVALID when nothing is kept.  With a communicator every rank makes the call (a block
+ * with Z.miss all-reduces its statistics; a slab-sharded PARAFAC2 block keeps and restores each rank's own slabs and
+ * ends with the gather that ends a solve).  Both entries answer AOADMM_ERR_UNSUPPORTED on a multi-device context
+ * (aoadmm_create_multi with more than one device). */
+int aoadmm_heldout_restore_best(aoadmm_ctx* ctx, int* iter);
+/* *have = 1 when a kept state can be restored, *iter = its iteration (-1: none), *launches = snapshot launches of the
+ * last solve (one per iteration at which H improved, iteration 0 included), *bytes = the bytes those launches read and
+ * wrote (launches * 2 * the state's bytes).  Each output may be NULL.  No device work. */
+int aoadmm_heldout_best_info(aoadmm_ctx* ctx, int* have, int* iter, int64_t* bytes, int64_t* launches);
 
 /* ---- state (the struct G) ---------------------------------------------- */
 /* slab = k for cell-valued fields (PARAFAC2 B mode, P, mu_DeltaB), else 0.  slab = AOADMM_ALL_SLABS moves

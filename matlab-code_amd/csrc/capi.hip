@@ -483,6 +483,24 @@ int aoadmm_heldout_trace(aoadmm_ctx* ctx, int p, double* out, int cap, int* len,
   CTX_OR_FAIL(ctx);
   return guarded([&] { ctx->eng->heldout_trace(p, out, cap, len, best_iter); });      // no device work
 }
+int aoadmm_heldout_keep_best(aoadmm_ctx* ctx, int on) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_heldout_keep_best");
+    ctx->eng->heldout_keep_best(on);
+  });
+}
+int aoadmm_heldout_restore_best(aoadmm_ctx* ctx, int* iter) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_heldout_restore_best");
+    ctx->eng->heldout_restore_best(iter);
+  });
+}
+int aoadmm_heldout_best_info(aoadmm_ctx* ctx, int* have, int* iter, int64_t* bytes, int64_t* launches) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] { ctx->eng->heldout_best_info(have, iter, bytes, launches); });   // no device work
+}
 int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes) {
   CTX_OR_FAIL(ctx);
   // no collective and no device work: rank 0's engine answers for a multi-device context (every rank holds the same

@@ -22,6 +22,7 @@
 #include "readback.h"
 #include "small.h"
 #include "sparse.h"
+#include "state_snapshot.h"
 
 typedef struct ncclComm* ncclComm_t;
 
@@ -131,6 +132,19 @@ struct CouplingInfo {
   bool has_state = false;
 };
 
+// aoadmm_heldout_keep_best: the copy of the solver state at the iteration with the smallest weighted held-out sum
+// (DESIGN.md section 9.4).  One table serves both directions: segments [0, nseg) copy the state into `store`, segments
+// [nseg, 2 nseg) copy it back.
+struct BestKeep {
+  bool on = false;
+  int iter = -1;                  // iteration `store` holds; -1: nothing kept
+  DevBuf store, table;
+  std::vector<SnapSeg> segs;      // host copy of the table's first half, as solve_setup built it
+  int64_t bytes = 0;              // state bytes of one snapshot (this rank's own slabs of a slab-sharded PARAFAC2 block)
+  int64_t launches = 0, moved = 0;   // snapshot launches of the last solve and the bytes they read + wrote
+  bool use_dimtree = true;        // aoadmm_options.use_dimtree of the last solve (the restore replays its tensor passes)
+};
+
 struct LocalGroup;
 struct SolveRun;                      // what one solve carries from step to step (solver_solve.hip)
 
@@ -190,6 +204,10 @@ class Engine {
   void heldout_stats(int p, double stats[4]);      // {sum (y-m)^2, sum y^2, sum m^2, count} for the current factors
   void heldout_info(int p, int64_t* n, int64_t* resident_bytes, int* row_major) const;
   void heldout_trace(int p, double* out, int cap, int* len, int* best_iter) const;
+  // the best held-out iterate: the switch, the copy back into the state, what is kept
+  void heldout_keep_best(int on);
+  void heldout_restore_best(int* iter);
+  void heldout_best_info(int* have, int* iter, int64_t* bytes, int64_t* launches) const;
   void resident_unfold_gram(int p, int pos, int slab, double* out_host);
   void resident_nvecs(int p, int pos, int r, const aoadmm_nvecs_options* opt, double* U_host, int64_t ldU, double* eig_host,
                       aoadmm_nvecs_info* info);
@@ -251,6 +269,9 @@ class Engine {
   HeldoutFactors heldout_factors(const TensorInfo& t, bool* row_major) const;   // the current fac state of block t as the pass gathers it
   void heldout_check_subs(const TensorInfo& t, int p, int64_t n, const int64_t* subs, std::vector<int>& idx32) const;
   void heldout_enqueue(int p, double* sums);       // block p's list against the current factors -> sums[0..2] (device)
+  std::vector<SnapSeg> best_state_segments() const;   // every array aoadmm_state_get can return, as (src, bytes, start)
+  void best_build_table();                         // solve_setup: the segment table and the kept buffer of this solve
+  void best_snapshot(int iter);                    // record_iteration: the state of iteration `iter` into the kept buffer
   void compute_gram(ModeInfo& mi, const LoopEnd* close = nullptr);
   FactorRef factor_ref(const ModeInfo& o) const {
     return FactorRef{o.fac.d(), o.rows, o.version, o.facT_version == o.version ? o.facT.d() : nullptr};
@@ -328,6 +349,7 @@ class Engine {
   DevBuf staging_;
   LaunchTimers timers_;   // event pool and kernel statistics (cpblock.h)
   int ho_best_iter_ = -1;   // iteration of the smallest weighted held-out sum of the last solve (-1: no list was attached)
+  BestKeep best_;           // aoadmm_heldout_keep_best
   int prepared_mode_ = -1;  // mode whose MTTKRP + system build were enqueued ahead (prepare_next_first_mode)
   ncclComm_t comm_ = nullptr;
   mutable std::mutex comm_mu_;          // comm_ / aborted_ against comm_abort() from another worker thread

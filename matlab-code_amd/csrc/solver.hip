@@ -55,6 +55,7 @@ void Engine::model_begin(int n_modes, int n_tensors, int n_couplings) {
   model_done_ = false;
   has_ridge_ = false;
   allow_xp_ = true;                                   // options.hip.no_permuted_copy of an earlier solve does not outlive its model
+  best_ = BestKeep();                                 // aoadmm_heldout_keep_best belongs to the model, as the lists do
 }
 
 void Engine::set_mode(int mode, int64_t rows, int rank) {
@@ -801,6 +802,7 @@ void Engine::state_set(int field, int index, int slab, const double* host, int64
   AO_REQUIRE(model_done_, "call aoadmm_model_end first");
   AO_REQUIRE(host != nullptr && rows > 0 && cols > 0, "state_set: empty array");
   AO_HIP(hipSetDevice(device_));
+  best_.iter = -1;                                    // a kept best iterate belongs to the state the last solve started from
   StateLoc loc{nullptr, 0, 0};
   if (field == AOADMM_F_COUPLING_FAC) {
     AO_REQUIRE(index >= 0 && index < n_couplings_, "coupling %d out of range", index);

@@ -294,6 +294,10 @@ void Engine::solve_setup(const aoadmm_options& opt) {
     AO_REQUIRE(b.res.d() == dev_.p2_res(p) && b.q.d() == dev_.p2_q(p) && b.regv.d() == dev_.p2_regv(p),
                "read-back arena: PARAFAC2 block %d keeps its sums elsewhere", p);
   }
+  if (best_.on) {                                     // after decide_slab_sharding: a rank keeps its own slabs
+    best_build_table();
+    best_.use_dimtree = opt.use_dimtree != 0;
+  }
 }
 
 // slabs over the ranks or every slab on every rank (aoadmm_options.par2_slab_sharding)
@@ -414,8 +418,15 @@ void Engine::record_iteration(SolveRun& r, int iter) {
       t.ho_trace.push_back(v);
       H += t.weight * v;
     }
-    if (iter == 0 || H < r.ho_best) { r.ho_best = H; ho_best_iter_ = iter; r.ho_bad = 0; }
-    else ++r.ho_bad;
+    if (iter == 0 || H < r.ho_best) {
+      r.ho_best = H; ho_best_iter_ = iter; r.ho_bad = 0;
+      // The device still holds the state of iteration `iter`: what was enqueued ahead of this read-back (the prefetched
+      // tensor pass, prepare_next_first_mode) writes scratch only, and the next iteration's updates follow the copy in
+      // stream order.
+      if (best_.on) best_snapshot(iter);
+    } else {
+      ++r.ho_bad;
+    }
   }
   if (iter == 0 || !out->innerIters) return;
   for (int m = 0; m < n_modes_; ++m) {
@@ -437,8 +448,10 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
   const bool has_ho = has_heldout();
   AO_REQUIRE(opt.heldout_patience >= 0, "heldout_patience = %d < 0", opt.heldout_patience);
   AO_REQUIRE(opt.heldout_patience == 0 || has_ho, "heldout_patience = %d needs a held-out list (aoadmm_tensor_set_heldout)", opt.heldout_patience);
+  AO_REQUIRE(!best_.on || has_ho, "aoadmm_heldout_keep_best needs a held-out list (aoadmm_tensor_set_heldout)");
   AO_HIP(hipSetDevice(device_));
   ho_best_iter_ = -1;
+  best_.iter = -1;
   for (TensorInfo& t : tensors_) t.ho_trace.clear();
   solve_setup(opt);
   SolveRun r{opt, out};
@@ -479,6 +492,7 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
   for (int p = 0; p < n_tensors_; ++p)
     if (tensors_[p].par2) par2_gather_slabs(tensors_[p]);
   AO_HIP(hipStreamSynchronize(stream_));
+  if (best_.on) best_.iter = ho_best_iter_;           // the solve came through: the kept copy may be restored
   out->OuterIterations = iter - 1;
   out->exit_code = iter > opt.MaxOuterIters ? 0 : stop ? 1 : 2;                // make_exit_flag.m:4-5; 2: heldout_patience
   for (int i = 0; i < 4; ++i) out->exit_abs[i] = f[i] < opt.AbsFuncTol ? 1 : 0;

@@ -426,6 +426,23 @@ def heldout_lists(Z, heldout, patience=0):
     return lists
 
 
+def heldout_keep_best_option(value, lists):
+    """`alg_options['hip']['heldout_keep_best']` -> 0 or 1, checked on the host before the engine is touched.  ValueError:
+    a value that is not an integer or is neither 0 nor 1 (True / False count), and 1 without a held-out list (`lists`
+    as `heldout_lists` returns them)."""
+    if isinstance(value, (bool, np.bool_)):
+        value = int(value)
+    try:
+        ok = not isinstance(value, (str, bytes)) and int(value) == value and int(value) in (0, 1)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('heldout_keep_best must be 0 or 1, got %r' % (value,))
+    if int(value) == 1 and not lists:
+        raise ValueError('heldout_keep_best = 1 needs a held-out list (alg_options.hip.heldout)')
+    return int(value)
+
+
 def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0):
     """Describe the struct Z to the engine and upload Z.object (cmtf_AOADMM.m:23-41,124-156).
 
@@ -777,22 +794,28 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
     # alg_options['hip']['heldout'] = {1-based block: (subs, vals) | sptensor} and ['heldout_patience'] (`heldout_lists`):
     # entries kept out of the fit, scored on the device with every evaluation of the objective
     held = heldout_lists(Z, hip.get('heldout'), hip.get('heldout_patience', 0))
+    # alg_options['hip']['heldout_keep_best'] (default 0): 1 returns the iterate with the smallest held-out sum
+    keep_best = heldout_keep_best_option(hip.get('heldout_keep_best', 0), held)
     build_model(eng, Z, precision, sparse_sharding=sharding, observed_only=observed_opt)
     for p, (hs, hv) in sorted(held.items()):
         eng.set_heldout(p, hs, hv)
+    if keep_best:
+        eng.heldout_keep_best(True)
     upload_state(eng, Z, G)
     out = run_solver(eng, alg_options, nb_modes,
                      has_missing=bool(observed) or (Z.get('miss') is not None and any(m is not None for m in Z['miss'])))
     if held:
         # out.func_heldout{block}: sum (y - m)^2 at iteration 0 .. OuterIterations; with heldout_sumsq = sum y^2 and
         # heldout_count the relative error sqrt(func_heldout / heldout_sumsq) and the RMSE sqrt(func_heldout /
-        # heldout_count) follow.  The factors returned are those of the LAST iteration: a run from the same init with
-        # MaxOuterIters = heldout_best_iter returns the best model (the solve is bit-reproducible)
+        # heldout_count) follow.  The factors returned are those of the LAST iteration unless heldout_keep_best = 1
         out['func_heldout'], out['heldout_sumsq'], out['heldout_count'] = {}, {}, {}
         for p, (hs, hv) in sorted(held.items()):
             out['func_heldout'][p + 1], out['heldout_best_iter'] = eng.heldout_trace(p)
             out['heldout_sumsq'][p + 1] = float(np.sum(hv * hv))
             out['heldout_count'][p + 1] = int(hv.shape[0])
+    if keep_best:
+        # Fac and Zhat are the iterate heldout_best_iter; every other field of out still describes the whole run
+        out['heldout_restored_iter'] = eng.heldout_restore_best()
     Fac = download_state(eng, Z, G)
     Zhat = []
     for p in range(len(Z['object'])):                                                 # :197-206

@@ -220,6 +220,29 @@ class Engine:
         capi.check(self.lib.aoadmm_heldout_trace(self.h, int(p), capi.dptr(out), ln.value, C.byref(ln), C.byref(best)))
         return out[:ln.value].copy(), best.value
 
+    def heldout_keep_best(self, on=True):
+        """Switch of the model (`aoadmm_heldout_keep_best`): every later solve keeps on the device a copy of the whole
+        solver state of the iteration with the smallest weighted held-out sum (the earliest such; iteration 0 is the
+        starting point).  The solve returns what it returned before; `heldout_restore_best` brings the copy back.
+        `build_model` clears the switch, `on=False` releases the copy."""
+        capi.check(self.lib.aoadmm_heldout_keep_best(self.h, int(on)))
+
+    def heldout_restore_best(self):
+        """Copies the kept state back into the engine's state (`aoadmm_heldout_restore_best`) and returns its iteration:
+        the engine is then where a solve of that many iterations from the same start would have left it.  A second call
+        returns the same; the next solve, any state upload and `build_model` invalidate the copy (`AoadmmError`,
+        ERR_INVALID, when nothing is kept).  With a communicator every rank makes the call."""
+        it = C.c_int(-1)
+        capi.check(self.lib.aoadmm_heldout_restore_best(self.h, C.byref(it)))
+        return it.value
+
+    def heldout_best_info(self):
+        """dict(have, iter, bytes, launches) (`aoadmm_heldout_best_info`): whether a kept state can be restored, its
+        iteration (-1: none), and the snapshot launches of the last solve with the bytes they read and wrote."""
+        have, it, nb, nl = C.c_int(0), C.c_int(-1), C.c_int64(0), C.c_int64(0)
+        capi.check(self.lib.aoadmm_heldout_best_info(self.h, C.byref(have), C.byref(it), C.byref(nb), C.byref(nl)))
+        return dict(have=bool(have.value), iter=it.value, bytes=nb.value, launches=nl.value)
+
     def resident_mttkrp(self, p, tensor_mode, rows, R):
         """One MTTKRP of the resident block p against the current factors (`aoadmm_resident_mttkrp`): rows x R."""
         out = np.zeros((rows, R), order='F')

@@ -579,6 +579,19 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (const mxArray* f = field(hip, "par2_slab_sharding", false)) o.par2_slab_sharding = (int)mxGetScalar(f);
     if (const mxArray* f = field(hip, "heldout_patience", false)) o.heldout_patience = (int)mxGetScalar(f);
   }
+  // ---- options.hip.heldout_keep_best = 1: Fac is the iterate with the smallest weighted held-out sum, not the last one
+  // (aoadmm_heldout_keep_best / aoadmm_heldout_restore_best).  The switch belongs to the model, which was just built.
+  bool keep_best = false;
+  if (const mxArray* hip = field(opt, "hip", false))
+    if (const mxArray* f = field(hip, "heldout_keep_best", false)) {
+      const double v = mxIsChar(f) || mxIsEmpty(f) ? -1.0 : mxGetScalar(f);
+      if (mxGetNumberOfElements(f) != 1 || (v != 0.0 && v != 1.0))
+        mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.heldout_keep_best must be 0 or 1");
+      keep_best = v == 1.0;
+      if (keep_best && std::find(has_list.begin(), has_list.end(), 1) == has_list.end())
+        mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.heldout_keep_best = 1 needs a held-out list (options.hip.heldout)");
+    }
+  if (keep_best) check(aoadmm_heldout_keep_best(g_ctx, 1));
 
   // ---- solve
   const int n = o.MaxOuterIters + 1;
@@ -600,6 +613,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   const int rc = aoadmm_solve(g_ctx, &o, &res);
   if (live) (void)aoadmm_set_progress(g_ctx, nullptr, nullptr, 0);
   check(rc);
+  int restored_iter = -1;
+  if (keep_best) check(aoadmm_heldout_restore_best(g_ctx, &restored_iter));   // before the state is read: Fac is the best iterate
 
   // ---- Fac: same fields as G (cmtf_AOADMM.m:193,197-206)
   plhs[0] = mxDuplicateArray(G);
@@ -635,6 +650,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (has_missing) fn.push_back("func_rel_missing");                     /* only with Z.miss (:490-492) */
     const bool any_list = std::find(has_list.begin(), has_list.end(), 1) != has_list.end();
     if (any_list) { fn.push_back("func_heldout"); fn.push_back("heldout_best_iter"); }   /* only with options.hip.heldout */
+    if (keep_best) fn.push_back("heldout_restored_iter");                  /* only with options.hip.heldout_keep_best */
     mxArray* out = mxCreateStructMatrix(1, 1, (int)fn.size(), fn.data());
     const int it = res.OuterIterations;
     auto vec = [&](const std::vector<double>& v, int len) {
@@ -650,8 +666,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (has_missing) mxSetField(out, 0, "func_rel_missing", vec(frm, it + 1));
     if (any_list) {
       // out.func_heldout{p}: sum (y - m)^2 of block p's list at iteration 0 .. OuterIterations; out.heldout_best_iter: the
-      // iteration of the smallest weighted sum.  Fac holds the LAST iteration: run again from the same G with
-      // MaxOuterIters = heldout_best_iter for the best model (the solve is bit-reproducible)
+      // iteration of the smallest weighted sum.  Fac holds the LAST iteration unless options.hip.heldout_keep_best = 1
       mxArray* fh = mxCreateCellMatrix(1, P);
       int best = -1;
       for (int p = 0; p < P; ++p) {
@@ -664,6 +679,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       mxSetField(out, 0, "func_heldout", fh);
       mxSetField(out, 0, "heldout_best_iter", mxCreateDoubleScalar(best));
     }
+    if (keep_best) mxSetField(out, 0, "heldout_restored_iter", mxCreateDoubleScalar(restored_iter));
     if (res.exit_code == 0) {
       mxSetField(out, 0, "exit_flag", mxCreateString("maxIterations"));      /* make_exit_flag.m:4-5 */
     } else if (res.exit_code == 2) {

@@ -6,6 +6,7 @@ data on the same GPU.
     python3 tools/time_sparse.py --as-rank 0 --of 8 [--skew] ...
     python3 tools/time_sparse.py --observed-only [--out profiles/sparse_observed_time.jsonl] ...
     python3 tools/time_sparse.py --heldout [FRAC] [--skew] [--reps 7] [--out profiles/sparse_heldout_time.jsonl] ...
+    python3 tools/time_sparse.py --heldout [FRAC] --keep-best [--out profiles/heldout_keep_best_time.jsonl] ...
 
 Prints one JSON line per (layout, mode) and a summary line.  Layouts: 'colmajor' gathers from the column-major factors
 (what aoadmm_resident_mttkrp sees before any solve), 'rowmajor' after one outer iteration, when the Gram kernel has left
@@ -44,6 +45,11 @@ without it, alternating.  Medians of --reps (at least 7).  `per_entry_ratio` is 
 the time per nonzero of a residual pass over modes 2 and 3 (both do N gathers per entry; the held-out pass writes
 nothing).  The list is scored in the caller's order and again sorted by its first subscript on the host, which is what
 a sort at attach time would give the pass.
+--heldout FRAC --keep-best times solves of 4 iterations (wall) of the plain block with the list attached and
+aoadmm_heldout_keep_best on and off, alternating, and one aoadmm_heldout_restore_best.  The held-out values are the
+model's own after those 4 iterations (the solve is bit-reproducible), so that the held-out sum falls from iteration to
+iteration: `snapshots_per_solve` is what aoadmm_heldout_best_info counted, 5 = the starting point and every iteration, the
+worst case.  `added_ms_per_snapshot` is the difference of the medians over that count.
 """
 from __future__ import annotations
 
@@ -81,10 +87,14 @@ def main():
     ap.add_argument('--of', default=None)
     ap.add_argument('--observed-only', action='store_true')
     ap.add_argument('--heldout', type=float, nargs='?', const=0.1, default=None, metavar='FRAC')
+    ap.add_argument('--keep-best', action='store_true')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.keep_best and a.heldout is None:
+        ap.error('--keep-best goes with --heldout')
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'sparse_heldout_time.jsonl' if a.heldout is not None else 'sparse_observed_time.jsonl')
+        a.out = os.path.join(ROOT, 'profiles', 'heldout_keep_best_time.jsonl' if a.keep_best else
+                             'sparse_heldout_time.jsonl' if a.heldout is not None else 'sparse_observed_time.jsonl')
     if a.heldout is not None:
         if not 0.0 < a.heldout < 1.0:
             ap.error('--heldout FRAC must lie inside (0, 1)')
@@ -438,6 +448,47 @@ def run_heldout(a, eng, dims, N, R, nnz, subs, vals, t_gen):
         t3 = solve(e, 3)
         return (t3 - t1) / 2
 
+    if a.keep_best:
+        # The snapshot is taken when the held-out sum improves.  The solve is bit-reproducible, so the list is given the
+        # model's own values after `iters` iterations: H_i = |m_i - m_iters|^2 then falls as the iterates approach their
+        # last one, and every iteration of the timed solves takes a snapshot (the worst case; the count is reported).
+        iters = 4
+        try:
+            prepare(eng, False)
+            set_factors(eng)
+            solve(eng, iters)
+            eng.set_heldout(0, hs, eng.model_at(0, hs))
+            state_bytes = 8 * R * sum(dims)
+
+            def solve_kept(on):
+                eng.heldout_keep_best(on)
+                set_factors(eng)
+                return solve(eng, iters), eng.heldout_best_info()
+
+            solve_kept(True), solve_kept(False)           # warm-up
+            w_on, w_off, shots = [], [], []
+            for _ in range(a.reps):                       # alternating: switch on, switch off
+                t, info = solve_kept(True)
+                w_on.append(t)
+                shots.append(info['launches'])
+                assert info['bytes'] == info['launches'] * 2 * state_bytes
+                w_off.append(solve_kept(False)[0])
+            solve_kept(True)
+            t_restore = []
+            for _ in range(a.reps):
+                eng.synchronize()
+                t0 = time.time()
+                eng.heldout_restore_best()
+                t_restore.append((time.time() - t0) * 1e3)
+            emit({'what': 'keep_best_solve', 'block': 'plain', 'dims': dims, 'nnz_given': nnz, 'heldout_n': k, 'R': R,
+                  'skew': a.skew, 'reps': a.reps, 'iters': iters, 'state_bytes': state_bytes,
+                  'snapshot_bytes_moved': 2 * state_bytes, 'solve_ms_wall_switch_on': mmm(w_on),
+                  'solve_ms_wall_switch_off': mmm(w_off), 'snapshots_per_solve': shots,
+                  'added_ms_per_snapshot': round((float(np.median(w_on)) - float(np.median(w_off))) / max(shots[0], 1), 4),
+                  'restore_ms_wall': mmm(t_restore)})
+        finally:
+            out.close()
+        return
     obs = pkg.Engine(0)
     try:
         prepare(eng, False)
