@@ -315,6 +315,24 @@ int aoadmm_tensor_set_observed_only(aoadmm_ctx* ctx, int p, int on);
  * aoadmm_resident_mttkrp on the block returns the MTTKRP of the imputed tensor as of this step (before any step: the
  * plain sparse MTTKRP, bit for bit). */
 int aoadmm_resident_em_step(aoadmm_ctx* ctx, int p, double stats[3]);
+/* One EM pass over the dense block p that holds a mask (aoadmm_tensor_mask_upload / aoadmm_par2_slab_mask_upload) with
+ * the current AOADMM_F_FAC state, exactly as aoadmm_solve runs it (cmtf_fun_AOADMM.m:408-441, :1224-1226): update = 0
+ * leaves the data alone (the pass behind the start objective and Znorm_const), update = 1 also overwrites the missing
+ * entries with the model.  fuse selects the partial contraction an update pass over a 3-way CP block leaves for the
+ * next outer iteration: 0 none (a solve's last iteration), 1 the solver's own choice, 2 the second mode whenever
+ * allowed; the library fuses only where a solve would (rank <= 24, not a block its one-launch MTTKRP serves).
+ * stats = {num, den, obs_res, obs_x2}: the squared change of the missing entries, the squared norm of their old
+ * values, and the squared residual and squared norm of the observed entries.  Returned when not NULL: data = the block
+ * after the pass, unpadded, column-major, as doubles (a PARAFAC2 block: its slabs back to back); data_t = the
+ * transposed copy a matrix block keeps (J x I); mttkrp = when the pass fused a contraction, the unweighted MTTKRP of
+ * the first mode the model updates (I_n x R), finished from the partial contraction the pass left, with no further
+ * tensor pass; info[0..7] = {rows per thread 4 / 2 / 1, rank class of the kernel, contracted tensor mode of the fused
+ * pass (0-based: 1 or 2) or -1, mode the strips walk (1: second, 2: third), strips, pieces of the walk, walk positions
+ * per piece, tensor mode of `mttkrp` or -1}; all zero but info[2] = info[7] = -1 for a PARAFAC2 block.  Two calls on
+ * the same data return the same bits.  AOADMM_ERR_INVALID for a sparse, fp16 or unmasked block; AOADMM_ERR_UNSUPPORTED
+ * on a context that belongs to a communicator or drives several devices. */
+int aoadmm_resident_em_pass(aoadmm_ctx* ctx, int p, int update, int fuse, double stats[4], double* data, double* data_t,
+                            double* mttkrp, int64_t info[8]);
 /* Z.object{p}{k} of a PARAFAC2 block as sparse matrices, all K slabs in one call: nnz nonzeros, subs column-major
  * nnz x 3, 0-based (i, j within the slab, k); vals nnz doubles.  Duplicates are summed, explicit zeros are allowed,
  * nnz = 0 is valid; a subscript out of range (j >= J_k included) or nnz < 0 is AOADMM_ERR_INVALID and leaves the block

@@ -448,6 +448,15 @@ int aoadmm_resident_em_step(aoadmm_ctx* ctx, int p, double stats[3]) {
     });
   });
 }
+// One EM pass of a masked dense block as Engine::outer_updates runs it (Engine::resident_em_pass)
+int aoadmm_resident_em_pass(aoadmm_ctx* ctx, int p, int update, int fuse, double stats[4], double* data, double* data_t,
+                            double* mttkrp, int64_t info[8]) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    if (ctx->multi) throw Error(AOADMM_ERR_UNSUPPORTED, "aoadmm_resident_em_pass runs on a single-device context");
+    ctx->eng->resident_em_pass(p, update, fuse, stats, data, data_t, mttkrp, info);
+  });
+}
 // Held-out scoring answers on one engine (which may belong to a communicator); a multi-device context would have to
 // keep one list per engine for no gain: it is refused
 static void require_single_engine(aoadmm_ctx* ctx, const char* what) {

@@ -33,6 +33,16 @@ inline size_t em_mask_bits_bytes(int64_t n) { return (size_t)((n + 7) / 8 + 16);
 constexpr int kEmFuseMaxRank = 24;
 bool em_cp_can_fuse(const EmCpArgs& a, int prec);
 int em_cp_fused_chunks(const EmCpArgs& a, int prec);
+// The launch em_cp_pass makes for `a` (fuse: with the fused contraction, whether a.T is set yet or not): what the pass
+// itself launches from and what aoadmm_resident_em_pass reports
+struct EmCpLaunch {
+  int vec;         // rows of the first mode per thread: 4 (fp32) / 2 (fp64) in the strip kernel, 1 in the kernel for R > 32
+  int rmax;        // rank class of the kernel's instantiation
+  int64_t strips;  // workgroups along the first mode
+  int jchunks;     // pieces the walk is cut into
+  int64_t jlen;    // walk positions per piece (whole 64-column tiles)
+};
+EmCpLaunch em_cp_launch_of(const EmCpArgs& a, int prec, bool fuse);
 size_t em_cp_ws_bytes(int64_t Ipad, int64_t J, int64_t K);
 // ws: em_cp_ws_bytes ; out4: device, 4 doubles
 void em_cp_pass(const EmCpArgs& a, int prec, double* ws, double* out4, hipStream_t s);

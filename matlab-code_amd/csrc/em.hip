@@ -386,12 +386,17 @@ bool em_cp_can_fuse(const EmCpArgs& a, int prec) {
   return a.R <= kEmFuseMaxRank && a.C != nullptr;    // 2 * R vectors of registers per thread (rows of A and of T)
 }
 
-int em_cp_fused_chunks(const EmCpArgs& a, int prec) {
+EmCpLaunch em_cp_launch_of(const EmCpArgs& a, int prec, bool fuse) {
   const bool wj = a.walk != 2;
-  int jchunks; int64_t jlen;
-  em_chunking(cdiv(a.Ipad, (int64_t)kEmThreads * em_vec(a, prec)), wj ? a.J : a.K, wj ? a.K : a.J, true, &jchunks, &jlen);
-  return jchunks;
+  EmCpLaunch l;
+  l.vec = em_vec(a, prec);
+  l.rmax = em_wide(a) ? (a.R + 3) / 4 * 4 : 64;      // em_cp_launch's classes; em_cp_k<T, 64>
+  l.strips = cdiv(a.Ipad, (int64_t)kEmThreads * l.vec);
+  em_chunking(l.strips, wj ? a.J : a.K, wj ? a.K : a.J, fuse, &l.jchunks, &l.jlen);
+  return l;
 }
+
+int em_cp_fused_chunks(const EmCpArgs& a, int prec) { return em_cp_launch_of(a, prec, true).jchunks; }
 
 size_t em_cp_ws_bytes(int64_t Ipad, int64_t J, int64_t K) {
   // strips <= cdiv(Ipad, 256) (VEC >= 1), the fixed index runs over J or K, pieces <= cdiv(kEmTargetBlocks, strips * fixed):
@@ -424,10 +429,9 @@ void em_cp_pass(const EmCpArgs& a, int prec, double* ws, double* out4, hipStream
   AO_REQUIRE((wj ? a.K : a.J) <= 65535, "em_cp_pass: mode too long for one launch");   // grid.y = the fixed index
   AO_REQUIRE(!fuse || em_cp_can_fuse(a, prec), "em_cp_pass: this block cannot take the fused contraction");
   AO_REQUIRE(wj || a.C != nullptr, "em_cp_pass: a matrix block has no third mode to walk");
-  const int vec = em_vec(a, prec);
-  const int64_t strips = cdiv(a.Ipad, (int64_t)kEmThreads * vec);
-  int jchunks; int64_t jlen;
-  em_chunking(strips, wj ? a.J : a.K, wj ? a.K : a.J, fuse, &jchunks, &jlen);
+  const EmCpLaunch l = em_cp_launch_of(a, prec, fuse);
+  const int64_t strips = l.strips, jlen = l.jlen;
+  const int jchunks = l.jchunks;
   const dim3 grid((unsigned)(strips * jchunks), (unsigned)(wj ? a.K : a.J));
   AO_REQUIRE((size_t)grid.x * grid.y * 4 * sizeof(double) <= em_cp_ws_bytes(a.Ipad, a.J, a.K), "em_cp_pass: workspace");
   if (prec == AOADMM_PREC_F32) {

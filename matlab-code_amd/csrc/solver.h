@@ -15,6 +15,7 @@
 #include "contract.h"
 #include "couple.h"
 #include "cpblock.h"
+#include "em.h"
 #include "heldout.h"
 #include "misc.h"
 #include "par2.h"
@@ -145,6 +146,19 @@ struct BestKeep {
   bool use_dimtree = true;        // aoadmm_options.use_dimtree of the last solve (the restore replays its tensor passes)
 };
 
+// which partial contraction an imputing EM pass leaves for the next outer iteration (Engine::em_pass_enqueue)
+enum EmFuse {
+  kEmFuseNone = 0,     // none: a solve's last iteration, use_dimtree = 0
+  kEmFuseAuto = 1,     // the mode whose factor stays unchanged longest
+  kEmFuseSecond = 2,   // the second mode whenever that is allowed (the test hook AOADMM_EM_FUSE_SECOND_MODE)
+};
+// what an EM pass over a CP block ran (aoadmm_resident_em_pass); zeros and fused = -1 for a PARAFAC2 block
+struct EmPassInfo {
+  EmCpLaunch launch{0, 0, 0, 0, 0};
+  int fused = -1;      // contracted tensor position of the fused pass (1 or 2), -1: none
+  int walk = 0;        // EmCpArgs::walk
+};
+
 struct LocalGroup;
 struct SolveRun;                      // what one solve carries from step to step (solver_solve.hip)
 
@@ -198,6 +212,13 @@ class Engine {
   void solve(const aoadmm_options& opt, aoadmm_result* out);
   void resident_mttkrp(int p, int pos, double* out_host, float* ms);
   void resident_em_step(int p, double stats[3]);   // one EM step of an observed-only block: {sum_Omega (x-m)^2, num, den}
+  // One EM pass over the masked dense block p as a solve runs it (aoadmm_resident_em_pass): em_pass_enqueue(p, update,
+  // fuse), then what it left.  stats: the four EM statistics in the EmStat order; data / data_t (may be null): the
+  // block's natural array / a matrix block's transposed copy, unpadded, as doubles (PARAFAC2: the slabs back to back);
+  // mttkrp (may be null): when the pass fused a contraction, the unweighted MTTKRP of the first position of the update
+  // sequence finished from the cached T; info[8] = {vec, rmax, fused, walk, strips, jchunks, jlen, that position or -1}
+  void resident_em_pass(int p, int update, int fuse, double stats[4], double* data, double* data_t, double* mttkrp,
+                        int64_t info[8]);
   // held-out scoring (heldout.h)
   void model_at(int p, int64_t n, const int64_t* subs, double* out_host);     // the model of block p at n subscripts
   void set_heldout(int p, int64_t n, const int64_t* subs, const double* vals);   // n = 0 removes the list
@@ -263,7 +284,8 @@ class Engine {
   void alloc_readback();
   void comm_release();                     // destroys the RCCL communicator, if any (solver_comm.hip)
   bool has_missing() const;
-  void em_pass_enqueue(int p, int update, bool fuse_next_pass = false);   // statistics of tensor p into its EM slots (+ imputation)
+  // statistics of tensor p into its EM slots (+ imputation); fuse: EmFuse, honoured where the block allows it
+  void em_pass_enqueue(int p, int update, int fuse = kEmFuseNone, EmPassInfo* info = nullptr);
   void sparse_em_enqueue(int p, bool stats_only);  // EM step of an observed-only sparse block into its EM slots
   bool has_heldout() const;
   HeldoutFactors heldout_factors(const TensorInfo& t, bool* row_major) const;   // the current fac state of block t as the pass gathers it

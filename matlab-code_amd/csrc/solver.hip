@@ -687,6 +687,79 @@ void Engine::resident_em_step(int p, double stats[3]) {
   stats[0] = h4[kEmObsRes]; stats[1] = h4[kEmNum]; stats[2] = h4[kEmDen];
 }
 
+// natural-layout array on the device (first dimension padded to `pad0`) -> unpadded doubles on the host
+static void download_unpadded(const DenseTensor& X, int64_t rows, int64_t cols, double* out, hipStream_t s) {
+  const size_t es = X.elem_size();
+  std::vector<char> h((size_t)X.pad0 * cols * es);
+  AO_HIP(hipMemcpyAsync(h.data(), X.data.p, h.size(), hipMemcpyDeviceToHost, s));
+  AO_HIP(hipStreamSynchronize(s));
+  for (int64_t c = 0; c < cols; ++c)
+    for (int64_t i = 0; i < rows; ++i) {
+      const size_t e = (size_t)i + (size_t)X.pad0 * c;
+      out[i + rows * c] = X.prec == AOADMM_PREC_F32 ? (double)reinterpret_cast<const float*>(h.data())[e]
+                                                    : reinterpret_cast<const double*>(h.data())[e];
+    }
+}
+
+void Engine::resident_em_pass(int p, int update, int fuse, double stats[4], double* data, double* data_t, double* mttkrp,
+                              int64_t info[8]) {
+  require_usable();
+  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
+  AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
+  AO_REQUIRE(stats != nullptr, "null stats");
+  AO_REQUIRE(fuse >= kEmFuseNone && fuse <= kEmFuseSecond, "fuse = %d outside 0..2", fuse);
+  if (sharded()) throw Error(AOADMM_ERR_UNSUPPORTED, "aoadmm_resident_em_pass runs on one engine without a communicator");
+  TensorInfo& t = tensors_[p];
+  if (t.par2) {
+    AO_REQUIRE(!t.p2.sparse, "tensor %d holds sparse slabs: it has no EM pass", p);
+    for (int k = 0; k < t.p2.K; ++k) AO_REQUIRE(t.p2.have_slab[k], "slab %d of tensor %d has no data", k, p);
+  } else {
+    AO_REQUIRE(t.blk.has_data && !t.blk.sparse, "tensor %d holds no dense data (sparse blocks: aoadmm_resident_em_step)", p);
+    AO_REQUIRE(!t.blk.half, "tensor %d is stored as fp16: it has no EM pass", p);
+  }
+  AO_REQUIRE(t.masked(), "tensor %d has no mask (aoadmm_tensor_mask_upload / aoadmm_par2_slab_mask_upload)", p);
+  for (int i = 0; i < t.nmodes; ++i) AO_REQUIRE(modes_[t.modes[i]].has_fac, "G.fac{%d} missing", t.modes[i] + 1);
+  AO_HIP(hipSetDevice(device_));
+  EmPassInfo pi;
+  em_pass_enqueue(p, update != 0, fuse, &pi);
+  int mpos = -1;
+  if (pi.fused >= 0) {
+    // the first MTTKRP of the next outer iteration as update_mode runs it: the cached T must serve it
+    CpBlock& b = t.blk;
+    const std::vector<int> seq = update_sequence(p);
+    mpos = seq.empty() ? 0 : seq[0];
+    if (mttkrp) {
+      FactorRef facs[8];
+      factor_refs(t, facs);
+      ModeInfo& mi = modes_[t.modes[mpos]];
+      ensure_mode_work(mi);
+      block_mttkrp(block_ctx(), b, mpos, facs, mi.R, 1.0, mi.A.d(), mi.rows, true, seq.data(), (int)seq.size());
+      AO_HIP(hipMemcpyAsync(mttkrp, mi.A.p, (size_t)mi.rows * mi.R * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    }
+    b.cached_mode = -1;                              // the solver's own factors may differ from what this pass used
+  }
+  double h4[kEmStats];
+  AO_HIP(hipMemcpyAsync(h4, dev_.em(p), sizeof h4, hipMemcpyDeviceToHost, stream_));
+  AO_HIP(hipStreamSynchronize(stream_));
+  for (int q = 0; q < kEmStats; ++q) stats[q] = h4[q];
+  if (info) {
+    info[0] = pi.launch.vec; info[1] = pi.launch.rmax; info[2] = pi.fused; info[3] = pi.walk;
+    info[4] = pi.launch.strips; info[5] = pi.launch.jchunks; info[6] = pi.launch.jlen; info[7] = mpos;
+  }
+  if (t.par2) {
+    if (data) {
+      AO_HIP(hipMemcpyAsync(data, t.p2.X.p, (size_t)t.p2.I * t.p2.Jtot * sizeof(double), hipMemcpyDeviceToHost, stream_));
+      AO_HIP(hipStreamSynchronize(stream_));
+    }
+    return;
+  }
+  CpBlock& b = t.blk;
+  int64_t cols = 1;
+  for (int i = 1; i < b.nd; ++i) cols *= b.dims[i];
+  if (data) download_unpadded(b.X, b.dims[0], cols, data, stream_);
+  if (data_t && b.nd == 2) download_unpadded(b.Xt, b.dims[1], b.dims[0], data_t, stream_);
+}
+
 bool Engine::has_missing() const {
   for (int p = 0; p < n_tensors_; ++p)
     if (tensors_[p].missing()) return true;
@@ -695,8 +768,9 @@ bool Engine::has_missing() const {
 
 // One EM pass over tensor p with the current factors: {num, den, obs_res, obs_x2} -> its EM slots, all-reduced
 // over the row shards; update = 1 also overwrites the missing entries with the model (:416-435).
-void Engine::em_pass_enqueue(int p, int update, bool fuse_next_pass) {
+void Engine::em_pass_enqueue(int p, int update, int fuse, EmPassInfo* info) {
   TensorInfo& t = tensors_[p];
+  if (info) *info = EmPassInfo();
   if (t.par2) {
     Par2Block& b = t.p2;
     EmPar2Args a;
@@ -743,7 +817,7 @@ void Engine::em_pass_enqueue(int p, int update, bool fuse_next_pass) {
   int fused_c = -1;
   ContractPlan fpl;
   FactorRef facs[8];
-  if (fuse_next_pass && update && b.nd == 3 && em_cp_can_fuse(a, b.X.prec) && b.dims[1] <= 65535 &&
+  if (fuse != kEmFuseNone && update && b.nd == 3 && em_cp_can_fuse(a, b.X.prec) && b.dims[1] <= 65535 &&
       b.dims[2] <= 65535 && !small_direct(sharded(), b, a.R)) {
     factor_refs(t, facs);
     const std::vector<int> seq = update_sequence(p);
@@ -754,9 +828,9 @@ void Engine::em_pass_enqueue(int p, int update, bool fuse_next_pass) {
       const int dist = next_update_distance(pos0, cand, seq.data(), (int)seq.size());
       if (dist > best) { best = dist; fused_c = cand; }
     }
-    // test hook (read per call): contract the second mode whenever that is allowed, so that the strip's walk along
-    // mode 2 with the fused contraction is exercised by models whose update order would never pick it
-    if (getenv("AOADMM_EM_FUSE_SECOND_MODE") != nullptr && pos0 != 1) fused_c = 1;
+    // contract the second mode whenever that is allowed, so that the strip's walk along mode 2 with the fused
+    // contraction is exercised by models whose update order would never pick it
+    if (fuse == kEmFuseSecond && pos0 != 1) fused_c = 1;
     const int64_t J = b.dims[1], K = b.dims[2];
     a.walk = fused_c == 1 ? 1 : 2;
     fpl = fused_c == 2 ? make_plan(1, 0, a.Ipad * J, a.Ipad * J, K, a.R, b.X.prec)
@@ -766,6 +840,7 @@ void Engine::em_pass_enqueue(int p, int update, bool fuse_next_pass) {
     a.T = b.T.p;
     a.t_chunk_stride = fpl.trows() * a.R;
   }
+  if (info) { info->launch = em_cp_launch_of(a, b.X.prec, a.T != nullptr); info->fused = fused_c; info->walk = a.walk; }
   em_cp_pass(a, b.X.prec, emws_.d(), dev_.em(p), stream_);
   if (b.nd == 2 && update) {
     // same imputation on the transposed copy (roles of the two factors swapped); its statistics are discarded

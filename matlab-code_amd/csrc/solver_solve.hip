@@ -325,6 +325,13 @@ void Engine::update_mode(int m, int cid, const aoadmm_options& opt, int iter) {
   else prepare_mode_system(m, coupled_nrho(m), opt);
 }
 
+// What the imputing EM pass of an iteration fuses.  The test hook (read per call) asks for the second mode, so that the
+// strip's walk along mode 2 with the fused contraction is exercised by models whose update order would never pick it.
+static int em_fuse_choice(bool next_pass_follows) {
+  if (!next_pass_follows) return kEmFuseNone;
+  return getenv("AOADMM_EM_FUSE_SECOND_MODE") != nullptr ? kEmFuseSecond : kEmFuseAuto;
+}
+
 // One outer iteration's updates: every mode in the schedule of :89-93, the coupled ADMM loops, then the EM passes.
 void Engine::outer_updates(const aoadmm_options& opt, int iter, bool has_miss) {
   for (ModeInfo& mq : modes_) mq.quad.dirty = true;   // rho moves once per outer iteration ('quadratic regularization', non-symmetric L)
@@ -348,7 +355,7 @@ void Engine::outer_updates(const aoadmm_options& opt, int iter, bool has_miss) {
   }
   if (has_miss)                                                              // EM imputation (:408-441)
     for (int p = 0; p < n_tensors_; ++p) {
-      if (tensors_[p].masked()) em_pass_enqueue(p, 1, opt.use_dimtree != 0 && iter < opt.MaxOuterIters);
+      if (tensors_[p].masked()) em_pass_enqueue(p, 1, em_fuse_choice(opt.use_dimtree != 0 && iter < opt.MaxOuterIters));
       else if (tensors_[p].observed_only()) sparse_em_enqueue(p, false);
     }
 }

@@ -164,6 +164,43 @@ class Engine:
         capi.check(self.lib.aoadmm_resident_em_step(self.h, int(p), capi.dptr(st)))
         return float(st[0]), float(st[1]), float(st[2])
 
+    def resident_em_pass(self, p, dims, R, update=1, fuse=0, with_data=True):
+        """One EM pass over the masked dense block p with the current factors, as a solve runs it
+        (`aoadmm_resident_em_pass`).  dims: the block's sizes (a PARAFAC2 block: (I, [J_k], K)); fuse: 0 none, 1 the
+        solver's choice, 2 the second mode.  Returns a dict: stats = (num, den, obs_res, obs_x2) as a float64 array;
+        data = the block after the pass as doubles (PARAFAC2: a list of I x J_k slabs), data_t = a matrix block's
+        transposed copy (J x I), both None without with_data; mttkrp = the MTTKRP of tensor mode `mttkrp_mode` finished
+        from the partial contraction the pass fused (None when it fused none); info = dict(vec, rmax, fused, walk,
+        strips, jchunks, jlen)."""
+        stats = np.zeros(4)
+        info = np.zeros(8, dtype=np.int64)
+        par2 = isinstance(dims[1], (list, tuple))
+        data = data_t = None
+        if with_data:
+            if par2:
+                data = np.zeros(int(dims[0]) * int(sum(dims[1])))
+            else:
+                data = np.zeros(tuple(int(d) for d in dims), order='F')
+                if len(dims) == 2:
+                    data_t = np.zeros((int(dims[1]), int(dims[0])), order='F')
+        rows = 0 if par2 else max(int(d) for d in dims)
+        mt = np.zeros((max(rows, 1), int(R)), order='F')           # room for any mode; cut to the mode reported
+        capi.check(self.lib.aoadmm_resident_em_pass(self.h, int(p), int(update), int(fuse), capi.dptr(stats),
+                                                    capi.dptr(data), capi.dptr(data_t), capi.dptr(mt),
+                                                    info.ctypes.data_as(C.POINTER(C.c_int64))))
+        if par2 and with_data:
+            off = np.concatenate([[0], np.cumsum([int(j) for j in dims[1]])]) * int(dims[0])
+            data = [data[off[k]:off[k + 1]].reshape((int(dims[0]), int(j)), order='F').copy()
+                    for k, j in enumerate(dims[1])]
+        mode = int(info[7])
+        mttkrp = None
+        if mode >= 0:
+            n = int(dims[mode])
+            mttkrp = np.array(mt.ravel(order='F')[:n * int(R)].reshape((n, int(R)), order='F'), order='F')
+        return dict(stats=stats, data=data, data_t=data_t, mttkrp=mttkrp, mttkrp_mode=mode,
+                    info=dict(vec=int(info[0]), rmax=int(info[1]), fused=int(info[2]), walk=int(info[3]),
+                              strips=int(info[4]), jchunks=int(info[5]), jlen=int(info[6])))
+
     # ---- held-out scoring ------------------------------------------------------------
     @staticmethod
     def _subs_f(subs, what):

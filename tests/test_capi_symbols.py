@@ -59,6 +59,12 @@ def test_coupled_loop_entry_and_its_path_codes(pkg):
     assert ids == dict(REGS=capi.CPATH_REGS, WG=capi.CPATH_WG, ROWSTEPS=capi.CPATH_ROWSTEPS, GENERIC=capi.CPATH_GENERIC)
 
 
+def test_em_pass_entry(pkg):
+    """aoadmm_resident_em_pass is declared, bound and exported, and the engine wraps it."""
+    assert 'aoadmm_resident_em_pass' in declared_functions() and 'aoadmm_resident_em_pass' in pkg.SYMBOLS
+    assert hasattr(pkg.load_library(), 'aoadmm_resident_em_pass') and hasattr(pkg.Engine, 'resident_em_pass')
+
+
 def test_no_cpu_fallback(pkg):
     """Without a GPU the product path must fail loudly (never route through the oracle)."""
     lib = pkg.load_library()
