@@ -421,6 +421,25 @@ int aoadmm_heldout_restore_best(aoadmm_ctx* ctx, int* iter);
  * wrote (launches * 2 * the state's bytes).  Each output may be NULL.  No device work. */
 int aoadmm_heldout_best_info(aoadmm_ctx* ctx, int* have, int* iter, int64_t* bytes, int64_t* launches);
 
+/* ---- top-k completions --------------------------- */
+/* The k best entries of CP block p along its mode `mode` (0-based position in the block) for nq queries, from the
+ * current AOADMM_F_FAC state.  Query q names a subscript for every other mode; w_q(r) = prod_{m != mode} F_m(s_{q,m}, r),
+ * score_q(i) = sum_r F_mode(i, r) w_q(r) for 0 <= i < I_mode.  The candidates of q are the rows that are not in q's
+ * exclusion list and whose score is not NaN; the answer is the k candidates that come first in the total order "larger
+ * score first, equal scores by smaller row", idx[q * k + j] and val[q * k + j] for j = 0 .. k - 1, padded with row -1
+ * and score -inf when fewer than k candidates exist.  subs is column-major nq x n_tensor_modes, 0-based, as for
+ * aoadmm_resident_model_at; its column `mode` is neither read nor range-checked.  excl_off holds nq + 1 offsets into
+ * excl_idx, the excluded rows per query in any order, repeats allowed; excl_off = NULL: no exclusions.  nq = 0 does
+ * nothing.  AOADMM_ERR_INVALID, with idx and val untouched, for: mode outside the block, k outside [1, 64], nq < 0 or
+ * nq >= 2^31, a subscript or an excluded row out of range, offsets that do not start at 0 or decrease.
+ * AOADMM_ERR_UNSUPPORTED for a PARAFAC2 block and on a multi-device context (aoadmm_create_multi with more than one
+ * device).  Like aoadmm_resident_model_at it reads factors only: the answer is the same for dense, fp16, masked,
+ * sparse, observed-only, sharded and row-sharded blocks, and there is no collective, so the ranks of a communicator
+ * may ask different queries.  The I_mode x nq score array never exists: device workspace O(nq R + nq k slabs).  The
+ * summation order of a score depends on R alone, so the answer's bits are a function of the inputs only. */
+int aoadmm_resident_topk(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const int64_t* subs, int k, const int64_t* excl_off,
+                         const int64_t* excl_idx, int64_t* idx, double* val);
+
 /* ---- state (the struct G) ---------------------------------------------- */
 /* slab = k for cell-valued fields (PARAFAC2 B mode, P, mu_DeltaB), else 0.  slab = AOADMM_ALL_SLABS moves
  * all K cells at once: host holds them back to back, each J_k x R column-major, rows = sum J_k. */
@@ -453,7 +472,9 @@ int aoadmm_resident_par2_rhs(aoadmm_ctx* ctx, int p, int tensor_mode, double* ou
  * sparse block: this rank's share (its nonzeros, and the rows of its span as the output written); the all-reduce is
  * outside the events; which = 12: the held-out passes (aoadmm_resident_model_at, aoadmm_resident_heldout_stats and the pass
  * of every objective evaluation of a solve with a list attached: one launch each; bytes = subscripts and values streamed
- * + factor rows gathered, flops = n * R * N + 8 n for the sums) */
+ * + factor rows gathered, flops = n * R * N + 8 n for the sums); which = 13: aoadmm_resident_topk (one launch per call:
+ * its weights, scores-and-selection and merge kernels inside one event pair; bytes = F_mode streamed once per query tile
+ * + rows gathered + the answer, flops = 2 * I_mode * nq * R) */
 int aoadmm_kernel_stats(aoadmm_ctx* ctx, int which, int reset, double* contract_ms, int64_t* contract_launches,
                         double* contract_bytes, double* contract_flops);
 

@@ -68,7 +68,7 @@ SYMBOLS = [
     'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_tensor_upload_coo_sharded', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq', 'aoadmm_tensor_storage_info',
     'aoadmm_tensor_set_observed_only', 'aoadmm_resident_em_step', 'aoadmm_resident_em_pass',
     'aoadmm_resident_model_at', 'aoadmm_tensor_set_heldout', 'aoadmm_resident_heldout_stats', 'aoadmm_heldout_info', 'aoadmm_heldout_trace',
-    'aoadmm_heldout_keep_best', 'aoadmm_heldout_restore_best', 'aoadmm_heldout_best_info',
+    'aoadmm_heldout_keep_best', 'aoadmm_heldout_restore_best', 'aoadmm_heldout_best_info', 'aoadmm_resident_topk',
     'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_resident_par2_rhs', 'aoadmm_kernel_stats',
     'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_resident_nvecs', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
     'aoadmm_op_admm_mode', 'aoadmm_op_par2_b_loop', 'aoadmm_op_coupled_loop',
@@ -184,6 +184,8 @@ def load_library():
     lib.aoadmm_heldout_keep_best.argtypes = [vp, C.c_int]
     lib.aoadmm_heldout_restore_best.argtypes = [vp, C.POINTER(C.c_int)]
     lib.aoadmm_heldout_best_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(i64)]
+    lib.aoadmm_resident_topk.argtypes = [vp, C.c_int, C.c_int, i64, C.POINTER(i64), C.c_int, C.POINTER(i64), C.POINTER(i64),
+                                         C.POINTER(i64), dp]
     lib.aoadmm_state_set.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, i64, i64]
     lib.aoadmm_state_get.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, i64, i64]
     lib.aoadmm_solve.argtypes = [vp, C.POINTER(Options), C.POINTER(Result)]

@@ -510,6 +510,14 @@ int aoadmm_heldout_best_info(aoadmm_ctx* ctx, int* have, int* iter, int64_t* byt
   CTX_OR_FAIL(ctx);
   return guarded([&] { ctx->eng->heldout_best_info(have, iter, bytes, launches); });   // no device work
 }
+int aoadmm_resident_topk(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const int64_t* subs, int k, const int64_t* excl_off,
+                         const int64_t* excl_idx, int64_t* idx, double* val) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_resident_topk");
+    ctx->eng->topk(p, mode, nq, subs, k, excl_off, excl_idx, idx, val);
+  });
+}
 int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes) {
   CTX_OR_FAIL(ctx);
   // no collective and no device work: rank 0's engine answers for a multi-device context (every rank holds the same

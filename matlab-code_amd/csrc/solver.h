@@ -229,6 +229,9 @@ class Engine {
   void heldout_keep_best(int on);
   void heldout_restore_best(int* iter);
   void heldout_best_info(int* have, int* iter, int64_t* bytes, int64_t* launches) const;
+  // top-k completions along one mode of a CP block (topk.h)
+  void topk(int p, int mode, int64_t nq, const int64_t* subs, int k, const int64_t* excl_off, const int64_t* excl_idx,
+            int64_t* idx_host, double* val_host);
   void resident_unfold_gram(int p, int pos, int slab, double* out_host);
   void resident_nvecs(int p, int pos, int r, const aoadmm_nvecs_options* opt, double* U_host, int64_t ldU, double* eig_host,
                       aoadmm_nvecs_info* info);

@@ -280,6 +280,35 @@ class Engine:
         capi.check(self.lib.aoadmm_heldout_best_info(self.h, C.byref(have), C.byref(it), C.byref(nb), C.byref(nl)))
         return dict(have=bool(have.value), iter=it.value, bytes=nb.value, launches=nl.value)
 
+    def topk(self, p, mode, subs, k, exclude=None):
+        """The k best entries of CP block p along its mode `mode` (0-based position in the block) for every query
+        (`aoadmm_resident_topk`).  subs is nq x N, 0-based; its column `mode` is ignored.  Query q scores every row i of
+        the free mode, sum_r F_mode(i, r) prod_{m != mode} F_m(subs[q, m], r), and gets the k rows that come first in
+        the order "larger score first, equal scores by smaller row" among those that are not excluded and whose score
+        is not NaN.  exclude = (off, idx): off has nq + 1 offsets into idx, the excluded rows per query in any order
+        (`sptensor.fiber_lists` gives the stored ones).  Returns (idx int64 nq x k, val float64 nq x k), padded with
+        -1 and -inf.  Needs the model and the factor state, not the block's data; no nq x I_mode array exists."""
+        subs = self._subs_f(subs, 'topk')
+        nq, k = int(subs.shape[0]), int(k)
+        idx = np.full((nq, max(k, 0)), -1, dtype=np.int64)
+        val = np.full((nq, max(k, 0)), -np.inf)
+        i64p = C.POINTER(C.c_int64)
+        off = ex = None
+        if exclude is not None:
+            off = np.ascontiguousarray(np.asarray(exclude[0], dtype=np.int64).reshape(-1))
+            ex = np.ascontiguousarray(np.asarray(exclude[1], dtype=np.int64).reshape(-1))
+            if off.shape[0] != nq + 1:
+                raise ValueError('topk: exclude[0] must hold nq + 1 = %d offsets, got %d' % (nq + 1, off.shape[0]))
+            if off[-1] != ex.shape[0]:
+                raise ValueError('topk: exclude[0][-1] = %d but exclude[1] holds %d rows' % (off[-1], ex.shape[0]))
+            if ex.shape[0] == 0:
+                ex = np.zeros(1, dtype=np.int64)          # a valid address for an empty list
+        capi.check(self.lib.aoadmm_resident_topk(
+            self.h, int(p), int(mode), nq, subs.ctypes.data_as(i64p), k,
+            off.ctypes.data_as(i64p) if off is not None else None, ex.ctypes.data_as(i64p) if ex is not None else None,
+            idx.ctypes.data_as(i64p), capi.dptr(val)))
+        return idx, val
+
     def resident_mttkrp(self, p, tensor_mode, rows, R):
         """One MTTKRP of the resident block p against the current factors (`aoadmm_resident_mttkrp`): rows x R."""
         out = np.zeros((rows, R), order='F')
@@ -300,7 +329,7 @@ class Engine:
         """(ms, launches, bytes, flops) of a kernel class since the last reset (`aoadmm_kernel_stats`); which = 3:
         MTTKRPs of sparse blocks (of a sharded block: this rank's share), passes over the nonzeros of PARAFAC2
         blocks with sparse slabs and EM steps of observed-only blocks; which = 4 + n: the pass of those EM steps over
-        the copy of tensor mode n; which = 12: the held-out passes."""
+        the copy of tensor mode n; which = 12: the held-out passes; which = 13: the top-k completions (one launch per `topk` call)."""
         ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         capi.check(self.lib.aoadmm_kernel_stats(self.h, int(which), int(bool(reset)), C.byref(ms), C.byref(n),
                                                 C.byref(by), C.byref(fl)))

@@ -79,6 +79,42 @@ class sptensor:
         return (sptensor(self.subs[~held], self.vals[~held], self.shape),
                 sptensor(self.subs[held], self.vals[held], self.shape))
 
+    def fiber_lists(self, mode, subs):
+        """(off, idx) for `Engine.topk(..., exclude=...)`: query q (row q of `subs`, nq x N, 0-based, column `mode`
+        ignored) names the fibre along `mode` through its other subscripts; idx[off[q]:off[q + 1]] are the indices
+        along `mode` of the entries stored in that fibre, ascending.  An empty fibre gives an empty list."""
+        mode = int(mode)
+        if not 0 <= mode < self.ndim:
+            raise ValueError('sptensor.fiber_lists: mode %d outside [0, %d)' % (mode, self.ndim))
+        subs = np.asarray(subs, dtype=np.int64)
+        if subs.ndim != 2 or subs.shape[1] != self.ndim:
+            raise ValueError('sptensor.fiber_lists: subs must be nq x %d, got %s' % (self.ndim, subs.shape))
+        others = [m for m in range(self.ndim) if m != mode]
+        dims = np.asarray([self.shape[m] for m in others], dtype=np.int64)
+        qs = subs[:, others]
+        if qs.size and (qs.min() < 0 or np.any(qs >= dims[None, :])):
+            raise ValueError('sptensor.fiber_lists: a query subscript is outside the tensor')
+        if float(np.prod(dims.astype(np.float64))) >= 2.0 ** 63:
+            raise ValueError('sptensor.fiber_lists: the fibres of mode %d have too many positions for 64-bit keys' % mode)
+
+        def key(s):                                # linear position of the fibre among the other modes
+            out = np.zeros(s.shape[0], dtype=np.int64)
+            stride = 1
+            for j in range(len(others)):
+                out += s[:, j] * stride
+                stride *= int(dims[j])
+            return out
+
+        fk = key(self.subs[:, others])
+        order = np.lexsort((self.subs[:, mode], fk))
+        fk, rows = fk[order], self.subs[order, mode]
+        qk = key(qs)
+        lo, hi = np.searchsorted(fk, qk, side='left'), np.searchsorted(fk, qk, side='right')
+        off = np.zeros(subs.shape[0] + 1, dtype=np.int64)
+        np.cumsum(hi - lo, out=off[1:])
+        take = np.repeat(lo - off[:-1], hi - lo) + np.arange(off[-1], dtype=np.int64)
+        return off, np.ascontiguousarray(rows[take].astype(np.int64))
+
     def __repr__(self):
         return 'sptensor(shape=%s, nnz=%d)' % (self.shape, self.nnz)
 
