@@ -353,6 +353,9 @@ int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out);
  * observed-only block N (4 N + 16) per nonzero plus the factor snapshots (2 * 8 * I_n * R bytes per mode); 0 for
  * PARAFAC2 data.  No device work. */
 int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes);
+/* *rank = the number of components R of block p, the columns of its factors: what a caller sizes the outputs of
+ * aoadmm_resident_fold_in and the W of aoadmm_resident_topk_w by.  Needs aoadmm_model_end; no device work. */
+int aoadmm_tensor_rank(aoadmm_ctx* ctx, int p, int* rank);
 
 /* ---- held-out entries ---------------------------- */
 /* The model of block p for the current AOADMM_F_FAC state at n subscripts: out[e] = sum_r prod_m F_m(s_m, r) for a CP
@@ -439,6 +442,52 @@ int aoadmm_heldout_best_info(aoadmm_ctx* ctx, int* have, int* iter, int64_t* byt
  * summation order of a score depends on R alone, so the answer's bits are a function of the inputs only. */
 int aoadmm_resident_topk(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const int64_t* subs, int k, const int64_t* excl_off,
                          const int64_t* excl_idx, int64_t* idx, double* val);
+/* aoadmm_resident_topk with the weights given instead of formed from subscripts: W is nq x R column-major, row q is w_q,
+ * uploaded as it is (finite or not; a NaN score is no candidate, by the rule above).  This is how a row that
+ * aoadmm_resident_fold_in returned is ranked: for a block of order 2 the folded rows ARE the weights along the other
+ * mode; for a higher order multiply them by the remaining modes' rows.  Everything else -- the order, the exclusions,
+ * the padding, the refusals, the kernels that score and select -- is that of aoadmm_resident_topk. */
+int aoadmm_resident_topk_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const double* W, int k, const int64_t* excl_off,
+                           const int64_t* excl_idx, int64_t* idx, double* val);
+
+/* ---- fold-in of new rows -------------------------- */
+/* The factor rows of nq NEW indices ("queries": a new user, document, sample) along mode `mode` (0-based position in
+ * the block) of CP block p, from their entries, with every other factor of the current AOADMM_F_FAC state held fixed:
+ * the row update of the observed-only model.  subs is column-major nobs x n_tensor_modes, 0-based, as for
+ * aoadmm_resident_model_at, except that column `mode` holds the query number q in [0, nq); vals holds one value per
+ * observation (not checked for finiteness: a NaN reaches its own query's row only).  Any order; duplicates are separate
+ * observations.  With z_e(r) = prod_{m != mode} F_m(s_{e,m}, r) (multiplied in mode order from 1) and, over the
+ * observations of q in the caller's order, G_q = sum z_e z_e', b_q = sum x_e z_e (the block's weight is not applied; it
+ * scales both sides):
+ *   constraint = 0:  u_q = (G_q + ridge I)^-1 b_q by Cholesky;
+ *   constraint = 1 (non-negativity): ADMM_constrained_only of the reference on the single row, cold-started: rho =
+ *     trace(G_q) / R, L = chol(G_q + (ridge + rho / 2) I), z = mu = 0, then u = (b + rho / 2 (z - mu)) / (L L'),
+ *     z_old = z, z = max(u + mu, 0), mu += u - z at least once and while iter < max_inner and ||u - z|| / ||u|| >
+ *     tol_primal or ||z - z_old|| / ||mu|| > tol_dual (the latter unscaled when mu = 0); the test is per query and the
+ *     row returned is z.
+ * rows is nq x R column-major; info[q] = 0, or 1 when a pivot of the query's Cholesky was not positive (the row is
+ * then NaN; the call still returns AOADMM_OK); iters[q] = ADMM iterations taken (0 without a constraint); gram holds
+ * nq blocks of R x R (column-major, both triangles) and rhs nq x R column-major: G_q and b_q before the ridge.  The
+ * last three may be NULL.  A query without observations gives the zero row when ridge > 0 and info 1 when ridge = 0.
+ * opt = NULL: ridge 0, no constraint.  nq = 0 does nothing.
+ * AOADMM_ERR_INVALID, with every output untouched, for: p or mode outside the model, nq < 0 or nq >= 2^31, nobs < 0, a
+ * query number outside [0, nq), any other subscript out of range, ridge negative or not finite, constraint outside
+ * {0, 1}, max_inner < 1, a negative tolerance, NULL subs / vals (with nobs > 0) / rows / info.  AOADMM_ERR_UNSUPPORTED
+ * for a PARAFAC2 block and on a multi-device context (aoadmm_create_multi with more than one device).  Like
+ * aoadmm_resident_model_at it reads factors only: the answer is the same for dense, fp16, masked, sparse,
+ * observed-only, sharded and row-sharded blocks, and there is no collective, so the ranks of a communicator may ask
+ * different things.  A query's outputs are a function of the factors, its own observations in the caller's order and
+ * the options: not of nq, the other queries or their order. */
+typedef struct {
+  double ridge;
+  int constraint;    /* 0: none, 1: non-negativity */
+  int max_inner;
+  double tol_primal;
+  double tol_dual;
+} aoadmm_foldin_options;
+int aoadmm_resident_fold_in(aoadmm_ctx* ctx, int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals,
+                            const aoadmm_foldin_options* opt_or_null, double* rows, int* info, int* iters_or_null,
+                            double* gram_or_null, double* rhs_or_null);
 
 /* ---- state (the struct G) ---------------------------------------------- */
 /* slab = k for cell-valued fields (PARAFAC2 B mode, P, mu_DeltaB), else 0.  slab = AOADMM_ALL_SLABS moves
@@ -474,7 +523,9 @@ int aoadmm_resident_par2_rhs(aoadmm_ctx* ctx, int p, int tensor_mode, double* ou
  * of every objective evaluation of a solve with a list attached: one launch each; bytes = subscripts and values streamed
  * + factor rows gathered, flops = n * R * N + 8 n for the sums); which = 13: aoadmm_resident_topk (one launch per call:
  * its weights, scores-and-selection and merge kernels inside one event pair; bytes = F_mode streamed once per query tile
- * + rows gathered + the answer, flops = 2 * I_mode * nq * R) */
+ * + rows gathered + the answer, flops = 2 * I_mode * nq * R); which = 14: aoadmm_resident_fold_in (one launch per call: its
+ * kernels inside one event pair; bytes = the list streamed + rows gathered + the outputs, flops = nobs * (R (R + 1) +
+ * 2 R (N - 1)) + nq * (R^3 / 3 + 2 R^2) for the solves) */
 int aoadmm_kernel_stats(aoadmm_ctx* ctx, int which, int reset, double* contract_ms, int64_t* contract_launches,
                         double* contract_bytes, double* contract_flops);
 

@@ -65,10 +65,11 @@ SYMBOLS = [
     'aoadmm_model_begin', 'aoadmm_model_set_mode', 'aoadmm_model_set_mode_slabs', 'aoadmm_model_add_cp',
     'aoadmm_model_add_par2', 'aoadmm_model_set_constraint', 'aoadmm_model_set_coupling',
     'aoadmm_model_set_coupling_type', 'aoadmm_model_set_ridge', 'aoadmm_model_end', 'aoadmm_tensor_upload',
-    'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_tensor_upload_coo_sharded', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq', 'aoadmm_tensor_storage_info',
+    'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_tensor_upload_coo_sharded', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq', 'aoadmm_tensor_storage_info', 'aoadmm_tensor_rank',
     'aoadmm_tensor_set_observed_only', 'aoadmm_resident_em_step', 'aoadmm_resident_em_pass',
     'aoadmm_resident_model_at', 'aoadmm_tensor_set_heldout', 'aoadmm_resident_heldout_stats', 'aoadmm_heldout_info', 'aoadmm_heldout_trace',
     'aoadmm_heldout_keep_best', 'aoadmm_heldout_restore_best', 'aoadmm_heldout_best_info', 'aoadmm_resident_topk',
+    'aoadmm_resident_topk_w', 'aoadmm_resident_fold_in',
     'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_resident_par2_rhs', 'aoadmm_kernel_stats',
     'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_resident_nvecs', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
     'aoadmm_op_admm_mode', 'aoadmm_op_par2_b_loop', 'aoadmm_op_coupled_loop',
@@ -116,6 +117,11 @@ class Result(C.Structure):
 
 class NvecsOptions(C.Structure):                  # aoadmm_nvecs_options (zeros = defaults)
     _fields_ = [('oversample', C.c_int), ('max_iters', C.c_int), ('tol', C.c_double), ('seed', C.c_uint64)]
+
+
+class FoldinOptions(C.Structure):                 # aoadmm_foldin_options
+    _fields_ = [('ridge', C.c_double), ('constraint', C.c_int), ('max_inner', C.c_int), ('tol_primal', C.c_double),
+                ('tol_dual', C.c_double)]
 
 
 class NvecsInfo(C.Structure):                     # aoadmm_nvecs_info
@@ -173,6 +179,7 @@ def load_library():
     lib.aoadmm_tensor_synth.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.c_double, C.c_int]
     lib.aoadmm_tensor_normsq.argtypes = [vp, C.c_int, dp]
     lib.aoadmm_tensor_storage_info.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp, C.POINTER(i64)]
+    lib.aoadmm_tensor_rank.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     lib.aoadmm_tensor_set_observed_only.argtypes = [vp, C.c_int, C.c_int]
     lib.aoadmm_resident_em_step.argtypes = [vp, C.c_int, dp]
     lib.aoadmm_resident_em_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, C.POINTER(i64)]
@@ -186,6 +193,9 @@ def load_library():
     lib.aoadmm_heldout_best_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(i64)]
     lib.aoadmm_resident_topk.argtypes = [vp, C.c_int, C.c_int, i64, C.POINTER(i64), C.c_int, C.POINTER(i64), C.POINTER(i64),
                                          C.POINTER(i64), dp]
+    lib.aoadmm_resident_topk_w.argtypes = [vp, C.c_int, C.c_int, i64, dp, C.c_int, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), dp]
+    lib.aoadmm_resident_fold_in.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.POINTER(i64), dp, C.POINTER(FoldinOptions), dp,
+                                            C.POINTER(C.c_int), C.POINTER(C.c_int), dp, dp]
     lib.aoadmm_state_set.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, i64, i64]
     lib.aoadmm_state_get.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, i64, i64]
     lib.aoadmm_solve.argtypes = [vp, C.POINTER(Options), C.POINTER(Result)]

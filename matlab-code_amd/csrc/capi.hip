@@ -518,11 +518,35 @@ int aoadmm_resident_topk(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const int
     ctx->eng->topk(p, mode, nq, subs, k, excl_off, excl_idx, idx, val);
   });
 }
+int aoadmm_resident_topk_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const double* W, int k, const int64_t* excl_off,
+                           const int64_t* excl_idx, int64_t* idx, double* val) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_resident_topk_w");
+    ctx->eng->topk_w(p, mode, nq, W, k, excl_off, excl_idx, idx, val);
+  });
+}
+int aoadmm_resident_fold_in(aoadmm_ctx* ctx, int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals,
+                            const aoadmm_foldin_options* opt_or_null, double* rows, int* info, int* iters_or_null,
+                            double* gram_or_null, double* rhs_or_null) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_resident_fold_in");
+    ctx->eng->fold_in(p, mode, nq, nobs, subs, vals, opt_or_null, rows, info, iters_or_null, gram_or_null, rhs_or_null);
+  });
+}
 int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes) {
   CTX_OR_FAIL(ctx);
   // no collective and no device work: rank 0's engine answers for a multi-device context (every rank holds the same
   // form; of a sharded sparse block rank 0's share)
   return guarded([&] { ctx->eng->tensor_storage_info(p, precision, scale, resident_bytes); });
+}
+int aoadmm_tensor_rank(aoadmm_ctx* ctx, int p, int* rank) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {                                 // no device work; the model is the same on every engine
+    AO_REQUIRE(rank != nullptr, "null pointer");
+    *rank = ctx->eng->tensor_rank(p);
+  });
 }
 int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out) {
   CTX_OR_FAIL(ctx);

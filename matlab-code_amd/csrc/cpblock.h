@@ -21,7 +21,8 @@ struct FactorRef {
 constexpr int kStatsEmPass = 4;
 constexpr int kStatsHeldout = kStatsEmPass + kCooMaxModes;   // the held-out pass (heldout.h)
 constexpr int kStatsTopk = kStatsHeldout + 1;                 // the top-k completions (topk.h)
-constexpr int kStatsClasses = kStatsTopk + 1;
+constexpr int kStatsFoldin = kStatsTopk + 1;                  // the fold-in of new rows (foldin.h)
+constexpr int kStatsClasses = kStatsFoldin + 1;
 
 struct KernelStats {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -36,7 +37,7 @@ struct LaunchTimers {
   std::vector<hipEvent_t> pool;   // timing events are recycled: creating two per tensor pass cost host time in the loop
   // [0] streaming contraction, [1] leading-mode contraction, [2] reductions over T, [3] sparse MTTKRP, the passes over
   // sparse PARAFAC2 slabs and the EM steps of observed-only blocks, [kStatsEmPass + n] the pass of those steps over
-  // mode n's copy, [kStatsHeldout] the held-out passes, [kStatsTopk] the top-k completions
+  // mode n's copy, [kStatsHeldout] the held-out passes, [kStatsTopk] the top-k completions, [kStatsFoldin] the fold-in of new rows
   KernelStats stats[kStatsClasses];
   bool profile = true;
   bool profile_reductions = false;   // switched on by the first kernel_stats(2, ...) call: two more events per reduction

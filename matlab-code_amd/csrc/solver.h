@@ -232,6 +232,15 @@ class Engine {
   // top-k completions along one mode of a CP block (topk.h)
   void topk(int p, int mode, int64_t nq, const int64_t* subs, int k, const int64_t* excl_off, const int64_t* excl_idx,
             int64_t* idx_host, double* val_host);
+  // the same with the weights given (W: nq x R column-major on the host) instead of formed from subscripts
+  void topk_w(int p, int mode, int64_t nq, const double* W, int k, const int64_t* excl_off, const int64_t* excl_idx,
+              int64_t* idx_host, double* val_host);
+  void topk_run(const char* what, int p, int mode, int64_t nq, const int64_t* subs, const double* W, int k, const int64_t* excl_off,
+                const int64_t* excl_idx, int64_t* idx_host, double* val_host);
+  // new rows along one mode of a CP block from their entries (foldin.h)
+  int tensor_rank(int p) const;                    // the number of components of block p (aoadmm_tensor_rank)
+  void fold_in(int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals, const aoadmm_foldin_options* opt,
+               double* rows_host, int* info_host, int* iters_host, double* gram_host, double* rhs_host);
   void resident_unfold_gram(int p, int pos, int slab, double* out_host);
   void resident_nvecs(int p, int pos, int r, const aoadmm_nvecs_options* opt, double* U_host, int64_t ldU, double* eig_host,
                       aoadmm_nvecs_info* info);
@@ -292,7 +301,8 @@ class Engine {
   void sparse_em_enqueue(int p, bool stats_only);  // EM step of an observed-only sparse block into its EM slots
   bool has_heldout() const;
   HeldoutFactors heldout_factors(const TensorInfo& t, bool* row_major) const;   // the current fac state of block t as the pass gathers it
-  void heldout_check_subs(const TensorInfo& t, int p, int64_t n, const int64_t* subs, std::vector<int>& idx32) const;
+  // skip_mode >= 0: that column of subs is neither read nor checked (its part of idx32 stays zero)
+  void heldout_check_subs(const TensorInfo& t, int p, int64_t n, const int64_t* subs, std::vector<int>& idx32, int skip_mode = -1) const;
   void heldout_enqueue(int p, double* sums);       // block p's list against the current factors -> sums[0..2] (device)
   std::vector<SnapSeg> best_state_segments() const;   // every array aoadmm_state_get can return, as (src, bytes, start)
   void best_build_table();                         // solve_setup: the segment table and the kept buffer of this solve

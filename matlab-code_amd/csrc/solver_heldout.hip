@@ -37,13 +37,14 @@ HeldoutFactors Engine::heldout_factors(const TensorInfo& t, bool* row_major) con
 }
 
 // subs: column-major n x N int64, 0-based -> idx32 in the same layout.  A subscript out of range is AOADMM_ERR_INVALID.
-void Engine::heldout_check_subs(const TensorInfo& t, int p, int64_t n, const int64_t* subs, std::vector<int>& idx32) const {
+// skip_mode: the column a caller gives another meaning (the free mode of a top-k query, the query number of a fold-in).
+void Engine::heldout_check_subs(const TensorInfo& t, int p, int64_t n, const int64_t* subs, std::vector<int>& idx32, int skip_mode) const {
   const int nd = t.nmodes;
   AO_REQUIRE(nd >= 2 && nd <= kCooMaxModes, "tensor %d: order %d", p, nd);
   idx32.resize((size_t)nd * n);
   for (int m = 0; m < nd; ++m) {
     const ModeInfo& mi = modes_[t.modes[m]];
-    if (mi.slabs) continue;                          // the slab-valued mode is checked against J_k below
+    if (mi.slabs || m == skip_mode) continue;        // the slab-valued mode is checked against J_k below
     AO_REQUIRE(mi.rows < ((int64_t)1 << 31), "tensor %d: mode %d too long for int32 subscripts", p, m);
     const int64_t* col = subs + (int64_t)m * n;
     for (int64_t e = 0; e < n; ++e) {

@@ -8,27 +8,37 @@ namespace aoadmm {
 
 void Engine::topk(int p, int mode, int64_t nq, const int64_t* subs, int k, const int64_t* excl_off, const int64_t* excl_idx,
                   int64_t* idx_host, double* val_host) {
+  topk_run("aoadmm_resident_topk", p, mode, nq, subs, nullptr, k, excl_off, excl_idx, idx_host, val_host);
+}
+
+void Engine::topk_w(int p, int mode, int64_t nq, const double* W, int k, const int64_t* excl_off, const int64_t* excl_idx,
+                    int64_t* idx_host, double* val_host) {
+  topk_run("aoadmm_resident_topk_w", p, mode, nq, nullptr, W, k, excl_off, excl_idx, idx_host, val_host);
+}
+
+// subs (the weights are formed on the device) or W (nq x R column-major on the host, uploaded as it is: finite or not)
+void Engine::topk_run(const char* what, int p, int mode, int64_t nq, const int64_t* subs, const double* W, int k, const int64_t* excl_off,
+                      const int64_t* excl_idx, int64_t* idx_host, double* val_host) {
+  const bool given = subs == nullptr && W != nullptr;
   require_usable();
   AO_REQUIRE(model_done_, "call aoadmm_model_end first");
   AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
   TensorInfo& t = tensors_[p];
   if (t.par2)
-    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("aoadmm_resident_topk: tensor %d is a PARAFAC2 block; top-k completions are for CP blocks", p));
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("%s: tensor %d is a PARAFAC2 block; top-k completions are for CP blocks", what, p));
   const int nd = t.nmodes;
   AO_REQUIRE(nd >= 2 && nd <= kCooMaxModes, "tensor %d: order %d", p, nd);
   AO_REQUIRE(mode >= 0 && mode < nd, "tensor %d: mode %d outside [0, %d)", p, mode, nd);
   AO_REQUIRE(k >= 1 && k <= kTopkMax, "k = %d outside [1, %d]", k, kTopkMax);
   AO_REQUIRE(nq >= 0 && nq < ((int64_t)1 << 31), "nq = %lld outside [0, 2^31)", (long long)nq);
   if (nq == 0) return;
-  AO_REQUIRE(subs != nullptr && idx_host != nullptr && val_host != nullptr, "null subs / idx / val");
+  AO_REQUIRE((subs != nullptr || W != nullptr) && idx_host != nullptr && val_host != nullptr, "null subs / W / idx / val");
   AO_REQUIRE(excl_off == nullptr || excl_idx != nullptr || excl_off[nq] == 0, "null excl_idx");
   const int64_t I = modes_[t.modes[mode]].rows;
 
-  // the free mode's column is ignored: it is checked as a column of zeros
-  std::vector<int64_t> s64(subs, subs + (size_t)nd * nq);
-  std::fill(s64.begin() + (size_t)mode * nq, s64.begin() + (size_t)(mode + 1) * nq, (int64_t)0);
+  // the free mode's column is ignored
   std::vector<int> idx32;
-  heldout_check_subs(t, p, nq, s64.data(), idx32);
+  if (!given) heldout_check_subs(t, p, nq, subs, idx32, mode);
 
   // the exclusion lists: offsets non-decreasing from 0, rows in range; every list sorted before the upload
   std::vector<int> ex32;
@@ -49,15 +59,25 @@ void Engine::topk(int p, int mode, int64_t nq, const int64_t* subs, int k, const
   AO_HIP(hipSetDevice(device_));
   const HeldoutFactors hf = heldout_factors(t, nullptr);
   const TopkPlan pl = topk_plan(I, hf.R, nq, k);
-  DevBuf idx, eoff, eidx, ws, oidx, oval;
+  DevBuf idx, wgiven, eoff, eidx, ws, oidx, oval;
   idx.alloc(idx32.size() * sizeof(int));
   ws.alloc(pl.workspace_bytes);
   oidx.alloc((size_t)nq * k * sizeof(int64_t));
   oval.alloc((size_t)nq * k * sizeof(double));
-  AO_HIP(hipMemcpyAsync(idx.p, idx32.data(), idx32.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
+  if (!given) AO_HIP(hipMemcpyAsync(idx.p, idx32.data(), idx32.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
   TopkArgs a;
   a.hf = hf; a.mode = mode; a.I = I; a.nq = nq; a.k = k;
   a.idx = idx.as<int>();
+  std::vector<double> wrow;                            // the scores kernel reads W row-major
+  if (given) {
+    const int R = hf.R;
+    wrow.resize((size_t)nq * R);
+    for (int64_t q = 0; q < nq; ++q)
+      for (int r = 0; r < R; ++r) wrow[(size_t)q * R + r] = W[(size_t)r * nq + q];
+    wgiven.alloc(wrow.size() * sizeof(double));
+    AO_HIP(hipMemcpyAsync(wgiven.p, wrow.data(), wrow.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+    a.W = wgiven.d();
+  }
   if (excl_off != nullptr) {
     eoff.alloc((size_t)(nq + 1) * sizeof(int64_t));
     eidx.alloc(std::max<size_t>(1, ex32.size()) * sizeof(int));

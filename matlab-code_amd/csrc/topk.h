@@ -34,6 +34,7 @@ struct TopkArgs {
   int64_t nq = 0;
   int k = 0;
   const int* idx = nullptr;          // device int32 [nd x nq]; row `mode` is not read
+  const double* W = nullptr;         // device [nq x R] row-major or null; given: the weights launch is skipped, idx unused
   const int64_t* excl_off = nullptr; // device [nq + 1] or null: no exclusions
   const int* excl_idx = nullptr;     // device, every query's list sorted ascending
   void* workspace = nullptr;         // plan.workspace_bytes

@@ -354,16 +354,18 @@ void topk_enqueue(const TopkArgs& a, const TopkPlan& pl, hipStream_t s) {
   ws += align256(c1 * sizeof(double));
   int* pong_idx = reinterpret_cast<int*>(ws);
 
-  TopkWArgs wa;
-  wa.hf = a.hf; wa.mode = a.mode; wa.nq = a.nq; wa.idx = a.idx; wa.W = W;
-  topk_weights_k<<<(unsigned)cdiv(a.nq * R, 256), 256, 0, s>>>(wa);
-  AO_KERNEL_CHECK();
+  if (a.W == nullptr) {
+    TopkWArgs wa;
+    wa.hf = a.hf; wa.mode = a.mode; wa.nq = a.nq; wa.idx = a.idx; wa.W = W;
+    topk_weights_k<<<(unsigned)cdiv(a.nq * R, 256), 256, 0, s>>>(wa);
+    AO_KERNEL_CHECK();
+  }
 
   TopkKArgs ka;
   ka.F = a.hf.f[a.mode];
   ka.R = R; ka.k = a.k; ka.cap = pl.cap;
   ka.I = a.I; ka.nq = a.nq; ka.slab_rows = pl.slab_rows; ka.slabs = pl.slabs;
-  ka.W = W; ka.excl_off = a.excl_off; ka.excl_idx = a.excl_idx;
+  ka.W = a.W != nullptr ? a.W : W; ka.excl_off = a.excl_off; ka.excl_idx = a.excl_idx;
   ka.cand_val = cand_val; ka.cand_idx = cand_idx;
   switch ((R + 3) / 4) {
     case 1: launch_scores<1>(ka, pl, s); break;

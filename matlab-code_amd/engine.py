@@ -289,7 +289,14 @@ class Engine:
         (`sptensor.fiber_lists` gives the stored ones).  Returns (idx int64 nq x k, val float64 nq x k), padded with
         -1 and -inf.  Needs the model and the factor state, not the block's data; no nq x I_mode array exists."""
         subs = self._subs_f(subs, 'topk')
-        nq, k = int(subs.shape[0]), int(k)
+        i64p = C.POINTER(C.c_int64)
+        return self._topk_call('topk', self.lib.aoadmm_resident_topk, p, mode, int(subs.shape[0]),
+                               subs.ctypes.data_as(i64p), k, exclude, keep=subs)
+
+    def _topk_call(self, what, entry, p, mode, nq, queries, k, exclude, keep=None):
+        """The part `topk` and `topk_w` share: the outputs, the exclusion lists, the call.  `queries` is the pointer the
+        entry takes as its fifth argument (the subscripts or the weights); `keep` holds its array alive."""
+        k = int(k)
         idx = np.full((nq, max(k, 0)), -1, dtype=np.int64)
         val = np.full((nq, max(k, 0)), -np.inf)
         i64p = C.POINTER(C.c_int64)
@@ -298,16 +305,70 @@ class Engine:
             off = np.ascontiguousarray(np.asarray(exclude[0], dtype=np.int64).reshape(-1))
             ex = np.ascontiguousarray(np.asarray(exclude[1], dtype=np.int64).reshape(-1))
             if off.shape[0] != nq + 1:
-                raise ValueError('topk: exclude[0] must hold nq + 1 = %d offsets, got %d' % (nq + 1, off.shape[0]))
+                raise ValueError('%s: exclude[0] must hold nq + 1 = %d offsets, got %d' % (what, nq + 1, off.shape[0]))
             if off[-1] != ex.shape[0]:
-                raise ValueError('topk: exclude[0][-1] = %d but exclude[1] holds %d rows' % (off[-1], ex.shape[0]))
+                raise ValueError('%s: exclude[0][-1] = %d but exclude[1] holds %d rows' % (what, off[-1], ex.shape[0]))
             if ex.shape[0] == 0:
                 ex = np.zeros(1, dtype=np.int64)          # a valid address for an empty list
-        capi.check(self.lib.aoadmm_resident_topk(
-            self.h, int(p), int(mode), nq, subs.ctypes.data_as(i64p), k,
-            off.ctypes.data_as(i64p) if off is not None else None, ex.ctypes.data_as(i64p) if ex is not None else None,
-            idx.ctypes.data_as(i64p), capi.dptr(val)))
+        capi.check(entry(self.h, int(p), int(mode), nq, queries, k,
+                         off.ctypes.data_as(i64p) if off is not None else None, ex.ctypes.data_as(i64p) if ex is not None else None,
+                         idx.ctypes.data_as(i64p), capi.dptr(val)))
         return idx, val
+
+    def block_rank(self, p):
+        """The number of components R of block p (`aoadmm_tensor_rank`), from the model the engine holds."""
+        r = C.c_int(0)
+        capi.check(self.lib.aoadmm_tensor_rank(self.h, int(p), C.byref(r)))
+        return r.value
+
+    def topk_w(self, p, mode, W, k, exclude=None):
+        """`topk` with the weights given (`aoadmm_resident_topk_w`): W is nq x R, row q the weights of query q, used as
+        they are.  Ranks a row that `fold_in` returned: for a 2-way block the folded rows are the weights along the
+        other mode; for a higher order multiply them by the rows of the remaining modes.  Same order, exclusions and
+        padding as `topk`."""
+        W = capi.as_f(W)
+        if W.ndim != 2:
+            raise ValueError('topk_w: W must be nq x R')
+        R = self.block_rank(p)                                  # an unknown block is refused here, as the library refuses it
+        if W.shape[1] != R:
+            raise ValueError('topk_w: W has %d columns, block %d has R = %d' % (W.shape[1], int(p), R))
+        return self._topk_call('topk_w', self.lib.aoadmm_resident_topk_w, p, mode, int(W.shape[0]), capi.dptr(W), k, exclude, keep=W)
+
+    def fold_in(self, p, mode, subs, vals, nq=None, ridge=0.0, nonneg=False, max_inner=5, tol=(0.0, 0.0), return_normal=False):
+        """The factor rows of new indices along mode `mode` (0-based position in the block) of CP block p from their
+        entries, every other factor held fixed (`aoadmm_resident_fold_in`).  subs is nobs x N, 0-based, with the query
+        number in column `mode` (`sptensor.take_rows` gives such a list); vals has nobs values; nq=None: max(q) + 1.
+        Row q solves (G_q + ridge I) u = b_q over the observations of q, or with nonneg=True runs the row ADMM loop for
+        non-negativity (at most max_inner iterations, tol = (primal, dual)) and returns its feasible iterate.  Returns
+        (rows nq x R, info int32 nq: 1 where the system was not positive definite and the row is NaN, iters int32 nq),
+        and with return_normal=True also (gram nq x R x R, rhs nq x R), the normal equations before the ridge."""
+        vals = np.ascontiguousarray(np.asarray(vals, dtype=np.float64).reshape(-1))
+        subs = self._subs_f(subs, 'fold_in')
+        nobs = int(vals.shape[0])
+        if subs.shape[0] != nobs:
+            raise ValueError('fold_in: subs must be nobs x N with nobs = len(vals)')
+        mode = int(mode)
+        if nq is None:
+            if not 0 <= mode < subs.shape[1]:
+                raise ValueError('fold_in: mode %d outside [0, %d)' % (mode, subs.shape[1]))
+            nq = int(subs[:, mode].max()) + 1 if nobs else 0
+        nq = int(nq)
+        R = self.block_rank(p)                                  # an unknown block is refused here, as the library refuses it
+        n = max(nq, 0)
+        rows = np.zeros((n, R), order='F')
+        info = np.zeros(n, dtype=np.int32)
+        iters = np.zeros(n, dtype=np.int32)
+        gram = np.zeros((n, R, R)) if return_normal else None     # block q: R x R, symmetric
+        rhs = np.zeros((n, R), order='F') if return_normal else None
+        opt = capi.FoldinOptions(float(ridge), 1 if nonneg else 0, int(max_inner), float(tol[0]), float(tol[1]))
+        ip = C.POINTER(C.c_int)
+        capi.check(self.lib.aoadmm_resident_fold_in(
+            self.h, int(p), mode, nq, nobs, subs.ctypes.data_as(C.POINTER(C.c_int64)) if nobs else None,
+            capi.dptr(vals) if nobs else None, C.byref(opt), capi.dptr(rows), info.ctypes.data_as(ip), iters.ctypes.data_as(ip),
+            capi.dptr(gram), capi.dptr(rhs)))
+        if return_normal:
+            return rows, info, iters, gram, rhs
+        return rows, info, iters
 
     def resident_mttkrp(self, p, tensor_mode, rows, R):
         """One MTTKRP of the resident block p against the current factors (`aoadmm_resident_mttkrp`): rows x R."""
@@ -329,7 +390,8 @@ class Engine:
         """(ms, launches, bytes, flops) of a kernel class since the last reset (`aoadmm_kernel_stats`); which = 3:
         MTTKRPs of sparse blocks (of a sharded block: this rank's share), passes over the nonzeros of PARAFAC2
         blocks with sparse slabs and EM steps of observed-only blocks; which = 4 + n: the pass of those EM steps over
-        the copy of tensor mode n; which = 12: the held-out passes; which = 13: the top-k completions (one launch per `topk` call)."""
+        the copy of tensor mode n; which = 12: the held-out passes; which = 13: the top-k completions (one launch per `topk` call);
+        which = 14: the fold-in of new rows (one launch per `fold_in` call)."""
         ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         capi.check(self.lib.aoadmm_kernel_stats(self.h, int(which), int(bool(reset)), C.byref(ms), C.byref(n),
                                                 C.byref(by), C.byref(fl)))

@@ -115,6 +115,26 @@ class sptensor:
         take = np.repeat(lo - off[:-1], hi - lo) + np.arange(off[-1], dtype=np.int64)
         return off, np.ascontiguousarray(rows[take].astype(np.int64))
 
+    def take_rows(self, mode, rows):
+        """(subs, vals) of the stored entries whose subscript along `mode` is in `rows` (distinct indices), in stored
+        order, with column `mode` renumbered to the position in `rows`: the list `Engine.fold_in` takes for the queries
+        rows[0], rows[1], ...  A row without stored entries contributes nothing."""
+        mode = int(mode)
+        if not 0 <= mode < self.ndim:
+            raise ValueError('sptensor.take_rows: mode %d outside [0, %d)' % (mode, self.ndim))
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        if rows.size and (rows.min() < 0 or rows.max() >= self.shape[mode]):
+            raise ValueError('sptensor.take_rows: a row is outside [0, %d)' % self.shape[mode])
+        if len(np.unique(rows)) != len(rows):
+            raise ValueError('sptensor.take_rows: rows must be distinct')
+        pos = np.full(self.shape[mode], -1, dtype=np.int64)
+        pos[rows] = np.arange(len(rows), dtype=np.int64)
+        q = pos[self.subs[:, mode]]
+        keep = q >= 0
+        subs = self.subs[keep].copy()
+        subs[:, mode] = q[keep]
+        return np.ascontiguousarray(subs), np.ascontiguousarray(self.vals[keep])
+
     def __repr__(self):
         return 'sptensor(shape=%s, nnz=%d)' % (self.shape, self.nnz)
 
