@@ -308,6 +308,33 @@ int aoadmm_tensor_upload_coo_sharded(aoadmm_ctx* ctx, int p, int64_t nnz, const 
  * sparse data stays refused.  With a communicator the block is replicated: every rank does the same work, no
  * collective. */
 int aoadmm_tensor_set_observed_only(aoadmm_ctx* ctx, int p, int on);
+/* WEIGHTS for an observed-only block: stored entry e gets w_e = wts[e] in [0, 1], every unstored entry the one weight
+ * unstored_weight (alpha) in [0, 1]; W is the dense array those define.  aoadmm_solve then minimises
+ * Z.weights(p) * sum W o (X - M)^2 with the rest of the model by the same EM (cmtf_fun_AOADMM.m:408-441) with the
+ * imputation Xhat = W o X + (1 - W) o M_old (the majoriser of Srebro and Jaakkola), from Xhat = W o X in every solve.
+ * w = 1 everywhere with alpha = 0 is the observed-only block, with alpha = 1 the plain block; w_e = 0 makes a stored
+ * entry missing.  The model never exists as an array:
+ *   residual array of a copy   r_e = w_e x_e - (w_e - alpha) m_old,e              (w_e x_e before the first step)
+ *   MTTKRP of mode n           weight * [sparse MTTKRP of r + (1 - alpha) Fo_n had_{j != n}(Fo_j' F_j)]
+ *   objective                  sum_Omega w_e (x_e - m_e)^2 + alpha (sum(had_n F_n' F_n) - sum_Omega m_e^2)
+ *   num of f_rel_missing       (1 - alpha)^2 (||M_new - M_old||^2 - sum_Omega dm^2) + sum_Omega (1 - w_e)^2 dm_e^2
+ *   den                        (1 - alpha)^2 (||M_old||^2 - sum_Omega m_old^2) + sum_Omega (1 - w_e)^2 m_old,e^2
+ * (the stopping rule :457-459 is unchanged, num = den = 0 gives 0), and aoadmm_tensor_normsq returns sum_Omega w x^2.
+ * subs is column-major nnz x N, 0-based, in any order, as aoadmm_tensor_upload_coo takes it, and must name exactly the
+ * block's stored entries (after coalescing), once each; wts[e] belongs to subs[e].  nnz = 0 with wts = NULL sets
+ * alpha alone, with stored weights 1 (and no weight array: the footprint stays that of the mark).  The call marks the
+ * block observed-only if it is not; aoadmm_tensor_set_observed_only(p, 0) and any upload drop the weights,
+ * aoadmm_tensor_set_observed_only(p, 1) on a weighted block keeps them.  Resident with a weight list: N (4 N + 24) bytes
+ * per nonzero plus the snapshots.  aoadmm_resident_em_step returns its three numbers under these definitions.
+ * Weights above 1 are the caller's to normalise: divide W by its maximum, which scales the block's objective by that
+ * maximum (fold it into Z.weights(p)).  Small alpha and small w slow EM down: its rate follows the share of the
+ * information that is imputed.
+ * AOADMM_ERR_INVALID, block untouched: a weight or alpha outside [0, 1] or not finite; a duplicate, an unstored or an
+ * out-of-range subscript, a stored entry the list leaves out; nnz other than the block's count of stored entries.
+ * AOADMM_ERR_UNSUPPORTED: a dense block, a PARAFAC2 block, a block uploaded with aoadmm_tensor_upload_coo_sharded and a
+ * multi-device context.  No float atomics: two runs return the same bits. */
+int aoadmm_tensor_set_entry_weights(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* wts,
+                                    double unstored_weight);
 /* One EM step of an observed-only block with the current factors: the residuals x - m of the stored entries, then the
  * snapshot of the factors.  stats = {sum over the stored entries of (x - m)^2, num, den} with num / den the squared
  * norms of the change of the missing entries and of their old values (:436-440); the first step after the mark or a

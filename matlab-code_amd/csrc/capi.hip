@@ -438,6 +438,15 @@ int aoadmm_tensor_set_observed_only(aoadmm_ctx* ctx, int p, int on) {
   CTX_OR_FAIL(ctx);
   return guarded([&] { on_engines(ctx, [&](Engine& e, int) { e.set_observed_only(p, on != 0); }); });
 }
+int aoadmm_tensor_set_entry_weights(aoadmm_ctx* ctx, int p, int64_t nnz, const int64_t* subs, const double* wts,
+                                    double unstored_weight) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    if (ctx->multi && ctx->multi->eng.size() > 1)
+      throw Error(AOADMM_ERR_UNSUPPORTED, "aoadmm_tensor_set_entry_weights is not available on a multi-device context (aoadmm_create_multi with more than one device): use one context per rank and a communicator");
+    on_engines(ctx, [&](Engine& e, int) { e.set_entry_weights(p, nnz, subs, wts, unstored_weight); });
+  });
+}
 int aoadmm_resident_em_step(aoadmm_ctx* ctx, int p, double stats[3]) {
   CTX_OR_FAIL(ctx);
   return guarded([&] {

@@ -583,8 +583,10 @@ static void sparse_mttkrp(const BlockCtx& cx, CpBlock& b, int pos, const FactorR
   const LaunchTimers::Pair pr = tm.begin(tm.stats[3], tm.profile, cx.stream);
   // observed-only block after an EM step: the imputed tensor is the residuals on the stored entries plus the snapshot's
   // model everywhere (sparse_em.h); before the first step the missing entries are 0 and this is the plain MTTKRP
+  // a weighted block reads its residual array from the start: W o X before the first step (sem_reset)
   const bool imputed = b.sem.on && b.sem.have_snap;
-  coo_mttkrp(b.coo, pos, f, R, scale, out, ldOut, cx.stream, span_only, imputed ? b.sem.res[pos].d() : nullptr);
+  coo_mttkrp(b.coo, pos, f, R, scale, out, ldOut, cx.stream, span_only,
+             imputed || (b.sem.on && b.sem.weighted) ? b.sem.res[pos].d() : nullptr);
   double bytes = coo_mttkrp_bytes(b.coo, pos, R), flops = coo_mttkrp_flops(b.coo, R);
   if (imputed) {
     AO_REQUIRE(b.sem.R == R, "observed-only block was marked for rank %d, the MTTKRP has rank %d", b.sem.R, R);

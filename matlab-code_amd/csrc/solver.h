@@ -198,6 +198,8 @@ class Engine {
   void tensor_mask_upload(int p, const uint8_t* mask);
   void par2_slab_mask_upload(int p, int k, const uint8_t* mask);
   void set_observed_only(int p, bool on);          // sparse CP block: unstored entries are missing (sparse_em.h)
+  // weights in [0, 1] for the stored entries (wts null with nnz = 0: all 1) and one for every unstored entry
+  void set_entry_weights(int p, int64_t nnz, const int64_t* subs, const double* wts, double unstored_weight);
   double tensor_normsq(int p);
   // what tensor p keeps on the device: the precision its passes stream, the power-of-two scale of a half block (else 1)
   // and the bytes of its natural array, pass copies, transposed copy and mask (dense CP blocks), of the per-mode copies

@@ -374,7 +374,7 @@ void Engine::tensor_storage_info(int p, int* precision, double* scale, int64_t* 
       for (int m = 0; m < b.coo.nd; ++m)
         for (const DevBuf* d : {&b.coo.mode[m].row, &b.coo.mode[m].oidx, &b.coo.mode[m].val})
           if (d->p) n += (int64_t)d->bytes;
-      n += sem_resident_bytes(b.sem);      // observed-only: 8 more bytes per nonzero per copy and the factor snapshots
+      n += sem_resident_bytes(b.sem);      // observed-only: 8 more bytes per nonzero per copy (16 with entry weights) and the factor snapshots
     }
     *resident_bytes = n;
   }
@@ -481,6 +481,10 @@ double Engine::tensor_normsq(int p) {
       tensor_sumsq(slot, t.p2.sp.coo.mode[0].val.p, AOADMM_PREC_F64, t.p2.sp.coo.nnz, ws.d(), stream_);
     } else if (t.par2) {   // sum_k ||X_k||_F^2  (cmtf_AOADMM.m:145-155)
       tensor_sumsq(slot, t.p2.X.p, AOADMM_PREC_F64, (int64_t)t.p2.I * t.p2.Jtot, ws.d(), stream_);
+    } else if (t.blk.sparse && t.blk.sem.on && t.blk.sem.weighted) {   // sum_Omega w x^2 (sem_set_weights)
+      t.normsq = t.blk.sem.wnormsq;
+      t.normsq_valid = true;
+      return t.normsq;
     } else if (t.blk.sparse) {     // norm(sptensor)^2 (:132): the coalesced values
       const CooBlock& c = t.blk.coo; // replicated: every rank holds all of them; sharded: the mode-0 shares cover them once
       AO_REQUIRE(!c.sharded || (c.cut_rank == rank_ && c.cut_world == world_),
@@ -640,8 +644,50 @@ void Engine::set_observed_only(int p, bool on) {
     throw Error(AOADMM_ERR_UNSUPPORTED, fmt("observed-only is not available for a block uploaded with aoadmm_tensor_upload_coo_sharded (tensor %d): upload it replicated", p));
   AO_REQUIRE(b.coo.nnz > 0, "tensor %d has no stored entry: an observed-only block needs observations", p);
   AO_HIP(hipSetDevice(device_));
+  if (b.sem.on && b.sem.weighted) t.normsq_valid = false;   // unmarking drops the weights: ||X||^2 is the plain one again
   if (!on) { b.sem.clear(); return; }
-  sem_enable(b.sem, b.coo, modes_[t.modes[0]].R);
+  sem_enable(b.sem, b.coo, modes_[t.modes[0]].R, stream_);   // a weighted block keeps its weights
+  AO_HIP(hipStreamSynchronize(stream_));
+}
+
+// Weighted least squares on an observed-only block (sparse_em.h): w_e in [0, 1] per stored entry, unstored_weight in
+// [0, 1] for every other entry.  The list must name exactly the block's stored entries, once each, in any order; it
+// goes through coo_build with the weights as values, which leaves every mode's weights in the order of that copy.
+// Everything is checked before the block changes.
+void Engine::set_entry_weights(int p, int64_t nnz, const int64_t* subs, const double* wts, double unstored_weight) {
+  require_usable();
+  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
+  AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
+  TensorInfo& t = tensors_[p];
+  if (t.par2)
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("entry weights are for sparse CP blocks: tensor %d is PARAFAC2", p));
+  CpBlock& b = t.blk;
+  AO_REQUIRE(b.has_data, "tensor %d has no data: upload it with aoadmm_tensor_upload_coo first", p);
+  if (!b.sparse)
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("entry weights are for sparse CP blocks: tensor %d holds dense data (use Z.miss / aoadmm_tensor_mask_upload)", p));
+  if (b.coo.sharded)
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("entry weights are not available for a block uploaded with aoadmm_tensor_upload_coo_sharded (tensor %d): upload it replicated", p));
+  AO_REQUIRE(b.coo.nnz > 0, "tensor %d has no stored entry: a weighted block needs observations", p);
+  AO_REQUIRE(std::isfinite(unstored_weight) && unstored_weight >= 0.0 && unstored_weight <= 1.0,
+             "entry weights: the unstored weight %g is outside [0, 1] (divide the weights by their maximum)", unstored_weight);
+  AO_REQUIRE(nnz >= 0 && (nnz == 0) == (wts == nullptr) && (nnz == 0 || subs != nullptr),
+             "entry weights: give subs and wts for every stored entry, or nnz = 0 and wts = NULL for stored weights 1");
+  AO_REQUIRE(nnz == 0 || nnz == b.coo.nnz, "entry weights: %lld weights for a block that stores %lld entries", (long long)nnz, (long long)b.coo.nnz);
+  for (int64_t e = 0; e < nnz; ++e)
+    AO_REQUIRE(std::isfinite(wts[e]) && wts[e] >= 0.0 && wts[e] <= 1.0,
+               "entry weights: weight %g of entry %lld is outside [0, 1] (divide the weights by their maximum)", wts[e], (long long)e);
+  AO_HIP(hipSetDevice(device_));
+  CooBlock wl;
+  if (nnz > 0) {
+    coo_build(wl, b.coo.nd, b.coo.dims, nnz, subs, wts, stream_);     // out-of-range subscripts: AOADMM_ERR_INVALID
+    if (wl.nnz != nnz)
+      throw Error(AOADMM_ERR_INVALID, fmt("entry weights: %lld of the %lld subscripts are duplicates", (long long)(nnz - wl.nnz), (long long)nnz));
+    sem_check_weight_list(b.coo, wl, stream_);
+  }
+  const int R = modes_[t.modes[0]].R;
+  if (!b.sem.on || b.sem.R != R) sem_enable(b.sem, b.coo, R, stream_);
+  sem_set_weights(b.sem, b.coo, nnz > 0 ? &wl : nullptr, unstored_weight, stream_);
+  t.normsq_valid = false;
 }
 
 void Engine::sparse_em_enqueue(int p, bool stats_only) {

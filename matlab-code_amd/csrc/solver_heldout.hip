@@ -282,7 +282,7 @@ void Engine::heldout_restore_best(int* iter) {
     // of 0 iterations leaves cannot be brought back, the entries stay as the last iteration left them).
     if (t.masked() && best_.iter > 0) em_pass_enqueue(p, 1);
     // observed-only: the next solve starts from missing entries at 0 whatever an earlier one left (solve_setup)
-    if (t.observed_only()) t.blk.sem.have_snap = false;
+    if (t.observed_only()) sem_reset(t.blk.sem, t.blk.coo, stream_);
     if (t.par2) par2_gather_slabs(t);                 // slab-sharded: the other ranks' slabs, as at the end of a solve
   }
   AO_HIP(hipStreamSynchronize(stream_));

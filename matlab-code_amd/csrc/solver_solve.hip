@@ -271,7 +271,7 @@ void Engine::solve_setup(const aoadmm_options& opt) {
       const CpBlock& b = t.blk;
       AO_REQUIRE(!b.coo.sharded && b.coo.nnz > 0 && b.sem.nnz == b.coo.nnz, "tensor %d: observed-only needs a replicated sparse block with stored entries", p);
       AO_REQUIRE(b.sem.R == modes_[t.modes[0]].R, "tensor %d was marked observed-only for rank %d", p, b.sem.R);
-      t.blk.sem.have_snap = false;
+      sem_reset(t.blk.sem, b.coo, stream_);
     }
   }
   for (int p = 0; p < n_tensors_; ++p) {

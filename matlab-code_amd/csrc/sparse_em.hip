@@ -23,7 +23,9 @@ struct SemArgs {
   CooFactor fo[kCooMaxModes];   // the snapshot in the same order (STAT == 2)
   int nd, R;
   double* res;                  // x - m per entry, or null
-  double* part;                 // 3 sums per team (STAT > 0)
+  double* part;                 // kSemSums (WT: kSemSumsW) sums per team (STAT > 0)
+  const double* wt;             // WT: the stored entries' weights in the copy's order, or null (all 1)
+  double alpha;                 // WT: the weight of every unstored entry
 };
 
 constexpr int kSemUnroll = 4;
@@ -38,7 +40,9 @@ __device__ __forceinline__ double team_sum(double v) {
 // ND = order of the block (2..4 compiled in; 0: a.nd at run time, up to 8)
 // STAT 0: residuals only; 1: + sum (x-m)^2 and sum m^2; 2: + sum (m_new - m_old)^2 in the telescoped form
 //   m_new - m_old = sum_a prod_{n<a} fo_n * (f_a - fo_a) * prod_{n>a} f_n   per column, then summed over the columns
-template <int G, int ND, int STAT>
+// WT: the weighted form.  res = w x - (w - alpha) m, the sums are sum w (x-m)^2, sum m^2, sum (1-w)^2 m^2 and, STAT == 2,
+//   sum dm^2, sum (1-w)^2 dm^2: no difference of sums is formed here
+template <int G, int ND, int STAT, bool WT>
 __global__ __launch_bounds__(256) void sem_pass_k(SemArgs a) {
   const int64_t team = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
   const int r = (int)(threadIdx.x % G);
@@ -49,9 +53,9 @@ __global__ __launch_bounds__(256) void sem_pass_k(SemArgs a) {
   const int nd = ND > 0 ? ND : a.nd;
   const bool live = r < a.R;
   const int rr = live ? r : a.R - 1;                 // lanes beyond R read column R - 1 and contribute +0
-  double s_res = 0.0, s_m2 = 0.0, s_d2 = 0.0;
+  double s_res = 0.0, s_m2 = 0.0, s_d2 = 0.0, s_cm2 = 0.0, s_cd2 = 0.0;
   for (int64_t i0 = start; i0 < end; i0 += kSemUnroll) {
-    double mu[kSemUnroll], du[kSemUnroll], xu[kSemUnroll];
+    double mu[kSemUnroll], du[kSemUnroll], xu[kSemUnroll], wu[kSemUnroll];
 #pragma unroll
     for (int u = 0; u < kSemUnroll; ++u) {
       const int64_t i = i0 + u < end ? i0 + u : end - 1;
@@ -65,6 +69,7 @@ __global__ __launch_bounds__(256) void sem_pass_k(SemArgs a) {
         }
       }
       xu[u] = a.val[i];
+      if (WT) wu[u] = a.wt != nullptr ? a.wt[i] : 1.0;
       double m = 1.0;
 #pragma unroll
       for (int n = 0; n < NMAX; ++n)
@@ -93,52 +98,82 @@ __global__ __launch_bounds__(256) void sem_pass_k(SemArgs a) {
     for (int u = 0; u < kSemUnroll; ++u) {
       if (i0 + u < end) {
         const double e = xu[u] - mu[u];
-        if (a.res != nullptr && r == 0) a.res[i0 + u] = e;
-        if (STAT > 0) { s_res += e * e; s_m2 += mu[u] * mu[u]; }
-        if (STAT == 2) s_d2 += du[u] * du[u];
+        if (WT) {
+          const double w = wu[u], c2 = (1.0 - w) * (1.0 - w), m2 = mu[u] * mu[u], d2 = du[u] * du[u];
+          if (a.res != nullptr && r == 0) a.res[i0 + u] = w * xu[u] - (w - a.alpha) * mu[u];
+          if (STAT > 0) { s_res += w * (e * e); s_m2 += m2; s_cm2 += c2 * m2; }
+          if (STAT == 2) { s_d2 += d2; s_cd2 += c2 * d2; }
+        } else {
+          if (a.res != nullptr && r == 0) a.res[i0 + u] = e;
+          if (STAT > 0) { s_res += e * e; s_m2 += mu[u] * mu[u]; }
+          if (STAT == 2) s_d2 += du[u] * du[u];
+        }
       }
     }
   }
   if (STAT > 0 && r == 0) {
-    a.part[3 * team + 0] = s_res;
-    a.part[3 * team + 1] = s_m2;
-    a.part[3 * team + 2] = s_d2;
+    if (WT) {
+      double* q = a.part + kSemSumsW * team;
+      q[0] = s_res; q[1] = s_m2; q[2] = s_cm2; q[3] = s_d2; q[4] = s_cd2;
+    } else {
+      a.part[3 * team + 0] = s_res;
+      a.part[3 * team + 1] = s_m2;
+      a.part[3 * team + 2] = s_d2;
+    }
   }
 }
 
 static unsigned sem_blocks(int64_t n, int t = 256) { return (unsigned)std::max<int64_t>(1, cdiv(n, t)); }
 
-template <int G, int STAT>
+template <int G, int STAT, bool WT>
 static void launch_sem_nd(const SemArgs& a, hipStream_t s) {
   const unsigned grid = sem_blocks(cdiv(a.nnz, kCooChunk) * G);
   switch (a.nd) {
-    case 2: sem_pass_k<G, 2, STAT><<<grid, 256, 0, s>>>(a); break;
-    case 3: sem_pass_k<G, 3, STAT><<<grid, 256, 0, s>>>(a); break;
-    case 4: sem_pass_k<G, 4, STAT><<<grid, 256, 0, s>>>(a); break;
-    default: sem_pass_k<G, 0, STAT><<<grid, 256, 0, s>>>(a); break;
+    case 2: sem_pass_k<G, 2, STAT, WT><<<grid, 256, 0, s>>>(a); break;
+    case 3: sem_pass_k<G, 3, STAT, WT><<<grid, 256, 0, s>>>(a); break;
+    case 4: sem_pass_k<G, 4, STAT, WT><<<grid, 256, 0, s>>>(a); break;
+    default: sem_pass_k<G, 0, STAT, WT><<<grid, 256, 0, s>>>(a); break;
   }
   AO_KERNEL_CHECK();
 }
 
-template <int G>
+template <int G, bool WT>
 static void launch_sem_stat(const SemArgs& a, int stat, hipStream_t s) {
   switch (stat) {
-    case 0: launch_sem_nd<G, 0>(a, s); break;
-    case 1: launch_sem_nd<G, 1>(a, s); break;
-    default: launch_sem_nd<G, 2>(a, s); break;
+    case 0: launch_sem_nd<G, 0, WT>(a, s); break;
+    case 1: launch_sem_nd<G, 1, WT>(a, s); break;
+    default: launch_sem_nd<G, 2, WT>(a, s); break;
   }
 }
 
-static void launch_sem(const SemArgs& a, int stat, hipStream_t s) {
+template <bool WT>
+static void launch_sem_team(const SemArgs& a, int stat, hipStream_t s) {
   const int R = a.R;
   const int G = R <= 4 ? 4 : R <= 8 ? 8 : R <= 16 ? 16 : R <= 32 ? 32 : 64;
   switch (G) {
-    case 4: launch_sem_stat<4>(a, stat, s); break;
-    case 8: launch_sem_stat<8>(a, stat, s); break;
-    case 16: launch_sem_stat<16>(a, stat, s); break;
-    case 32: launch_sem_stat<32>(a, stat, s); break;
-    default: launch_sem_stat<64>(a, stat, s); break;
+    case 4: launch_sem_stat<4, WT>(a, stat, s); break;
+    case 8: launch_sem_stat<8, WT>(a, stat, s); break;
+    case 16: launch_sem_stat<16, WT>(a, stat, s); break;
+    case 32: launch_sem_stat<32, WT>(a, stat, s); break;
+    default: launch_sem_stat<64, WT>(a, stat, s); break;
   }
+}
+
+static void launch_sem(const SemArgs& a, int stat, bool weighted, hipStream_t s) {
+  if (weighted) launch_sem_team<true>(a, stat, s);
+  else launch_sem_team<false>(a, stat, s);
+}
+
+// res = w o x, the residual array of the starting point of a weighted block (w absent: res = x)
+__global__ void sem_fill_k(double* res, const double* val, const double* wt, int64_t n) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
+    res[e] = wt != nullptr ? wt[e] * val[e] : val[e];
+}
+
+// flag[0] = 1 where two subscript arrays differ (every writer stores the same value)
+__global__ void sem_differ_k(int* flag, const int* x, const int* y, int64_t n) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
+    if (x[e] != y[e]) flag[0] = 1;
 }
 
 // ---------------------------------------------------------------------------
@@ -181,6 +216,7 @@ struct SemFinish {
   int form;                              // 0: statistics only; 1: first step (no snapshot); 2: later step
   double* em;                            // the block's EM slots
   double* hold;
+  double alpha;                          // WT: the weight of every unstored entry
 };
 
 // block-wide sum in a fixed order: every thread's value, then a tree over LDS
@@ -213,18 +249,28 @@ __device__ __forceinline__ double sem_pair(int ta, int tb, const double* GFo, co
 //   form 2: num = ||M_new - M_old||^2 - sum_Omega (dm)^2 with the telescoped norm
 //             sum_{a,b} sum(had_n T^a_n' T^b_n),  T^a_n = Fo_n (n < a), D_n (n = a), F_n (n > a);  den = hold[0]
 //   both leave hold[0] = sum(had F'F) - sum_Omega m_new^2 for the next step
+// WT (the weighted form; unst = sum(had F'F) - sum_Omega m^2 is the unstored entries' share of ||M||^2, never below 0):
+//   every form: em[kEmObsRes] = sum_Omega w (x - m)^2 + alpha * unst (form 0 needs F'F for that when alpha > 0)
+//   form 1: num = (1 - alpha)^2 unst + sum_Omega (1 - w)^2 m_new^2, den = 0
+//   form 2: num = (1 - alpha)^2 (||M_new - M_old||^2 - sum_Omega dm^2) + sum_Omega (1 - w)^2 dm^2;  den = hold[0]
+//   both leave hold[0] = (1 - alpha)^2 unst + sum_Omega (1 - w)^2 m_new^2
+template <bool WT>
 __global__ __launch_bounds__(256) void sem_finish_k(SemFinish a) {
   __shared__ double sh[256];
-  double p0 = 0.0, p1 = 0.0, p2 = 0.0;
+  constexpr int NS = WT ? kSemSumsW : kSemSums;
+  double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0, p4 = 0.0;
   for (int64_t t = threadIdx.x; t < a.nteams; t += 256) {
-    p0 += a.part[3 * t];
-    p1 += a.part[3 * t + 1];
-    p2 += a.part[3 * t + 2];
+    p0 += a.part[NS * t];
+    p1 += a.part[NS * t + 1];
+    p2 += a.part[NS * t + 2];
+    if (WT) { p3 += a.part[NS * t + 3]; p4 += a.part[NS * t + 4]; }
   }
   const double s_res = sem_block_sum(p0, sh);
   const double s_m2 = sem_block_sum(p1, sh);
-  const double s_d2 = sem_block_sum(p2, sh);
-  if (a.form == 0) {
+  const double s_cm2 = WT ? sem_block_sum(p2, sh) : 0.0;
+  const double s_d2 = sem_block_sum(WT ? p3 : p2, sh);
+  const double s_cd2 = WT ? sem_block_sum(p4, sh) : 0.0;
+  if (a.form == 0 && !(WT && a.alpha > 0.0)) {
     if (threadIdx.x == 0) a.em[kEmObsRes] = s_res;
     return;
   }
@@ -249,6 +295,21 @@ __global__ __launch_bounds__(256) void sem_finish_k(SemFinish a) {
   }
   const double normF = sem_block_sum(full, sh);
   const double normD = sem_block_sum(delta, sh);
+  if (WT) {
+    if (threadIdx.x == 0) {
+      const double unst = normF - s_m2 > 0.0 ? normF - s_m2 : 0.0;
+      const double move = normD - s_d2 > 0.0 ? normD - s_d2 : 0.0;
+      const double c2 = (1.0 - a.alpha) * (1.0 - a.alpha);
+      a.em[kEmObsRes] = s_res + a.alpha * unst;
+      if (a.form != 0) {
+        const double den = a.form == 2 ? a.hold[0] : 0.0;
+        a.em[kEmNum] = a.form == 2 ? c2 * move + s_cd2 : c2 * unst + s_cm2;
+        a.em[kEmDen] = den;
+        a.hold[0] = c2 * unst + s_cm2;
+      }
+    }
+    return;
+  }
   if (threadIdx.x == 0) {
     const double den = a.form == 2 ? a.hold[0] : 0.0;
     const double num = a.form == 2 ? normD - s_d2 : normF - s_m2;
@@ -262,7 +323,7 @@ __global__ __launch_bounds__(256) void sem_finish_k(SemFinish a) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-void sem_enable(SparseEm& e, const CooBlock& b, int R) {
+void sem_enable(SparseEm& e, const CooBlock& b, int R, hipStream_t s) {
   AO_REQUIRE(R >= 1 && R <= kMaxRank, "observed-only block: rank %d outside 1..%d", R, kMaxRank);
   SparseEm n;
   n.on = true; n.nd = b.nd; n.R = R; n.nnz = b.nnz;
@@ -276,17 +337,74 @@ void sem_enable(SparseEm& e, const CooBlock& b, int R) {
   }
   n.small.alloc(((size_t)5 * kCooMaxModes + 1) * R * R * sizeof(double));
   n.D.alloc((size_t)maxrows * R * sizeof(double));
-  n.part.alloc((size_t)3 * cdiv(b.nnz, kCooChunk) * sizeof(double));
+  n.part.alloc((size_t)kSemSumsW * cdiv(b.nnz, kCooChunk) * sizeof(double));
   n.ws.alloc(atb_ws_bytes(maxrows, R, R));
   n.hold.alloc(2 * sizeof(double));
+  if (e.on && e.weighted && e.nd == b.nd && e.nnz == b.nnz) {     // marked again: the weights stay
+    n.weighted = true; n.alpha = e.alpha; n.wnormsq = e.wnormsq;
+    for (int m = 0; m < b.nd; ++m) n.wt[m] = std::move(e.wt[m]);
+  }
   e = std::move(n);
+  sem_reset(e, b, s);
+}
+
+void sem_reset(SparseEm& e, const CooBlock& b, hipStream_t s) {
+  e.have_snap = false;
+  if (!e.weighted) return;                           // the plain MTTKRP reads the block's own values
+  AO_REQUIRE(e.on && e.nd == b.nd && e.nnz == b.nnz, "internal: weights of another block");
+  for (int m = 0; m < e.nd; ++m) {
+    sem_fill_k<<<sem_blocks(std::min<int64_t>(e.nnz, (int64_t)1 << 22)), 256, 0, s>>>(e.res[m].d(), b.mode[m].val.d(),
+                                                                                     e.wt[m].p ? e.wt[m].d() : nullptr, e.nnz);
+    AO_KERNEL_CHECK();
+  }
+}
+
+void sem_check_weight_list(const CooBlock& b, const CooBlock& wts, hipStream_t s) {
+  if (wts.nd != b.nd || wts.nnz != b.nnz)
+    throw Error(AOADMM_ERR_INVALID, fmt("entry weights: the list holds %lld distinct subscripts, the block stores %lld entries",
+                                        (long long)wts.nnz, (long long)b.nnz));
+  DevBuf flag;
+  flag.alloc(sizeof(int));
+  AO_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), s));
+  const unsigned grid = sem_blocks(std::min<int64_t>(b.nnz * std::max(1, b.nd - 1), (int64_t)1 << 22));
+  for (int m = 0; m < b.nd; ++m) {
+    sem_differ_k<<<grid, 256, 0, s>>>(flag.as<int>(), b.mode[m].row.as<int>(), wts.mode[m].row.as<int>(), b.nnz);
+    AO_KERNEL_CHECK();
+    sem_differ_k<<<grid, 256, 0, s>>>(flag.as<int>(), b.mode[m].oidx.as<int>(), wts.mode[m].oidx.as<int>(), b.nnz * (b.nd - 1));
+    AO_KERNEL_CHECK();
+  }
+  int differ = 0;
+  AO_HIP(hipMemcpyAsync(&differ, flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  AO_HIP(hipStreamSynchronize(s));
+  if (differ) throw Error(AOADMM_ERR_INVALID, "entry weights: the list names an entry the block does not store");
+}
+
+void sem_set_weights(SparseEm& e, const CooBlock& b, CooBlock* wts, double alpha, hipStream_t s) {
+  AO_REQUIRE(e.on && e.nd == b.nd && e.nnz == b.nnz && (!wts || (wts->nd == b.nd && wts->nnz == b.nnz)), "internal: weights for a block that is not marked");
+  e.weighted = true;
+  e.alpha = alpha;
+  for (int m = 0; m < e.nd; ++m) {
+    if (wts) e.wt[m] = std::move(wts->mode[m].val);
+    else e.wt[m].release();
+  }
+  sem_reset(e, b, s);
+  // sum_Omega w x^2 = <w o x, x> over the first copy
+  DevBuf ws;
+  ws.alloc(((size_t)kReduceBatchMax * kReduceBatchSplit + 1) * sizeof(double));
+  ReduceBatch rb;
+  ReduceTask k;
+  k.kind = RT_DOT; k.slot = ws.d() + (size_t)kReduceBatchMax * kReduceBatchSplit; k.x = e.res[0].d(); k.y = b.mode[0].val.d(); k.n = e.nnz;
+  rb.add(k);
+  reduce_batch(rb, ws.d(), s);
+  AO_HIP(hipMemcpyAsync(&e.wnormsq, k.slot, sizeof(double), hipMemcpyDeviceToHost, s));
+  AO_HIP(hipStreamSynchronize(s));
 }
 
 int64_t sem_resident_bytes(const SparseEm& e) {
   int64_t n = 0;
   if (!e.on) return 0;
   for (int m = 0; m < e.nd; ++m)
-    for (const DevBuf* d : {&e.res[m], &e.snapC[m], &e.snapR[m]})
+    for (const DevBuf* d : {&e.res[m], &e.wt[m], &e.snapC[m], &e.snapR[m]})
       if (d->p) n += (int64_t)d->bytes;
   return n;
 }
@@ -323,6 +441,8 @@ void sem_step_pass(SparseEm& e, const CooBlock& b, const SemFac* f, int pos, boo
   const CooMode& cm = b.mode[pos];
   a.row = cm.row.as<int>(); a.oidx = cm.oidx.as<int>(); a.val = cm.val.d();
   a.res = stats_only ? nullptr : e.res[pos].d();
+  a.wt = e.weighted && e.wt[pos].p ? e.wt[pos].d() : nullptr;
+  a.alpha = e.alpha;
   copy_order(a.f, f, nd, pos, R);
   int stat = 0;
   if (pos == 0) {                                    // the statistics ride on the mode-1 copy's pass
@@ -333,7 +453,7 @@ void sem_step_pass(SparseEm& e, const CooBlock& b, const SemFac* f, int pos, boo
       copy_order(a.fo, fo, nd, 0, R);
     }
   }
-  launch_sem(a, stat, s);
+  launch_sem(a, stat, e.weighted, s);
 }
 
 void sem_step_finish(SparseEm& e, const SemFac* f, bool stats_only, double* em, hipStream_t s) {
@@ -344,10 +464,12 @@ void sem_step_finish(SparseEm& e, const SemFac* f, bool stats_only, double* em, 
   fa.part = e.part.d(); fa.nteams = nteams; fa.nd = nd; fa.R = R; fa.em = em; fa.hold = e.hold.d();
   fa.GFo = e.mat(0, 0); fa.GF = e.mat(1, 0); fa.DtD = e.mat(2, 0); fa.DtFo = e.mat(3, 0);
   fa.form = stats_only ? 0 : snap ? 2 : 1;
-  if (!stats_only)
+  fa.alpha = e.alpha;
+  if (!stats_only || (e.weighted && e.alpha > 0.0))   // the weighted objective of the starting point needs ||M||^2
     for (int n = 0; n < nd; ++n)
       atb_small(e.mat(1, n), f[n].p, f[n].ld, f[n].p, f[n].ld, e.dims[n], R, R, e.ws.d(), nullptr, s);
-  sem_finish_k<<<1, 256, 0, s>>>(fa);
+  if (e.weighted) sem_finish_k<true><<<1, 256, 0, s>>>(fa);
+  else sem_finish_k<false><<<1, 256, 0, s>>>(fa);
   AO_KERNEL_CHECK();
   if (stats_only) return;
   // the snapshot: Fo <- F, Fo'Fo <- F'F
@@ -363,6 +485,8 @@ void sem_step_finish(SparseEm& e, const SemFac* f, bool stats_only, double* em, 
 void sem_mttkrp_correct(SparseEm& e, int pos, const SemFac* f, double scale, double* out, int64_t ldOut, hipStream_t s) {
   AO_REQUIRE(e.on && e.have_snap && pos >= 0 && pos < e.nd, "internal: imputed MTTKRP without a snapshot");
   const int R = e.R, RR = R * R;
+  if (e.weighted) scale *= 1.0 - e.alpha;            // the unstored entries keep (1 - alpha) of the snapshot's model
+  if (e.weighted && e.alpha == 1.0) return;          // nothing is imputed off the stored set
   for (int j = 0; j < e.nd; ++j)
     if (j != pos) atb_small(e.mat(4, j), e.snapC[j].d(), e.dims[j], f[j].p, f[j].ld, e.dims[j], R, R, e.ws.d(), nullptr, s);
   sem_had_k<<<sem_blocks(RR), 256, 0, s>>>(e.W(), e.mat(4, 0), RR, e.nd, pos, RR);
@@ -372,7 +496,8 @@ void sem_mttkrp_correct(SparseEm& e, int pos, const SemFac* f, double scale, dou
 
 double sem_pass_bytes(const SparseEm& e, bool stats, bool with_snapshot, bool writes) {
   const double nz = (double)e.nnz, nd = (double)e.nd;
-  return nz * (4.0 * nd + 8.0) + nz * nd * e.R * 8.0 * (stats && with_snapshot ? 2.0 : 1.0) + (writes ? nz * 8.0 : 0.0);
+  const double wbytes = e.weighted && e.wt[0].p ? nz * 8.0 : 0.0;   // the weights in the copy's order
+  return nz * (4.0 * nd + 8.0) + wbytes + nz * nd * e.R * 8.0 * (stats && with_snapshot ? 2.0 : 1.0) + (writes ? nz * 8.0 : 0.0);
 }
 
 double sem_pass_flops(const SparseEm& e, bool stats, bool with_snapshot) {

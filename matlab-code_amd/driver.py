@@ -369,6 +369,57 @@ def observed_only_blocks(Z, observed_only, sparse_sharding=False):
     return blocks
 
 
+def entry_weight_blocks(Z, entry_weights, unstored_weight, observed=(), sparse_sharding=False):
+    """`alg_options['hip']['sparse_entry_weights']` / `['sparse_unstored_weight']` -> {0-based block: (wts or None,
+    alpha)}, checked on the host before the engine is touched.  Each option is None or a list over the blocks:
+    `entry_weights[p]` is an array aligned with the `subs` / `vals` of Z.object{p} as an `sptensor` (or with the
+    entries `.tocoo()` returns), or None for stored weights 1; `unstored_weight[p]` is alpha for block p, or None.
+    `unstored_weight` may be one number: the alpha of every block named in `entry_weights` and of every block in
+    `observed` (the blocks `sparse_observed_only` marks).  A block named in either list is weighted (and marked
+    observed-only); its alpha defaults to 0.  ValueError: a list of another length than Z.object, a length mismatch
+    with the stored entries, a weight or alpha that is not finite or lies outside [0, 1].  `UnsupportedOnDevice`: a dense
+    block, a PAR2 block, and any weighted block together with `sparse_sharding`."""
+    P = len(Z['object'])
+    if entry_weights is None and unstored_weight is None:
+        return {}
+    scalar = unstored_weight is not None and not isinstance(unstored_weight, (list, tuple, np.ndarray))
+    if entry_weights is not None and (not isinstance(entry_weights, (list, tuple)) or len(entry_weights) != P):
+        raise ValueError('sparse_entry_weights must be a list over the %d blocks of Z.object' % P)
+    if unstored_weight is not None and not scalar and len(unstored_weight) != P:
+        raise ValueError('sparse_unstored_weight must be one number or a list over the %d blocks of Z.object' % P)
+    named = [p for p in range(P) if (entry_weights is not None and entry_weights[p] is not None) or
+             (unstored_weight is not None and not scalar and unstored_weight[p] is not None)]
+    if scalar:
+        named = sorted(set(named) | set(observed))
+    out = {}
+    for p in named:
+        obj = Z['object'][p]
+        if Z['model'][p] != 'CP':
+            raise _unsupported('sparse_entry_weights: Z.object{%d} is a PARAFAC2 block (weights on sparse slabs are not '
+                               'supported)' % (p + 1))
+        coo = None if isinstance(obj, dict) else coo_of(obj)
+        if coo is None:
+            raise _unsupported('sparse_entry_weights: Z.object{%d} is dense (weights are for sparse CP blocks)' % (p + 1))
+        alpha = unstored_weight if scalar else (None if unstored_weight is None else unstored_weight[p])
+        alpha = 0.0 if alpha is None else float(alpha)
+        if not (np.isfinite(alpha) and 0.0 <= alpha <= 1.0):
+            raise ValueError('sparse_unstored_weight: %r for Z.object{%d} is outside [0, 1] (divide the weights by their '
+                             'maximum)' % (alpha, p + 1))
+        w = None
+        if entry_weights is not None and entry_weights[p] is not None:
+            w = np.ascontiguousarray(np.asarray(entry_weights[p], dtype=np.float64).reshape(-1))
+            if w.shape[0] != len(coo[1]):
+                raise ValueError('sparse_entry_weights{%d}: %d weights for %d stored entries' % (p + 1, w.shape[0], len(coo[1])))
+            if not (np.all(np.isfinite(w)) and np.all(w >= 0.0) and np.all(w <= 1.0)):
+                raise ValueError('sparse_entry_weights{%d}: a weight is outside [0, 1] (divide the weights by their '
+                                 'maximum)' % (p + 1))
+        out[p] = (w, alpha)
+    if out and sparse_sharding:
+        raise _unsupported('sparse_entry_weights is not available together with sparse_sharding: a weighted block is '
+                           'replicated')
+    return out
+
+
 def heldout_lists(Z, heldout, patience=0):
     """`alg_options['hip']['heldout']` -> {0-based block: (subs n x N int64 0-based, vals n float64)}, checked on the
     host before the engine is touched.  `heldout` maps 1-based block numbers to `(subs, vals)` or to an `sptensor` of the
@@ -443,7 +494,7 @@ def heldout_keep_best_option(value, lists):
     return int(value)
 
 
-def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0):
+def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0, entry_weights=None, unstored_weight=None):
     """Describe the struct Z to the engine and upload Z.object (cmtf_AOADMM.m:23-41,124-156).
 
     Z.object{p} of a CP block may be dense, an `sptensor`, or (2-way blocks) any object with `.tocoo()` such as a
@@ -463,9 +514,14 @@ def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0)
     observed_only (`observed_only_blocks`: 0, 1 or a list of 1-based block numbers): the named sparse CP blocks are
     marked observed-only after their upload (`Engine.set_observed_only`): their stored entries are the observations,
     every other entry is missing and fitted by EM as Z.miss does for dense data.  Z.miss on a sparse block keeps
-    raising the reference's error."""
+    raising the reference's error.
+    entry_weights, unstored_weight (`entry_weight_blocks`): weighted least squares on the named sparse CP blocks
+    (`Engine.set_entry_weights`): a weight in [0, 1] for every stored entry and one for all unstored entries.  A named
+    block is marked observed-only as well."""
     prec = capi.precision_id(precision)                # an unknown string fails before the engine is touched
     observed = observed_only_blocks(Z, observed_only, sparse_sharding)
+    weighted = entry_weight_blocks(Z, entry_weights, unstored_weight, observed, sparse_sharding)
+    observed = sorted(set(observed) | set(weighted))
     lib = eng.lib
     nb_modes = len(Z['size'])
     which_p = _which_p(Z)
@@ -553,6 +609,9 @@ def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0)
                     if len(vals) == 0:
                         raise ValueError('sparse_observed_only: Z.object{%d} has no stored entry' % (p + 1))
                     eng.set_observed_only(p, True)
+                if p in weighted:
+                    w, alpha = weighted[p]
+                    eng.set_entry_weights(p, None if w is None else subs, w, alpha)
                 continue
             if isinstance(obj, dict) and obj.get('synthetic'):
                 capi.check(lib.aoadmm_tensor_synth(eng.h, p, int(obj['rank']), int(obj['seed']), float(obj['noise']), prec))
@@ -791,12 +850,17 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
     sharding = bool(int(hip.get('sparse_sharding', 0)))
     observed_opt = hip.get('sparse_observed_only', 0)
     observed = observed_only_blocks(Z, observed_opt, sharding)
+    # alg_options['hip']['sparse_entry_weights'] / ['sparse_unstored_weight'] (`entry_weight_blocks`): a weight in [0, 1]
+    # per stored entry and one for the unstored entries of the named sparse CP blocks, which are observed-only as well
+    weights_opt, alpha_opt = hip.get('sparse_entry_weights'), hip.get('sparse_unstored_weight')
+    observed = sorted(set(observed) | set(entry_weight_blocks(Z, weights_opt, alpha_opt, observed, sharding)))
     # alg_options['hip']['heldout'] = {1-based block: (subs, vals) | sptensor} and ['heldout_patience'] (`heldout_lists`):
     # entries kept out of the fit, scored on the device with every evaluation of the objective
     held = heldout_lists(Z, hip.get('heldout'), hip.get('heldout_patience', 0))
     # alg_options['hip']['heldout_keep_best'] (default 0): 1 returns the iterate with the smallest held-out sum
     keep_best = heldout_keep_best_option(hip.get('heldout_keep_best', 0), held)
-    build_model(eng, Z, precision, sparse_sharding=sharding, observed_only=observed_opt)
+    build_model(eng, Z, precision, sparse_sharding=sharding, observed_only=observed_opt, entry_weights=weights_opt,
+                unstored_weight=alpha_opt)
     for p, (hs, hv) in sorted(held.items()):
         eng.set_heldout(p, hs, hv)
     if keep_best:

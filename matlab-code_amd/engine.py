@@ -156,6 +156,25 @@ class Engine:
         block uploaded with `upload_coo` (not sharded) that holds at least one entry; any later upload clears it."""
         capi.check(self.lib.aoadmm_tensor_set_observed_only(self.h, int(p), int(bool(on))))
 
+    def set_entry_weights(self, p, subs, wts, unstored_weight=0.0):
+        """Weights for the sparse CP block p (`aoadmm_tensor_set_entry_weights`): wts[e] in [0, 1] for the stored entry
+        subs[e] (subs nnz x N, 0-based, any order, exactly the block's stored entries once each) and `unstored_weight`
+        in [0, 1] for every other entry.  subs = wts = None sets `unstored_weight` alone, with stored weights 1.  Marks
+        the block observed-only if it is not; weights above 1 are the caller's to normalise (divide by the maximum)."""
+        if wts is None:
+            if subs is not None:
+                raise ValueError('set_entry_weights: subs without wts')
+            capi.check(self.lib.aoadmm_tensor_set_entry_weights(self.h, int(p), 0, None, None, float(unstored_weight)))
+            return
+        subs = np.asarray(subs, dtype=np.int64)
+        wts = np.ascontiguousarray(np.asarray(wts, dtype=np.float64).reshape(-1))
+        if subs.ndim != 2 or subs.shape[0] != wts.shape[0]:
+            raise ValueError('set_entry_weights: subs must be nnz x N with nnz = len(wts)')
+        subs = np.asfortranarray(subs)
+        capi.check(self.lib.aoadmm_tensor_set_entry_weights(self.h, int(p), int(wts.shape[0]),
+                                                            subs.ctypes.data_as(C.POINTER(C.c_int64)), capi.dptr(wts),
+                                                            float(unstored_weight)))
+
     def em_step(self, p):
         """One EM step of the observed-only block p with the current factors (`aoadmm_resident_em_step`):
         (sum over the stored entries of (x - m)^2, num, den) of `f_rel_missing`; `resident_mttkrp` then returns the

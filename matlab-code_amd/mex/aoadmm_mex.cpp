@@ -144,7 +144,11 @@ void read_sparse(int p, const mxArray* obj, int N, std::vector<int64_t>& subs, s
   }
 }
 
-void upload_sparse(int p, const mxArray* obj, const mxArray* sz, const std::vector<int>& md, bool sharded) {
+// wts (weighted): options.hip.sparse_entry_weights{p}, aligned with the entries of the object as read_sparse returns them
+// (an sptensor's subs / vals, a sparse matrix's stored entries column by column), or null / empty for stored weights 1;
+// alpha: the block's unstored weight (aoadmm_tensor_set_entry_weights, which marks the block observed-only)
+void upload_sparse(int p, const mxArray* obj, const mxArray* sz, const std::vector<int>& md, bool sharded,
+                   bool weighted = false, const mxArray* wts = nullptr, double alpha = 0.0) {
   const int N = (int)md.size();
   std::vector<int64_t> subs;
   std::vector<double> vals;
@@ -156,6 +160,15 @@ void upload_sparse(int p, const mxArray* obj, const mxArray* sz, const std::vect
   // options.hip.sparse_sharding: the engines of a multi-device context (options.hip.devices) keep one share each
   check((sharded ? aoadmm_tensor_upload_coo_sharded : aoadmm_tensor_upload_coo)(g_ctx, p, (int64_t)vals.size(), subs.data(),
                                                                                 vals.data()));
+  if (!weighted) return;
+  if (wts && !mxIsEmpty(wts)) {
+    if (!mxIsDouble(wts) || mxIsComplex(wts) || mxGetNumberOfElements(wts) != vals.size())
+      mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.sparse_entry_weights{%d} must hold one real double per stored entry of Z.object{%d} (%d)",
+                        p + 1, p + 1, (int)vals.size());
+    check(aoadmm_tensor_set_entry_weights(g_ctx, p, (int64_t)vals.size(), subs.data(), mxGetDoubles(wts), alpha));
+  } else {
+    check(aoadmm_tensor_set_entry_weights(g_ctx, p, 0, nullptr, nullptr, alpha));
+  }
 }
 
 void put_state(int field_id, int index, int slab, const mxArray* a) {
@@ -289,6 +302,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   // unstored entries of those blocks are missing, not zero (aoadmm_tensor_set_observed_only)
   bool observed_all = false;
   std::vector<int> observed_list;
+  const mxArray *entry_weights = nullptr, *unstored_weight = nullptr;
   if (const mxArray* hip = field(opt, "hip", false)) {
     if (const mxArray* f = field(hip, "sparse_sharding", false)) sparse_sharding = mxGetScalar(f) != 0;
     if (const mxArray* f = field(hip, "sparse_observed_only", false)) {
@@ -302,6 +316,17 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         for (mwSize i = 0; i < ne; ++i) observed_list.push_back((int)mxGetDoubles(f)[i] - 1);
       }
     }
+    // options.hip.sparse_entry_weights: a cell over the blocks, {p} = one weight in [0, 1] per stored entry of the sparse
+    // CP block p or []; options.hip.sparse_unstored_weight: one number for all named blocks (those with weights and
+    // those sparse_observed_only names), or a cell over the blocks of numbers or [].  A named block is observed-only.
+    entry_weights = field(hip, "sparse_entry_weights", false);
+    unstored_weight = field(hip, "sparse_unstored_weight", false);
+    if (entry_weights && !mxIsCell(entry_weights))
+      mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.sparse_entry_weights must be a cell over the blocks of Z.object");
+    if (unstored_weight && !mxIsCell(unstored_weight) && !(mxIsDouble(unstored_weight) && mxGetNumberOfElements(unstored_weight) == 1))
+      mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.sparse_unstored_weight must be one number or a cell over the blocks of Z.object");
+    if ((entry_weights || unstored_weight) && sparse_sharding)
+      mexErrMsgIdAndTxt("cmtf:hip:unsupported", "options.hip.sparse_entry_weights is not available together with options.hip.sparse_sharding");
     if ((observed_all || !observed_list.empty()) && sparse_sharding)
       mexErrMsgIdAndTxt("cmtf:hip:unsupported", "options.hip.sparse_observed_only is not available together with options.hip.sparse_sharding");
     if (const mxArray* d = field(hip, "device", false)) devices.assign(1, (int)mxGetScalar(d));
@@ -462,8 +487,17 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       const mxArray* mp = mxGetCell(modes, p);
       std::vector<int> md(mxGetNumberOfElements(mp));
       for (size_t i = 0; i < md.size(); ++i) md[i] = (int)mxGetDoubles(mp)[i] - 1;
-      upload_sparse(p, obj, sz, md, sparse_sharding);    // values stay fp64 whatever options.hip.precision says
-      if (observed_all || std::find(observed_list.begin(), observed_list.end(), p) != observed_list.end()) {
+      const bool marked = observed_all || std::find(observed_list.begin(), observed_list.end(), p) != observed_list.end();
+      const mxArray* wp = entry_weights && (mwSize)p < mxGetNumberOfElements(entry_weights) ? mxGetCell(entry_weights, p) : nullptr;
+      const mxArray* ap = unstored_weight && mxIsCell(unstored_weight)
+                              ? ((mwSize)p < mxGetNumberOfElements(unstored_weight) ? mxGetCell(unstored_weight, p) : nullptr)
+                              : nullptr;
+      const bool has_w = wp && !mxIsEmpty(wp), has_a = ap && !mxIsEmpty(ap);
+      const bool scalar_a = unstored_weight && !mxIsCell(unstored_weight);
+      const bool weighted = has_w || has_a || (scalar_a && marked);
+      const double alpha = has_a ? mxGetScalar(ap) : (scalar_a && weighted ? mxGetScalar(unstored_weight) : 0.0);
+      upload_sparse(p, obj, sz, md, sparse_sharding, weighted, wp, alpha);    // values stay fp64 whatever options.hip.precision says
+      if (marked || weighted) {
         check(aoadmm_tensor_set_observed_only(g_ctx, p, 1));
         has_missing = true;                               // out.func_rel_missing and the display column as for Z.miss
       }

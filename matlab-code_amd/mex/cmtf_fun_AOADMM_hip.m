@@ -12,6 +12,10 @@ function [G,out] = cmtf_fun_AOADMM_hip(Z,Znorm_const,G,fh,gh,lscalar,uscalar,opt
 % no_permuted_copy).  sparse_observed_only = 1 (every sparse CP block) or a list of block numbers: the entries an
 % sptensor does not store are MISSING, not zero, and are fitted by the EM step as Z.miss does for full data (Z.miss itself
 % stays refused for an sptensor, cmtf_AOADMM.m:77-79); not together with sparse_sharding.
+% sparse_entry_weights = cell over the blocks, {p} one weight in [0,1] per stored entry of the sptensor Z.object{p}
+% (aligned with its subs / vals) or []; sparse_unstored_weight = one number for all named blocks or a cell over the
+% blocks: weighted least squares, the unstored entries are zeros of that small confidence.  A named block is
+% observed-only as well; weights above 1 are divided by their maximum by the caller; not together with sparse_sharding.
 % 'f16': dense 3-way CP blocks without Z.miss are stored as fp16 with one power-of-two scale per block (half the bytes
 % of every tensor pass, 6 instead of 16 resident bytes per entry; the model is fitted to the quantised data), every other
 % dense block as fp32; not with several devices, not with no_permuted_copy = 1.

@@ -5,6 +5,7 @@ data on the same GPU.
     python3 tools/time_sparse.py --nvecs [--nvecs-iters 20] [--host-gram] ...
     python3 tools/time_sparse.py --as-rank 0 --of 8 [--skew] ...
     python3 tools/time_sparse.py --observed-only [--out profiles/sparse_observed_time.jsonl] ...
+    python3 tools/time_sparse.py --observed-only --weights [ALPHA] [--reps 7] [--out profiles/sparse_weighted_time.jsonl] ...
     python3 tools/time_sparse.py --heldout [FRAC] [--skew] [--reps 7] [--out profiles/sparse_heldout_time.jsonl] ...
     python3 tools/time_sparse.py --heldout [FRAC] --keep-best [--out profiles/heldout_keep_best_time.jsonl] ...
 
@@ -37,6 +38,14 @@ aoadmm_kernel_stats(3) and (4 + n); the pass over the first copy carries the sta
 and their ratio next to N / (N - 1).  Then the statistics-only pass (first step after a new mark: no snapshot, residuals
 written), the whole EM step, and the wall time of one outer iteration of both engines (difference of solves of 3 and of
 1 iterations, unconstrained modes).  Every line also goes to --out.
+--observed-only --weights ALPHA (default 0.1) times the passes of a weighted block (aoadmm_tensor_set_entry_weights:
+uniform weights on the coalesced entries, ALPHA on the unstored ones) against those of the observed-only block of the
+same data in the same process, one engine each, after one outer iteration of both; the EM steps of the two engines
+alternate.  Per mode: the median (min, max) over --reps (at least 7) of both passes (HIP events, aoadmm_kernel_stats
+(4 + n); the pass over the first copy is the statistics pass with the snapshot's gathers), the ratio of the medians and
+the ratio of the algorithmic bytes, which is what 8 more streamed bytes per entry predict.  Then the statistics pass of
+a first step (no snapshot) of both.  The duplicates of the drawn list are dropped on the host first: the weight list
+must name the stored entries once each.
 --heldout FRAC (default 0.1) holds FRAC of the drawn list out (its first rows: the draw is i.i.d.) and times the
 held-out pass (csrc/heldout.hip, aoadmm_resident_heldout_stats, HIP events of aoadmm_kernel_stats(12)) in one process
 with the residual passes of an observed-only block of the training entries (classes 4 + n) and with one outer iteration
@@ -86,14 +95,22 @@ def main():
     ap.add_argument('--as-rank', type=int, default=None)
     ap.add_argument('--of', default=None)
     ap.add_argument('--observed-only', action='store_true')
+    ap.add_argument('--weights', type=float, nargs='?', const=0.1, default=None, metavar='ALPHA')
     ap.add_argument('--heldout', type=float, nargs='?', const=0.1, default=None, metavar='FRAC')
     ap.add_argument('--keep-best', action='store_true')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.keep_best and a.heldout is None:
         ap.error('--keep-best goes with --heldout')
+    if a.weights is not None:
+        if not a.observed_only:
+            ap.error('--weights goes with --observed-only')
+        if not 0.0 <= a.weights <= 1.0:
+            ap.error('--weights ALPHA must lie inside [0, 1]')
+        a.reps = max(a.reps, 7)
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'heldout_keep_best_time.jsonl' if a.keep_best else
+        a.out = os.path.join(ROOT, 'profiles', 'sparse_weighted_time.jsonl' if a.weights is not None else
+                             'heldout_keep_best_time.jsonl' if a.keep_best else
                              'sparse_heldout_time.jsonl' if a.heldout is not None else 'sparse_observed_time.jsonl')
     if a.heldout is not None:
         if not 0.0 < a.heldout < 1.0:
@@ -122,7 +139,8 @@ def main():
     t_gen = time.time() - t0
     eng = pkg.Engine(0)
     try:
-        (run_nvecs if a.nvecs else run_share if a.of is not None else run_observed if a.observed_only else
+        (run_nvecs if a.nvecs else run_share if a.of is not None else run_weighted if a.weights is not None else
+         run_observed if a.observed_only else
          run_heldout if a.heldout is not None else run)(a, eng, dims, N, R, nnz, subs, vals, t_gen)
     finally:
         eng.close()
@@ -375,6 +393,114 @@ def run_observed(a, eng, dims, N, R, nnz, subs, vals, t_gen):
               'ratio': round(float(np.median(it['observed'])) / float(np.median(it['plain'])), 3)})
     finally:
         obs.close()
+        out.close()
+
+
+def run_weighted(a, eng, dims, N, R, nnz, subs, vals, t_gen):
+    lib = eng.lib
+    out = open(a.out, 'a')
+
+    def emit(r):
+        line = json.dumps(r)
+        print(line, flush=True)
+        out.write(line + '\n')
+        out.flush()
+
+    def mmm(v):
+        return [round(float(np.median(v)), 4), round(min(v), 4), round(max(v), 4)]
+
+    # the stored entries once each (column-major linear index; the sizes' product must fit in 63 bits)
+    t0 = time.time()
+    assert float(np.prod([float(s) for s in dims])) < 2.0 ** 63, 'linear index of --dims does not fit in int64'
+    lin = np.zeros(nnz, dtype=np.int64)
+    stride = 1
+    for m, s in enumerate(dims):
+        lin += subs[:, m] * stride
+        stride *= s
+    _, first = np.unique(lin, return_index=True)
+    del lin
+    if len(first) < nnz:
+        first.sort()
+        subs, vals = np.asfortranarray(subs[first]), vals[first]
+    nnz_c = len(vals)
+    wts = np.random.default_rng(a.seed + 2).random(nnz_c)
+    t_unique = time.time() - t0
+
+    def set_factors(e):
+        rng = np.random.default_rng(a.seed + 1)
+        for m in range(N):
+            Um = np.asfortranarray(rng.random((dims[m], R)))
+            capi.check(lib.aoadmm_state_set(e.h, capi.F_FAC, m, 0, capi.dptr(Um), dims[m], R))
+
+    def mark(e, weighted):
+        if weighted:
+            e.set_entry_weights(0, subs, wts, a.weights)
+        else:
+            e.set_observed_only(0)
+
+    def prepare(e, weighted):
+        h = e.h
+        capi.check(lib.aoadmm_model_begin(h, N, 1, 0))
+        for m, s in enumerate(dims):
+            capi.check(lib.aoadmm_model_set_mode(h, m, s, R))
+        capi.check(lib.aoadmm_model_add_cp(h, 0, N, (C.c_int * N)(*range(N)), 1.0))
+        for m in range(N):
+            capi.check(lib.aoadmm_model_set_coupling(h, m, -1, None, 0, 0, None, 0, 0))
+        capi.check(lib.aoadmm_model_end(h))
+        e.upload_coo(0, subs, vals)
+        e.synchronize()
+        t0 = time.time()
+        mark(e, weighted)
+        e.synchronize()
+        t_mark = time.time() - t0
+        set_factors(e)
+        o = capi.Options()
+        o.MaxOuterIters, o.MaxInnerIters, o.use_dimtree = 1, 1, 1
+        res = capi.Result()
+        capi.check(lib.aoadmm_solve(e.h, C.byref(o), C.byref(res)))   # row-major factor copies and a snapshot
+        return t_mark
+
+    def step_once(e):
+        """([ms of the pass over every copy], [their algorithmic bytes]) of one EM step"""
+        for c in [3] + [4 + n for n in range(N)]:
+            e.kernel_stats(c, reset=True)
+        e.em_step(0)
+        per = [e.kernel_stats(4 + n, reset=True) for n in range(N)]
+        return [p[0] for p in per], [p[2] for p in per]
+
+    wtd = pkg.Engine(0)
+    try:
+        t_mark_obs = prepare(eng, False)
+        t_mark_wtd = prepare(wtd, True)
+        emit({'what': 'setup', 'dims': dims, 'nnz_given': nnz, 'nnz_coalesced': int(nnz_c), 'R': R, 'skew': a.skew,
+              'reps': a.reps, 'alpha': a.weights, 'gen_s': round(t_gen, 2), 'unique_s': round(t_unique, 2),
+              'mark_s': round(t_mark_obs, 2), 'set_entry_weights_s': round(t_mark_wtd, 2),
+              'resident_bytes_observed': int(eng.tensor_storage_info(0)[2]),
+              'resident_bytes_weighted': int(wtd.tensor_storage_info(0)[2])})
+        step_once(eng), step_once(wtd)                # warm-up
+        so, sw = [], []
+        for _ in range(a.reps):                       # alternating, same process, same data
+            so.append(step_once(eng))
+            sw.append(step_once(wtd))
+        for n in range(N):
+            po, pw = [s[0][n] for s in so], [s[0][n] for s in sw]
+            emit({'what': 'weighted_mode', 'mode': n + 1, 'rows': dims[n], 'statistics_pass': n == 0,
+                  'observed_pass_ms': mmm(po), 'weighted_pass_ms': mmm(pw),
+                  'observed_pass_GB': round(so[0][1][n] / 1e9, 3), 'weighted_pass_GB': round(sw[0][1][n] / 1e9, 3),
+                  'weighted_pass_TBps': round(sw[0][1][n] / float(np.median(pw)) / 1e9, 3),
+                  'time_ratio': round(float(np.median(pw)) / float(np.median(po)), 4),
+                  'bytes_ratio': round(sw[0][1][n] / so[0][1][n], 4)})
+        fo, fw = [], []
+        for _ in range(a.reps):                       # a first step: statistics without a snapshot
+            mark(eng, False)
+            fo.append(step_once(eng)[0][0])
+            wtd.set_observed_only(0)                  # marked again: the weights stay, the snapshot goes
+            fw.append(step_once(wtd)[0][0])
+        emit({'what': 'weighted_first_pass', 'observed_statistics_pass_no_snapshot_ms': mmm(fo),
+              'weighted_statistics_pass_no_snapshot_ms': mmm(fw),
+              'time_ratio': round(float(np.median(fw)) / float(np.median(fo)), 4)})
+    finally:
+        wtd.close()
         out.close()
 
 
