@@ -515,6 +515,32 @@ typedef struct {
 int aoadmm_resident_fold_in(aoadmm_ctx* ctx, int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals,
                             const aoadmm_foldin_options* opt_or_null, double* rows, int* info, int* iters_or_null,
                             double* gram_or_null, double* rhs_or_null);
+/* aoadmm_resident_fold_in for a model fitted under entry weights and a weight for the unstored entries
+ * (aoadmm_tensor_set_entry_weights): wts[e] in [0, 1] is the weight of observation e in the
+ * caller's order (NULL: all ones) and unstored_weight = alpha in [0, 1] the weight of every cell of the new row that the
+ * list does not name, where the data is 0.  Row q minimises sum_listed w_e (x_e - z_e'u)^2 + alpha sum_unlisted (z'u)^2 +
+ * ridge |u|^2 with every other factor fixed, the fixed point of the weighted EM row by row.  With z_e as above and
+ * H = had_{m != mode} F_m'F_m over ALL rows of the other modes' factors (computed inside the call, in a fixed order):
+ *   G_q = sum_e (w_e - alpha) z_e z_e' + alpha H,   b_q = sum_e (w_e x_e) z_e
+ * and then constraint 0 / 1, rho = trace(G_q) / R with alpha H included, info, iters, the pivot rule, the NaN row and the
+ * exit are those of aoadmm_resident_fold_in; gram / rhs return G_q with alpha H included, before the ridge, and b_q.  Entry
+ * (i, j) of the stored part with i <= j is the sum of ((w_e - alpha) z_e(i)) z_e(j) and defines (j, i); alpha H is added
+ * once, as fma(alpha, H(i, j), .).  subs, vals, opt, the outputs and the role of mode are unchanged.
+ * What follows from the form and is not special-cased: every listed observation contributes (w_e - alpha) z z', so a cell
+ * listed twice is subtracted twice and with alpha > 0 the caller lists each cell once; a query without observations has
+ * G_q = alpha H, b_q = 0 and gives the zero row with info 0 whenever alpha H + ridge I is positive definite; w_e - alpha
+ * may be negative: G_q is positive semidefinite mathematically and what cancellation does at ridge 0 is reported through
+ * info; a factor entry that is not finite reaches every query through H when alpha > 0, a value that is not finite only
+ * its own query.
+ * AOADMM_ERR_INVALID, before any output is written, for a weight or alpha outside [0, 1] or not finite (the convention of
+ * aoadmm_tensor_set_entry_weights: the caller normalises and scales ridge with it), and for everything
+ * aoadmm_resident_fold_in refuses, with the same codes (a PARAFAC2 block and a multi-device context:
+ * AOADMM_ERR_UNSUPPORTED).  nq = 0 returns at once.  wts = NULL or all ones with alpha = 0 returns the bits of
+ * aoadmm_resident_fold_in; the weighted kernels are instantiations of their own and aoadmm_resident_fold_in launches what
+ * it always launched.  The block's own weight list is not read: the call stays data-less. */
+int aoadmm_resident_fold_in_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals,
+                              const double* wts_or_null, double unstored_weight, const aoadmm_foldin_options* opt_or_null,
+                              double* rows, int* info, int* iters_or_null, double* gram_or_null, double* rhs_or_null);
 
 /* ---- state (the struct G) ---------------------------------------------- */
 /* slab = k for cell-valued fields (PARAFAC2 B mode, P, mu_DeltaB), else 0.  slab = AOADMM_ALL_SLABS moves
@@ -552,7 +578,9 @@ int aoadmm_resident_par2_rhs(aoadmm_ctx* ctx, int p, int tensor_mode, double* ou
  * its weights, scores-and-selection and merge kernels inside one event pair; bytes = F_mode streamed once per query tile
  * + rows gathered + the answer, flops = 2 * I_mode * nq * R); which = 14: aoadmm_resident_fold_in (one launch per call: its
  * kernels inside one event pair; bytes = the list streamed + rows gathered + the outputs, flops = nobs * (R (R + 1) +
- * 2 R (N - 1)) + nq * (R^3 / 3 + 2 R^2) for the solves) */
+ * 2 R (N - 1)) + nq * (R^3 / 3 + 2 R^2) for the solves; aoadmm_resident_fold_in_w counts in the same class: with a weight
+ * list 8 nobs bytes more, and with alpha > 0 the factor rows read for H, 8 R sum_{m != mode} I_m bytes, and its
+ * R^2 sum_{m != mode} I_m flops) */
 int aoadmm_kernel_stats(aoadmm_ctx* ctx, int which, int reset, double* contract_ms, int64_t* contract_launches,
                         double* contract_bytes, double* contract_flops);
 

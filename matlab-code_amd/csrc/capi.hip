@@ -544,6 +544,16 @@ int aoadmm_resident_fold_in(aoadmm_ctx* ctx, int p, int mode, int64_t nq, int64_
     ctx->eng->fold_in(p, mode, nq, nobs, subs, vals, opt_or_null, rows, info, iters_or_null, gram_or_null, rhs_or_null);
   });
 }
+int aoadmm_resident_fold_in_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals,
+                              const double* wts_or_null, double unstored_weight, const aoadmm_foldin_options* opt_or_null,
+                              double* rows, int* info, int* iters_or_null, double* gram_or_null, double* rhs_or_null) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_resident_fold_in_w");
+    ctx->eng->fold_in_w(p, mode, nq, nobs, subs, vals, wts_or_null, unstored_weight, opt_or_null, rows, info, iters_or_null, gram_or_null,
+                        rhs_or_null);
+  });
+}
 int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes) {
   CTX_OR_FAIL(ctx);
   // no collective and no device work: rank 0's engine answers for a multi-device context (every rank holds the same

@@ -9,6 +9,12 @@
 // reach HBM only when they are asked for); a longer one leaves one partial per chunk and a second launch sums them in
 // chunk order and solves.  No float atomics, no dependence between workgroups: a query's outputs are a function of the
 // factors, its own observations in the caller's order and the options.
+//
+// Weighted (aoadmm_resident_fold_in_w): with a weight w_e in [0, 1] per observation and alpha in [0, 1] for every cell of
+// the new row the list does not name (data 0 there), and H = had_{m != mode} F_m'F_m over all rows of the other factors,
+//   G_q = sum_e (w_e - alpha) z_e z_e' + alpha H,   b_q = sum_e (w_e x_e) z_e
+// and everything after that is the same solve.  The weighted instantiations of the kernel run for such a call; H is
+// computed inside it, once, by fixed-order kernels (skipped at alpha = 0).
 #pragma once
 #include "common.h"
 #include "heldout.h"
@@ -58,11 +64,23 @@ struct FoldinArgs {
   int* iters = nullptr;              // device [nq]
   double* gram = nullptr;            // device [nq][R x R] or null
   double* rhs = nullptr;             // device [nq x R] column-major or null
+  // the weighted form: the weighted instantiations run, whatever wts and alpha are
+  bool weighted = false;
+  const double* wts = nullptr;       // device [nobs], sorted list; null: all ones
+  double alpha = 0.0;                // the weight of an unlisted cell
+  int64_t frows[kCooMaxModes] = {};  // rows of every factor of hf (alpha != 0)
+  double* H = nullptr;               // device [R x R]: written by the call when alpha != 0
+  double* gram_ws = nullptr;         // device, foldin_gram_ws_doubles (alpha != 0)
 };
 void foldin_enqueue(const FoldinArgs& a, hipStream_t s);
+// H = had_{m != mode} F_m'F_m from the factors as the pass gathers them, in a fixed order that no stride enters
+size_t foldin_gram_ws_doubles(const HeldoutFactors& hf, const int64_t* rows, int mode);
+void foldin_gram_enqueue(const HeldoutFactors& hf, const int64_t* rows, int mode, double* ws, double* H, hipStream_t s);
 
-// algorithmic bytes (the list streamed, the rows gathered, the outputs) and flops (the normal equations, the solves)
-double foldin_bytes(int nd, int R, int64_t nq, int64_t nobs, bool normal);
-double foldin_flops(int nd, int R, int64_t nq, int64_t nobs);
+// algorithmic bytes (the list streamed, the rows gathered, the outputs) and flops (the normal equations, the solves); a
+// weight list adds 8 bytes per observation, alpha != 0 the 8 R other_rows bytes and R R other_rows flops of H, with
+// other_rows the rows of the other modes' factors together
+double foldin_bytes(int nd, int R, int64_t nq, int64_t nobs, bool normal, bool wts = false, double alpha = 0.0, int64_t other_rows = 0);
+double foldin_flops(int nd, int R, int64_t nq, int64_t nobs, double alpha = 0.0, int64_t other_rows = 0);
 
 }  // namespace aoadmm

@@ -243,6 +243,13 @@ class Engine {
   int tensor_rank(int p) const;                    // the number of components of block p (aoadmm_tensor_rank)
   void fold_in(int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals, const aoadmm_foldin_options* opt,
                double* rows_host, int* info_host, int* iters_host, double* gram_host, double* rhs_host);
+  // the same under entry weights (null: ones) and a weight for the unlisted cells: the weighted instantiations run
+  void fold_in_w(int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals, const double* wts,
+                 double unstored_weight, const aoadmm_foldin_options* opt, double* rows_host, int* info_host, int* iters_host,
+                 double* gram_host, double* rhs_host);
+  void fold_in_run(const char* what, bool weighted, int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals,
+                   const double* wts, double alpha, const aoadmm_foldin_options* opt, double* rows_host, int* info_host,
+                   int* iters_host, double* gram_host, double* rhs_host);
   void resident_unfold_gram(int p, int pos, int slab, double* out_host);
   void resident_nvecs(int p, int pos, int r, const aoadmm_nvecs_options* opt, double* U_host, int64_t ldU, double* eig_host,
                       aoadmm_nvecs_info* info);

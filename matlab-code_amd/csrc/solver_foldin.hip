@@ -16,12 +16,28 @@ int Engine::tensor_rank(int p) const {
 void Engine::fold_in(int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals,
                      const aoadmm_foldin_options* opt, double* rows_host, int* info_host, int* iters_host, double* gram_host,
                      double* rhs_host) {
+  fold_in_run("aoadmm_resident_fold_in", false, p, mode, nq, nobs, subs, vals, nullptr, 0.0, opt, rows_host, info_host, iters_host,
+              gram_host, rhs_host);
+}
+
+void Engine::fold_in_w(int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals, const double* wts,
+                       double unstored_weight, const aoadmm_foldin_options* opt, double* rows_host, int* info_host, int* iters_host,
+                       double* gram_host, double* rhs_host) {
+  fold_in_run("aoadmm_resident_fold_in_w", true, p, mode, nq, nobs, subs, vals, wts, unstored_weight, opt, rows_host, info_host,
+              iters_host, gram_host, rhs_host);
+}
+
+// One implementation for both entries.  weighted: the weighted instantiations of the kernel run (wts null: ones); the
+// unweighted entry passes wts = null and alpha = 0 and launches what it always launched.
+void Engine::fold_in_run(const char* what, bool weighted, int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs,
+                         const double* vals, const double* wts, double alpha, const aoadmm_foldin_options* opt, double* rows_host,
+                         int* info_host, int* iters_host, double* gram_host, double* rhs_host) {
   require_usable();
   AO_REQUIRE(model_done_, "call aoadmm_model_end first");
   AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
   TensorInfo& t = tensors_[p];
   if (t.par2)
-    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("aoadmm_resident_fold_in: tensor %d is a PARAFAC2 block; rows are folded into CP blocks", p));
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("%s: tensor %d is a PARAFAC2 block; rows are folded into CP blocks", what, p));
   const int nd = t.nmodes;
   AO_REQUIRE(nd >= 2 && nd <= kCooMaxModes, "tensor %d: order %d", p, nd);
   AO_REQUIRE(mode >= 0 && mode < nd, "tensor %d: mode %d outside [0, %d)", p, mode, nd);
@@ -36,6 +52,8 @@ void Engine::fold_in(int p, int mode, int64_t nq, int64_t nobs, const int64_t* s
     fo.ridge = opt->ridge; fo.constraint = opt->constraint; fo.max_inner = opt->max_inner;
     fo.tol_primal = opt->tol_primal; fo.tol_dual = opt->tol_dual;
   }
+  // the convention of aoadmm_tensor_set_entry_weights: weights in [0, 1], the caller normalises and scales ridge with it
+  AO_REQUIRE(std::isfinite(alpha) && alpha >= 0.0 && alpha <= 1.0, "unstored_weight = %g outside [0, 1]", alpha);
   if (nq == 0) return;
   AO_REQUIRE(rows_host != nullptr && info_host != nullptr, "null rows / info");
   AO_REQUIRE(nobs == 0 || (subs != nullptr && vals != nullptr), "null subs / vals");
@@ -47,6 +65,10 @@ void Engine::fold_in(int p, int mode, int64_t nq, int64_t nobs, const int64_t* s
                (long long)e, (long long)nq);
   std::vector<int> idx32;
   heldout_check_subs(t, p, nobs, subs, idx32, mode);
+  if (wts != nullptr)
+    for (int64_t e = 0; e < nobs; ++e)
+      AO_REQUIRE(std::isfinite(wts[e]) && wts[e] >= 0.0 && wts[e] <= 1.0, "tensor %d: weight %g at observation %lld is outside [0, 1]", p, wts[e],
+                 (long long)e);
 
   // the observations in a stable order by query: 4 (N - 1) + 8 bytes each
   const FoldinPlan pl = foldin_plan(nq, nobs, qcol);
@@ -60,6 +82,11 @@ void Engine::fold_in(int p, int mode, int64_t nq, int64_t nobs, const int64_t* s
     ++j;
   }
   for (int64_t e = 0; e < nobs; ++e) val_sorted[(size_t)e] = vals[pl.order[(size_t)e]];
+  std::vector<double> wt_sorted;                       // beside the values: 8 bytes more per observation
+  if (wts != nullptr) {
+    wt_sorted.resize((size_t)nobs);
+    for (int64_t e = 0; e < nobs; ++e) wt_sorted[(size_t)e] = wts[pl.order[(size_t)e]];
+  }
 
   AO_HIP(hipSetDevice(device_));
   const HeldoutFactors hf = heldout_factors(t, nullptr);
@@ -67,13 +94,14 @@ void Engine::fold_in(int p, int mode, int64_t nq, int64_t nobs, const int64_t* s
   const int64_t items = (int64_t)pl.item_q.size(), splits = (int64_t)pl.split_q.size();
   AO_REQUIRE(items < ((int64_t)1 << 31), "%lld work items: too many for one call", (long long)items);
   const bool normal = gram_host != nullptr || rhs_host != nullptr;
-  DevBuf idx, val, qoff, iq, ic, pbase, sq, part, orow, oinfo, oit, ogram, orhs;
+  DevBuf idx, val, wt, qoff, iq, ic, pbase, sq, part, orow, oinfo, oit, ogram, orhs, had, gws;
   auto up = [&](DevBuf& b, const void* src, size_t bytes) {
     b.alloc(std::max<size_t>(bytes, 8));
     if (bytes > 0) AO_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, stream_));
   };
   up(idx, idx_sorted.data(), idx_sorted.size() * sizeof(int));
   up(val, val_sorted.data(), val_sorted.size() * sizeof(double));
+  if (wts != nullptr) up(wt, wt_sorted.data(), wt_sorted.size() * sizeof(double));
   up(qoff, pl.qoff.data(), pl.qoff.size() * sizeof(int64_t));
   up(iq, pl.item_q.data(), pl.item_q.size() * sizeof(int));
   up(ic, pl.item_chunk.data(), pl.item_chunk.size() * sizeof(int));
@@ -95,10 +123,22 @@ void Engine::fold_in(int p, int mode, int64_t nq, int64_t nobs, const int64_t* s
   a.rows = orow.d(); a.info = oinfo.as<int>(); a.iters = oit.as<int>();
   a.gram = gram_host != nullptr ? ogram.d() : nullptr;
   a.rhs = rhs_host != nullptr ? orhs.d() : nullptr;
+  a.weighted = weighted; a.wts = wts != nullptr ? wt.d() : nullptr; a.alpha = alpha;
+  int64_t other_rows = 0;
+  if (alpha != 0.0) {                                  // H from the factors of this call, never from a Gram matrix a solve left
+    for (int m = 0; m < nd; ++m) {
+      a.frows[m] = modes_[t.modes[m]].rows;
+      if (m != mode) other_rows += a.frows[m];
+    }
+    had.alloc((size_t)R * R * sizeof(double));
+    gws.alloc(foldin_gram_ws_doubles(hf, a.frows, mode) * sizeof(double));
+    a.H = had.d(); a.gram_ws = gws.d();
+  }
   KernelStats& ks = timers_.stats[kStatsFoldin];
   const LaunchTimers::Pair pr = timers_.begin(ks, timers_.profile, stream_);
   foldin_enqueue(a, stream_);
-  timers_.end(ks, pr, stream_, foldin_bytes(nd, R, nq, nobs, normal), foldin_flops(nd, R, nq, nobs));
+  timers_.end(ks, pr, stream_, foldin_bytes(nd, R, nq, nobs, normal, wts != nullptr, alpha, other_rows),
+              foldin_flops(nd, R, nq, nobs, alpha, other_rows));
   // The outputs are written last, and only after the device work has succeeded: a refusal or a failure above leaves
   // them untouched.
   std::vector<double> hrow((size_t)nq * R), hgram, hrhs;

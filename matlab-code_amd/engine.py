@@ -353,14 +353,20 @@ class Engine:
             raise ValueError('topk_w: W has %d columns, block %d has R = %d' % (W.shape[1], int(p), R))
         return self._topk_call('topk_w', self.lib.aoadmm_resident_topk_w, p, mode, int(W.shape[0]), capi.dptr(W), k, exclude, keep=W)
 
-    def fold_in(self, p, mode, subs, vals, nq=None, ridge=0.0, nonneg=False, max_inner=5, tol=(0.0, 0.0), return_normal=False):
+    def fold_in(self, p, mode, subs, vals, nq=None, ridge=0.0, nonneg=False, max_inner=5, tol=(0.0, 0.0), return_normal=False,
+                weights=None, unstored_weight=0.0):
         """The factor rows of new indices along mode `mode` (0-based position in the block) of CP block p from their
         entries, every other factor held fixed (`aoadmm_resident_fold_in`).  subs is nobs x N, 0-based, with the query
         number in column `mode` (`sptensor.take_rows` gives such a list); vals has nobs values; nq=None: max(q) + 1.
         Row q solves (G_q + ridge I) u = b_q over the observations of q, or with nonneg=True runs the row ADMM loop for
         non-negativity (at most max_inner iterations, tol = (primal, dual)) and returns its feasible iterate.  Returns
         (rows nq x R, info int32 nq: 1 where the system was not positive definite and the row is NaN, iters int32 nq),
-        and with return_normal=True also (gram nq x R x R, rhs nq x R), the normal equations before the ridge."""
+        and with return_normal=True also (gram nq x R x R, rhs nq x R), the normal equations before the ridge.
+        weights (nobs values in [0, 1]) and unstored_weight = alpha in [0, 1] give the row of a model fitted under
+        `set_entry_weights` (`aoadmm_resident_fold_in_w`): G_q = sum (w_e - alpha) z z' + alpha H with H the Hadamard
+        product of the other factors' Gram matrices, b_q = sum w_e x_e z; every cell the list does not name counts as a
+        zero of weight alpha, so with alpha > 0 each cell is listed once.  With both at their defaults the unweighted
+        entry is called."""
         vals = np.ascontiguousarray(np.asarray(vals, dtype=np.float64).reshape(-1))
         subs = self._subs_f(subs, 'fold_in')
         nobs = int(vals.shape[0])
@@ -381,10 +387,18 @@ class Engine:
         rhs = np.zeros((n, R), order='F') if return_normal else None
         opt = capi.FoldinOptions(float(ridge), 1 if nonneg else 0, int(max_inner), float(tol[0]), float(tol[1]))
         ip = C.POINTER(C.c_int)
-        capi.check(self.lib.aoadmm_resident_fold_in(
-            self.h, int(p), mode, nq, nobs, subs.ctypes.data_as(C.POINTER(C.c_int64)) if nobs else None,
-            capi.dptr(vals) if nobs else None, C.byref(opt), capi.dptr(rows), info.ctypes.data_as(ip), iters.ctypes.data_as(ip),
-            capi.dptr(gram), capi.dptr(rhs)))
+        head = (self.h, int(p), mode, nq, nobs, subs.ctypes.data_as(C.POINTER(C.c_int64)) if nobs else None,
+                capi.dptr(vals) if nobs else None)
+        tail = (C.byref(opt), capi.dptr(rows), info.ctypes.data_as(ip), iters.ctypes.data_as(ip), capi.dptr(gram), capi.dptr(rhs))
+        if weights is None and float(unstored_weight) == 0.0:
+            capi.check(self.lib.aoadmm_resident_fold_in(*head, *tail))
+        else:
+            w = None
+            if weights is not None:
+                w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+                if w.shape[0] != nobs:
+                    raise ValueError('fold_in: weights must hold nobs = %d values, got %d' % (nobs, w.shape[0]))
+            capi.check(self.lib.aoadmm_resident_fold_in_w(*head, capi.dptr(w) if w is not None and nobs else None, float(unstored_weight), *tail))
         if return_normal:
             return rows, info, iters, gram, rhs
         return rows, info, iters
@@ -410,7 +424,7 @@ class Engine:
         MTTKRPs of sparse blocks (of a sharded block: this rank's share), passes over the nonzeros of PARAFAC2
         blocks with sparse slabs and EM steps of observed-only blocks; which = 4 + n: the pass of those EM steps over
         the copy of tensor mode n; which = 12: the held-out passes; which = 13: the top-k completions (one launch per `topk` call);
-        which = 14: the fold-in of new rows (one launch per `fold_in` call)."""
+        which = 14: the fold-in of new rows (one launch per `fold_in` call, weighted or not)."""
         ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         capi.check(self.lib.aoadmm_kernel_stats(self.h, int(which), int(bool(reset)), C.byref(ms), C.byref(n),
                                                 C.byref(by), C.byref(fl)))

@@ -115,10 +115,12 @@ class sptensor:
         take = np.repeat(lo - off[:-1], hi - lo) + np.arange(off[-1], dtype=np.int64)
         return off, np.ascontiguousarray(rows[take].astype(np.int64))
 
-    def take_rows(self, mode, rows):
+    def take_rows(self, mode, rows, return_index=False):
         """(subs, vals) of the stored entries whose subscript along `mode` is in `rows` (distinct indices), in stored
         order, with column `mode` renumbered to the position in `rows`: the list `Engine.fold_in` takes for the queries
-        rows[0], rows[1], ...  A row without stored entries contributes nothing."""
+        rows[0], rows[1], ...  A row without stored entries contributes nothing.  return_index=True: (subs, vals, index)
+        with index the positions of the taken entries in the stored list, so that an array kept beside `vals` (the entry
+        weights of a fit) is cut the same way: `w[index]`."""
         mode = int(mode)
         if not 0 <= mode < self.ndim:
             raise ValueError('sptensor.take_rows: mode %d outside [0, %d)' % (mode, self.ndim))
@@ -133,6 +135,8 @@ class sptensor:
         keep = q >= 0
         subs = self.subs[keep].copy()
         subs[:, mode] = q[keep]
+        if return_index:
+            return np.ascontiguousarray(subs), np.ascontiguousarray(self.vals[keep]), np.flatnonzero(keep).astype(np.int64)
         return np.ascontiguousarray(subs), np.ascontiguousarray(self.vals[keep])
 
     def __repr__(self):

@@ -3,6 +3,7 @@ observed-only block over the same number of entries and to a torch baseline on t
 
     python3 tools/time_foldin.py [--dims 1000000,100000,10000] [--R 20] [--nq 100000] [--nobs 10000000] [--reps 7]
                                  [--ridge 0.1] [--skip residual,torch,paths] [--out profiles/foldin_time.jsonl]
+                                 [--weights] [--alpha 0.05]
 
 A data-less block of --dims at rank R; --nq new rows of mode 0 are folded in from --nobs observations, once with the same
 count for every query ('uniform') and once with counts that follow 1 / rank ('powerlaw': a few queries hold more than
@@ -16,6 +17,10 @@ count for every query ('uniform') and once with counts that follow 1 / rank ('po
                copy (class 4 + n, n >= 1: the residuals x - m alone), which gathers N rows per entry where the fold-in
                gathers N - 1.
 'paths' times 256 and 257 observations per query (the largest fused query and the smallest split one) at the same total.
+--weights and/or --alpha > 0 add, per case, one `foldin_weighted` line: the unweighted call, the call under uniform random
+weights at alpha = 0 and (with --alpha) the call under the same weights at --alpha, on the same list, alternating call by
+call in this process, --reps of each after one warm-up round; `h_ms` is the call with --alpha on one query without
+observations, that is the launches that form H and one wave.
 """
 from __future__ import annotations
 
@@ -81,6 +86,8 @@ def main():
     ap.add_argument('--torch-chunk', type=float, default=1e6)
     ap.add_argument('--skip', default='')
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--weights', action='store_true', help='time calls under entry weights against unweighted ones')
+    ap.add_argument('--alpha', type=float, default=0.0, help='unstored weight of the weighted calls')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'foldin_time.jsonl'))
     a = ap.parse_args()
     skip = set(a.skip.split(',')) if a.skip else set()
@@ -119,6 +126,19 @@ def main():
                 t_dev.append(ms)
                 t_call.append(1e3 * (t1 - t0))
         return med(t_dev), med(t_call), by, rows
+
+    def time_alternating(eng, subs, vals, n, variants):
+        """{name: median (min, max) of the kernels' ms} for calls that differ in their keywords, taken turn by turn."""
+        t = {name: [] for name, _ in variants}
+        for rep in range(a.reps + 1):                          # the first round warms up and is dropped
+            for name, kw in variants:
+                eng.kernel_stats(FOLDIN_CLASS, reset=True)
+                rows, info, _ = eng.fold_in(0, 0, subs, vals, nq=n, ridge=a.ridge, **kw)
+                ms, launches, by, _ = eng.kernel_stats(FOLDIN_CLASS)
+                assert launches == 1 and not info.any()
+                if rep:
+                    t[name].append(ms)
+        return {name: med(v) for name, v in t.items()}
 
     residual_ns = None
     if 'residual' not in skip:
@@ -187,6 +207,21 @@ def main():
                 del subs_t, vals_t, got
                 torch.cuda.empty_cache()
             emit(line)
+            if a.weights or a.alpha > 0:
+                w = rng.random(n)
+                variants = [('unweighted', {}), ('weighted', dict(weights=w))]
+                if a.alpha > 0:
+                    variants.append(('weighted_alpha', dict(weights=w, unstored_weight=a.alpha)))
+                t = time_alternating(eng, subs, vals, nq, variants)
+                wline = dict(what='foldin_weighted', case=name, dims=list(dims), R=R, N=N, nq=nq, nobs=n, ridge=a.ridge, reps=a.reps,
+                             alpha=a.alpha, foldin_ms=t, weighted_over_unweighted=round(t['weighted']['median'] / t['unweighted']['median'], 4),
+                             expected_bytes_ratio=round((4.0 * (N - 1) + 16.0 + 8.0 * R * (N - 1)) / (4.0 * (N - 1) + 8.0 + 8.0 * R * (N - 1)), 4))
+                if a.alpha > 0:
+                    wline['alpha_over_unweighted'] = round(t['weighted_alpha']['median'] / t['unweighted']['median'], 4)
+                    none = np.zeros((0, N), dtype=np.int64, order='F')
+                    wline['h_ms'] = time_alternating(eng, none, np.zeros(0), 1, [('h', dict(unstored_weight=a.alpha))])['h']
+                    wline['h_bytes'] = 8 * R * int(sum(dims[1:]))
+                emit(wline)
         if 'paths' not in skip:
             for per_query in (256, 257):
                 n = max(1, nobs // 4 // per_query)
