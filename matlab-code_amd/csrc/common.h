@@ -85,6 +85,8 @@ struct DevBuf {
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// workgroups of t threads for n work items, at least one
+inline unsigned blocks_for(int64_t n, int t = 256) { return (unsigned)(n > t ? cdiv(n, t) : 1); }
 
 constexpr int kMaxRank = 64;   // R <= 64 (two 32-wide MFMA N tiles); typical R <= 32
 

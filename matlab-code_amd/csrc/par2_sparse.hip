@@ -8,8 +8,6 @@
 
 namespace aoadmm {
 
-static unsigned blocks_for(int64_t n, int t = 256) { return (unsigned)std::max<int64_t>(1, cdiv(n, t)); }
-
 // xn[k] = sum of squares of the coalesced values of slab k.  `col` is the column-sorted copy's key array (global
 // column of every nonzero), so slab k is the contiguous range [lower_bound(off[k]), lower_bound(off[k+1])).  One
 // workgroup per slab, strided partial sums folded by a fixed tree: the same bits every run.

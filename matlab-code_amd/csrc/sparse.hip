@@ -5,7 +5,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "sparse.h"
+#include "coo_team.h"
 
 namespace aoadmm {
 
@@ -73,7 +73,6 @@ __global__ void coo_gather_k(int* oidx, double* oval, const int* perm, const int
   oval[i] = cval[q];
 }
 
-static unsigned blocks_for(int64_t n, int t = 256) { return (unsigned)std::max<int64_t>(1, cdiv(n, t)); }
 static int bits_for(uint64_t count) {       // bits of the largest key count - 1
   int b = 0;
   while (b < 64 && (count - 1) >> b) ++b;
@@ -246,8 +245,8 @@ void coo_keep_share(CooBlock& b, int rank, int world, hipStream_t s) {
 // ---------------------------------------------------------------------------
 // MTTKRP
 // ---------------------------------------------------------------------------
-// A team of G lanes (lane r = column r of the result, G >= R) walks a contiguous list of entries sorted by row and
-// keeps the running sum of the current row in a register.  A row that starts and ends inside the team's range is
+// A team (coo_team.h; lane r = column r of the result) walks its range of a list of entries sorted by row and keeps
+// the running sum of the current row in a register.  A row that starts and ends inside the team's range is
 // complete: one plain store.  A row that continues into the previous or the next range goes to one of the team's two
 // carry slots (2 t: its first row, 2 t + 1: its last row); a row that runs through the whole range fills both, the
 // second with +0.  Unused slots hold row -1, which only ever sits between two different rows, so the slots of one row
@@ -320,18 +319,13 @@ constexpr int kCooUnroll = 8;    // entries whose loads are in flight together
 // NO = number of other modes (1..3 compiled in; 0: a.no at run time, up to 7)
 template <int G, int NO>
 __global__ __launch_bounds__(256) void mttkrp_coo_k(CooArgs a) {
-  const int64_t team = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-  const int r = (int)(threadIdx.x % G);
-  const int64_t start = team * kCooChunk;
-  if (start >= a.nnz) return;
-  const int64_t end = start + kCooChunk < a.nnz ? start + kCooChunk : a.nnz;
+  const CooTeam<G> t(a.nnz, a.R);
+  if (t.idle()) return;
+  const int64_t end = t.end();
+  const int rr = t.rr();
   const int no = NO > 0 ? NO : a.no;
-  const int rr = r < a.R ? r : a.R - 1;            // lanes beyond R read column R - 1 and store nothing
-  SegAcc sa;
-  sa.rows = a.row; sa.n = a.nnz; sa.start = start; sa.end = end; sa.team = team;
-  sa.r = r; sa.R = a.R; sa.scale = a.scale; sa.out = a.out; sa.oI = a.oI; sa.oR = a.oR;
-  sa.slot_row = a.slot_row; sa.slot_val = a.slot_val;
-  for (int64_t i0 = start; i0 < end; i0 += kCooUnroll) {
+  SegAcc sa{a.row, a.nnz, t.start, end, t.team, t.r, a.R, a.scale, a.out, a.oI, a.oR, a.slot_row, a.slot_val};
+  for (int64_t i0 = t.start; i0 < end; i0 += kCooUnroll) {
     int rowu[kCooUnroll];
     double pu[kCooUnroll];
 #pragma unroll
@@ -342,9 +336,9 @@ __global__ __launch_bounds__(256) void mttkrp_coo_k(CooArgs a) {
       if (NO > 0) {
 #pragma unroll
         for (int k = 0; k < (NO > 0 ? NO : 1); ++k)
-          p *= a.f[k].p[(int64_t)a.oidx[k * a.nnz + i] * a.f[k].sI + rr * a.f[k].sR];
+          p *= coo_at(a.f[k], a.oidx[k * a.nnz + i], rr);
       } else {
-        for (int k = 0; k < no; ++k) p *= a.f[k].p[(int64_t)a.oidx[k * a.nnz + i] * a.f[k].sI + rr * a.f[k].sR];
+        for (int k = 0; k < no; ++k) p *= coo_at(a.f[k], a.oidx[k * a.nnz + i], rr);
       }
       pu[u] = p;
     }
@@ -360,17 +354,12 @@ __global__ __launch_bounds__(256) void mttkrp_coo_k(CooArgs a) {
 template <int G>
 __global__ __launch_bounds__(256) void coo_carry_k(const int* rin, const double* vin, int64_t n, int R, double scale,
                                                    double* out, int64_t oI, int64_t oR, int* rout, double* vout) {
-  const int64_t team = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-  const int r = (int)(threadIdx.x % G);
-  const int64_t start = team * kCooChunk;
-  if (start >= n) return;
-  const int64_t end = start + kCooChunk < n ? start + kCooChunk : n;
-  const int rr = r < R ? r : R - 1;
-  SegAcc sa;
-  sa.rows = rin; sa.n = n; sa.start = start; sa.end = end; sa.team = team;
-  sa.r = r; sa.R = R; sa.scale = scale; sa.out = out; sa.oI = oI; sa.oR = oR;
-  sa.slot_row = rout; sa.slot_val = vout;
-  for (int64_t i0 = start; i0 < end; i0 += kCooUnroll) {
+  const CooTeam<G> t(n, R);
+  if (t.idle()) return;
+  const int64_t end = t.end();
+  const int rr = t.rr();
+  SegAcc sa{rin, n, t.start, end, t.team, t.r, R, scale, out, oI, oR, rout, vout};
+  for (int64_t i0 = t.start; i0 < end; i0 += kCooUnroll) {
     int rowu[kCooUnroll];
     double vu[kCooUnroll];
 #pragma unroll
@@ -386,31 +375,11 @@ __global__ __launch_bounds__(256) void coo_carry_k(const int* rin, const double*
   sa.finish();
 }
 
-template <int G>
-static void launch_coo(const CooArgs& a, int64_t nteams, hipStream_t s) {
-  const unsigned grid = blocks_for(nteams * G);
-  switch (a.no) {
-    case 1: mttkrp_coo_k<G, 1><<<grid, 256, 0, s>>>(a); break;
-    case 2: mttkrp_coo_k<G, 2><<<grid, 256, 0, s>>>(a); break;
-    case 3: mttkrp_coo_k<G, 3><<<grid, 256, 0, s>>>(a); break;
-    default: mttkrp_coo_k<G, 0><<<grid, 256, 0, s>>>(a); break;
-  }
-  AO_KERNEL_CHECK();
-}
-
-template <int G>
-static void launch_carry(const int* rin, const double* vin, int64_t n, int R, double scale, double* out, int64_t oI,
-                         int64_t oR, int* rout, double* vout, hipStream_t s) {
-  coo_carry_k<G><<<blocks_for(cdiv(n, kCooChunk) * G), 256, 0, s>>>(rin, vin, n, R, scale, out, oI, oR, rout, vout);
-  AO_KERNEL_CHECK();
-}
-
 // Sums a list sorted by row (rows rin, R-vectors vin, n entries; row -1 = empty) into out, level by level until one team
 // covers the list (a level shrinks the list kCooChunk / 2 = 128 times).  Level outputs alternate between srow/sval[next]
 // and [next ^ 1], never the buffer the level reads.
 static void carry_passes(const int* rin, const double* vin, int64_t n, int R, double scale, double* out, int64_t oI,
                          int64_t oR, DevBuf* srow, DevBuf* sval, int next, hipStream_t s) {
-  const int G = R <= 4 ? 4 : R <= 8 ? 8 : R <= 16 ? 16 : R <= 32 ? 32 : 64;
   for (;;) {
     const int64_t teams = cdiv(n, kCooChunk);
     int* rout = nullptr;
@@ -421,13 +390,11 @@ static void carry_passes(const int* rin, const double* vin, int64_t n, int R, do
       rout = srow[next].as<int>();
       vout = sval[next].d();
     }
-    switch (G) {
-      case 4: launch_carry<4>(rin, vin, n, R, scale, out, oI, oR, rout, vout, s); break;
-      case 8: launch_carry<8>(rin, vin, n, R, scale, out, oI, oR, rout, vout, s); break;
-      case 16: launch_carry<16>(rin, vin, n, R, scale, out, oI, oR, rout, vout, s); break;
-      case 32: launch_carry<32>(rin, vin, n, R, scale, out, oI, oR, rout, vout, s); break;
-      default: launch_carry<64>(rin, vin, n, R, scale, out, oI, oR, rout, vout, s); break;
-    }
+    for_team_width(R, [&](auto g) {
+      constexpr int G = decltype(g)::value;
+      coo_carry_k<G><<<coo_team_grid(n, G), 256, 0, s>>>(rin, vin, n, R, scale, out, oI, oR, rout, vout);
+    });
+    AO_KERNEL_CHECK();
     if (teams <= 1) break;
     rin = rout; vin = vout; n = 2 * teams;
     next ^= 1;
@@ -445,14 +412,13 @@ static void run_list(CooArgs a, DevBuf* slot_row, DevBuf* slot_val, hipStream_t 
   }
   a.slot_row = nteams > 1 ? slot_row[0].as<int>() : nullptr;
   a.slot_val = nteams > 1 ? slot_val[0].d() : nullptr;
-  const int G = R <= 4 ? 4 : R <= 8 ? 8 : R <= 16 ? 16 : R <= 32 ? 32 : 64;
-  switch (G) {
-    case 4: launch_coo<4>(a, nteams, s); break;
-    case 8: launch_coo<8>(a, nteams, s); break;
-    case 16: launch_coo<16>(a, nteams, s); break;
-    case 32: launch_coo<32>(a, nteams, s); break;
-    default: launch_coo<64>(a, nteams, s); break;
-  }
+  for_team_width(R, [&](auto g) {
+    for_order<1>(a.no, [&](auto no) {                // the other modes: 1..3 compiled in
+      constexpr int G = decltype(g)::value;
+      mttkrp_coo_k<G, decltype(no)::value><<<coo_team_grid(a.nnz, G), 256, 0, s>>>(a);
+    });
+  });
+  AO_KERNEL_CHECK();
   if (nteams > 1)
     carry_passes(slot_row[0].as<int>(), slot_val[0].d(), 2 * nteams, R, a.scale, a.out, a.oI, a.oR, slot_row, slot_val, 1, s);
 }

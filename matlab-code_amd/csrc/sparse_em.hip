@@ -2,6 +2,7 @@
 // parts of f_rel_missing and the dense correction of the MTTKRP.  See sparse_em.h and DESIGN.md section 9.3.
 #include <algorithm>
 
+#include "coo_team.h"
 #include "readback.h"
 #include "small.h"
 #include "sparse_em.h"
@@ -11,9 +12,8 @@ namespace aoadmm {
 // ---------------------------------------------------------------------------
 // passes over one copy of the nonzeros
 // ---------------------------------------------------------------------------
-// mttkrp_coo_k's team layout: G lanes walk kCooChunk consecutive entries, lane r owns column r of every factor row,
-// kSemUnroll entries' loads are in flight together.  The model value of an entry is the sum of the lanes' products
-// (xor butterfly inside the team: every lane ends with the same bits).
+// The team layout of coo_team.h, kSemUnroll entries at a time.  The model value of an entry is the team_sum of the
+// lanes' products.
 struct SemArgs {
   const int* row;
   const int* oidx;
@@ -30,13 +30,6 @@ struct SemArgs {
 
 constexpr int kSemUnroll = 4;
 
-template <int G>
-__device__ __forceinline__ double team_sum(double v) {
-#pragma unroll
-  for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, G);
-  return v;
-}
-
 // ND = order of the block (2..4 compiled in; 0: a.nd at run time, up to 8)
 // STAT 0: residuals only; 1: + sum (x-m)^2 and sum m^2; 2: + sum (m_new - m_old)^2 in the telescoped form
 //   m_new - m_old = sum_a prod_{n<a} fo_n * (f_a - fo_a) * prod_{n>a} f_n   per column, then summed over the columns
@@ -44,17 +37,15 @@ __device__ __forceinline__ double team_sum(double v) {
 //   sum dm^2, sum (1-w)^2 dm^2: no difference of sums is formed here
 template <int G, int ND, int STAT, bool WT>
 __global__ __launch_bounds__(256) void sem_pass_k(SemArgs a) {
-  const int64_t team = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-  const int r = (int)(threadIdx.x % G);
-  const int64_t start = team * kCooChunk;
-  if (start >= a.nnz) return;                        // whole teams leave: the butterfly stays inside a team
-  const int64_t end = start + kCooChunk < a.nnz ? start + kCooChunk : a.nnz;
+  const CooTeam<G> t(a.nnz, a.R);
+  if (t.idle()) return;
+  const int64_t end = t.end();
+  const int rr = t.rr();
+  const bool live = t.live();
   constexpr int NMAX = ND > 0 ? ND : kCooMaxModes;
   const int nd = ND > 0 ? ND : a.nd;
-  const bool live = r < a.R;
-  const int rr = live ? r : a.R - 1;                 // lanes beyond R read column R - 1 and contribute +0
   double s_res = 0.0, s_m2 = 0.0, s_d2 = 0.0, s_cm2 = 0.0, s_cd2 = 0.0;
-  for (int64_t i0 = start; i0 < end; i0 += kSemUnroll) {
+  for (int64_t i0 = t.start; i0 < end; i0 += kSemUnroll) {
     double mu[kSemUnroll], du[kSemUnroll], xu[kSemUnroll], wu[kSemUnroll];
 #pragma unroll
     for (int u = 0; u < kSemUnroll; ++u) {
@@ -64,8 +55,8 @@ __global__ __launch_bounds__(256) void sem_pass_k(SemArgs a) {
       for (int n = 0; n < NMAX; ++n) {
         if (n < nd) {
           const int64_t idx = n == 0 ? a.row[i] : a.oidx[(int64_t)(n - 1) * a.nnz + i];
-          fv[n] = a.f[n].p[idx * a.f[n].sI + rr * a.f[n].sR];
-          if (STAT == 2) fov[n] = a.fo[n].p[idx * a.fo[n].sI + rr * a.fo[n].sR];
+          fv[n] = coo_at(a.f[n], idx, rr);
+          if (STAT == 2) fov[n] = coo_at(a.fo[n], idx, rr);
         }
       }
       xu[u] = a.val[i];
@@ -100,68 +91,52 @@ __global__ __launch_bounds__(256) void sem_pass_k(SemArgs a) {
         const double e = xu[u] - mu[u];
         if (WT) {
           const double w = wu[u], c2 = (1.0 - w) * (1.0 - w), m2 = mu[u] * mu[u], d2 = du[u] * du[u];
-          if (a.res != nullptr && r == 0) a.res[i0 + u] = w * xu[u] - (w - a.alpha) * mu[u];
+          if (a.res != nullptr && t.r == 0) a.res[i0 + u] = w * xu[u] - (w - a.alpha) * mu[u];
           if (STAT > 0) { s_res += w * (e * e); s_m2 += m2; s_cm2 += c2 * m2; }
           if (STAT == 2) { s_d2 += d2; s_cd2 += c2 * d2; }
         } else {
-          if (a.res != nullptr && r == 0) a.res[i0 + u] = e;
+          if (a.res != nullptr && t.r == 0) a.res[i0 + u] = e;
           if (STAT > 0) { s_res += e * e; s_m2 += mu[u] * mu[u]; }
           if (STAT == 2) s_d2 += du[u] * du[u];
         }
       }
     }
   }
-  if (STAT > 0 && r == 0) {
+  if (STAT > 0 && t.r == 0) {
     if (WT) {
-      double* q = a.part + kSemSumsW * team;
+      double* q = a.part + kSemSumsW * t.team;
       q[0] = s_res; q[1] = s_m2; q[2] = s_cm2; q[3] = s_d2; q[4] = s_cd2;
     } else {
-      a.part[3 * team + 0] = s_res;
-      a.part[3 * team + 1] = s_m2;
-      a.part[3 * team + 2] = s_d2;
+      a.part[3 * t.team + 0] = s_res;
+      a.part[3 * t.team + 1] = s_m2;
+      a.part[3 * t.team + 2] = s_d2;
     }
   }
 }
 
-static unsigned sem_blocks(int64_t n, int t = 256) { return (unsigned)std::max<int64_t>(1, cdiv(n, t)); }
-
-template <int G, int STAT, bool WT>
-static void launch_sem_nd(const SemArgs& a, hipStream_t s) {
-  const unsigned grid = sem_blocks(cdiv(a.nnz, kCooChunk) * G);
-  switch (a.nd) {
-    case 2: sem_pass_k<G, 2, STAT, WT><<<grid, 256, 0, s>>>(a); break;
-    case 3: sem_pass_k<G, 3, STAT, WT><<<grid, 256, 0, s>>>(a); break;
-    case 4: sem_pass_k<G, 4, STAT, WT><<<grid, 256, 0, s>>>(a); break;
-    default: sem_pass_k<G, 0, STAT, WT><<<grid, 256, 0, s>>>(a); break;
-  }
+template <int STAT, bool WT>
+static void launch_sem_pass(const SemArgs& a, hipStream_t s) {
+  for_team_width(a.R, [&](auto g) {
+    for_order<2>(a.nd, [&](auto nd) {                // orders 2..4 compiled in
+      constexpr int G = decltype(g)::value;
+      sem_pass_k<G, decltype(nd)::value, STAT, WT><<<coo_team_grid(a.nnz, G), 256, 0, s>>>(a);
+    });
+  });
   AO_KERNEL_CHECK();
 }
 
-template <int G, bool WT>
+template <bool WT>
 static void launch_sem_stat(const SemArgs& a, int stat, hipStream_t s) {
   switch (stat) {
-    case 0: launch_sem_nd<G, 0, WT>(a, s); break;
-    case 1: launch_sem_nd<G, 1, WT>(a, s); break;
-    default: launch_sem_nd<G, 2, WT>(a, s); break;
-  }
-}
-
-template <bool WT>
-static void launch_sem_team(const SemArgs& a, int stat, hipStream_t s) {
-  const int R = a.R;
-  const int G = R <= 4 ? 4 : R <= 8 ? 8 : R <= 16 ? 16 : R <= 32 ? 32 : 64;
-  switch (G) {
-    case 4: launch_sem_stat<4, WT>(a, stat, s); break;
-    case 8: launch_sem_stat<8, WT>(a, stat, s); break;
-    case 16: launch_sem_stat<16, WT>(a, stat, s); break;
-    case 32: launch_sem_stat<32, WT>(a, stat, s); break;
-    default: launch_sem_stat<64, WT>(a, stat, s); break;
+    case 0: launch_sem_pass<0, WT>(a, s); break;
+    case 1: launch_sem_pass<1, WT>(a, s); break;
+    default: launch_sem_pass<2, WT>(a, s); break;
   }
 }
 
 static void launch_sem(const SemArgs& a, int stat, bool weighted, hipStream_t s) {
-  if (weighted) launch_sem_team<true>(a, stat, s);
-  else launch_sem_team<false>(a, stat, s);
+  if (weighted) launch_sem_stat<true>(a, stat, s);
+  else launch_sem_stat<false>(a, stat, s);
 }
 
 // res = w o x, the residual array of the starting point of a weighted block (w absent: res = x)
@@ -219,18 +194,6 @@ struct SemFinish {
   double alpha;                          // WT: the weight of every unstored entry
 };
 
-// block-wide sum in a fixed order: every thread's value, then a tree over LDS
-__device__ double sem_block_sum(double v, double* sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
 // T_a' T_b of one mode at (r, s), T in {0: Fo, 1: D, 2: F}, from Fo'Fo, D'D, D'Fo and F'F (F = Fo + D)
 __device__ __forceinline__ double sem_pair(int ta, int tb, const double* GFo, const double* GF, const double* DtD,
                                            const double* DtFo, int r, int s, int R) {
@@ -265,11 +228,11 @@ __global__ __launch_bounds__(256) void sem_finish_k(SemFinish a) {
     p2 += a.part[NS * t + 2];
     if (WT) { p3 += a.part[NS * t + 3]; p4 += a.part[NS * t + 4]; }
   }
-  const double s_res = sem_block_sum(p0, sh);
-  const double s_m2 = sem_block_sum(p1, sh);
-  const double s_cm2 = WT ? sem_block_sum(p2, sh) : 0.0;
-  const double s_d2 = sem_block_sum(WT ? p3 : p2, sh);
-  const double s_cd2 = WT ? sem_block_sum(p4, sh) : 0.0;
+  const double s_res = coo_block_sum(p0, sh);
+  const double s_m2 = coo_block_sum(p1, sh);
+  const double s_cm2 = WT ? coo_block_sum(p2, sh) : 0.0;
+  const double s_d2 = coo_block_sum(WT ? p3 : p2, sh);
+  const double s_cd2 = WT ? coo_block_sum(p4, sh) : 0.0;
   if (a.form == 0 && !(WT && a.alpha > 0.0)) {
     if (threadIdx.x == 0) a.em[kEmObsRes] = s_res;
     return;
@@ -293,8 +256,8 @@ __global__ __launch_bounds__(256) void sem_finish_k(SemFinish a) {
         }
     }
   }
-  const double normF = sem_block_sum(full, sh);
-  const double normD = sem_block_sum(delta, sh);
+  const double normF = coo_block_sum(full, sh);
+  const double normD = coo_block_sum(delta, sh);
   if (WT) {
     if (threadIdx.x == 0) {
       const double unst = normF - s_m2 > 0.0 ? normF - s_m2 : 0.0;
@@ -353,7 +316,7 @@ void sem_reset(SparseEm& e, const CooBlock& b, hipStream_t s) {
   if (!e.weighted) return;                           // the plain MTTKRP reads the block's own values
   AO_REQUIRE(e.on && e.nd == b.nd && e.nnz == b.nnz, "internal: weights of another block");
   for (int m = 0; m < e.nd; ++m) {
-    sem_fill_k<<<sem_blocks(std::min<int64_t>(e.nnz, (int64_t)1 << 22)), 256, 0, s>>>(e.res[m].d(), b.mode[m].val.d(),
+    sem_fill_k<<<blocks_for(std::min<int64_t>(e.nnz, (int64_t)1 << 22)), 256, 0, s>>>(e.res[m].d(), b.mode[m].val.d(),
                                                                                      e.wt[m].p ? e.wt[m].d() : nullptr, e.nnz);
     AO_KERNEL_CHECK();
   }
@@ -366,7 +329,7 @@ void sem_check_weight_list(const CooBlock& b, const CooBlock& wts, hipStream_t s
   DevBuf flag;
   flag.alloc(sizeof(int));
   AO_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), s));
-  const unsigned grid = sem_blocks(std::min<int64_t>(b.nnz * std::max(1, b.nd - 1), (int64_t)1 << 22));
+  const unsigned grid = blocks_for(std::min<int64_t>(b.nnz * std::max(1, b.nd - 1), (int64_t)1 << 22));
   for (int m = 0; m < b.nd; ++m) {
     sem_differ_k<<<grid, 256, 0, s>>>(flag.as<int>(), b.mode[m].row.as<int>(), wts.mode[m].row.as<int>(), b.nnz);
     AO_KERNEL_CHECK();
@@ -424,7 +387,7 @@ void sem_step_begin(SparseEm& e, const CooBlock& b, const SemFac* f, bool stats_
   if (e.have_snap && !stats_only)
     for (int n = 0; n < nd; ++n) {
       const int64_t rows = e.dims[n];
-      sem_diff_k<<<sem_blocks(std::min<int64_t>(rows * R, (int64_t)1 << 20)), 256, 0, s>>>(e.D.d(), f[n].p, f[n].ld, e.snapC[n].d(), rows, R);
+      sem_diff_k<<<blocks_for(std::min<int64_t>(rows * R, (int64_t)1 << 20)), 256, 0, s>>>(e.D.d(), f[n].p, f[n].ld, e.snapC[n].d(), rows, R);
       AO_KERNEL_CHECK();
       atb_small(e.mat(2, n), e.D.d(), rows, e.D.d(), rows, rows, R, R, e.ws.d(), nullptr, s);
       atb_small(e.mat(3, n), e.D.d(), rows, e.snapC[n].d(), rows, rows, R, R, e.ws.d(), nullptr, s);
@@ -475,7 +438,7 @@ void sem_step_finish(SparseEm& e, const SemFac* f, bool stats_only, double* em, 
   // the snapshot: Fo <- F, Fo'Fo <- F'F
   for (int n = 0; n < nd; ++n) {
     const int64_t rows = e.dims[n];
-    sem_snapshot_k<<<sem_blocks(std::min<int64_t>(rows * R, (int64_t)1 << 20)), 256, 0, s>>>(e.snapC[n].d(), e.snapR[n].d(), f[n].p, f[n].ld, rows, R);
+    sem_snapshot_k<<<blocks_for(std::min<int64_t>(rows * R, (int64_t)1 << 20)), 256, 0, s>>>(e.snapC[n].d(), e.snapR[n].d(), f[n].p, f[n].ld, rows, R);
     AO_KERNEL_CHECK();
   }
   AO_HIP(hipMemcpyAsync(e.mat(0, 0), e.mat(1, 0), (size_t)nd * RR * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -489,7 +452,7 @@ void sem_mttkrp_correct(SparseEm& e, int pos, const SemFac* f, double scale, dou
   if (e.weighted && e.alpha == 1.0) return;          // nothing is imputed off the stored set
   for (int j = 0; j < e.nd; ++j)
     if (j != pos) atb_small(e.mat(4, j), e.snapC[j].d(), e.dims[j], f[j].p, f[j].ld, e.dims[j], R, R, e.ws.d(), nullptr, s);
-  sem_had_k<<<sem_blocks(RR), 256, 0, s>>>(e.W(), e.mat(4, 0), RR, e.nd, pos, RR);
+  sem_had_k<<<blocks_for(RR), 256, 0, s>>>(e.W(), e.mat(4, 0), RR, e.nd, pos, RR);
   AO_KERNEL_CHECK();
   gemm_small(out, ldOut, e.snapC[pos].d(), e.dims[pos], e.W(), R, e.dims[pos], R, R, 0, coef(scale), 1.0, nullptr, s);
 }

@@ -12,8 +12,6 @@
 
 namespace aoadmm {
 
-static unsigned blocks_for(int64_t n, int t = 256) { return (unsigned)std::max<int64_t>(1, cdiv(n, t)); }
-
 // ---------------------------------------------------------------------------
 // fiber lists
 // ---------------------------------------------------------------------------
