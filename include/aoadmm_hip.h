@@ -682,6 +682,57 @@ int aoadmm_op_par2_b_loop(aoadmm_ctx* ctx, int K, const int64_t* rows_k, int R, 
                           int n_params, int max_inner, const double* tol, double* P, double* mu_DeltaB,
                           double* DeltaB, double* Z, double* muZ, double* B, double* rho, double* L, double* GB,
                           int* inner_iters, double* res, int* path);
+/* The three entries below run the steps of a dense PARAFAC2 block outside the B_k loop as aoadmm_solve runs them, on
+ * host arrays and without a model: K slabs X_k (I x rows_k[k], column-major) back to back in X; B (and P, Z) = the
+ * slab-valued factors back to back, slab k rows_k[k] x R column-major; A (I x R); C (K x R).  Each answers
+ * AOADMM_ERR_UNSUPPORTED on a context that belongs to a communicator or drives several devices.
+ *
+ * Mode A (cmtf_fun_AOADMM.m:160-165): GB[k] = B_k'*B_k, T1[k] = X_k*B_k, Amt = sum_k T1[k]*D_k (the unweighted MTTKRP,
+ * I x R), Csys = sum_k D_k GB[k] D_k (R x R), and Csys_only = the same Csys from the launch a block with sparse slabs
+ * uses.  Every output may be NULL.  T1 is [K][I*R], GB [K][R*R].  path[0] / path[1] = tile width (4, 16 or 64 outputs per
+ * workgroup) of the Amt + Csys launch / of the Csys-only launch; the library picks them from I*R + R*R and R*R. */
+int aoadmm_op_par2_mode_a(aoadmm_ctx* ctx, int K, const int64_t* rows_k, int I, int R, const double* X, const double* B,
+                          const double* C, double* T1, double* GB, double* Amt, double* Csys, double* Csys_only,
+                          int* path);
+/* What aoadmm_op_par2_mode_c builds (`system`) and the form its uncoupled update took (path[0]). */
+enum {
+  AOADMM_P2CSYS_UNCOUPLED = 0,    /* the uncoupled update: systems, then the row solve or the ADMM loop (:219-248) */
+  AOADMM_P2CSYS_ROWS = 1,         /* coupled, types 0, 3, 4: chol(w*C_k + ... + rho_k/2*(1 + constrained)*I)  (:260-267) */
+  AOADMM_P2CSYS_HHT = 2,          /* coupled, type 2: chol(... + rho_k/2*(H*H' + constrained*I))  (:305-312) */
+  AOADMM_P2CSYS_DIAG = 3,         /* coupled, types 1, 5, H'*H = diag(d): chol(B_k + mean(rho)/2*(d_k + constrained)*I) */
+  AOADMM_P2CSYS_DENSE = 4         /* coupled, types 1, 5: M = blkdiag(B_k) + mean(rho)/2*(kron(H'*H, I) + constrained*I) */
+};
+enum {
+  AOADMM_P2C_SINGLE = 0,          /* unconstrained: one row solve (:236) */
+  AOADMM_P2C_WG = 1,              /* whole ADMM loop in one workgroup, a row system per thread: K <= 256, R <= 16 */
+  AOADMM_P2C_LAUNCHED = 2         /* row solve, constraint update and loop test launched per inner iteration */
+};
+/* Mode C (cmtf_fun_AOADMM.m:219-248, coupled systems :260-312).  A'*A, B_k'*B_k and X_k*B_k are formed on the device;
+ * a(k,r) = weight*sum_i A(i,r)(X_k B_k)(i,r) + bsum_half*C(k,r), C_k = A'A .* B_k'B_k, rho_k = trace(C_k)/R,
+ * B_k = weight*C_k + (ridge + bsum_half)*I.  constraint = AOADMM_C_NONE: unconstrained.
+ * system = AOADMM_P2CSYS_UNCOUPLED: L_k = chol(B_k + constrained*rho_k/2*I); unconstrained, C(k,:) = a_k / (L_k L_k');
+ * constrained, ADMM_constrained_only on the K row systems (:600-606) with max(rho) in the prox, from C / Z / mu (K x R,
+ * updated in place) for at most max_inner iterations under tol = {pr_constr, du_constr}.
+ * Other systems: only the builders run (C, Z, mu are not changed; max_inner and tol are ignored); `constrained` is
+ * constraint != AOADMM_C_NONE; sysmat = H*H' (R x R), d (K) or H'*H (K x K) for systems 2, 3, 4.
+ * Returned (each may be NULL): a (K x R); rho (K); L ([K][R*R]: the factors, the raw B_k for system 4);
+ * rho_stats[0..2] = max, mean, sum of rho (the uncoupled update sets [0] only, and nothing when path[0] is
+ * AOADMM_P2C_WG: that loop takes the maximum itself); M ((K*R) x (K*R), system 4, unknowns ordered k*R + r); the
+ * inner iteration count (0 without a loop); res[0] / res[1] = relative primal / dual constraint residual of the last
+ * iteration; path[0] = AOADMM_P2C_* (-1 for the coupled builders), path[1] = rank class of the row solve (4, 8, 16 or
+ * 64).  AOADMM_ERR_NOT_PD when a factorisation fails. */
+int aoadmm_op_par2_mode_c(aoadmm_ctx* ctx, int system, int K, const int64_t* rows_k, int I, int R, const double* X,
+                          const double* A, const double* B, double weight, double ridge, double bsum_half,
+                          int constraint, const double* params, int n_params, int max_inner, const double* tol,
+                          const double* sysmat, double* C, double* Z, double* mu, double* a, double* rho, double* L,
+                          double* rho_stats, double* M, int* inner_iters, double* res, int* path);
+/* Objective pieces (cmtf_fun_AOADMM.m:1262-1264, :1355, :1337, :1279-1281): res[k] = ||X_k - A D_k B_k'||_F^2;
+ * q[4k..4k+3] = ||B_k - P_k DeltaB||^2, ||B_k||^2, ||B_k - Z_k||^2 (0 when Z is NULL), ||B_k - B_{k-1}||^2 (0 for k = 0
+ * and where the two slabs differ in size); regv[k] = reg_func(B_k) of regularisation type reg_type (an AOADMM_C_* with
+ * a reg_func value other than the quadratic one; AOADMM_C_NONE: regv untouched, may be NULL) with parameter eta. */
+int aoadmm_op_par2_objective(aoadmm_ctx* ctx, int K, const int64_t* rows_k, int I, int R, const double* X,
+                             const double* A, const double* B, const double* C, const double* P, const double* DeltaB,
+                             const double* Z, int reg_type, double eta, double* res, double* q, double* regv);
 /* Form of the coupled ADMM loop (cmtf_fun_AOADMM.m:625-1075; reported by aoadmm_op_coupled_loop).  The library picks
  * it from the coupling type, the number of coupled modes, the rows and columns of Delta, the ranks and the constraints. */
 enum {

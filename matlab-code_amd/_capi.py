@@ -56,6 +56,8 @@ ALL_SLABS = -1            # AOADMM_ALL_SLABS
 (PATH_WG, PATH_MFMA, PATH_ROWS_FUSED, PATH_ROWS_COLPROX, PATH_ROWS_TV, PATH_ROWL) = range(6)   # AOADMM_PATH_*
 (CPATH_REGS, CPATH_WG, CPATH_ROWSTEPS, CPATH_GENERIC) = range(4)   # AOADMM_CPATH_*
 (P2SLAB_REGS1, P2SLAB_REGS2, P2SLAB_REGS4, P2SLAB_LDS4, P2SLAB_LDS8, P2SLAB_LDS16, P2SLAB_LDS64) = range(7)   # AOADMM_P2SLAB_*
+(P2CSYS_UNCOUPLED, P2CSYS_ROWS, P2CSYS_HHT, P2CSYS_DIAG, P2CSYS_DENSE) = range(5)   # AOADMM_P2CSYS_*
+(P2C_SINGLE, P2C_WG, P2C_LAUNCHED) = range(3)   # AOADMM_P2C_*
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double)   # aoadmm_progress_fn
 
 # every symbol include/aoadmm_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -73,6 +75,7 @@ SYMBOLS = [
     'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_resident_par2_rhs', 'aoadmm_kernel_stats',
     'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_resident_nvecs', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
     'aoadmm_op_admm_mode', 'aoadmm_op_par2_b_loop', 'aoadmm_op_coupled_loop',
+    'aoadmm_op_par2_mode_a', 'aoadmm_op_par2_mode_c', 'aoadmm_op_par2_objective',
 ]
 
 
@@ -222,6 +225,12 @@ def load_library():
                                           C.c_int, dp, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip, dp, ip]
     dpp = C.POINTER(dp)
     lib.aoadmm_op_coupled_loop.argtypes = [vp, C.c_int, dpp, dpp, C.c_int, dp, ip, dp, dp, dpp, dpp, dp, ip]
+    lib.aoadmm_op_par2_mode_a.argtypes = [vp, C.c_int, C.POINTER(i64), C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, ip]
+    lib.aoadmm_op_par2_mode_c.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i64), C.c_int, C.c_int, dp, dp, dp, C.c_double,
+                                          C.c_double, C.c_double, C.c_int, dp, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp,
+                                          dp, dp, dp, dp, ip, dp, ip]
+    lib.aoadmm_op_par2_objective.argtypes = [vp, C.c_int, C.POINTER(i64), C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp,
+                                             C.c_int, C.c_double, dp, dp, dp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name != 'aoadmm_last_error':

@@ -971,6 +971,184 @@ int aoadmm_op_par2_b_loop(aoadmm_ctx* ctx, int K, const int64_t* rows_k, int R, 
   });
 }
 
+// Slab layout of the op-level PARAFAC2 entries below: K dense slabs of rows_k[k] columns (par2.h)
+struct OpSlabs {
+  std::vector<int64_t> off;
+  DevBuf offd;
+  P2Dims d;
+};
+static void op_slabs(OpSlabs& o, aoadmm_ctx* ctx, const char* who, int K, const int64_t* rows_k, int I, int R, hipStream_t s) {
+  if (ctx->multi || ctx->eng->sharded())
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("%s runs on one engine without a communicator", who));
+  AO_REQUIRE(K >= 1 && rows_k && R > 0 && R <= kMaxRank && I >= 1, "bad arguments");
+  AO_REQUIRE((int64_t)I * R + (int64_t)R * R < ((int64_t)1 << 31) / K, "block too large");
+  o.off.assign((size_t)K + 1, 0);
+  int64_t jmax = 0;
+  for (int k = 0; k < K; ++k) {
+    AO_REQUIRE(rows_k[k] >= 1 && rows_k[k] < ((int64_t)1 << 31) / std::max(R, I), "slab %d: bad column count", k);
+    o.off[k + 1] = o.off[k] + rows_k[k];
+    jmax = std::max(jmax, rows_k[k]);
+  }
+  o.offd.alloc((size_t)(K + 1) * sizeof(int64_t));
+  AO_HIP(hipMemcpyAsync(o.offd.p, o.off.data(), (size_t)(K + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  o.d.K = K; o.d.I = I; o.d.R = R; o.d.off = o.offd.as<int64_t>(); o.d.off_h = o.off.data();
+  o.d.Jtot = o.off[K]; o.d.Jmax = (int)jmax; o.d.k0 = 0; o.d.k1 = K;
+}
+
+// Mode A of a dense PARAFAC2 block as Engine::par2_prepare_modeA runs it in front of the common system build: the Gram
+// matrices the B_k update leaves (par2_gram), par2_mode_a, and the Csys-only launch of a block with sparse slabs.
+int aoadmm_op_par2_mode_a(aoadmm_ctx* ctx, int K, const int64_t* rows_k, int I, int R, const double* X, const double* B,
+                          const double* Cmat, double* T1, double* GB, double* Amt, double* Csys, double* Csys_only,
+                          int* path) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    AO_REQUIRE(X && B && Cmat, "bad arguments");
+    Engine& e = *ctx->eng;
+    hipStream_t s = e.stream();
+    AO_HIP(hipSetDevice(e.device()));
+    OpSlabs o;
+    op_slabs(o, ctx, "aoadmm_op_par2_mode_a", K, rows_k, I, R, s);
+    const P2Dims& d = o.d;
+    const int64_t RR = (int64_t)R * R, nA = (int64_t)I * R;
+    DevBuf x, b, c, t1, gb, am, cs, co;
+    h2d(x, X, (int64_t)I * d.Jtot, s); h2d(b, B, d.Jtot * R, s); h2d(c, Cmat, (int64_t)K * R, s);
+    t1.alloc((size_t)K * nA * 8); gb.alloc((size_t)K * RR * 8); am.alloc((size_t)nA * 8); cs.alloc((size_t)RR * 8);
+    co.alloc((size_t)RR * 8);
+    par2_gram(b.d(), d, gb.d(), s);
+    par2_mode_a(x.d(), b.d(), c.d(), gb.d(), d, t1.d(), am.d(), cs.d(), s);
+    par2_modeA_csys(c.d(), gb.d(), d, co.d(), s);
+    if (path) { path[0] = par2_modeA_tile_width(d); path[1] = par2_modeA_csys_tile_width(d); }
+    AO_HIP(hipStreamSynchronize(s));
+    if (T1) d2h(T1, t1, (int64_t)K * nA, s);
+    if (GB) d2h(GB, gb, (int64_t)K * RR, s);
+    if (Amt) d2h(Amt, am, nA, s);
+    if (Csys) d2h(Csys, cs, RR, s);
+    if (Csys_only) d2h(Csys_only, co, RR, s);
+  });
+}
+
+// Mode C of a dense PARAFAC2 block: system 0 = the uncoupled update as Engine::par2_update_C runs it (par2_c_systems,
+// par2_c_solve on the path par2_c_path() names); systems 1..4 = the builders of Engine::par2_prepare_C_coupled
+// (par2_c_coupled_kind, par2_c_systems, par2_rho_max, par2_c_coupled_big).
+int aoadmm_op_par2_mode_c(aoadmm_ctx* ctx, int system, int K, const int64_t* rows_k, int I, int R, const double* X,
+                          const double* A, const double* B, double weight, double ridge, double bsum_half, int constraint,
+                          const double* params, int n_params, int max_inner, const double* tol, const double* sysmat,
+                          double* Cmat, double* Z, double* mu, double* a, double* rho, double* L, double* rho_stats,
+                          double* M, int* inner_iters, double* res, int* path) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    AO_REQUIRE(X && A && B && Cmat, "bad arguments");
+    AO_REQUIRE(system >= AOADMM_P2CSYS_UNCOUPLED && system <= AOADMM_P2CSYS_DENSE, "system selector %d out of range", system);
+    AO_REQUIRE(constraint >= AOADMM_C_NONE && constraint < AOADMM_C_TPARAFAC2 && constraint != AOADMM_C_QUADRATIC,
+               "constraint id %d is not available here", constraint);
+    const bool constr = constraint != AOADMM_C_NONE;
+    const bool uncoupled = system == AOADMM_P2CSYS_UNCOUPLED;
+    AO_REQUIRE(!uncoupled || !constr || (Z && mu && tol && max_inner >= 1), "a constrained C update needs Z, mu, tol and max_inner >= 1");
+    AO_REQUIRE(system < AOADMM_P2CSYS_HHT || sysmat, "systems 2, 3 and 4 need their matrix (H*H', the diagonal of H'*H, H'*H)");
+    Engine& e = *ctx->eng;
+    hipStream_t s = e.stream();
+    AO_HIP(hipSetDevice(e.device()));
+    OpSlabs o;
+    op_slabs(o, ctx, "aoadmm_op_par2_mode_c", K, rows_k, I, R, s);
+    const P2Dims& d = o.d;
+    const int64_t RR = (int64_t)R * R, KR = (int64_t)K * R, n = KR;
+    if (system == AOADMM_P2CSYS_DENSE) AO_REQUIRE(n <= kDenseMaxN, "K*R = %lld exceeds the dense-system limit %d", (long long)n, kDenseMaxN);
+    DevBuf x, af, bf, cf, ga, gb, t1, ac, rh, l, sm, rst, mbig, z, m, zold, v, ws, slots, red, ctl, aws;
+    h2d(x, X, (int64_t)I * d.Jtot, s); h2d(af, A, (int64_t)I * R, s); h2d(bf, B, d.Jtot * R, s); h2d(cf, Cmat, KR, s);
+    ga.alloc((size_t)RR * 8); gb.alloc((size_t)K * RR * 8); t1.alloc((size_t)K * I * R * 8);
+    ac.alloc((size_t)KR * 8); rh.alloc((size_t)K * 8); l.alloc((size_t)K * RR * 8); rst.alloc(64);
+    AO_HIP(hipMemsetAsync(l.p, 0, (size_t)K * RR * 8, s));
+    aws.alloc(atb_ws_bytes(I, R, R));
+    ctl.alloc(sizeof(AdmmCtl));
+    AO_HIP(hipMemsetAsync(ctl.p, 0, sizeof(AdmmCtl), s));
+    AdmmCtl* c = ctl.as<AdmmCtl>();
+    atb_small(ga.d(), af.d(), I, af.d(), I, I, R, R, aws.d(), nullptr, s);     // A'A as the A update leaves it (:148)
+    par2_gram(bf.d(), d, gb.d(), s);                                           // B_k'B_k as the B_k update leaves them
+    P2CSys cs;
+    cs.X = x.d(); cs.A = af.d(); cs.B = bf.d(); cs.GA = ga.d(); cs.GB = gb.d(); cs.Cfac = cf.d();
+    cs.w = weight; cs.ridge = ridge; cs.bsum_half = bsum_half;
+    cs.T1 = t1.d(); cs.a = ac.d(); cs.rho = rh.d(); cs.L = l.d();
+    int pth = -1;
+    if (uncoupled) {
+      cs.nrho = constr ? 1 : 0; cs.raw = 0;
+      par2_c_systems(cs, d, c, s);
+      P2CSolve g;
+      g.a = ac.d(); g.rho = rh.d(); g.L = l.d(); g.fac = cf.d();
+      g.constrained = constr; g.prox = make_spec(constraint, params, n_params);
+      g.max_inner = constr ? max_inner : 0; g.tol_pr = constr ? tol[0] : 0.0; g.tol_du = constr ? tol[1] : 0.0;
+      g.rhomax = rst.d();
+      if (constr) {
+        h2d(z, Z, KR, s); h2d(m, mu, KR, s);
+        zold.alloc((size_t)KR * 8); v.alloc((size_t)KR * 8); ws.alloc(prox_ws_bytes(constraint, K, R));
+        slots.alloc(8 * 8); red.alloc(4096 * sizeof(double));
+        AO_HIP(hipMemsetAsync(slots.p, 0, 8 * 8, s));
+        g.Z = z.d(); g.mu = m.d(); g.Zold = zold.d(); g.V = v.d(); g.prox_ws = ws.d(); g.slots = slots.d(); g.red_ws = red.d();
+      }
+      pth = (int)par2_c_solve(g, d, c, s);
+    } else {
+      // the coupling types that lead to each builder: 0 (also 3, 4) | 2 | 1 (also 5) with a diagonal / a dense H'H
+      const int ctype = system == AOADMM_P2CSYS_ROWS ? 0 : (system == AOADMM_P2CSYS_HHT ? 2 : 1);
+      const P2CCoupledKind ck = par2_c_coupled_kind(ctype, constr ? 1 : 0);
+      if (sysmat) h2d(sm, sysmat, system == AOADMM_P2CSYS_HHT ? RR : (system == AOADMM_P2CSYS_DIAG ? (int64_t)K : (int64_t)K * K), s);
+      cs.nrho = ck.nrho; cs.raw = ck.raw; cs.Madd = ck.madd ? sm.d() : nullptr;
+      par2_c_systems(cs, d, c, s);
+      par2_rho_max(rh.d(), K, rst.d(), s, rst.d() + 1, rst.d() + 2);
+      if (ck.raw) {
+        const bool diag = system == AOADMM_P2CSYS_DIAG;
+        if (!diag) mbig.alloc((size_t)n * n * 8);
+        par2_c_coupled_big(l.d(), sm.d(), diag, rst.d() + 1, constr ? 1 : 0, K, R, diag ? nullptr : mbig.d(), c, s);
+      }
+    }
+    AdmmCtl h;
+    AO_HIP(hipMemcpyAsync(&h, ctl.p, sizeof h, hipMemcpyDeviceToHost, s));
+    AO_HIP(hipStreamSynchronize(s));
+    if (h.notpd) throw Error(AOADMM_ERR_NOT_PD, "Matrix must be positive definite.");
+    if (inner_iters) *inner_iters = h.iters;
+    if (res) { res[0] = h.res[1]; res[1] = h.res[3]; }
+    if (path) { path[0] = pth; path[1] = par2_c_rowsolve_class(R); }
+    if (a) d2h(a, ac, KR, s);
+    if (rho) d2h(rho, rh, K, s);
+    if (L) d2h(L, l, (int64_t)K * RR, s);
+    if (rho_stats && !(uncoupled && pth == (int)kP2CWgLoop)) d2h(rho_stats, rst, uncoupled ? 1 : 3, s);
+    if (M && system == AOADMM_P2CSYS_DENSE) d2h(M, mbig, n * n, s);
+    if (uncoupled) {
+      d2h(Cmat, cf, KR, s);
+      if (constr) { d2h(Z, z, KR, s); d2h(mu, m, KR, s); }
+    }
+  });
+}
+
+// Objective pieces of a dense PARAFAC2 block as Engine::par2_objective_enqueue runs them (par2_objective).
+int aoadmm_op_par2_objective(aoadmm_ctx* ctx, int K, const int64_t* rows_k, int I, int R, const double* X, const double* A,
+                             const double* B, const double* Cmat, const double* P, const double* DeltaB, const double* Z,
+                             int reg_type, double eta, double* res, double* q, double* regv) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    AO_REQUIRE(X && A && B && Cmat && P && DeltaB && res && q, "bad arguments");
+    AO_REQUIRE(reg_type == AOADMM_C_NONE || (prox_has_reg_value(reg_type) && reg_type != AOADMM_C_QUADRATIC && regv),
+               "regularisation type %d has no value here", reg_type);
+    Engine& e = *ctx->eng;
+    hipStream_t s = e.stream();
+    AO_HIP(hipSetDevice(e.device()));
+    OpSlabs o;
+    op_slabs(o, ctx, "aoadmm_op_par2_objective", K, rows_k, I, R, s);
+    const P2Dims& d = o.d;
+    const int64_t nB = d.Jtot * R;
+    DevBuf x, af, bf, cf, pf, db, zf, rs, qq, rv;
+    h2d(x, X, (int64_t)I * d.Jtot, s); h2d(af, A, (int64_t)I * R, s); h2d(bf, B, nB, s); h2d(cf, Cmat, (int64_t)K * R, s);
+    h2d(pf, P, nB, s); h2d(db, DeltaB, (int64_t)R * R, s);
+    if (Z) h2d(zf, Z, nB, s);
+    rs.alloc((size_t)K * 8); qq.alloc((size_t)K * 4 * 8); rv.alloc((size_t)K * 8);
+    P2Objective g;
+    g.X = x.d(); g.A = af.d(); g.B = bf.d(); g.Cfac = cf.d(); g.P = pf.d(); g.DeltaB = db.d(); g.Z = Z ? zf.d() : nullptr;
+    g.reg_type = reg_type; g.eta = eta;
+    g.res = rs.d(); g.q = qq.d(); g.regv = rv.d();
+    par2_objective(g, d, s);
+    d2h(res, rs, K, s); d2h(q, qq, (int64_t)K * 4, s);
+    if (reg_type != AOADMM_C_NONE) d2h(regv, rv, K, s);
+  });
+}
+
 // The coupled loop of one coupling of the declared model as Engine::outer_updates runs it behind the MTTKRPs
 // (Engine::coupled_loop_op: the solver's own system build, coupled_admm and Gram matrices).
 int aoadmm_op_coupled_loop(aoadmm_ctx* ctx, int coupling, const double* const* A, const double* const* C, int max_inner,

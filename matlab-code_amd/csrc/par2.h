@@ -136,12 +136,75 @@ void par2_c_big_system(const double* Bk, const double* HtH, const double* rhoC, 
 void par2_c_rowsolve(const double* a, const double* rho, const double* L, const double* Z, const double* mu,
                      int use_admm, const P2Dims& d, double* Cfac, const AdmmCtl* ctl, hipStream_t s);
 
+// The steps of a dense block outside the B_k loop, each written once: Engine::par2_prepare_modeA / par2_update_C /
+// par2_prepare_C_coupled / par2_objective_enqueue and the op-level entries (capi.hip aoadmm_op_par2_mode_a / _mode_c /
+// _objective) run exactly these.
+// Tile width `ew` par2_modeA_combine launches with for this block, and par2_modeA_csys for this rank
+int par2_modeA_tile_width(const P2Dims& d);
+int par2_modeA_csys_tile_width(const P2Dims& d);
+// mode A from dense slabs (:160-165): T1 = X_k B_k, then Amt and Csys (par2_xkb, par2_modeA_combine)
+void par2_mode_a(const double* X, const double* B, const double* Cfac, const double* GB, const P2Dims& d, double* T1,
+                 double* Amt, double* Csys, hipStream_t s);
+
+// mode C from dense slabs, up to the systems (:219-240, coupled :260-312): T1 = X_k B_k, then par2_c_system
+struct P2CSys {
+  const double *X, *A, *B, *GA, *GB, *Cfac;   // slabs, A (I x R), B_k, A'A, B_k'B_k [K][R*R], C (K x R)
+  double w, ridge, bsum_half;
+  int nrho = 0, raw = 0;                      // see par2_c_system
+  const double* Madd = nullptr;
+  double *T1, *a, *rho, *L;                   // out: [K][I*R], K x R, K, [K][R*R]
+};
+void par2_c_systems(const P2CSys& g, const P2Dims& d, AdmmCtl* ctl, hipStream_t s);
+// What par2_c_system builds for a C mode inside a coupling of type `ctype` (:260-267, :305-312, :282-297): per-row
+// factors with nrho = 1 + constrained (types 0, 3, 4), the same with Madd = H*H' and nrho = constrained (type 2), or
+// the raw B_k for the (K*R)-system of types 1 and 5
+struct P2CCoupledKind { int nrho, raw, madd; };
+P2CCoupledKind par2_c_coupled_kind(int ctype, int constrained);
+// types 1, 5 behind the raw B_k: K row systems when H'H is diagonal (HtH holds the K diagonal entries, L is factored in
+// place), else the dense (K*R) x (K*R) system M from HtH (K x K)
+void par2_c_coupled_big(double* L, const double* HtH, bool hth_diag, const double* rhoC, int constrained, int K, int R,
+                        double* M, AdmmCtl* ctl, hipStream_t s);
+
+// Which form the uncoupled C update takes.  Decided from the inputs alone, in one place (par2_c_path); the values are
+// part of the C ABI (include/aoadmm_hip.h AOADMM_P2C_*).
+enum P2CPath {
+  kP2CSingle = 0,     // unconstrained: one par2_c_rowsolve (:236)
+  kP2CWgLoop = 1,     // admm_loop_wg_k<RM, 256, 2>: K <= 256 rows, R <= 16, element-/row-wise or column-norm prox
+  kP2CLaunched = 2    // par2_c_rowsolve + constraint_update + admm_finalize_generic per inner iteration
+};
+P2CPath par2_c_path(int K, int R, bool constrained, int ptype, int max_inner);
+int par2_c_rowsolve_class(int R);             // RMAX of par2_c_rowsolve_k: 4, 8, 16 or kMaxRank
+// The uncoupled C update behind the systems (:236, :602-606 with max(rho) in the prox, :1423-1424)
+struct P2CSolve {
+  const double *a, *rho, *L;                  // K x R, K, [K][R*R]
+  double *fac, *Z = nullptr, *mu = nullptr;   // K x R each
+  bool constrained = false;
+  ProxSpec prox;
+  int max_inner;
+  double tol_pr, tol_du;                      // innerRelPrTol_constr, innerRelDualTol_constr
+  double* rhomax;                             // device scalar (written unless the one-workgroup loop runs)
+  double *Zold = nullptr, *V = nullptr, *prox_ws = nullptr;   // launched loop: K x R, K x R, prox_ws_bytes
+  double *slots = nullptr, *red_ws = nullptr;                 // launched loop: 8 residual slots, 4096 doubles
+};
+P2CPath par2_c_solve(const P2CSolve& g, const P2Dims& dall, AdmmCtl* ctl, hipStream_t s);
+
+// objective pieces of a block (:1262-1264, :1355, :1337, :1279-1281): par2_residual (X != nullptr), par2_b_gaps,
+// par2_reg_values (reg_type with a reg_func value, else AOADMM_C_NONE)
+struct P2Objective {
+  const double *X, *A, *B, *Cfac, *P, *DeltaB, *Z;   // Z nullable
+  int reg_type = AOADMM_C_NONE;
+  double eta = 0.0;
+  double *res, *q, *regv;                     // out: K, [K][4], K
+};
+void par2_objective(const P2Objective& g, const P2Dims& d, hipStream_t s);
+
 // res[k] = ||X_k - A D_k B_k'||_F^2                                                       (:1262-1264)
 void par2_residual(const double* X, const double* A, const double* B, const double* Cfac, const P2Dims& d,
                    double* res, hipStream_t s);
 // regv[k] = reg_func(B_k) of a regularisation-type constraint on the B_k mode            (:1279-1281)
 void par2_reg_values(const double* B, int type, double eta, const P2Dims& d, double* regv, hipStream_t s);
-// q[k][0..3] = ||B_k - P_k DeltaB||^2, ||B_k||^2, ||B_k - Z_k||^2 (Z nullable), 0          (:1355, :1337)
+// q[k][0..3] = ||B_k - P_k DeltaB||^2, ||B_k||^2, ||B_k - Z_k||^2 (Z nullable), ||B_k - B_{k-1}||^2 (0 for k = 0 and for
+// neighbours of different size; t_smoothness_penalty.m)                                  (:1355, :1337)
 void par2_b_gaps(const double* B, const double* P, const double* DeltaB, const double* Z, const P2Dims& d,
                  double* q, hipStream_t s);
 

@@ -78,6 +78,8 @@ __device__ inline double ksum_tile(bool live, int g, int ng, int ew, int k0, int
   return red[threadIdx.x];
 }
 static inline int ksum_tile_width(int64_t n) { return n >= 16384 ? 64 : (n >= 2048 ? 16 : 4); }
+int par2_modeA_tile_width(const P2Dims& d) { return ksum_tile_width((int64_t)d.I * d.R + (int64_t)d.R * d.R); }
+int par2_modeA_csys_tile_width(const P2Dims& d) { return ksum_tile_width((int64_t)d.R * d.R); }
 
 // A{m} = sum_k X_k B_k diag(C(k,:)) ; C{m} = sum_k diag(C(k,:)) (B_k'B_k) diag(C(k,:))   (:163-164)
 __global__ __launch_bounds__(kKsumThreads) void par2_modeA_combine_k(const double* T1, const double* Cfac,
@@ -105,7 +107,7 @@ __global__ __launch_bounds__(kKsumThreads) void par2_modeA_combine_k(const doubl
 void par2_modeA_combine(const double* T1, const double* Cfac, const double* GB, const P2Dims& d, double* Amt,
                         double* Csys, hipStream_t s) {
   const int64_t nA = (int64_t)d.I * d.R, nC = (int64_t)d.R * d.R;
-  const int ew = ksum_tile_width(nA + nC);
+  const int ew = par2_modeA_tile_width(d);
   const unsigned nb = (unsigned)(cdiv(nA, ew) + cdiv(nC, ew));
   par2_modeA_combine_k<<<nb, kKsumThreads, 0, s>>>(T1, Cfac, GB, d, Amt, Csys, ew);
   AO_KERNEL_CHECK();
@@ -115,7 +117,7 @@ void par2_modeA_csys(const double* Cfac, const double* GB, const P2Dims& d, doub
   P2Dims d0 = d;
   d0.I = 0;
   const int64_t nC = (int64_t)d.R * d.R;
-  const int ew = ksum_tile_width(nC);
+  const int ew = par2_modeA_csys_tile_width(d);
   par2_modeA_combine_k<<<(unsigned)cdiv(nC, ew), kKsumThreads, 0, s>>>(nullptr, Cfac, GB, d0, nullptr, Csys, ew);
   AO_KERNEL_CHECK();
 }
@@ -1250,14 +1252,92 @@ __global__ void par2_c_rowsolve_k(const double* a, const double* rho, const doub
   for (int r = 0; r < RMAX; ++r)
     if (r < R) Cfac[k + K * r] = x[r];                                             // :236 / :605
 }
+int par2_c_rowsolve_class(int R) { return R <= 4 ? 4 : (R <= 8 ? 8 : (R <= 16 ? 16 : kMaxRank)); }
 void par2_c_rowsolve(const double* a, const double* rho, const double* L, const double* Z, const double* mu,
                      int use_admm, const P2Dims& d, double* Cfac, const AdmmCtl* ctl, hipStream_t s) {
   const unsigned nb = (unsigned)((d.K + 63) / 64);
-  if (d.R <= 4) par2_c_rowsolve_k<4><<<nb, 64, 0, s>>>(a, rho, L, Z, mu, use_admm, d, Cfac, ctl);
-  else if (d.R <= 8) par2_c_rowsolve_k<8><<<nb, 64, 0, s>>>(a, rho, L, Z, mu, use_admm, d, Cfac, ctl);
-  else if (d.R <= 16) par2_c_rowsolve_k<16><<<nb, 64, 0, s>>>(a, rho, L, Z, mu, use_admm, d, Cfac, ctl);
-  else par2_c_rowsolve_k<kMaxRank><<<nb, 64, 0, s>>>(a, rho, L, Z, mu, use_admm, d, Cfac, ctl);
+  switch (par2_c_rowsolve_class(d.R)) {
+    case 4: par2_c_rowsolve_k<4><<<nb, 64, 0, s>>>(a, rho, L, Z, mu, use_admm, d, Cfac, ctl); break;
+    case 8: par2_c_rowsolve_k<8><<<nb, 64, 0, s>>>(a, rho, L, Z, mu, use_admm, d, Cfac, ctl); break;
+    case 16: par2_c_rowsolve_k<16><<<nb, 64, 0, s>>>(a, rho, L, Z, mu, use_admm, d, Cfac, ctl); break;
+    default: par2_c_rowsolve_k<kMaxRank><<<nb, 64, 0, s>>>(a, rho, L, Z, mu, use_admm, d, Cfac, ctl); break;
+  }
   AO_KERNEL_CHECK();
+}
+
+// mode A from dense slabs (:160-165) -- see par2.h
+void par2_mode_a(const double* X, const double* B, const double* Cfac, const double* GB, const P2Dims& d, double* T1,
+                 double* Amt, double* Csys, hipStream_t s) {
+  par2_xkb(X, B, d, T1, s);
+  par2_modeA_combine(T1, Cfac, GB, d, Amt, Csys, s);
+}
+
+// mode C from dense slabs up to the systems -- see par2.h
+void par2_c_systems(const P2CSys& g, const P2Dims& d, AdmmCtl* ctl, hipStream_t s) {
+  par2_xkb(g.X, g.B, d, g.T1, s);
+  par2_c_system(g.A, g.T1, g.GA, g.GB, g.w, g.ridge, g.bsum_half, g.nrho, g.raw, d, g.Cfac, g.a, g.rho, g.L, ctl, s,
+                g.Madd);
+}
+P2CCoupledKind par2_c_coupled_kind(int ctype, int constrained) {
+  const int con = constrained ? 1 : 0;
+  if (ctype == 1 || ctype == 5) return P2CCoupledKind{0, 1, 0};     // H*C = ...: one (K*R) x (K*R) system from the raw B_k
+  if (ctype == 2) return P2CCoupledKind{con, 0, 1};                 // rho_k/2*H*H' carries the coupling term (:307)
+  return P2CCoupledKind{1 + con, 0, 0};
+}
+void par2_c_coupled_big(double* L, const double* HtH, bool hth_diag, const double* rhoC, int constrained, int K, int R,
+                        double* M, AdmmCtl* ctl, hipStream_t s) {
+  // row k: C(k,:) * (B_k + rhoC/2*(d_k [+ 1])*I) = A_inner(k,:); L holds B_k and is overwritten by the factors
+  if (hth_diag) par2_c_rowsys_diag(L, HtH, rhoC, constrained, K, R, ctl, s);
+  else par2_c_big_system(L, HtH, rhoC, constrained, K, R, M, s);
+}
+
+P2CPath par2_c_path(int K, int R, bool constrained, int ptype, int max_inner) {
+  if (!constrained) return kP2CSingle;
+  return admm_loop_wg_ok(K, R, ptype, max_inner) ? kP2CWgLoop : kP2CLaunched;
+}
+// the uncoupled C update behind the systems -- see par2.h
+P2CPath par2_c_solve(const P2CSolve& g, const P2Dims& dall, AdmmCtl* ctl, hipStream_t s) {
+  const int K = dall.K, R = dall.R;
+  const P2CPath path = par2_c_path(K, R, g.constrained, g.prox.type, g.max_inner);
+  if (path == kP2CWgLoop) {
+    // K <= 256 rows: the K row systems, update_constraint with max(rho) (the loop takes it itself) and the loop test in
+    // one launch (:602-606)
+    WgLoopU wa;
+    wa.A = g.a; wa.Binv = nullptr; wa.L = g.L; wa.rho = g.rho; wa.rho_prox = nullptr;
+    wa.fac = g.fac; wa.Z = g.Z; wa.mu = g.mu;
+    wa.rows = K; wa.R = R; wa.per_row = 1;
+    wa.ptype = g.prox.type; wa.p0 = g.prox.p0; wa.p1 = g.prox.p1;
+    wa.max_inner = g.max_inner; wa.tol_pr = g.tol_pr; wa.tol_du = g.tol_du;
+    wa.ctl = ctl; wa.reset = 1;
+    wa.gram = nullptr; wa.facT = nullptr;
+    admm_loop_wg(wa, s);
+    return path;
+  }
+  par2_rho_max(g.rho, K, g.rhomax, s);
+  ctl_reset(ctl, s);
+  if (path == kP2CSingle) {
+    par2_c_rowsolve(g.a, g.rho, g.L, nullptr, nullptr, 0, dall, g.fac, nullptr, s);                       // :236
+    return path;
+  }
+  FinalizeArgs fa;
+  fa.nmodes = 1; fa.max_inner = g.max_inner;
+  fa.tol_pr_coupl = fa.tol_du_coupl = 1e300;            // only the constraint residuals steer this loop (:600)
+  fa.tol_pr_constr = g.tol_pr; fa.tol_du_constr = g.tol_du;
+  fa.slots[0] = g.slots; fa.constrained[0] = 1; fa.coupled[0] = 0;
+  for (int it = 0; it < g.max_inner; ++it) {
+    par2_c_rowsolve(g.a, g.rho, g.L, g.Z, g.mu, 1, dall, g.fac, ctl, s);                                  // :603-606
+    // update_constraint with max(rho) (:1423-1424)
+    constraint_update(g.prox, g.fac, g.Z, g.mu, g.Zold, g.V, K, R, g.rhomax, 1.0, g.prox_ws, g.slots, g.red_ws, ctl, s);
+    admm_finalize_generic(fa, ctl, s);
+  }
+  return path;
+}
+
+// objective pieces -- see par2.h
+void par2_objective(const P2Objective& g, const P2Dims& d, hipStream_t s) {
+  if (g.X) par2_residual(g.X, g.A, g.B, g.Cfac, d, g.res, s);
+  par2_b_gaps(g.B, g.P, g.DeltaB, g.Z, d, g.q, s);
+  if (g.reg_type != AOADMM_C_NONE) par2_reg_values(g.B, g.reg_type, g.eta, d, g.regv, s);
 }
 
 // ---------------------------------------------------------------------------

@@ -222,8 +222,7 @@ void Engine::par2_prepare_modeA(int m, int nrho, const aoadmm_options& opt) {
     par2s_rhs_A(t, mi.tmp.d());
     par2_modeA_csys(mC.fac.d(), b.GB.d(), d, b.Csys.d(), stream_);
   } else {
-    par2_xkb(b.X.d(), mB.fac.d(), d, b.T1.d(), stream_);
-    par2_modeA_combine(b.T1.d(), mC.fac.d(), b.GB.d(), d, mi.tmp.d(), b.Csys.d(), stream_);
+    par2_mode_a(b.X.d(), mB.fac.d(), mC.fac.d(), b.GB.d(), d, b.T1.d(), mi.tmp.d(), b.Csys.d(), stream_);
   }
   if (b.slab_sharded) {                               // sums over this rank's slabs -> sums over all slabs
     allreduce(mi.tmp.d(), mi.rows * mi.R);
@@ -308,67 +307,40 @@ void Engine::par2_update_C(int m, const aoadmm_options& opt) {
   ModeInfo& mA = modes_[t.modes[0]];
   ModeInfo& mB = modes_[t.modes[1]];
   AdmmCtl* ctl = ctl_of_mode(m);
-  if (b.sparse) {                                     // diag(A' X_k B_k) from Y: no pass while A has not moved
-    par2s_ensure_Y(t);
-    par2s_slab_sums(mB.fac.d(), b.sp.Y.d(), d, b.sp.s.d(), nullptr, nullptr, nullptr, nullptr, nullptr, stream_);
-  } else {
-    par2_xkb(b.X.d(), mB.fac.d(), d, b.T1.d(), stream_);
-  }
   const size_t RR = (size_t)b.R * b.R;
   if (b.slab_sharded) {                               // rows of the other ranks arrive through the all-reduce
     AO_HIP(hipMemsetAsync(b.ac.p, 0, (size_t)b.K * b.R * 8, stream_));
     AO_HIP(hipMemsetAsync(b.rhoc.p, 0, (size_t)b.K * 8, stream_));
     AO_HIP(hipMemsetAsync(b.Lc.p, 0, (size_t)b.K * RR * 8, stream_));
   }
-  if (b.sparse)
+  if (b.sparse) {                                     // diag(A' X_k B_k) from Y: no pass while A has not moved
+    par2s_ensure_Y(t);
+    par2s_slab_sums(mB.fac.d(), b.sp.Y.d(), d, b.sp.s.d(), nullptr, nullptr, nullptr, nullptr, nullptr, stream_);
     par2_c_system_pre(b.sp.s.d(), mA.gram.d(), b.GB.d(), t.weight, has_ridge_ ? mi.ridge : 0.0,
                       opt.bsum ? opt.bsum_weight / 2 : 0.0, mi.constrained ? 1 : 0, 0, d, mi.fac.d(), b.ac.d(),
                       b.rhoc.d(), b.Lc.d(), ctl, stream_);
-  else
-    par2_c_system(mA.fac.d(), b.T1.d(), mA.gram.d(), b.GB.d(), t.weight, has_ridge_ ? mi.ridge : 0.0,
-                  opt.bsum ? opt.bsum_weight / 2 : 0.0, mi.constrained ? 1 : 0, 0, d, mi.fac.d(), b.ac.d(), b.rhoc.d(),
-                  b.Lc.d(), ctl, stream_);
+  } else {
+    P2CSys cs;
+    cs.X = b.X.d(); cs.A = mA.fac.d(); cs.B = mB.fac.d(); cs.GA = mA.gram.d(); cs.GB = b.GB.d(); cs.Cfac = mi.fac.d();
+    cs.w = t.weight; cs.ridge = has_ridge_ ? mi.ridge : 0.0; cs.bsum_half = opt.bsum ? opt.bsum_weight / 2 : 0.0;
+    cs.nrho = mi.constrained ? 1 : 0; cs.raw = 0;
+    cs.T1 = b.T1.d(); cs.a = b.ac.d(); cs.rho = b.rhoc.d(); cs.L = b.Lc.d();
+    par2_c_systems(cs, d, ctl, stream_);
+  }
   if (b.slab_sharded) {
     allreduce(b.ac.d(), (int64_t)b.K * b.R);
     allreduce(b.rhoc.d(), b.K);
     allreduce(b.Lc.d(), (int64_t)b.K * RR);
   }
-  const bool wg_loop = mi.constrained && admm_loop_wg_ok(mi.rows, mi.R, mi.prox.type, opt.MaxInnerIters);
-  if (!wg_loop) par2_rho_max(b.rhoc.d(), b.K, b.rhomax.d(), stream_);   // the one-workgroup loop takes max(rho) itself
-  const P2Dims dall = b.dims_all();                   // the K x R row systems are solved on every rank
   t.last_pos = 2;                                                                        // last_m(p) = 3
-  if (wg_loop) {
-    // K <= 256 rows: the K row systems, update_constraint with max(rho) and the loop test in one launch (:602-606)
-    WgLoopU wa;
-    wa.A = b.ac.d(); wa.Binv = nullptr; wa.L = b.Lc.d(); wa.rho = b.rhoc.d(); wa.rho_prox = nullptr;
-    wa.fac = mi.fac.d(); wa.Z = mi.Z.d(); wa.mu = mi.mu.d();
-    wa.rows = mi.rows; wa.R = mi.R; wa.per_row = 1;
-    wa.ptype = mi.prox.type; wa.p0 = mi.prox.p0; wa.p1 = mi.prox.p1;
-    wa.max_inner = opt.MaxInnerIters; wa.tol_pr = opt.innerRelPrTol_constr; wa.tol_du = opt.innerRelDualTol_constr;
-    wa.ctl = ctl; wa.reset = 1;
-    wa.gram = nullptr; wa.facT = nullptr;
-    admm_loop_wg(wa, stream_);
-    mi.version++;
-    return;
-  }
-  ctl_reset(ctl, stream_);
-  if (!mi.constrained) {
-    par2_c_rowsolve(b.ac.d(), b.rhoc.d(), b.Lc.d(), nullptr, nullptr, 0, dall, mi.fac.d(), nullptr, stream_);   // :236
-  } else {
-    double* sl = resid_slots(m);
-    FinalizeArgs fa;
-    fa.nmodes = 1; fa.max_inner = opt.MaxInnerIters;
-    fa.tol_pr_coupl = fa.tol_du_coupl = 1e300;          // only the constraint residuals steer this loop (:600)
-    fa.tol_pr_constr = opt.innerRelPrTol_constr; fa.tol_du_constr = opt.innerRelDualTol_constr;
-    fa.slots[0] = sl; fa.constrained[0] = 1; fa.coupled[0] = 0;
-    for (int it = 0; it < opt.MaxInnerIters; ++it) {
-      par2_c_rowsolve(b.ac.d(), b.rhoc.d(), b.Lc.d(), mi.Z.d(), mi.mu.d(), 1, dall, mi.fac.d(), ctl, stream_);  // :603-606
-      // update_constraint with max(rho) (:1423-1424)
-      constraint_update(mi.prox, mi.fac.d(), mi.Z.d(), mi.mu.d(), mi.Zold.d(), mi.V.d(), mi.rows, mi.R, b.rhomax.d(),
-                        1.0, mi.proxws.d(), sl, redws_.d(), ctl, stream_);
-      admm_finalize_generic(fa, ctl, stream_);
-    }
-  }
+  P2CSolve g;                                         // the K x R row systems are solved on every rank
+  g.a = b.ac.d(); g.rho = b.rhoc.d(); g.L = b.Lc.d();
+  g.fac = mi.fac.d(); g.Z = mi.Z.d(); g.mu = mi.mu.d();
+  g.constrained = mi.constrained; g.prox = mi.prox;
+  g.max_inner = opt.MaxInnerIters; g.tol_pr = opt.innerRelPrTol_constr; g.tol_du = opt.innerRelDualTol_constr;
+  g.rhomax = b.rhomax.d();
+  g.Zold = mi.Zold.d(); g.V = mi.V.d(); g.prox_ws = mi.proxws.d(); g.slots = resid_slots(m); g.red_ws = redws_.d();
+  par2_c_solve(g, b.dims_all(), ctl, stream_);        // single solve, one-workgroup loop or launched loop (par2_c_path)
   mi.version++;
 }
 
@@ -385,19 +357,22 @@ void Engine::par2_prepare_C_coupled(int m, int ctype, const aoadmm_options& opt)
   ModeInfo& mB = modes_[t.modes[1]];
   AdmmCtl* ctl = ctl_of_mode(m);
   const int con = mi.constrained ? 1 : 0;
-  const bool big = ctype == 1 || ctype == 5;          // H*C = ...: one (K*R) x (K*R) system instead of K row systems
+  const P2CCoupledKind ck = par2_c_coupled_kind(ctype, con);
+  const bool big = ck.raw != 0;                       // H*C = ...: one (K*R) x (K*R) system instead of K row systems
   b.rhosum.ensure(64);
   if (b.sparse) {
     par2s_ensure_Y(t);
     par2s_slab_sums(mB.fac.d(), b.sp.Y.d(), d, b.sp.s.d(), nullptr, nullptr, nullptr, nullptr, nullptr, stream_);
     par2_c_system_pre(b.sp.s.d(), mA.gram.d(), b.GB.d(), t.weight, has_ridge_ ? mi.ridge : 0.0,
-                      opt.bsum ? opt.bsum_weight / 2 : 0.0, big ? 0 : (ctype == 2 ? con : 1 + con), big ? 1 : 0, d,
-                      mi.fac.d(), b.ac.d(), b.rhoc.d(), b.Lc.d(), ctl, stream_, ctype == 2 ? mi.HHt.d() : nullptr);
+                      opt.bsum ? opt.bsum_weight / 2 : 0.0, ck.nrho, ck.raw, d, mi.fac.d(), b.ac.d(), b.rhoc.d(),
+                      b.Lc.d(), ctl, stream_, ck.madd ? mi.HHt.d() : nullptr);
   } else {
-    par2_xkb(b.X.d(), mB.fac.d(), d, b.T1.d(), stream_);
-    par2_c_system(mA.fac.d(), b.T1.d(), mA.gram.d(), b.GB.d(), t.weight, has_ridge_ ? mi.ridge : 0.0,
-                  opt.bsum ? opt.bsum_weight / 2 : 0.0, big ? 0 : (ctype == 2 ? con : 1 + con), big ? 1 : 0, d,
-                  mi.fac.d(), b.ac.d(), b.rhoc.d(), b.Lc.d(), ctl, stream_, ctype == 2 ? mi.HHt.d() : nullptr);
+    P2CSys cs;
+    cs.X = b.X.d(); cs.A = mA.fac.d(); cs.B = mB.fac.d(); cs.GA = mA.gram.d(); cs.GB = b.GB.d(); cs.Cfac = mi.fac.d();
+    cs.w = t.weight; cs.ridge = has_ridge_ ? mi.ridge : 0.0; cs.bsum_half = opt.bsum ? opt.bsum_weight / 2 : 0.0;
+    cs.nrho = ck.nrho; cs.raw = ck.raw; cs.Madd = ck.madd ? mi.HHt.d() : nullptr;
+    cs.T1 = b.T1.d(); cs.a = b.ac.d(); cs.rho = b.rhoc.d(); cs.L = b.Lc.d();
+    par2_c_systems(cs, d, ctl, stream_);
   }
   // max(rho) for the prox (:1424); mean(rho) takes the place of the scalar rho of a CP mode (:284, :712), sum(rho)
   // weighs this mode in the Delta update (:736)
@@ -433,15 +408,13 @@ void Engine::par2_prepare_C_coupled(int m, int ctype, const aoadmm_options& opt)
       AO_HIP(hipStreamSynchronize(stream_));          // hth / dd are locals
       b.have_HtH = true;
     }
-    if (b.hth_diag) {
-      // row k: C(k,:) * (B_k + rhoC/2*(d_k [+ 1])*I) = A_inner(k,:); b.Lc holds B_k and is overwritten by the factors
-      par2_c_rowsys_diag(b.Lc.d(), b.HtH.d(), mi.rho.d(), con, b.K, b.R, ctl, stream_);
-    } else {
+    if (!b.hth_diag) {
       AO_REQUIRE(n <= kDenseMaxN, "PARAFAC2 C mode coupled with type %d through a matrix whose H'H is not diagonal: K*R = %d exceeds the dense-system limit %d", ctype, n, kDenseMaxN);
       b.Mbig.ensure((size_t)n * n * 8); b.Minv.ensure((size_t)n * n * 8);
-      par2_c_big_system(b.Lc.d(), b.HtH.d(), mi.rho.d(), con, b.K, b.R, b.Mbig.d(), stream_);
-      dense_spd_inverse(b.Mbig.d(), b.Minv.d(), n, ctl, stream_);
     }
+    par2_c_coupled_big(b.Lc.d(), b.HtH.d(), b.hth_diag, mi.rho.d(), con, b.K, b.R, b.hth_diag ? nullptr : b.Mbig.d(), ctl,
+                       stream_);
+    if (!b.hth_diag) dense_spd_inverse(b.Mbig.d(), b.Minv.d(), n, ctl, stream_);
   }
 }
 
@@ -463,11 +436,13 @@ void Engine::par2_objective_enqueue(TensorInfo& t) {
     // move): no pass of its own unless A moved since Y was formed, and then the next B_k update reuses Y
     par2s_ensure_Y(t);
     par2s_slab_sums(mB.fac.d(), b.sp.Y.d(), d, b.sp.s.d(), b.sp.xn.d(), mC.fac.d(), mA.gram.d(), b.GB.d(), b.res.d(), stream_);
-  } else {
-    par2_residual(b.X.d(), mA.fac.d(), mB.fac.d(), mC.fac.d(), d, b.res.d(), stream_);
   }
-  par2_b_gaps(mB.fac.d(), b.P.d(), b.DeltaB.d(), mB.constrained ? mB.Z.d() : nullptr, d, b.q.d(), stream_);
-  if (regs) par2_reg_values(mB.fac.d(), mB.prox.type, mB.prox.p0, d, b.regv.d(), stream_);
+  P2Objective og;                                     // residual (dense slabs), gaps, reg_func values
+  og.X = b.sparse ? nullptr : b.X.d(); og.A = mA.fac.d(); og.B = mB.fac.d(); og.Cfac = mC.fac.d();
+  og.P = b.P.d(); og.DeltaB = b.DeltaB.d(); og.Z = mB.constrained ? mB.Z.d() : nullptr;
+  og.reg_type = regs ? mB.prox.type : AOADMM_C_NONE; og.eta = mB.prox.p0;
+  og.res = b.res.d(); og.q = b.q.d(); og.regv = b.regv.d();
+  par2_objective(og, d, stream_);
   if (b.slab_sharded) {
     // res[K] carries the not-positive-definite flags of this block's modes, so that a Cholesky failure in one
     // rank's slabs stops every rank (check_not_pd) instead of leaving the others waiting in a collective

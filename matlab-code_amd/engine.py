@@ -586,6 +586,104 @@ class Engine:
                     muZ=unpack(mz) if cid else None, DeltaB=db, rho=rho, L=mats(L), GB=mats(GB), inner_iters=it.value,
                     res=res, path=tuple(path))
 
+    @staticmethod
+    def _par2_pack(who, xs, rows, n, slabs=False):
+        """Slab layout of csrc/par2.h: X_k (n x J_k) or slab-valued factors (J_k x n), column-major, back to back."""
+        if len(xs) != len(rows):
+            raise ValueError('%s: one array per slab' % who)
+        shape = (lambda j: (n, j)) if slabs else (lambda j: (j, n))
+        return np.concatenate([np.asarray(x, dtype=np.float64).reshape(shape(j)).ravel(order='F')
+                               for x, j in zip(xs, rows)])
+
+    def par2_mode_a(self, X, B, Cmat):
+        """Mode A of a dense PARAFAC2 block as the solver runs it (`aoadmm_op_par2_mode_a`, cmtf_fun_AOADMM.m:160-165).
+        X: list of K slabs I x J_k; B: list of K arrays J_k x R; Cmat K x R.  Returns a dict: T1 (K x I x R, X_k B_k),
+        GB (K x R x R), Amt (I x R, unweighted), Csys (R x R), Csys_only (the launch of blocks with sparse slabs) and
+        path = (tile width of the Amt + Csys launch, of the Csys-only launch)."""
+        cm = capi.as_f(Cmat)
+        K, R = cm.shape
+        I = int(np.asarray(X[0]).shape[0])
+        rows = [int(np.asarray(x).shape[1]) for x in X]
+        x, b = self._par2_pack('par2_mode_a', X, rows, I, True), self._par2_pack('par2_mode_a', B, rows, R)
+        if len(rows) != K:
+            raise ValueError('par2_mode_a: C has one row per slab')
+        T1, GB = np.zeros(K * I * R), np.zeros(K * R * R)
+        Amt, Csys, Cso = np.zeros((I, R), order='F'), np.zeros((R, R), order='F'), np.zeros((R, R), order='F')
+        path = (C.c_int * 2)(-1, -1)
+        capi.check(self.lib.aoadmm_op_par2_mode_a(
+            self.h, K, (C.c_int64 * K)(*rows), I, R, capi.dptr(x), capi.dptr(b), capi.dptr(cm), capi.dptr(T1),
+            capi.dptr(GB), capi.dptr(Amt), capi.dptr(Csys), capi.dptr(Cso), path))
+        return dict(T1=T1.reshape(K, R, I).transpose(0, 2, 1).copy(), GB=GB.reshape(K, R, R).transpose(0, 2, 1).copy(),
+                    Amt=Amt, Csys=Csys, Csys_only=Cso, path=tuple(path))
+
+    def par2_mode_c(self, X, A, B, Cmat, weight=1.0, ridge=0.0, bsum_half=0.0, constraint=None, Z=None, mu=None,
+                    max_inner=5, tol=(0.0, 0.0), system=0, sysmat=None):
+        """Mode C of a dense PARAFAC2 block as the solver runs it (`aoadmm_op_par2_mode_c`, cmtf_fun_AOADMM.m:219-248 and
+        the coupled systems :260-312).  X, B: lists of K slabs I x J_k / J_k x R; A I x R; Cmat, Z, mu K x R;
+        constraint: a `Z.constraints` cell or None; tol: (pr_constr, du_constr); system: capi.P2CSYS_* (0: the
+        uncoupled update; 1..4: only the builders of a coupled C mode, sysmat = H*H' (R x R) for 2, the diagonal of H'*H
+        (K) for 3, H'*H (K x K) for 4).  Returns a dict: a (K x R), rho (K), L (K x R x R), rho_max / rho_mean /
+        rho_sum (NaN where the entry does not set them), M ((K R)^2, system 4), C, Z, mu, inner_iters, res (2) and
+        path = (capi.P2C_* or -1, rank class of the row solve)."""
+        A = capi.as_f(A)
+        I, R = A.shape
+        rows = [int(np.asarray(x).shape[1]) for x in X]
+        K = len(rows)
+        if constraint is None:
+            cid, params = 0, np.zeros(0)
+        else:
+            cid, params, Lmat = constraint_descriptor(constraint)
+            if Lmat is not None:
+                raise ValueError('par2_mode_c: quadratic regularization is not available here')
+        x, b = self._par2_pack('par2_mode_c', X, rows, I, True), self._par2_pack('par2_mode_c', B, rows, R)
+        cm = capi.as_f(Cmat).copy(order='F')
+        if cm.shape != (K, R):
+            raise ValueError('par2_mode_c: C must be K x R')
+        z = capi.as_f(Z).copy(order='F') if Z is not None else None
+        m = capi.as_f(mu).copy(order='F') if mu is not None else None
+        sm = capi.as_f(sysmat) if sysmat is not None else None
+        a, rho, L = np.zeros((K, R), order='F'), np.zeros(K), np.zeros(K * R * R)
+        stats = np.full(3, np.nan)
+        M = np.zeros((K * R, K * R), order='F') if system == capi.P2CSYS_DENSE else None
+        it = C.c_int(-1)
+        res = np.zeros(2)
+        path = (C.c_int * 2)(-1, -1)
+        tolv = np.asarray(tol, dtype=np.float64).reshape(2).copy()
+        capi.check(self.lib.aoadmm_op_par2_mode_c(
+            self.h, int(system), K, (C.c_int64 * K)(*rows), I, R, capi.dptr(x), capi.dptr(A), capi.dptr(b),
+            float(weight), float(ridge), float(bsum_half), cid, capi.dptr(params) if params.size else None, params.size,
+            int(max_inner), capi.dptr(tolv), capi.dptr(sm), capi.dptr(cm), capi.dptr(z), capi.dptr(m), capi.dptr(a),
+            capi.dptr(rho), capi.dptr(L), capi.dptr(stats), capi.dptr(M), C.byref(it), capi.dptr(res), path))
+        return dict(a=a, rho=rho, L=L.reshape(K, R, R).transpose(0, 2, 1).copy(), rho_max=float(stats[0]),
+                    rho_mean=float(stats[1]), rho_sum=float(stats[2]), M=M, C=cm, Z=z, mu=m, inner_iters=it.value,
+                    res=res, path=tuple(path))
+
+    def par2_objective(self, X, A, B, Cmat, P, DeltaB, Z=None, reg=None):
+        """Objective pieces of a dense PARAFAC2 block as the solver runs them (`aoadmm_op_par2_objective`,
+        cmtf_fun_AOADMM.m:1262-1264, :1355, :1337, :1279-1281).  X, B, P, Z: lists of K slabs; reg: a `Z.constraints`
+        cell of a regularisation type (its first parameter is eta) or None.  Returns a dict: res (K), q (K x 4),
+        regv (K, None without reg)."""
+        A = capi.as_f(A)
+        I, R = A.shape
+        rows = [int(np.asarray(x).shape[1]) for x in X]
+        K = len(rows)
+        who = 'par2_objective'
+        x, b, p = self._par2_pack(who, X, rows, I, True), self._par2_pack(who, B, rows, R), self._par2_pack(who, P, rows, R)
+        z = self._par2_pack(who, Z, rows, R) if Z is not None else None
+        cm, db = capi.as_f(Cmat), capi.as_f(DeltaB)
+        if cm.shape != (K, R) or db.shape != (R, R):
+            raise ValueError('par2_objective: C must be K x R and DeltaB R x R')
+        rid, eta = 0, 0.0
+        if reg is not None:
+            rid, params, _ = constraint_descriptor(reg)
+            eta = float(params[0]) if params.size else 0.0
+        res, q = np.zeros(K), np.zeros((K, 4))
+        regv = np.zeros(K) if rid else None
+        capi.check(self.lib.aoadmm_op_par2_objective(
+            self.h, K, (C.c_int64 * K)(*rows), I, R, capi.dptr(x), capi.dptr(A), capi.dptr(b), capi.dptr(cm), capi.dptr(p),
+            capi.dptr(db), capi.dptr(z), rid, eta, capi.dptr(res), capi.dptr(q), capi.dptr(regv)))
+        return dict(res=res, q=q, regv=regv)
+
     def coupled_loop(self, coupling, A, Cmat, max_inner, tol):
         """The inner loop of coupling `coupling` (0-based) of the model this engine holds, as the solver runs it behind
         the MTTKRPs (`aoadmm_op_coupled_loop`): systems, the form of the loop the library picks, Gram matrices.  A, Cmat:

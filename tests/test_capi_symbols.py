@@ -65,6 +65,24 @@ def test_em_pass_entry(pkg):
     assert hasattr(pkg.load_library(), 'aoadmm_resident_em_pass') and hasattr(pkg.Engine, 'resident_em_pass')
 
 
+def test_par2_mode_entries_and_their_path_codes(pkg):
+    """aoadmm_op_par2_mode_a / _mode_c / _objective are declared, bound, exported and wrapped, and the AOADMM_P2CSYS_* and
+    AOADMM_P2C_* values are those of the binding."""
+    capi = __import__('importlib').import_module('matlab-code_amd._capi')
+    lib = pkg.load_library()
+    for name, wrapper in (('aoadmm_op_par2_mode_a', 'par2_mode_a'), ('aoadmm_op_par2_mode_c', 'par2_mode_c'),
+                          ('aoadmm_op_par2_objective', 'par2_objective')):
+        assert name in declared_functions() and name in pkg.SYMBOLS and name in capi.SYMBOLS
+        assert hasattr(lib, name) and getattr(lib, name).argtypes is not None and hasattr(pkg.Engine, wrapper)
+    text = open(HEADER).read()
+    ids = {m.group(1): int(m.group(2)) for m in re.finditer(r'AOADMM_P2CSYS_([A-Z]+)\s*=\s*(\d+)', text)}
+    assert ids == dict(UNCOUPLED=capi.P2CSYS_UNCOUPLED, ROWS=capi.P2CSYS_ROWS, HHT=capi.P2CSYS_HHT, DIAG=capi.P2CSYS_DIAG,
+                       DENSE=capi.P2CSYS_DENSE)
+    ids = {m.group(1): int(m.group(2)) for m in re.finditer(r'AOADMM_P2C_([A-Z]+)\s*=\s*(\d+)', text)}
+    assert ids == dict(SINGLE=capi.P2C_SINGLE, WG=capi.P2C_WG, LAUNCHED=capi.P2C_LAUNCHED)
+    assert lib.aoadmm_abi_version() == 3          # functions were added, nothing moved: the version stays
+
+
 def test_no_cpu_fallback(pkg):
     """Without a GPU the product path must fail loudly (never route through the oracle)."""
     lib = pkg.load_library()

@@ -349,6 +349,25 @@ def test_parafac2_larger_ranks(pkg, eng, R, K):
     compare_par2(*run_both(pkg, eng, Z, io, options(MaxOuterIters=6)))
 
 
+@pytest.mark.parametrize('I,R', [pytest.param(67, 31, id='ew16'), pytest.param(5, 3, id='xta-rem1')])
+def test_parafac2_modeA_wide_tile(pkg, eng, I, R):
+    """I = 67, R = 31: I R + R R = 3038 outputs, so par2_modeA_combine_k runs at 16 outputs per workgroup with a ragged
+    last A tile (2077 % 16 = 13) in front of the Csys half (each class alone against fp64: tests/test_gpu_par2_modes.py).
+    I = 5: the remainder loop of par2_xta_k (I % 4) runs once per entry, which no other solve's I (20, 40, 6, 67) does."""
+    from helpers import par2_slabs
+    rng = np.random.default_rng(19)
+    Jk = [35, 45, 38, 41]
+    K = len(Jk)
+    X, _ = par2_slabs(I, Jk, R, rng, 0.2)
+    Z = dict(loss_function=['Frobenius'], model=['PAR2'], modes=[[1, 2, 3]], size=[I, Jk, K],
+             coupling=dict(lin_coupled_modes=[0, 0, 0], coupling_type=[], coupl_trafo_matrices=[None] * 3),
+             constrained_modes=[0, 0, 1], constraints=[None, None, ('non-negativity',)], weights=[1.0], object=[X])
+    distr = [lambda a, b: rng.standard_normal((a, b)), lambda a, b: rng.standard_normal((a, b)),
+             lambda a, b: rng.random((a, b)) + 0.1]
+    io = dict(lambdas_init=[[1] * R], nvecs=0, distr=distr, normalize=1)
+    compare_par2(*run_both(pkg, eng, Z, io, options(MaxOuterIters=3)))
+
+
 @pytest.mark.parametrize('R,Jk', [
     pytest.param(3, [64, 33, 40, 17], id='regs1'),            # longest slab <= 64: one row per lane, folded loop
     pytest.param(3, [129, 256, 200, 131], id='regs4'),        # 129..256: four rows per lane
