@@ -1,72 +1,12 @@
-// ADMM inner-loop kernels and the proximal operator catalogue
-// (functions/cmtf_fun_AOADMM.m:591-623,1420-1429 ; functions/constraints_to_prox.m:13-91).
+// ADMM inner-loop kernels (functions/cmtf_fun_AOADMM.m:591-623,1420-1429); the proximal operators they apply are
+// declared in prox.h.
 #pragma once
-#include <vector>
 #include "common.h"
 #include "small.h"
 #include "loopctl.h"
+#include "prox.h"
 
 namespace aoadmm {
-
-struct ProxSpec {
-  int type = AOADMM_C_NONE;
-  double p0 = 0.0, p1 = 0.0;       // constraint parameters (eta | l,u | nn)
-  // AOADMM_C_QUADRATIC only (device pointers, see QuadPrep): L = U diag(w) U'
-  const double* Lmat = nullptr;
-  const double* LU = nullptr;
-  const double* LUt = nullptr;
-  const double* Lw = nullptr;
-  struct QuadPrep* quad = nullptr; // non-symmetric L: the prox refreshes (2*eta/rho*L + I)^-1 through it when rho moved
-};
-
-// 'quadratic regularization' (constraints_to_prox.m:62-67): prox(x,rho) = (2*eta/rho*L + I) \ x with a fixed
-// user matrix L.  rho changes every outer iteration, L does not: L is diagonalised once on the host
-// (symmetric L required) and the prox becomes U * diag(1/(2*eta/rho*w_i + 1)) * U' * x, two small GEMMs.
-// A non-symmetric L has no orthogonal eigenbasis: whenever 2*eta/rho may have moved (once per outer iteration: rho is
-// fixed inside an inner loop; the engine sets `dirty`) the prox inverts 2*eta/rho*L + I ON THE DEVICE by Gauss-Jordan
-// elimination with row pivoting (what MATLAB's `\` pivots on; admm.hip quad_gj_step_k, rho read from device memory, no
-// host synchronisation) and is then one small GEMM.  The reference factorises the same matrix in EVERY prox call.
-struct QuadPrep {
-  DevBuf L, U, Ut, w;
-  DevBuf Minv, Mwork, piv, pval;   // non-symmetric L: the two buffers the elimination alternates between, pivot rows, pivot value
-  bool nonsym = false;
-  bool dirty = true;               // the cached inverse may belong to another rho
-  const double* key_rho = nullptr; // what the cached inverse was built for
-  double key_mul = 0.0, key_eta = 0.0;
-  const double* result = nullptr;
-  int64_t n = 0;
-  void build(const double* L_host, int64_t rows, hipStream_t s);
-  void attach(ProxSpec& ps) {
-    ps.Lmat = L.d(); ps.LU = U.d(); ps.LUt = Ut.d(); ps.Lw = w.d();
-    ps.quad = nonsym ? this : nullptr;
-  }
-  // (g*L + I)^-1 for g = 2*eta/(rho*rho_mul), column-major n x n on the device; rebuilt when dirty or asked for another rho
-  const double* refresh(double eta, const double* rho_dev, double rho_mul, hipStream_t s);
-};
-
-// iso.hip: workgroup-parallel isotonic / unimodal projections and the path-Laplacian smoothness prox
-// mode 0: non-decreasing, 1: non-increasing, 2: unimodal (nonneg != 0: with projection onto x >= 0)
-size_t iso_ws_bytes(int64_t rows, int R);
-void prox_iso(const double* V, int64_t ldv, double* Z, int64_t ldz, int64_t rows, int R, int mode, double nonneg,
-              double* ws, const AdmmCtl* ctl, hipStream_t s);
-// beyond 4096 rows the reduction runs in `ws` (prox_gl_ws_doubles); false: no workspace (the caller solves sequentially)
-bool prox_gl_pcr(const double* V, int64_t ldv, double* Z, int64_t ldz, int64_t rows, int R, double eta, const double* rho,
-                 double rho_mul, const AdmmCtl* ctl, hipStream_t s, double* ws = nullptr);
-size_t prox_gl_ws_doubles(int64_t rows, int R);
-
-bool prox_is_fusable(int type);
-// constraints with a reg_func entry (constraints_to_prox.m): their value enters f_tensors (cmtf_fun_AOADMM.m:1272-1288)
-inline bool prox_has_reg_value(int t) {
-  return t == AOADMM_C_L1_REG || t == AOADMM_C_L0_REG || t == AOADMM_C_L2_REG || t == AOADMM_C_RIDGE ||
-         t == AOADMM_C_GL_SMOOTH || t == AOADMM_C_TV || t == AOADMM_C_QUADRATIC;
-}     // element-wise or row-wise: folded into the primal kernel
-size_t prox_ws_bytes(int type, int64_t rows, int R);
-
-// Z_out = prox(V, rho) for any catalogue entry; rho read from device memory.
-void prox_apply(const ProxSpec& ps, const double* V, int64_t ldv, double* Zout, int64_t ldz,
-                int64_t rows, int R, const double* rho_dev, double rho_mul, double* ws,
-                const AdmmCtl* ctl, hipStream_t s, const double* warm = nullptr, int64_t ldw = 0);
-// `warm`: optional previous value of the prox output (same shape); only a speed hint (TV warm start)
 
 // The whole ADMM_constrained_only loop (:596-622) for a CP mode, enqueued without host synchronisation:
 //   element-wise prox, up to 4096 rows and 10 inner iterations : two launches for the whole loop (admm_rows_mfma_k);
@@ -96,11 +36,12 @@ struct GramFold {
   double* At = nullptr;
   int nb = 0;
 };
-// Which kernels run the loop of one constrained CP mode.  Decided from the inputs alone, in one place: the solver,
-// admm_constrained_loop and the op-level entry (capi.hip aoadmm_op_admm_mode) all branch on admm_path().  The values
-// are part of the C ABI (include/aoadmm_hip.h AOADMM_PATH_*).
+// Which kernels run the loop of one constrained CP mode.  Decided from the inputs alone, in one place: admm_mode_update
+// and admm_constrained_loop branch on admm_path(); the solver and the op-level entry (capi.hip aoadmm_op_admm_mode) call
+// admm_mode_update and only report what it returns.  The values are part of the C ABI (include/aoadmm_hip.h
+// AOADMM_PATH_*).
 enum AdmmPath {
-  kAdmmPathWg = 0,          // admm_loop_wg_k: the whole loop in one workgroup (caller runs admm_loop_wg)
+  kAdmmPathWg = 0,          // admm_loop_wg_k: the whole loop in one workgroup (admm_loop_wg)
   kAdmmPathMfma = 1,        // admm_rows_mfma_k: the two-launch speculative loop
   kAdmmPathRowsFused = 2,   // admm_rows_k with the element-/row-wise prox inside
   kAdmmPathRowsColProx = 3, // admm_rows_k -> prox_apply -> dual_update_k
@@ -140,6 +81,15 @@ struct WgLoopU {
 };
 bool admm_loop_wg_ok(int64_t rows, int R, int ptype, int max_inner);
 void admm_loop_wg(const WgLoopU& a, hipStream_t s);
+
+// One constrained CP mode's update from the system on, as the solver runs it: the loop on the path admm_path() names
+// (admm_loop_wg or admm_constrained_loop), then whatever that path still owes.  Every path leaves fac'*fac in `gram`
+// (R x R) and the row-major copy of fac in `facT` (rows x R) and has closed the loop in `ctl`.  `gram_ws` holds
+// admm_mode_ws_bytes(); `part`, `V`, `Znew`, `prox_ws` as for admm_constrained_loop.  Returns the path taken.
+size_t admm_mode_ws_bytes(int64_t rows, int R);
+AdmmPath admm_mode_update(const AdmmMode& m, double* part, double* V, double* Znew, double* prox_ws,
+                          double* gram, double* facT, double* gram_ws,
+                          AdmmCtl* ctl, int max_inner, double tol_pr, double tol_du, hipStream_t s);
 
 // generic pieces for the coupled / PARAFAC2 loops -------------------------------
 // (Z,mu) <- update_constraint (:1420-1429): Zold kept in `Zold`; slots[0..3] receive

@@ -636,6 +636,19 @@ static void d2h(double* h, const DevBuf& b, int64_t n, hipStream_t s) {
   AO_HIP(hipMemcpyAsync(h, b.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
   AO_HIP(hipStreamSynchronize(s));
 }
+// a zeroed loop-control record on the device; and what the kernels left in it, once the stream has drained
+static AdmmCtl* ctl_new(DevBuf& b, hipStream_t s) {
+  b.alloc(sizeof(AdmmCtl));
+  AO_HIP(hipMemsetAsync(b.p, 0, sizeof(AdmmCtl), s));
+  return b.as<AdmmCtl>();
+}
+static AdmmCtl ctl_fetch(const DevBuf& b, hipStream_t s) {
+  AdmmCtl h;
+  AO_HIP(hipMemcpyAsync(&h, b.p, sizeof h, hipMemcpyDeviceToHost, s));
+  AO_HIP(hipStreamSynchronize(s));
+  if (h.notpd) throw Error(AOADMM_ERR_NOT_PD, "Matrix must be positive definite.");
+  return h;
+}
 
 int aoadmm_op_mttkrp(aoadmm_ctx* ctx, const double* X, int ndims, const int64_t* dims, const double* const* U, int R,
                      int n, int precision, double* out) {
@@ -735,14 +748,10 @@ int aoadmm_op_chol(aoadmm_ctx* ctx, const double* B, int R, double* L) {
     DevBuf b, l, c;
     h2d(b, B, (int64_t)R * R, e.stream());
     l.alloc((size_t)R * R * 8);
-    c.alloc(sizeof(AdmmCtl));
-    AO_HIP(hipMemsetAsync(c.p, 0, sizeof(AdmmCtl), e.stream()));
+    ctl_new(c, e.stream());
     AO_HIP(hipMemsetAsync(l.p, 0, (size_t)R * R * 8, e.stream()));
     chol_only(l.d(), b.d(), R, c.as<AdmmCtl>(), e.stream());
-    AdmmCtl h;
-    AO_HIP(hipMemcpyAsync(&h, c.p, sizeof h, hipMemcpyDeviceToHost, e.stream()));
-    AO_HIP(hipStreamSynchronize(e.stream()));
-    if (h.notpd) throw Error(AOADMM_ERR_NOT_PD, "Matrix must be positive definite.");
+    (void)ctl_fetch(c, e.stream());
     d2h(L, l, (int64_t)R * R, e.stream());
   });
 }
@@ -792,8 +801,7 @@ int aoadmm_op_admm_constrained(aoadmm_ctx* ctx, const double* A, const double* B
     part.alloc((size_t)admm_partials(rows) * 4 * 8 + 2048);
     V.alloc((size_t)rows * R * 8); Zn.alloc((size_t)rows * R * 8);
     ws.alloc(prox_ws_bytes(constraint, rows, R));
-    ctl.alloc(sizeof(AdmmCtl));
-    AO_HIP(hipMemsetAsync(ctl.p, 0, sizeof(AdmmCtl), s));
+    ctl_new(ctl, s);
     // B + rho/2*I and its Cholesky (cmtf_fun_AOADMM.m:141-142): feed sys_build with C = Bsys, w = 1
     // but keep the caller's rho: do it by hand
     std::vector<double> Bh(Bsys, Bsys + (size_t)R * R);
@@ -810,18 +818,15 @@ int aoadmm_op_admm_constrained(aoadmm_ctx* ctx, const double* A, const double* B
     QuadPrep qp;
     if (constraint == AOADMM_C_QUADRATIC) { qp.build(Lmat, rows, s); qp.attach(am.prox); }
     admm_constrained_loop(am, part.d(), V.d(), Zn.d(), ws.d(), ctl.as<AdmmCtl>(), max_inner, tol_pr, tol_du, s);
-    AdmmCtl h;
-    AO_HIP(hipMemcpyAsync(&h, ctl.p, sizeof h, hipMemcpyDeviceToHost, s));
-    AO_HIP(hipStreamSynchronize(s));
-    if (h.notpd) throw Error(AOADMM_ERR_NOT_PD, "Matrix must be positive definite.");
+    const AdmmCtl h = ctl_fetch(ctl, s);
     if (inner_iters) *inner_iters = h.iters;
     d2h(fac, f, rows * R, s); d2h(Z, z, rows * R, s); d2h(mu, m, rows * R, s);
   });
 }
 
 // One mode's ADMM update as Engine::update_uncoupled_cp_mode runs it for a constrained mode: the system from sys_build
-// (rho, L, inv(L*L')), the path from admm_path(), the Gram matrix and row-major copy from whichever kernel the solver
-// takes them from on that path.
+// (rho, L, inv(L*L')), then the solver's own step (admm_mode_update): the loop on the path admm_path() names, the Gram
+// matrix and the row-major copy.
 int aoadmm_op_admm_mode(aoadmm_ctx* ctx, const double* A, const double* Cmat, int constraint, const double* params,
                         int n_params, const double* Lmat, int64_t rows, int R, int max_inner, double tol_pr,
                         double tol_du, double* fac, double* Z, double* mu, int* inner_iters, double* res,
@@ -842,11 +847,8 @@ int aoadmm_op_admm_mode(aoadmm_ctx* ctx, const double* A, const double* Cmat, in
     V.alloc((size_t)nR * 8); Zn.alloc((size_t)nR * 8);
     ws.alloc(prox_ws_bytes(constraint, rows, R));
     g.alloc((size_t)RR * 8); ft.alloc((size_t)nR * 8);
-    const size_t fold = (size_t)cdiv(rows, 16) * RR * 8, atb = atb_ws_bytes(rows, R, R);
-    aws.alloc(fold > atb ? fold : atb);
-    ctl.alloc(sizeof(AdmmCtl));
-    AO_HIP(hipMemsetAsync(ctl.p, 0, sizeof(AdmmCtl), s));
-    AdmmCtl* c = ctl.as<AdmmCtl>();
+    aws.alloc(admm_mode_ws_bytes(rows, R));
+    AdmmCtl* c = ctl_new(ctl, s);
     SysBuild sb;                                     // prepare_mode_system with the Hadamard product given
     sb.ngram = 0; sb.Cpre = cpre.d(); sb.w = 1.0; sb.ridge = 0.0; sb.bsum_half = 0.0; sb.rho_scale = 1.0;
     sb.nrho = 1; sb.R = R;
@@ -855,33 +857,13 @@ int aoadmm_op_admm_mode(aoadmm_ctx* ctx, const double* A, const double* Cmat, in
     ProxSpec ps = make_spec(constraint, params, n_params);
     QuadPrep qp;
     if (constraint == AOADMM_C_QUADRATIC) { qp.build(Lmat, rows, s); qp.attach(ps); }
-    const AdmmPath ap = admm_path(rows, R, constraint, max_inner, true, ws.d() != nullptr);
-    if (ap == kAdmmPathWg) {
-      WgLoopU wa;
-      wa.A = a.d(); wa.Binv = bi.d(); wa.L = l.d(); wa.rho = rh.d(); wa.rho_prox = rh.d();
-      wa.fac = f.d(); wa.Z = z.d(); wa.mu = m.d();
-      wa.rows = rows; wa.R = R; wa.per_row = 0;
-      wa.ptype = ps.type; wa.p0 = ps.p0; wa.p1 = ps.p1;
-      wa.max_inner = max_inner; wa.tol_pr = tol_pr; wa.tol_du = tol_du;
-      wa.ctl = c;
-      wa.gram = g.d(); wa.facT = ft.d();
-      admm_loop_wg(wa, s);
-    } else {
-      AdmmMode am;
-      am.A = a.d(); am.L = l.d(); am.Binv = bi.d(); am.rho = rh.d();
-      am.fac = f.d(); am.Z = z.d(); am.mu = m.d();
-      am.rows = rows; am.R = R; am.prox = ps;
-      LoopEnd le;
-      GramFold gf;
-      gf.ws = aws.d(); gf.At = ft.d();
-      admm_constrained_loop(am, part.d(), V.d(), Zn.d(), ws.d(), c, max_inner, tol_pr, tol_du, s, &le, &gf);
-      if (gf.nb > 0) atb_fin(g.d(), aws.d(), gf.nb, R * R, nullptr, s);
-      else atb_small(g.d(), f.d(), rows, f.d(), rows, rows, R, R, aws.d(), nullptr, s, ft.d(), le.ctl ? &le : nullptr);
-    }
-    AdmmCtl h;
-    AO_HIP(hipMemcpyAsync(&h, ctl.p, sizeof h, hipMemcpyDeviceToHost, s));
-    AO_HIP(hipStreamSynchronize(s));
-    if (h.notpd) throw Error(AOADMM_ERR_NOT_PD, "Matrix must be positive definite.");
+    AdmmMode am;
+    am.A = a.d(); am.L = l.d(); am.Binv = bi.d(); am.rho = rh.d();
+    am.fac = f.d(); am.Z = z.d(); am.mu = m.d();
+    am.rows = rows; am.R = R; am.prox = ps;
+    const AdmmPath ap = admm_mode_update(am, part.d(), V.d(), Zn.d(), ws.d(), g.d(), ft.d(), aws.d(), c, max_inner,
+                                         tol_pr, tol_du, s);
+    const AdmmCtl h = ctl_fetch(ctl, s);
     if (inner_iters) *inner_iters = h.iters;
     if (res) { res[0] = h.res[1]; res[1] = h.res[3]; }
     if (path) *path = (int)ap;
@@ -937,8 +919,7 @@ int aoadmm_op_par2_b_loop(aoadmm_ctx* ctx, int K, const int64_t* rows_k, int R, 
       zold.alloc((size_t)n * 8); v.alloc((size_t)n * 8);
       ws.alloc(prox_ws_bytes(constraint, jmax, R));
     }
-    ctl.alloc(sizeof(AdmmCtl));
-    AO_HIP(hipMemsetAsync(ctl.p, 0, sizeof(AdmmCtl), s));
+    ctl_new(ctl, s);
     P2Dims d;
     d.K = K; d.I = 0; d.R = R; d.off = offd.as<int64_t>(); d.off_h = off.data();
     d.Jtot = off[K]; d.Jmax = (int)jmax; d.k0 = 0; d.k1 = K;
@@ -956,10 +937,7 @@ int aoadmm_op_par2_b_loop(aoadmm_ctx* ctx, int K, const int64_t* rows_k, int R, 
     g.GB = gb.d();
     const P2BPath bp = par2_b_path(d, constr, false);
     par2_b_loop(g, d, ctl.as<AdmmCtl>(), s);
-    AdmmCtl h;
-    AO_HIP(hipMemcpyAsync(&h, ctl.p, sizeof h, hipMemcpyDeviceToHost, s));
-    AO_HIP(hipStreamSynchronize(s));
-    if (h.notpd) throw Error(AOADMM_ERR_NOT_PD, "Matrix must be positive definite.");
+    const AdmmCtl h = ctl_fetch(ctl, s);
     if (inner_iters) *inner_iters = h.iters;
     if (res) for (int i = 0; i < 4; ++i) res[i] = h.res[i];
     if (path) { path[0] = bp.folded; path[1] = bp.slab; path[2] = bp.in_lds; path[3] = bp.dual_fold; }
@@ -1059,9 +1037,7 @@ int aoadmm_op_par2_mode_c(aoadmm_ctx* ctx, int system, int K, const int64_t* row
     ac.alloc((size_t)KR * 8); rh.alloc((size_t)K * 8); l.alloc((size_t)K * RR * 8); rst.alloc(64);
     AO_HIP(hipMemsetAsync(l.p, 0, (size_t)K * RR * 8, s));
     aws.alloc(atb_ws_bytes(I, R, R));
-    ctl.alloc(sizeof(AdmmCtl));
-    AO_HIP(hipMemsetAsync(ctl.p, 0, sizeof(AdmmCtl), s));
-    AdmmCtl* c = ctl.as<AdmmCtl>();
+    AdmmCtl* c = ctl_new(ctl, s);
     atb_small(ga.d(), af.d(), I, af.d(), I, I, R, R, aws.d(), nullptr, s);     // A'A as the A update leaves it (:148)
     par2_gram(bf.d(), d, gb.d(), s);                                           // B_k'B_k as the B_k update leaves them
     P2CSys cs;
@@ -1099,10 +1075,7 @@ int aoadmm_op_par2_mode_c(aoadmm_ctx* ctx, int system, int K, const int64_t* row
         par2_c_coupled_big(l.d(), sm.d(), diag, rst.d() + 1, constr ? 1 : 0, K, R, diag ? nullptr : mbig.d(), c, s);
       }
     }
-    AdmmCtl h;
-    AO_HIP(hipMemcpyAsync(&h, ctl.p, sizeof h, hipMemcpyDeviceToHost, s));
-    AO_HIP(hipStreamSynchronize(s));
-    if (h.notpd) throw Error(AOADMM_ERR_NOT_PD, "Matrix must be positive definite.");
+    const AdmmCtl h = ctl_fetch(ctl, s);
     if (inner_iters) *inner_iters = h.iters;
     if (res) { res[0] = h.res[1]; res[1] = h.res[3]; }
     if (path) { path[0] = pth; path[1] = par2_c_rowsolve_class(R); }

@@ -21,13 +21,10 @@
 // criterion pairs the left prefix 1..i with the right prefix of length n-i+1 for i >= 2 and uses the right fit alone
 // for i = 1 (:22-26), the first minimum wins (ties up to the rounding of the error sums: see prox_iso_k), the right part is rebuilt with length n-i (:16), and with
 // non-negativity a prefix whose last level is negative gets the error sum_{t < i-1} s_t^2 (:70, one term short).
-#include "admm.h"
+#include "prox.h"
 #include "device_utils.h"
 
 namespace aoadmm {
-
-#define CTL_GUARD(ctl) \
-  if ((ctl) != nullptr && (ctl)->active == 0) return;
 
 // bytes of scratch per column: 6 double arrays, 4 int arrays, 3 byte arrays of n + 1 entries
 __host__ __device__ inline size_t iso_col_bytes(int64_t n) {

@@ -1,8 +1,12 @@
-// Device-side loop control of the ADMM inner loops, shared by the kernels that evaluate it (admm.hip) and the
-// Gram kernel that closes a loop (small.hip).
+// Device-side loop control of the ADMM inner loops, shared by the kernels that evaluate it (admm.hip), the
+// Gram kernel that closes a loop (small.hip) and every kernel that is enqueued behind a loop's control record.
 #pragma once
 #include "small.h"
 #include "device_utils.h"
+
+// first statement of a kernel enqueued inside a loop: nothing to do once the loop's record is no longer active
+#define CTL_GUARD(ctl) \
+  if ((ctl) != nullptr && (ctl)->active == 0) return;
 
 namespace aoadmm {
 

@@ -5,9 +5,6 @@
 
 namespace aoadmm {
 
-#define CTL_GUARD(ctl) \
-  if ((ctl) != nullptr && (ctl)->active == 0) return;
-
 static constexpr int kP2Threads = 64;
 
 // ---------------------------------------------------------------------------

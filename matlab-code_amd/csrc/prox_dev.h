@@ -1,10 +1,22 @@
 // Device-side pieces of the element-wise / row-wise proximal operators (functions/constraints_to_prox.m), shared by
-// the ADMM kernels of admm.hip and the one-workgroup coupled loop of solver.hip.
+// the prox kernels of prox.hip, the ADMM kernels of admm.hip and the one-workgroup coupled loop of solver.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/aoadmm_hip.h"
 
 namespace aoadmm {
+
+// parameter record of the prox kernels (prox.hip; admm.hip constraint_update_rows_k takes it as well)
+struct ColArgs {
+  const double* V;
+  double* Z;
+  int64_t ldv, ldz, rows;
+  int R, type;
+  double p0, p1;
+  const double* rho;
+  double rho_mul;
+  double* ws;
+};
 
 __device__ __forceinline__ double prox_elem(int type, double v, double p0, double p1, double rho) {
   switch (type) {

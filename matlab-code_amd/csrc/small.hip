@@ -8,9 +8,6 @@
 
 namespace aoadmm {
 
-#define CTL_GUARD(ctl) \
-  if ((ctl) != nullptr && (ctl)->active == 0) return;
-
 __device__ __forceinline__ double coef_val(const Coef& c) { return c.dev ? c.mul * (*c.dev) : c.mul; }
 
 // ---------------------------------------------------------------------------

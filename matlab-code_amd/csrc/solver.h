@@ -316,7 +316,7 @@ class Engine {
   std::vector<SnapSeg> best_state_segments() const;   // every array aoadmm_state_get can return, as (src, bytes, start)
   void best_build_table();                         // solve_setup: the segment table and the kept buffer of this solve
   void best_snapshot(int iter);                    // record_iteration: the state of iteration `iter` into the kept buffer
-  void compute_gram(ModeInfo& mi, const LoopEnd* close = nullptr);
+  void compute_gram(ModeInfo& mi);
   FactorRef factor_ref(const ModeInfo& o) const {
     return FactorRef{o.fac.d(), o.rows, o.version, o.facT_version == o.version ? o.facT.d() : nullptr};
   }

@@ -54,15 +54,17 @@ void Engine::ensure_mode_work(ModeInfo& mi) {
   mi.Zold.ensure(nR); mi.V.ensure(nR); mi.Znew.ensure(nR); mi.RHS.ensure(nR); mi.TD.ensure(nR); mi.tmp.ensure(nR);
   mi.part.ensure((size_t)admm_partials(mi.rows) * 4 * sizeof(double));
   if (mi.constrained) mi.proxws.ensure(prox_ws_bytes(mi.prox.type, mi.rows, mi.R));
-  atbws_.ensure(atb_ws_bytes(mi.rows, mi.R, mi.R));
+  mi.facT.ensure(nR);
+  atbws_.ensure(admm_mode_ws_bytes(mi.rows, mi.R));    // covers atb_ws_bytes: the Gram kernel and the loop's fold partials
 }
 
 // Gram of the current factor (:66, :148); the same kernel leaves a row-major copy of the factor for the T
-// reductions and closes the ADMM loop that produced the factor.  Call BEFORE bumping mi.version.
-void Engine::compute_gram(ModeInfo& mi, const LoopEnd* close) {
+// reductions, recorded as belonging to the factor's current version.  (A constrained CP mode gets both from
+// admm_mode_update, whose last kernel also closes the mode's ADMM loop.)
+void Engine::compute_gram(ModeInfo& mi) {
   mi.facT.ensure((size_t)mi.rows * mi.R * sizeof(double));
   atb_small(mi.gram.d(), mi.fac.d(), mi.rows, mi.fac.d(), mi.rows, mi.rows, mi.R, mi.R, atbws_.d(), nullptr, stream_,
-            mi.facT.d(), close);
+            mi.facT.d());
   mi.facT_version = mi.version;
 }
 
@@ -155,45 +157,22 @@ void Engine::update_uncoupled_cp_mode(int m, const aoadmm_options& opt) {
   ModeInfo& mi = modes_[m];
   if (prepared_mode_ == m) prepared_mode_ = -1;     // MTTKRP and system were enqueued at the end of the last iteration
   else prepare_mode_system(m, mi.constrained ? 1 : 0, opt);
-  AdmmCtl* ctl = ctl_of_mode(m);
-  LoopEnd le;
-  GramFold gf;
   if (!mi.constrained) {
     // G.fac{m} = A{m}/B{m}  (:134): B is symmetric positive definite -> Cholesky solve
     row_solve(mi.fac.d(), mi.rows, mi.Aeff, mi.rows, mi.L.d(), mi.rows, mi.R, nullptr, stream_);
-  } else if (admm_path(mi.rows, mi.R, mi.prox.type, opt.MaxInnerIters, true, mi.proxws.d() != nullptr) == kAdmmPathWg) {
-    // short mode: loop, Gram matrix and row-major copy in one launch of one workgroup
-    WgLoopU wa;
-    wa.A = mi.Aeff; wa.Binv = mi.Binv.d(); wa.L = mi.L.d(); wa.rho = mi.rho.d(); wa.rho_prox = mi.rho.d();
-    wa.fac = mi.fac.d(); wa.Z = mi.Z.d(); wa.mu = mi.mu.d();
-    wa.rows = mi.rows; wa.R = mi.R; wa.per_row = 0;
-    wa.ptype = mi.prox.type; wa.p0 = mi.prox.p0; wa.p1 = mi.prox.p1;
-    wa.max_inner = opt.MaxInnerIters; wa.tol_pr = opt.innerRelPrTol_constr; wa.tol_du = opt.innerRelDualTol_constr;
-    wa.ctl = ctl;
-    mi.facT.ensure((size_t)mi.rows * mi.R * sizeof(double));
-    wa.gram = mi.gram.d(); wa.facT = mi.facT.d();
-    admm_loop_wg(wa, stream_);
     mi.version++;
-    mi.facT_version = mi.version;
+    compute_gram(mi);                                                           // :148
     return;
-  } else {
-    AdmmMode am;
-    am.A = mi.Aeff; am.L = mi.L.d(); am.Binv = mi.Binv.d(); am.rho = mi.rho.d();
-    am.fac = mi.fac.d(); am.Z = mi.Z.d(); am.mu = mi.mu.d();
-    am.rows = mi.rows; am.R = mi.R; am.prox = mi.prox;
-    mi.facT.ensure((size_t)mi.rows * mi.R * sizeof(double));
-    atbws_.ensure((size_t)cdiv(mi.rows, 16) * mi.R * mi.R * sizeof(double));
-    gf.ws = atbws_.d(); gf.At = mi.facT.d();
-    admm_constrained_loop(am, mi.part.d(), mi.V.d(), mi.Znew.d(), mi.proxws.d(), ctl, opt.MaxInnerIters,
-                          opt.innerRelPrTol_constr, opt.innerRelDualTol_constr, stream_, &le, &gf);
   }
+  // the ADMM loop on the path admm_path() names, the Gram matrix (:148) and the row-major copy
+  AdmmMode am;
+  am.A = mi.Aeff; am.L = mi.L.d(); am.Binv = mi.Binv.d(); am.rho = mi.rho.d();
+  am.fac = mi.fac.d(); am.Z = mi.Z.d(); am.mu = mi.mu.d();
+  am.rows = mi.rows; am.R = mi.R; am.prox = mi.prox;
+  admm_mode_update(am, mi.part.d(), mi.V.d(), mi.Znew.d(), mi.proxws.d(), mi.gram.d(), mi.facT.d(), atbws_.d(),
+                   ctl_of_mode(m), opt.MaxInnerIters, opt.innerRelPrTol_constr, opt.innerRelDualTol_constr, stream_);
   mi.version++;
-  if (gf.nb > 0) {                                                            // :148, partials left by the loop's last launch
-    atb_fin(mi.gram.d(), atbws_.d(), gf.nb, mi.R * mi.R, nullptr, stream_);
-    mi.facT_version = mi.version;
-  } else {
-    compute_gram(mi, le.ctl ? &le : nullptr);                                 // :148
-  }
+  mi.facT_version = mi.version;
 }
 
 static bool stop_one(double f, double fo, const aoadmm_options& o) {
