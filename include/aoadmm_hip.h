@@ -477,6 +477,34 @@ int aoadmm_resident_topk(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const int
 int aoadmm_resident_topk_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const double* W, int k, const int64_t* excl_off,
                            const int64_t* excl_idx, int64_t* idx, double* val);
 
+/* ---- ranks of held-out entries -------------------- */
+/* Where a known row stands among the candidates of aoadmm_resident_topk: the integer that hit-rate@k, NDCG@k, MRR and
+ * AUC follow from.  subs is column-major nq x n_tensor_modes, 0-based, as for aoadmm_resident_topk, except that column
+ * `mode` IS read and range-checked: it holds the target row t_q.  w_q and score_q(i) are those of aoadmm_resident_topk
+ * bit for bit (the same products, the same chain of MFMAs).  The candidates of q are the rows whose score is not NaN
+ * and that are not in q's exclusion list -- and, unlike top-k, the target itself whenever its score is not NaN: listing
+ * it is ignored, so the stored rows of the whole tensor can be passed as they are.
+ *   score[q] = score_q(t_q)
+ *   rank[q]  = the number of candidates c != t_q with score_q(c) > score[q], or score_q(c) == score[q] and c < t_q: the
+ *              0-based place of t_q in top-k's total order; -1 when score[q] is NaN
+ *   ncand[q] = the number of candidates, also when rank[q] = -1 (ncand may be NULL)
+ * excl_off / excl_idx follow top-k's rules (any order, repeats allowed -- a repeated row counts once --, NULL: none).
+ * nq = 0 does nothing.  AOADMM_ERR_INVALID, with every output untouched, for: p or mode outside the model, nq < 0 or
+ * nq >= 2^31, a subscript or an excluded row out of range, offsets that do not start at 0 or decrease, NULL rank or
+ * score.  AOADMM_ERR_UNSUPPORTED for a PARAFAC2 block and on a multi-device context (aoadmm_create_multi with more than
+ * one device).  Like aoadmm_resident_topk it reads factors only: the same answer for every kind of block, no
+ * collective, the ranks of a communicator may ask different queries.  The I_mode x nq score array never exists: device
+ * workspace 8 nq R + 8 nq + 8 nq_pad slabs bytes and 8 bytes per 1024 excluded rows.  Integer counts of scores whose
+ * summation order depends on R alone: the answer's bits are a function of the inputs only. */
+int aoadmm_resident_rank_of(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const int64_t* subs, const int64_t* excl_off,
+                            const int64_t* excl_idx, int64_t* rank, double* score, int64_t* ncand_or_null);
+/* aoadmm_resident_rank_of with the weights given: W is nq x R column-major, row q is w_q, uploaded as it is, and
+ * targets[q] in [0, I_mode) is t_q (out of range: AOADMM_ERR_INVALID).  This is how a row that aoadmm_resident_fold_in
+ * returned is ranked; see aoadmm_resident_topk_w for the weights of a block of higher order. */
+int aoadmm_resident_rank_of_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const double* W, const int64_t* targets,
+                              const int64_t* excl_off, const int64_t* excl_idx, int64_t* rank, double* score,
+                              int64_t* ncand_or_null);
+
 /* ---- fold-in of new rows -------------------------- */
 /* The factor rows of nq NEW indices ("queries": a new user, document, sample) along mode `mode` (0-based position in
  * the block) of CP block p, from their entries, with every other factor of the current AOADMM_F_FAC state held fixed:
@@ -576,7 +604,10 @@ int aoadmm_resident_par2_rhs(aoadmm_ctx* ctx, int p, int tensor_mode, double* ou
  * of every objective evaluation of a solve with a list attached: one launch each; bytes = subscripts and values streamed
  * + factor rows gathered, flops = n * R * N + 8 n for the sums); which = 13: aoadmm_resident_topk (one launch per call:
  * its weights, scores-and-selection and merge kernels inside one event pair; bytes = F_mode streamed once per query tile
- * + rows gathered + the answer, flops = 2 * I_mode * nq * R); which = 14: aoadmm_resident_fold_in (one launch per call: its
+ * + rows gathered + the answer, flops = 2 * I_mode * nq * R) and aoadmm_resident_rank_of / _w (one launch per call: every
+ * kernel of the call inside one event pair; bytes = F_mode streamed once per query tile + the rows gathered for the
+ * weights, the targets and the excluded rows + the answer, flops = 2 * I_mode * nq * R + 2 * R * (excluded rows after
+ * repeats are dropped + nq)); which = 14: aoadmm_resident_fold_in (one launch per call: its
  * kernels inside one event pair; bytes = the list streamed + rows gathered + the outputs, flops = nobs * (R (R + 1) +
  * 2 R (N - 1)) + nq * (R^3 / 3 + 2 R^2) for the solves; aoadmm_resident_fold_in_w counts in the same class: with a weight
  * list 8 nobs bytes more, and with alpha > 0 the factor rows read for H, 8 R sum_{m != mode} I_m bytes, and its

@@ -71,7 +71,7 @@ SYMBOLS = [
     'aoadmm_tensor_set_observed_only', 'aoadmm_tensor_set_entry_weights', 'aoadmm_resident_em_step', 'aoadmm_resident_em_pass',
     'aoadmm_resident_model_at', 'aoadmm_tensor_set_heldout', 'aoadmm_resident_heldout_stats', 'aoadmm_heldout_info', 'aoadmm_heldout_trace',
     'aoadmm_heldout_keep_best', 'aoadmm_heldout_restore_best', 'aoadmm_heldout_best_info', 'aoadmm_resident_topk',
-    'aoadmm_resident_topk_w', 'aoadmm_resident_fold_in', 'aoadmm_resident_fold_in_w',
+    'aoadmm_resident_topk_w', 'aoadmm_resident_rank_of', 'aoadmm_resident_rank_of_w', 'aoadmm_resident_fold_in', 'aoadmm_resident_fold_in_w',
     'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_resident_par2_rhs', 'aoadmm_kernel_stats',
     'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_resident_nvecs', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
     'aoadmm_op_admm_mode', 'aoadmm_op_par2_b_loop', 'aoadmm_op_coupled_loop',
@@ -198,6 +198,10 @@ def load_library():
     lib.aoadmm_resident_topk.argtypes = [vp, C.c_int, C.c_int, i64, C.POINTER(i64), C.c_int, C.POINTER(i64), C.POINTER(i64),
                                          C.POINTER(i64), dp]
     lib.aoadmm_resident_topk_w.argtypes = [vp, C.c_int, C.c_int, i64, dp, C.c_int, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), dp]
+    lib.aoadmm_resident_rank_of.argtypes = [vp, C.c_int, C.c_int, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), dp,
+                                            C.POINTER(i64)]
+    lib.aoadmm_resident_rank_of_w.argtypes = [vp, C.c_int, C.c_int, i64, dp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
+                                              dp, C.POINTER(i64)]
     lib.aoadmm_resident_fold_in.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.POINTER(i64), dp, C.POINTER(FoldinOptions), dp,
                                             C.POINTER(C.c_int), C.POINTER(C.c_int), dp, dp]
     lib.aoadmm_resident_fold_in_w.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.POINTER(i64), dp, dp, C.c_double, C.POINTER(FoldinOptions),

@@ -535,6 +535,22 @@ int aoadmm_resident_topk_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const d
     ctx->eng->topk_w(p, mode, nq, W, k, excl_off, excl_idx, idx, val);
   });
 }
+int aoadmm_resident_rank_of(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const int64_t* subs, const int64_t* excl_off,
+                            const int64_t* excl_idx, int64_t* rank, double* score, int64_t* ncand_or_null) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_resident_rank_of");
+    ctx->eng->rank_of(p, mode, nq, subs, excl_off, excl_idx, rank, score, ncand_or_null);
+  });
+}
+int aoadmm_resident_rank_of_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const double* W, const int64_t* targets,
+                              const int64_t* excl_off, const int64_t* excl_idx, int64_t* rank, double* score, int64_t* ncand_or_null) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_resident_rank_of_w");
+    ctx->eng->rank_of_w(p, mode, nq, W, targets, excl_off, excl_idx, rank, score, ncand_or_null);
+  });
+}
 int aoadmm_resident_fold_in(aoadmm_ctx* ctx, int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals,
                             const aoadmm_foldin_options* opt_or_null, double* rows, int* info, int* iters_or_null,
                             double* gram_or_null, double* rhs_or_null) {

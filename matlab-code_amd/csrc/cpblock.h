@@ -20,7 +20,7 @@ struct FactorRef {
 
 constexpr int kStatsEmPass = 4;
 constexpr int kStatsHeldout = kStatsEmPass + kCooMaxModes;   // the held-out pass (heldout.h)
-constexpr int kStatsTopk = kStatsHeldout + 1;                 // the top-k completions (topk.h)
+constexpr int kStatsTopk = kStatsHeldout + 1;                 // the top-k completions (topk.h) and the ranks of targets (rank_of.h)
 constexpr int kStatsFoldin = kStatsTopk + 1;                  // the fold-in of new rows (foldin.h)
 constexpr int kStatsClasses = kStatsFoldin + 1;
 

@@ -239,6 +239,14 @@ class Engine {
               int64_t* idx_host, double* val_host);
   void topk_run(const char* what, int p, int mode, int64_t nq, const int64_t* subs, const double* W, int k, const int64_t* excl_off,
                 const int64_t* excl_idx, int64_t* idx_host, double* val_host);
+  // the place of a target row among a query's candidates (rank_of.h): subs' column `mode` holds
+  // the target; _w: the weights given (W: nq x R column-major on the host) with the targets beside them
+  void rank_of(int p, int mode, int64_t nq, const int64_t* subs, const int64_t* excl_off, const int64_t* excl_idx, int64_t* rank_host,
+               double* score_host, int64_t* ncand_host);
+  void rank_of_w(int p, int mode, int64_t nq, const double* W, const int64_t* targets, const int64_t* excl_off, const int64_t* excl_idx,
+                 int64_t* rank_host, double* score_host, int64_t* ncand_host);
+  void rank_of_run(const char* what, int p, int mode, int64_t nq, const int64_t* subs, const double* W, const int64_t* targets,
+                   const int64_t* excl_off, const int64_t* excl_idx, int64_t* rank_host, double* score_host, int64_t* ncand_host);
   // new rows along one mode of a CP block from their entries (foldin.h)
   int tensor_rank(int p) const;                    // the number of components of block p (aoadmm_tensor_rank)
   void fold_in(int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals, const aoadmm_foldin_options* opt,

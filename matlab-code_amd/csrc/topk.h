@@ -42,6 +42,8 @@ struct TopkArgs {
   double* out_val = nullptr;         // device [nq x k]
 };
 void topk_enqueue(const TopkArgs& a, const TopkPlan& plan, hipStream_t s);
+// the weights launch alone: W[q x R row-major] from idx (device int32 [nd x nq]; row `mode` is not read)
+void topk_weights_enqueue(const HeldoutFactors& hf, int mode, int64_t nq, const int* idx, double* W, hipStream_t s);
 
 // algorithmic bytes (F_mode streamed once per query tile, the gathered rows, the answer) and flops 2 I nq R
 double topk_bytes(int nd, int R, int64_t I, int64_t nq, int k, const TopkPlan& plan);

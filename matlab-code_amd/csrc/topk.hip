@@ -335,6 +335,13 @@ static void launch_scores(const TopkKArgs& ka, const TopkPlan& pl, hipStream_t s
   AO_KERNEL_CHECK();
 }
 
+void topk_weights_enqueue(const HeldoutFactors& hf, int mode, int64_t nq, const int* idx, double* W, hipStream_t s) {
+  TopkWArgs wa;
+  wa.hf = hf; wa.mode = mode; wa.nq = nq; wa.idx = idx; wa.W = W;
+  topk_weights_k<<<(unsigned)cdiv(nq * hf.R, 256), 256, 0, s>>>(wa);
+  AO_KERNEL_CHECK();
+}
+
 void topk_enqueue(const TopkArgs& a, const TopkPlan& pl, hipStream_t s) {
   const int R = a.hf.R;
   AO_REQUIRE(R >= 1 && R <= kMaxRank && a.hf.nd >= 2 && a.hf.nd <= kCooMaxModes && a.hf.off == nullptr, "internal: top-k pass of rank %d, order %d", R, a.hf.nd);
@@ -354,12 +361,7 @@ void topk_enqueue(const TopkArgs& a, const TopkPlan& pl, hipStream_t s) {
   ws += align256(c1 * sizeof(double));
   int* pong_idx = reinterpret_cast<int*>(ws);
 
-  if (a.W == nullptr) {
-    TopkWArgs wa;
-    wa.hf = a.hf; wa.mode = a.mode; wa.nq = a.nq; wa.idx = a.idx; wa.W = W;
-    topk_weights_k<<<(unsigned)cdiv(a.nq * R, 256), 256, 0, s>>>(wa);
-    AO_KERNEL_CHECK();
-  }
+  if (a.W == nullptr) topk_weights_enqueue(a.hf, a.mode, a.nq, a.idx, W, s);
 
   TopkKArgs ka;
   ka.F = a.hf.f[a.mode];

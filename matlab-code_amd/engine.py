@@ -334,6 +334,57 @@ class Engine:
                          idx.ctypes.data_as(i64p), capi.dptr(val)))
         return idx, val
 
+    def rank_of(self, p, mode, subs, exclude=None):
+        """Where held-out entries stand along mode `mode` of CP block p (`aoadmm_resident_rank_of`).  subs is nq x N,
+        0-based; unlike `topk` its column `mode` is read: it holds the target row t_q.  Scores, order and exclusion
+        lists are `topk`'s, with one difference: the target is a candidate whenever its score is not NaN, listed or not,
+        so `sptensor.fiber_lists` of the whole tensor can be passed.  Returns (rank int64 nq, score float64 nq, ncand
+        int64 nq): rank[q] is the number of candidates that come before t_q in `topk`'s order (its 0-based place; -1
+        when its score is NaN), score[q] its score, ncand[q] the number of candidates.  `ranking_metrics` turns them
+        into hit-rate, NDCG, MRR and AUC.  No nq x I_mode array exists."""
+        subs = self._subs_f(subs, 'rank_of')
+        i64p = C.POINTER(C.c_int64)
+        return self._rank_call('rank_of', self.lib.aoadmm_resident_rank_of, p, mode, int(subs.shape[0]),
+                               (subs.ctypes.data_as(i64p),), exclude, keep=subs)
+
+    def rank_of_w(self, p, mode, W, targets, exclude=None):
+        """`rank_of` with the weights given (`aoadmm_resident_rank_of_w`): W is nq x R, row q the weights of query q,
+        used as they are, and targets[q] the row to place.  Ranks a row that `fold_in` returned (see `topk_w`)."""
+        W = capi.as_f(W)
+        if W.ndim != 2:
+            raise ValueError('rank_of_w: W must be nq x R')
+        R = self.block_rank(p)                                  # an unknown block is refused here, as the library refuses it
+        if W.shape[1] != R:
+            raise ValueError('rank_of_w: W has %d columns, block %d has R = %d' % (W.shape[1], int(p), R))
+        targets = np.ascontiguousarray(np.asarray(targets, dtype=np.int64).reshape(-1))
+        if targets.shape[0] != W.shape[0]:
+            raise ValueError('rank_of_w: %d targets for %d rows of W' % (targets.shape[0], W.shape[0]))
+        i64p = C.POINTER(C.c_int64)
+        return self._rank_call('rank_of_w', self.lib.aoadmm_resident_rank_of_w, p, mode, int(W.shape[0]),
+                               (capi.dptr(W), targets.ctypes.data_as(i64p)), exclude, keep=(W, targets))
+
+    def _rank_call(self, what, entry, p, mode, nq, queries, exclude, keep=None):
+        """The part `rank_of` and `rank_of_w` share: the outputs, the exclusion lists, the call.  `queries` holds the
+        pointers the entry takes after nq; `keep` holds their arrays alive."""
+        rank = np.full(nq, -1, dtype=np.int64)
+        score = np.full(nq, np.nan)
+        ncand = np.zeros(nq, dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        off = ex = None
+        if exclude is not None:
+            off = np.ascontiguousarray(np.asarray(exclude[0], dtype=np.int64).reshape(-1))
+            ex = np.ascontiguousarray(np.asarray(exclude[1], dtype=np.int64).reshape(-1))
+            if off.shape[0] != nq + 1:
+                raise ValueError('%s: exclude[0] must hold nq + 1 = %d offsets, got %d' % (what, nq + 1, off.shape[0]))
+            if off[-1] != ex.shape[0]:
+                raise ValueError('%s: exclude[0][-1] = %d but exclude[1] holds %d rows' % (what, off[-1], ex.shape[0]))
+            if ex.shape[0] == 0:
+                ex = np.zeros(1, dtype=np.int64)          # a valid address for an empty list
+        capi.check(entry(self.h, int(p), int(mode), nq, *queries,
+                         off.ctypes.data_as(i64p) if off is not None else None, ex.ctypes.data_as(i64p) if ex is not None else None,
+                         rank.ctypes.data_as(i64p), capi.dptr(score), ncand.ctypes.data_as(i64p)))
+        return rank, score, ncand
+
     def block_rank(self, p):
         """The number of components R of block p (`aoadmm_tensor_rank`), from the model the engine holds."""
         r = C.c_int(0)
@@ -423,7 +474,7 @@ class Engine:
         """(ms, launches, bytes, flops) of a kernel class since the last reset (`aoadmm_kernel_stats`); which = 3:
         MTTKRPs of sparse blocks (of a sharded block: this rank's share), passes over the nonzeros of PARAFAC2
         blocks with sparse slabs and EM steps of observed-only blocks; which = 4 + n: the pass of those EM steps over
-        the copy of tensor mode n; which = 12: the held-out passes; which = 13: the top-k completions (one launch per `topk` call);
+        the copy of tensor mode n; which = 12: the held-out passes; which = 13: the top-k completions and the ranks of targets (one launch per `topk` or `rank_of` call);
         which = 14: the fold-in of new rows (one launch per `fold_in` call, weighted or not)."""
         ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         capi.check(self.lib.aoadmm_kernel_stats(self.h, int(which), int(bool(reset)), C.byref(ms), C.byref(n),
