@@ -168,8 +168,9 @@ typedef struct aoadmm_result {
   double f_tensors, f_couplings, f_constraints, f_PAR2_couplings;
   int32_t OuterIterations;
   int32_t exit_code;            /* 0 = 'maxIterations', 1 = stopping rule met (make_exit_flag.m), 2 = stopped by
-                                   aoadmm_options.heldout_patience (when both rules fire in one iteration: 1;
-                                   a rule that fires in iteration MaxOuterIters reports 0, as before) */
+                                   aoadmm_options.heldout_patience, 3 = stopped by the patience of aoadmm_rank_track
+                                   (when the stopping rule fires in the same iteration: 1; a rule that fires in
+                                   iteration MaxOuterIters reports 0, as before) */
   int32_t exit_abs[4];          /* per quantity: 1 = 'AbsFuncTol', 0 = 'RelFuncTol' */
   double *func_val_conv, *func_coupl_conv, *func_constr_conv, *func_PAR2_coupl, *time_at_it;
   double *innerIters;
@@ -432,7 +433,9 @@ int aoadmm_heldout_trace(aoadmm_ctx* ctx, int p, double* out, int cap, int* len,
  * is added.  The solve itself does not change: its state on return, its traces, exit_code and result scalars are those
  * of the LAST iteration, bit for bit, with the switch on or off.  on = 0 releases the copy; any other value is
  * AOADMM_ERR_INVALID.  The switch belongs to the MODEL, as the lists do: aoadmm_model_begin clears it.  A solve with
- * the switch on and no list attached is AOADMM_ERR_INVALID before any work.  Costs the state's bytes once more in HBM. */
+ * the switch on and no list attached is AOADMM_ERR_INVALID before any work.  Costs the state's bytes once more in HBM.
+ * With aoadmm_rank_track(criterion = 1) the copy follows the best ranking score S instead of the smallest H, and the
+ * list the solve needs is a ranking list (aoadmm_tensor_set_ranklist). */
 int aoadmm_heldout_keep_best(aoadmm_ctx* ctx, int on);
 /* Copies the kept state back into the engine's state and reports its iteration in *iter (may be NULL).  Afterwards the
  * engine is where a solve of *iter iterations from the same start would have left it: what is derived from the factors
@@ -504,6 +507,72 @@ int aoadmm_resident_rank_of(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const 
 int aoadmm_resident_rank_of_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const double* W, const int64_t* targets,
                               const int64_t* excl_off, const int64_t* excl_idx, int64_t* rank, double* score,
                               int64_t* ncand_or_null);
+
+/* ---- ranking metrics tracked inside a solve ------- */
+/* the metric aoadmm_rank_track follows; also the order of the float sums in aoadmm_rank_trace */
+enum {
+  AOADMM_RANK_HIT = 0,    /* hit-rate@k: the share of queries with rank < k */
+  AOADMM_RANK_NDCG = 1,   /* NDCG@k: the mean of 1 / log2(rank + 2) where rank < k, else 0 */
+  AOADMM_RANK_MRR = 2,    /* the mean of 1 / (rank + 1) */
+  AOADMM_RANK_AUC = 3     /* the mean of 1 - rank / (ncand - 1) over the queries with ncand >= 2 */
+};
+/* the quantities of aoadmm_rank_trace and the slots of aoadmm_op_rank_metrics: sums, not means; counts are doubles
+ * that hold integers */
+enum {
+  AOADMM_RANKSUM_N = 0,       /* queries with rank >= 0 */
+  AOADMM_RANKSUM_N_AUC = 1,   /* those of them with ncand >= 2 */
+  AOADMM_RANKSUM_HITS = 2,    /* #{rank < k} */
+  AOADMM_RANKSUM_NDCG = 3,    /* sum over rank < k of 1 / log2(rank + 2) */
+  AOADMM_RANKSUM_MRR = 4,     /* sum of 1 / (rank + 1) */
+  AOADMM_RANKSUM_AUC = 5,     /* sum over the N_AUC queries of 1 - rank / (ncand - 1) */
+  AOADMM_RANKSUM_COUNT = 6    /* slots 6 and 7 of an out[8] are spare and zero */
+};
+/* Attaches (nq > 0) or removes (nq = 0) the RANKING LIST of CP block p: nq queries with one target row each along mode
+ * `mode`, and their exclusion lists.  Arguments and validation are exactly those of aoadmm_resident_rank_of (column
+ * `mode` of subs is the target; lists in any order, repeats allowed, NULL: none); an error leaves the previous list
+ * untouched.  The call does once what aoadmm_resident_rank_of does per call -- range checks, per-query sort and removal
+ * of repeats, the chunk table -- uploads the result and allocates the rank pass's workspace and the three per-query
+ * output arrays: an evaluation inside a solve allocates nothing, uploads nothing and touches no host memory.  The list
+ * belongs to the MODEL, as a held-out list does: aoadmm_model_begin drops it, a new upload of the block's data keeps it.
+ * One list per block.  With a list attached, aoadmm_solve evaluates it at iteration 0 and at every iteration i with
+ * i % every == 0 (aoadmm_rank_track) beside the objective: the launches of aoadmm_resident_rank_of against the factors
+ * that evaluation uses, then two launches that reduce rank and ncand to the AOADMM_RANKSUM_* sums, which travel in the
+ * solve's one read-back per outer iteration.  Nothing else the solve computes changes: factors, duals, innerIters, the
+ * objective and held-out traces and every kernel-statistics class but 13 are bit for bit those of the solve without a
+ * list; class 13 counts one launch per list and evaluation.  With a communicator every rank attaches the same list and
+ * does the same work (no collective, bit-identical ranks, so every rank takes the same decision).
+ * AOADMM_ERR_UNSUPPORTED for a PARAFAC2 block and on a multi-device context (aoadmm_create_multi with more than one
+ * device). */
+int aoadmm_tensor_set_ranklist(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const int64_t* subs, const int64_t* excl_off,
+                               const int64_t* excl_idx);
+/* *nq = queries of block p's ranking list (0: none), *mode = its target mode (-1: none), *listed_after_dedup = excluded
+ * rows kept after the per-query removal of repeats, *resident_bytes = device bytes of the list, the workspace and the
+ * outputs.  Each output may be NULL.  No device work. */
+int aoadmm_ranklist_info(aoadmm_ctx* ctx, int p, int64_t* nq, int* mode, int64_t* listed_after_dedup, int64_t* resident_bytes);
+/* What a solve does with the ranking lists.  metric: AOADMM_RANK_*; k in [1, 2^31): the cut-off of hit-rate and NDCG;
+ * every >= 1: the lists are evaluated at iteration 0 and at every iteration i with i % every == 0; patience >= 0;
+ * criterion 0 or 1.  At an evaluation S is the pooled mean of the metric over all blocks with a list: the sum of their
+ * sums over the sum of their N (N_AUC for AUC); block weights do not enter; 0 / 0 is NaN.  Larger is better: iteration 0
+ * is the first best, a later evaluation becomes the best only if S is strictly larger; a NaN never does, and a NaN at
+ * iteration 0 is replaced by the first S that is not NaN.  The best evaluation's iteration is reported by
+ * aoadmm_rank_trace whatever the criterion.
+ *   criterion = 0: trace only.  The held-out sum H, heldout_patience and aoadmm_heldout_keep_best work as without lists.
+ *   criterion = 1: S is the solve's model-selection number.  patience = n > 0 stops the solve after the evaluation at
+ *     which S has not improved for n consecutive EVALUATIONS (exit_code 3); aoadmm_heldout_keep_best keeps the state
+ *     of the best S instead of the smallest H, and aoadmm_heldout_restore_best returns it.  aoadmm_solve answers
+ *     AOADMM_ERR_INVALID before any work when no ranking list is attached or aoadmm_options.heldout_patience > 0.
+ * patience > 0 with criterion = 0, or any argument out of range, is AOADMM_ERR_INVALID and the settings stay.  The
+ * settings belong to the MODEL: aoadmm_model_begin restores the defaults (AOADMM_RANK_NDCG, 10, 1, 0, 0). */
+int aoadmm_rank_track(aoadmm_ctx* ctx, int metric, int k, int every, int patience, int criterion);
+/* After aoadmm_solve: out[e] = the sum `what` (AOADMM_RANKSUM_*) of block p's list at its e-th evaluation and iters[e]
+ * (may be NULL) the iteration of that evaluation; at most cap entries each are written, *len = evaluations (0 when the
+ * block had no list), *best_iter = the iteration of the best S (-1 without a list).  len and best_iter may be NULL.
+ * No device work. */
+int aoadmm_rank_trace(aoadmm_ctx* ctx, int p, int what, double* out, int cap, int* len, int* iters_or_null, int* best_iter);
+/* rank, score and ncand (nq entries each; any may be NULL) of block p's list as its last evaluation left them on the
+ * device: the outputs of aoadmm_resident_rank_of for the factors that evaluation used.  AOADMM_ERR_INVALID without a
+ * list or before its first evaluation; AOADMM_ERR_UNSUPPORTED on a multi-device context. */
+int aoadmm_ranklist_last(aoadmm_ctx* ctx, int p, int64_t* rank, double* score, int64_t* ncand);
 
 /* ---- fold-in of new rows -------------------------- */
 /* The factor rows of nq NEW indices ("queries": a new user, document, sample) along mode `mode` (0-based position in
@@ -790,6 +859,11 @@ enum {
 int aoadmm_op_coupled_loop(aoadmm_ctx* ctx, int coupling, const double* const* A, const double* const* C, int max_inner,
                            const double* tol, int* inner_iters, double* res, double* rho, double* const* L,
                            double* const* gram, double* slots, int* path);
+/* The reduction a solve runs behind the rank pass of a ranking list, on host arrays: out[0..5] =
+ * the AOADMM_RANKSUM_* sums of rank[0..n) and ncand[0..n) at cut-off k, out[6] = out[7] = 0.  n >= 1, k >= 1;
+ * a query with rank < 0 is left out of everything.  Two launches (team partials in query order, a one-workgroup
+ * finisher in a fixed order): the bits are a function of (rank, ncand, k) alone. */
+int aoadmm_op_rank_metrics(aoadmm_ctx* ctx, int64_t n, const int64_t* rank, const int64_t* ncand, int64_t k, double out[8]);
 
 #ifdef __cplusplus
 }

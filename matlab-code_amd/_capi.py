@@ -58,6 +58,9 @@ ALL_SLABS = -1            # AOADMM_ALL_SLABS
 (P2SLAB_REGS1, P2SLAB_REGS2, P2SLAB_REGS4, P2SLAB_LDS4, P2SLAB_LDS8, P2SLAB_LDS16, P2SLAB_LDS64) = range(7)   # AOADMM_P2SLAB_*
 (P2CSYS_UNCOUPLED, P2CSYS_ROWS, P2CSYS_HHT, P2CSYS_DIAG, P2CSYS_DENSE) = range(5)   # AOADMM_P2CSYS_*
 (P2C_SINGLE, P2C_WG, P2C_LAUNCHED) = range(3)   # AOADMM_P2C_*
+(RANK_HIT, RANK_NDCG, RANK_MRR, RANK_AUC) = range(4)   # AOADMM_RANK_*
+RANK_METRICS = {'hit': RANK_HIT, 'ndcg': RANK_NDCG, 'mrr': RANK_MRR, 'auc': RANK_AUC}
+(RANKSUM_N, RANKSUM_N_AUC, RANKSUM_HITS, RANKSUM_NDCG, RANKSUM_MRR, RANKSUM_AUC, RANKSUM_COUNT) = range(7)   # AOADMM_RANKSUM_*
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double)   # aoadmm_progress_fn
 
 # every symbol include/aoadmm_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -72,10 +75,11 @@ SYMBOLS = [
     'aoadmm_resident_model_at', 'aoadmm_tensor_set_heldout', 'aoadmm_resident_heldout_stats', 'aoadmm_heldout_info', 'aoadmm_heldout_trace',
     'aoadmm_heldout_keep_best', 'aoadmm_heldout_restore_best', 'aoadmm_heldout_best_info', 'aoadmm_resident_topk',
     'aoadmm_resident_topk_w', 'aoadmm_resident_rank_of', 'aoadmm_resident_rank_of_w', 'aoadmm_resident_fold_in', 'aoadmm_resident_fold_in_w',
+    'aoadmm_tensor_set_ranklist', 'aoadmm_ranklist_info', 'aoadmm_rank_track', 'aoadmm_rank_trace', 'aoadmm_ranklist_last',
     'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_resident_par2_rhs', 'aoadmm_kernel_stats',
     'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_resident_nvecs', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
     'aoadmm_op_admm_mode', 'aoadmm_op_par2_b_loop', 'aoadmm_op_coupled_loop',
-    'aoadmm_op_par2_mode_a', 'aoadmm_op_par2_mode_c', 'aoadmm_op_par2_objective',
+    'aoadmm_op_par2_mode_a', 'aoadmm_op_par2_mode_c', 'aoadmm_op_par2_objective', 'aoadmm_op_rank_metrics',
 ]
 
 
@@ -202,6 +206,12 @@ def load_library():
                                             C.POINTER(i64)]
     lib.aoadmm_resident_rank_of_w.argtypes = [vp, C.c_int, C.c_int, i64, dp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
                                               dp, C.POINTER(i64)]
+    lib.aoadmm_tensor_set_ranklist.argtypes = [vp, C.c_int, C.c_int, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    lib.aoadmm_ranklist_info.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(i64)]
+    lib.aoadmm_rank_track.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.aoadmm_rank_trace.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.aoadmm_ranklist_last.argtypes = [vp, C.c_int, C.POINTER(i64), dp, C.POINTER(i64)]
+    lib.aoadmm_op_rank_metrics.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64), i64, dp]
     lib.aoadmm_resident_fold_in.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.POINTER(i64), dp, C.POINTER(FoldinOptions), dp,
                                             C.POINTER(C.c_int), C.POINTER(C.c_int), dp, dp]
     lib.aoadmm_resident_fold_in_w.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.POINTER(i64), dp, dp, C.c_double, C.POINTER(FoldinOptions),

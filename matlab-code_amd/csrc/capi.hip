@@ -15,6 +15,7 @@
 
 #include "solver.h"
 #include "misc.h"
+#include "rank_metrics.h"
 
 using namespace aoadmm;
 
@@ -551,6 +552,36 @@ int aoadmm_resident_rank_of_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, cons
     ctx->eng->rank_of_w(p, mode, nq, W, targets, excl_off, excl_idx, rank, score, ncand_or_null);
   });
 }
+int aoadmm_tensor_set_ranklist(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const int64_t* subs, const int64_t* excl_off,
+                               const int64_t* excl_idx) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_tensor_set_ranklist");
+    ctx->eng->set_ranklist(p, mode, nq, subs, excl_off, excl_idx);
+  });
+}
+int aoadmm_ranklist_info(aoadmm_ctx* ctx, int p, int64_t* nq, int* mode, int64_t* listed_after_dedup, int64_t* resident_bytes) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] { ctx->eng->ranklist_info(p, nq, mode, listed_after_dedup, resident_bytes); });   // no device work
+}
+int aoadmm_rank_track(aoadmm_ctx* ctx, int metric, int k, int every, int patience, int criterion) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_rank_track");
+    ctx->eng->rank_track(metric, k, every, patience, criterion);
+  });
+}
+int aoadmm_rank_trace(aoadmm_ctx* ctx, int p, int what, double* out, int cap, int* len, int* iters_or_null, int* best_iter) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] { ctx->eng->rank_trace(p, what, out, cap, len, iters_or_null, best_iter); });     // no device work
+}
+int aoadmm_ranklist_last(aoadmm_ctx* ctx, int p, int64_t* rank, double* score, int64_t* ncand) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_ranklist_last");
+    ctx->eng->ranklist_last(p, rank, score, ncand);
+  });
+}
 int aoadmm_resident_fold_in(aoadmm_ctx* ctx, int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals,
                             const aoadmm_foldin_options* opt_or_null, double* rows, int* info, int* iters_or_null,
                             double* gram_or_null, double* rhs_or_null) {
@@ -752,6 +783,25 @@ int aoadmm_op_gram(aoadmm_ctx* ctx, const double* F, int64_t rows, int R, double
     ws.alloc(atb_ws_bytes(rows, R, R));
     atb_small(g.d(), f.d(), rows, f.d(), rows, rows, R, R, ws.d(), nullptr, e.stream());
     d2h(out, g, (int64_t)R * R, e.stream());
+  });
+}
+
+// The metric reduction of a ranking list (rank_metrics.h) on host arrays
+int aoadmm_op_rank_metrics(aoadmm_ctx* ctx, int64_t n, const int64_t* rank, const int64_t* ncand, int64_t k, double out[8]) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    AO_REQUIRE(rank && ncand && out && n >= 1 && k >= 1, "bad arguments");
+    Engine& e = *ctx->eng;
+    AO_HIP(hipSetDevice(e.device()));
+    DevBuf r, c, part, slots;
+    r.alloc((size_t)n * sizeof(int64_t));
+    c.alloc((size_t)n * sizeof(int64_t));
+    part.alloc(rank_metrics_part_bytes(n));
+    slots.alloc(kRankSlots * sizeof(double));
+    AO_HIP(hipMemcpyAsync(r.p, rank, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, e.stream()));
+    AO_HIP(hipMemcpyAsync(c.p, ncand, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, e.stream()));
+    rank_metrics_enqueue(r.as<int64_t>(), c.as<int64_t>(), n, k, part.d(), slots.d(), e.stream());
+    d2h(out, slots, kRankSlots, e.stream());
   });
 }
 

@@ -1,6 +1,6 @@
 // The read-back arena: everything the host reads once per outer iteration, in one piece so that one copy fetches it.
 //   [8 objective slots per mode | 2 per tensor | 8 residual slots per mode | 16 scratch | 4 EM statistics per tensor
-//    | 4 held-out sums per tensor]
+//    | 4 held-out sums per tensor | 8 ranking-metric sums per tensor]
 //   | AdmmCtl[n_modes + n_couplings + 1] | per PARAFAC2 block: res (K + 1), q (4 K), regv (K)
 // ArenaLayout holds the offsets (Engine::model_end fills it); ArenaView hands out typed pointers from a base pointer,
 // the device arena and its pinned host copy alike.
@@ -34,6 +34,18 @@ enum TensorObj {
 enum EmStat { kEmNum = 0, kEmDen = 1, kEmObsRes = 2, kEmObsX2 = 3, kEmStats = 4 };
 // held-out sums of a tensor (heldout; heldout.h): written only while the tensor has a list attached
 enum HeldoutSlot { kHoRes = 0, kHoY2 = 1, kHoM2 = 2, kHoSlots = 4 };
+// ranking-metric sums of a tensor (rank; rank_metrics.h): written only while the tensor has a ranking list attached.
+// Counts are doubles holding integers.
+enum RankSlot {
+  kRankN = 0,         // queries with rank >= 0
+  kRankNAuc = 1,      // those of them with ncand >= 2
+  kRankHits = 2,      // #{rank < k}
+  kRankNdcg = 3,      // sum over rank < k of 1 / log2(rank + 2)
+  kRankMrr = 4,       // sum of 1 / (rank + 1)
+  kRankAuc = 5,       // sum over the kRankNAuc queries of 1 - rank / (ncand - 1)
+  kRankUsed = 6,
+  kRankSlots = 8,     // two spare
+};
 // sums per slab in a PARAFAC2 block's q (p2_q)[kSlabSums * k + ...]
 enum SlabSum {
   kSlabGapP = 0,      // ||B_k - P_k DeltaB||^2
@@ -52,7 +64,7 @@ struct ArenaLayout {
   size_t off_ctl = 0, bytes = 0;
 
   int n_doubles() const {
-    return n_modes * (kSlotsPerMode + kResidPerMode) + (kSlotsPerTensor + kEmStats + kHoSlots) * n_tensors + kScratchSlots;
+    return n_modes * (kSlotsPerMode + kResidPerMode) + (kSlotsPerTensor + kEmStats + kHoSlots + kRankSlots) * n_tensors + kScratchSlots;
   }
   int n_ctl() const { return n_modes + n_couplings; }       // the records the host checks (one spare behind them)
   void build(int modes, int tensors, int couplings, const std::vector<int>& slabs) {
@@ -77,6 +89,7 @@ struct ArenaView {
   double* scratch() const { return resid(L->n_modes); }
   double* em(int p) const { return scratch() + kScratchSlots + kEmStats * p; }
   double* heldout(int p) const { return em(L->n_tensors) + kHoSlots * p; }
+  double* rank(int p) const { return heldout(L->n_tensors) + kRankSlots * p; }
   AdmmCtl* ctl(int i) const { return reinterpret_cast<AdmmCtl*>(base + L->off_ctl) + i; }
   // PARAFAC2 block p: K + 1 slab residuals (+ the not-PD flag of sharded slabs), kSlabSums K gap sums, K regulariser values
   double* p2_res(int p) const { return reinterpret_cast<double*>(base + L->off_p2[p]); }

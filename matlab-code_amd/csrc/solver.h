@@ -20,6 +20,7 @@
 #include "misc.h"
 #include "par2.h"
 #include "par2_sparse.h"
+#include "rank_of.h"
 #include "readback.h"
 #include "small.h"
 #include "sparse.h"
@@ -101,6 +102,41 @@ struct Par2Block {
   }
 };
 
+// Ranking list of one block (aoadmm_tensor_set_ranklist): what Engine::rank_of_run prepares and
+// uploads per call, kept on the device with the plan's workspace and the per-query outputs, so that an evaluation inside
+// a solve allocates nothing and touches no host memory.
+struct RankList {
+  int64_t nq = 0;                 // queries; 0: no list
+  int mode = -1, nd = 0;
+  int64_t I = 0;                  // rows of the target mode
+  int64_t listed = 0;             // excluded rows after the per-query removal of repeats
+  RankPlan plan;
+  DevBuf idx;                     // int32 [nd x nq]; row `mode` holds the targets
+  DevBuf eoff, eidx, coff, cq;    // the exclusion lists and their chunk table (plan.chunks > 0)
+  DevBuf ws, rank, score, ncand;  // the plan's workspace and the per-query outputs of the last evaluation
+  DevBuf part;                    // the metric reduction's partial sums per team (rank_metrics.h)
+  bool evaluated = false;         // rank / score / ncand hold an evaluation
+  int64_t resident_bytes() const {
+    return (int64_t)(idx.bytes + eoff.bytes + eidx.bytes + coff.bytes + cq.bytes + ws.bytes + rank.bytes + score.bytes + ncand.bytes + part.bytes);
+  }
+  void clear() { *this = RankList(); }
+  RankList() = default;
+  RankList(RankList&&) = default;
+  RankList& operator=(RankList&&) = default;
+};
+
+// aoadmm_rank_track: what a solve does with the ranking lists; belongs to the model
+struct RankTrack {
+  int metric = AOADMM_RANK_NDCG;
+  int k = 10, every = 1, patience = 0, criterion = 0;
+};
+
+// the exclusion lists of a rank pass as the host prepares them (Engine::rank_prepare_excl)
+struct RankExclHost {
+  std::vector<int> ex32, chq;           // every query's rows sorted without repeats; the query of every chunk
+  std::vector<int64_t> eoff64, choff;   // nq + 1 offsets into ex32 / into the chunks
+};
+
 struct TensorInfo {
   bool defined = false;
   bool par2 = false;
@@ -118,6 +154,8 @@ struct TensorInfo {
   int ho_row_major = -1;        // what the block's last held-out pass gathered from: 1 the row-major factor copies, 0 the
                                 // column-major factors, -1 no pass yet
   std::vector<double> ho_trace; // sum (y - m)^2 at iteration 0 .. OuterIterations of the last solve
+  RankList rl;                  // ranking list (aoadmm_tensor_set_ranklist): belongs to the model, as the held-out list does
+  std::vector<double> rl_trace; // kRankSlots sums per evaluation of the last solve (the iterations: Engine::rank_iters_)
   bool eval_shortcut = false;   // PARAFAC2: the enqueued objective evaluation took the last_mttkrp shortcut (:1254-1260)
   bool masked() const { return par2 ? p2.has_mask : blk.has_mask; }   // Z.miss{p} given
   bool observed_only() const { return !par2 && blk.sparse && blk.sem.on; }   // sparse block whose unstored entries are missing
@@ -247,6 +285,12 @@ class Engine {
                  int64_t* rank_host, double* score_host, int64_t* ncand_host);
   void rank_of_run(const char* what, int p, int mode, int64_t nq, const int64_t* subs, const double* W, const int64_t* targets,
                    const int64_t* excl_off, const int64_t* excl_idx, int64_t* rank_host, double* score_host, int64_t* ncand_host);
+  // ranking metrics tracked inside a solve (rank_metrics.h)
+  void set_ranklist(int p, int mode, int64_t nq, const int64_t* subs, const int64_t* excl_off, const int64_t* excl_idx);   // nq = 0 removes the list
+  void ranklist_info(int p, int64_t* nq, int* mode, int64_t* listed, int64_t* resident_bytes) const;
+  void rank_track(int metric, int k, int every, int patience, int criterion);
+  void rank_trace(int p, int what, double* out, int cap, int* len, int* iters, int* best_iter) const;
+  void ranklist_last(int p, int64_t* rank_host, double* score_host, int64_t* ncand_host);
   // new rows along one mode of a CP block from their entries (foldin.h)
   int tensor_rank(int p) const;                    // the number of components of block p (aoadmm_tensor_rank)
   void fold_in(int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals, const aoadmm_foldin_options* opt,
@@ -320,6 +364,13 @@ class Engine {
   HeldoutFactors heldout_factors(const TensorInfo& t, bool* row_major) const;   // the current fac state of block t as the pass gathers it
   // skip_mode >= 0: that column of subs is neither read nor checked (its part of idx32 stays zero)
   void heldout_check_subs(const TensorInfo& t, int p, int64_t n, const int64_t* subs, std::vector<int>& idx32, int skip_mode = -1) const;
+  // the range checks, the per-query sort and removal of repeats and the chunk table of the exclusion lists of a rank pass
+  void rank_prepare_excl(int p, int64_t I, int64_t nq, const int64_t* excl_off, const int64_t* excl_idx, RankExclHost& h) const;
+  // uploads them (asynchronously: the caller synchronises before `h` goes) and names them in `a`
+  void rank_upload_excl(const RankExclHost& h, int64_t nq, DevBuf& eoff, DevBuf& eidx, DevBuf& coff, DevBuf& cq, RankArgs& a);
+  bool has_ranklist() const;
+  void ranklist_enqueue(int p, double* slots);     // block p's ranking list against the current factors -> kRankSlots sums (device)
+  double rank_score(const ArenaView& h) const;     // the pooled mean of the tracked metric over the blocks with a list
   void heldout_enqueue(int p, double* sums);       // block p's list against the current factors -> sums[0..2] (device)
   std::vector<SnapSeg> best_state_segments() const;   // every array aoadmm_state_get can return, as (src, bytes, start)
   void best_build_table();                         // solve_setup: the segment table and the kept buffer of this solve
@@ -402,6 +453,10 @@ class Engine {
   LaunchTimers timers_;   // event pool and kernel statistics (cpblock.h)
   int ho_best_iter_ = -1;   // iteration of the smallest weighted held-out sum of the last solve (-1: no list was attached)
   BestKeep best_;           // aoadmm_heldout_keep_best
+  RankTrack track_;         // aoadmm_rank_track
+  bool rank_eval_now_ = false;     // set by solve(): the evaluation being enqueued also evaluates the ranking lists
+  std::vector<int> rank_iters_;    // the evaluated iterations of the last solve
+  int rank_best_iter_ = -1;        // iteration of the largest pooled score of the last solve (-1: no list was attached)
   int prepared_mode_ = -1;  // mode whose MTTKRP + system build were enqueued ahead (prepare_next_first_mode)
   ncclComm_t comm_ = nullptr;
   mutable std::mutex comm_mu_;          // comm_ / aborted_ against comm_abort() from another worker thread

@@ -56,6 +56,9 @@ void Engine::model_begin(int n_modes, int n_tensors, int n_couplings) {
   has_ridge_ = false;
   allow_xp_ = true;                                   // options.hip.no_permuted_copy of an earlier solve does not outlive its model
   best_ = BestKeep();                                 // aoadmm_heldout_keep_best belongs to the model, as the lists do
+  track_ = RankTrack();                               // and so does aoadmm_rank_track
+  rank_iters_.clear();
+  rank_best_iter_ = -1;
 }
 
 void Engine::set_mode(int mode, int64_t rows, int rank) {

@@ -20,6 +20,9 @@ void Engine::eval_objective_enqueue(bool first) {
   };
   for (int p = 0; p < n_tensors_; ++p)           // held-out lists: scored against the fac state this evaluation uses
     if (tensors_[p].ho.n > 0) heldout_enqueue(p, dev_.heldout(p));
+  if (rank_eval_now_)                            // ranking lists, at the iterations aoadmm_rank_track names: the same fac state
+    for (int p = 0; p < n_tensors_; ++p)
+      if (tensors_[p].rl.nq > 0) ranklist_enqueue(p, dev_.rank(p));
   for (int p = 0; p < n_tensors_; ++p) {
     TensorInfo& t = tensors_[p];
     const bool masked = t.masked();

@@ -16,6 +16,58 @@ void Engine::rank_of_w(int p, int mode, int64_t nq, const double* W, const int64
   rank_of_run("aoadmm_resident_rank_of_w", p, mode, nq, nullptr, W, targets, excl_off, excl_idx, rank_host, score_host, ncand_host);
 }
 
+// The exclusion lists of a rank pass: offsets non-decreasing from 0, rows in range; every list sorted and stripped of
+// repeats (a repeated row must not be subtracted twice), then cut into the chunks of the exclusion pass.  Shared by
+// rank_of_run (per call) and set_ranklist (once per list).
+void Engine::rank_prepare_excl(int p, int64_t I, int64_t nq, const int64_t* excl_off, const int64_t* excl_idx, RankExclHost& h) const {
+  std::vector<int>& ex32 = h.ex32;
+  std::vector<int>& chq = h.chq;
+  std::vector<int64_t>& eoff64 = h.eoff64;
+  std::vector<int64_t>& choff = h.choff;
+  ex32.clear(); chq.clear(); eoff64.clear(); choff.clear();
+  if (excl_off == nullptr) return;
+  AO_REQUIRE(excl_off[0] == 0, "excl_off[0] = %lld, not 0", (long long)excl_off[0]);
+  for (int64_t q = 0; q < nq; ++q)
+    AO_REQUIRE(excl_off[q + 1] >= excl_off[q], "excl_off decreases at query %lld", (long long)q);
+  const int64_t ne = excl_off[nq];
+  ex32.resize((size_t)ne);
+  for (int64_t e = 0; e < ne; ++e) {
+    AO_REQUIRE(excl_idx[e] >= 0 && excl_idx[e] < I, "tensor %d: excluded row %lld at position %lld is outside [0, %lld)", p,
+               (long long)excl_idx[e], (long long)e, (long long)I);
+    ex32[(size_t)e] = (int)excl_idx[e];
+  }
+  eoff64.assign((size_t)nq + 1, 0);
+  choff.assign((size_t)nq + 1, 0);
+  int64_t out = 0;
+  for (int64_t q = 0; q < nq; ++q) {
+    std::sort(ex32.begin() + excl_off[q], ex32.begin() + excl_off[q + 1]);
+    const auto last = std::unique(ex32.begin() + excl_off[q], ex32.begin() + excl_off[q + 1]);
+    out = std::copy(ex32.begin() + excl_off[q], last, ex32.begin() + out) - ex32.begin();   // out <= excl_off[q]: moves left
+    eoff64[(size_t)q + 1] = out;
+    const int64_t nch = cdiv(out - eoff64[(size_t)q], (int64_t)kRankExclChunk);
+    choff[(size_t)q + 1] = choff[(size_t)q] + nch;
+    chq.insert(chq.end(), (size_t)nch, (int)q);
+  }
+  ex32.resize((size_t)out);
+  AO_REQUIRE(choff[(size_t)nq] < ((int64_t)1 << 31), "%lld chunks of excluded rows: more than one launch holds", (long long)choff[(size_t)nq]);
+}
+
+void Engine::rank_upload_excl(const RankExclHost& h, int64_t nq, DevBuf& eoff, DevBuf& eidx, DevBuf& coff, DevBuf& cq, RankArgs& a) {
+  if (h.chq.empty()) return;
+  eoff.alloc((size_t)(nq + 1) * sizeof(int64_t));
+  eidx.alloc(h.ex32.size() * sizeof(int));
+  coff.alloc((size_t)(nq + 1) * sizeof(int64_t));
+  cq.alloc(h.chq.size() * sizeof(int));
+  AO_HIP(hipMemcpyAsync(eoff.p, h.eoff64.data(), (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+  AO_HIP(hipMemcpyAsync(eidx.p, h.ex32.data(), h.ex32.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
+  AO_HIP(hipMemcpyAsync(coff.p, h.choff.data(), (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+  AO_HIP(hipMemcpyAsync(cq.p, h.chq.data(), h.chq.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
+  a.excl_off = eoff.as<int64_t>();
+  a.excl_idx = eidx.as<int>();
+  a.chunk_off = coff.as<int64_t>();
+  a.chunk_q = cq.as<int>();
+}
+
 // subs (column `mode` holds the target; the weights are formed on the device) or W (nq x R column-major on the host,
 // uploaded as it is) with targets
 void Engine::rank_of_run(const char* what, int p, int mode, int64_t nq, const int64_t* subs, const double* W, const int64_t* targets,
@@ -51,37 +103,9 @@ void Engine::rank_of_run(const char* what, int p, int mode, int64_t nq, const in
     }
   }
 
-  // the exclusion lists: offsets non-decreasing from 0, rows in range; every list sorted and stripped of repeats (a
-  // repeated row must not be subtracted twice), then cut into the chunks of the exclusion pass
-  std::vector<int> ex32, chq;
-  std::vector<int64_t> eoff64, choff;
-  if (excl_off != nullptr) {
-    AO_REQUIRE(excl_off[0] == 0, "excl_off[0] = %lld, not 0", (long long)excl_off[0]);
-    for (int64_t q = 0; q < nq; ++q)
-      AO_REQUIRE(excl_off[q + 1] >= excl_off[q], "excl_off decreases at query %lld", (long long)q);
-    const int64_t ne = excl_off[nq];
-    ex32.resize((size_t)ne);
-    for (int64_t e = 0; e < ne; ++e) {
-      AO_REQUIRE(excl_idx[e] >= 0 && excl_idx[e] < I, "tensor %d: excluded row %lld at position %lld is outside [0, %lld)", p,
-                 (long long)excl_idx[e], (long long)e, (long long)I);
-      ex32[(size_t)e] = (int)excl_idx[e];
-    }
-    eoff64.assign((size_t)nq + 1, 0);
-    choff.assign((size_t)nq + 1, 0);
-    int64_t out = 0;
-    for (int64_t q = 0; q < nq; ++q) {
-      std::sort(ex32.begin() + excl_off[q], ex32.begin() + excl_off[q + 1]);
-      const auto last = std::unique(ex32.begin() + excl_off[q], ex32.begin() + excl_off[q + 1]);
-      out = std::copy(ex32.begin() + excl_off[q], last, ex32.begin() + out) - ex32.begin();   // out <= excl_off[q]: moves left
-      eoff64[(size_t)q + 1] = out;
-      const int64_t nch = cdiv(out - eoff64[(size_t)q], (int64_t)kRankExclChunk);
-      choff[(size_t)q + 1] = choff[(size_t)q] + nch;
-      chq.insert(chq.end(), (size_t)nch, (int)q);
-    }
-    ex32.resize((size_t)out);
-    AO_REQUIRE(choff[(size_t)nq] < ((int64_t)1 << 31), "%lld chunks of excluded rows: more than one launch holds", (long long)choff[(size_t)nq]);
-  }
-  const int64_t listed = (int64_t)ex32.size(), chunks = (int64_t)chq.size();
+  RankExclHost xh;
+  rank_prepare_excl(p, I, nq, excl_off, excl_idx, xh);
+  const int64_t listed = (int64_t)xh.ex32.size(), chunks = (int64_t)xh.chq.size();
 
   AO_HIP(hipSetDevice(device_));
   const HeldoutFactors hf = heldout_factors(t, nullptr);
@@ -111,20 +135,7 @@ void Engine::rank_of_run(const char* what, int p, int mode, int64_t nq, const in
     a.W = wgiven.d();
     a.target = tgt.as<int>();
   }
-  if (chunks > 0) {
-    eoff.alloc((size_t)(nq + 1) * sizeof(int64_t));
-    eidx.alloc(ex32.size() * sizeof(int));
-    coff.alloc((size_t)(nq + 1) * sizeof(int64_t));
-    cq.alloc(chq.size() * sizeof(int));
-    AO_HIP(hipMemcpyAsync(eoff.p, eoff64.data(), (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
-    AO_HIP(hipMemcpyAsync(eidx.p, ex32.data(), ex32.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
-    AO_HIP(hipMemcpyAsync(coff.p, choff.data(), (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
-    AO_HIP(hipMemcpyAsync(cq.p, chq.data(), chq.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
-    a.excl_off = eoff.as<int64_t>();
-    a.excl_idx = eidx.as<int>();
-    a.chunk_off = coff.as<int64_t>();
-    a.chunk_q = cq.as<int>();
-  }
+  rank_upload_excl(xh, nq, eoff, eidx, coff, cq, a);
   a.workspace = ws.p;
   a.rank = orank.as<int64_t>();
   a.score = oscore.d();

@@ -210,6 +210,10 @@ struct SolveRun {
   bool has_ho = false;                              // some block has a held-out list
   double ho_best = 0.0;                             // smallest H_i = sum_p w_p sum (y - m)^2 so far ...
   int ho_bad = 0;                                   // ... and the iterations since that were not strictly below it
+  bool has_rl = false;                              // some block has a ranking list
+  bool rk_select = false;                           // aoadmm_rank_track criterion = 1: S selects the kept iterate and may stop the solve
+  double rk_best = 0.0;                             // largest pooled score S so far ...
+  int rk_bad = 0;                                   // ... and the evaluations since that did not improve on it
   std::chrono::steady_clock::time_point t0;
 };
 
@@ -409,9 +413,26 @@ void Engine::record_iteration(SolveRun& r, int iter) {
       // The device still holds the state of iteration `iter`: what was enqueued ahead of this read-back (the prefetched
       // tensor pass, prepare_next_first_mode) writes scratch only, and the next iteration's updates follow the copy in
       // stream order.
-      if (best_.on) best_snapshot(iter);
+      if (best_.on && !r.rk_select) best_snapshot(iter);
     } else {
       ++r.ho_bad;
+    }
+  }
+  if (r.has_rl && iter % track_.every == 0) {        // the ranking sums came in the same read-back (other iterations: stale slots)
+    for (int p = 0; p < n_tensors_; ++p) {
+      TensorInfo& t = tensors_[p];
+      if (t.rl.nq == 0) continue;
+      const double* v = r.host.rank(p);
+      t.rl_trace.insert(t.rl_trace.end(), v, v + kRankSlots);
+    }
+    rank_iters_.push_back(iter);
+    const double S = rank_score(r.host);
+    // larger is better and the comparison is strict; a NaN never becomes the best, a NaN best yields to the first number
+    if (iter == 0 || S > r.rk_best || (std::isnan(r.rk_best) && !std::isnan(S))) {
+      r.rk_best = S; rank_best_iter_ = iter; r.rk_bad = 0;
+      if (best_.on && r.rk_select) best_snapshot(iter);     // the same place and the same reason as above
+    } else {
+      ++r.rk_bad;
     }
   }
   if (iter == 0 || !out->innerIters) return;
@@ -434,18 +455,31 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
   const bool has_ho = has_heldout();
   AO_REQUIRE(opt.heldout_patience >= 0, "heldout_patience = %d < 0", opt.heldout_patience);
   AO_REQUIRE(opt.heldout_patience == 0 || has_ho, "heldout_patience = %d needs a held-out list (aoadmm_tensor_set_heldout)", opt.heldout_patience);
-  AO_REQUIRE(!best_.on || has_ho, "aoadmm_heldout_keep_best needs a held-out list (aoadmm_tensor_set_heldout)");
+  const bool has_rl = has_ranklist();
+  const bool rk_select = track_.criterion == 1;
+  AO_REQUIRE(!rk_select || has_rl, "aoadmm_rank_track criterion = 1 needs a ranking list (aoadmm_tensor_set_ranklist)");
+  AO_REQUIRE(!rk_select || opt.heldout_patience == 0, "aoadmm_rank_track criterion = 1 and heldout_patience = %d: one rule selects the model", opt.heldout_patience);
+  AO_REQUIRE(!best_.on || (rk_select ? has_rl : has_ho), "aoadmm_heldout_keep_best needs a held-out list (aoadmm_tensor_set_heldout)");
   AO_HIP(hipSetDevice(device_));
   ho_best_iter_ = -1;
+  rank_best_iter_ = -1;
+  rank_iters_.clear();
   best_.iter = -1;
-  for (TensorInfo& t : tensors_) t.ho_trace.clear();
+  for (TensorInfo& t : tensors_) { t.ho_trace.clear(); t.rl_trace.clear(); }
+  struct EvalFlag {                                   // rank_eval_now_ does not outlive the solve, however it ends
+    bool& f;
+    ~EvalFlag() { f = false; }
+  } eval_flag{rank_eval_now_};
   solve_setup(opt);
   SolveRun r{opt, out};
   r.has_miss = has_missing();
   r.has_ho = has_ho;
+  r.has_rl = has_rl;
+  r.rk_select = rk_select;
   r.pin.alloc(readback_.bytes);
   r.host = arena_.at(r.pin.p);
 
+  rank_eval_now_ = has_rl;                                                     // iteration 0 is always evaluated
   eval_objective_enqueue(true);                                                // :32
   enqueue_readback(r);
   finish_objective(r);
@@ -458,10 +492,11 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
   const double* f = r.f;
   double fo[4];
   int iter = 1;
-  bool stop = false, ho_stop = false;
-  while (iter <= opt.MaxOuterIters && !stop && !ho_stop) {                     // :87
+  bool stop = false, ho_stop = false, rk_stop = false;
+  while (iter <= opt.MaxOuterIters && !stop && !ho_stop && !rk_stop) {         // :87
     outer_updates(opt, iter, r.has_miss);
     for (int i = 0; i < 4; ++i) fo[i] = f[i];
+    rank_eval_now_ = has_rl && iter % track_.every == 0;
     enqueue_objective(r, iter);
     finish_objective(r);
     if (r.has_miss) r.f_rel_missing = rel_missing_from_host(r.host);           // :436-440
@@ -470,6 +505,7 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
            stop_one(f[3], fo[3], opt);                                         // :456
     if (r.has_miss) stop = stop && (r.f_rel_missing < opt.OuterRelTol);        // :457-459
     ho_stop = opt.heldout_patience > 0 && r.ho_bad >= opt.heldout_patience;    // held-out early stopping (heldout.h)
+    rk_stop = rk_select && track_.patience > 0 && r.rk_bad >= track_.patience;   // counts evaluations (rank_metrics.h)
     if (report && iter % progress_every_ == 0) progress_fn_(progress_user_, iter, r.f, r.f_rel_missing);   // :462-468
     ++iter;
   }
@@ -478,9 +514,9 @@ void Engine::solve(const aoadmm_options& opt, aoadmm_result* out) {
   for (int p = 0; p < n_tensors_; ++p)
     if (tensors_[p].par2) par2_gather_slabs(tensors_[p]);
   AO_HIP(hipStreamSynchronize(stream_));
-  if (best_.on) best_.iter = ho_best_iter_;           // the solve came through: the kept copy may be restored
+  if (best_.on) best_.iter = rk_select ? rank_best_iter_ : ho_best_iter_;   // the solve came through: the kept copy may be restored
   out->OuterIterations = iter - 1;
-  out->exit_code = iter > opt.MaxOuterIters ? 0 : stop ? 1 : 2;                // make_exit_flag.m:4-5; 2: heldout_patience
+  out->exit_code = iter > opt.MaxOuterIters ? 0 : stop ? 1 : ho_stop ? 2 : 3;  // make_exit_flag.m:4-5; 2: heldout_patience, 3: rank patience
   for (int i = 0; i < 4; ++i) out->exit_abs[i] = f[i] < opt.AbsFuncTol ? 1 : 0;
 }
 }  // namespace aoadmm

@@ -25,6 +25,7 @@ import numpy as np
 
 from . import _capi as capi
 from .engine import Engine, constraint_descriptor, default_engine
+from .ranking import parse_rank_metric
 from .sptensor import coo_of, pack_par2_slabs, sptensor
 from .sptensor import slab_gram as _sparse_slab_gram
 from .sptensor import unfold_gram as _sparse_unfold_gram
@@ -477,6 +478,88 @@ def heldout_lists(Z, heldout, patience=0):
     return lists
 
 
+def rank_options(Z, hip, heldout_patience=0):
+    """`alg_options['hip']['rank_lists']`, `['rank_metric']`, `['rank_every']`, `['rank_patience']`, `['rank_criterion']` ->
+    dict(lists={0-based block: (mode 0-based, subs nq x N int64 0-based, exclude or None)}, metric, k, every, patience,
+    criterion), checked on the host before the engine is touched.  `rank_lists` maps 1-based block numbers of CP blocks
+    to dict(mode=1-based position in the block, subs=nq x N 0-based with the target in that column, exclude=(off, idx) or
+    None); None / {} -> no list.  ValueError: a block the model does not have or a PAR2 block, a mode outside the block,
+    subs that are not nq x N integers in range, exclusion lists that do not match nq or hold rows out of range, a metric
+    string `parse_rank_metric` refuses, every < 1, patience < 0, a criterion that is neither 0 nor 1, patience > 0
+    without criterion = 1, and criterion = 1 without a list or together with heldout_patience > 0."""
+    P = len(Z['object'])
+    spec = hip.get('rank_lists')
+    if spec is not None and not isinstance(spec, dict):
+        raise ValueError('rank_lists must be a dict {1-based block number: dict(mode=, subs=, exclude=)}')
+
+    def integer(name, lo, default):
+        v = hip.get(name, default)
+        if isinstance(v, (bool, np.bool_)):
+            v = int(v)
+        try:
+            ok = not isinstance(v, (str, bytes)) and int(v) == v and int(v) >= lo
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('%s must be an integer >= %d, got %r' % (name, lo, v))
+        return int(v)
+
+    metric, k = parse_rank_metric(hip.get('rank_metric', 'ndcg@10'))
+    every = integer('rank_every', 1, 1)
+    patience = integer('rank_patience', 0, 0)
+    criterion = integer('rank_criterion', 0, 0)
+    if criterion not in (0, 1):
+        raise ValueError('rank_criterion must be 0 or 1, got %r' % (criterion,))
+    if patience > 0 and criterion != 1:
+        raise ValueError('rank_patience = %d needs rank_criterion = 1' % patience)
+    lists = {}
+    for q, item in (spec or {}).items():
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or q < 1 or q > P:
+            raise ValueError('rank_lists names Z.object{%s}: the model has %d blocks' % (q, P))
+        p = int(q) - 1
+        if Z['model'][p] == 'PAR2':
+            raise ValueError('rank_lists{%d}: ranking lists are for CP blocks, Z.object{%d} is a PARAFAC2 block' % (q, q))
+        if not isinstance(item, dict) or 'mode' not in item or 'subs' not in item:
+            raise ValueError('rank_lists{%d} must be dict(mode=, subs=, exclude=)' % q)
+        md = [m - 1 for m in Z['modes'][p]]
+        shape = [int(Z['size'][m]) for m in md]
+        mode = item['mode']
+        if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or mode < 1 or mode > len(md):
+            raise ValueError('rank_lists{%d}: mode %r outside [1, %d]' % (q, mode, len(md)))
+        mode = int(mode) - 1
+        subs = np.asarray(item['subs'])
+        if subs.ndim != 2 or subs.shape[1] != len(md):
+            raise ValueError('rank_lists{%d}: subs must be nq x %d, got %s' % (q, len(md), subs.shape))
+        if not np.issubdtype(subs.dtype, np.integer):
+            if not (np.issubdtype(subs.dtype, np.floating) and np.all(np.isfinite(subs)) and np.all(subs == np.floor(subs))):
+                raise ValueError('rank_lists{%d}: subscripts must be integers' % q)
+        subs = np.ascontiguousarray(subs.astype(np.int64))
+        nq = subs.shape[0]
+        for m in range(len(md)):
+            if nq and (subs[:, m].min() < 0 or subs[:, m].max() >= shape[m]):
+                raise ValueError('rank_lists{%d}: a subscript of mode %d is outside [0, %d)' % (q, m + 1, shape[m]))
+        exclude = item.get('exclude')
+        if exclude is not None:
+            try:
+                off, idx = exclude
+            except (TypeError, ValueError):
+                raise ValueError('rank_lists{%d}: exclude must be (off, idx)' % q) from None
+            off = np.ascontiguousarray(np.asarray(off, dtype=np.int64).reshape(-1))
+            idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).reshape(-1))
+            if off.shape[0] != nq + 1 or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != idx.shape[0]:
+                raise ValueError('rank_lists{%d}: exclude[0] must hold nq + 1 = %d non-decreasing offsets from 0 to len(exclude[1])' % (q, nq + 1))
+            if idx.shape[0] and (idx.min() < 0 or idx.max() >= shape[mode]):
+                raise ValueError('rank_lists{%d}: an excluded row is outside [0, %d)' % (q, shape[mode]))
+            exclude = (off, idx)
+        if nq:
+            lists[p] = (mode, subs, exclude)
+    if criterion == 1 and not lists:
+        raise ValueError('rank_criterion = 1 needs a ranking list (alg_options.hip.rank_lists)')
+    if criterion == 1 and int(heldout_patience) > 0:
+        raise ValueError('rank_criterion = 1 and heldout_patience = %d: one rule selects the model' % int(heldout_patience))
+    return dict(lists=lists, metric=metric, k=k, every=every, patience=patience, criterion=criterion)
+
+
 def heldout_keep_best_option(value, lists):
     """`alg_options['hip']['heldout_keep_best']` -> 0 or 1, checked on the host before the engine is touched.  ValueError:
     a value that is not an integer or is neither 0 nor 1 (True / False count), and 1 without a held-out list (`lists`
@@ -806,6 +889,8 @@ def run_solver(eng, alg_options, nb_modes, has_missing=False):
         out['exit_flag'] = 'maxIterations'                                   # make_exit_flag.m:4-5
     elif res.exit_code == 2:
         out['exit_flag'] = 'heldoutPatience'                                 # alg_options.hip.heldout_patience
+    elif res.exit_code == 3:
+        out['exit_flag'] = 'rankPatience'                                    # alg_options.hip.rank_patience
     else:
         out['exit_flag'] = {nm: ('AbsFuncTol' if res.exit_abs[i] else 'RelFuncTol') for i, nm in enumerate(names)}
     return out
@@ -857,12 +942,20 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
     # alg_options['hip']['heldout'] = {1-based block: (subs, vals) | sptensor} and ['heldout_patience'] (`heldout_lists`):
     # entries kept out of the fit, scored on the device with every evaluation of the objective
     held = heldout_lists(Z, hip.get('heldout'), hip.get('heldout_patience', 0))
-    # alg_options['hip']['heldout_keep_best'] (default 0): 1 returns the iterate with the smallest held-out sum
-    keep_best = heldout_keep_best_option(hip.get('heldout_keep_best', 0), held)
+    # alg_options['hip']['rank_lists'] = {1-based block: dict(mode=, subs=, exclude=)} with ['rank_metric'], ['rank_every'],
+    # ['rank_patience'] and ['rank_criterion'] (`rank_options`): ranking metrics of held-out rows tracked inside the solve
+    rank = rank_options(Z, hip, hip.get('heldout_patience', 0))
+    # alg_options['hip']['heldout_keep_best'] (default 0): 1 returns the iterate with the smallest held-out sum, or with
+    # rank_criterion = 1 the one with the best ranking score
+    keep_best = heldout_keep_best_option(hip.get('heldout_keep_best', 0), rank['lists'] if rank['criterion'] == 1 else held)
     build_model(eng, Z, precision, sparse_sharding=sharding, observed_only=observed_opt, entry_weights=weights_opt,
                 unstored_weight=alpha_opt)
     for p, (hs, hv) in sorted(held.items()):
         eng.set_heldout(p, hs, hv)
+    for p, (rmode, rsubs, rexcl) in sorted(rank['lists'].items()):
+        eng.set_ranklist(p, rmode, rsubs, exclude=rexcl)
+    if rank['lists'] or rank['criterion']:
+        eng.rank_track(rank['metric'], rank['k'], rank['every'], rank['patience'], rank['criterion'])
     if keep_best:
         eng.heldout_keep_best(True)
     upload_state(eng, Z, G)
@@ -877,8 +970,13 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
             out['func_heldout'][p + 1], out['heldout_best_iter'] = eng.heldout_trace(p)
             out['heldout_sumsq'][p + 1] = float(np.sum(hv * hv))
             out['heldout_count'][p + 1] = int(hv.shape[0])
+    if rank['lists']:
+        # out.rank_trace{block}: per evaluation the iteration, the counts, the means hit / ndcg / mrr / auc and the raw sums
+        # (`Engine.rank_trace`); out.rank_best_iter: the iteration of the best pooled score
+        out['rank_trace'] = {p + 1: eng.rank_trace(p) for p in sorted(rank['lists'])}
+        out['rank_best_iter'] = next(iter(out['rank_trace'].values()))['best_iter']
     if keep_best:
-        # Fac and Zhat are the iterate heldout_best_iter; every other field of out still describes the whole run
+        # Fac and Zhat are the iterate heldout_best_iter (rank_criterion = 1: rank_best_iter); every other field of out still describes the whole run
         out['heldout_restored_iter'] = eng.heldout_restore_best()
     Fac = download_state(eng, Z, G)
     Zhat = []

@@ -385,6 +385,113 @@ class Engine:
                          rank.ctypes.data_as(i64p), capi.dptr(score), ncand.ctypes.data_as(i64p)))
         return rank, score, ncand
 
+    @staticmethod
+    def _exclude_arrays(what, nq, exclude):
+        """(off, ex) int64 arrays of an `exclude = (off, idx)` argument, checked against nq; (None, None) without one."""
+        if exclude is None:
+            return None, None
+        off = np.ascontiguousarray(np.asarray(exclude[0], dtype=np.int64).reshape(-1))
+        ex = np.ascontiguousarray(np.asarray(exclude[1], dtype=np.int64).reshape(-1))
+        if off.shape[0] != nq + 1:
+            raise ValueError('%s: exclude[0] must hold nq + 1 = %d offsets, got %d' % (what, nq + 1, off.shape[0]))
+        if off[-1] != ex.shape[0]:
+            raise ValueError('%s: exclude[0][-1] = %d but exclude[1] holds %d rows' % (what, off[-1], ex.shape[0]))
+        if ex.shape[0] == 0:
+            ex = np.zeros(1, dtype=np.int64)          # a valid address for an empty list
+        return off, ex
+
+    def set_ranklist(self, p, mode, subs, exclude=None):
+        """Attaches the ranking list of CP block p (`aoadmm_tensor_set_ranklist`): the arguments of `rank_of` (subs nq x N,
+        0-based, column `mode` the target row; exclude = (off, idx) in any order, repeats allowed).  An empty subs
+        removes the list; an error leaves the previous one.  The list is checked, sorted and uploaded once and belongs
+        to the model: `build_model` drops it, a new upload of the block's data keeps it.  A solve then evaluates it at
+        iteration 0 and every `every`-th iteration (`rank_track`) beside the objective and keeps the metric sums as a
+        trace (`rank_trace`); nothing else the solve computes changes."""
+        subs = np.asarray(subs, dtype=np.int64)
+        if subs.size == 0:
+            capi.check(self.lib.aoadmm_tensor_set_ranklist(self.h, int(p), int(mode), 0, None, None, None))
+            return
+        subs = self._subs_f(subs, 'set_ranklist')
+        nq = int(subs.shape[0])
+        off, ex = self._exclude_arrays('set_ranklist', nq, exclude)
+        i64p = C.POINTER(C.c_int64)
+        capi.check(self.lib.aoadmm_tensor_set_ranklist(self.h, int(p), int(mode), nq, subs.ctypes.data_as(i64p),
+                                                       off.ctypes.data_as(i64p) if off is not None else None,
+                                                       ex.ctypes.data_as(i64p) if ex is not None else None))
+
+    def ranklist_info(self, p):
+        """dict(nq, mode, listed, resident_bytes) of block p's ranking list (`aoadmm_ranklist_info`): listed counts the
+        excluded rows kept after the per-query removal of repeats; nq = 0 and mode = -1 without a list."""
+        nq, mode, listed, nb = C.c_int64(0), C.c_int(-1), C.c_int64(0), C.c_int64(0)
+        capi.check(self.lib.aoadmm_ranklist_info(self.h, int(p), C.byref(nq), C.byref(mode), C.byref(listed), C.byref(nb)))
+        return dict(nq=nq.value, mode=mode.value, listed=listed.value, resident_bytes=nb.value)
+
+    def rank_track(self, metric='ndcg', k=10, every=1, patience=0, criterion=0):
+        """What a solve does with the ranking lists (`aoadmm_rank_track`).  metric: 'hit', 'ndcg', 'mrr' or 'auc'; k: the
+        cut-off of hit and ndcg; the lists are evaluated at iteration 0 and every `every`-th iteration.  At an
+        evaluation S is the pooled mean of the metric over the blocks with a list (`rank_rule` states the best /
+        patience rule).  criterion = 0: trace only.  criterion = 1: S selects the iterate `heldout_keep_best` keeps, and
+        patience = n > 0 stops the solve after n consecutive evaluations without improvement
+        (`exit_flag = 'rankPatience'`).  Belongs to the model: `build_model` restores the defaults."""
+        try:
+            mid = capi.RANK_METRICS[metric]
+        except (KeyError, TypeError):
+            raise ValueError("rank_track: metric must be one of 'hit', 'ndcg', 'mrr', 'auc', got %r" % (metric,)) from None
+        k = int(k)
+        if not 1 <= k < 2 ** 31:
+            raise ValueError('rank_track: k = %d outside [1, 2^31)' % k)
+        capi.check(self.lib.aoadmm_rank_track(self.h, mid, k, int(every), int(patience), int(criterion)))
+
+    def rank_trace(self, p):
+        """The ranking trace of block p's list over the last solve (`aoadmm_rank_trace`): a dict of arrays with one
+        entry per evaluation: `iters`, the counts `n`, `n_auc`, the means `hit`, `ndcg`, `mrr` (over n) and `auc` (over
+        n_auc; a mean over nothing is NaN), the raw sums `hits`, `ndcg_sum`, `mrr_sum`, `auc_sum`, and `best_iter`, the
+        iteration of the best pooled score (-1 without a list)."""
+        ln, best = C.c_int(0), C.c_int(-1)
+        capi.check(self.lib.aoadmm_rank_trace(self.h, int(p), 0, None, 0, C.byref(ln), None, C.byref(best)))
+        n = ln.value
+        iters = np.zeros(max(n, 1), dtype=np.int32)
+        sums = np.zeros((capi.RANKSUM_COUNT, max(n, 1)))
+        for what in range(capi.RANKSUM_COUNT):
+            capi.check(self.lib.aoadmm_rank_trace(self.h, int(p), what, capi.dptr(sums[what]), n, None,
+                                                  iters.ctypes.data_as(C.POINTER(C.c_int)), None))
+        return self._rank_trace_dict(iters[:n].astype(np.int64), sums[:, :n], best.value)
+
+    @staticmethod
+    def _rank_trace_dict(iters, sums, best_iter):
+        cnt, cnt_auc = sums[capi.RANKSUM_N], sums[capi.RANKSUM_N_AUC]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            mean = lambda x, c: np.where(c > 0, x / c, np.nan)
+            return dict(iters=iters, n=cnt.astype(np.int64), n_auc=cnt_auc.astype(np.int64),
+                        hit=mean(sums[capi.RANKSUM_HITS], cnt), ndcg=mean(sums[capi.RANKSUM_NDCG], cnt),
+                        mrr=mean(sums[capi.RANKSUM_MRR], cnt), auc=mean(sums[capi.RANKSUM_AUC], cnt_auc),
+                        hits=sums[capi.RANKSUM_HITS].copy(), ndcg_sum=sums[capi.RANKSUM_NDCG].copy(),
+                        mrr_sum=sums[capi.RANKSUM_MRR].copy(), auc_sum=sums[capi.RANKSUM_AUC].copy(), best_iter=int(best_iter))
+
+    def ranklist_last(self, p):
+        """(rank, score, ncand) of block p's ranking list as its last evaluation left them (`aoadmm_ranklist_last`): what
+        `rank_of` returns for the factors that evaluation used."""
+        nq = self.ranklist_info(p)['nq']
+        rank = np.full(max(nq, 1), -1, dtype=np.int64)
+        score = np.full(max(nq, 1), np.nan)
+        ncand = np.zeros(max(nq, 1), dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        capi.check(self.lib.aoadmm_ranklist_last(self.h, int(p), rank.ctypes.data_as(i64p), capi.dptr(score), ncand.ctypes.data_as(i64p)))
+        return rank[:nq], score[:nq], ncand[:nq]
+
+    def op_rank_metrics(self, rank, ncand, k):
+        """The device reduction from ranks to metric sums on host arrays (`aoadmm_op_rank_metrics`): eight doubles,
+        `capi.RANKSUM_*` order (n, n_auc, hits, sum ndcg, sum mrr, sum auc, two spare zeros)."""
+        rank = np.ascontiguousarray(np.asarray(rank, dtype=np.int64).reshape(-1))
+        ncand = np.ascontiguousarray(np.asarray(ncand, dtype=np.int64).reshape(-1))
+        if rank.shape[0] != ncand.shape[0]:
+            raise ValueError('op_rank_metrics: %d ranks but %d candidate counts' % (rank.shape[0], ncand.shape[0]))
+        out = np.zeros(8)
+        i64p = C.POINTER(C.c_int64)
+        capi.check(self.lib.aoadmm_op_rank_metrics(self.h, int(rank.shape[0]), rank.ctypes.data_as(i64p), ncand.ctypes.data_as(i64p),
+                                                   int(k), capi.dptr(out)))
+        return out
+
     def block_rank(self, p):
         """The number of components R of block p (`aoadmm_tensor_rank`), from the model the engine holds."""
         r = C.c_int(0)
@@ -474,7 +581,8 @@ class Engine:
         """(ms, launches, bytes, flops) of a kernel class since the last reset (`aoadmm_kernel_stats`); which = 3:
         MTTKRPs of sparse blocks (of a sharded block: this rank's share), passes over the nonzeros of PARAFAC2
         blocks with sparse slabs and EM steps of observed-only blocks; which = 4 + n: the pass of those EM steps over
-        the copy of tensor mode n; which = 12: the held-out passes; which = 13: the top-k completions and the ranks of targets (one launch per `topk` or `rank_of` call);
+        the copy of tensor mode n; which = 12: the held-out passes; which = 13: the top-k completions and the ranks of targets (one launch per `topk` or `rank_of` call and per
+        evaluation of a ranking list inside a solve);
         which = 14: the fold-in of new rows (one launch per `fold_in` call, weighted or not)."""
         ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         capi.check(self.lib.aoadmm_kernel_stats(self.h, int(which), int(bool(reset)), C.byref(ms), C.byref(n),

@@ -571,6 +571,83 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       }
     }
 
+  // ---- options.hip.rank_lists: a cell per block of a struct with `mode` (1-based position in the block), `subs` (nq x N,
+  // 1-based; column `mode` holds the target row) and optionally `excl_off` (nq + 1 offsets from 0) with `excl_idx` (1-based
+  // rows): ranking metrics of held-out rows, evaluated on the device beside the objective (aoadmm_tensor_set_ranklist).
+  // options.hip.rank_metric ('ndcg@10', 'hit@5', 'mrr', 'auc'), rank_every, rank_patience, rank_criterion: aoadmm_rank_track.
+  std::vector<char> has_rank(P, 0);
+  int rank_criterion = 0;
+  if (const mxArray* hip = field(opt, "hip", false)) {
+    if (const mxArray* rl = field(hip, "rank_lists", false)) {
+      if (!mxIsCell(rl) || mxGetNumberOfElements(rl) > (mwSize)P)
+        mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.rank_lists must be a cell with at most one entry per block of Z.object");
+      for (mwSize p = 0; p < mxGetNumberOfElements(rl); ++p) {
+        const mxArray* e = mxGetCell(rl, p);
+        if (!e || mxIsEmpty(e)) continue;
+        if (!mxIsStruct(e)) mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.rank_lists{%d} must be a struct with mode and subs", (int)p + 1);
+        const mxArray* rs = field(e, "subs");
+        const mwSize N = mxGetNumberOfElements(mxGetCell(modes, p));
+        const mwSize nq = mxGetM(rs);
+        if (!mxIsDouble(rs) || mxGetN(rs) != N)
+          mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.rank_lists{%d}: subs must be a double nq x %d array", (int)p + 1, (int)N);
+        if (nq == 0) continue;
+        auto ints = [&](const mxArray* a, double shift, const char* what) {
+          std::vector<int64_t> v(mxGetNumberOfElements(a));
+          const double* d = mxGetDoubles(a);
+          for (size_t i = 0; i < v.size(); ++i) {
+            if (d[i] != std::floor(d[i]))
+              mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.rank_lists{%d}: %s must hold integers", (int)p + 1, what);
+            v[i] = (int64_t)d[i] - (int64_t)shift;
+          }
+          return v;
+        };
+        const std::vector<int64_t> s0 = ints(rs, 1.0, "subs");   // column-major nq x N as subs is; 1-based -> 0-based
+        std::vector<int64_t> eo, ei;
+        const mxArray* xo = field(e, "excl_off", false);
+        const mxArray* xi = field(e, "excl_idx", false);
+        if (xo && !mxIsEmpty(xo)) {
+          if (!mxIsDouble(xo) || mxGetNumberOfElements(xo) != nq + 1 || (xi && !mxIsDouble(xi)))
+            mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.rank_lists{%d}: excl_off must hold nq + 1 offsets and excl_idx doubles", (int)p + 1);
+          eo = ints(xo, 0.0, "excl_off");
+          if (xi) ei = ints(xi, 1.0, "excl_idx");
+          if (eo.back() != (int64_t)ei.size())
+            mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.rank_lists{%d}: excl_off ends at %lld, excl_idx holds %lld rows", (int)p + 1,
+                              (long long)eo.back(), (long long)ei.size());
+          if (ei.empty()) ei.push_back(0);                     // a valid address for an empty list
+        }
+        check(aoadmm_tensor_set_ranklist(g_ctx, (int)p, (int)scalar(e, "mode") - 1, (int64_t)nq, s0.data(), eo.empty() ? nullptr : eo.data(),
+                                         eo.empty() ? nullptr : ei.data()));   // ranges: the library
+        has_rank[p] = 1;
+      }
+    }
+    int metric = AOADMM_RANK_NDCG, rk = 10, every = 1, patience = 0;
+    bool given = false;
+    if (const mxArray* f = field(hip, "rank_metric", false)) {
+      if (!mxIsChar(f)) mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.rank_metric must be a string such as 'ndcg@10', 'hit@5', 'mrr' or 'auc'");
+      const std::string spec = str(f);
+      const size_t at = spec.find('@');
+      const std::string name = spec.substr(0, at);
+      if (name == "hit") metric = AOADMM_RANK_HIT;
+      else if (name == "ndcg") metric = AOADMM_RANK_NDCG;
+      else if (name == "mrr") metric = AOADMM_RANK_MRR;
+      else if (name == "auc") metric = AOADMM_RANK_AUC;
+      else mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.rank_metric '%s': the metric must be hit, ndcg, mrr or auc", spec.c_str());
+      if (at != std::string::npos) {
+        const std::string ktxt = spec.substr(at + 1);
+        if ((metric != AOADMM_RANK_HIT && metric != AOADMM_RANK_NDCG) || ktxt.empty() || ktxt.size() > 10 ||
+            ktxt.find_first_not_of("0123456789") != std::string::npos || std::stoll(ktxt) < 1 || std::stoll(ktxt) >= (1LL << 31))
+          mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.rank_metric '%s': the cut-off must be an integer in [1, 2^31) after hit or ndcg", spec.c_str());
+        rk = (int)std::stoll(ktxt);
+      }
+      given = true;
+    }
+    if (const mxArray* f = field(hip, "rank_every", false)) { every = (int)mxGetScalar(f); given = true; }
+    if (const mxArray* f = field(hip, "rank_patience", false)) { patience = (int)mxGetScalar(f); given = true; }
+    if (const mxArray* f = field(hip, "rank_criterion", false)) { rank_criterion = (int)mxGetScalar(f); given = true; }
+    const bool any_rank = std::find(has_rank.begin(), has_rank.end(), 1) != has_rank.end();
+    if (given || any_rank) check(aoadmm_rank_track(g_ctx, metric, rk, every, patience, rank_criterion));   // ranges and combinations: the library
+  }
+
   // ---- state: the struct G (init_coupled_AOADMM_CMTF.m:41-45)
   for (int m = 0; m < n_modes; ++m) {
     put_state_maybe_cell(AOADMM_F_FAC, m, mxGetCell(fac, m));
@@ -622,7 +699,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       if (mxGetNumberOfElements(f) != 1 || (v != 0.0 && v != 1.0))
         mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.heldout_keep_best must be 0 or 1");
       keep_best = v == 1.0;
-      if (keep_best && std::find(has_list.begin(), has_list.end(), 1) == has_list.end())
+      const std::vector<char>& serves = rank_criterion == 1 ? has_rank : has_list;   // rank_criterion = 1: the best ranking score is kept
+      if (keep_best && std::find(serves.begin(), serves.end(), 1) == serves.end())
         mexErrMsgIdAndTxt("cmtf:hip:invalid", "options.hip.heldout_keep_best = 1 needs a held-out list (options.hip.heldout)");
     }
   if (keep_best) check(aoadmm_heldout_keep_best(g_ctx, 1));
@@ -685,6 +763,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     const bool any_list = std::find(has_list.begin(), has_list.end(), 1) != has_list.end();
     if (any_list) { fn.push_back("func_heldout"); fn.push_back("heldout_best_iter"); }   /* only with options.hip.heldout */
     if (keep_best) fn.push_back("heldout_restored_iter");                  /* only with options.hip.heldout_keep_best */
+    const bool any_rank = std::find(has_rank.begin(), has_rank.end(), 1) != has_rank.end();
+    if (any_rank) { fn.push_back("rank_trace"); fn.push_back("rank_best_iter"); }        /* only with options.hip.rank_lists */
     mxArray* out = mxCreateStructMatrix(1, 1, (int)fn.size(), fn.data());
     const int it = res.OuterIterations;
     auto vec = [&](const std::vector<double>& v, int len) {
@@ -714,10 +794,49 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       mxSetField(out, 0, "heldout_best_iter", mxCreateDoubleScalar(best));
     }
     if (keep_best) mxSetField(out, 0, "heldout_restored_iter", mxCreateDoubleScalar(restored_iter));
+    if (any_rank) {
+      // out.rank_trace{p}: per evaluation of block p's ranking list the iteration, the counts n and n_auc, the means hit,
+      // ndcg, mrr (over n) and auc (over n_auc; NaN over nothing) and the raw sums; out.rank_best_iter: the iteration of
+      // the best pooled score
+      const char* rf[] = {"iters", "n", "n_auc", "hit", "ndcg", "mrr", "auc", "hits", "ndcg_sum", "mrr_sum", "auc_sum"};
+      mxArray* rt = mxCreateCellMatrix(1, P);
+      int best = -1;
+      for (int p = 0; p < P; ++p) {
+        if (!has_rank[p]) continue;
+        int len = 0;
+        check(aoadmm_rank_trace(g_ctx, p, AOADMM_RANKSUM_N, nullptr, 0, &len, nullptr, &best));
+        std::vector<int> iters((size_t)len + 1);
+        std::vector<std::vector<double>> sums(AOADMM_RANKSUM_COUNT, std::vector<double>((size_t)len + 1));
+        for (int w = 0; w < AOADMM_RANKSUM_COUNT; ++w) check(aoadmm_rank_trace(g_ctx, p, w, sums[w].data(), len, nullptr, iters.data(), nullptr));
+        mxArray* st = mxCreateStructMatrix(1, 1, 11, rf);
+        std::vector<double> itd(iters.begin(), iters.end());
+        mxSetField(st, 0, "iters", vec(itd, len));
+        mxSetField(st, 0, "n", vec(sums[AOADMM_RANKSUM_N], len));
+        mxSetField(st, 0, "n_auc", vec(sums[AOADMM_RANKSUM_N_AUC], len));
+        auto mean = [&](int num, int den) {
+          std::vector<double> m((size_t)len + 1);
+          for (int e = 0; e < len; ++e) m[e] = sums[den][e] > 0 ? sums[num][e] / sums[den][e] : mxGetNaN();
+          return vec(m, len);
+        };
+        mxSetField(st, 0, "hit", mean(AOADMM_RANKSUM_HITS, AOADMM_RANKSUM_N));
+        mxSetField(st, 0, "ndcg", mean(AOADMM_RANKSUM_NDCG, AOADMM_RANKSUM_N));
+        mxSetField(st, 0, "mrr", mean(AOADMM_RANKSUM_MRR, AOADMM_RANKSUM_N));
+        mxSetField(st, 0, "auc", mean(AOADMM_RANKSUM_AUC, AOADMM_RANKSUM_N_AUC));
+        mxSetField(st, 0, "hits", vec(sums[AOADMM_RANKSUM_HITS], len));
+        mxSetField(st, 0, "ndcg_sum", vec(sums[AOADMM_RANKSUM_NDCG], len));
+        mxSetField(st, 0, "mrr_sum", vec(sums[AOADMM_RANKSUM_MRR], len));
+        mxSetField(st, 0, "auc_sum", vec(sums[AOADMM_RANKSUM_AUC], len));
+        mxSetCell(rt, p, st);
+      }
+      mxSetField(out, 0, "rank_trace", rt);
+      mxSetField(out, 0, "rank_best_iter", mxCreateDoubleScalar(best));
+    }
     if (res.exit_code == 0) {
       mxSetField(out, 0, "exit_flag", mxCreateString("maxIterations"));      /* make_exit_flag.m:4-5 */
     } else if (res.exit_code == 2) {
       mxSetField(out, 0, "exit_flag", mxCreateString("heldoutPatience"));    /* options.hip.heldout_patience */
+    } else if (res.exit_code == 3) {
+      mxSetField(out, 0, "exit_flag", mxCreateString("rankPatience"));       /* options.hip.rank_patience */
     } else {
       const char* q[] = {"f_tensors", "f_couplings", "f_constraints", "f_PAR2_couplings"};
       mxArray* ef = mxCreateStructMatrix(1, 1, 4, q);

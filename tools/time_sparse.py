@@ -8,6 +8,7 @@ data on the same GPU.
     python3 tools/time_sparse.py --observed-only --weights [ALPHA] [--reps 7] [--out profiles/sparse_weighted_time.jsonl] ...
     python3 tools/time_sparse.py --heldout [FRAC] [--skew] [--reps 7] [--out profiles/sparse_heldout_time.jsonl] ...
     python3 tools/time_sparse.py --heldout [FRAC] --keep-best [--out profiles/heldout_keep_best_time.jsonl] ...
+    python3 tools/time_sparse.py --ranklist NQ [--rank-every M] [--reps 7] [--out profiles/rank_track_time.jsonl] ...
 
 Prints one JSON line per (layout, mode) and a summary line.  Layouts: 'colmajor' gathers from the column-major factors
 (what aoadmm_resident_mttkrp sees before any solve), 'rowmajor' after one outer iteration, when the Gram kernel has left
@@ -54,6 +55,13 @@ without it, alternating.  Medians of --reps (at least 7).  `per_entry_ratio` is 
 the time per nonzero of a residual pass over modes 2 and 3 (both do N gathers per entry; the held-out pass writes
 nothing).  The list is scored in the caller's order and again sorted by its first subscript on the host, which is what
 a sort at attach time would give the pass.
+--ranklist NQ times a ranking list of NQ queries along the first mode tracked inside a solve,
+without exclusions and with 100 excluded rows per query: the wall time of an outer iteration with the list attached and
+removed, alternating in one process (every --rank-every-th iteration is evaluated; the added time is per evaluated
+iteration), the HIP-event time of the evaluation's launches inside the solve (aoadmm_kernel_stats(13): the rank pass and
+the two launches of the metric reduction), and next to it the launches of a stand-alone `Engine.rank_of` of the same
+list.  `rank_metrics` lines time `Engine.op_rank_metrics` (wall, uploads included) at 16 384 and 10^7 queries.
+
 --heldout FRAC --keep-best times solves of 4 iterations (wall) of the plain block with the list attached and
 aoadmm_heldout_keep_best on and off, alternating, and one aoadmm_heldout_restore_best.  The held-out values are the
 model's own after those 4 iterations (the solve is bit-reproducible), so that the held-out sum falls from iteration to
@@ -98,6 +106,8 @@ def main():
     ap.add_argument('--weights', type=float, nargs='?', const=0.1, default=None, metavar='ALPHA')
     ap.add_argument('--heldout', type=float, nargs='?', const=0.1, default=None, metavar='FRAC')
     ap.add_argument('--keep-best', action='store_true')
+    ap.add_argument('--ranklist', type=int, default=None, metavar='NQ')
+    ap.add_argument('--rank-every', type=int, default=1, metavar='M')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.keep_best and a.heldout is None:
@@ -108,8 +118,13 @@ def main():
         if not 0.0 <= a.weights <= 1.0:
             ap.error('--weights ALPHA must lie inside [0, 1]')
         a.reps = max(a.reps, 7)
+    if a.ranklist is not None:
+        if a.ranklist < 1 or a.rank_every < 1:
+            ap.error('--ranklist NQ and --rank-every M must be positive')
+        a.reps = max(a.reps, 7)
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'sparse_weighted_time.jsonl' if a.weights is not None else
+        a.out = os.path.join(ROOT, 'profiles', 'rank_track_time.jsonl' if a.ranklist is not None else
+                             'sparse_weighted_time.jsonl' if a.weights is not None else
                              'heldout_keep_best_time.jsonl' if a.keep_best else
                              'sparse_heldout_time.jsonl' if a.heldout is not None else 'sparse_observed_time.jsonl')
     if a.heldout is not None:
@@ -125,7 +140,7 @@ def main():
     N, R, nnz = len(dims), a.R, int(a.nnz)
     if (a.as_rank is None) != (a.of is None):
         ap.error('--as-rank and --of go together')
-    if a.nvecs or a.of is not None or a.observed_only or a.heldout is not None:
+    if a.nvecs or a.of is not None or a.observed_only or a.heldout is not None or a.ranklist is not None:
         a.no_torch = True
     rng = np.random.default_rng(a.seed)
     t0 = time.time()
@@ -139,7 +154,7 @@ def main():
     t_gen = time.time() - t0
     eng = pkg.Engine(0)
     try:
-        (run_nvecs if a.nvecs else run_share if a.of is not None else run_weighted if a.weights is not None else
+        (run_ranklist if a.ranklist is not None else run_nvecs if a.nvecs else run_share if a.of is not None else run_weighted if a.weights is not None else
          run_observed if a.observed_only else
          run_heldout if a.heldout is not None else run)(a, eng, dims, N, R, nnz, subs, vals, t_gen)
     finally:
@@ -659,6 +674,112 @@ def run_heldout(a, eng, dims, N, R, nnz, subs, vals, t_gen):
                   'added_ms': round(float(np.median(w_list)) - float(np.median(w_none)), 4)})
     finally:
         obs.close()
+        out.close()
+
+
+def run_ranklist(a, eng, dims, N, R, nnz, subs, vals, t_gen):
+    lib = eng.lib
+    out = open(a.out, 'a')
+
+    def emit(r):
+        line = json.dumps(r)
+        print(line, flush=True)
+        out.write(line + '\n')
+        out.flush()
+
+    def mmm(v):
+        return [round(float(np.median(v)), 4), round(min(v), 4), round(max(v), 4)]
+
+    def solve(e, iters):
+        o = capi.Options()
+        o.MaxOuterIters, o.MaxInnerIters, o.use_dimtree = iters, 1, 1
+        res = capi.Result()
+        e.synchronize()
+        t0 = time.time()
+        capi.check(lib.aoadmm_solve(e.h, C.byref(o), C.byref(res)))
+        e.synchronize()
+        return (time.time() - t0) * 1e3
+
+    def set_factors(e):
+        rng = np.random.default_rng(a.seed + 1)
+        for m in range(N):
+            Um = np.asfortranarray(rng.random((dims[m], R)))
+            capi.check(lib.aoadmm_state_set(e.h, capi.F_FAC, m, 0, capi.dptr(Um), dims[m], R))
+
+    M, nq = a.rank_every, a.ranklist
+    span = 2 * M                                      # iterations between the two timed solves: two evaluations
+
+    def iteration(e):
+        """wall time per outer iteration and, with a list, the event time of one evaluation's launches"""
+        set_factors(e)
+        t1 = solve(e, M)
+        set_factors(e)
+        e.kernel_stats(13, reset=True)
+        t3 = solve(e, M + span)
+        ms, launches, _, _ = e.kernel_stats(13, reset=True)
+        return (t3 - t1) / span, (ms / launches if launches else 0.0), launches
+
+    try:
+        h = eng.h
+        capi.check(lib.aoadmm_model_begin(h, N, 1, 0))
+        for m, s in enumerate(dims):
+            capi.check(lib.aoadmm_model_set_mode(h, m, s, R))
+        capi.check(lib.aoadmm_model_add_cp(h, 0, N, (C.c_int * N)(*range(N)), 1.0))
+        for m in range(N):
+            capi.check(lib.aoadmm_model_set_coupling(h, m, -1, None, 0, 0, None, 0, 0))
+        capi.check(lib.aoadmm_model_end(h))
+        eng.upload_coo(0, subs, vals)
+        set_factors(eng)
+        solve(eng, 1)                                 # row-major factor copies
+        emit({'what': 'setup', 'dims': dims, 'nnz_given': nnz, 'R': R, 'skew': a.skew, 'reps': a.reps, 'nq': nq, 'rank_every': M,
+              'gen_s': round(t_gen, 2)})
+        rng = np.random.default_rng(a.seed + 2)
+        q = np.stack([rng.integers(0, s, nq) for s in dims], axis=1).astype(np.int64)
+        for ne in (0, 100):
+            ex = None
+            if ne:
+                ex = (np.arange(nq + 1, dtype=np.int64) * ne, rng.integers(0, dims[0], nq * ne).astype(np.int64))
+
+            def alone():
+                eng.kernel_stats(13, reset=True)
+                eng.rank_of(0, 0, q, exclude=ex)
+                ms, launches, _, _ = eng.kernel_stats(13, reset=True)
+                assert launches == 1
+                return ms
+
+            t0 = time.time()
+            eng.set_ranklist(0, 0, q, exclude=ex)
+            t_attach = (time.time() - t0) * 1e3
+            eng.rank_track(metric='ndcg', k=10, every=M)
+            info = eng.ranklist_info(0)
+            iteration(eng), alone()                   # warm-up
+            w_list, w_none, ev, sa = [], [], [], []
+            for _ in range(a.reps):                   # alternating: list attached, list removed, the stand-alone call
+                eng.set_ranklist(0, 0, q, exclude=ex)
+                w, e_ms, launches = iteration(eng)
+                assert launches == 4                  # 3 M iterations: evaluations at 0, M, 2 M and 3 M
+                w_list.append(w)
+                ev.append(e_ms)
+                eng.set_ranklist(0, 0, q[:0])
+                w_none.append(iteration(eng)[0])
+                sa.append(alone())
+            added_wall = (float(np.median(w_list)) - float(np.median(w_none))) * M
+            emit({'what': 'rank_track_iteration', 'nq': nq, 'excl_per_query': ne, 'rank_every': M, 'attach_ms': round(t_attach, 3),
+                  'ranklist_info': info, 'iter_ms_wall_with_list': mmm(w_list), 'iter_ms_wall_no_list': mmm(w_none),
+                  'added_ms_wall_per_evaluated_iteration': round(added_wall, 4), 'evaluation_ms_events_in_solve': mmm(ev),
+                  'rank_of_alone_ms_events': mmm(sa),
+                  'evaluation_minus_alone_ms': round(float(np.median(ev)) - float(np.median(sa)), 4)})
+        for n in (16384, 10 ** 7):
+            rank = rng.integers(-1, 10 ** 6, n).astype(np.int64)
+            ncand = np.full(n, 10 ** 6, dtype=np.int64)
+            eng.op_rank_metrics(rank, ncand, 10)
+            t = []
+            for _ in range(a.reps):
+                t0 = time.time()
+                eng.op_rank_metrics(rank, ncand, 10)
+                t.append((time.time() - t0) * 1e3)
+            emit({'what': 'rank_metrics', 'n': n, 'op_ms_wall_with_uploads': mmm(t), 'bytes_read_by_the_kernels': 16 * n})
+    finally:
         out.close()
 
 
