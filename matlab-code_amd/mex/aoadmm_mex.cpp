@@ -8,10 +8,13 @@
  * file walks them with the mx* API, feeds the engine through the C ABI and builds
  * `Fac` (same fields as G) and `out` (cmtf_fun_AOADMM.m:480-494).
  *
- * Build (on a machine that has MATLAB; neither mex.h nor libmx exist in the
- * development container, where this file is only syntax-checked against
- * mex_stub/mex.h by `make -C matlab-code_amd/mex check`):
+ * Build (on a machine that has MATLAB):
  *     mex -R2018a -largeArrayDims aoadmm_mex.cpp -I../../include -L.. -laoadmm_hip
+ * Neither mex.h nor libmx exist where the project is developed and tested.  There this file is compiled against
+ * mex_stub/mex.h and linked with a functional mock of the C Matrix API (tests/mxmock/mxmock.cpp), and its logic is
+ * executed: on the CPU against a recording fake of the C ABI (tests/test_mex_gateway_host.py: every marshalled value,
+ * every field of Fac / out and every error id below is asserted) and on the GPU against libaoadmm_hip.so, bit for bit
+ * beside driver.py (tests/test_gpu_mex_gateway.py).  Real MATLAB has still never run it.
  *
  * Errors: every non-zero status becomes mexErrMsgIdAndTxt with an id in the
  * `cmtf:` namespace; AOADMM_ERR_UNSUPPORTED maps to
@@ -204,6 +207,13 @@ void print_progress(void* user, int iter, const double f[4], double f_rel_missin
   else
     mexPrintf("%6d %12f %12f %12f %17f %12f\n", iter, f[0] + f[1] + f[2] + f[3], f[0], f[1], f[2], f[3]);
   mexEvalString("drawnow;");                          // flush the command window while the solve is running
+}
+
+// mxSetCell does not free the element it replaces (the copy of G's, here): destroy it, or every call leaks it
+void replace_cell(mxArray* c, mwIndex i, mxArray* v) {
+  mxArray* old = mxGetCell(c, i);
+  mxSetCell(c, i, v);
+  mxDestroyArray(old);
 }
 
 mxArray* get_like(int field_id, int index, const mxArray* ref) {
@@ -477,9 +487,23 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (mxIsCell(obj)) {
       if (std::find(observed_list.begin(), observed_list.end(), p) != observed_list.end())
         mexErrMsgIdAndTxt("cmtf:hip:unsupported", "options.hip.sparse_observed_only: Z.object{%d} is a PARAFAC2 block", p + 1);
+      // shapes against Z.size, as for sparse slabs and as the Python layer does: the library reads I x sum(J_k) doubles
+      // whatever the cells hold, so a short slab or a missing cell would be read past its end
+      const mxArray* mp = mxGetCell(modes, p);
+      const int mA = (int)mxGetDoubles(mp)[0] - 1, mB = (int)mxGetDoubles(mp)[1] - 1;
+      const mxArray* szB = mxGetCell(sz, mB);
+      if (mxGetNumberOfElements(obj) != mxGetNumberOfElements(szB))
+        mexErrMsgIdAndTxt("aoadmm:slabCount", "Z.object{%d} has %d slabs, Z.size says %d.", p + 1,
+                          (int)mxGetNumberOfElements(obj), (int)mxGetNumberOfElements(szB));
+      const double rowsA = mxGetScalar(mxGetCell(sz, mA));
       std::vector<double> packed;                         // the slabs back to back, one transfer
       for (mwSize k = 0; k < mxGetNumberOfElements(obj); ++k) {
         const mxArray* xk = mxGetCell(obj, k);
+        if (!xk || !mxIsDouble(xk) || mxIsComplex(xk))
+          mexErrMsgIdAndTxt("cmtf:hip:unsupported", "Z.object{%d}{%d} is not a real double matrix: it stays on the MATLAB path", p + 1, (int)k + 1);
+        if ((double)mxGetM(xk) != rowsA || (double)mxGetN(xk) != mxGetDoubles(szB)[k])
+          mexErrMsgIdAndTxt("aoadmm:slabSize", "Z.object{%d}{%d} has size [%d %d], Z.size says [%d %d].", p + 1, (int)k + 1,
+                            (int)mxGetM(xk), (int)mxGetN(xk), (int)rowsA, (int)mxGetDoubles(szB)[k]);
         packed.insert(packed.end(), mxGetDoubles(xk), mxGetDoubles(xk) + mxGetNumberOfElements(xk));
       }
       check(aoadmm_par2_slab_upload(g_ctx, p, AOADMM_ALL_SLABS, packed.data()));
@@ -510,7 +534,18 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const mxArray* mkp = (miss && !mxIsEmpty(miss) && (mwSize)p < mxGetNumberOfElements(miss)) ? mxGetCell(miss, p) : nullptr;
         if (mxGetNumberOfElements(mxGetCell(modes, p)) != 3 || (mkp && !mxIsEmpty(mkp))) prec_p = AOADMM_PREC_F32;
       }
-      check(aoadmm_tensor_upload(g_ctx, p, mxGetDoubles(dense_data(obj)), prec_p));
+      // the shape against Z.size, as for a sparse block and as the Python layer does: the library reads prod(Z.size of
+      // the block's modes) doubles whatever the array holds
+      const mxArray* data = dense_data(obj);
+      const mxArray* mp = mxGetCell(modes, p);
+      const mwSize N = mxGetNumberOfElements(mp), nd = mxGetNumberOfDimensions(data);
+      bool same = !mxIsComplex(data);
+      for (mwSize i = 0; same && i < (N > nd ? N : nd); ++i) {   // trailing singleton dimensions are not stored
+        const double want = i < N ? mxGetScalar(mxGetCell(sz, (mwIndex)mxGetDoubles(mp)[i] - 1)) : 1.0;
+        same = (i < nd ? (double)mxGetDimensions(data)[i] : 1.0) == want;
+      }
+      if (!same) mexErrMsgIdAndTxt("cmtf:hip:invalid", "Z.object{%d}: size does not match Z.size of its modes", p + 1);
+      check(aoadmm_tensor_upload(g_ctx, p, mxGetDoubles(data), prec_p));
     }
     // Z.miss{p} (cmtf_AOADMM.m:68-121): same shape as the data, uint8
     const mxArray* mk = (miss && !mxIsEmpty(miss) && (mwSize)p < mxGetNumberOfElements(miss)) ? mxGetCell(miss, p) : nullptr;
@@ -732,17 +767,17 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = mxDuplicateArray(G);
   mxArray* Fac = plhs[0];
   for (int m = 0; m < n_modes; ++m) {
-    mxSetCell(mxGetField(Fac, 0, "fac"), m, get_like(AOADMM_F_FAC, m, mxGetCell(fac, m)));
+    replace_cell(mxGetField(Fac, 0, "fac"), m, get_like(AOADMM_F_FAC, m, mxGetCell(fac, m)));
     const char* names[3] = {"constraint_fac", "constraint_dual_fac", "coupling_dual_fac"};
     const int ids[3] = {AOADMM_F_CONSTRAINT_FAC, AOADMM_F_CONSTRAINT_DUAL, AOADMM_F_COUPLING_DUAL};
     for (int q = 0; q < 3; ++q)
       if (mxArray* f = mxGetField(Fac, 0, names[q])) {
         const mxArray* ref = mxGetCell(f, m);
-        if (ref && !mxIsEmpty(ref)) mxSetCell(f, m, get_like(ids[q], m, ref));
+        if (ref && !mxIsEmpty(ref)) replace_cell(f, m, get_like(ids[q], m, ref));
       }
   }
   if (mxArray* f = mxGetField(Fac, 0, "coupling_fac"))
-    for (int c = 0; c < n_couplings; ++c) mxSetCell(f, c, get_like(AOADMM_F_COUPLING_FAC, c, mxGetCell(f, c)));
+    for (int c = 0; c < n_couplings; ++c) replace_cell(f, c, get_like(AOADMM_F_COUPLING_FAC, c, mxGetCell(f, c)));
   for (int p = 0; p < P; ++p) {
     const char* names[3] = {"DeltaB", "P", "mu_DeltaB"};
     const int ids[3] = {AOADMM_F_DELTAB, AOADMM_F_P, AOADMM_F_MU_DELTAB};
@@ -750,7 +785,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       if (mxArray* f = mxGetField(Fac, 0, names[q]))
         if ((mwSize)p < mxGetNumberOfElements(f)) {
           const mxArray* ref = mxGetCell(f, p);
-          if (ref && !mxIsEmpty(ref)) mxSetCell(f, p, get_like(ids[q], p, ref));
+          if (ref && !mxIsEmpty(ref)) replace_cell(f, p, get_like(ids[q], p, ref));
         }
   }
 

@@ -1,7 +1,10 @@
 /*
- * mex_stub/mex.h -- DECLARATIONS ONLY, for `g++ -fsyntax-only` of aoadmm_mex.cpp in a container
- * that has no MATLAB (no mex.h / libmx).  Nothing here is linked, run or shipped; a real build uses
- * MATLAB's own mex.h (R2018a interleaved-complex API).  Signatures follow the documented C Matrix API.
+ * mex_stub/mex.h -- the part of the C Matrix API that aoadmm_mex.cpp uses, declared for machines that have no MATLAB
+ * (no mex.h / libmx).  `make check` syntax-checks the gateway against it, and the tests compile the gateway against it
+ * and link tests/mxmock/mxmock.cpp, which defines every function declared here (a functional mock: what is checked and
+ * what is executed are this one file).  Nothing here is shipped; a real build uses MATLAB's own mex.h (R2018a
+ * interleaved-complex API).  Signatures follow the documented C Matrix API; a declaration added here needs its
+ * definition in the mock.
  */
 #ifndef AOADMM_MEX_STUB_H
 #define AOADMM_MEX_STUB_H
