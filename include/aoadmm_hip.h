@@ -260,6 +260,29 @@ int aoadmm_par2_slab_upload(aoadmm_ctx* ctx, int p, int k, const double* Xk);
  * the resident copy of the data is overwritten at the missing positions every outer iteration. */
 int aoadmm_tensor_mask_upload(aoadmm_ctx* ctx, int p, const uint8_t* mask);
 int aoadmm_par2_slab_mask_upload(aoadmm_ctx* ctx, int p, int k, const uint8_t* mask_k);
+/* PER-ENTRY WEIGHTS on a dense CP block: W in [0, 1], same shape and column-major order as
+ * Z.object{p} (the FULL array also when row-sharded, like the mask).  Upload after the data.  aoadmm_solve then minimises
+ * Z.weights(p) * sum W o (X - M)^2 with the rest of the model by the reference's EM (cmtf_fun_AOADMM.m:408-441) with the
+ * imputation Xhat = W o X + (1 - W) o M(F) after every outer iteration, from Xhat = W o X in every solve:
+ *   func_val_conv      carries Z.weights(p) * sum W o (X - M)^2 for the block
+ *   func_rel_missing   num = ||(1 - W) o (M_new - M_old)||^2, den = ||(1 - W) o M_old||^2, M_old = 0 before the first
+ *                      iteration (den = 0 gives sqrt(num), as with a mask)
+ *   aoadmm_tensor_normsq   sum W o X^2
+ * A boolean W is Z.miss, W = 1 everywhere the plain block, w = 0 makes an entry missing.  The weights live in the
+ * block's precision: an fp32 block rounds W to fp32 here, and the objective uses the rounded weights.  The block keeps
+ * the data as uploaded and the weights beside Xhat: three arrays of the tensor's size (a matrix: six with the transposed
+ * copies; aoadmm_tensor_storage_info counts them), and no pass copies.  W = NULL removes the weights: the block is plain
+ * again and holds the data as uploaded.  A later upload of the data clears the weights; of aoadmm_tensor_mask_upload and
+ * this call the later one wins (a mask drops the weights, weights drop the mask).  Weights above 1 are the caller's to
+ * normalise: divide W by its maximum and fold that maximum into Z.weights(p).
+ * On a masked block the call takes what the block holds as the data, so it is refused once an EM pass or a solve has
+ * written model values over the missing entries: upload the data again first.  With a communicator every rank checks the
+ * whole W, so all ranks reach the same verdict.
+ * AOADMM_ERR_INVALID, block as it was: a value outside [0, 1] or not finite; no data yet; a masked block that has been
+ * imputed; a sparse block (its weights go
+ * through aoadmm_tensor_set_entry_weights); an fp16 block; a block whose natural array was released.
+ * AOADMM_ERR_UNSUPPORTED: a PARAFAC2 block, a multi-device context.  Two runs return the same bits. */
+int aoadmm_tensor_weights_upload(aoadmm_ctx* ctx, int p, const double* W);
 /* device-side synthetic CP tensor: X = [[A1,..,AN]] + noise, ||X|| = 1;
  * never crosses PCIe.  normsq_out receives ||X||^2 after normalisation. */
 int aoadmm_tensor_synth(aoadmm_ctx* ctx, int p, int rank, uint64_t seed, double noise, int precision);
@@ -343,7 +366,8 @@ int aoadmm_tensor_set_entry_weights(aoadmm_ctx* ctx, int p, int64_t nnz, const i
  * aoadmm_resident_mttkrp on the block returns the MTTKRP of the imputed tensor as of this step (before any step: the
  * plain sparse MTTKRP, bit for bit). */
 int aoadmm_resident_em_step(aoadmm_ctx* ctx, int p, double stats[3]);
-/* One EM pass over the dense block p that holds a mask (aoadmm_tensor_mask_upload / aoadmm_par2_slab_mask_upload) with
+/* One EM pass over the dense block p that holds a mask (aoadmm_tensor_mask_upload / aoadmm_par2_slab_mask_upload) or
+ * weights (aoadmm_tensor_weights_upload; see the end of this comment) with
  * the current AOADMM_F_FAC state, exactly as aoadmm_solve runs it (cmtf_fun_AOADMM.m:408-441, :1224-1226): update = 0
  * leaves the data alone (the pass behind the start objective and Znorm_const), update = 1 also overwrites the missing
  * entries with the model.  fuse selects the partial contraction an update pass over a 3-way CP block leaves for the
@@ -357,8 +381,12 @@ int aoadmm_resident_em_step(aoadmm_ctx* ctx, int p, double stats[3]);
  * tensor pass; info[0..7] = {rows per thread 4 / 2 / 1, rank class of the kernel, contracted tensor mode of the fused
  * pass (0-based: 1 or 2) or -1, mode the strips walk (1: second, 2: third), strips, pieces of the walk, walk positions
  * per piece, tensor mode of `mttkrp` or -1}; all zero but info[2] = info[7] = -1 for a PARAFAC2 block.  Two calls on
- * the same data return the same bits.  AOADMM_ERR_INVALID for a sparse, fp16 or unmasked block; AOADMM_ERR_UNSUPPORTED
- * on a context that belongs to a communicator or drives several devices. */
+ * the same data return the same bits.  AOADMM_ERR_INVALID for a sparse or fp16 block and for one that is neither masked nor
+ * weighted; AOADMM_ERR_UNSUPPORTED on a context that belongs to a communicator or drives several devices.
+ *   A weighted block: stats = {||(1 - W) o M - Q||^2, ||Q||^2, sum W o (X - M)^2, sum W o X^2} with Q = Xhat - W o X
+ * before the pass (0 after the upload and at the start of a solve), data = Xhat after the pass (data_t for a matrix), fuse
+ * is ignored (a weighted pass fuses no contraction), info[2] = info[7] = -1 and the other fields describe the unfused
+ * launch. */
 int aoadmm_resident_em_pass(aoadmm_ctx* ctx, int p, int update, int fuse, double stats[4], double* data, double* data_t,
                             double* mttkrp, int64_t info[8]);
 /* Z.object{p}{k} of a PARAFAC2 block as sparse matrices, all K slabs in one call: nnz nonzeros, subs column-major
@@ -666,7 +694,8 @@ int aoadmm_resident_par2_rhs(aoadmm_ctx* ctx, int p, int tensor_mode, double* ou
  * factor rows gathered + output written; flops = nnz * R * N) and the passes over the nonzeros of PARAFAC2 blocks
  * with sparse slabs (one launch per pass, counted as the MTTKRP of the I x sum(J_k) matrix it is); an EM step of an
  * observed-only block counts as one launch with the bytes and flops of its N passes, and its MTTKRPs include the
- * dense correction; which = 4 + n (n = 0 .. 7): the pass of those EM steps over the copy of tensor mode n alone (the
+ * dense correction; which = 4 + n (n = 0 .. 7): the pass of those EM steps over the copy of tensor mode n alone, and under which = 4 also the
+ * pass of every aoadmm_resident_em_pass call over a dense CP block, masked or weighted (a solve's own EM passes record no events) (the
  * residuals x - m; n = 0 also carries the statistics, and is the whole of a statistics-only step).  Of a sharded
  * sparse block: this rank's share (its nonzeros, and the rows of its span as the output written); the all-reduce is
  * outside the events; which = 12: the held-out passes (aoadmm_resident_model_at, aoadmm_resident_heldout_stats and the pass

@@ -70,7 +70,7 @@ SYMBOLS = [
     'aoadmm_model_begin', 'aoadmm_model_set_mode', 'aoadmm_model_set_mode_slabs', 'aoadmm_model_add_cp',
     'aoadmm_model_add_par2', 'aoadmm_model_set_constraint', 'aoadmm_model_set_coupling',
     'aoadmm_model_set_coupling_type', 'aoadmm_model_set_ridge', 'aoadmm_model_end', 'aoadmm_tensor_upload',
-    'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_tensor_upload_coo_sharded', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq', 'aoadmm_tensor_storage_info', 'aoadmm_tensor_rank',
+    'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_tensor_upload_coo_sharded', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_tensor_weights_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq', 'aoadmm_tensor_storage_info', 'aoadmm_tensor_rank',
     'aoadmm_tensor_set_observed_only', 'aoadmm_tensor_set_entry_weights', 'aoadmm_resident_em_step', 'aoadmm_resident_em_pass',
     'aoadmm_resident_model_at', 'aoadmm_tensor_set_heldout', 'aoadmm_resident_heldout_stats', 'aoadmm_heldout_info', 'aoadmm_heldout_trace',
     'aoadmm_heldout_keep_best', 'aoadmm_heldout_restore_best', 'aoadmm_heldout_best_info', 'aoadmm_resident_topk',
@@ -183,6 +183,7 @@ def load_library():
     lib.aoadmm_par2_slab_upload_coo.argtypes = [vp, C.c_int, i64, C.POINTER(i64), dp]
     lib.aoadmm_tensor_mask_upload.argtypes = [vp, C.c_int, C.POINTER(C.c_uint8)]
     lib.aoadmm_par2_slab_mask_upload.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
+    lib.aoadmm_tensor_weights_upload.argtypes = [vp, C.c_int, dp]
     lib.aoadmm_tensor_synth.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.c_double, C.c_int]
     lib.aoadmm_tensor_normsq.argtypes = [vp, C.c_int, dp]
     lib.aoadmm_tensor_storage_info.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp, C.POINTER(i64)]

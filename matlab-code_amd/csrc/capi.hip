@@ -407,6 +407,14 @@ int aoadmm_tensor_mask_upload(aoadmm_ctx* ctx, int p, const uint8_t* mask) {
   CTX_OR_FAIL(ctx);
   return guarded([&] { on_engines(ctx, [&](Engine& e, int) { e.tensor_mask_upload(p, mask); }); });
 }
+int aoadmm_tensor_weights_upload(aoadmm_ctx* ctx, int p, const double* W) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    if (ctx->multi && ctx->multi->eng.size() > 1)
+      throw Error(AOADMM_ERR_UNSUPPORTED, "aoadmm_tensor_weights_upload is not available on a multi-device context (aoadmm_create_multi with more than one device): use one context per rank and a communicator");
+    on_engines(ctx, [&](Engine& e, int) { e.tensor_weights_upload(p, W); });
+  });
+}
 int aoadmm_par2_slab_mask_upload(aoadmm_ctx* ctx, int p, int k, const uint8_t* mask_k) {
   CTX_OR_FAIL(ctx);
   return guarded([&] { on_engines(ctx, [&](Engine& e, int) { e.par2_slab_mask_upload(p, k, mask_k); }); });
@@ -458,7 +466,7 @@ int aoadmm_resident_em_step(aoadmm_ctx* ctx, int p, double stats[3]) {
     });
   });
 }
-// One EM pass of a masked dense block as Engine::outer_updates runs it (Engine::resident_em_pass)
+// One EM pass of a masked or weighted dense block as Engine::outer_updates runs it (Engine::resident_em_pass)
 int aoadmm_resident_em_pass(aoadmm_ctx* ctx, int p, int update, int fuse, double stats[4], double* data, double* data_t,
                             double* mttkrp, int64_t info[8]) {
   CTX_OR_FAIL(ctx);

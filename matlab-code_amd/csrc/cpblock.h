@@ -109,6 +109,14 @@ struct CpBlock {
   // Z.miss{p}: one byte per entry in the layout of X (and of Xt for matrices), 1 = observed
   DevBuf mask, maskT;
   bool has_mask = false;
+  bool mask_imputed = false;   // an EM pass has written model values over the missing entries of X since the data arrived
+  // Per-entry weights in [0, 1] (aoadmm_tensor_weights_upload): X.data is then Xhat =
+  // W o X0 + (1 - W) o M, X0 the data as uploaded and Wt the weights, both in the layout and precision of X (an fp32
+  // block keeps fp32 weights); X0t / WtT are their transposed copies beside Xt (matrices).  Never together with a mask.
+  DevBuf X0, Wt, X0t, WtT;
+  bool has_weights = false;
+  bool imputed() const { return has_mask || has_weights; }   // the EM pass rewrites X: no pass copy, no release of X
+  void clear_weights() { X0.release(); Wt.release(); X0t.release(); WtT.release(); has_weights = false; }
   // sparse form of Z.object{p}: replaces everything above but nd / dims / has_data.  aoadmm_tensor_upload_coo: every
   // rank of a communicator holds all nonzeros and computes the complete MTTKRP (no collective);
   // aoadmm_tensor_upload_coo_sharded: every rank holds its share of the nonzeros (coo.sharded) and the MTTKRP is an
@@ -120,7 +128,7 @@ struct CpBlock {
   // New data has arrived, dense or sparse: no copy, cached contraction or release state of the old data holds.  Frees
   // nothing (a pass copy's buffer is reused by the next build; the sparse upload releases what it no longer needs).
   void reset_derived() {
-    has_data = true; x_released = false; cached_mode = -1; xp_ksharded = false; half = false; scale = 1.0;
+    has_data = true; x_released = false; cached_mode = -1; xp_ksharded = false; half = false; scale = 1.0; mask_imputed = false;
     for (PassCopy& c : copy) c.present = c.refused = false;
   }
 };
@@ -147,6 +155,18 @@ using SlabSource = std::function<void(DevBuf& slab, int64_t k0, int64_t kloc)>;
 // rank, after the exchange), AOADMM_ERR_NOMEM / AOADMM_ERR_UNSUPPORTED when a copy cannot be built (this rank alone); the
 // block is then left without data.
 void block_make_half(const BlockCtx& cx, CpBlock& b, const SlabSource* slab_source = nullptr);
+// Gives the dense block weights (CpBlock::has_weights) from `host`, the block's local rows x the other modes, column-major
+// fp64: converted to the block's precision, checked on the device while they pass through the staging buffer, and Xhat
+// reset to W o X0.  X0 is what the block holds at the first call (later calls replace W alone); a mask is dropped.
+// False, with the block as it was, when a weight is not a finite number in [0, 1].
+bool block_set_weights(const BlockCtx& cx, CpBlock& b, const double* host);
+// false when some host[e], e < n, is not a finite number in [0, 1]: the same check on an array the block keeps only a
+// part of (a rank of a communicator checks the whole W, so that every rank reaches the same verdict)
+bool block_weights_in_range(const BlockCtx& cx, const double* host, int64_t n);
+// the block without its weights: Xhat <- X0
+void block_drop_weights(const BlockCtx& cx, CpBlock& b);
+// Xhat <- W o X0: where every solve of a weighted block starts
+void block_reset_weighted(const BlockCtx& cx, CpBlock& b);
 // builds the mode-3-sharded copy[0] from a natural-layout slab X(:, :, [k0, k0 + kloc)) already on the device
 void adopt_ksharded_xp(const BlockCtx& cx, CpBlock& b, const void* slab, int64_t k0, int64_t kloc);
 bool want_ksharded_xp(const BlockCtx& cx, const CpBlock& b, int64_t K, int64_t* k0, int64_t* kloc);

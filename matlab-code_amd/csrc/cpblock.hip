@@ -1,5 +1,6 @@
 // Dense CP block: upload, pass copies, partial-contraction cache and the MTTKRP paths (see cpblock.h).
 #include "cpblock.h"
+#include "em.h"
 #include "misc.h"
 
 #include <algorithm>
@@ -87,7 +88,9 @@ static void timed_contract(const BlockCtx& cx, const void* X, int prec, const Co
 static size_t blocked_bytes(int64_t M, int64_t C, size_t es) { return (size_t)round_up(M, kRowBlockElems) * C * es; }
 
 // host array (rows x ncols, column-major fp64) -> dst in `prec` with the rows padded to `pad`, through the staging buffer
-static void upload_padded(const BlockCtx& cx, void* dst, int prec, int64_t pad, const double* host, int64_t rows, int64_t ncols) {
+// (`bad01`: device flag raised when a value is not a finite number in [0, 1] -- the weights' way in)
+static void upload_padded(const BlockCtx& cx, void* dst, int prec, int64_t pad, const double* host, int64_t rows, int64_t ncols,
+                          int* bad01 = nullptr) {
   DevBuf& staging = *cx.staging;
   const int64_t chunk_cols = std::max<int64_t>(1, (int64_t)(64ll << 20) / rows);   // ~512 MB of doubles
   staging.ensure((size_t)std::min(chunk_cols, ncols) * rows * sizeof(double));
@@ -95,6 +98,7 @@ static void upload_padded(const BlockCtx& cx, void* dst, int prec, int64_t pad, 
     const int64_t nc = std::min(chunk_cols, ncols - c0);
     AO_HIP(hipMemcpyAsync(staging.p, host + c0 * rows, (size_t)nc * rows * sizeof(double), hipMemcpyHostToDevice, cx.stream));
     pad_convert(dst, prec, pad, staging.d(), rows, nc, c0, cx.stream);
+    if (bad01) em_w_check(staging.d(), nc * rows, bad01, cx.stream);
     AO_HIP(hipStreamSynchronize(cx.stream));
   }
 }
@@ -161,11 +165,87 @@ void block_upload(const BlockCtx& cx, CpBlock& b, int nd, const int64_t* dims, c
   if (nd == 3) { (void)ensure_pass_copy(cx, b, 1); (void)ensure_pass_copy(cx, b, 2); }   // one-off set-up cost belongs to the upload
 }
 
+// ---- per-entry weights -------------------------------------------------------
+void block_reset_weighted(const BlockCtx& cx, CpBlock& b) {
+  em_w_reset(b.X.data.p, b.X0.p, b.Wt.p, b.X.prec, b.X.elems_padded(), cx.stream);
+  if (b.nd == 2) em_w_reset(b.Xt.data.p, b.X0t.p, b.WtT.p, b.Xt.prec, b.Xt.pad0 * b.dims[0], cx.stream);
+  b.cached_mode = -1;
+}
+
+bool block_weights_in_range(const BlockCtx& cx, const double* host, int64_t n) {
+  DevBuf& staging = *cx.staging;
+  DevBuf flag;
+  flag.alloc(sizeof(int));
+  AO_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), cx.stream));
+  const int64_t chunk = (int64_t)(64ll << 20);         // 512 MB of doubles, as upload_padded
+  staging.ensure((size_t)std::min(chunk, n) * sizeof(double));
+  for (int64_t e0 = 0; e0 < n; e0 += chunk) {
+    const int64_t ne = std::min(chunk, n - e0);
+    AO_HIP(hipMemcpyAsync(staging.p, host + e0, (size_t)ne * sizeof(double), hipMemcpyHostToDevice, cx.stream));
+    em_w_check(staging.d(), ne, flag.as<int>(), cx.stream);
+    AO_HIP(hipStreamSynchronize(cx.stream));           // the staging buffer is reused
+  }
+  int bad = 0;
+  AO_HIP(hipMemcpy(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost));
+  return bad == 0;
+}
+
+bool block_set_weights(const BlockCtx& cx, CpBlock& b, const double* host) {
+  hipStream_t s = cx.stream;
+  const int prec = b.X.prec;
+  const int64_t rows = b.dims[0];
+  int64_t ncols = 1;
+  for (int i = 1; i < b.nd; ++i) ncols *= b.dims[i];
+  const size_t bytes = (size_t)b.X.elems_padded() * b.X.elem_size();
+  const size_t bytes_t = b.nd == 2 ? (size_t)b.Xt.pad0 * rows * b.Xt.elem_size() : 0;
+  DevBuf W, WT, X0, X0t, flag;                         // the block changes only once everything is in place
+  flag.alloc(sizeof(int));
+  AO_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), s));
+  W.alloc(bytes);
+  upload_padded(cx, W.p, prec, b.X.pad0, host, rows, ncols, flag.as<int>());
+  if (b.nd == 2) {
+    WT.alloc(bytes_t);
+    cx.staging->ensure((size_t)ncols * rows * sizeof(double));
+    AO_HIP(hipMemcpyAsync(cx.staging->p, host, (size_t)ncols * rows * sizeof(double), hipMemcpyHostToDevice, s));
+    transpose_convert(WT.p, prec, b.Xt.pad0, cx.staging->d(), rows, ncols, s);
+  }
+  if (!b.has_weights) {                                // the data as the block holds it becomes X0
+    X0.alloc(bytes);
+    AO_HIP(hipMemcpyAsync(X0.p, b.X.data.p, bytes, hipMemcpyDeviceToDevice, s));
+    if (b.nd == 2) {
+      X0t.alloc(bytes_t);
+      AO_HIP(hipMemcpyAsync(X0t.p, b.Xt.data.p, bytes_t, hipMemcpyDeviceToDevice, s));
+    }
+  }
+  int bad = 0;
+  AO_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  AO_HIP(hipStreamSynchronize(s));                     // the verdict is read back once, behind the last chunk
+  if (bad) return false;
+  if (!b.has_weights) { b.X0 = std::move(X0); b.X0t = std::move(X0t); }
+  b.Wt = std::move(W); b.WtT = std::move(WT);
+  b.has_weights = true;
+  b.has_mask = false; b.mask.release(); b.maskT.release();   // w = 0 is the spelling of "missing"
+  drop_pass_copies(b);                                 // the imputation would have to update them too
+  block_reset_weighted(cx, b);
+  AO_HIP(hipStreamSynchronize(s));
+  return true;
+}
+
+void block_drop_weights(const BlockCtx& cx, CpBlock& b) {
+  if (!b.has_weights) return;
+  AO_HIP(hipMemcpyAsync(b.X.data.p, b.X0.p, (size_t)b.X.elems_padded() * b.X.elem_size(), hipMemcpyDeviceToDevice, cx.stream));
+  if (b.nd == 2)
+    AO_HIP(hipMemcpyAsync(b.Xt.data.p, b.X0t.p, (size_t)b.Xt.pad0 * b.dims[0] * b.Xt.elem_size(), hipMemcpyDeviceToDevice, cx.stream));
+  AO_HIP(hipStreamSynchronize(cx.stream));
+  b.clear_weights();
+  b.cached_mode = -1;
+}
+
 // ---- half storage ----------------------------------------------------------
 static bool room_for(size_t bytes);
 
 void block_make_half(const BlockCtx& cx, CpBlock& b, const SlabSource* slab_source) {
-  AO_REQUIRE(b.nd == 3 && b.X.prec == AOADMM_PREC_F32 && b.X.data.p && !b.has_mask,
+  AO_REQUIRE(b.nd == 3 && b.X.prec == AOADMM_PREC_F32 && b.X.data.p && !b.imputed(),
              "internal: half storage is built from an unmasked fp32 3-way block");
   hipStream_t s = cx.stream;
   auto drop = [&] {                                    // the fp32 array is not the data: nothing valid is left
@@ -261,7 +341,7 @@ static bool room_for(size_t bytes) {
 // Mode-3 sharding of the mode-1 pass's copy: every rank must reach the same verdict (the collectives that follow the
 // pass differ: own rows of mode 3 instead of partial sums).
 bool want_ksharded_xp(const BlockCtx& cx, const CpBlock& b, int64_t K, int64_t* k0, int64_t* kloc) {
-  if (!cx.sharded || cx.world <= 1 || !cx.allow_copies || b.has_mask || b.nd != 3) return false;
+  if (!cx.sharded || cx.world <= 1 || !cx.allow_copies || b.imputed() || b.nd != 3) return false;
   const int64_t per = cdiv(K, cx.world);
   if (per * (cx.world - 1) >= K) return false;        // some rank would own no slab
   *k0 = per * cx.rank;
@@ -286,7 +366,7 @@ bool ensure_pass_copy(const BlockCtx& cx, CpBlock& b, int c) {
   PassCopy& pc = b.copy[c];
   if (pc.present) return true;
   if (pc.refused) return false;
-  if (c == 1 ? !ensure_pass_copy(cx, b, 0) : (!cx.allow_copies || b.has_mask || b.nd != 3)) return false;
+  if (c == 1 ? !ensure_pass_copy(cx, b, 0) : (!cx.allow_copies || b.imputed() || b.nd != 3)) return false;
   // rows: the two uncontracted modes in cyclic order after c, the first of them padded; columns: mode c
   const int64_t I = b.dims[0], J = b.dims[1], K = b.dims[2];
   const int64_t pad = c == 0 ? pad_of(b.X.prec, J) : (c == 1 ? pad_of(b.X.prec, K) : b.X.pad0);
@@ -308,7 +388,7 @@ bool ensure_pass_copy(const BlockCtx& cx, CpBlock& b, int c) {
 // AOADMM_ERR_UNSUPPORTED (the caller falls back to the host-array form).
 void maybe_release_natural(const BlockCtx& cx, CpBlock& b, bool normsq_valid) {
   const bool all_copies = b.copy[0].present && b.copy[1].present && b.copy[2].present;
-  if (b.sparse || b.x_released || b.nd != 3 || !all_copies || b.has_mask || !normsq_valid || !b.X.data.p) return;
+  if (b.sparse || b.x_released || b.nd != 3 || !all_copies || b.imputed() || !normsq_valid || !b.X.data.p) return;
   const char* pe = getenv("AOADMM_RELEASE_NATURAL");   // read per solve (the test suite switches it inside one process)
   const int policy = pe ? (atoi(pe) != 0 ? 1 : -1) : 0;
   if (policy < 0) return;

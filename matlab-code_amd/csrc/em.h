@@ -25,6 +25,12 @@ struct EmCpArgs {
   // walked mode (ContractPlan in contract.h; chunks = em_cp_fused_chunks, t_chunk_stride = rows of T times R).
   void* T = nullptr;
   int64_t t_chunk_stride = 0;
+  // Weighted block (both null: masked block).  X is then Xhat, X0 the data as uploaded and Wt the weights in [0, 1], all
+  // three in the layout and precision of X; `mask` is not read and T must be null.  Per entry, with q = xh - w x0
+  // (= (1 - w) m_old):   obs_res += w (x0 - m)^2 ; obs_x2 += w x0^2 ; num += ((1 - w) m - q)^2 ; den += q^2 ;
+  // xh <- w x0 + (1 - w) m   (update only)
+  const void* X0 = nullptr;
+  const void* Wt = nullptr;
 };
 // bits[e >> 3] bit (e & 7) = bytes[e] != 0 for e < n; room for cdiv(n, 8) + 16 bytes (the strip kernel's clamped
 // look-ahead loads stay inside the block, the slack is for the padding of the last byte)
@@ -46,6 +52,12 @@ EmCpLaunch em_cp_launch_of(const EmCpArgs& a, int prec, bool fuse);
 size_t em_cp_ws_bytes(int64_t Ipad, int64_t J, int64_t K);
 // ws: em_cp_ws_bytes ; out4: device, 4 doubles
 void em_cp_pass(const EmCpArgs& a, int prec, double* ws, double* out4, hipStream_t s);
+
+// Weighted blocks: xh[e] = w[e] * x0[e] for e < n, one rounding in the arrays' precision -- the product the weighted
+// pass subtracts from xh, so that q is exactly 0 in the first pass after it
+void em_w_reset(void* xh, const void* x0, const void* w, int prec, int64_t n, hipStream_t s);
+// *flag (device, zeroed by the caller) becomes 1 when some w[e], e < n, is not a finite number in [0, 1]
+void em_w_check(const double* w, int64_t n, int* flag, hipStream_t s);
 
 struct EmPar2Args {
   double* X;               // slabs back to back (I x J_k each), fp64

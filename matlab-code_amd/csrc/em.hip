@@ -8,8 +8,10 @@
 // tensor is read once (16-byte loads), the mask is ONE BIT per entry (packed on the device when Z.miss arrives: at
 // 1000^3 the byte-per-entry mask was 1 GB of the pass's 9 GB), and only 128-byte lines that contain a missing entry are
 // written back: the pass is bound by HBM like the contractions.
+// A block with per-entry weights (EmCpArgs::X0 / Wt) runs the weighted forms of both kernels below.
 #include "em.h"
 
+#include <algorithm>
 #include <type_traits>
 
 namespace aoadmm {
@@ -346,6 +348,216 @@ __global__ __launch_bounds__(kEmThreads) void em_cp_k(EmCpArgs a, int jchunks, i
   }
 }
 
+// ---- weighted blocks (em.h EmCpArgs::X0 / Wt) -----------------------------------------------------------------------------
+// One vector of entries of the weighted pass: the new value and the four terms' accumulators.  Products and differences
+// are rounded one by one -- contracted, q = fma(-w, x0, xh) would be the rounding residue of em_w_reset's product instead
+// of 0 in a solve's first pass, and f_rel_missing divides by the sum of q^2 -- and the multiply-adds written as such are
+// fused.  With w in {0, 1}, xh = x0 where w = 1 and zeros in x0 where w = 0 every term is the masked kernel's, bit for bit:
+// w = 1 gives q = 0, p = 0 and wd = d; w = 0 gives q = xh, wd = 0 and xn = p = m.
+template <typename T, typename XV>
+__device__ __forceinline__ XV em_w_entry(XV x0, XV w, XV xh, XV m, XV& s_ores, XV& s_ox2, XV& s_num, XV& s_den) {
+#pragma clang fp contract(off)
+  const XV wx = w * x0;
+  const XV q = xh - wx;                                                    // (1 - w) m_old
+  const XV p = ((T)1 - w) * m;
+  const XV d = x0 - m;
+  const XV wd = w * d;
+  const XV n = p - q;
+  s_ores = __builtin_elementwise_fma(wd, d, s_ores);
+  s_ox2 = __builtin_elementwise_fma(wx, x0, s_ox2);
+  s_num = __builtin_elementwise_fma(n, n, s_num);
+  s_den = __builtin_elementwise_fma(q, q, s_den);
+  return __builtin_elementwise_fma(w, x0, p);
+}
+
+// The strip kernel (em_cp_vec_k without FUSE) for a weighted block: three streams in (X0, W, Xhat) through the same
+// look-ahead ring, Xhat out.  A 128-byte line of Xhat is written when some weight in it is not 1; under unit weights
+// xh = x0 and stays.  Padding rows: zero row of A, w forced to 1 (X0 and Xhat hold zeros there).
+template <typename T, int VEC, int RMAX>
+__global__ __launch_bounds__(kEmThreads, 1) void em_cp_w_vec_k(EmCpArgs a, int jchunks, int64_t jlen, double* ws) {
+  typedef typename EmVec<T, VEC>::type XV;
+  __shared__ __attribute__((aligned(16))) T Bsh[kEmJTile][RMAX];
+  __shared__ double sh4[4];
+  const int R = a.R;
+  const int t = threadIdx.x;
+  const bool wj = a.walk != 2;
+  const int64_t f = blockIdx.y;
+  const int64_t NW = wj ? a.J : a.K;
+  const double* Ff = wj ? a.C : a.B;
+  const int64_t ldf = wj ? a.ldC : a.ldB;
+  const double* Fw = wj ? a.B : a.C;
+  const int64_t ldw = wj ? a.ldB : a.ldC;
+  const int64_t step = wj ? a.Ipad : a.Ipad * a.J;
+  const int chunk = blockIdx.x % jchunks;
+  const int64_t i0 = ((int64_t)(blockIdx.x / jchunks) * kEmThreads + t) * VEC;
+  const int64_t jbeg = chunk * jlen, jend = jbeg + jlen < NW ? jbeg + jlen : NW;
+  XV areg[RMAX];
+  bool pad[VEC];
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) pad[v] = i0 + v >= a.I;
+#pragma unroll
+  for (int r = 0; r < RMAX; ++r) {
+    const int rr = r < R ? r : 0;
+    const double c = Ff ? Ff[f + ldf * rr] : 1.0;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const int64_t i = pad[v] ? a.I - 1 : i0 + v;
+      areg[r][v] = (r < R && !pad[v]) ? (T)(a.A[i + a.ldA * rr] * c) : (T)0;
+    }
+  }
+  const int64_t base = (wj ? a.Ipad * a.J : a.Ipad) * f;
+  T* X = reinterpret_cast<T*>(a.X) + base;
+  const T* X0 = reinterpret_cast<const T*>(a.X0) + base;
+  const T* W = reinterpret_cast<const T*>(a.Wt) + base;
+  const int lane = t & 63;
+  const bool in_range = i0 < a.Ipad;                                     // Ipad is a multiple of VEC
+  const XV zero = {};
+  double num = 0, den = 0, ores = 0, ox2 = 0;
+  for (int64_t j0 = jbeg; j0 < jend; j0 += kEmJTile) {
+    __syncthreads();
+    for (int e = t; e < kEmJTile * RMAX; e += kEmThreads) {
+      const int jj = e / RMAX, r = e - jj * RMAX;
+      Bsh[jj][r] = (r < R && j0 + jj < jend) ? (T)Fw[j0 + jj + ldw * r] : (T)0;
+    }
+    __syncthreads();
+    const int nj = (int)((jend - j0 < kEmJTile) ? (jend - j0) : kEmJTile);
+    if (!in_range) continue;
+    constexpr int PD = 4;                              // columns in flight
+    XV xq[PD], wq[PD], hq[PD];
+#pragma unroll
+    for (int p = 0; p < PD; ++p) {
+      const int64_t op = i0 + step * (j0 + (p < nj ? p : nj - 1));
+      xq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(X0 + op));
+      wq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(W + op));
+      hq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(X + op));
+    }
+    XV s_ores = zero, s_ox2 = zero, s_num = zero, s_den = zero;
+    for (int jj = 0; jj < nj; jj += PD) {
+#pragma unroll
+      for (int p = 0; p < PD; ++p) {
+        const int jc = jj + p;                                           // wave-uniform
+        const XV x0 = xq[p], xh = hq[p];
+        XV w = wq[p];
+        {
+          const int jn = jc + PD < nj ? jc + PD : nj - 1;                // clamped: the last loads are discarded
+          const int64_t on = i0 + step * (j0 + jn);
+          xq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(X0 + on));
+          wq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(W + on));
+          hq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(X + on));
+        }
+        if (jc < nj) {
+          bool changes = false;                                          // some weight of this vector is not 1
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) {
+            w[v] = pad[v] ? (T)1 : w[v];
+            changes |= w[v] != (T)1;
+          }
+          const XV m = em_row_dot<T, VEC, RMAX, XV>(areg, &Bsh[jc][0], zero);
+          XV xn = em_w_entry<T, XV>(x0, w, xh, m, s_ores, s_ox2, s_num, s_den);
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) xn[v] = w[v] == (T)1 ? x0[v] : xn[v];   // the data itself, also beside a model value that is not finite
+          if (a.update) {
+            // by 128-byte line, as in em_cp_vec_k
+            XV* dst = reinterpret_cast<XV*>(X + i0 + step * (j0 + jc));
+            const unsigned long long bal = __ballot(changes);
+            const unsigned s16 = (unsigned)(((reinterpret_cast<uintptr_t>(dst) >> 4) - (unsigned)lane) & 7u);
+            const unsigned g = ((unsigned)lane + s16) >> 3;
+            const unsigned grp = g < 8 ? (unsigned)((bal << s16) >> (8 * g)) & 0xffu : (unsigned)(bal >> (64 - s16)) & 0xffu;
+            if (grp) __builtin_nontemporal_store(xn, dst);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      ores += (double)s_ores[v]; ox2 += (double)s_ox2[v]; num += (double)s_num[v]; den += (double)s_den[v];
+    }
+  }
+  num = em_block_sum(num, sh4); den = em_block_sum(den, sh4);
+  ores = em_block_sum(ores, sh4); ox2 = em_block_sum(ox2, sh4);
+  if (t == 0) {
+    double* w = ws + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4;
+    w[0] = num; w[1] = den; w[2] = ores; w[3] = ox2;
+  }
+}
+
+// One row per thread, for R > 32 (em_cp_k for a weighted block)
+template <typename T, int RMAX>
+__global__ __launch_bounds__(kEmThreads) void em_cp_w_k(EmCpArgs a, int jchunks, int64_t jlen, double* ws) {
+  __shared__ T Bsh[kEmJTile][RMAX];
+  __shared__ double sh4[4];
+  const int R = a.R;
+  const int t = threadIdx.x;
+  const int64_t k = blockIdx.y;
+  const int chunk = blockIdx.x % jchunks;
+  const int64_t i0 = (int64_t)(blockIdx.x / jchunks) * kEmThreads + t;
+  const int64_t jbeg = chunk * jlen, jend = jbeg + jlen < a.J ? jbeg + jlen : a.J;
+  T areg[RMAX];
+  {
+    const int64_t i = i0 < a.I ? i0 : a.I - 1;                          // clamped: padding rows are skipped below
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r) {
+      const int rr = r < R ? r : 0;
+      const double c = a.C ? a.C[k + a.ldC * rr] : 1.0;
+      areg[r] = r < R ? (T)(a.A[i + a.ldA * rr] * c) : (T)0;
+    }
+  }
+  const int64_t base = a.Ipad * a.J * k;
+  T* X = reinterpret_cast<T*>(a.X) + base;
+  const T* X0 = reinterpret_cast<const T*>(a.X0) + base;
+  const T* W = reinterpret_cast<const T*>(a.Wt) + base;
+  double num = 0, den = 0, ores = 0, ox2 = 0;
+  for (int64_t j0 = jbeg; j0 < jend; j0 += kEmJTile) {
+    __syncthreads();
+    for (int e = t; e < kEmJTile * RMAX; e += kEmThreads) {
+      const int jj = e / RMAX, r = e - jj * RMAX;
+      Bsh[jj][r] = (r < R && j0 + jj < jend) ? (T)a.B[j0 + jj + a.ldB * r] : (T)0;
+    }
+    __syncthreads();
+    const int nj = (int)((jend - j0 < kEmJTile) ? (jend - j0) : kEmJTile);
+    if (i0 >= a.I) continue;
+    for (int jj = 0; jj < nj; ++jj) {
+      const int64_t o = i0 + a.Ipad * (j0 + jj);
+      const T x0 = X0[o], w = W[o], xh = X[o];
+      T m = (T)0;
+#pragma unroll
+      for (int r = 0; r < RMAX; ++r) m += areg[r] * Bsh[jj][r];
+      T t_ores = (T)0, t_ox2 = (T)0, t_num = (T)0, t_den = (T)0;        // this entry's terms: the squares, rounded once
+      const T xn = em_w_entry<T, T>(x0, w, xh, m, t_ores, t_ox2, t_num, t_den);
+      ores += (double)t_ores; ox2 += (double)t_ox2; num += (double)t_num; den += (double)t_den;
+      if (a.update && w != (T)1) X[o] = xn;
+    }
+  }
+  num = em_block_sum(num, sh4); den = em_block_sum(den, sh4);
+  ores = em_block_sum(ores, sh4); ox2 = em_block_sum(ox2, sh4);
+  if (t == 0) {
+    double* w = ws + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4;
+    w[0] = num; w[1] = den; w[2] = ores; w[3] = ox2;
+  }
+}
+
+template <typename T>
+__global__ void em_w_reset_k(T* __restrict__ xh, const T* __restrict__ x0, const T* __restrict__ w, int64_t n) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) xh[e] = w[e] * x0[e];
+}
+void em_w_reset(void* xh, const void* x0, const void* w, int prec, int64_t n, hipStream_t s) {
+  const unsigned blocks = (unsigned)std::min<int64_t>(cdiv(n, (int64_t)256), 65536);
+  if (prec == AOADMM_PREC_F32) em_w_reset_k<float><<<blocks, 256, 0, s>>>((float*)xh, (const float*)x0, (const float*)w, n);
+  else em_w_reset_k<double><<<blocks, 256, 0, s>>>((double*)xh, (const double*)x0, (const double*)w, n);
+  AO_KERNEL_CHECK();
+}
+
+__global__ void em_w_check_k(const double* __restrict__ w, int64_t n, int* flag) {
+  bool bad = false;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
+    bad |= !(w[e] >= 0.0 && w[e] <= 1.0);                                // a NaN fails both comparisons
+  if (bad) *flag = 1;
+}
+void em_w_check(const double* w, int64_t n, int* flag, hipStream_t s) {
+  em_w_check_k<<<(unsigned)std::min<int64_t>(cdiv(n, (int64_t)256), 65536), 256, 0, s>>>(w, n, flag);
+  AO_KERNEL_CHECK();
+}
+
 // out4[q] = sum_b ws[b][q], fixed order (256 threads, strided partial sums then a tree)
 __global__ __launch_bounds__(256) void em_sum4_k(const double* ws, int64_t nb, double* out4) {
   __shared__ double sh4[4];
@@ -422,9 +634,25 @@ static void em_cp_launch(const EmCpArgs& a, int jchunks, int64_t jlen, double* w
   }
 }
 
+template <typename T, int VEC>
+static void em_cp_w_launch(const EmCpArgs& a, int jchunks, int64_t jlen, double* ws, dim3 grid, hipStream_t s) {
+  switch ((a.R + 3) / 4) {                           // the classes of em_cp_launch
+    case 1: em_cp_w_vec_k<T, VEC, 4><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
+    case 2: em_cp_w_vec_k<T, VEC, 8><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
+    case 3: em_cp_w_vec_k<T, VEC, 12><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
+    case 4: em_cp_w_vec_k<T, VEC, 16><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
+    case 5: em_cp_w_vec_k<T, VEC, 20><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
+    case 6: em_cp_w_vec_k<T, VEC, 24><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
+    case 7: em_cp_w_vec_k<T, VEC, 28><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
+    default: em_cp_w_vec_k<T, VEC, 32><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
+  }
+}
+
 void em_cp_pass(const EmCpArgs& a, int prec, double* ws, double* out4, hipStream_t s) {
   AO_REQUIRE(a.R >= 1 && a.R <= kMaxRank && a.I > 0 && a.J > 0 && a.K > 0, "em_cp_pass: bad sizes");
   const bool fuse = a.T != nullptr;
+  const bool weighted = a.Wt != nullptr;
+  AO_REQUIRE(!weighted || (a.X0 != nullptr && !fuse), "em_cp_pass: a weighted block needs X0 and takes no fused contraction");
   const bool wj = a.walk != 2;
   AO_REQUIRE((wj ? a.K : a.J) <= 65535, "em_cp_pass: mode too long for one launch");   // grid.y = the fixed index
   AO_REQUIRE(!fuse || em_cp_can_fuse(a, prec), "em_cp_pass: this block cannot take the fused contraction");
@@ -434,7 +662,15 @@ void em_cp_pass(const EmCpArgs& a, int prec, double* ws, double* out4, hipStream
   const int jchunks = l.jchunks;
   const dim3 grid((unsigned)(strips * jchunks), (unsigned)(wj ? a.K : a.J));
   AO_REQUIRE((size_t)grid.x * grid.y * 4 * sizeof(double) <= em_cp_ws_bytes(a.Ipad, a.J, a.K), "em_cp_pass: workspace");
-  if (prec == AOADMM_PREC_F32) {
+  if (weighted) {
+    if (prec == AOADMM_PREC_F32) {
+      if (em_wide(a)) em_cp_w_launch<float, 4>(a, jchunks, jlen, ws, grid, s);
+      else em_cp_w_k<float, 64><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws);
+    } else {
+      if (em_wide(a)) em_cp_w_launch<double, 2>(a, jchunks, jlen, ws, grid, s);
+      else em_cp_w_k<double, 64><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws);
+    }
+  } else if (prec == AOADMM_PREC_F32) {
     if (fuse) em_cp_launch<float, 4, true>(a, jchunks, jlen, ws, grid, s);
     else if (em_wide(a)) em_cp_launch<float, 4, false>(a, jchunks, jlen, ws, grid, s);
     else em_cp_k<float, 64><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws);

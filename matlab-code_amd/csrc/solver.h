@@ -157,7 +157,7 @@ struct TensorInfo {
   RankList rl;                  // ranking list (aoadmm_tensor_set_ranklist): belongs to the model, as the held-out list does
   std::vector<double> rl_trace; // kRankSlots sums per evaluation of the last solve (the iterations: Engine::rank_iters_)
   bool eval_shortcut = false;   // PARAFAC2: the enqueued objective evaluation took the last_mttkrp shortcut (:1254-1260)
-  bool masked() const { return par2 ? p2.has_mask : blk.has_mask; }   // Z.miss{p} given
+  bool masked() const { return par2 ? p2.has_mask : blk.imputed(); }  // Z.miss{p} or per-entry weights given: the dense EM pass runs
   bool observed_only() const { return !par2 && blk.sparse && blk.sem.on; }   // sparse block whose unstored entries are missing
   bool missing() const { return masked() || observed_only(); }        // the block takes part in the EM step
 };
@@ -234,6 +234,7 @@ class Engine {
   void par2_slab_upload(int p, int k, const double* Xk);
   void par2_slab_upload_coo(int p, int64_t nnz, const int64_t* subs, const double* vals);
   void tensor_mask_upload(int p, const uint8_t* mask);
+  void tensor_weights_upload(int p, const double* W);   // full array, like the mask; null: the block is plain again
   void par2_slab_mask_upload(int p, int k, const uint8_t* mask);
   void set_observed_only(int p, bool on);          // sparse CP block: unstored entries are missing (sparse_em.h)
   // weights in [0, 1] for the stored entries (wts null with nnz = 0: all 1) and one for every unstored entry

@@ -371,7 +371,8 @@ void Engine::tensor_storage_info(int p, int* precision, double* scale, int64_t* 
   if (resident_bytes) {
     int64_t n = 0;
     if (dense_cp) {
-      for (const DevBuf* d : {&b.X.data, &b.Xt.data, &b.copy[0].buf, &b.copy[1].buf, &b.copy[2].buf, &b.mask, &b.maskT})
+      for (const DevBuf* d : {&b.X.data, &b.Xt.data, &b.copy[0].buf, &b.copy[1].buf, &b.copy[2].buf, &b.mask, &b.maskT,
+                              &b.X0, &b.Wt, &b.X0t, &b.WtT})
         if (d->p) n += (int64_t)d->bytes;
     } else if (!t.par2) {            // the per-mode copies of the nonzeros this rank holds: N (4 N + 8) bytes each
       for (int m = 0; m < b.coo.nd; ++m)
@@ -405,6 +406,7 @@ void Engine::tensor_upload(int p, const double* data, int prec, int64_t row0, in
     AO_REQUIRE(per * (world_ - 1) < I, "tensor %d: first mode of %lld rows cannot be split over %d ranks (the last rank would own no rows)",
                p, (long long)I, world_);
     if (world_ == 1) {
+      t.blk.clear_weights();             // past the last refusal: new data makes a plain block again
       block_upload(cx, t.blk, t.nmodes, dims, data, prec, 0, I);
     } else {
       int64_t ncols = 1;
@@ -412,9 +414,11 @@ void Engine::tensor_upload(int p, const double* data, int prec, int64_t row0, in
       std::vector<double> blk((size_t)local_rows * ncols);
       for (int64_t c = 0; c < ncols; ++c)
         std::memcpy(&blk[(size_t)c * local_rows], data + c * I + row0, (size_t)local_rows * sizeof(double));
+      t.blk.clear_weights();
       block_upload(cx, t.blk, t.nmodes, dims, blk.data(), prec, row0, local_rows, data);
     }
   } else {
+    t.blk.clear_weights();
     block_upload(cx, t.blk, t.nmodes, dims, data, prec, row0, local_rows);
   }
   t.normsq_valid = false;
@@ -441,7 +445,7 @@ void Engine::tensor_upload_coo(int p, int64_t nnz, const int64_t* subs, const do
   drop_pass_copies(b);
   b.X.data.release(); b.Xt.data.release();
   b.emkr.release(); b.emkr2.release(); b.T.release(); b.frag.release(); b.scratch.release(); b.ft.release();
-  b.tmpA.release(); b.tmpB.release(); b.mask.release(); b.maskT.release();
+  b.tmpA.release(); b.tmpB.release(); b.mask.release(); b.maskT.release(); b.clear_weights();
   for (int i = 0; i < 2; ++i) { b.own[i].release(); b.own_bytes[i] = 0; b.own_row0[i] = -1; }
   b.coo = std::move(coo);
   b.sem.clear();                                       // a new upload is a plain block again
@@ -625,8 +629,51 @@ void Engine::tensor_mask_upload(int p, const uint8_t* mask) {
     AO_HIP(hipStreamSynchronize(stream_));             // bytesT and mt are locals
   }
   AO_HIP(hipStreamSynchronize(stream_));
+  block_drop_weights(block_ctx(), b);                // the later of mask and weights wins: Xhat <- X0 (nothing can refuse any more)
   b.has_mask = true;
+  b.mask_imputed = false;
   drop_pass_copies(b);                               // the imputation would have to update them too
+  t.normsq_valid = false;
+}
+
+// Per-entry weights on a dense CP block: W in [0, 1] of the block's shape, the FULL array under
+// a communicator like the mask.  Everything is checked before the block changes.
+void Engine::tensor_weights_upload(int p, const double* W) {
+  require_usable();
+  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
+  AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
+  TensorInfo& t = tensors_[p];
+  if (t.par2)
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("per-entry weights are for CP blocks: tensor %d is PARAFAC2", p));
+  CpBlock& b = t.blk;
+  AO_REQUIRE(b.has_data, "tensor %d has no data: upload Z.object{%d} before its weights", p, p + 1);
+  AO_REQUIRE(!b.sparse, "tensor %d holds sparse data: its weights go through aoadmm_tensor_set_entry_weights", p);
+  AO_REQUIRE(!b.half, "tensor %d is stored as fp16: per-entry weights need fp64 or fp32 storage", p);
+  AO_REQUIRE(!b.x_released, "Z.object{%d} was released after its pass copies were built: upload it again before its weights", p + 1);
+  AO_REQUIRE(!(b.has_mask && b.mask_imputed), "Z.object{%d} holds imputed values at its missing entries (a masked EM pass has run): upload the data again before its weights", p + 1);
+  AO_HIP(hipSetDevice(device_));
+  const BlockCtx cx = block_ctx();
+  if (W == nullptr) {
+    if (b.has_weights) { block_drop_weights(cx, b); t.normsq_valid = false; }
+    return;
+  }
+  const int64_t Iloc = b.dims[0], Ifull = b.full0;
+  int64_t ncols = 1;
+  for (int i = 1; i < b.nd; ++i) ncols *= b.dims[i];
+  bool ok;
+  if (Iloc == Ifull) {
+    ok = block_set_weights(cx, b, W);
+  } else {                                             // this rank's rows of every column
+    // the same verdict on every rank: each holds the whole W and checks all of it, not only the rows it keeps
+    if (!block_weights_in_range(cx, W, Ifull * ncols))
+      throw Error(AOADMM_ERR_INVALID, fmt("weights of tensor %d: a value is not a finite number in [0, 1] (divide the weights by their maximum)", p));
+    std::vector<double> rows((size_t)Iloc * ncols);
+    for (int64_t c = 0; c < ncols; ++c)
+      std::memcpy(&rows[(size_t)c * Iloc], W + c * Ifull + b.row0, (size_t)Iloc * sizeof(double));
+    ok = block_set_weights(cx, b, rows.data());
+  }
+  if (!ok)
+    throw Error(AOADMM_ERR_INVALID, fmt("weights of tensor %d: a value is not a finite number in [0, 1] (divide the weights by their maximum)", p));
   t.normsq_valid = false;
 }
 
@@ -667,7 +714,7 @@ void Engine::set_entry_weights(int p, int64_t nnz, const int64_t* subs, const do
   CpBlock& b = t.blk;
   AO_REQUIRE(b.has_data, "tensor %d has no data: upload it with aoadmm_tensor_upload_coo first", p);
   if (!b.sparse)
-    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("entry weights are for sparse CP blocks: tensor %d holds dense data (use Z.miss / aoadmm_tensor_mask_upload)", p));
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("aoadmm_tensor_set_entry_weights is for sparse CP blocks: tensor %d holds dense data (use aoadmm_tensor_weights_upload, or Z.miss / aoadmm_tensor_mask_upload)", p));
   if (b.coo.sharded)
     throw Error(AOADMM_ERR_UNSUPPORTED, fmt("entry weights are not available for a block uploaded with aoadmm_tensor_upload_coo_sharded (tensor %d): upload it replicated", p));
   AO_REQUIRE(b.coo.nnz > 0, "tensor %d has no stored entry: a weighted block needs observations", p);
@@ -766,7 +813,7 @@ void Engine::resident_em_pass(int p, int update, int fuse, double stats[4], doub
     AO_REQUIRE(t.blk.has_data && !t.blk.sparse, "tensor %d holds no dense data (sparse blocks: aoadmm_resident_em_step)", p);
     AO_REQUIRE(!t.blk.half, "tensor %d is stored as fp16: it has no EM pass", p);
   }
-  AO_REQUIRE(t.masked(), "tensor %d has no mask (aoadmm_tensor_mask_upload / aoadmm_par2_slab_mask_upload)", p);
+  AO_REQUIRE(t.masked(), "tensor %d is neither masked nor weighted (aoadmm_tensor_mask_upload / aoadmm_par2_slab_mask_upload / aoadmm_tensor_weights_upload)", p);
   for (int i = 0; i < t.nmodes; ++i) AO_REQUIRE(modes_[t.modes[i]].has_fac, "G.fac{%d} missing", t.modes[i] + 1);
   AO_HIP(hipSetDevice(device_));
   EmPassInfo pi;
@@ -835,6 +882,7 @@ void Engine::em_pass_enqueue(int p, int update, int fuse, EmPassInfo* info) {
   const ModeInfo& m1 = modes_[t.modes[1]];
   EmCpArgs a;
   a.X = b.X.data.p; a.mask = b.mask.as<uint8_t>();
+  if (b.has_weights) { a.X0 = b.X0.p; a.Wt = b.Wt.p; fuse = kEmFuseNone; }   // no fused form: the plain pass, then the ordinary contraction
   a.A = m0.fac.d() + (sharded() ? b.row0 : 0); a.ldA = m0.rows;
   a.B = m1.fac.d(); a.ldB = m1.rows;
   a.C = nullptr; a.ldC = 0;
@@ -890,11 +938,17 @@ void Engine::em_pass_enqueue(int p, int update, int fuse, EmPassInfo* info) {
     a.t_chunk_stride = fpl.trows() * a.R;
   }
   if (info) { info->launch = em_cp_launch_of(a, b.X.prec, a.T != nullptr); info->fused = fused_c; info->walk = a.walk; }
+  // the op-level call (aoadmm_resident_em_pass) brackets the pass with events of class kStatsEmPass; a solve records none
+  const double es = (double)b.X.elem_size(), ne = (double)b.X.elems_padded();
+  const LaunchTimers::Pair pr = info ? timers_.begin(timers_.stats[kStatsEmPass], timers_.profile, stream_) : LaunchTimers::Pair();
   em_cp_pass(a, b.X.prec, emws_.d(), dev_.em(p), stream_);
+  if (info) timers_.end(timers_.stats[kStatsEmPass], pr, stream_, b.has_weights ? (update ? 4 : 3) * es * ne : (update ? 2 : 1) * es * ne + ne / 8, 0.0);
+  if (update && b.has_mask) b.mask_imputed = true;
   if (b.nd == 2 && update) {
     // same imputation on the transposed copy (roles of the two factors swapped); its statistics are discarded
     EmCpArgs at = a;
     at.X = b.Xt.data.p; at.mask = b.maskT.as<uint8_t>();
+    if (b.has_weights) { at.X0 = b.X0t.p; at.Wt = b.WtT.p; }
     at.A = m1.fac.d(); at.ldA = m1.rows; at.B = m0.fac.d() + (sharded() ? b.row0 : 0); at.ldB = m0.rows;
     at.I = b.dims[1]; at.Ipad = b.Xt.pad0; at.J = b.dims[0];
     const size_t wsb = em_cp_ws_bytes(at.Ipad, at.J, 1);

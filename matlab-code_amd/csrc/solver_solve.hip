@@ -249,6 +249,8 @@ void Engine::solve_setup(const aoadmm_options& opt) {
       for (int k = 0; k < t.p2.K; ++k)
         AO_REQUIRE(t.p2.have_P[k] && t.p2.have_mu[k], "G.P{%d}{%d} / G.mu_DeltaB{%d}{%d} missing", p + 1, k + 1, p + 1, k + 1);
     }
+    // a weighted block starts every solve from Xhat = W o X0 (M_old = 0), whatever an earlier solve imputed
+    if (!t.par2 && t.blk.has_weights) block_reset_weighted(block_ctx(), t.blk);
     (void)tensor_normsq(p);          // Znorm_const{p}; a masked block needs the factors (statistics-only EM pass)
     if (t.observed_only()) {         // a solve starts with the missing entries at 0: no snapshot of an earlier one
       const CpBlock& b = t.blk;

@@ -400,7 +400,8 @@ def entry_weight_blocks(Z, entry_weights, unstored_weight, observed=(), sparse_s
                                'supported)' % (p + 1))
         coo = None if isinstance(obj, dict) else coo_of(obj)
         if coo is None:
-            raise _unsupported('sparse_entry_weights: Z.object{%d} is dense (weights are for sparse CP blocks)' % (p + 1))
+            raise _unsupported('sparse_entry_weights: Z.object{%d} is dense (weights are for sparse CP blocks; a dense block '
+                               'takes entry_weights)' % (p + 1))
         alpha = unstored_weight if scalar else (None if unstored_weight is None else unstored_weight[p])
         alpha = 0.0 if alpha is None else float(alpha)
         if not (np.isfinite(alpha) and 0.0 <= alpha <= 1.0):
@@ -418,6 +419,47 @@ def entry_weight_blocks(Z, entry_weights, unstored_weight, observed=(), sparse_s
     if out and sparse_sharding:
         raise _unsupported('sparse_entry_weights is not available together with sparse_sharding: a weighted block is '
                            'replicated')
+    return out
+
+
+def dense_weight_blocks(Z, entry_weights):
+    """`alg_options['hip']['entry_weights']` -> {0-based block: W (float64, column-major) as it goes to
+    `Engine.tensor_weights_upload`}, checked on the host before the engine is touched.  The option is None or a list over
+    the blocks holding None or an array of the block's shape with entries in [0, 1]; with Z.miss{p} as well the block's
+    weights are W o miss and no mask is uploaded (w = 0 is the spelling of "missing").  ValueError: a list of another
+    length than Z.object, a wrong shape, a weight that is not finite or lies outside [0, 1].  `UnsupportedOnDevice`: a
+    PAR2 block, and a sparse block (its weights are `sparse_entry_weights`)."""
+    P = len(Z['object'])
+    if entry_weights is None:
+        return {}
+    if not isinstance(entry_weights, (list, tuple)) or len(entry_weights) != P:
+        raise ValueError('entry_weights must be a list over the %d blocks of Z.object' % P)
+    miss = Z.get('miss') if Z.get('miss') is not None else [None] * P
+    out = {}
+    for p in range(P):
+        if entry_weights[p] is None:
+            continue
+        obj = Z['object'][p]
+        if Z['model'][p] != 'CP':
+            raise _unsupported('entry_weights: Z.object{%d} is a PARAFAC2 block (weights are for dense CP blocks, and for '
+                               'sparse ones through sparse_entry_weights)' % (p + 1))
+        if isinstance(obj, dict):
+            raise ValueError('entry_weights needs explicit data in Z.object{%d}' % (p + 1))
+        if coo_of(obj) is not None:
+            raise _unsupported('entry_weights: Z.object{%d} is sparse (use sparse_entry_weights / sparse_unstored_weight)'
+                               % (p + 1))
+        W = np.asarray(entry_weights[p], dtype=np.float64)
+        if tuple(W.shape) != tuple(np.shape(obj)):
+            raise ValueError('entry_weights{%d} has size %s, Z.object{%d} has %s' % (p + 1, tuple(W.shape), p + 1,
+                                                                                  tuple(np.shape(obj))))
+        if not (np.all(np.isfinite(W)) and np.all(W >= 0.0) and np.all(W <= 1.0)):
+            raise ValueError('entry_weights{%d}: a weight is outside [0, 1] (divide the weights by their maximum)' % (p + 1))
+        if miss[p] is not None:
+            mk = np.asarray(miss[p])
+            if tuple(mk.shape) != tuple(W.shape):
+                raise ValueError('Z.miss{%d} size does not match Z.object{%d}.' % (p + 1, p + 1))
+            W = W * (mk != 0)
+        out[p] = np.asfortranarray(W)
     return out
 
 
@@ -577,7 +619,8 @@ def heldout_keep_best_option(value, lists):
     return int(value)
 
 
-def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0, entry_weights=None, unstored_weight=None):
+def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0, entry_weights=None, unstored_weight=None,
+                dense_entry_weights=None):
     """Describe the struct Z to the engine and upload Z.object (cmtf_AOADMM.m:23-41,124-156).
 
     Z.object{p} of a CP block may be dense, an `sptensor`, or (2-way blocks) any object with `.tocoo()` such as a
@@ -600,8 +643,13 @@ def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0,
     raising the reference's error.
     entry_weights, unstored_weight (`entry_weight_blocks`): weighted least squares on the named sparse CP blocks
     (`Engine.set_entry_weights`): a weight in [0, 1] for every stored entry and one for all unstored entries.  A named
-    block is marked observed-only as well."""
+    block is marked observed-only as well.
+    dense_entry_weights (`dense_weight_blocks`): weighted least squares on the named DENSE CP blocks
+    (`Engine.tensor_weights_upload`): a list over the blocks, or the dict `dense_weight_blocks` made of it; a block with Z.miss as well
+    gets W o miss as weights and no mask.  Under 'f16' such a block goes up as fp32, like a masked one."""
     prec = capi.precision_id(precision)                # an unknown string fails before the engine is touched
+    # a dict is what dense_weight_blocks returned to the caller already: not checked and copied a second time
+    dense_w = dense_entry_weights if isinstance(dense_entry_weights, dict) else dense_weight_blocks(Z, dense_entry_weights)
     observed = observed_only_blocks(Z, observed_only, sparse_sharding)
     weighted = entry_weight_blocks(Z, entry_weights, unstored_weight, observed, sparse_sharding)
     observed = sorted(set(observed) | set(weighted))
@@ -674,7 +722,7 @@ def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0,
             obj = Z['object'][p]
             # 'f16': dense 3-way blocks without a mask; matrices, order > 3 and masked blocks go up as fp32
             prec = model_prec
-            if prec == capi.PREC_F16 and (len(Z['modes'][p]) != 3 or miss[p] is not None):
+            if prec == capi.PREC_F16 and (len(Z['modes'][p]) != 3 or miss[p] is not None or p in dense_w):
                 prec = capi.PREC_F32
             coo = None if isinstance(obj, dict) else coo_of(obj)
             if coo is not None:
@@ -704,6 +752,9 @@ def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0,
                 if tuple(X.shape) != tuple(int(Z['size'][m]) for m in md):
                     raise ValueError('Z.object{%d} has size %s, Z.size says %s' % (p + 1, X.shape, [Z['size'][m] for m in md]))
                 capi.check(lib.aoadmm_tensor_upload(eng.h, p, capi.dptr(X), prec))
+            if p in dense_w:                                                         # carries Z.miss{p} as zeros
+                eng.tensor_weights_upload(p, dense_w[p])
+                continue
             if miss[p] is not None:                                                  # cmtf_AOADMM.m:78-97
                 if isinstance(obj, dict):
                     raise ValueError('Z.miss needs explicit data in Z.object{%d}' % (p + 1))
@@ -939,6 +990,9 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
     # per stored entry and one for the unstored entries of the named sparse CP blocks, which are observed-only as well
     weights_opt, alpha_opt = hip.get('sparse_entry_weights'), hip.get('sparse_unstored_weight')
     observed = sorted(set(observed) | set(entry_weight_blocks(Z, weights_opt, alpha_opt, observed, sharding)))
+    # alg_options['hip']['entry_weights'] (`dense_weight_blocks`): an array of weights in [0, 1] per named DENSE CP block
+    dense_w_opt = hip.get('entry_weights')
+    dense_weighted = dense_weight_blocks(Z, dense_w_opt)
     # alg_options['hip']['heldout'] = {1-based block: (subs, vals) | sptensor} and ['heldout_patience'] (`heldout_lists`):
     # entries kept out of the fit, scored on the device with every evaluation of the objective
     held = heldout_lists(Z, hip.get('heldout'), hip.get('heldout_patience', 0))
@@ -949,7 +1003,7 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
     # rank_criterion = 1 the one with the best ranking score
     keep_best = heldout_keep_best_option(hip.get('heldout_keep_best', 0), rank['lists'] if rank['criterion'] == 1 else held)
     build_model(eng, Z, precision, sparse_sharding=sharding, observed_only=observed_opt, entry_weights=weights_opt,
-                unstored_weight=alpha_opt)
+                unstored_weight=alpha_opt, dense_entry_weights=dense_weighted)
     for p, (hs, hv) in sorted(held.items()):
         eng.set_heldout(p, hs, hv)
     for p, (rmode, rsubs, rexcl) in sorted(rank['lists'].items()):
@@ -960,7 +1014,7 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
         eng.heldout_keep_best(True)
     upload_state(eng, Z, G)
     out = run_solver(eng, alg_options, nb_modes,
-                     has_missing=bool(observed) or (Z.get('miss') is not None and any(m is not None for m in Z['miss'])))
+                     has_missing=bool(observed) or bool(dense_weighted) or (Z.get('miss') is not None and any(m is not None for m in Z['miss'])))
     if held:
         # out.func_heldout{block}: sum (y - m)^2 at iteration 0 .. OuterIterations; with heldout_sumsq = sum y^2 and
         # heldout_count the relative error sqrt(func_heldout / heldout_sumsq) and the RMSE sqrt(func_heldout /

@@ -175,6 +175,17 @@ class Engine:
                                                             subs.ctypes.data_as(C.POINTER(C.c_int64)), capi.dptr(wts),
                                                             float(unstored_weight)))
 
+    def tensor_weights_upload(self, p, W):
+        """Per-entry weights for the dense CP block p (`aoadmm_tensor_weights_upload`): W has the block's shape (the full
+        array under a communicator) with entries in [0, 1]; upload after the data.  None removes the weights.  An fp32
+        block keeps W rounded to fp32.  A value outside [0, 1] raises `AoadmmError` (ERR_INVALID) and leaves the block
+        as it was."""
+        if W is None:
+            capi.check(self.lib.aoadmm_tensor_weights_upload(self.h, int(p), None))
+            return
+        W = np.asfortranarray(np.asarray(W, dtype=np.float64))
+        capi.check(self.lib.aoadmm_tensor_weights_upload(self.h, int(p), capi.dptr(W)))
+
     def em_step(self, p):
         """One EM step of the observed-only block p with the current factors (`aoadmm_resident_em_step`):
         (sum over the stored entries of (x - m)^2, num, den) of `f_rel_missing`; `resident_mttkrp` then returns the
@@ -184,7 +195,7 @@ class Engine:
         return float(st[0]), float(st[1]), float(st[2])
 
     def resident_em_pass(self, p, dims, R, update=1, fuse=0, with_data=True):
-        """One EM pass over the masked dense block p with the current factors, as a solve runs it
+        """One EM pass over the masked or weighted dense block p with the current factors, as a solve runs it
         (`aoadmm_resident_em_pass`).  dims: the block's sizes (a PARAFAC2 block: (I, [J_k], K)); fuse: 0 none, 1 the
         solver's choice, 2 the second mode.  Returns a dict: stats = (num, den, obs_res, obs_x2) as a float64 array;
         data = the block after the pass as doubles (PARAFAC2: a list of I x J_k slabs), data_t = a matrix block's
@@ -581,7 +592,7 @@ class Engine:
         """(ms, launches, bytes, flops) of a kernel class since the last reset (`aoadmm_kernel_stats`); which = 3:
         MTTKRPs of sparse blocks (of a sharded block: this rank's share), passes over the nonzeros of PARAFAC2
         blocks with sparse slabs and EM steps of observed-only blocks; which = 4 + n: the pass of those EM steps over
-        the copy of tensor mode n; which = 12: the held-out passes; which = 13: the top-k completions and the ranks of targets (one launch per `topk` or `rank_of` call and per
+        the copy of tensor mode n, and for which = 4 the pass of every `resident_em_pass` call over a dense CP block; which = 12: the held-out passes; which = 13: the top-k completions and the ranks of targets (one launch per `topk` or `rank_of` call and per
         evaluation of a ranking list inside a solve);
         which = 14: the fold-in of new rows (one launch per `fold_in` call, weighted or not)."""
         ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
