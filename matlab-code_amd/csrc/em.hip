@@ -8,7 +8,10 @@
 // tensor is read once (16-byte loads), the mask is ONE BIT per entry (packed on the device when Z.miss arrives: at
 // 1000^3 the byte-per-entry mask was 1 GB of the pass's 9 GB), and only 128-byte lines that contain a missing entry are
 // written back: the pass is bound by HBM like the contractions.
-// A block with per-entry weights (EmCpArgs::X0 / Wt) runs the weighted forms of both kernels below.
+// The walk is written once: the strip kernel em_cp_vec_k (R <= 32) and the one-row kernel em_cp_k (beyond) share the
+// geometry (EmWalk), the prologue, the tile staging, the line write-back and the epilogue, and take what differs per
+// entry from a policy: EmMasked (data + mask bits; the only one that can fuse the contraction) or EmWeighted (X0, W and
+// Xhat of a block with per-entry weights, EmCpArgs::X0 / Wt).
 #include "em.h"
 
 #include <algorithm>
@@ -19,6 +22,7 @@ namespace aoadmm {
 template <typename T, int VEC> struct EmVec;
 template <> struct EmVec<float, 4> { typedef float type __attribute__((ext_vector_type(4))); };
 template <> struct EmVec<double, 2> { typedef double type __attribute__((ext_vector_type(2))); };
+template <typename T> struct EmVec<T, 1> { typedef T type __attribute__((ext_vector_type(1))); };   // the one-row kernel
 
 // Z.miss as one bit per entry (bit e of the padded layout in byte e >> 3, position e & 7), 1 = observed.  A thread's VEC
 // entries start at a multiple of VEC, so they sit in one byte.
@@ -28,7 +32,7 @@ __global__ void em_mask_pack_k(const uint8_t* __restrict__ bytes, uint8_t* __res
   if (e0 >= n) return;
   unsigned v = 0;
   if (e0 + 8 <= n) {
-    const uint64_t w = *reinterpret_cast<const uint64_t*>(bytes + e0);     // cudaMalloc-aligned base, e0 multiple of 8
+    const uint64_t w = *reinterpret_cast<const uint64_t*>(bytes + e0);     // hipMalloc-aligned base, e0 multiple of 8
 #pragma unroll
     for (int q = 0; q < 8; ++q) v |= (((w >> (8 * q)) & 0xff) != 0 ? 1u : 0u) << q;
   } else {
@@ -52,6 +56,15 @@ __device__ __forceinline__ double em_block_sum(double v, double* sh4) {
   const double r = (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
   __syncthreads();
   return r;
+}
+
+// The end of every pass kernel: the workgroup's four statistics, summed in fixed order, into its slot w of the workspace
+__device__ __forceinline__ void em_store_stats(double num, double den, double ores, double ox2, double* sh4, double* w) {
+  num = em_block_sum(num, sh4); den = em_block_sum(den, sh4);
+  ores = em_block_sum(ores, sh4); ox2 = em_block_sum(ox2, sh4);
+  if (threadIdx.x == 0) {
+    w[0] = num; w[1] = den; w[2] = ores; w[3] = ox2;
+  }
 }
 
 // acc + a * b[h] on both rows of a register pair: v_pk_fma_f32 reading one half of the pair `b` for both lanes
@@ -119,134 +132,254 @@ __device__ __forceinline__ void em_row_axpy(XV* tacc, const T* brow, XV x) {
   }
 }
 
-// Strip kernel for R <= 32.  Everything in the column loop is branch-free vector arithmetic in the tensor's
-// precision (v_pk_*_f32 for fp32): the first version spent ~330 vector instructions per 16-byte vector of entries
-// (a register ring shifted with moves, one branch per entry, fp64 statistics) and was bound by instruction issue
-// at 4.3 TB/s, not by memory.
-//   * VEC rows of A (times C(k,:)) per thread, held as R vectors areg[r]; B rows broadcast from LDS (ds_read_b128)
-//   * loads run PD columns ahead in a statically indexed register ring (the column loop is unrolled by PD)
-//   * the four statistics are accumulated per 64-column tile in the tensor's precision (64 terms per accumulator
-//     lane) and join the fp64 sums once per tile
-//   * padding rows (i >= I; the tensor holds zeros there) get a zero row of A and are forced 'observed': they add
-//     exact zeros and are written back unchanged
-//   * write-back by 128-byte line: a line leaves (streaming stores of all its vectors) when any of its entries is
-//     missing -- whole cache lines, nothing read-modified-written in L2 (storing only the VECTORS with a missing entry
-//     measured slower than storing everything); at 20 % missing every line qualifies, at 1 % about a quarter
-//   * the strip can walk the second mode at a fixed third-mode index (walk = 1) or the third mode at a fixed
-//     second-mode index (walk = 2, steps of Ipad*J elements); with FUSE it also accumulates, from the values it
-//     writes back, the partial contraction of the walked mode  T(i, f, r) = sum_w x_new(i, w, f) W(w, r)  -- the
-//     tensor pass the next outer iteration would start with (contract.h ContractPlan: T is [chunk][i + Ipad*f][R]
-//     in the tensor's precision, one chunk per piece of the walk)
-template <typename T, int VEC, int RMAX, bool FUSE>
-__global__ __launch_bounds__(kEmThreads, FUSE ? 2 : 1) void em_cp_vec_k(EmCpArgs a, int jchunks, int64_t jlen, double* ws) {
-  typedef typename EmVec<T, VEC>::type XV;
-  typedef uint8_t MV;                                                    // the byte that holds this thread's VEC mask bits
-  constexpr unsigned kFull = (1u << VEC) - 1u;
-  __shared__ __attribute__((aligned(16))) T Bsh[kEmJTile][RMAX];
-  __shared__ double sh4[4];
-  const int R = a.R;
-  const int t = threadIdx.x;
-  const bool wj = a.walk != 2;                                           // walking the second mode
-  const int64_t f = blockIdx.y;                                          // the fixed index (k, or j when walking k)
-  const int64_t NW = wj ? a.J : a.K;
-  const double* Ff = wj ? a.C : a.B;                                     // factor of the fixed mode: scales the rows of A
-  const int64_t ldf = wj ? a.ldC : a.ldB;
-  const double* Fw = wj ? a.B : a.C;                                     // factor of the walked mode: rows through LDS
-  const int64_t ldw = wj ? a.ldB : a.ldC;
-  const int64_t step = wj ? a.Ipad : a.Ipad * a.J;                       // elements between two walk positions
-  const int chunk = blockIdx.x % jchunks;                                // the walk is cut into jchunks pieces
-  const int64_t i0 = ((int64_t)(blockIdx.x / jchunks) * kEmThreads + t) * VEC;   // first row of this thread
-  const int64_t jbeg = chunk * jlen, jend = jbeg + jlen < NW ? jbeg + jlen : NW;
-  XV areg[RMAX];                                                         // areg[r][v] = A(i0+v, r) * Ff(f, r)
-  unsigned padmask = 0;
+// Where a thread of a pass kernel stands: the strip can walk the second mode at a fixed third-mode index (walk = 1) or
+// the third mode at a fixed second-mode index (walk = 2, steps of Ipad*J elements).  The walk is cut into jchunks pieces
+// of jlen positions; a thread owns the VEC rows from i0 on.
+// The shared pieces below take EmCpArgs and EmWalk BY VALUE: with the kernel-argument struct handed on by reference the
+// fused R = 20 fp32 instantiation went from 20 to 52 bytes of scratch per lane (profiles/em_strip_once.md).
+template <int VEC> struct EmWalk {
+  bool wj;                                                               // walking the second mode
+  int64_t f;                                                             // the fixed index (k, or j when walking k)
+  const double *Ff, *Fw;                                                 // factors of the fixed mode (scales the rows of A) and of the walked mode (rows through LDS)
+  int64_t ldf, ldw;
+  int64_t step;                                                          // elements between two walk positions
+  int chunk;
+  int64_t i0, jbeg, jend;
+  int64_t base;                                                          // first element at the fixed index
+  bool in_range;                                                         // Ipad is a multiple of VEC
+  __device__ __forceinline__ EmWalk(EmCpArgs a, int jchunks, int64_t jlen) {
+    wj = a.walk != 2;
+    f = blockIdx.y;
+    const int64_t NW = wj ? a.J : a.K;
+    Ff = wj ? a.C : a.B;
+    ldf = wj ? a.ldC : a.ldB;
+    Fw = wj ? a.B : a.C;
+    ldw = wj ? a.ldB : a.ldC;
+    step = wj ? a.Ipad : a.Ipad * a.J;
+    chunk = blockIdx.x % jchunks;
+    i0 = ((int64_t)(blockIdx.x / jchunks) * kEmThreads + threadIdx.x) * VEC;
+    jbeg = chunk * jlen;
+    jend = jbeg + jlen < NW ? jbeg + jlen : NW;
+    base = (wj ? a.Ipad * a.J : a.Ipad) * f;
+    in_range = i0 < a.Ipad;
+  }
+  // row i0 + v is padding (i >= I; the arrays hold zeros there); padmask: bit v set for such a row
+  __device__ __forceinline__ bool pad(EmCpArgs a, int v) const { return i0 + v >= a.I; }
+  __device__ __forceinline__ unsigned padmask(EmCpArgs a) const {
+    unsigned m = 0;
 #pragma unroll
-  for (int v = 0; v < VEC; ++v)
-    if (i0 + v >= a.I) padmask |= 1u << v;
+    for (int v = 0; v < VEC; ++v)
+      if (pad(a, v)) m |= 1u << v;
+    return m;
+  }
+};
+
+// Prologue: areg[r][v] = A(i0+v, r) * Ff(f, r), zero for padding rows and for r >= R
+template <typename T, int VEC, int RMAX, bool FUSE, typename XV>
+__device__ __forceinline__ void em_load_rows(EmCpArgs a, const EmWalk<VEC> g, XV* areg) {
+  const int R = a.R;
 #pragma unroll
   for (int r = 0; r < RMAX; ++r) {
     const int rr = r < R ? r : 0;
-    const double c = Ff ? Ff[f + ldf * rr] : 1.0;
+    const double c = g.Ff ? g.Ff[g.f + g.ldf * rr] : 1.0;
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
-      const bool valid = i0 + v < a.I;
-      const int64_t i = valid ? i0 + v : a.I - 1;
+      const bool valid = g.i0 + v < a.I;
+      const int64_t i = valid ? g.i0 + v : a.I - 1;
       areg[r][v] = (r < R && valid) ? (T)(a.A[i + a.ldA * rr] * c) : (T)0;
     }
     // the fp64 loads of this prologue must not all be in flight at once: 2 * VEC * RMAX registers on top of tacc
     if constexpr (FUSE) { if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0); }
   }
-  const int64_t base = (wj ? a.Ipad * a.J : a.Ipad) * f;
-  T* X = reinterpret_cast<T*>(a.X) + base;
-  const uint8_t* M = a.mask;                                             // bits: entry e at byte e >> 3, position e & 7
-  const int64_t mbase = base + i0;                                       // this thread's first entry at walk position 0
-  const unsigned sh0 = (unsigned)(mbase & 7), shs = (unsigned)(step & 7);   // position inside the byte at walk position w: (sh0 + shs*w) & 7
-  const int lane = t & 63;
-  const bool in_range = i0 < a.Ipad;                                     // Ipad is a multiple of VEC
+}
+
+// Rows j0 .. j0+63 of the walked mode's factor into the LDS tile, zero past jend and for r >= R
+template <typename T, int VEC, int RMAX>
+__device__ __forceinline__ void em_stage_tile(T (*Bsh)[RMAX], const EmWalk<VEC> g, int R, int64_t j0) {
+  const int t = threadIdx.x;
+  __syncthreads();
+  for (int e = t; e < kEmJTile * RMAX; e += kEmThreads) {
+    const int jj = e / RMAX, r = e - jj * RMAX;
+    Bsh[jj][r] = (r < R && j0 + jj < g.jend) ? (T)g.Fw[j0 + jj + g.ldw * r] : (T)0;
+  }
+  __syncthreads();
+}
+
+// Write-back of the strip kernel.  Only 128-byte lines in which some lane's vector `changes` go back (at 1-5 % missing
+// most lines hold no missing entry; whole lines, so nothing is read-modified-written in L2 -- storing single 16-byte
+// vectors was slower than storing everything).  The wave's 1024 bytes start 16-byte aligned: lane l shares its line with
+// the lanes of the same (l + s) >> 3, s = the first lane's 16-byte slot inside its line; lines cut by the wave's ends go
+// back if this wave's part of them changes.
+template <typename XV>
+__device__ __forceinline__ void em_line_store(bool changes, XV xn, XV* dst) {
+  const unsigned lane = threadIdx.x & 63;
+  const unsigned long long bal = __ballot(changes);
+  const unsigned s16 = (unsigned)(((reinterpret_cast<uintptr_t>(dst) >> 4) - lane) & 7u);
+  const unsigned g = (lane + s16) >> 3;
+  const unsigned grp = g < 8 ? (unsigned)((bal << s16) >> (8 * g)) & 0xffu : (unsigned)(bal >> (64 - s16)) & 0xffu;
+  if (grp) __builtin_nontemporal_store(xn, dst);
+}
+
+// ---- entry policies ---------------------------------------------------------------------------------------------------------
+// What a pass reads per vector of entries and what it makes of it.  A policy names its ring slot, loads one for a walk
+// position w (the strip kernel streams, the one-row kernel's loads are plain), and evaluates it against the model
+// vector m: the new value, whether it differs from what is stored (`changes`), and the four statistics' accumulators.
+template <int VEC, typename XV>
+__device__ __forceinline__ XV em_load(const XV* p) {
+  if constexpr (VEC > 1) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+
+// Masked block: the data and the byte that holds this thread's VEC mask bits.  Padding rows are forced 'observed': they
+// add exact zeros and are written back unchanged.
+template <typename T, int VEC> struct EmMasked {
+  typedef typename EmVec<T, VEC>::type XV;
+  static constexpr bool kFuses = true;
+  static constexpr unsigned kFull = (1u << VEC) - 1u;
+  struct Slot { XV x; unsigned m; };                                     // m: the byte that holds this thread's VEC mask bits
+  T* X;
+  const uint8_t* M;                                                      // bits: entry e at byte e >> 3, position e & 7
+  int64_t i0, step, mbase;                                               // mbase: this thread's first entry at walk position 0
+  unsigned sh0, shs, padmask;                                            // position inside the byte at walk position w: (sh0 + shs*w) & 7
+  __device__ __forceinline__ EmMasked(EmCpArgs a, const EmWalk<VEC> g)
+      : X(reinterpret_cast<T*>(a.X) + g.base), M(a.mask), i0(g.i0), step(g.step), mbase(g.base + g.i0),
+        sh0((unsigned)(mbase & 7)), shs((unsigned)(g.step & 7)), padmask(g.padmask(a)) {}
+  __device__ __forceinline__ XV* at(int64_t w) const { return reinterpret_cast<XV*>(X + i0 + step * w); }
+  __device__ __forceinline__ Slot load(int64_t w) const {
+    const int64_t o = i0 + step * w;
+    return {em_load<VEC>(reinterpret_cast<const XV*>(X + o)), M[(mbase + step * w) >> 3]};
+  }
+  __device__ __forceinline__ XV eval(const Slot& q, int64_t w, XV m, bool& changes, XV& s_ores, XV& s_ox2, XV& s_num,
+                                     XV& s_den) const {
+    const XV xv = q.x;
+    const unsigned mv = ((q.m >> ((sh0 + shs * (unsigned)w) & 7u)) & kFull) | padmask;
+    const XV d = xv - m;
+    XV od, ox, xn;                                                       // residual / value where observed, else 0
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const bool observed = ((mv >> v) & 1u) != 0;
+      od[v] = observed ? d[v] : (T)0;
+      ox[v] = observed ? xv[v] : (T)0;
+      xn[v] = observed ? xv[v] : m[v];
+    }
+    const XV md = d - od, mx = xv - ox;                                  // the same where missing (exact)
+    s_ores = __builtin_elementwise_fma(od, od, s_ores);
+    s_ox2 = __builtin_elementwise_fma(ox, ox, s_ox2);
+    s_num = __builtin_elementwise_fma(md, md, s_num);
+    s_den = __builtin_elementwise_fma(mx, mx, s_den);
+    changes = mv != kFull;
+    return xn;
+  }
+};
+
+// One vector of entries of the weighted pass (em.h EmCpArgs::X0 / Wt): the new value and the four terms' accumulators.
+// Products and differences are rounded one by one -- contracted, q = fma(-w, x0, xh) would be the rounding residue of
+// em_w_reset's product instead of 0 in a solve's first pass, and f_rel_missing divides by the sum of q^2 -- and the
+// multiply-adds written as such are fused.  With w in {0, 1}, xh = x0 where w = 1 and zeros in x0 where w = 0 every term
+// is the masked policy's, bit for bit: w = 1 gives q = 0, p = 0 and wd = d; w = 0 gives q = xh, wd = 0 and xn = p = m.
+template <typename T, typename XV>
+__device__ __forceinline__ XV em_w_entry(XV x0, XV w, XV xh, XV m, XV& s_ores, XV& s_ox2, XV& s_num, XV& s_den) {
+#pragma clang fp contract(off)
+  const XV wx = w * x0;
+  const XV q = xh - wx;                                                    // (1 - w) m_old
+  const XV p = ((T)1 - w) * m;
+  const XV d = x0 - m;
+  const XV wd = w * d;
+  const XV n = p - q;
+  s_ores = __builtin_elementwise_fma(wd, d, s_ores);
+  s_ox2 = __builtin_elementwise_fma(wx, x0, s_ox2);
+  s_num = __builtin_elementwise_fma(n, n, s_num);
+  s_den = __builtin_elementwise_fma(q, q, s_den);
+  return __builtin_elementwise_fma(w, x0, p);
+}
+
+// Weighted block: three streams in (X0, W, Xhat), Xhat out.  A vector changes when some weight in it is not 1; under unit
+// weights xh = x0 and stays.  Padding rows get w = 1 (X0 and Xhat hold zeros there).
+template <typename T, int VEC> struct EmWeighted {
+  typedef typename EmVec<T, VEC>::type XV;
+  static constexpr bool kFuses = false;                                  // 2 * R register vectors and three streams do not fit
+  struct Slot { XV x0, w, xh; };
+  T* X;
+  const T *X0, *W;
+  int64_t i0, step;
+  bool pad[VEC];
+  __device__ __forceinline__ EmWeighted(EmCpArgs a, const EmWalk<VEC> g)
+      : X(reinterpret_cast<T*>(a.X) + g.base), X0(reinterpret_cast<const T*>(a.X0) + g.base),
+        W(reinterpret_cast<const T*>(a.Wt) + g.base), i0(g.i0), step(g.step) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) pad[v] = g.pad(a, v);
+  }
+  __device__ __forceinline__ XV* at(int64_t w) const { return reinterpret_cast<XV*>(X + i0 + step * w); }
+  __device__ __forceinline__ Slot load(int64_t w) const {
+    const int64_t o = i0 + step * w;
+    return {em_load<VEC>(reinterpret_cast<const XV*>(X0 + o)), em_load<VEC>(reinterpret_cast<const XV*>(W + o)),
+            em_load<VEC>(reinterpret_cast<const XV*>(X + o))};
+  }
+  __device__ __forceinline__ XV eval(const Slot& q, int64_t, XV m, bool& changes, XV& s_ores, XV& s_ox2, XV& s_num,
+                                     XV& s_den) const {
+    XV w = q.w;
+    changes = false;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      w[v] = pad[v] ? (T)1 : w[v];
+      changes |= w[v] != (T)1;
+    }
+    XV xn = em_w_entry<T, XV>(q.x0, w, q.xh, m, s_ores, s_ox2, s_num, s_den);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) xn[v] = w[v] == (T)1 ? q.x0[v] : xn[v];   // the data itself, also beside a model value that is not finite
+    return xn;
+  }
+};
+
+// Strip kernel for R <= 32.  Everything in the column loop is branch-free vector arithmetic in the tensor's
+// precision (v_pk_*_f32 for fp32): the first version spent ~330 vector instructions per 16-byte vector of entries
+// (a register ring shifted with moves, one branch per entry, fp64 statistics) and was bound by instruction issue
+// at 4.3 TB/s, not by memory.
+//   * VEC rows of A (times C(k,:)) per thread, held as R vectors areg[r]; B rows broadcast from LDS (ds_read_b128)
+//   * the policy's loads run PD columns ahead in a statically indexed register ring (the column loop is unrolled by PD)
+//   * the four statistics are accumulated per 64-column tile in the tensor's precision (64 terms per accumulator
+//     lane) and join the fp64 sums once per tile
+//   * write-back by 128-byte line (em_line_store): at 20 % missing every line qualifies, at 1 % about a quarter
+//   * with FUSE it also accumulates, from the values it writes back, the partial contraction of the walked mode
+//     T(i, f, r) = sum_w x_new(i, w, f) W(w, r)  -- the tensor pass the next outer iteration would start with
+//     (contract.h ContractPlan: T is [chunk][i + Ipad*f][R] in the tensor's precision, one chunk per piece of the walk)
+template <typename T, int VEC, int RMAX, bool FUSE, template <typename, int> class POL>
+__global__ __launch_bounds__(kEmThreads, FUSE ? 2 : 1) void em_cp_vec_k(EmCpArgs a, int jchunks, int64_t jlen, double* ws) {
+  static_assert(!FUSE || (POL<T, VEC>::kFuses && RMAX <= kEmFuseMaxRank), "no fused form of this pass");
+  typedef typename EmVec<T, VEC>::type XV;
+  typedef typename POL<T, VEC>::Slot Slot;
+  __shared__ __attribute__((aligned(16))) T Bsh[kEmJTile][RMAX];
+  __shared__ double sh4[4];
+  const int R = a.R;
+  const EmWalk<VEC> g(a, jchunks, jlen);
+  XV areg[RMAX];                                                         // areg[r][v] = A(i0+v, r) * Ff(f, r)
+  em_load_rows<T, VEC, RMAX, FUSE>(a, g, areg);
+  const POL<T, VEC> pol(a, g);
   const XV zero = {};
   XV tacc[FUSE ? RMAX : 1];
 #pragma unroll
   for (int r = 0; r < (FUSE ? RMAX : 1); ++r) tacc[r] = zero;
   double num = 0, den = 0, ores = 0, ox2 = 0;
-  for (int64_t j0 = jbeg; j0 < jend; j0 += kEmJTile) {
-    __syncthreads();
-    for (int e = t; e < kEmJTile * RMAX; e += kEmThreads) {
-      const int jj = e / RMAX, r = e - jj * RMAX;
-      Bsh[jj][r] = (r < R && j0 + jj < jend) ? (T)Fw[j0 + jj + ldw * r] : (T)0;
-    }
-    __syncthreads();
-    const int nj = (int)((jend - j0 < kEmJTile) ? (jend - j0) : kEmJTile);
-    if (!in_range) continue;
+  for (int64_t j0 = g.jbeg; j0 < g.jend; j0 += kEmJTile) {
+    em_stage_tile<T, VEC, RMAX>(Bsh, g, R, j0);
+    const int nj = (int)((g.jend - j0 < kEmJTile) ? (g.jend - j0) : kEmJTile);
+    if (!g.in_range) continue;
     constexpr int PD = 4;                              // columns in flight
-    XV xq[PD]; MV mq[PD];
+    Slot ring[PD];
 #pragma unroll
-    for (int p = 0; p < PD; ++p) {
-      const int64_t wp = j0 + (p < nj ? p : nj - 1);
-      const int64_t op = i0 + step * wp;
-      xq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(X + op));
-      mq[p] = M[(mbase + step * wp) >> 3];
-    }
+    for (int p = 0; p < PD; ++p) ring[p] = pol.load(j0 + (p < nj ? p : nj - 1));
     XV s_ores = zero, s_ox2 = zero, s_num = zero, s_den = zero;
     for (int jj = 0; jj < nj; jj += PD) {
 #pragma unroll
       for (int p = 0; p < PD; ++p) {
         const int jc = jj + p;                                           // wave-uniform
-        const XV xv = xq[p];
-        const unsigned mv = (((unsigned)mq[p] >> ((sh0 + shs * (unsigned)(j0 + jc)) & 7u)) & kFull) | padmask;
-        {
-          const int jn = jc + PD < nj ? jc + PD : nj - 1;                // clamped: the last loads are discarded
-          const int64_t on = i0 + step * (j0 + jn);
-          xq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(X + on));
-          mq[p] = M[(mbase + step * (j0 + jn)) >> 3];
-        }
+        const Slot q = ring[p];
+        ring[p] = pol.load(j0 + (jc + PD < nj ? jc + PD : nj - 1));      // clamped: the last loads are discarded
         if (jc < nj) {
           const XV m = em_row_dot<T, VEC, RMAX, XV>(areg, &Bsh[jc][0], zero);
-          const XV d = xv - m;
-          XV od, ox, xn;                                                 // residual / value where observed, else 0
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) {
-            const bool observed = ((mv >> v) & 1u) != 0;
-            od[v] = observed ? d[v] : (T)0;
-            ox[v] = observed ? xv[v] : (T)0;
-            xn[v] = observed ? xv[v] : m[v];
-          }
-          const XV md = d - od, mx = xv - ox;                            // the same where missing (exact)
-          s_ores = __builtin_elementwise_fma(od, od, s_ores);
-          s_ox2 = __builtin_elementwise_fma(ox, ox, s_ox2);
-          s_num = __builtin_elementwise_fma(md, md, s_num);
-          s_den = __builtin_elementwise_fma(mx, mx, s_den);
-          if (a.update) {
-            // Only 128-byte lines with a missing entry go back (at 1-5 % missing most lines hold none; whole lines, so
-            // nothing is read-modified-written in L2 -- storing single 16-byte vectors was slower than storing everything).
-            // The wave's 1024 bytes start 16-byte aligned: lane l shares its line with the lanes of the same (l + s) >> 3,
-            // s = the first lane's 16-byte slot inside its line; lines cut by the wave's ends go back if this wave's part
-            // of them has a missing entry.
-            XV* dst = reinterpret_cast<XV*>(X + i0 + step * (j0 + jc));
-            const unsigned long long bal = __ballot(mv != kFull);
-            const unsigned s16 = (unsigned)(((reinterpret_cast<uintptr_t>(dst) >> 4) - (unsigned)lane) & 7u);
-            const unsigned g = ((unsigned)lane + s16) >> 3;
-            const unsigned grp = g < 8 ? (unsigned)((bal << s16) >> (8 * g)) & 0xffu : (unsigned)(bal >> (64 - s16)) & 0xffu;
-            if (grp) __builtin_nontemporal_store(xn, dst);
-          }
+          bool changes;
+          const XV xn = pol.eval(q, j0 + jc, m, changes, s_ores, s_ox2, s_num, s_den);
+          if (a.update) em_line_store(changes, xn, pol.at(j0 + jc));
           if constexpr (FUSE) em_row_axpy<T, VEC, RMAX, XV>(tacc, &Bsh[jc][0], xn);
         }
         // 2 * RMAX vectors are live across the loop: keep the scheduler from interleaving the columns of one
@@ -260,9 +393,9 @@ __global__ __launch_bounds__(kEmThreads, FUSE ? 2 : 1) void em_cp_vec_k(EmCpArgs
     }
   }
   if constexpr (FUSE) {
-    if (in_range) {
+    if (g.in_range) {
       // rows i0 .. i0+VEC-1 of T at fixed index f: VEC*R contiguous values per thread, consecutive threads adjacent
-      T* Tt = reinterpret_cast<T*>(a.T) + (int64_t)chunk * a.t_chunk_stride + (i0 + a.Ipad * f) * R;
+      T* Tt = reinterpret_cast<T*>(a.T) + (int64_t)g.chunk * a.t_chunk_stride + (g.i0 + a.Ipad * g.f) * R;
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         if (R == RMAX && (RMAX * sizeof(T)) % 16 == 0) {
@@ -283,257 +416,36 @@ __global__ __launch_bounds__(kEmThreads, FUSE ? 2 : 1) void em_cp_vec_k(EmCpArgs
       }
     }
   }
-  num = em_block_sum(num, sh4); den = em_block_sum(den, sh4);
-  ores = em_block_sum(ores, sh4); ox2 = em_block_sum(ox2, sh4);
-  if (t == 0) {
-    double* w = ws + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4;
-    w[0] = num; w[1] = den; w[2] = ores; w[3] = ox2;
-  }
+  em_store_stats(num, den, ores, ox2, sh4, ws + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4);
 }
 
-// One row per thread, for R > 32 (the rows of A no longer fit in registers VEC at a time).
-template <typename T, int RMAX>
+// One row per thread, for R > 32 (the rows of A no longer fit in registers VEC at a time): the policies at VEC = 1, no
+// ring, each entry's terms (the squares, rounded once) straight into the fp64 sums, stores by entry.
+template <typename T, int RMAX, template <typename, int> class POL>
 __global__ __launch_bounds__(kEmThreads) void em_cp_k(EmCpArgs a, int jchunks, int64_t jlen, double* ws) {
+  typedef typename EmVec<T, 1>::type XV;
   __shared__ T Bsh[kEmJTile][RMAX];
   __shared__ double sh4[4];
-  const int R = a.R;
-  const int t = threadIdx.x;
-  const int64_t k = blockIdx.y;
-  const int chunk = blockIdx.x % jchunks;
-  const int64_t i0 = (int64_t)(blockIdx.x / jchunks) * kEmThreads + t;
-  const int64_t jbeg = chunk * jlen, jend = jbeg + jlen < a.J ? jbeg + jlen : a.J;
-  T areg[RMAX];
-  {
-    const int64_t i = i0 < a.I ? i0 : a.I - 1;                          // clamped: padding rows are skipped below
-#pragma unroll
-    for (int r = 0; r < RMAX; ++r) {
-      const int rr = r < R ? r : 0;
-      const double c = a.C ? a.C[k + a.ldC * rr] : 1.0;
-      areg[r] = r < R ? (T)(a.A[i + a.ldA * rr] * c) : (T)0;
-    }
-  }
-  T* X = reinterpret_cast<T*>(a.X) + a.Ipad * a.J * k;
-  const uint8_t* M = a.mask;                                             // bits (see em_mask_pack_k)
-  const int64_t mb = a.Ipad * a.J * k;
-  double num = 0, den = 0, ores = 0, ox2 = 0;
-  for (int64_t j0 = jbeg; j0 < jend; j0 += kEmJTile) {
-    __syncthreads();
-    for (int e = t; e < kEmJTile * RMAX; e += kEmThreads) {
-      const int jj = e / RMAX, r = e - jj * RMAX;
-      Bsh[jj][r] = (r < R && j0 + jj < jend) ? (T)a.B[j0 + jj + a.ldB * r] : (T)0;
-    }
-    __syncthreads();
-    const int nj = (int)((jend - j0 < kEmJTile) ? (jend - j0) : kEmJTile);
-    if (i0 >= a.I) continue;
-    for (int jj = 0; jj < nj; ++jj) {
-      const int64_t o = i0 + a.Ipad * (j0 + jj);
-      const T x = X[o];
-      T m = (T)0;
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r) m += areg[r] * Bsh[jj][r];
-      const T d = x - m;
-      if ((M[(mb + o) >> 3] >> ((mb + o) & 7)) & 1) {
-        ores += (double)(d * d); ox2 += (double)(x * x);
-      } else {
-        num += (double)(d * d); den += (double)(x * x);
-        if (a.update) X[o] = m;
-      }
-    }
-  }
-  num = em_block_sum(num, sh4); den = em_block_sum(den, sh4);
-  ores = em_block_sum(ores, sh4); ox2 = em_block_sum(ox2, sh4);
-  if (t == 0) {
-    double* w = ws + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4;
-    w[0] = num; w[1] = den; w[2] = ores; w[3] = ox2;
-  }
-}
-
-// ---- weighted blocks (em.h EmCpArgs::X0 / Wt) -----------------------------------------------------------------------------
-// One vector of entries of the weighted pass: the new value and the four terms' accumulators.  Products and differences
-// are rounded one by one -- contracted, q = fma(-w, x0, xh) would be the rounding residue of em_w_reset's product instead
-// of 0 in a solve's first pass, and f_rel_missing divides by the sum of q^2 -- and the multiply-adds written as such are
-// fused.  With w in {0, 1}, xh = x0 where w = 1 and zeros in x0 where w = 0 every term is the masked kernel's, bit for bit:
-// w = 1 gives q = 0, p = 0 and wd = d; w = 0 gives q = xh, wd = 0 and xn = p = m.
-template <typename T, typename XV>
-__device__ __forceinline__ XV em_w_entry(XV x0, XV w, XV xh, XV m, XV& s_ores, XV& s_ox2, XV& s_num, XV& s_den) {
-#pragma clang fp contract(off)
-  const XV wx = w * x0;
-  const XV q = xh - wx;                                                    // (1 - w) m_old
-  const XV p = ((T)1 - w) * m;
-  const XV d = x0 - m;
-  const XV wd = w * d;
-  const XV n = p - q;
-  s_ores = __builtin_elementwise_fma(wd, d, s_ores);
-  s_ox2 = __builtin_elementwise_fma(wx, x0, s_ox2);
-  s_num = __builtin_elementwise_fma(n, n, s_num);
-  s_den = __builtin_elementwise_fma(q, q, s_den);
-  return __builtin_elementwise_fma(w, x0, p);
-}
-
-// The strip kernel (em_cp_vec_k without FUSE) for a weighted block: three streams in (X0, W, Xhat) through the same
-// look-ahead ring, Xhat out.  A 128-byte line of Xhat is written when some weight in it is not 1; under unit weights
-// xh = x0 and stays.  Padding rows: zero row of A, w forced to 1 (X0 and Xhat hold zeros there).
-template <typename T, int VEC, int RMAX>
-__global__ __launch_bounds__(kEmThreads, 1) void em_cp_w_vec_k(EmCpArgs a, int jchunks, int64_t jlen, double* ws) {
-  typedef typename EmVec<T, VEC>::type XV;
-  __shared__ __attribute__((aligned(16))) T Bsh[kEmJTile][RMAX];
-  __shared__ double sh4[4];
-  const int R = a.R;
-  const int t = threadIdx.x;
-  const bool wj = a.walk != 2;
-  const int64_t f = blockIdx.y;
-  const int64_t NW = wj ? a.J : a.K;
-  const double* Ff = wj ? a.C : a.B;
-  const int64_t ldf = wj ? a.ldC : a.ldB;
-  const double* Fw = wj ? a.B : a.C;
-  const int64_t ldw = wj ? a.ldB : a.ldC;
-  const int64_t step = wj ? a.Ipad : a.Ipad * a.J;
-  const int chunk = blockIdx.x % jchunks;
-  const int64_t i0 = ((int64_t)(blockIdx.x / jchunks) * kEmThreads + t) * VEC;
-  const int64_t jbeg = chunk * jlen, jend = jbeg + jlen < NW ? jbeg + jlen : NW;
+  const EmWalk<1> g(a, jchunks, jlen);
   XV areg[RMAX];
-  bool pad[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) pad[v] = i0 + v >= a.I;
-#pragma unroll
-  for (int r = 0; r < RMAX; ++r) {
-    const int rr = r < R ? r : 0;
-    const double c = Ff ? Ff[f + ldf * rr] : 1.0;
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      const int64_t i = pad[v] ? a.I - 1 : i0 + v;
-      areg[r][v] = (r < R && !pad[v]) ? (T)(a.A[i + a.ldA * rr] * c) : (T)0;
-    }
-  }
-  const int64_t base = (wj ? a.Ipad * a.J : a.Ipad) * f;
-  T* X = reinterpret_cast<T*>(a.X) + base;
-  const T* X0 = reinterpret_cast<const T*>(a.X0) + base;
-  const T* W = reinterpret_cast<const T*>(a.Wt) + base;
-  const int lane = t & 63;
-  const bool in_range = i0 < a.Ipad;                                     // Ipad is a multiple of VEC
+  em_load_rows<T, 1, RMAX, false>(a, g, areg);
+  const POL<T, 1> pol(a, g);
   const XV zero = {};
   double num = 0, den = 0, ores = 0, ox2 = 0;
-  for (int64_t j0 = jbeg; j0 < jend; j0 += kEmJTile) {
-    __syncthreads();
-    for (int e = t; e < kEmJTile * RMAX; e += kEmThreads) {
-      const int jj = e / RMAX, r = e - jj * RMAX;
-      Bsh[jj][r] = (r < R && j0 + jj < jend) ? (T)Fw[j0 + jj + ldw * r] : (T)0;
-    }
-    __syncthreads();
-    const int nj = (int)((jend - j0 < kEmJTile) ? (jend - j0) : kEmJTile);
-    if (!in_range) continue;
-    constexpr int PD = 4;                              // columns in flight
-    XV xq[PD], wq[PD], hq[PD];
-#pragma unroll
-    for (int p = 0; p < PD; ++p) {
-      const int64_t op = i0 + step * (j0 + (p < nj ? p : nj - 1));
-      xq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(X0 + op));
-      wq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(W + op));
-      hq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(X + op));
-    }
-    XV s_ores = zero, s_ox2 = zero, s_num = zero, s_den = zero;
-    for (int jj = 0; jj < nj; jj += PD) {
-#pragma unroll
-      for (int p = 0; p < PD; ++p) {
-        const int jc = jj + p;                                           // wave-uniform
-        const XV x0 = xq[p], xh = hq[p];
-        XV w = wq[p];
-        {
-          const int jn = jc + PD < nj ? jc + PD : nj - 1;                // clamped: the last loads are discarded
-          const int64_t on = i0 + step * (j0 + jn);
-          xq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(X0 + on));
-          wq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(W + on));
-          hq[p] = __builtin_nontemporal_load(reinterpret_cast<const XV*>(X + on));
-        }
-        if (jc < nj) {
-          bool changes = false;                                          // some weight of this vector is not 1
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) {
-            w[v] = pad[v] ? (T)1 : w[v];
-            changes |= w[v] != (T)1;
-          }
-          const XV m = em_row_dot<T, VEC, RMAX, XV>(areg, &Bsh[jc][0], zero);
-          XV xn = em_w_entry<T, XV>(x0, w, xh, m, s_ores, s_ox2, s_num, s_den);
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) xn[v] = w[v] == (T)1 ? x0[v] : xn[v];   // the data itself, also beside a model value that is not finite
-          if (a.update) {
-            // by 128-byte line, as in em_cp_vec_k
-            XV* dst = reinterpret_cast<XV*>(X + i0 + step * (j0 + jc));
-            const unsigned long long bal = __ballot(changes);
-            const unsigned s16 = (unsigned)(((reinterpret_cast<uintptr_t>(dst) >> 4) - (unsigned)lane) & 7u);
-            const unsigned g = ((unsigned)lane + s16) >> 3;
-            const unsigned grp = g < 8 ? (unsigned)((bal << s16) >> (8 * g)) & 0xffu : (unsigned)(bal >> (64 - s16)) & 0xffu;
-            if (grp) __builtin_nontemporal_store(xn, dst);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      ores += (double)s_ores[v]; ox2 += (double)s_ox2[v]; num += (double)s_num[v]; den += (double)s_den[v];
-    }
-  }
-  num = em_block_sum(num, sh4); den = em_block_sum(den, sh4);
-  ores = em_block_sum(ores, sh4); ox2 = em_block_sum(ox2, sh4);
-  if (t == 0) {
-    double* w = ws + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4;
-    w[0] = num; w[1] = den; w[2] = ores; w[3] = ox2;
-  }
-}
-
-// One row per thread, for R > 32 (em_cp_k for a weighted block)
-template <typename T, int RMAX>
-__global__ __launch_bounds__(kEmThreads) void em_cp_w_k(EmCpArgs a, int jchunks, int64_t jlen, double* ws) {
-  __shared__ T Bsh[kEmJTile][RMAX];
-  __shared__ double sh4[4];
-  const int R = a.R;
-  const int t = threadIdx.x;
-  const int64_t k = blockIdx.y;
-  const int chunk = blockIdx.x % jchunks;
-  const int64_t i0 = (int64_t)(blockIdx.x / jchunks) * kEmThreads + t;
-  const int64_t jbeg = chunk * jlen, jend = jbeg + jlen < a.J ? jbeg + jlen : a.J;
-  T areg[RMAX];
-  {
-    const int64_t i = i0 < a.I ? i0 : a.I - 1;                          // clamped: padding rows are skipped below
-#pragma unroll
-    for (int r = 0; r < RMAX; ++r) {
-      const int rr = r < R ? r : 0;
-      const double c = a.C ? a.C[k + a.ldC * rr] : 1.0;
-      areg[r] = r < R ? (T)(a.A[i + a.ldA * rr] * c) : (T)0;
-    }
-  }
-  const int64_t base = a.Ipad * a.J * k;
-  T* X = reinterpret_cast<T*>(a.X) + base;
-  const T* X0 = reinterpret_cast<const T*>(a.X0) + base;
-  const T* W = reinterpret_cast<const T*>(a.Wt) + base;
-  double num = 0, den = 0, ores = 0, ox2 = 0;
-  for (int64_t j0 = jbeg; j0 < jend; j0 += kEmJTile) {
-    __syncthreads();
-    for (int e = t; e < kEmJTile * RMAX; e += kEmThreads) {
-      const int jj = e / RMAX, r = e - jj * RMAX;
-      Bsh[jj][r] = (r < R && j0 + jj < jend) ? (T)a.B[j0 + jj + a.ldB * r] : (T)0;
-    }
-    __syncthreads();
-    const int nj = (int)((jend - j0 < kEmJTile) ? (jend - j0) : kEmJTile);
-    if (i0 >= a.I) continue;
+  for (int64_t j0 = g.jbeg; j0 < g.jend; j0 += kEmJTile) {
+    em_stage_tile<T, 1, RMAX>(Bsh, g, a.R, j0);
+    const int nj = (int)((g.jend - j0 < kEmJTile) ? (g.jend - j0) : kEmJTile);
+    if (g.i0 >= a.I) continue;                                           // padding rows are skipped
     for (int jj = 0; jj < nj; ++jj) {
-      const int64_t o = i0 + a.Ipad * (j0 + jj);
-      const T x0 = X0[o], w = W[o], xh = X[o];
-      T m = (T)0;
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r) m += areg[r] * Bsh[jj][r];
-      T t_ores = (T)0, t_ox2 = (T)0, t_num = (T)0, t_den = (T)0;        // this entry's terms: the squares, rounded once
-      const T xn = em_w_entry<T, T>(x0, w, xh, m, t_ores, t_ox2, t_num, t_den);
-      ores += (double)t_ores; ox2 += (double)t_ox2; num += (double)t_num; den += (double)t_den;
-      if (a.update && w != (T)1) X[o] = xn;
+      const XV m = em_row_dot<T, 1, RMAX, XV>(areg, &Bsh[jj][0], zero);
+      XV t_ores = zero, t_ox2 = zero, t_num = zero, t_den = zero;
+      bool changes;
+      const XV xn = pol.eval(pol.load(j0 + jj), j0 + jj, m, changes, t_ores, t_ox2, t_num, t_den);
+      ores += (double)t_ores[0]; ox2 += (double)t_ox2[0]; num += (double)t_num[0]; den += (double)t_den[0];
+      if (a.update && changes) *pol.at(j0 + jj) = xn;
     }
   }
-  num = em_block_sum(num, sh4); den = em_block_sum(den, sh4);
-  ores = em_block_sum(ores, sh4); ox2 = em_block_sum(ox2, sh4);
-  if (t == 0) {
-    double* w = ws + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4;
-    w[0] = num; w[1] = den; w[2] = ores; w[3] = ox2;
-  }
+  em_store_stats(num, den, ores, ox2, sh4, ws + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4);
 }
 
 template <typename T>
@@ -616,35 +528,28 @@ size_t em_cp_ws_bytes(int64_t Ipad, int64_t J, int64_t K) {
   return (size_t)(cdiv(Ipad, (int64_t)kEmThreads) * (J > K ? J : K) + kEmTargetBlocks) * 4 * sizeof(double);
 }
 
-template <typename T, int VEC, bool FUSE>
-static void em_cp_launch(const EmCpArgs& a, int jchunks, int64_t jlen, double* ws, dim3 grid, hipStream_t s) {
-  switch ((a.R + 3) / 4) {                           // rank rounded up to a multiple of 4 (one ds_read_b128 of fp32)
-    case 1: em_cp_vec_k<T, VEC, 4, FUSE><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    case 2: em_cp_vec_k<T, VEC, 8, FUSE><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    case 3: em_cp_vec_k<T, VEC, 12, FUSE><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    case 4: em_cp_vec_k<T, VEC, 16, FUSE><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    case 5: em_cp_vec_k<T, VEC, 20, FUSE><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    case 6: em_cp_vec_k<T, VEC, 24, FUSE><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    default:
-      if constexpr (!FUSE) {
-        if ((a.R + 3) / 4 == 7) em_cp_vec_k<T, VEC, 28, false><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws);
-        else em_cp_vec_k<T, VEC, 32, false><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws);
-      }
-      break;
-  }
-}
-
-template <typename T, int VEC>
-static void em_cp_w_launch(const EmCpArgs& a, int jchunks, int64_t jlen, double* ws, dim3 grid, hipStream_t s) {
-  switch ((a.R + 3) / 4) {                           // the classes of em_cp_launch
-    case 1: em_cp_w_vec_k<T, VEC, 4><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    case 2: em_cp_w_vec_k<T, VEC, 8><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    case 3: em_cp_w_vec_k<T, VEC, 12><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    case 4: em_cp_w_vec_k<T, VEC, 16><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    case 5: em_cp_w_vec_k<T, VEC, 20><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    case 6: em_cp_w_vec_k<T, VEC, 24><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    case 7: em_cp_w_vec_k<T, VEC, 28><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
-    default: em_cp_w_vec_k<T, VEC, 32><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws); break;
+// The kernel of one precision and policy for the launch `l`: the strip kernel of its rank class, fused where the policy
+// and the class have a fused form (em_cp_pass has refused a fused pass that has none), or the one-row kernel
+template <typename T, template <typename, int> class POL>
+static void em_cp_launch(const EmCpArgs& a, const EmCpLaunch& l, bool fuse, double* ws, dim3 grid, hipStream_t s) {
+  constexpr int VEC = 16 / sizeof(T);
+  const auto strip = [&](auto rmax) {
+    constexpr int RMAX = decltype(rmax)::value;
+    if constexpr (POL<T, VEC>::kFuses && RMAX <= kEmFuseMaxRank) {
+      if (fuse) return em_cp_vec_k<T, VEC, RMAX, true, POL><<<grid, kEmThreads, 0, s>>>(a, l.jchunks, l.jlen, ws);
+    }
+    em_cp_vec_k<T, VEC, RMAX, false, POL><<<grid, kEmThreads, 0, s>>>(a, l.jchunks, l.jlen, ws);
+  };
+  switch (l.rmax) {                                  // rank rounded up to a multiple of 4 (one ds_read_b128 of fp32)
+    case 4: strip(std::integral_constant<int, 4>()); break;
+    case 8: strip(std::integral_constant<int, 8>()); break;
+    case 12: strip(std::integral_constant<int, 12>()); break;
+    case 16: strip(std::integral_constant<int, 16>()); break;
+    case 20: strip(std::integral_constant<int, 20>()); break;
+    case 24: strip(std::integral_constant<int, 24>()); break;
+    case 28: strip(std::integral_constant<int, 28>()); break;
+    case 32: strip(std::integral_constant<int, 32>()); break;
+    default: em_cp_k<T, 64, POL><<<grid, kEmThreads, 0, s>>>(a, l.jchunks, l.jlen, ws); break;
   }
 }
 
@@ -658,26 +563,14 @@ void em_cp_pass(const EmCpArgs& a, int prec, double* ws, double* out4, hipStream
   AO_REQUIRE(!fuse || em_cp_can_fuse(a, prec), "em_cp_pass: this block cannot take the fused contraction");
   AO_REQUIRE(wj || a.C != nullptr, "em_cp_pass: a matrix block has no third mode to walk");
   const EmCpLaunch l = em_cp_launch_of(a, prec, fuse);
-  const int64_t strips = l.strips, jlen = l.jlen;
-  const int jchunks = l.jchunks;
-  const dim3 grid((unsigned)(strips * jchunks), (unsigned)(wj ? a.K : a.J));
+  const dim3 grid((unsigned)(l.strips * l.jchunks), (unsigned)(wj ? a.K : a.J));
   AO_REQUIRE((size_t)grid.x * grid.y * 4 * sizeof(double) <= em_cp_ws_bytes(a.Ipad, a.J, a.K), "em_cp_pass: workspace");
-  if (weighted) {
-    if (prec == AOADMM_PREC_F32) {
-      if (em_wide(a)) em_cp_w_launch<float, 4>(a, jchunks, jlen, ws, grid, s);
-      else em_cp_w_k<float, 64><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws);
-    } else {
-      if (em_wide(a)) em_cp_w_launch<double, 2>(a, jchunks, jlen, ws, grid, s);
-      else em_cp_w_k<double, 64><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws);
-    }
-  } else if (prec == AOADMM_PREC_F32) {
-    if (fuse) em_cp_launch<float, 4, true>(a, jchunks, jlen, ws, grid, s);
-    else if (em_wide(a)) em_cp_launch<float, 4, false>(a, jchunks, jlen, ws, grid, s);
-    else em_cp_k<float, 64><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws);
+  if (prec == AOADMM_PREC_F32) {
+    if (weighted) em_cp_launch<float, EmWeighted>(a, l, fuse, ws, grid, s);
+    else em_cp_launch<float, EmMasked>(a, l, fuse, ws, grid, s);
   } else {
-    if (fuse) em_cp_launch<double, 2, true>(a, jchunks, jlen, ws, grid, s);
-    else if (em_wide(a)) em_cp_launch<double, 2, false>(a, jchunks, jlen, ws, grid, s);
-    else em_cp_k<double, 64><<<grid, kEmThreads, 0, s>>>(a, jchunks, jlen, ws);
+    if (weighted) em_cp_launch<double, EmWeighted>(a, l, fuse, ws, grid, s);
+    else em_cp_launch<double, EmMasked>(a, l, fuse, ws, grid, s);
   }
   AO_KERNEL_CHECK();
   em_sum4_k<<<1, 256, 0, s>>>(ws, (int64_t)grid.x * grid.y, out4);
@@ -708,12 +601,7 @@ __global__ __launch_bounds__(256) void em_par2_k(EmPar2Args a, double* ws) {
       if (a.update) X[e] = m;
     }
   }
-  num = em_block_sum(num, sh4); den = em_block_sum(den, sh4);
-  ores = em_block_sum(ores, sh4); ox2 = em_block_sum(ox2, sh4);
-  if (threadIdx.x == 0) {
-    double* w = ws + (int64_t)k * 4;
-    w[0] = num; w[1] = den; w[2] = ores; w[3] = ox2;
-  }
+  em_store_stats(num, den, ores, ox2, sh4, ws + (int64_t)k * 4);
 }
 
 void em_par2_pass(const EmPar2Args& a, double* ws, double* out4, hipStream_t s) {

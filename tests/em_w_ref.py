@@ -1,4 +1,4 @@
-"""Reference and error bounds for ONE weighted dense EM pass (csrc/em.hip em_cp_w_vec_k / em_cp_w_k, DESIGN.md section
+"""Reference and error bounds for ONE weighted dense EM pass (csrc/em.hip em_cp_vec_k / em_cp_k under EmWeighted, DESIGN.md section
 4.5.1).  Shared by tests/test_em_w_host.py (which checks the bounds against an emulation of the kernel's fp32 arithmetic on
 the CPU) and tests/test_gpu_em_w_pass.py (which compares the device pass with them).  The manner is that of tests/em_ref.py.
 

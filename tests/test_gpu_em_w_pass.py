@@ -1,4 +1,4 @@
-"""GPU: ONE weighted dense EM pass (csrc/em.hip em_cp_w_vec_k / em_cp_w_k) as a solve runs it -- `Engine.resident_em_pass`
+"""GPU: ONE weighted dense EM pass (csrc/em.hip em_cp_vec_k / em_cp_k under EmWeighted) as a solve runs it -- `Engine.resident_em_pass`
 on a block with `Engine.tensor_weights_upload` -- against the longdouble reference and the derived bounds of
 tests/em_w_ref.py, in both precisions: every rank class of the strip kernel, the kernel for R > 32, rows, walk lengths,
 several tiles per piece, matrix and 4-way blocks, the statistics-only pass, a second pass with other factors (q != 0), the
@@ -103,7 +103,7 @@ RANK_SHAPES = [(37, 70, 9), (131, 67, 70)]
 @pytest.mark.parametrize('R', [1, 4, 5, 20, 21, 32, 33, 64])
 @pytest.mark.parametrize('dims', RANK_SHAPES, ids=str)
 def test_rank_classes(pkg, eng, dims, R, prec):
-    """Both ends of rank classes of the strip kernel and em_cp_w_k; fuse = 1 is ignored."""
+    """Both ends of rank classes of the strip kernel and the one-row kernel em_cp_k; fuse = 1 is ignored."""
     out = _run(pkg, eng, dims, R, prec, fuse=1)
     want = (1, 64) if R > 32 else (2 if prec == 'f64' else 4, (R + 3) // 4 * 4)
     assert (out['info']['vec'], out['info']['rmax']) == want

@@ -30,8 +30,8 @@ for frac in ('0.2', '0.01'):
     p = float(frac)
     lines = 1.0 - (1.0 - p) ** 32                      # share of 128-B lines (32 fp32 entries) with a missing entry
     algo = 4e9 + 0.125e9 + 4e9 * lines + 0.08e9
-    fe, nf = collect('fetch_' + frac, 'em_cp_vec_k<float, 4, 20, true>')
-    wr, nw = collect('write_' + frac, 'em_cp_vec_k<float, 4, 20, true>')
+    fe, nf = collect('fetch_' + frac, 'em_cp_vec_k<float, 4, 20, true, aoadmm::EmMasked>')
+    wr, nw = collect('write_' + frac, 'em_cp_vec_k<float, 4, 20, true, aoadmm::EmMasked>')
     raw = fe.get('FETCH_SIZE', 0.0); w = wr.get('WRITE_SIZE', 0.0)
     unit = 1024.0 if 0 < raw < 1e9 else 1.0
     res['missing_' + frac] = {'FETCH_SIZE_bytes_raw': raw * unit, 'FETCH_SIZE_bytes_corrected_x2': 2 * raw * unit, 'WRITE_SIZE_bytes': w * unit,
