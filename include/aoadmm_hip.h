@@ -536,6 +536,33 @@ int aoadmm_resident_rank_of_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, cons
                               const int64_t* excl_off, const int64_t* excl_idx, int64_t* rank, double* score,
                               int64_t* ncand_or_null);
 
+/* ---- Tucker projection and core consistency ------- */
+/* core (r[0] x r[1] x r[2], column-major) = X x_1 M[0]' x_2 M[1]' x_3 M[2]' of the resident 3-way block p;
+ * M[n] is dims[n] x r[n] column-major with leading dimension ld[n], host memory.  X is the block as it stands on the
+ * device, whatever is resident of it: the natural array, the pass copies alone after the natural array was released,
+ * the half copies of an AOADMM_PREC_F16 block (q / scale), the imputed array Xhat of a block with a mask or per-entry
+ * weights (after a solve or an EM pass; a mask whose missing entries were never imputed is AOADMM_ERR_INVALID), or the
+ * nonzeros of a plain sparse block (unstored entries are zero).  Dense: one tensor pass with M[c] in place of factor c
+ * (c the mode with the largest dims[c] / r[c] the block can contract) and one fold over its result that reads it once;
+ * sparse: with a the mode of the largest r[a], max(r[b], r[c]) MTTKRPs of mode a over the nonzeros and a fold of each
+ * (workspace: I_a x max(r[b], r[c]) doubles and the fold's partial sums).  No float atomics and fixed summation orders: two calls return the same bits.  Nothing of the solver's state
+ * moves: a solve after the call returns the bits of the solve without it.  Kernel statistics: the pass under which = 0 /
+ * 1, the fold under which = 2, the sparse MTTKRPs under which = 3.
+ * AOADMM_ERR_INVALID, with core untouched, for: p outside the model, a block without data, r[n] outside 1..64, NULL M,
+ * M[n], ld, r or core, ld[n] smaller than dims[n].  AOADMM_ERR_UNSUPPORTED, with core and the block untouched, for: a
+ * block that is not 3-way, a PARAFAC2 block, a sparse block fitted on its stored entries only or under entry weights (its
+ * Xhat has no array), a sharded block (dense or sparse), any engine of a communicator with more than one rank, and a
+ * multi-device context (aoadmm_create_multi with more than one device). */
+int aoadmm_resident_project(aoadmm_ctx* ctx, int p, const double* const* M, const int64_t* ld, const int* r, double* core);
+/* Core consistency of block p's CP model with the current AOADMM_F_FAC state: M[n] = F_n (F_n'F_n)^+ , core as above
+ * (R x R x R, may be NULL), *cc = 100 (1 - sum (core - superdiagonal ones)^2 / R) (CORCONDIA, Bro & Kiers 2003: near 100
+ * the data are trilinear at this R, far below -- it has no lower bound -- R is too large).  The factors are downloaded and
+ * the pseudo-inverses formed on the host from the eigendecomposition of the R x R Gram matrices; eigenvalues below
+ * R 2^-52 lambda_max count as zero and set *rank_deficient (may be NULL) to 1, else it is 0.  Refusals and block states
+ * are those of aoadmm_resident_project; also AOADMM_ERR_INVALID for NULL cc or a missing factor.  Every output is
+ * written last: an error leaves all three untouched. */
+int aoadmm_resident_core_consistency(aoadmm_ctx* ctx, int p, double* cc, double* core_or_null, int* rank_deficient_or_null);
+
 /* ---- ranking metrics tracked inside a solve ------- */
 /* the metric aoadmm_rank_track follows; also the order of the float sums in aoadmm_rank_trace */
 enum {

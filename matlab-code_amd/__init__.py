@@ -14,6 +14,7 @@ from ._capi import (AoadmmError, NotPositiveDefinite, UnsupportedOnDevice, LIB_P
 from .engine import CONSTRAINT_IDS, Engine, constraint_descriptor, default_engine
 from .dist import init_engine_comm, row_block
 from .sptensor import pack_par2_slabs, sptensor
+from .corecons import core_consistency
 from .ranking import parse_rank_metric, pooled_score, rank_rule, ranking_metrics
 from .driver import (build_model, cmtf_AOADMM, cmtf_nvecs, constraints_to_prox, download_state, heldout_keep_best_option,
                      heldout_lists, init_coupled_AOADMM_CMTF, rank_options, run_solver, upload_state)
@@ -22,4 +23,4 @@ __all__ = ['AoadmmError', 'NotPositiveDefinite', 'UnsupportedOnDevice', 'LIB_PAT
            'CONSTRAINT_IDS', 'Engine', 'constraint_descriptor', 'default_engine', 'build_model', 'cmtf_AOADMM',
            'cmtf_nvecs', 'constraints_to_prox', 'download_state', 'init_coupled_AOADMM_CMTF', 'run_solver', 'upload_state', 'init_engine_comm', 'row_block', 'sptensor',
            'pack_par2_slabs', 'heldout_lists', 'heldout_keep_best_option', 'ranking_metrics', 'rank_options',
-           'parse_rank_metric', 'pooled_score', 'rank_rule']
+           'parse_rank_metric', 'pooled_score', 'rank_rule', 'core_consistency']

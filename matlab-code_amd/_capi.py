@@ -74,7 +74,7 @@ SYMBOLS = [
     'aoadmm_tensor_set_observed_only', 'aoadmm_tensor_set_entry_weights', 'aoadmm_resident_em_step', 'aoadmm_resident_em_pass',
     'aoadmm_resident_model_at', 'aoadmm_tensor_set_heldout', 'aoadmm_resident_heldout_stats', 'aoadmm_heldout_info', 'aoadmm_heldout_trace',
     'aoadmm_heldout_keep_best', 'aoadmm_heldout_restore_best', 'aoadmm_heldout_best_info', 'aoadmm_resident_topk',
-    'aoadmm_resident_topk_w', 'aoadmm_resident_rank_of', 'aoadmm_resident_rank_of_w', 'aoadmm_resident_fold_in', 'aoadmm_resident_fold_in_w',
+    'aoadmm_resident_topk_w', 'aoadmm_resident_rank_of', 'aoadmm_resident_rank_of_w', 'aoadmm_resident_project', 'aoadmm_resident_core_consistency', 'aoadmm_resident_fold_in', 'aoadmm_resident_fold_in_w',
     'aoadmm_tensor_set_ranklist', 'aoadmm_ranklist_info', 'aoadmm_rank_track', 'aoadmm_rank_trace', 'aoadmm_ranklist_last',
     'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_resident_par2_rhs', 'aoadmm_kernel_stats',
     'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_resident_nvecs', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
@@ -207,6 +207,8 @@ def load_library():
                                             C.POINTER(i64)]
     lib.aoadmm_resident_rank_of_w.argtypes = [vp, C.c_int, C.c_int, i64, dp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
                                               dp, C.POINTER(i64)]
+    lib.aoadmm_resident_project.argtypes = [vp, C.c_int, C.POINTER(dp), C.POINTER(i64), C.POINTER(C.c_int), dp]
+    lib.aoadmm_resident_core_consistency.argtypes = [vp, C.c_int, dp, dp, C.POINTER(C.c_int)]
     lib.aoadmm_tensor_set_ranklist.argtypes = [vp, C.c_int, C.c_int, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     lib.aoadmm_ranklist_info.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(i64)]
     lib.aoadmm_rank_track.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]

@@ -560,6 +560,20 @@ int aoadmm_resident_rank_of_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, cons
     ctx->eng->rank_of_w(p, mode, nq, W, targets, excl_off, excl_idx, rank, score, ncand_or_null);
   });
 }
+int aoadmm_resident_project(aoadmm_ctx* ctx, int p, const double* const* M, const int64_t* ld, const int* r, double* core) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_resident_project");
+    ctx->eng->project(p, M, ld, r, core);
+  });
+}
+int aoadmm_resident_core_consistency(aoadmm_ctx* ctx, int p, double* cc, double* core_or_null, int* rank_deficient_or_null) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_resident_core_consistency");
+    ctx->eng->core_consistency(p, cc, core_or_null, rank_deficient_or_null);
+  });
+}
 int aoadmm_tensor_set_ranklist(aoadmm_ctx* ctx, int p, int mode, int64_t nq, const int64_t* subs, const int64_t* excl_off,
                                const int64_t* excl_idx) {
   CTX_OR_FAIL(ctx);

@@ -303,6 +303,10 @@ class Engine {
   void fold_in_run(const char* what, bool weighted, int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals,
                    const double* wts, double alpha, const aoadmm_foldin_options* opt, double* rows_host, int* info_host,
                    int* iters_host, double* gram_host, double* rhs_host);
+  // Tucker projection of a resident 3-way CP block and the core consistency of its CP model (core.h, DESIGN.md section
+  // 9.9): core (r[0] x r[1] x r[2], column-major) = X x_1 M[0]' x_2 M[1]' x_3 M[2]', M[n] on the host
+  void project(int p, const double* const* M, const int64_t* ld, const int* r, double* core_host);
+  void core_consistency(int p, double* cc, double* core_host, int* rank_deficient);
   void resident_unfold_gram(int p, int pos, int slab, double* out_host);
   void resident_nvecs(int p, int pos, int r, const aoadmm_nvecs_options* opt, double* U_host, int64_t ldU, double* eig_host,
                       aoadmm_nvecs_info* info);
@@ -369,6 +373,9 @@ class Engine {
   void rank_prepare_excl(int p, int64_t I, int64_t nq, const int64_t* excl_off, const int64_t* excl_idx, RankExclHost& h) const;
   // uploads them (asynchronously: the caller synchronises before `h` goes) and names them in `a`
   void rank_upload_excl(const RankExclHost& h, int64_t nq, DevBuf& eoff, DevBuf& eidx, DevBuf& coff, DevBuf& cq, RankArgs& a);
+  CpBlock& project_block(const char* what, int p);   // tensor p's block, or the refusal of what cannot be projected
+  void project_dense(CpBlock& b, const double* const* M, const int64_t* ld, const int* r, double* G);    // G: device
+  void project_sparse(CpBlock& b, const double* const* M, const int64_t* ld, const int* r, double* G);
   bool has_ranklist() const;
   void ranklist_enqueue(int p, double* slots);     // block p's ranking list against the current factors -> kRankSlots sums (device)
   double rank_score(const ArenaView& h) const;     // the pooled mean of the tracked metric over the blocks with a list

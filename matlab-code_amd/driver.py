@@ -1032,6 +1032,17 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
     if keep_best:
         # Fac and Zhat are the iterate heldout_best_iter (rank_criterion = 1: rank_best_iter); every other field of out still describes the whole run
         out['heldout_restored_iter'] = eng.heldout_restore_best()
+    if int(hip.get('core_consistency', 0)):
+        # alg_options['hip']['core_consistency'] = 1: out.core_consistency{0-based block} of every block the library can
+        # project (3-way CP, not sharded, not observed-only), for the factors returned; the others are left out
+        out['core_consistency'] = {}
+        for p in range(len(Z['object'])):
+            if Z['model'][p] != 'CP' or len(Z['modes'][p]) != 3:
+                continue
+            try:
+                out['core_consistency'][p] = eng.core_consistency(p)
+            except capi.UnsupportedOnDevice:
+                pass
     Fac = download_state(eng, Z, G)
     Zhat = []
     for p in range(len(Z['object'])):                                                 # :197-206

@@ -572,6 +572,42 @@ class Engine:
             return rows, info, iters, gram, rhs
         return rows, info, iters
 
+    def project(self, p, mats):
+        """Tucker projection of the resident 3-way block p (`aoadmm_resident_project`): mats = (M0, M1, M2) with M_n of
+        shape dims[n] x r_n; returns the core X x_1 M0' x_2 M1' x_3 M2' as an ndarray of shape (r0, r1, r2).  X is the
+        block as it stands on the device: released, half, imputed (Xhat) or sparse with zeros for the unstored entries.
+        A block the library cannot project raises `UnsupportedOnDevice`; see include/aoadmm_hip.h for the list."""
+        if len(mats) != 3:
+            raise ValueError('project: mats must hold three matrices, got %d' % len(mats))
+        M = [capi.as_f(m) for m in mats]
+        if any(m.ndim != 2 for m in M):
+            raise ValueError('project: every matrix must be dims[n] x r_n')
+        r = [int(m.shape[1]) for m in M]
+        dp = C.POINTER(C.c_double)
+        ptrs = (dp * 3)(*[capi.dptr(m) for m in M])
+        ld = (C.c_int64 * 3)(*[max(1, int(m.shape[0])) for m in M])
+        rr = (C.c_int * 3)(*r)
+        core = np.zeros(tuple(max(x, 0) for x in r), order='F')
+        capi.check(self.lib.aoadmm_resident_project(self.h, int(p), ptrs, ld, rr, capi.dptr(core)))
+        return core
+
+    def core_consistency(self, p, return_core=False, return_info=False):
+        """Core consistency (CORCONDIA) of block p's CP model with the factors the engine holds
+        (`aoadmm_resident_core_consistency`): 100 (1 - sum (core - superdiagonal ones)^2 / R) with core the projection
+        of the block on M_n = F_n (F_n'F_n)^+.  Near 100: trilinear at this R; it has no lower bound.  Returns cc, then
+        the R x R x R core with return_core=True, then {'rank_deficient': bool} with return_info=True (a factor whose
+        Gram matrix has an eigenvalue below R 2^-52 of its largest)."""
+        R = self.block_rank(p)
+        cc, flag = C.c_double(0), C.c_int(0)
+        core = np.zeros((R, R, R), order='F') if return_core else None
+        capi.check(self.lib.aoadmm_resident_core_consistency(self.h, int(p), C.byref(cc), capi.dptr(core), C.byref(flag)))
+        out = (cc.value,)
+        if return_core:
+            out += (core,)
+        if return_info:
+            out += ({'rank_deficient': bool(flag.value)},)
+        return out[0] if len(out) == 1 else out
+
     def resident_mttkrp(self, p, tensor_mode, rows, R):
         """One MTTKRP of the resident block p against the current factors (`aoadmm_resident_mttkrp`): rows x R."""
         out = np.zeros((rows, R), order='F')
