@@ -65,7 +65,10 @@ constexpr int kReduceBatchSplit = 64;
 struct ReduceBatch {
   ReduceTask t[kReduceBatchMax];
   int n = 0;
-  void add(const ReduceTask& k) { if (n < kReduceBatchMax) t[n] = k; ++n; }   // overflow is caught by reduce_batch
+  // The caller flushes: it launches reduce_batch and starts an empty batch before adding to a full one (n ==
+  // kReduceBatchMax; Engine::eval_objective_enqueue does).  add() only counts past the end, and reduce_batch refuses
+  // such a batch instead of dropping its tasks.
+  void add(const ReduceTask& k) { if (n < kReduceBatchMax) t[n] = k; ++n; }
 };
 // ws >= kReduceBatchMax * kReduceBatchSplit doubles
 void reduce_batch(const ReduceBatch& rb, double* ws, hipStream_t s);

@@ -13,10 +13,21 @@ namespace aoadmm {
 // ---------------------------------------------------------------------------
 void Engine::eval_objective_enqueue(bool first) {
   ReduceBatch rb;                                  // every plain reduction of this evaluation in one launch
+  auto flush = [&]() {
+    reduce_batch(rb, redws_.d(), stream_);
+    rb = ReduceBatch();
+  };
+  // a batch holds kReduceBatchMax tasks and the model sets no cap on blocks or modes (20 coupled matrices are 40 tasks
+  // before the first mode): a full batch is launched before the next task goes in.  Only models that did not fit one
+  // batch before reach this, so the batches, and with them the summation order, of every other model stay as they were
+  auto push = [&](const ReduceTask& k) {
+    if (rb.n == kReduceBatchMax) flush();
+    rb.add(k);
+  };
   auto add = [&](int kind, double* slot, const double* x, const double* y, int64_t n) {
     ReduceTask k;
     k.kind = kind; k.slot = slot; k.x = x; k.y = y; k.n = n;
-    rb.add(k);
+    push(k);
   };
   for (int p = 0; p < n_tensors_; ++p)           // held-out lists: scored against the fac state this evaluation uses
     if (tensors_[p].ho.n > 0) heldout_enqueue(p, dev_.heldout(p));
@@ -80,12 +91,12 @@ void Engine::eval_objective_enqueue(bool first) {
                    coef(1.0), 0.0, nullptr, stream_);
         ReduceTask k;
         k.kind = RT_DOT; k.slot = sm + kObjRegValue; k.x = mi.fac.d(); k.y = mi.proxws.d(); k.n = nm; k.scale = mi.prox.p0;
-        rb.add(k);
+        push(k);
       } else if (ty == AOADMM_C_L1_REG || ty == AOADMM_C_L0_REG || ty == AOADMM_C_RIDGE || ty == AOADMM_C_GL_SMOOTH ||
                  ty == AOADMM_C_TV) {
         ReduceTask k;
         k.kind = RT_REG; k.aux = ty; k.slot = sm + kObjRegValue; k.x = mi.fac.d(); k.rows = mi.rows; k.R = mi.R; k.scale = mi.prox.p0;
-        rb.add(k);
+        push(k);
       }
     }
     if (mi.coupling >= 0) {                        // :1303-1329
@@ -97,12 +108,9 @@ void Engine::eval_objective_enqueue(bool first) {
       add(RT_SUMSQ_DIFF, sm + kObjCouplGap, tf, td, mi.img_rows * mi.img_cols);
       if (tf != mi.fac.d()) add(RT_SUMSQ_DIFF, sm + kObjImageSq, tf, nullptr, mi.img_rows * mi.img_cols);   // ||H*C|| / ||C*H||
     }
-    if (rb.n >= kReduceBatchMax - 4) {           // many modes: flush and start the next batch
-      reduce_batch(rb, redws_.d(), stream_);
-      rb = ReduceBatch();
-    }
+    if (rb.n >= kReduceBatchMax - 4) flush();    // many modes: start the next batch
   }
-  reduce_batch(rb, redws_.d(), stream_);
+  flush();
 }
 
 // ---------------------------------------------------------------------------
