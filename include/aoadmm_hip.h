@@ -389,6 +389,34 @@ int aoadmm_resident_em_step(aoadmm_ctx* ctx, int p, double stats[3]);
  * launch. */
 int aoadmm_resident_em_pass(aoadmm_ctx* ctx, int p, int update, int fuse, double stats[4], double* data, double* data_t,
                             double* mttkrp, int64_t info[8]);
+/* Marks (on != 0) the masked dense CP block p: the library builds, on the device, the list of its missing entries in
+ * ascending storage order (column-major, first mode fastest) from the resident mask, and every imputing EM pass of the
+ * block (aoadmm_solve, the re-imputation of aoadmm_heldout_restore_best) then evaluates the model at the listed entries
+ * only and scatters it into the array, instead of passing over the whole block with a fused contraction.  Opt-in: an
+ * unmarked block launches what it always did.  The statistics-only pass behind the start objective and Znorm_const stays
+ * the dense one, so a marked block's iteration-0 objective is bit for bit the unmarked one.  Later objective values of
+ * the block are formed as  (obs_x2 + den) - 2 <Xhat, M> + ||M||^2 - num  from the last MTTKRP of the iteration, as an
+ * unmasked block's are, clamped at 0: they carry that form's absolute floor of about u * ||Xhat||^2 (u the fp64 unit
+ * roundoff), where an unmarked block's directly summed residual has none.  A noise-free fit to machine precision
+ * belongs on an unmarked block.  Resident: 4 N bytes per missing entry plus 16 bytes per 256 of them
+ * (aoadmm_tensor_storage_info counts them); no cap on the missing share: AOADMM_ERR_NOMEM when the list does not fit,
+ * with the block as it was.  on = 0 releases the list and the mark; so does any later upload of the block's data, mask
+ * or weights.  AOADMM_ERR_UNSUPPORTED for a PARAFAC2, sparse or weighted block, on a context whose communicator has
+ * more than one rank and on a multi-device context; AOADMM_ERR_INVALID for a block without a mask. */
+int aoadmm_tensor_set_missing_list(aoadmm_ctx* ctx, int p, int on);
+/* The list of the marked block p: *n (may be NULL) = its entries; subs (may be NULL) = their 0-based subscripts,
+ * column-major n x N (mode m of entry e at subs[m * n + e]), in list order.  AOADMM_ERR_INVALID for an unmarked block. */
+int aoadmm_tensor_missing_list(aoadmm_ctx* ctx, int p, int64_t* n, int64_t* subs_or_null);
+/* One list pass over the marked block p with the current AOADMM_F_FAC state, exactly as aoadmm_solve enqueues it:
+ * per listed entry m = sum_r prod_n F_n(s_n, r) in fp64, stats2 = {num, den} = {sum (m - x_old)^2, sum x_old^2} over
+ * the list, and with update != 0 x <- m rounded once to the block's precision (a matrix block: in its transposed copy
+ * too).  Observed entries are never touched.  Returned when not NULL: data = the block after the pass, unpadded,
+ * column-major, as doubles; data_t = the transposed copy a matrix block keeps (J x I).  An empty list launches nothing
+ * and returns two zeros.  Two calls on the same data return the same bits.  Timed under aoadmm_kernel_stats class 16.
+ * AOADMM_ERR_INVALID for an unmarked block; AOADMM_ERR_UNSUPPORTED on a context that belongs to a communicator or
+ * drives several devices.  (aoadmm_resident_em_pass with update != 0 on a marked block is AOADMM_ERR_UNSUPPORTED; with
+ * update = 0 it is the dense statistics pass, as in a solve.) */
+int aoadmm_resident_em_list_pass(aoadmm_ctx* ctx, int p, int update, double stats2[2], double* data, double* data_t);
 /* Z.object{p}{k} of a PARAFAC2 block as sparse matrices, all K slabs in one call: nnz nonzeros, subs column-major
  * nnz x 3, 0-based (i, j within the slab, k); vals nnz doubles.  Duplicates are summed, explicit zeros are allowed,
  * nnz = 0 is valid; a subscript out of range (j >= J_k included) or nnz < 0 is AOADMM_ERR_INVALID and leaves the block
@@ -404,7 +432,7 @@ int aoadmm_tensor_normsq(aoadmm_ctx* ctx, int p, double* out);
 /* How tensor p is stored on the device (each output may be NULL): *precision = the AOADMM_PREC_* its passes stream
  * (AOADMM_PREC_F64 for sparse and PARAFAC2 data), *scale = the power-of-two scale s of an AOADMM_PREC_F16 block (1.0
  * otherwise), *resident_bytes = what a CP block holds now: natural-layout array, pass copies, transposed copy and
- * mask of a dense block; the per-mode copies of the nonzeros of a sparse block, N (4 N + 8) bytes per nonzero this
+ * mask of a dense block, and the list of a block marked with aoadmm_tensor_set_missing_list; the per-mode copies of the nonzeros of a sparse block, N (4 N + 8) bytes per nonzero this
  * rank holds (all of them, or its share of a sharded block; a multi-device context reports rank 0's), for an
  * observed-only block N (4 N + 16) per nonzero plus the factor snapshots (2 * 8 * I_n * R bytes per mode); 0 for
  * PARAFAC2 data.  No device work. */
@@ -736,7 +764,10 @@ int aoadmm_resident_par2_rhs(aoadmm_ctx* ctx, int p, int tensor_mode, double* ou
  * kernels inside one event pair; bytes = the list streamed + rows gathered + the outputs, flops = nobs * (R (R + 1) +
  * 2 R (N - 1)) + nq * (R^3 / 3 + 2 R^2) for the solves; aoadmm_resident_fold_in_w counts in the same class: with a weight
  * list 8 nobs bytes more, and with alpha > 0 the factor rows read for H, 8 R sum_{m != mode} I_m bytes, and its
- * R^2 sum_{m != mode} I_m flops) */
+ * R^2 sum_{m != mode} I_m flops); which = 16 (15 is not assigned and stays AOADMM_ERR_INVALID): the list pass of every aoadmm_resident_em_list_pass call (one launch per
+ * call, the gather kernel and its finisher inside one event pair; a solve's own list passes record no events; bytes =
+ * subscripts streamed + factor rows gathered + the value read and, with update = 1, written in the block's precision,
+ * twice for a matrix; flops = n * R * N + 8 n for the sums) */
 int aoadmm_kernel_stats(aoadmm_ctx* ctx, int which, int reset, double* contract_ms, int64_t* contract_launches,
                         double* contract_bytes, double* contract_flops);
 

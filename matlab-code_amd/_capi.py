@@ -72,6 +72,7 @@ SYMBOLS = [
     'aoadmm_model_set_coupling_type', 'aoadmm_model_set_ridge', 'aoadmm_model_end', 'aoadmm_tensor_upload',
     'aoadmm_tensor_upload_rows', 'aoadmm_tensor_upload_coo', 'aoadmm_tensor_upload_coo_sharded', 'aoadmm_par2_slab_upload', 'aoadmm_par2_slab_upload_coo', 'aoadmm_tensor_mask_upload', 'aoadmm_tensor_weights_upload', 'aoadmm_par2_slab_mask_upload', 'aoadmm_tensor_synth', 'aoadmm_tensor_normsq', 'aoadmm_tensor_storage_info', 'aoadmm_tensor_rank',
     'aoadmm_tensor_set_observed_only', 'aoadmm_tensor_set_entry_weights', 'aoadmm_resident_em_step', 'aoadmm_resident_em_pass',
+    'aoadmm_tensor_set_missing_list', 'aoadmm_tensor_missing_list', 'aoadmm_resident_em_list_pass',
     'aoadmm_resident_model_at', 'aoadmm_tensor_set_heldout', 'aoadmm_resident_heldout_stats', 'aoadmm_heldout_info', 'aoadmm_heldout_trace',
     'aoadmm_heldout_keep_best', 'aoadmm_heldout_restore_best', 'aoadmm_heldout_best_info', 'aoadmm_resident_topk',
     'aoadmm_resident_topk_w', 'aoadmm_resident_rank_of', 'aoadmm_resident_rank_of_w', 'aoadmm_resident_project', 'aoadmm_resident_core_consistency', 'aoadmm_resident_fold_in', 'aoadmm_resident_fold_in_w',
@@ -192,6 +193,9 @@ def load_library():
     lib.aoadmm_tensor_set_entry_weights.argtypes = [vp, C.c_int, i64, C.POINTER(i64), dp, C.c_double]
     lib.aoadmm_resident_em_step.argtypes = [vp, C.c_int, dp]
     lib.aoadmm_resident_em_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, C.POINTER(i64)]
+    lib.aoadmm_tensor_set_missing_list.argtypes = [vp, C.c_int, C.c_int]
+    lib.aoadmm_tensor_missing_list.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64)]
+    lib.aoadmm_resident_em_list_pass.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp]
     lib.aoadmm_resident_model_at.argtypes = [vp, C.c_int, i64, C.POINTER(i64), dp]
     lib.aoadmm_tensor_set_heldout.argtypes = [vp, C.c_int, i64, C.POINTER(i64), dp]
     lib.aoadmm_resident_heldout_stats.argtypes = [vp, C.c_int, dp]

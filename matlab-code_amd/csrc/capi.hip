@@ -475,6 +475,25 @@ int aoadmm_resident_em_pass(aoadmm_ctx* ctx, int p, int update, int fuse, double
     ctx->eng->resident_em_pass(p, update, fuse, stats, data, data_t, mttkrp, info);
   });
 }
+// The missing entries of a masked dense block as a list (Engine::set_missing_list)
+int aoadmm_tensor_set_missing_list(aoadmm_ctx* ctx, int p, int on) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    if (ctx->multi) throw Error(AOADMM_ERR_UNSUPPORTED, "aoadmm_tensor_set_missing_list is not available on a multi-device context (aoadmm_create_multi)");
+    ctx->eng->set_missing_list(p, on != 0);
+  });
+}
+int aoadmm_tensor_missing_list(aoadmm_ctx* ctx, int p, int64_t* n, int64_t* subs_or_null) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] { ctx->eng->missing_list(p, n, subs_or_null); });
+}
+int aoadmm_resident_em_list_pass(aoadmm_ctx* ctx, int p, int update, double stats2[2], double* data, double* data_t) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    if (ctx->multi) throw Error(AOADMM_ERR_UNSUPPORTED, "aoadmm_resident_em_list_pass runs on a single-device context");
+    ctx->eng->resident_em_list_pass(p, update, stats2, data, data_t);
+  });
+}
 // Held-out scoring answers on one engine (which may belong to a communicator); a multi-device context would have to
 // keep one list per engine for no gain: it is refused
 static void require_single_engine(aoadmm_ctx* ctx, const char* what) {

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "contract.h"
+#include "em_list.h"
 #include "sparse.h"
 #include "sparse_em.h"
 
@@ -22,7 +23,10 @@ constexpr int kStatsEmPass = 4;
 constexpr int kStatsHeldout = kStatsEmPass + kCooMaxModes;   // the held-out pass (heldout.h)
 constexpr int kStatsTopk = kStatsHeldout + 1;                 // the top-k completions (topk.h) and the ranks of targets (rank_of.h)
 constexpr int kStatsFoldin = kStatsTopk + 1;                  // the fold-in of new rows (foldin.h)
-constexpr int kStatsClasses = kStatsFoldin + 1;
+// (kStatsFoldin + 1 stays unassigned: aoadmm_kernel_stats has always refused it, and callers that probe one past the
+// fold-in class rely on that)
+constexpr int kStatsEmList = kStatsFoldin + 2;                // the list pass of aoadmm_resident_em_list_pass (em_list.h)
+constexpr int kStatsClasses = kStatsEmList + 1;
 
 struct KernelStats {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -37,7 +41,8 @@ struct LaunchTimers {
   std::vector<hipEvent_t> pool;   // timing events are recycled: creating two per tensor pass cost host time in the loop
   // [0] streaming contraction, [1] leading-mode contraction, [2] reductions over T, [3] sparse MTTKRP, the passes over
   // sparse PARAFAC2 slabs and the EM steps of observed-only blocks, [kStatsEmPass + n] the pass of those steps over
-  // mode n's copy, [kStatsHeldout] the held-out passes, [kStatsTopk] the top-k completions, [kStatsFoldin] the fold-in of new rows
+  // mode n's copy, [kStatsHeldout] the held-out passes, [kStatsTopk] the top-k completions, [kStatsFoldin] the fold-in of new rows,
+  // [kStatsEmList] the op-level list passes of marked masked blocks
   KernelStats stats[kStatsClasses];
   bool profile = true;
   bool profile_reductions = false;   // switched on by the first kernel_stats(2, ...) call: two more events per reduction
@@ -110,6 +115,9 @@ struct CpBlock {
   DevBuf mask, maskT;
   bool has_mask = false;
   bool mask_imputed = false;   // an EM pass has written model values over the missing entries of X since the data arrived
+  // aoadmm_tensor_set_missing_list: the imputing EM pass walks the list of the missing entries
+  // instead of the array.  Belongs to the data and its mask: every upload of either, and of weights, drops it.
+  MissingList mlist;
   // Per-entry weights in [0, 1] (aoadmm_tensor_weights_upload): X.data is then Xhat =
   // W o X0 + (1 - W) o M, X0 the data as uploaded and Wt the weights, both in the layout and precision of X (an fp32
   // block keeps fp32 weights); X0t / WtT are their transposed copies beside Xt (matrices).  Never together with a mask.
@@ -126,9 +134,11 @@ struct CpBlock {
   // observed-only form of a sparse block (aoadmm_tensor_set_observed_only): the unstored entries are missing, not zero
   SparseEm sem;
   // New data has arrived, dense or sparse: no copy, cached contraction or release state of the old data holds.  Frees
-  // nothing (a pass copy's buffer is reused by the next build; the sparse upload releases what it no longer needs).
+  // nothing but the list of the old mask's missing entries (a pass copy's buffer is reused by the next build; the sparse
+  // upload releases what it no longer needs).
   void reset_derived() {
     has_data = true; x_released = false; cached_mode = -1; xp_ksharded = false; half = false; scale = 1.0; mask_imputed = false;
+    mlist.clear();
     for (PassCopy& c : copy) c.present = c.refused = false;
   }
 };

@@ -225,6 +225,7 @@ bool block_set_weights(const BlockCtx& cx, CpBlock& b, const double* host) {
   b.Wt = std::move(W); b.WtT = std::move(WT);
   b.has_weights = true;
   b.has_mask = false; b.mask.release(); b.maskT.release();   // w = 0 is the spelling of "missing"
+  b.mlist.clear();                                     // the list was the mask's
   drop_pass_copies(b);                                 // the imputation would have to update them too
   block_reset_weighted(cx, b);
   AO_HIP(hipStreamSynchronize(s));

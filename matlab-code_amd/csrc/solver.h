@@ -157,6 +157,7 @@ struct TensorInfo {
   RankList rl;                  // ranking list (aoadmm_tensor_set_ranklist): belongs to the model, as the held-out list does
   std::vector<double> rl_trace; // kRankSlots sums per evaluation of the last solve (the iterations: Engine::rank_iters_)
   bool eval_shortcut = false;   // PARAFAC2: the enqueued objective evaluation took the last_mttkrp shortcut (:1254-1260)
+  bool eval_list = false;       // marked masked CP block: the enqueued evaluation took the list form
   bool masked() const { return par2 ? p2.has_mask : blk.imputed(); }  // Z.miss{p} or per-entry weights given: the dense EM pass runs
   bool observed_only() const { return !par2 && blk.sparse && blk.sem.on; }   // sparse block whose unstored entries are missing
   bool missing() const { return masked() || observed_only(); }        // the block takes part in the EM step
@@ -199,6 +200,9 @@ struct EmPassInfo {
 
 struct LocalGroup;
 struct SolveRun;                      // what one solve carries from step to step (solver_solve.hip)
+
+// natural-layout array on the device (first dimension padded to X.pad0) -> unpadded doubles on the host (solver.hip)
+void download_unpadded(const DenseTensor& X, int64_t rows, int64_t cols, double* out, hipStream_t s);
 
 // coupling images (solver_coupled.hip): Sd(D), Tf(F) and Tf'(Y) for mode `mi` of coupling `ci`; each returns its input
 // where the map is the identity and `dst` otherwise
@@ -260,6 +264,14 @@ class Engine {
   // sequence finished from the cached T; info[8] = {vec, rmax, fused, walk, strips, jchunks, jlen, that position or -1}
   void resident_em_pass(int p, int update, int fuse, double stats[4], double* data, double* data_t, double* mttkrp,
                         int64_t info[8]);
+  // The missing entries of a masked dense CP block as a list (em_list.h).  on: builds the list
+  // from the resident mask and marks the block, so that its imputing EM passes walk the list; off: releases both.
+  void set_missing_list(int p, bool on);
+  // n (may be null): entries of the list; subs (may be null): their subscripts, column-major n x N, in list order
+  void missing_list(int p, int64_t* n, int64_t* subs);
+  // One list pass over the marked block p as a solve runs it (aoadmm_resident_em_list_pass): stats2 = {num, den};
+  // data / data_t as for resident_em_pass
+  void resident_em_list_pass(int p, int update, double stats2[2], double* data, double* data_t);
   // held-out scoring (heldout.h)
   void model_at(int p, int64_t n, const int64_t* subs, double* out_host);     // the model of block p at n subscripts
   void set_heldout(int p, int64_t n, const int64_t* subs, const double* vals);   // n = 0 removes the list
@@ -365,6 +377,8 @@ class Engine {
   // statistics of tensor p into its EM slots (+ imputation); fuse: EmFuse, honoured where the block allows it
   void em_pass_enqueue(int p, int update, int fuse = kEmFuseNone, EmPassInfo* info = nullptr);
   void sparse_em_enqueue(int p, bool stats_only);  // EM step of an observed-only sparse block into its EM slots
+  // list pass of the marked block p: num and den into its EM slots (+ imputation); timed: events of class kStatsEmList
+  void em_list_enqueue(int p, int update, bool timed);
   bool has_heldout() const;
   HeldoutFactors heldout_factors(const TensorInfo& t, bool* row_major) const;   // the current fac state of block t as the pass gathers it
   // skip_mode >= 0: that column of subs is neither read nor checked (its part of idx32 stays zero)

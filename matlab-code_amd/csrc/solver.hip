@@ -374,6 +374,7 @@ void Engine::tensor_storage_info(int p, int* precision, double* scale, int64_t* 
       for (const DevBuf* d : {&b.X.data, &b.Xt.data, &b.copy[0].buf, &b.copy[1].buf, &b.copy[2].buf, &b.mask, &b.maskT,
                               &b.X0, &b.Wt, &b.X0t, &b.WtT})
         if (d->p) n += (int64_t)d->bytes;
+      n += b.mlist.resident_bytes();       // a marked block: 4 N bytes per missing entry and the teams' partial sums
     } else if (!t.par2) {            // the per-mode copies of the nonzeros this rank holds: N (4 N + 8) bytes each
       for (int m = 0; m < b.coo.nd; ++m)
         for (const DevBuf* d : {&b.coo.mode[m].row, &b.coo.mode[m].oidx, &b.coo.mode[m].val})
@@ -632,6 +633,7 @@ void Engine::tensor_mask_upload(int p, const uint8_t* mask) {
   block_drop_weights(block_ctx(), b);                // the later of mask and weights wins: Xhat <- X0 (nothing can refuse any more)
   b.has_mask = true;
   b.mask_imputed = false;
+  b.mlist.clear();                                   // the list of the old mask's missing entries, and the mark with it
   drop_pass_copies(b);                               // the imputation would have to update them too
   t.normsq_valid = false;
 }
@@ -784,7 +786,7 @@ void Engine::resident_em_step(int p, double stats[3]) {
 }
 
 // natural-layout array on the device (first dimension padded to `pad0`) -> unpadded doubles on the host
-static void download_unpadded(const DenseTensor& X, int64_t rows, int64_t cols, double* out, hipStream_t s) {
+void download_unpadded(const DenseTensor& X, int64_t rows, int64_t cols, double* out, hipStream_t s) {
   const size_t es = X.elem_size();
   std::vector<char> h((size_t)X.pad0 * cols * es);
   AO_HIP(hipMemcpyAsync(h.data(), X.data.p, h.size(), hipMemcpyDeviceToHost, s));
@@ -814,6 +816,8 @@ void Engine::resident_em_pass(int p, int update, int fuse, double stats[4], doub
     AO_REQUIRE(!t.blk.half, "tensor %d is stored as fp16: it has no EM pass", p);
   }
   AO_REQUIRE(t.masked(), "tensor %d is neither masked nor weighted (aoadmm_tensor_mask_upload / aoadmm_par2_slab_mask_upload / aoadmm_tensor_weights_upload)", p);
+  if (!t.par2 && t.blk.mlist.on && update)
+    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("tensor %d is marked with aoadmm_tensor_set_missing_list: its imputing pass is aoadmm_resident_em_list_pass", p));
   for (int i = 0; i < t.nmodes; ++i) AO_REQUIRE(modes_[t.modes[i]].has_fac, "G.fac{%d} missing", t.modes[i] + 1);
   AO_HIP(hipSetDevice(device_));
   EmPassInfo pi;
@@ -878,6 +882,10 @@ void Engine::em_pass_enqueue(int p, int update, int fuse, EmPassInfo* info) {
     return;
   }
   CpBlock& b = t.blk;
+  if (update && b.mlist.on) {                         // a marked block imputes from its list; update = 0 stays the dense pass
+    em_list_enqueue(p, 1, false);
+    return;
+  }
   const ModeInfo& m0 = modes_[t.modes[0]];
   const ModeInfo& m1 = modes_[t.modes[1]];
   EmCpArgs a;
@@ -1088,6 +1096,8 @@ void Engine::state_get(int field, int index, int slab, double* host, int64_t row
 // MTTKRP engine
 // ---------------------------------------------------------------------------
 void Engine::kernel_stats(int which, int reset, double* ms, int64_t* launches, double* bytes, double* flops) {
+  static_assert(kStatsEmList == 16, "include/aoadmm_hip.h documents the list pass as class 16");
+  AO_REQUIRE(which != kStatsFoldin + 1, "kernel_stats: class %d is not assigned", which);
   AO_REQUIRE(which >= 0 && which < kStatsClasses, "kernel_stats: which must be 0 .. %d", kStatsClasses - 1);
   if (which == 2) timers_.profile_reductions = true;
   AO_HIP(hipSetDevice(device_));

@@ -54,7 +54,10 @@ void Engine::eval_objective_enqueue(bool first) {
       }
       continue;
     }
-    if (masked) continue;
+    // A marked block's imputing pass walked its list and left no observed-entry residual: later evaluations take the
+    // two dot products an unmasked block gets and objective_from_host combines them with the list's sums
+    t.eval_list = masked && !first && t.blk.mlist.on;
+    if (masked && !t.eval_list) continue;
     if (first) {
       // cp_func.m:47-55 / pca_func.m:29-39: same formula with the first mode's MTTKRP
       ModeInfo& m0 = modes_[t.modes[0]];
@@ -168,6 +171,12 @@ void Engine::objective_from_host(const ArenaView& h, double f[4]) const {
         if (g != 0.0) ++ncon;
         if (has_ridge_) ft += mB.ridge * nb2;                                                 // :1292-1295 (quirk: only if constrained)
       }
+    } else if (masked && t.eval_list) {
+      // ||miss.*(X - M)||^2 = ||Xhat - M||^2 - num with Xhat the array the iteration's last MTTKRP ran on (its missing
+      // entries still held the previous imputation, whose squares are den) and normsq = ||miss.*X||^2
+      const double f2 = sp[kObjMttkrpDot] / t.weight;
+      const double res = (t.normsq + h.em(p)[kEmDen]) - 2.0 * f2 + sp[kObjHadDot] - h.em(p)[kEmNum];
+      ft += t.weight * (res > 0.0 ? res : 0.0);
     } else if (masked) {
       ft += t.weight * h.em(p)[kEmObsRes];                                   // :1224-1226 = w * ||miss.*(X - M)||^2
     } else {

@@ -370,6 +370,47 @@ def observed_only_blocks(Z, observed_only, sparse_sharding=False):
     return blocks
 
 
+def missing_list_blocks(Z, missing_list, dense_weighted=(), world=1):
+    """The 0-based blocks that `alg_options['hip']['missing_list']` marks (`Engine.set_missing_list`): 0 / None / False ->
+    none, 1 / True -> every dense CP block with Z.miss that carries no entry weights, a list -> those 1-based blocks, each
+    of which must be such a block.  Checked on the host before anything is uploaded.  Raises `UnsupportedOnDevice` for a
+    PAR2 block, a sparse block, a block named in `entry_weights` as well (`dense_weighted`: the blocks `dense_weight_blocks`
+    returned) and for any marked block on an engine whose communicator has `world` > 1 ranks; ValueError for a block
+    without Z.miss."""
+    P = len(Z['object'])
+    miss = Z.get('miss') if Z.get('miss') is not None else [None] * P
+
+    def dense_masked_cp(p):
+        obj = Z['object'][p]
+        return Z['model'][p] == 'CP' and not isinstance(obj, dict) and coo_of(obj) is None and miss[p] is not None
+
+    if missing_list is None or isinstance(missing_list, (bool, int, np.integer)):
+        if missing_list is None or int(missing_list) == 0:
+            return []
+        if int(missing_list) != 1:
+            raise ValueError('missing_list must be 0, 1 or a list of 1-based block numbers')
+        blocks = [p for p in range(P) if dense_masked_cp(p) and p not in dense_weighted]
+    else:
+        blocks = []
+        for q in missing_list:
+            p = int(q) - 1
+            if int(q) != q or p < 0 or p >= P:
+                raise ValueError('missing_list names Z.object{%s}: the model has %d blocks' % (q, P))
+            if Z['model'][p] != 'CP':
+                raise _unsupported('missing_list: Z.object{%d} is a PARAFAC2 block' % (p + 1))
+            if not isinstance(Z['object'][p], dict) and coo_of(Z['object'][p]) is not None:
+                raise _unsupported('missing_list: Z.object{%d} is sparse (use sparse_observed_only)' % (p + 1))
+            if p in dense_weighted:
+                raise _unsupported('missing_list: Z.object{%d} carries entry_weights (a weighted block has no mask)' % (p + 1))
+            if not dense_masked_cp(p):
+                raise ValueError('missing_list: Z.object{%d} has no Z.miss{%d}' % (p + 1, p + 1))
+            if p not in blocks:
+                blocks.append(p)
+    if blocks and world > 1:
+        raise _unsupported('missing_list is not available under a communicator of %d ranks' % world)
+    return blocks
+
+
 def entry_weight_blocks(Z, entry_weights, unstored_weight, observed=(), sparse_sharding=False):
     """`alg_options['hip']['sparse_entry_weights']` / `['sparse_unstored_weight']` -> {0-based block: (wts or None,
     alpha)}, checked on the host before the engine is touched.  Each option is None or a list over the blocks:
@@ -620,7 +661,7 @@ def heldout_keep_best_option(value, lists):
 
 
 def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0, entry_weights=None, unstored_weight=None,
-                dense_entry_weights=None):
+                dense_entry_weights=None, missing_list=0):
     """Describe the struct Z to the engine and upload Z.object (cmtf_AOADMM.m:23-41,124-156).
 
     Z.object{p} of a CP block may be dense, an `sptensor`, or (2-way blocks) any object with `.tocoo()` such as a
@@ -646,10 +687,14 @@ def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0,
     block is marked observed-only as well.
     dense_entry_weights (`dense_weight_blocks`): weighted least squares on the named DENSE CP blocks
     (`Engine.tensor_weights_upload`): a list over the blocks, or the dict `dense_weight_blocks` made of it; a block with Z.miss as well
-    gets W o miss as weights and no mask.  Under 'f16' such a block goes up as fp32, like a masked one."""
+    gets W o miss as weights and no mask.  Under 'f16' such a block goes up as fp32, like a masked one.
+    missing_list (`missing_list_blocks`: 0, 1 or a list of 1-based block numbers): the named dense CP blocks with Z.miss
+    are marked after their mask is uploaded (`Engine.set_missing_list`): their imputing EM passes walk the list of the
+    missing entries instead of the whole array."""
     prec = capi.precision_id(precision)                # an unknown string fails before the engine is touched
     # a dict is what dense_weight_blocks returned to the caller already: not checked and copied a second time
     dense_w = dense_entry_weights if isinstance(dense_entry_weights, dict) else dense_weight_blocks(Z, dense_entry_weights)
+    listed = missing_list_blocks(Z, missing_list, dense_w, eng.comm_rank()[1] if missing_list else 1)
     observed = observed_only_blocks(Z, observed_only, sparse_sharding)
     weighted = entry_weight_blocks(Z, entry_weights, unstored_weight, observed, sparse_sharding)
     observed = sorted(set(observed) | set(weighted))
@@ -763,6 +808,8 @@ def build_model(eng, Z, precision='f64', sparse_sharding=False, observed_only=0,
                     raise ValueError('Z.miss{%d} size does not match Z.object{%d}.' % (p + 1, p + 1))
                 mk = np.asfortranarray(mk != 0, dtype=np.uint8)
                 capi.check(lib.aoadmm_tensor_mask_upload(eng.h, p, mk.ctypes.data_as(C.POINTER(C.c_uint8))))
+                if p in listed:
+                    eng.set_missing_list(p, True)
         elif _par2_sparse(Z['object'][p], p):
             # sparse slabs: the nonzeros of all slabs as (i, j, k) in one transfer; fp64 whatever `precision` says
             md = [m - 1 for m in Z['modes'][p]]
@@ -993,6 +1040,10 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
     # alg_options['hip']['entry_weights'] (`dense_weight_blocks`): an array of weights in [0, 1] per named DENSE CP block
     dense_w_opt = hip.get('entry_weights')
     dense_weighted = dense_weight_blocks(Z, dense_w_opt)
+    # alg_options['hip']['missing_list'] (default 0; 1: every dense CP block with Z.miss; a list: 1-based block numbers):
+    # the imputing EM passes of those blocks walk the list of their missing entries (`missing_list_blocks`)
+    listed_opt = hip.get('missing_list', 0)
+    missing_list_blocks(Z, listed_opt, dense_weighted, eng.comm_rank()[1] if listed_opt else 1)
     # alg_options['hip']['heldout'] = {1-based block: (subs, vals) | sptensor} and ['heldout_patience'] (`heldout_lists`):
     # entries kept out of the fit, scored on the device with every evaluation of the objective
     held = heldout_lists(Z, hip.get('heldout'), hip.get('heldout_patience', 0))
@@ -1003,7 +1054,7 @@ def cmtf_AOADMM(Z, alg_options=None, init='random', init_options=None, rng=None,
     # rank_criterion = 1 the one with the best ranking score
     keep_best = heldout_keep_best_option(hip.get('heldout_keep_best', 0), rank['lists'] if rank['criterion'] == 1 else held)
     build_model(eng, Z, precision, sparse_sharding=sharding, observed_only=observed_opt, entry_weights=weights_opt,
-                unstored_weight=alpha_opt, dense_entry_weights=dense_weighted)
+                unstored_weight=alpha_opt, dense_entry_weights=dense_weighted, missing_list=listed_opt)
     for p, (hs, hv) in sorted(held.items()):
         eng.set_heldout(p, hs, hv)
     for p, (rmode, rsubs, rexcl) in sorted(rank['lists'].items()):

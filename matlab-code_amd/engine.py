@@ -231,6 +231,48 @@ class Engine:
                     info=dict(vec=int(info[0]), rmax=int(info[1]), fused=int(info[2]), walk=int(info[3]),
                               strips=int(info[4]), jchunks=int(info[5]), jlen=int(info[6])))
 
+    # ---- the missing entries of a masked dense block as a list -------------------------
+    def set_missing_list(self, p, on=True):
+        """Marks the masked dense CP block p (`aoadmm_tensor_set_missing_list`): the list of its missing entries is built
+        on the device from the resident mask, and every imputing EM pass of the block then evaluates the model at the
+        listed entries only instead of passing over the whole array.  Opt-in; on=False releases the list, as does any
+        later upload of the block's data, mask or weights.  The iteration-0 objective stays the dense pass's, bit for
+        bit.  Later objective values of a marked block are formed from the iteration's last MTTKRP like an unmasked
+        block's, (obs_x2 + den) - 2 <Xhat, M> + ||M||^2 - num clamped at 0, and so have that form's absolute floor of
+        about u * ||Xhat||^2 (u = 2^-53), where an unmarked block's directly summed residual has none: leave a
+        noise-free fit to machine precision unmarked.  Raises `AoadmmError` with ERR_UNSUPPORTED for a PARAFAC2, sparse
+        or weighted block, under a communicator of more than one rank and on a multi-device context, ERR_INVALID for a
+        block without a mask, ERR_NOMEM (block unchanged) when the list does not fit."""
+        capi.check(self.lib.aoadmm_tensor_set_missing_list(self.h, int(p), int(bool(on))))
+
+    def missing_list(self, p, nmodes=None):
+        """The list of the marked block p (`aoadmm_tensor_missing_list`): without `nmodes` the number of entries; with
+        the block's order N an int64 array n x N of their 0-based subscripts in list order (ascending column-major
+        storage offset)."""
+        n = C.c_int64(0)
+        capi.check(self.lib.aoadmm_tensor_missing_list(self.h, int(p), C.byref(n), None))
+        if nmodes is None:
+            return int(n.value)
+        subs = np.zeros((int(n.value), int(nmodes)), dtype=np.int64, order='F')
+        if n.value > 0:
+            capi.check(self.lib.aoadmm_tensor_missing_list(self.h, int(p), None, subs.ctypes.data_as(C.POINTER(C.c_int64))))
+        return subs
+
+    def resident_em_list_pass(self, p, dims, update=1, with_data=True):
+        """One list pass over the marked block p with the current factors, as a solve runs it
+        (`aoadmm_resident_em_list_pass`).  Returns a dict: stats = (num, den) as a float64 array; data = the block after
+        the pass as doubles, data_t = a matrix block's transposed copy (J x I), both None without with_data.  Timed
+        under `kernel_stats(16)`."""
+        stats = np.zeros(2)
+        data = data_t = None
+        if with_data:
+            data = np.zeros(tuple(int(d) for d in dims), order='F')
+            if len(dims) == 2:
+                data_t = np.zeros((int(dims[1]), int(dims[0])), order='F')
+        capi.check(self.lib.aoadmm_resident_em_list_pass(self.h, int(p), int(update), capi.dptr(stats), capi.dptr(data),
+                                                         capi.dptr(data_t)))
+        return dict(stats=stats, data=data, data_t=data_t)
+
     # ---- held-out scoring ------------------------------------------------------------
     @staticmethod
     def _subs_f(subs, what):
@@ -630,7 +672,8 @@ class Engine:
         blocks with sparse slabs and EM steps of observed-only blocks; which = 4 + n: the pass of those EM steps over
         the copy of tensor mode n, and for which = 4 the pass of every `resident_em_pass` call over a dense CP block; which = 12: the held-out passes; which = 13: the top-k completions and the ranks of targets (one launch per `topk` or `rank_of` call and per
         evaluation of a ranking list inside a solve);
-        which = 14: the fold-in of new rows (one launch per `fold_in` call, weighted or not)."""
+        which = 14: the fold-in of new rows (one launch per `fold_in` call, weighted or not); which = 16: the list pass
+        of every `resident_em_list_pass` call."""
         ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         capi.check(self.lib.aoadmm_kernel_stats(self.h, int(which), int(bool(reset)), C.byref(ms), C.byref(n),
                                                 C.byref(by), C.byref(fl)))
