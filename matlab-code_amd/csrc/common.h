@@ -85,6 +85,7 @@ struct DevBuf {
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }   // the segments of a carved workspace
 // workgroups of t threads for n work items, at least one
 inline unsigned blocks_for(int64_t n, int t = 256) { return (unsigned)(n > t ? cdiv(n, t) : 1); }
 

@@ -1,19 +1,18 @@
 // The place of a known target row among a query's candidates: the targets' scores, the counting pass, the exclusion
 // pass and the finisher.  See rank_of.h and DESIGN.md section 9.7.
 //
-// Every score, the target's included, is one element of the chain of ceil(R / 4) v_mfma_f64_16x16x4_f64 that
-// topk_scores_k runs (topk.hip: the operand map, zeros beyond R, the chain from +0), so equal scores compare equal and a
-// rank is the position top-k gives the row.  The load ring and the chain of rank_count_k are a copy of topk_scores_k's:
-// that kernel is left as it is (DESIGN.md section 9.7 says why).  Every workgroup is one wave; no kernel here uses LDS,
-// a ballot or an atomic.
+// Every score, the target's included, comes from topk_dev.h: the operand map, the clamped gather and the chain that
+// topk_scores_k runs, and for rank_count_k the same stream over the slab, so equal scores compare equal and a rank is
+// the position top-k gives the row.  This unit is what is done with a score.  Every workgroup is one wave; no kernel
+// here uses LDS, a ballot or an atomic.
 #include <algorithm>
 
 #include "rank_of.h"
+#include "topk_dev.h"
 
 namespace aoadmm {
 
-typedef double rank_f64x4 __attribute__((ext_vector_type(4)));
-constexpr int kRankWave = 64;
+constexpr int kRankWave = kTopkWave;
 
 struct RankKArgs {
   CooFactor F;            // the free mode's factor
@@ -37,38 +36,26 @@ struct RankKArgs {
 template <int KS>
 __global__ __launch_bounds__(kRankWave) void rank_target_k(RankKArgs a) {
   const int lane = (int)threadIdx.x, c = lane & 15, q4 = lane >> 4;
-  const int R = a.R;
   const int64_t q = (int64_t)blockIdx.x * kTopkTile + c;
   const bool live = q < a.nq;
-  const int t = live ? a.target[q] : 0;
-  const double* fp = a.F.p + (int64_t)t * a.F.sI;
-  double x[KS], w[KS];
-#pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    const int kk = 4 * s + q4;
-    const double f = fp[(int64_t)(kk < R ? kk : R - 1) * a.F.sR];
-    x[s] = kk < R ? f : 0.0;
-    w[s] = live && kk < R ? a.W[q * R + kk] : 0.0;
-  }
-  rank_f64x4 acc = rank_f64x4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x[s], w[s], acc, 0, 0, 0);
+  double x[KS], w[1][KS];
+  topk_load_row(x, a.F, live ? a.target[q] : 0, a.R, q4);
+  topk_load_w(w[0], a.W, q, live, a.R, q4);
+  topk_f64x4 acc[1];
+  topk_chain(acc, x, w, topk_last_ok<KS>(a.R, q4));
   // this lane holds D[q4 + 4 e][c]: the diagonal is e = c >> 2 in the lanes with q4 == (c & 3)
-  double d = acc[0];
+  double d = acc[0][0];
 #pragma unroll
-  for (int e = 1; e < 4; ++e) d = (c >> 2) == e ? acc[e] : d;
+  for (int e = 1; e < 4; ++e) d = (c >> 2) == e ? acc[0][e] : d;
   if (live && q4 == (c & 3)) a.tscore[q] = d;
 }
 
-// KS = ceil(R / 4) MFMA steps, compiled in; QT: query tiles per workgroup.  The stream over the slab is topk_scores_k's.
+// KS = ceil(R / 4) MFMA steps, compiled in; QT: query tiles per workgroup
 template <int KS, int QT>
 __global__ __launch_bounds__(kRankWave) void rank_count_k(RankKArgs a) {
   const int lane = (int)threadIdx.x, c = lane & 15, q4 = lane >> 4;
-  const int R = a.R;
   const int64_t slab = blockIdx.y;
-  const int rb = (int)(slab * a.slab_rows);                       // I < 2^31: rows are ints from here on
-  const int re = (int)(slab * a.slab_rows + a.slab_rows < a.I ? slab * a.slab_rows + a.slab_rows : a.I);
-  const bool last_ok = 4 * (KS - 1) + q4 < R;                     // only the last step can hold columns beyond R
+  const TopkSlab sl = topk_slab(slab, a.slab_rows, a.I);
 
   double w[QT][KS];
   double sv[QT];                                                  // the target's score and row: the four lanes of a
@@ -78,68 +65,25 @@ __global__ __launch_bounds__(kRankWave) void rank_count_k(RankKArgs a) {
   for (int qt = 0; qt < QT; ++qt) {
     const int64_t q = ((int64_t)blockIdx.x * QT + qt) * kTopkTile + c;
     const bool live = q < a.nq;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int kk = 4 * s + q4;
-      w[qt][s] = live && kk < R ? a.W[q * R + kk] : 0.0;
-    }
+    topk_load_w(w[qt], a.W, q, live, a.R, q4);
     sv[qt] = live ? a.tscore[q] : 0.0;
     tr[qt] = live ? a.target[q] : 0;
     before[qt] = notnan[qt] = 0;
   }
 
-  // Unconditional loads on clamped addresses (a row of this slab, a column below R): no branch around a load, so the
-  // loads of D steps stay in flight.  What a clamp brought in is dropped where it is used.
-  auto load_rows = [&](double (&av)[KS], int r0) {
-    const int ar = r0 + c < re ? r0 + c : re - 1;
-    const double* fp = a.F.p + (int64_t)ar * a.F.sI;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int kk = 4 * s + q4;
-      av[s] = fp[(int64_t)(kk < R ? kk : R - 1) * a.F.sR];
-    }
-  };
-
-  auto step = [&](const double (&av)[KS], int r0) {
-    rank_f64x4 acc[QT];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) acc[qt] = rank_f64x4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const double x = s + 1 < KS || last_ok ? av[s] : 0.0;
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) acc[qt] = __builtin_amdgcn_mfma_f64_16x16x4f64(x, w[qt][s], acc[qt], 0, 0, 0);
-    }
+  auto step = [&](const topk_f64x4 (&acc)[QT], int r0) {
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int row = r0 + q4 + 4 * e;
         const double v = acc[qt][e];
-        const bool in = row < re;                                  // a row the clamp brought in counts nowhere
+        const bool in = row < sl.re;                               // a row the clamp brought in counts nowhere
         before[qt] += in && (v > sv[qt] || (v == sv[qt] && row < tr[qt])) ? 1 : 0;   // the target itself: neither
         notnan[qt] += in && v == v ? 1 : 0;
       }
   };
-
-  // A ring of D steps' rows with fixed roles (no register moves: a move would wait for the load it copies)
-  constexpr int D = KS <= 8 ? 4 : 2;
-  double av[D][KS];
-#pragma unroll
-  for (int d = 0; d < D; ++d) load_rows(av[d], rb + d * kTopkRows);
-  for (int row0 = rb; row0 < re; row0 += D * kTopkRows) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      const int r0 = row0 + d * kTopkRows;
-      if (r0 < re) {                                               // uniform
-        double cur[KS];
-#pragma unroll
-        for (int s = 0; s < KS; ++s) cur[s] = av[d][s];
-        load_rows(av[d], r0 + D * kTopkRows);
-        step(cur, r0);
-      }
-    }
-  }
+  topk_stream(a.F, a.R, sl, w, step);
 
   // the slab's pair per query: the four lanes of a column hold the four row classes q4 + 4 e
 #pragma unroll
@@ -157,35 +101,26 @@ __global__ __launch_bounds__(kRankWave) void rank_count_k(RankKArgs a) {
 template <int KS>
 __global__ __launch_bounds__(kRankWave) void rank_excl_k(RankKArgs a) {
   const int lane = (int)threadIdx.x, c = lane & 15, q4 = lane >> 4;
-  const int R = a.R;
   const int64_t ch = blockIdx.x;
   const int64_t q = a.chunk_q[ch];
   const int64_t lb = a.excl_off[q] + (ch - a.chunk_off[q]) * kRankExclChunk;
   const int64_t le = lb + kRankExclChunk < a.excl_off[q + 1] ? lb + kRankExclChunk : a.excl_off[q + 1];   // lb < le
   const double sv = a.tscore[q];
   const int tr = a.target[q];
-  double w[KS];
-#pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    const int kk = 4 * s + q4;
-    w[s] = kk < R ? a.W[q * R + kk] : 0.0;
-  }
+  double w[1][KS];
+  topk_load_w(w[0], a.W, q, true, a.R, q4);
   int before = 0, notnan = 0;
   for (int64_t l0 = lb; l0 < le; l0 += kTopkRows) {
     const int row = a.excl_idx[l0 + c < le ? l0 + c : le - 1];    // clamped: dropped where it is used
-    const double* fp = a.F.p + (int64_t)row * a.F.sI;
-    rank_f64x4 acc = rank_f64x4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int kk = 4 * s + q4;
-      const double f = fp[(int64_t)(kk < R ? kk : R - 1) * a.F.sR];
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(kk < R ? f : 0.0, w[s], acc, 0, 0, 0);
-    }
+    double x[KS];
+    topk_load_row(x, a.F, row, a.R, q4);
+    topk_f64x4 acc[1];
+    topk_chain(acc, x, w, topk_last_ok<KS>(a.R, q4));
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int j = q4 + 4 * e;                                    // D's row: the listed row lane j gathered
       const int rj = __shfl(row, j);
-      const double v = acc[e];
+      const double v = acc[0][e];
       const bool in = c == 0 && l0 + j < le && rj != tr;           // the target is a candidate, listed or not
       before += in && (v > sv || (v == sv && rj < tr)) ? 1 : 0;
       notnan += in && v == v ? 1 : 0;
@@ -226,30 +161,25 @@ __global__ __launch_bounds__(kRankWave) void rank_finish_k(RankKArgs a) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// the workspace: where every segment starts, and its size
+struct RankWs { size_t W, tscore, cnt, ex, bytes; };
+static RankWs rank_ws(int R, int64_t nq, int64_t nq_pad, int64_t slabs, int64_t chunks) {
+  RankWs o;
+  o.W = 0;
+  o.tscore = o.W + align256((size_t)nq * R * sizeof(double));
+  o.cnt = o.tscore + align256((size_t)nq * sizeof(double));
+  o.ex = o.cnt + align256((size_t)nq_pad * slabs * sizeof(int2));
+  o.bytes = o.ex + align256((size_t)chunks * sizeof(int2));
+  return o;
+}
 
 RankPlan rank_plan(int64_t I, int R, int64_t nq, int64_t chunks) {
   RankPlan pl;
   pl.tp = topk_plan(I, R, nq, 1);      // two tiles per workgroup beyond 16 queries, slabs until the device is full
   pl.nq_pad = pl.tp.qtiles * pl.tp.qt * kTopkTile;
   pl.chunks = chunks;
-  pl.workspace_bytes = align256((size_t)nq * R * sizeof(double)) + align256((size_t)nq * sizeof(double)) +
-                       align256((size_t)pl.nq_pad * pl.tp.slabs * sizeof(int2)) + align256((size_t)chunks * sizeof(int2));
+  pl.workspace_bytes = rank_ws(R, nq, pl.nq_pad, pl.tp.slabs, chunks).bytes;
   return pl;
-}
-
-template <int KS>
-static void launch_rank(const RankKArgs& ka, const RankPlan& pl, hipStream_t s) {
-  rank_target_k<KS><<<(unsigned)cdiv(ka.nq, (int64_t)kTopkTile), kRankWave, 0, s>>>(ka);
-  AO_KERNEL_CHECK();
-  const dim3 grid((unsigned)pl.tp.qtiles, (unsigned)pl.tp.slabs);
-  if (pl.tp.qt == 2) rank_count_k<KS, 2><<<grid, kRankWave, 0, s>>>(ka);
-  else rank_count_k<KS, 1><<<grid, kRankWave, 0, s>>>(ka);
-  AO_KERNEL_CHECK();
-  if (pl.chunks > 0) {
-    rank_excl_k<KS><<<(unsigned)pl.chunks, kRankWave, 0, s>>>(ka);
-    AO_KERNEL_CHECK();
-  }
 }
 
 void rank_enqueue(const RankArgs& a, const RankPlan& pl, hipStream_t s) {
@@ -262,13 +192,8 @@ void rank_enqueue(const RankArgs& a, const RankPlan& pl, hipStream_t s) {
                  (pl.chunks == 0 || (a.excl_off != nullptr && a.excl_idx != nullptr && a.chunk_off != nullptr && a.chunk_q != nullptr)),
              "internal: rank plan");
   char* ws = static_cast<char*>(a.workspace);
-  double* W = reinterpret_cast<double*>(ws);
-  ws += align256((size_t)a.nq * R * sizeof(double));
-  double* tscore = reinterpret_cast<double*>(ws);
-  ws += align256((size_t)a.nq * sizeof(double));
-  int2* cnt = reinterpret_cast<int2*>(ws);
-  ws += align256((size_t)pl.nq_pad * pl.tp.slabs * sizeof(int2));
-  int2* ex = reinterpret_cast<int2*>(ws);
+  const RankWs o = rank_ws(R, a.nq, pl.nq_pad, pl.tp.slabs, pl.chunks);
+  double* W = reinterpret_cast<double*>(ws + o.W);
 
   if (a.W == nullptr) topk_weights_enqueue(a.hf, a.mode, a.nq, a.idx, W, s);
 
@@ -279,26 +204,23 @@ void rank_enqueue(const RankArgs& a, const RankPlan& pl, hipStream_t s) {
   ka.W = a.W != nullptr ? a.W : W; ka.target = a.target;
   ka.excl_off = a.excl_off; ka.excl_idx = a.excl_idx;
   ka.chunk_off = pl.chunks > 0 ? a.chunk_off : nullptr; ka.chunk_q = a.chunk_q;
-  ka.tscore = tscore; ka.cnt = cnt; ka.ex = ex;
+  ka.tscore = reinterpret_cast<double*>(ws + o.tscore);
+  ka.cnt = reinterpret_cast<int2*>(ws + o.cnt);
+  ka.ex = reinterpret_cast<int2*>(ws + o.ex);
   ka.rank = a.rank; ka.score = a.score; ka.ncand = a.ncand;
-  switch ((R + 3) / 4) {
-    case 1: launch_rank<1>(ka, pl, s); break;
-    case 2: launch_rank<2>(ka, pl, s); break;
-    case 3: launch_rank<3>(ka, pl, s); break;
-    case 4: launch_rank<4>(ka, pl, s); break;
-    case 5: launch_rank<5>(ka, pl, s); break;
-    case 6: launch_rank<6>(ka, pl, s); break;
-    case 7: launch_rank<7>(ka, pl, s); break;
-    case 8: launch_rank<8>(ka, pl, s); break;
-    case 9: launch_rank<9>(ka, pl, s); break;
-    case 10: launch_rank<10>(ka, pl, s); break;
-    case 11: launch_rank<11>(ka, pl, s); break;
-    case 12: launch_rank<12>(ka, pl, s); break;
-    case 13: launch_rank<13>(ka, pl, s); break;
-    case 14: launch_rank<14>(ka, pl, s); break;
-    case 15: launch_rank<15>(ka, pl, s); break;
-    default: launch_rank<16>(ka, pl, s); break;
-  }
+  for_topk_steps(R, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    rank_target_k<KS><<<(unsigned)cdiv(ka.nq, (int64_t)kTopkTile), kRankWave, 0, s>>>(ka);
+    AO_KERNEL_CHECK();
+    const dim3 grid((unsigned)pl.tp.qtiles, (unsigned)pl.tp.slabs);
+    if (pl.tp.qt == 2) rank_count_k<KS, 2><<<grid, kRankWave, 0, s>>>(ka);
+    else rank_count_k<KS, 1><<<grid, kRankWave, 0, s>>>(ka);
+    AO_KERNEL_CHECK();
+    if (pl.chunks > 0) {
+      rank_excl_k<KS><<<(unsigned)pl.chunks, kRankWave, 0, s>>>(ka);
+      AO_KERNEL_CHECK();
+    }
+  });
   rank_finish_k<<<(unsigned)a.nq, kRankWave, 0, s>>>(ka);
   AO_KERNEL_CHECK();
 }

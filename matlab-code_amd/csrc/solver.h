@@ -119,6 +119,24 @@ struct RankList {
   int64_t resident_bytes() const {
     return (int64_t)(idx.bytes + eoff.bytes + eidx.bytes + coff.bytes + cq.bytes + ws.bytes + rank.bytes + score.bytes + ncand.bytes + part.bytes);
   }
+  // the rank pass of this list against the factors hf (rank_of_w: the caller names its W and targets instead of idx)
+  RankArgs args(const HeldoutFactors& hf) const {
+    RankArgs a;
+    a.hf = hf; a.mode = mode; a.I = I; a.nq = nq;
+    a.idx = idx.as<int>();
+    a.target = idx.as<int>() + (size_t)mode * nq;
+    if (plan.chunks > 0) {
+      a.excl_off = eoff.as<int64_t>();
+      a.excl_idx = eidx.as<int>();
+      a.chunk_off = coff.as<int64_t>();
+      a.chunk_q = cq.as<int>();
+    }
+    a.workspace = ws.p;
+    a.rank = rank.as<int64_t>();
+    a.score = score.d();
+    a.ncand = ncand.as<int64_t>();
+    return a;
+  }
   void clear() { *this = RankList(); }
   RankList() = default;
   RankList(RankList&&) = default;
@@ -383,10 +401,20 @@ class Engine {
   HeldoutFactors heldout_factors(const TensorInfo& t, bool* row_major) const;   // the current fac state of block t as the pass gathers it
   // skip_mode >= 0: that column of subs is neither read nor checked (its part of idx32 stays zero)
   void heldout_check_subs(const TensorInfo& t, int p, int64_t n, const int64_t* subs, std::vector<int>& idx32, int skip_mode = -1) const;
-  // the range checks, the per-query sort and removal of repeats and the chunk table of the exclusion lists of a rank pass
+  // The opening of the calls that ask nq queries along one mode of CP block p (top-k, rank-of, the ranking list, fold-in):
+  // usable engine, ended model, p, no PARAFAC2 block ("<what>: tensor p is a PARAFAC2 block; <purpose>"), order, mode,
+  // nq in [0, 2^31).  (solver_topk.hip)
+  TensorInfo& query_block(const char* what, const char* purpose, int p, int mode, int64_t nq);
+  // exclusion lists (excl_off not null): offsets non-decreasing from 0, rows in [0, I); ex32: the rows as int32, unsorted
+  void check_excl(int p, int64_t I, int64_t nq, const int64_t* excl_off, const int64_t* excl_idx, std::vector<int>& ex32) const;
+  // W (nq x R column-major on the host) row-major into `dev`; asynchronous: `rows` lives until the caller synchronises
+  void upload_w_rows(const double* W, int64_t nq, int R, std::vector<double>& rows, DevBuf& dev);
+  // check_excl, the per-query sort and removal of repeats and the chunk table of the exclusion lists of a rank pass
   void rank_prepare_excl(int p, int64_t I, int64_t nq, const int64_t* excl_off, const int64_t* excl_idx, RankExclHost& h) const;
-  // uploads them (asynchronously: the caller synchronises before `h` goes) and names them in `a`
-  void rank_upload_excl(const RankExclHost& h, int64_t nq, DevBuf& eoff, DevBuf& eidx, DevBuf& coff, DevBuf& cq, RankArgs& a);
+  // uploads them into l (asynchronously: the caller synchronises before `h` goes)
+  void rank_upload_excl(const RankExclHost& h, RankList& l);
+  // the device side of nq checked queries (everything of a RankList but `part`); idx32 empty: no subscripts (rank_of_w)
+  RankList rank_list_build(const TensorInfo& t, int mode, int64_t nq, int64_t I, const std::vector<int>& idx32, const RankExclHost& xh);
   CpBlock& project_block(const char* what, int p);   // tensor p's block, or the refusal of what cannot be projected
   void project_dense(CpBlock& b, const double* const* M, const int64_t* ld, const int* r, double* G);    // G: device
   void project_sparse(CpBlock& b, const double* const* M, const int64_t* ld, const int* r, double* G);

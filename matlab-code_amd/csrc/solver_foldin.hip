@@ -32,16 +32,8 @@ void Engine::fold_in_w(int p, int mode, int64_t nq, int64_t nobs, const int64_t*
 void Engine::fold_in_run(const char* what, bool weighted, int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs,
                          const double* vals, const double* wts, double alpha, const aoadmm_foldin_options* opt, double* rows_host,
                          int* info_host, int* iters_host, double* gram_host, double* rhs_host) {
-  require_usable();
-  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
-  AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
-  TensorInfo& t = tensors_[p];
-  if (t.par2)
-    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("%s: tensor %d is a PARAFAC2 block; rows are folded into CP blocks", what, p));
+  TensorInfo& t = query_block(what, "rows are folded into CP blocks", p, mode, nq);
   const int nd = t.nmodes;
-  AO_REQUIRE(nd >= 2 && nd <= kCooMaxModes, "tensor %d: order %d", p, nd);
-  AO_REQUIRE(mode >= 0 && mode < nd, "tensor %d: mode %d outside [0, %d)", p, mode, nd);
-  AO_REQUIRE(nq >= 0 && nq < ((int64_t)1 << 31), "nq = %lld outside [0, 2^31)", (long long)nq);
   AO_REQUIRE(nobs >= 0, "nobs = %lld < 0", (long long)nobs);
   FoldinOptions fo;                                    // null: ridge 0, no constraint
   if (opt != nullptr) {

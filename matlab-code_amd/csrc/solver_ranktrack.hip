@@ -16,17 +16,7 @@ bool Engine::has_ranklist() const {
 // Arguments and validation are those of rank_of_run with subscripts; everything is checked and prepared before the
 // previous list is touched.
 void Engine::set_ranklist(int p, int mode, int64_t nq, const int64_t* subs, const int64_t* excl_off, const int64_t* excl_idx) {
-  const char* what = "aoadmm_tensor_set_ranklist";
-  require_usable();
-  AO_REQUIRE(model_done_, "call aoadmm_model_end first");
-  AO_REQUIRE(p >= 0 && p < n_tensors_, "tensor %d out of range", p);
-  TensorInfo& t = tensors_[p];
-  if (t.par2)
-    throw Error(AOADMM_ERR_UNSUPPORTED, fmt("%s: tensor %d is a PARAFAC2 block; ranks of held-out entries are for CP blocks", what, p));
-  const int nd = t.nmodes;
-  AO_REQUIRE(nd >= 2 && nd <= kCooMaxModes, "tensor %d: order %d", p, nd);
-  AO_REQUIRE(mode >= 0 && mode < nd, "tensor %d: mode %d outside [0, %d)", p, mode, nd);
-  AO_REQUIRE(nq >= 0 && nq < ((int64_t)1 << 31), "nq = %lld outside [0, 2^31)", (long long)nq);
+  TensorInfo& t = query_block("aoadmm_tensor_set_ranklist", "ranks of held-out entries are for CP blocks", p, mode, nq);
   if (nq == 0) { t.rl.clear(); return; }
   AO_REQUIRE(subs != nullptr, "null subs");
   AO_REQUIRE(excl_off == nullptr || excl_idx != nullptr || excl_off[nq] == 0, "null excl_idx");
@@ -38,19 +28,8 @@ void Engine::set_ranklist(int p, int mode, int64_t nq, const int64_t* subs, cons
   rank_prepare_excl(p, I, nq, excl_off, excl_idx, xh);
 
   AO_HIP(hipSetDevice(device_));
-  RankList l;
-  l.nq = nq; l.mode = mode; l.nd = nd; l.I = I;
-  l.listed = (int64_t)xh.ex32.size();
-  l.plan = rank_plan(I, modes_[t.modes[0]].R, nq, (int64_t)xh.chq.size());
-  l.idx.alloc(idx32.size() * sizeof(int));
-  l.ws.alloc(l.plan.workspace_bytes);
-  l.rank.alloc((size_t)nq * sizeof(int64_t));
-  l.score.alloc((size_t)nq * sizeof(double));
-  l.ncand.alloc((size_t)nq * sizeof(int64_t));
+  RankList l = rank_list_build(t, mode, nq, I, idx32, xh);
   l.part.alloc(rank_metrics_part_bytes(nq));
-  AO_HIP(hipMemcpyAsync(l.idx.p, idx32.data(), idx32.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
-  RankArgs unused;
-  rank_upload_excl(xh, nq, l.eoff, l.eidx, l.coff, l.cq, unused);
   AO_HIP(hipStreamSynchronize(stream_));                 // the host arrays go out of scope
   t.rl = std::move(l);
 }
@@ -82,20 +61,7 @@ void Engine::ranklist_enqueue(int p, double* slots) {
   TensorInfo& t = tensors_[p];
   RankList& l = t.rl;
   const HeldoutFactors hf = heldout_factors(t, nullptr);
-  RankArgs a;
-  a.hf = hf; a.mode = l.mode; a.I = l.I; a.nq = l.nq;
-  a.idx = l.idx.as<int>();
-  a.target = l.idx.as<int>() + (size_t)l.mode * l.nq;
-  if (l.plan.chunks > 0) {
-    a.excl_off = l.eoff.as<int64_t>();
-    a.excl_idx = l.eidx.as<int>();
-    a.chunk_off = l.coff.as<int64_t>();
-    a.chunk_q = l.cq.as<int>();
-  }
-  a.workspace = l.ws.p;
-  a.rank = l.rank.as<int64_t>();
-  a.score = l.score.d();
-  a.ncand = l.ncand.as<int64_t>();
+  const RankArgs a = l.args(hf);
   KernelStats& ks = timers_.stats[kStatsTopk];           // one launch count per list and evaluation, as a rank_of call
   const LaunchTimers::Pair pr = timers_.begin(ks, timers_.profile, stream_);
   rank_enqueue(a, l.plan, stream_);

@@ -1,11 +1,7 @@
 // Top-k completions along one mode: the weights, the fused scores-and-selection pass and the merge.  See topk.h and
 // DESIGN.md section 9.5.
 //
-// Scores: v_mfma_f64_16x16x4_f64 with 16 rows of F_mode on the row axis and 16 queries on the column axis, the operand
-// map admm_rows_mfma_k uses: lane (c = l & 15, q4 = l >> 4) supplies A[row c][k = 4 s + q4] = F_mode(row0 + c, 4 s + q4)
-// and B[k = 4 s + q4][col c] = w_c(4 s + q4) and receives D[row q4 + 4 e][col c], e = 0 .. 3.  A score is the chain of
-// ceil(R / 4) MFMAs over s = 0, 1, ... starting from +0 with columns beyond R supplied as zeros: its summation order is
-// a function of R alone, whatever the slab, the tile, the query's place in the tile or the strides gathered through.
+// Scores: the stream of topk_dev.h (the operand map, the chain from +0, the load ring); this unit is the selection.
 //
 // Selection: a workgroup is ONE wave, so its candidate buffers are wave-private and every barrier is a one-wave barrier
 // in uniform control flow.  Per query: `cap` slots of (score, row) in LDS, a count and a threshold in registers (the
@@ -17,12 +13,10 @@
 #include <algorithm>
 #include <cmath>
 
-#include "topk.h"
+#include "topk_dev.h"
 
 namespace aoadmm {
 
-typedef double topk_f64x4 __attribute__((ext_vector_type(4)));
-constexpr int kTopkWave = 64;
 constexpr int kTopkMergeCap = 2 * kTopkMax;      // the merge's buffer: the best k so far and one chunk of 64 candidates
 
 struct TopkKArgs {
@@ -95,8 +89,7 @@ __device__ __forceinline__ bool topk_excluded(const int* ex, int64_t lo, int64_t
   return lo < end && ex[lo] == row;
 }
 
-// KS = ceil(R / 4) MFMA steps, compiled in (a chain whose length is a run-time value reads its accumulator back after
-// every MFMA); QT: query tiles per workgroup
+// KS = ceil(R / 4) MFMA steps, compiled in; QT: query tiles per workgroup
 template <int KS, int QT>
 __global__ __launch_bounds__(kTopkWave) void topk_scores_k(TopkKArgs a) {
   extern __shared__ double topk_lds[];
@@ -105,10 +98,9 @@ __global__ __launch_bounds__(kTopkWave) void topk_scores_k(TopkKArgs a) {
   const int lane = (int)threadIdx.x, c = lane & 15, q4 = lane >> 4;
   const int R = a.R, k = a.k, cap = a.cap;
   const int64_t slab = blockIdx.y;
-  const int rb = (int)(slab * a.slab_rows);                       // I < 2^31: rows are ints from here on
-  const int re = (int)(slab * a.slab_rows + a.slab_rows < a.I ? slab * a.slab_rows + a.slab_rows : a.I);
+  const TopkSlab sl = topk_slab(slab, a.slab_rows, a.I);
+  const int re = sl.re;
   const double ninf = -__builtin_inf();
-  const bool last_ok = 4 * (KS - 1) + q4 < R;                     // only the last step can hold columns beyond R
 
   // A query beyond nq never takes a candidate: its threshold is +inf from the start.
   double w[QT][KS];
@@ -120,11 +112,7 @@ __global__ __launch_bounds__(kTopkWave) void topk_scores_k(TopkKArgs a) {
   for (int qt = 0; qt < QT; ++qt) {
     const int64_t q = ((int64_t)blockIdx.x * QT + qt) * kTopkTile + c;
     const bool live = q < a.nq;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int kk = 4 * s + q4;
-      w[qt][s] = live && kk < R ? a.W[q * R + kk] : 0.0;
-    }
+    topk_load_w(w[qt], a.W, q, live, R, q4);
     eb[qt] = ee[qt] = 0;
     if (live && a.excl_off != nullptr) { eb[qt] = a.excl_off[q]; ee[qt] = a.excl_off[q + 1]; }
     cnt[qt] = 0;
@@ -132,28 +120,7 @@ __global__ __launch_bounds__(kTopkWave) void topk_scores_k(TopkKArgs a) {
     act[qt] = !live;
   }
 
-  // Unconditional loads on clamped addresses (a row of this slab, a column below R): no branch around a load, so the
-  // loads of D steps stay in flight.  What a clamp brought in is dropped where it is used.
-  auto load_rows = [&](double (&av)[KS], int r0) {
-    const int ar = r0 + c < re ? r0 + c : re - 1;
-    const double* fp = a.F.p + (int64_t)ar * a.F.sI;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int kk = 4 * s + q4;
-      av[s] = fp[(int64_t)(kk < R ? kk : R - 1) * a.F.sR];
-    }
-  };
-
-  auto step = [&](const double (&av)[KS], int r0) {
-    topk_f64x4 acc[QT];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) acc[qt] = topk_f64x4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const double x = s + 1 < KS || last_ok ? av[s] : 0.0;
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) acc[qt] = __builtin_amdgcn_mfma_f64_16x16x4f64(x, w[qt][s], acc[qt], 0, 0, 0);
-    }
+  auto step = [&](const topk_f64x4 (&acc)[QT], int r0) {
     // most steps of a long slab bring no candidate at all: one ballot decides (rows beyond the slab and excluded rows
     // are sorted out below)
     bool any = false;
@@ -169,7 +136,9 @@ __global__ __launch_bounds__(kTopkWave) void topk_scores_k(TopkKArgs a) {
       int* Xq = X + (size_t)(qt * kTopkTile + c) * cap;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const int row = r0 + q4 + 4 * e;
+        // r0 as the scalar it is: folded into the lane's part, the ring's D steps each keep their own four row offsets
+        // in VGPRs (6 to 8 more, a wave per SIMD less at <1, 1>, <3, 1> and <6, 2>)
+        const int row = __builtin_amdgcn_readfirstlane(r0) + q4 + 4 * e;
         const double v = acc[qt][e];
         bool pred = row < re && (v > tv[qt] || (!act[qt] && v == ninf));   // never a NaN
         if (pred && ee[qt] > eb[qt]) pred = !topk_excluded(a.excl_idx, eb[qt], ee[qt], row);
@@ -200,24 +169,7 @@ __global__ __launch_bounds__(kTopkWave) void topk_scores_k(TopkKArgs a) {
     }
   };
 
-  // A ring of D steps' rows with fixed roles (no register moves: a move would wait for the load it copies)
-  constexpr int D = KS <= 8 ? 4 : 2;
-  double av[D][KS];
-#pragma unroll
-  for (int d = 0; d < D; ++d) load_rows(av[d], rb + d * kTopkRows);
-  for (int row0 = rb; row0 < re; row0 += D * kTopkRows) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      const int r0 = row0 + d * kTopkRows;
-      if (r0 < re) {                                               // uniform
-        double cur[KS];
-#pragma unroll
-        for (int s = 0; s < KS; ++s) cur[s] = av[d][s];
-        load_rows(av[d], r0 + D * kTopkRows);
-        step(cur, r0);
-      }
-    }
-  }
+  topk_stream(a.F, R, sl, w, step);
 
   // the slab's answer: every buffer sorted, k entries per query to this workgroup's own area
   __syncthreads();
@@ -307,7 +259,19 @@ constexpr int64_t kTopkTargetGroups = 2048;      // workgroups that fill the dev
 constexpr int64_t kTopkMinSlabRows = 256;        // a slab shorter than this spends its time on the final compaction
 constexpr int64_t kTopkMergeGroup = 32;          // slabs one merge workgroup reduces; more slabs take another level
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// the workspace: where every segment starts, and its size
+struct TopkWs { size_t W, cand_val, cand_idx, pong_val, pong_idx, bytes; };
+static TopkWs topk_ws(int R, int64_t nq, int k, int64_t slabs) {
+  const size_t c0 = (size_t)nq * slabs * k, c1 = (size_t)nq * cdiv(slabs, kTopkMergeGroup) * k;   // the merge's ping and pong
+  TopkWs o;
+  o.W = 0;
+  o.cand_val = o.W + align256((size_t)nq * R * sizeof(double));
+  o.cand_idx = o.cand_val + align256(c0 * sizeof(double));
+  o.pong_val = o.cand_idx + align256(c0 * sizeof(int));
+  o.pong_idx = o.pong_val + align256(c1 * sizeof(double));
+  o.bytes = o.pong_idx + align256(c1 * sizeof(int));
+  return o;
+}
 
 TopkPlan topk_plan(int64_t I, int R, int64_t nq, int k) {
   TopkPlan pl;
@@ -321,18 +285,8 @@ TopkPlan topk_plan(int64_t I, int R, int64_t nq, int k) {
   pl.slabs = cdiv(I, pl.slab_rows);
   pl.cap = 2 * std::max(k, kTopkRows);
   pl.lds_bytes = (size_t)pl.qt * kTopkTile * pl.cap * (sizeof(double) + sizeof(int));
-  const size_t c0 = (size_t)nq * pl.slabs * k, c1 = (size_t)nq * cdiv(pl.slabs, kTopkMergeGroup) * k;   // the merge's ping and pong
-  pl.workspace_bytes = align256((size_t)nq * R * sizeof(double)) + align256(c0 * sizeof(double)) + align256(c0 * sizeof(int)) +
-                       align256(c1 * sizeof(double)) + align256(c1 * sizeof(int));
+  pl.workspace_bytes = topk_ws(R, nq, k, pl.slabs).bytes;
   return pl;
-}
-
-template <int KS>
-static void launch_scores(const TopkKArgs& ka, const TopkPlan& pl, hipStream_t s) {
-  const dim3 grid((unsigned)pl.qtiles, (unsigned)pl.slabs);
-  if (pl.qt == 2) topk_scores_k<KS, 2><<<grid, kTopkWave, pl.lds_bytes, s>>>(ka);
-  else topk_scores_k<KS, 1><<<grid, kTopkWave, pl.lds_bytes, s>>>(ka);
-  AO_KERNEL_CHECK();
 }
 
 void topk_weights_enqueue(const HeldoutFactors& hf, int mode, int64_t nq, const int* idx, double* W, hipStream_t s) {
@@ -350,16 +304,12 @@ void topk_enqueue(const TopkArgs& a, const TopkPlan& pl, hipStream_t s) {
                  pl.slab_rows % kTopkRows == 0 && pl.slabs * pl.slab_rows >= a.I && pl.qtiles * pl.qt * kTopkTile >= a.nq,
              "internal: top-k plan");
   char* ws = static_cast<char*>(a.workspace);
-  double* W = reinterpret_cast<double*>(ws);
-  ws += align256((size_t)a.nq * R * sizeof(double));
-  double* cand_val = reinterpret_cast<double*>(ws);
-  ws += align256((size_t)a.nq * pl.slabs * a.k * sizeof(double));
-  int* cand_idx = reinterpret_cast<int*>(ws);
-  ws += align256((size_t)a.nq * pl.slabs * a.k * sizeof(int));
-  const size_t c1 = (size_t)a.nq * cdiv(pl.slabs, kTopkMergeGroup) * a.k;
-  double* pong_val = reinterpret_cast<double*>(ws);
-  ws += align256(c1 * sizeof(double));
-  int* pong_idx = reinterpret_cast<int*>(ws);
+  const TopkWs o = topk_ws(R, a.nq, a.k, pl.slabs);
+  double* W = reinterpret_cast<double*>(ws + o.W);
+  double* cand_val = reinterpret_cast<double*>(ws + o.cand_val);
+  int* cand_idx = reinterpret_cast<int*>(ws + o.cand_idx);
+  double* pong_val = reinterpret_cast<double*>(ws + o.pong_val);
+  int* pong_idx = reinterpret_cast<int*>(ws + o.pong_idx);
 
   if (a.W == nullptr) topk_weights_enqueue(a.hf, a.mode, a.nq, a.idx, W, s);
 
@@ -369,24 +319,13 @@ void topk_enqueue(const TopkArgs& a, const TopkPlan& pl, hipStream_t s) {
   ka.I = a.I; ka.nq = a.nq; ka.slab_rows = pl.slab_rows; ka.slabs = pl.slabs;
   ka.W = a.W != nullptr ? a.W : W; ka.excl_off = a.excl_off; ka.excl_idx = a.excl_idx;
   ka.cand_val = cand_val; ka.cand_idx = cand_idx;
-  switch ((R + 3) / 4) {
-    case 1: launch_scores<1>(ka, pl, s); break;
-    case 2: launch_scores<2>(ka, pl, s); break;
-    case 3: launch_scores<3>(ka, pl, s); break;
-    case 4: launch_scores<4>(ka, pl, s); break;
-    case 5: launch_scores<5>(ka, pl, s); break;
-    case 6: launch_scores<6>(ka, pl, s); break;
-    case 7: launch_scores<7>(ka, pl, s); break;
-    case 8: launch_scores<8>(ka, pl, s); break;
-    case 9: launch_scores<9>(ka, pl, s); break;
-    case 10: launch_scores<10>(ka, pl, s); break;
-    case 11: launch_scores<11>(ka, pl, s); break;
-    case 12: launch_scores<12>(ka, pl, s); break;
-    case 13: launch_scores<13>(ka, pl, s); break;
-    case 14: launch_scores<14>(ka, pl, s); break;
-    case 15: launch_scores<15>(ka, pl, s); break;
-    default: launch_scores<16>(ka, pl, s); break;
-  }
+  for_topk_steps(R, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    const dim3 grid((unsigned)pl.qtiles, (unsigned)pl.slabs);
+    if (pl.qt == 2) topk_scores_k<KS, 2><<<grid, kTopkWave, pl.lds_bytes, s>>>(ka);
+    else topk_scores_k<KS, 1><<<grid, kTopkWave, pl.lds_bytes, s>>>(ka);
+    AO_KERNEL_CHECK();
+  });
 
   // levels of 32 slabs per workgroup until one workgroup per query is left; each level's output fits the other buffer
   double* in_val = cand_val;

@@ -80,6 +80,26 @@ def test_exact(pkg, eng, N, mode, R, I, nq):
     assert (got[2] == I).all() and (got[0] >= 0).all()
 
 
+@pytest.mark.parametrize('KS', range(1, 17))
+def test_exact_at_every_chain_length(pkg, eng, KS):
+    """Every compiled-in chain length ceil(R / 4) = 1 .. 16 at R = 4 KS - 1: the last step carries a zeroed column and a
+    clamped column address.  I = 273 and nq = 17 are the smallest that take every branch of the stream: two tiles per
+    workgroup, the second ragged, and two slabs of 144 and 129 rows, which is more than two turns of the ring of four
+    steps and a last step that holds one live row.  The first targets as in test_exact."""
+    mode, R, I, nq = 1, 4 * KS - 1, 273, 17                    # N = 3
+    qt, qtiles, slabs, slab_rows = count_plan(I, nq)
+    assert (qt, qtiles, slabs, slab_rows, I - slab_rows) == (2, 1, 2, 144, 129)
+    rng = np.random.default_rng(2000 + KS)
+    shape = [6, I, 4]
+    U = int_factors(rng, shape, R)
+    dataless(pkg, eng, U)
+    subs = queries(rng, shape, nq)
+    subs[:3, mode] = [0, I - 1, (I - 1) - (I - 1) % 16]
+    got = eng.rank_of(0, mode, subs)
+    assert same(got, ref_rank(U, mode, subs))
+    assert (got[2] == I).all() and (got[0] >= 0).all()
+
+
 # ---- 2. slabs ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('nq', [3, 40])
 def test_targets_on_the_slab_cuts(pkg, eng, nq):

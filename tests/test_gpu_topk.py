@@ -123,6 +123,28 @@ def test_exact(pkg, eng, N, mode, R, I, nq, k):
     assert np.array_equal(idx, ridx) and np.array_equal(val, rval)
 
 
+@pytest.mark.parametrize('KS', range(1, 17))
+def test_exact_at_every_chain_length(pkg, eng, KS):
+    """Every compiled-in chain length ceil(R / 4) = 1 .. 16 at R = 4 KS - 1: the last step carries a zeroed column and a
+    clamped column address.  I = 273 and nq = 17 are the smallest that take every branch of the stream: two tiles per
+    workgroup, the second ragged, and two slabs of 144 and 129 rows, which is more than two turns of the ring of four
+    steps and a last step that holds one live row."""
+    from rank_of_ref import count_plan
+    mode, R, I, nq, k = 1, 4 * KS - 1, 273, 17, 2              # N = 3
+    qt, qtiles, slabs, slab_rows = count_plan(I, nq)           # top-k's plan at k <= 32
+    assert (qt, qtiles, slabs, slab_rows, I - slab_rows) == (2, 1, 2, 144, 129)
+    rng = np.random.default_rng(1000 + KS)
+    shape = [6, I, 4]
+    U = int_factors(rng, shape, R)
+    dataless(pkg, eng, U)
+    subs = queries(rng, shape, nq)
+    subs[:, mode] = -5                                         # ignored and not range-checked
+    idx, val = eng.topk(0, mode, subs, k)
+    ridx, rval = ref_topk(U, mode, subs, k)
+    assert idx.shape == (nq, k) and idx.dtype == np.int64 and val.shape == (nq, k)
+    assert np.array_equal(idx, ridx) and np.array_equal(val, rval)
+
+
 def test_nan_scores_are_no_candidates(pkg, eng):
     rng = np.random.default_rng(3)
     U = int_factors(rng, (300, 5), 4)
