@@ -722,6 +722,65 @@ int aoadmm_resident_fold_in_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, int6
                               const double* wts_or_null, double unstored_weight, const aoadmm_foldin_options* opt_or_null,
                               double* rows, int* info, int* iters_or_null, double* gram_or_null, double* rhs_or_null);
 
+/* ---- fold-in of new slabs into a PARAFAC2 block ---- */
+/* The rows of C of nk NEW slabs (a new sample, run, patient visit) of PARAFAC2 block p, with the fitted A = AOADMM_F_FAC
+ * of the block's first mode (I x R) and DeltaB = AOADMM_F_DELTAB (R x R) held fixed and B_q = P_q DeltaB imposed exactly
+ * (direct-fitting PARAFAC2).  X holds the slabs back to back, slab q is I x cols[q] column-major; cols[q] = J_q >= R.
+ * With Y = X_q' A (J_q x R, the only pass over the data) and S = (A'A) .* (DeltaB'DeltaB) (once per call, fixed order), per
+ * slab, starting from c = c0[q] (c0 is nk x R column-major; NULL: ones), at least once and at most max_iter times:
+ *   W = Y diag(c) DeltaB';  P = U V' of svd(W, 'econ') by one-sided Jacobi (cmtf_fun_AOADMM.m:532-534);  B = P DeltaB;
+ *   b(r) = sum_j Y(j, r) B(j, r);  c_old = c;
+ *   constraint = 0:  c = (S + ridge I)^-1 b by Cholesky, factored once per call;
+ *   constraint = 1 (non-negativity): the cold-started row loop of aoadmm_resident_fold_in on (S + ridge I, b): rho =
+ *     trace(S) / R, L = chol(S + (ridge + rho / 2) I) once per call, z = mu = 0, u = (b + rho / 2 (z - mu)) / (L L'),
+ *     z_old = z, z = max(u + mu, 0), mu += u - z at least once and while iter < max_inner and ||u - z|| / ||u|| > tol_primal
+ *     or ||z - z_old|| / ||mu|| > tol_dual (unscaled when mu = 0); c = z;
+ *   stop when ||c - c_old|| <= tol ||c||.
+ * Then res[q] = ||X_q||^2 - 2 c'b + c'S c and xnorm[q] = ||X_q||^2.  With P'P = I the system of c does not depend on the
+ * slab, which is why one factorisation serves the call.
+ * Outputs: C nk x R column-major; B and P in the slab layout of the state fields (slab q at (sum_{q' < q} J_q') R, J_q x R
+ * column-major); res, xnorm, iters (outer iterations taken), info: one per slab; Y in the slab layout; sys = S (R x R)
+ * before the ridge; path[0] = AOADMM_P2FOLD_Y_* of the Y pass and path[1] = AOADMM_P2FOLD_ALT_* of the alternation.
+ * B, P, xnorm, Y, sys and path may be NULL; so may c0 and opt (NULL: max_iter 50, tol 1e-8, ridge 0, no constraint).
+ * info[q] = 1 when W lost a column in some iteration: its norm after the sweeps was exactly 0 (an all-zero slab is the
+ * plainest case); the polar factor then has a zero column there and the row is still returned (a zero slab gives C = 0,
+ * res = 0).  A failed pivot of the shared system returns AOADMM_ERR_NOT_PD with every output untouched.
+ * AOADMM_ERR_INVALID, with every output untouched, for: p out of range or not a PARAFAC2 block, A or DeltaB never set,
+ * nk < 0, J_q < R, J_q, sum J_q or R sum J_q beyond the int range, max_iter < 1, tol or ridge negative or not finite, every option
+ * value aoadmm_resident_fold_in refuses, NULL cols / X / C / res / iters / info.  AOADMM_ERR_UNSUPPORTED on a multi-device
+ * context (aoadmm_create_multi with more than one device).  nk = 0 returns at once.
+ * Values are not checked for finiteness: a NaN reaches its own slab only.  The block's weight, B_k, P_k, C and its data are
+ * not read: dense, sparse-slab, masked and slab-sharded blocks answer alike, there is no collective, and the ranks of a
+ * communicator may ask different things.  A slab's outputs are a function of A, DeltaB, the slab, c0[q] and the options:
+ * not of nk, the other slabs or their order.
+ * The call takes the number of rows of every slab from the model: X must hold I sum J_q doubles with I =
+ * aoadmm_par2_rows(p), which a caller that receives slabs from elsewhere checks first (Engine.par2_fold_in does).  A call
+ * that fails counts nothing in kernel-statistics class 17. */
+typedef struct {
+  int max_iter;
+  double tol;
+  double ridge;
+  int constraint;    /* 0: none, 1: non-negativity */
+  int max_inner;
+  double tol_primal;
+  double tol_dual;
+} aoadmm_par2_foldin_options;
+/* path[0]: 2 (T - 1) + chunked, T = ceil(R / 16) factor tiles of 16 columns per wave; chunked: I > 4096 rows, the Y pass
+ * cuts I into ceil(I / 4096) chunks (a number that depends on I alone) and adds their partials in chunk order */
+enum {
+  AOADMM_P2FOLD_Y_T1 = 0, AOADMM_P2FOLD_Y_T1_CHUNKED = 1, AOADMM_P2FOLD_Y_T2 = 2, AOADMM_P2FOLD_Y_T2_CHUNKED = 3,
+  AOADMM_P2FOLD_Y_T3 = 4, AOADMM_P2FOLD_Y_T3_CHUNKED = 5, AOADMM_P2FOLD_Y_T4 = 6, AOADMM_P2FOLD_Y_T4_CHUNKED = 7
+};
+/* path[1]: Y_q and W of every slab in LDS (R^2 + 2 max(J_q) R doubles within 48 KB), or in a workspace */
+enum { AOADMM_P2FOLD_ALT_LDS = 0, AOADMM_P2FOLD_ALT_WS = 1 };
+/* *rows = I of PARAFAC2 block p, the number of rows of each of its slabs and of its first factor.  AOADMM_ERR_INVALID for
+ * p out of range, a CP block or a NULL pointer.  No device work. */
+int aoadmm_par2_rows(aoadmm_ctx* ctx, int p, int64_t* rows);
+int aoadmm_resident_par2_fold_in(aoadmm_ctx* ctx, int p, int64_t nk, const int64_t* cols, const double* X, const double* c0_or_null,
+                                 const aoadmm_par2_foldin_options* opt_or_null, double* C, double* B_or_null, double* P_or_null,
+                                 double* res, double* xnorm_or_null, int* iters, int* info, double* Y_or_null, double* sys_or_null,
+                                 int* path_or_null);
+
 /* ---- state (the struct G) ---------------------------------------------- */
 /* slab = k for cell-valued fields (PARAFAC2 B mode, P, mu_DeltaB), else 0.  slab = AOADMM_ALL_SLABS moves
  * all K cells at once: host holds them back to back, each J_k x R column-major, rows = sum J_k. */
@@ -767,7 +826,9 @@ int aoadmm_resident_par2_rhs(aoadmm_ctx* ctx, int p, int tensor_mode, double* ou
  * R^2 sum_{m != mode} I_m flops); which = 16 (15 is not assigned and stays AOADMM_ERR_INVALID): the list pass of every aoadmm_resident_em_list_pass call (one launch per
  * call, the gather kernel and its finisher inside one event pair; a solve's own list passes record no events; bytes =
  * subscripts streamed + factor rows gathered + the value read and, with update = 1, written in the block's precision,
- * twice for a matrix; flops = n * R * N + 8 n for the sums) */
+ * twice for a matrix; flops = n * R * N + 8 n for the sums); which = 17: aoadmm_resident_par2_fold_in (one launch per
+ * call: its kernels inside one event pair; bytes = the slabs + A + the outputs Y, P, B, C, res, xnorm, iters, info; flops =
+ * 2 I sum(J_q) R for Y + 9 R^2 J_q per slab and iteration taken: W, P, B and one sweep of rotations) */
 int aoadmm_kernel_stats(aoadmm_ctx* ctx, int which, int reset, double* contract_ms, int64_t* contract_launches,
                         double* contract_bytes, double* contract_flops);
 

@@ -58,6 +58,7 @@ ALL_SLABS = -1            # AOADMM_ALL_SLABS
 (P2SLAB_REGS1, P2SLAB_REGS2, P2SLAB_REGS4, P2SLAB_LDS4, P2SLAB_LDS8, P2SLAB_LDS16, P2SLAB_LDS64) = range(7)   # AOADMM_P2SLAB_*
 (P2CSYS_UNCOUPLED, P2CSYS_ROWS, P2CSYS_HHT, P2CSYS_DIAG, P2CSYS_DENSE) = range(5)   # AOADMM_P2CSYS_*
 (P2C_SINGLE, P2C_WG, P2C_LAUNCHED) = range(3)   # AOADMM_P2C_*
+(P2FOLD_ALT_LDS, P2FOLD_ALT_WS) = range(2)      # AOADMM_P2FOLD_ALT_*; AOADMM_P2FOLD_Y_* is 2 (T - 1) + chunked
 (RANK_HIT, RANK_NDCG, RANK_MRR, RANK_AUC) = range(4)   # AOADMM_RANK_*
 RANK_METRICS = {'hit': RANK_HIT, 'ndcg': RANK_NDCG, 'mrr': RANK_MRR, 'auc': RANK_AUC}
 (RANKSUM_N, RANKSUM_N_AUC, RANKSUM_HITS, RANKSUM_NDCG, RANKSUM_MRR, RANKSUM_AUC, RANKSUM_COUNT) = range(7)   # AOADMM_RANKSUM_*
@@ -76,6 +77,7 @@ SYMBOLS = [
     'aoadmm_resident_model_at', 'aoadmm_tensor_set_heldout', 'aoadmm_resident_heldout_stats', 'aoadmm_heldout_info', 'aoadmm_heldout_trace',
     'aoadmm_heldout_keep_best', 'aoadmm_heldout_restore_best', 'aoadmm_heldout_best_info', 'aoadmm_resident_topk',
     'aoadmm_resident_topk_w', 'aoadmm_resident_rank_of', 'aoadmm_resident_rank_of_w', 'aoadmm_resident_project', 'aoadmm_resident_core_consistency', 'aoadmm_resident_fold_in', 'aoadmm_resident_fold_in_w',
+    'aoadmm_resident_par2_fold_in', 'aoadmm_par2_rows',
     'aoadmm_tensor_set_ranklist', 'aoadmm_ranklist_info', 'aoadmm_rank_track', 'aoadmm_rank_trace', 'aoadmm_ranklist_last',
     'aoadmm_state_set', 'aoadmm_state_get', 'aoadmm_solve', 'aoadmm_resident_mttkrp', 'aoadmm_resident_par2_rhs', 'aoadmm_kernel_stats',
     'aoadmm_op_mttkrp', 'aoadmm_op_unfold_gram', 'aoadmm_resident_unfold_gram', 'aoadmm_resident_nvecs', 'aoadmm_op_gram', 'aoadmm_op_chol', 'aoadmm_op_prox', 'aoadmm_op_admm_constrained',
@@ -130,6 +132,11 @@ class NvecsOptions(C.Structure):                  # aoadmm_nvecs_options (zeros 
 class FoldinOptions(C.Structure):                 # aoadmm_foldin_options
     _fields_ = [('ridge', C.c_double), ('constraint', C.c_int), ('max_inner', C.c_int), ('tol_primal', C.c_double),
                 ('tol_dual', C.c_double)]
+
+
+class Par2FoldinOptions(C.Structure):             # aoadmm_par2_foldin_options
+    _fields_ = [('max_iter', C.c_int), ('tol', C.c_double), ('ridge', C.c_double), ('constraint', C.c_int), ('max_inner', C.c_int),
+                ('tol_primal', C.c_double), ('tol_dual', C.c_double)]
 
 
 class NvecsInfo(C.Structure):                     # aoadmm_nvecs_info
@@ -223,6 +230,9 @@ def load_library():
                                             C.POINTER(C.c_int), C.POINTER(C.c_int), dp, dp]
     lib.aoadmm_resident_fold_in_w.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.POINTER(i64), dp, dp, C.c_double, C.POINTER(FoldinOptions),
                                               dp, C.POINTER(C.c_int), C.POINTER(C.c_int), dp, dp]
+    lib.aoadmm_par2_rows.argtypes = [vp, C.c_int, C.POINTER(i64)]
+    lib.aoadmm_resident_par2_fold_in.argtypes = [vp, C.c_int, i64, C.POINTER(i64), dp, dp, C.POINTER(Par2FoldinOptions), dp, dp, dp, dp, dp,
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), dp, dp, C.POINTER(C.c_int)]
     lib.aoadmm_state_set.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, i64, i64]
     lib.aoadmm_state_get.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, i64, i64]
     lib.aoadmm_solve.argtypes = [vp, C.POINTER(Options), C.POINTER(Result)]

@@ -642,6 +642,24 @@ int aoadmm_resident_fold_in_w(aoadmm_ctx* ctx, int p, int mode, int64_t nq, int6
                         rhs_or_null);
   });
 }
+int aoadmm_par2_rows(aoadmm_ctx* ctx, int p, int64_t* rows) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {                                 // no device work; the model is the same on every engine
+    AO_REQUIRE(rows != nullptr, "null pointer");
+    *rows = ctx->eng->par2_rows(p);
+  });
+}
+int aoadmm_resident_par2_fold_in(aoadmm_ctx* ctx, int p, int64_t nk, const int64_t* cols, const double* X, const double* c0_or_null,
+                                 const aoadmm_par2_foldin_options* opt_or_null, double* C, double* B_or_null, double* P_or_null,
+                                 double* res, double* xnorm_or_null, int* iters, int* info, double* Y_or_null, double* sys_or_null,
+                                 int* path_or_null) {
+  CTX_OR_FAIL(ctx);
+  return guarded([&] {
+    require_single_engine(ctx, "aoadmm_resident_par2_fold_in");
+    ctx->eng->par2_fold_in(p, nk, cols, X, c0_or_null, opt_or_null, C, B_or_null, P_or_null, res, xnorm_or_null, iters, info, Y_or_null,
+                           sys_or_null, path_or_null);
+  });
+}
 int aoadmm_tensor_storage_info(aoadmm_ctx* ctx, int p, int* precision, double* scale, int64_t* resident_bytes) {
   CTX_OR_FAIL(ctx);
   // no collective and no device work: rank 0's engine answers for a multi-device context (every rank holds the same

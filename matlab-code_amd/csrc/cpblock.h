@@ -26,7 +26,8 @@ constexpr int kStatsFoldin = kStatsTopk + 1;                  // the fold-in of 
 // (kStatsFoldin + 1 stays unassigned: aoadmm_kernel_stats has always refused it, and callers that probe one past the
 // fold-in class rely on that)
 constexpr int kStatsEmList = kStatsFoldin + 2;                // the list pass of aoadmm_resident_em_list_pass (em_list.h)
-constexpr int kStatsClasses = kStatsEmList + 1;
+constexpr int kStatsPar2Foldin = kStatsEmList + 1;            // the fold-in of new PARAFAC2 slabs (par2_foldin.h)
+constexpr int kStatsClasses = kStatsPar2Foldin + 1;
 
 struct KernelStats {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -42,7 +43,7 @@ struct LaunchTimers {
   // [0] streaming contraction, [1] leading-mode contraction, [2] reductions over T, [3] sparse MTTKRP, the passes over
   // sparse PARAFAC2 slabs and the EM steps of observed-only blocks, [kStatsEmPass + n] the pass of those steps over
   // mode n's copy, [kStatsHeldout] the held-out passes, [kStatsTopk] the top-k completions, [kStatsFoldin] the fold-in of new rows,
-  // [kStatsEmList] the op-level list passes of marked masked blocks
+  // [kStatsEmList] the op-level list passes of marked masked blocks, [kStatsPar2Foldin] the fold-in of new PARAFAC2 slabs
   KernelStats stats[kStatsClasses];
   bool profile = true;
   bool profile_reductions = false;   // switched on by the first kernel_stats(2, ...) call: two more events per reduction

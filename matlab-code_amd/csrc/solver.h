@@ -333,6 +333,11 @@ class Engine {
   void fold_in_run(const char* what, bool weighted, int p, int mode, int64_t nq, int64_t nobs, const int64_t* subs, const double* vals,
                    const double* wts, double alpha, const aoadmm_foldin_options* opt, double* rows_host, int* info_host,
                    int* iters_host, double* gram_host, double* rhs_host);
+  // new slabs of a PARAFAC2 block: their rows of C against the fitted A and DeltaB (par2_foldin.h)
+  int64_t par2_rows(int p) const;                  // I of PARAFAC2 block p: the rows every slab has (aoadmm_par2_rows)
+  void par2_fold_in(int p, int64_t nk, const int64_t* cols, const double* X, const double* c0, const aoadmm_par2_foldin_options* opt,
+                    double* C_host, double* B_host, double* P_host, double* res_host, double* xnorm_host, int* iters_host, int* info_host,
+                    double* Y_host, double* sys_host, int* path_host);
   // Tucker projection of a resident 3-way CP block and the core consistency of its CP model (core.h, DESIGN.md section
   // 9.9): core (r[0] x r[1] x r[2], column-major) = X x_1 M[0]' x_2 M[1]' x_3 M[2]', M[n] on the host
   void project(int p, const double* const* M, const int64_t* ld, const int* r, double* core_host);

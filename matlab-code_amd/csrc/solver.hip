@@ -1097,6 +1097,7 @@ void Engine::state_get(int field, int index, int slab, double* host, int64_t row
 // ---------------------------------------------------------------------------
 void Engine::kernel_stats(int which, int reset, double* ms, int64_t* launches, double* bytes, double* flops) {
   static_assert(kStatsEmList == 16, "include/aoadmm_hip.h documents the list pass as class 16");
+  static_assert(kStatsPar2Foldin == 17, "include/aoadmm_hip.h documents the fold-in of PARAFAC2 slabs as class 17");
   AO_REQUIRE(which != kStatsFoldin + 1, "kernel_stats: class %d is not assigned", which);
   AO_REQUIRE(which >= 0 && which < kStatsClasses, "kernel_stats: which must be 0 .. %d", kStatsClasses - 1);
   if (which == 2) timers_.profile_reductions = true;

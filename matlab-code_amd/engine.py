@@ -614,6 +614,74 @@ class Engine:
             return rows, info, iters, gram, rhs
         return rows, info, iters
 
+    def par2_rows(self, p):
+        """I of PARAFAC2 block p: the rows of each of its slabs (`aoadmm_par2_rows`)."""
+        rows = C.c_int64(0)
+        capi.check(self.lib.aoadmm_par2_rows(self.h, int(p), C.byref(rows)))
+        return rows.value
+
+    def par2_fold_in(self, p, slabs, c0=None, max_iter=50, tol=1e-8, ridge=0.0, nonneg=False, max_inner=5, inner_tol=(0, 0),
+                     return_B=True, return_P=False, return_y=False, return_sys=False):
+        """The rows of C of new slabs of PARAFAC2 block p against its fitted A and DeltaB, B_q = P_q DeltaB imposed exactly
+        (`aoadmm_resident_par2_fold_in`).  slabs is a list of 2-D arrays, each I x J_q with J_q >= R (a scipy.sparse slab
+        is densified, one at a time); c0 (nk x R) starts the alternation (None: ones).  Per slab W = Y diag(c) DeltaB' with
+        Y = X_q' A, P = its polar factor, b = diag(Y' P DeltaB), then c = (S + ridge I)^-1 b with S = (A'A) .* (DeltaB'DeltaB),
+        or with nonneg=True the row ADMM loop of `fold_in` (at most max_inner iterations, inner_tol = (primal, dual)), at
+        most max_iter times and until ||c - c_old|| <= tol ||c||.  Returns a dict: C (nk x R), B and P (lists of J_q x R,
+        None unless asked for), res = ||X_q - A diag(c) B_q'||^2, xnorm = ||X_q||^2, fit = 1 - res / xnorm, iters, info (1:
+        W lost a column, a zero slab for one), path = (Y class, alternation class), and with return_y / return_sys also
+        Y (list) and sys = S."""
+        mats = []
+        for Xq in slabs:
+            if hasattr(Xq, 'toarray'):
+                Xq = Xq.toarray()
+            Xq = np.asarray(Xq, dtype=np.float64)
+            if Xq.ndim != 2:
+                raise ValueError('par2_fold_in: every slab must be a 2-D array')
+            mats.append(Xq)
+        nk = len(mats)
+        R = self.block_rank(p)                                  # an unknown block is refused here, as the library refuses it
+        I = self.par2_rows(p)                                   # and so is a block that is not PARAFAC2
+        for q, m in enumerate(mats):                            # the library reads I x J_q doubles per slab
+            if m.shape[0] != I:
+                raise ValueError('par2_fold_in: slab %d has %d rows, block %d has I = %d' % (q, m.shape[0], int(p), I))
+        cols = np.array([m.shape[1] for m in mats], dtype=np.int64)
+        Jtot = int(cols.sum())
+        X = np.concatenate([m.ravel(order='F') for m in mats]) if nk else np.zeros(0)
+        C0 = None
+        if c0 is not None:
+            C0 = capi.as_f(c0)
+            if C0.shape != (nk, R):
+                raise ValueError('par2_fold_in: c0 must be nk x R = %d x %d' % (nk, R))
+        Cm = np.zeros((nk, R), order='F')
+        res, xnorm = np.zeros(nk), np.zeros(nk)
+        iters, info = np.zeros(nk, dtype=np.int32), np.zeros(nk, dtype=np.int32)
+        flat = lambda want: np.zeros(Jtot * R) if want else None
+        Bf, Pf, Yf = flat(return_B), flat(return_P), flat(return_y)
+        sysm = np.zeros((R, R), order='F') if return_sys else None
+        path = (C.c_int * 2)(-1, -1)
+        opt = capi.Par2FoldinOptions(int(max_iter), float(tol), float(ridge), 1 if nonneg else 0, int(max_inner),
+                                     float(inner_tol[0]), float(inner_tol[1]))
+        ip = C.POINTER(C.c_int)
+        capi.check(self.lib.aoadmm_resident_par2_fold_in(
+            self.h, int(p), nk, cols.ctypes.data_as(C.POINTER(C.c_int64)) if nk else None, capi.dptr(X) if nk else None, capi.dptr(C0),
+            C.byref(opt), capi.dptr(Cm), capi.dptr(Bf), capi.dptr(Pf), capi.dptr(res), capi.dptr(xnorm), iters.ctypes.data_as(ip),
+            info.ctypes.data_as(ip), capi.dptr(Yf), capi.dptr(sysm), path))
+        off = np.concatenate([[0], np.cumsum(cols)]) * R
+
+        def cells(flatv):
+            if flatv is None:
+                return None
+            return [flatv[off[q]:off[q + 1]].reshape((int(cols[q]), R), order='F') for q in range(nk)]
+        with np.errstate(invalid='ignore', divide='ignore'):
+            fit = 1.0 - res / xnorm
+        out = dict(C=Cm, B=cells(Bf), P=cells(Pf), res=res, xnorm=xnorm, fit=fit, iters=iters, info=info, path=(path[0], path[1]))
+        if return_y:
+            out['Y'] = cells(Yf)
+        if return_sys:
+            out['sys'] = sysm
+        return out
+
     def project(self, p, mats):
         """Tucker projection of the resident 3-way block p (`aoadmm_resident_project`): mats = (M0, M1, M2) with M_n of
         shape dims[n] x r_n; returns the core X x_1 M0' x_2 M1' x_3 M2' as an ndarray of shape (r0, r1, r2).  X is the
@@ -673,7 +741,8 @@ class Engine:
         the copy of tensor mode n, and for which = 4 the pass of every `resident_em_pass` call over a dense CP block; which = 12: the held-out passes; which = 13: the top-k completions and the ranks of targets (one launch per `topk` or `rank_of` call and per
         evaluation of a ranking list inside a solve);
         which = 14: the fold-in of new rows (one launch per `fold_in` call, weighted or not); which = 16: the list pass
-        of every `resident_em_list_pass` call."""
+        of every `resident_em_list_pass` call; which = 17: the fold-in of new PARAFAC2 slabs (one launch per `par2_fold_in`
+        call)."""
         ms, n, by, fl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         capi.check(self.lib.aoadmm_kernel_stats(self.h, int(which), int(bool(reset)), C.byref(ms), C.byref(n),
                                                 C.byref(by), C.byref(fl)))
