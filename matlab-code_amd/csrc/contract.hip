@@ -225,26 +225,55 @@ __global__ __launch_bounds__(256, NT <= 2 ? 2 : 1) void contract16_f32(KArgs a) 
     AO_FMA_S(XC, FC, EC, 2) AO_LOAD1(XL, GI, 2) __builtin_amdgcn_sched_barrier(0);                   \
     AO_FMA_S(XC, FC, EC, 3) AO_LOAD1(XL, GI, 3) AO_LOADF(FL, EL, GI) __builtin_amdgcn_sched_barrier(0); \
   }
-  if (ng > 0) AO_LOAD_STAGE(x0, f0, e0, 0)
-  if (ng > 1) AO_LOAD_STAGE(x1, f1, e1, 1)
+  // The same stage, every load pinned in the order the steady state issues them (x[0..3], fragment, leftover-column
+  // fragments).  The compiler derives the loop's s_waitcnt operands from the loads pending on EVERY path into the loop
+  // header and keeps the strictest: with a conditional, freely scheduled prologue in front of it the header got a static
+  // vmcnt(2) and the ring was drained once per revolution.  The steady loop is therefore entered only through this
+  // prologue (ng >= 5: both stages are in range), and chunks too short for it never pass the loop header.
+#define AO_LOAD_STAGE_ORDERED(XS, FS, ES, GI)                                                        \
+  {                                                                                                  \
+    AO_LOAD1(XS, GI, 0) __builtin_amdgcn_sched_barrier(0);                                           \
+    AO_LOAD1(XS, GI, 1) __builtin_amdgcn_sched_barrier(0);                                           \
+    AO_LOAD1(XS, GI, 2) __builtin_amdgcn_sched_barrier(0);                                           \
+    AO_LOAD1(XS, GI, 3) __builtin_amdgcn_sched_barrier(0);                                           \
+    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                                              \
+      FS[nt] = fp[(GI) * 64 + nt * fnt];                                                             \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+    }                                                                                                \
+    if (EX) {                                                                                        \
+      ES[0] = fe[(GI) * 8];                                                                          \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+      ES[1] = fe[(GI) * 8 + 4];                                                                      \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+    }                                                                                                \
+  }
   int64_t g = 0;
   int since_flush = 0;
-  for (; g + 5 <= ng; g += 3) {                      // steady state: every prefetch is in range
-    AO_MIX_STAGE(x0, f0, e0, x2, f2, e2, g + 2)
-    AO_MIX_STAGE(x1, f1, e1, x0, f0, e0, g + 3)
-    AO_MIX_STAGE(x2, f2, e2, x1, f1, e1, g + 4)
-    if (L2 && ++since_flush == a.flush_every) {      // the next stages' loads are in flight behind this
-      since_flush = 0;
-      AO_FLUSH()
-    }
+  if (ng >= 5) {
+    AO_LOAD_STAGE_ORDERED(x0, f0, e0, 0)
+    AO_LOAD_STAGE_ORDERED(x1, f1, e1, 1)
+    do {                                             // steady state: every prefetch is in range
+      AO_MIX_STAGE(x0, f0, e0, x2, f2, e2, g + 2)
+      AO_MIX_STAGE(x1, f1, e1, x0, f0, e0, g + 3)
+      AO_MIX_STAGE(x2, f2, e2, x1, f1, e1, g + 4)
+      if (L2 && ++since_flush == a.flush_every) {    // the next stages' loads are in flight behind this
+        since_flush = 0;
+        AO_FLUSH()
+      }
+      g += 3;
+    } while (g + 5 <= ng);
+  } else {                                           // 0..4 full groups: no steady state
+    if (ng > 0) AO_LOAD_STAGE(x0, f0, e0, 0)
+    if (ng > 1) AO_LOAD_STAGE(x1, f1, e1, 1)
   }
-  for (; g + 3 <= ng; g += 3) {                      // at most one drained round
+  if (g + 3 <= ng) {                                 // one drained round
     if (g + 2 < ng) AO_LOAD_STAGE(x2, f2, e2, g + 2)
     AO_COMPUTE_STAGE(x0, f0, e0)
     if (g + 3 < ng) AO_LOAD_STAGE(x0, f0, e0, g + 3)
     AO_COMPUTE_STAGE(x1, f1, e1)
     if (g + 4 < ng) AO_LOAD_STAGE(x1, f1, e1, g + 4)
     AO_COMPUTE_STAGE(x2, f2, e2)
+    g += 3;
   }
   if (g < ng) AO_COMPUTE_STAGE(x0, f0, e0)
   if (g + 1 < ng) AO_COMPUTE_STAGE(x1, f1, e1)
@@ -275,6 +304,7 @@ __global__ __launch_bounds__(256, NT <= 2 ? 2 : 1) void contract16_f32(KArgs a) 
 #undef AO_LOAD1
 #undef AO_LOADF
 #undef AO_LOAD_STAGE
+#undef AO_LOAD_STAGE_ORDERED
 #undef AO_FMA_S
 #undef AO_COMPUTE_STAGE
 #undef AO_MIX_STAGE
@@ -546,8 +576,9 @@ __global__ __launch_bounds__(256, NT <= 2 ? 2 : 1) void contract_lead16_f32(LArg
 //   multiplies its rows by F[c + q][16NT + e], e = 0..3 (v_fma_f64 runs at the MFMA's fp64 rate on this chip), the four
 //   k-quarters are added at the end.  A second, mostly empty MFMA tile doubled the matrix-pipe time: 6.5 ms of matrix
 //   work against an 8.1 ms HBM floor at 2000^3, R = 20 (round 1: 14.0 ms per pass).
-//   Register ring of three 8-column stages with the next stages' loads issued between MFMA groups (two stages, loads
-//   in front of the MFMA block, in the leftover-column form: three need 290 registers); the T tile is assembled in LDS
+//   Register ring of three 8-column stages with the next stages' loads issued between MFMA groups (two stages, each
+//   refilled in place between its own MFMA groups, in the leftover-column form: three need 290 registers).  The steady
+//   loops are entered only through an ordered prologue (see contract16_f32); the T tile is assembled in LDS
 //   and stored with coalesced streaming stores (see contract16_f32).  2000^3, R = 20: 10.1-10.3 ms per pass
 //   (6.3-6.4 TB/s algorithmic); MFMA tiles only with three stages: 10.2-10.3 ms (tools/micro/pass_f64.hip).
 static constexpr int kTileRows64 = 64;
@@ -646,34 +677,85 @@ __global__ __launch_bounds__(256, NT <= 2 ? 2 : 1) void contract_f64(KArgs a) {
     AO_FMA_S(XC, FC, EC, 2) AO_LOAD1(XL, GI, 2) __builtin_amdgcn_sched_barrier(0);                   \
     AO_FMA_S(XC, FC, EC, 3) AO_LOAD1(XL, GI, 3) AO_LOADF(FL, EL, GI) __builtin_amdgcn_sched_barrier(0); \
   }
+  // every load of a stage pinned in the steady state's order: the only way into a steady loop (see contract16_f32)
+#define AO_LOAD_STAGE_ORDERED(XS, FS, ES, GI)                                                        \
+  {                                                                                                  \
+    AO_LOAD1(XS, GI, 0) __builtin_amdgcn_sched_barrier(0);                                           \
+    AO_LOAD1(XS, GI, 1) __builtin_amdgcn_sched_barrier(0);                                           \
+    AO_LOAD1(XS, GI, 2) __builtin_amdgcn_sched_barrier(0);                                           \
+    AO_LOAD1(XS, GI, 3) __builtin_amdgcn_sched_barrier(0);                                           \
+    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                                              \
+      FS[nt] = fp[(GI) * 64 + nt * fnt];                                                             \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+    }                                                                                                \
+    if (EX) {                                                                                        \
+      ES[0] = fe[(GI) * 8];                                                                          \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+      ES[1] = fe[(GI) * 8 + 4];                                                                      \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+    }                                                                                                \
+  }
   int64_t g = 0;
   if (RING == 3) {
-    if (ng > 0) AO_LOAD_STAGE(x0, f0, e0, 0)
-    if (ng > 1) AO_LOAD_STAGE(x1, f1, e1, 1)
-    for (; g + 5 <= ng; g += 3) {                    // steady state: every prefetch is in range
-      AO_MIX_STAGE(x0, f0, e0, x2, f2, e2, g + 2)
-      AO_MIX_STAGE(x1, f1, e1, x0, f0, e0, g + 3)
-      AO_MIX_STAGE(x2, f2, e2, x1, f1, e1, g + 4)
+    if (ng >= 5) {
+      AO_LOAD_STAGE_ORDERED(x0, f0, e0, 0)
+      AO_LOAD_STAGE_ORDERED(x1, f1, e1, 1)
+      do {                                           // steady state: every prefetch is in range
+        AO_MIX_STAGE(x0, f0, e0, x2, f2, e2, g + 2)
+        AO_MIX_STAGE(x1, f1, e1, x0, f0, e0, g + 3)
+        AO_MIX_STAGE(x2, f2, e2, x1, f1, e1, g + 4)
+        g += 3;
+      } while (g + 5 <= ng);
+    } else {                                         // 0..4 full groups: no steady state
+      if (ng > 0) AO_LOAD_STAGE(x0, f0, e0, 0)
+      if (ng > 1) AO_LOAD_STAGE(x1, f1, e1, 1)
     }
-    for (; g + 3 <= ng; g += 3) {                    // at most one drained round
+    if (g + 3 <= ng) {                               // one drained round
       if (g + 2 < ng) AO_LOAD_STAGE(x2, f2, e2, g + 2)
       AO_COMPUTE_STAGE(x0, f0, e0)
       if (g + 3 < ng) AO_LOAD_STAGE(x0, f0, e0, g + 3)
       AO_COMPUTE_STAGE(x1, f1, e1)
       if (g + 4 < ng) AO_LOAD_STAGE(x1, f1, e1, g + 4)
       AO_COMPUTE_STAGE(x2, f2, e2)
+      g += 3;
     }
     if (g < ng) AO_COMPUTE_STAGE(x0, f0, e0)
     if (g + 1 < ng) AO_COMPUTE_STAGE(x1, f1, e1)
   } else {                                           // two stages: the leftover-column form has no room for a third
-    if (ng > 0) AO_LOAD_STAGE(x0, f0, e0, 0)
-    for (; g + 2 <= ng; g += 2) {
-      AO_LOAD_STAGE(x1, f1, e1, g + 1)
-      AO_COMPUTE_STAGE(x0, f0, e0)
+    // consume stage (XC, FC, EC) and refill it in place with stage GI: an x register is free as soon as its MFMA group
+    // has read it, the fragments after the last group
+#define AO_MIX2_STAGE(XC, FC, EC, GI)                                                                \
+  {                                                                                                  \
+    AO_FMA_S(XC, FC, EC, 0) AO_LOAD1(XC, GI, 0) __builtin_amdgcn_sched_barrier(0);                   \
+    AO_FMA_S(XC, FC, EC, 1) AO_LOAD1(XC, GI, 1) __builtin_amdgcn_sched_barrier(0);                   \
+    AO_FMA_S(XC, FC, EC, 2) AO_LOAD1(XC, GI, 2) __builtin_amdgcn_sched_barrier(0);                   \
+    AO_FMA_S(XC, FC, EC, 3) AO_LOAD1(XC, GI, 3) AO_LOADF(FC, EC, GI) __builtin_amdgcn_sched_barrier(0); \
+  }
+    if (ng >= 4) {
+      AO_LOAD_STAGE_ORDERED(x0, f0, e0, 0)
+      AO_LOAD_STAGE_ORDERED(x1, f1, e1, 1)
+      do {                                           // steady state: every prefetch is in range
+        AO_MIX2_STAGE(x0, f0, e0, g + 2)
+        AO_MIX2_STAGE(x1, f1, e1, g + 3)
+        g += 2;
+      } while (g + 4 <= ng);
+      AO_COMPUTE_STAGE(x0, f0, e0)                   // stages g and g + 1 are loaded; one more may follow
       if (g + 2 < ng) AO_LOAD_STAGE(x0, f0, e0, g + 2)
       AO_COMPUTE_STAGE(x1, f1, e1)
+      if (g + 2 < ng) AO_COMPUTE_STAGE(x0, f0, e0)
+    } else {                                         // 0..3 full groups: no steady state
+      if (ng > 0) AO_LOAD_STAGE(x0, f0, e0, 0)
+      if (ng > 1) {
+        AO_LOAD_STAGE(x1, f1, e1, 1)
+        AO_COMPUTE_STAGE(x0, f0, e0)
+        if (ng > 2) AO_LOAD_STAGE(x0, f0, e0, 2)
+        AO_COMPUTE_STAGE(x1, f1, e1)
+        if (ng > 2) AO_COMPUTE_STAGE(x0, f0, e0)
+      } else if (ng > 0) {
+        AO_COMPUTE_STAGE(x0, f0, e0)
+      }
     }
-    if (g < ng) AO_COMPUTE_STAGE(x0, f0, e0)
+#undef AO_MIX2_STAGE
   }
   g = gfull > g0 ? gfull : g0;
   // ragged tail group: columns >= C are clamped (finite data) and meet zero B fragments
@@ -698,6 +780,7 @@ __global__ __launch_bounds__(256, NT <= 2 ? 2 : 1) void contract_f64(KArgs a) {
 #undef AO_LOAD1
 #undef AO_LOADF
 #undef AO_LOAD_STAGE
+#undef AO_LOAD_STAGE_ORDERED
 #undef AO_FMA_S
 #undef AO_COMPUTE_STAGE
 #undef AO_MIX_STAGE
@@ -877,27 +960,49 @@ __global__ __launch_bounds__(256, NT <= 2 ? 2 : 1) void contract16_f16(KArgs16 a
       __builtin_amdgcn_sched_barrier(0);                                                             \
     }                                                                                                \
   }
-  if (ng > 0) AO_LOAD_STAGE(x0, f0, 0)
-  if (ng > 1) AO_LOAD_STAGE(x1, f1, 1)
-  int64_t g = 0;
-  for (; g + 5 <= ng; g += 3) {                      // steady state: every prefetch is in range
-    AO_MIX_STAGE(x0, f0, x2, f2, g + 2)
-    AO_MIX_STAGE(x1, f1, x0, f0, g + 3)
-    AO_MIX_STAGE(x2, f2, x1, f1, g + 4)
+  // every load of a stage pinned in the steady state's order: the only way into the steady loop (see contract16_f32)
+#define AO_LOAD_STAGE_ORDERED(XS, FS, GI)                                                            \
+  {                                                                                                  \
+    _Pragma("unroll") for (int tl_ = 0; tl_ < 8; ++tl_) {                                            \
+      AO_LOAD1(XS, GI, tl_)                                                                          \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+    }                                                                                                \
+    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                                              \
+      FS[nt][0] = fp[(GI) * (NT * 128) + nt * 128];                                                  \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+      FS[nt][1] = fp[(GI) * (NT * 128) + nt * 128 + 64];                                             \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+    }                                                                                                \
   }
-  for (; g + 3 <= ng; g += 3) {                      // at most one drained round
+  int64_t g = 0;
+  if (ng >= 5) {
+    AO_LOAD_STAGE_ORDERED(x0, f0, 0)
+    AO_LOAD_STAGE_ORDERED(x1, f1, 1)
+    do {                                             // steady state: every prefetch is in range
+      AO_MIX_STAGE(x0, f0, x2, f2, g + 2)
+      AO_MIX_STAGE(x1, f1, x0, f0, g + 3)
+      AO_MIX_STAGE(x2, f2, x1, f1, g + 4)
+      g += 3;
+    } while (g + 5 <= ng);
+  } else {                                           // 0..4 groups: no steady state
+    if (ng > 0) AO_LOAD_STAGE(x0, f0, 0)
+    if (ng > 1) AO_LOAD_STAGE(x1, f1, 1)
+  }
+  if (g + 3 <= ng) {                                 // one drained round
     if (g + 2 < ng) AO_LOAD_STAGE(x2, f2, g + 2)
     AO_COMPUTE_STAGE(x0, f0)
     if (g + 3 < ng) AO_LOAD_STAGE(x0, f0, g + 3)
     AO_COMPUTE_STAGE(x1, f1)
     if (g + 4 < ng) AO_LOAD_STAGE(x1, f1, g + 4)
     AO_COMPUTE_STAGE(x2, f2)
+    g += 3;
   }
   if (g < ng) AO_COMPUTE_STAGE(x0, f0)
   if (g + 1 < ng) AO_COMPUTE_STAGE(x1, f1)
 #undef AO_LOAD1
 #undef AO_LOADF
 #undef AO_LOAD_STAGE
+#undef AO_LOAD_STAGE_ORDERED
 #undef AO_FMA_T
 #undef AO_COMPUTE_STAGE
 #undef AO_MIX_STAGE
