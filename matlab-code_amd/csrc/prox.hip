@@ -600,9 +600,13 @@ __global__ void prox_gl_k(ColArgs a, const AdmmCtl* ctl) {
 // U*S (orthogonal columns); instead of rotating the rows x R matrix pair by pair (190 pairs x ~10 sweeps x a pass
 // over 2000 rows each: 7.7 ms at 2000 x 20 in one workgroup), pass 1 takes J1 from the eigenvectors of G = W'W
 // (R x R, one wave: sym_eig_small) and forms W1 = W*J1 with one small GEMM; pass 2 and 3 repeat that on W1, W2, whose
-// Gram matrices are already diagonal up to rounding -- Jacobi on such a matrix is accurate in the relative sense, so the
-// cond(W)^2 error of a single Gram-eigen step is removed.  Then S = column norms (the last eigenvalues), U = W3/S and
-// Z = U*(J1*J2*J3)'.  Columns with S = 0 give zero columns, as before.
+// Gram matrices are already diagonal up to rounding of size eps*||W||^2 -- Jacobi on such a matrix is accurate in the
+// relative sense, so the cond(W)^2 error of a single Gram-eigen step is removed.  That needs the RELATIVE stopping rule
+// |a_pq| <= 1e-15*sqrt(a_pp*a_qq) (sym_eig_small's `relative`): under the norm-wise rule the other callers use, a Gram
+// matrix whose off-diagonal part is eps*||W||^2 has converged before its first sweep, passes 2 and 3 did nothing and
+// the columns of the small singular values stayed non-orthogonal by eps*cond(W)^2 (measured: 3e-6 from the SVD's polar
+// factor at 40 x 12, cond 1e6; 1.3e-11 with the relative rule, the error of numpy's own SVD).  Then S = column norms
+// (the last eigenvalues), U = W3/S and Z = U*(J1*J2*J3)'.  Columns with S = 0 give zero columns, as before.
 __global__ void ortho_m_k(double* M, const double* Jt, const double* G, int R, const AdmmCtl* ctl) {
   CTL_GUARD(ctl);                                      // M(r,c) = Jt(c,r) / S_r with S_r^2 = G(r,r)
   for (int e = threadIdx.x; e < R * R; e += blockDim.x) {
@@ -631,7 +635,7 @@ static void prox_ortho(const double* V, int64_t ldv, double* Z, int64_t ldz, int
   const double* Jt = nullptr;                          // accumulated rotation J1*J2*...
   for (int pass = 0; pass < 3; ++pass) {
     atb_small(G, W, ldw, W, ldw, rows, R, R, aws, ctl, s);
-    sym_eig_small(G, R, wv, Q, s, ctl);
+    sym_eig_small(G, R, wv, Q, s, ctl, true);         // relative stopping rule, see above
     double* Wn = (W == Wa) ? Wb : Wa;
     gemm_small(Wn, rows, W, ldw, Q, R, rows, R, R, 0, coef(1.0), 0.0, ctl, s);          // W <- W*Q
     double* Jn = (Jt == Ja) ? Jb : Ja;

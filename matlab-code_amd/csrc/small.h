@@ -98,8 +98,11 @@ void ctl_reset(AdmmCtl* ctl, hipStream_t s);
 // L = chol(B) only (B symmetric R x R); flag -> ctl->notpd
 void chol_only(double* L, const double* B, int R, AdmmCtl* ctl, hipStream_t s);
 
-// B = V diag(w) V' for a symmetric n x n matrix, n <= 64 (cyclic Jacobi, one wave)
-void sym_eig_small(const double* B, int n, double* w, double* V, hipStream_t s, const AdmmCtl* ctl = nullptr);
+// B = V diag(w) V' for a symmetric n x n matrix, n <= 64 (cyclic Jacobi, one wave).  Stops when the off-diagonal part is
+// below 1e-15 of the matrix norm-wise; with `relative` when every |a_pq| <= 1e-15 * sqrt(|a_pp * a_qq|) (Gram matrices
+// of ill-conditioned factors: the orthonormality prox)
+void sym_eig_small(const double* B, int n, double* w, double* V, hipStream_t s, const AdmmCtl* ctl = nullptr,
+                   bool relative = false);
 // BB <- AA \ BB, AA symmetric positive definite q x q (destroyed), BB q x nrhs; failure -> ctl->notpd
 void spd_solve_left(double* AA, int64_t q, double* BB, int nrhs, AdmmCtl* ctl, hipStream_t s);
 // Dense SPD system of order n <= kDenseMaxN: M (n x n, column-major) is overwritten by its Cholesky factor, Minv

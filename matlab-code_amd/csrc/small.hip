@@ -556,6 +556,14 @@ void dense_symv_rows(const double* Minv, const double* rhs, double* out, int K, 
 // its pair, then all column rotations of the round are applied at once, then all row rotations (disjoint rotations
 // commute).  A serial cyclic sweep took ~1 us per pair with two barriers each (190 pairs at n = 20); a round here is two
 // wave barriers for n/2 pairs.  Fixed schedule, fixed arithmetic order: deterministic.
+// Stopping rule.  REL = false: norm-wise, off^2 <= 1e-30 * tot^2 -- eigenvalues and vectors to an absolute error of
+// eps * ||B||, what the Sylvester-type updates and the subspace iteration need.  REL = true (the orthonormality prox):
+// every |a_pq| <= 1e-15 * sqrt(|a_pp * a_qq|), the rule of a one-sided Jacobi SVD (par2_polar_dev.h), which resolves the
+// small eigenvalues of a graded Gram matrix to their own size; a nearly diagonal graded matrix passes the norm-wise
+// rule before its first sweep.  The rule reads the upper triangle only, the entries the rotations are computed from:
+// the two triangles are updated by separate statements, and the lower one keeps a rounding residue of size eps * ||B||
+// that no rotation removes.
+template <bool REL>
 __global__ __launch_bounds__(64) void sym_eig_small_k(const double* B, int n, double* w, double* V, const AdmmCtl* ctl) {
   CTL_GUARD(ctl);
   extern __shared__ double sh[];          // A[n*n], Q[n*n], cs[2*32], pq[2*32] (as ints)
@@ -570,10 +578,20 @@ __global__ __launch_bounds__(64) void sym_eig_small_k(const double* B, int n, do
   const int m = (n + 1) & ~1;             // players of the tournament (one dummy when n is odd)
   const int half = m / 2;
   for (int sweep = 0; sweep < 60; ++sweep) {
-    double off = 0.0, tot = 0.0;
-    for (int e = t; e < n * n; e += 64) { const double v = A[e]; tot += v * v; if (e % n != e / n) off += v * v; }
-    for (int o = 32; o > 0; o >>= 1) { off += __shfl_xor(off, o); tot += __shfl_xor(tot, o); }
-    if (t == 0) done = !(off > 1e-30 * tot);
+    if constexpr (REL) {
+      int big = 0;
+      for (int e = t; e < n * n; e += 64) {
+        const int p = e % n, q = e / n;
+        if (p < q && fabs(A[e]) > 1e-15 * sqrt(fabs(A[p + n * p] * A[q + n * q]))) big = 1;
+      }
+      for (int o = 32; o > 0; o >>= 1) big |= __shfl_xor(big, o);
+      if (t == 0) done = !big;
+    } else {
+      double off = 0.0, tot = 0.0;
+      for (int e = t; e < n * n; e += 64) { const double v = A[e]; tot += v * v; if (e % n != e / n) off += v * v; }
+      for (int o = 32; o > 0; o >>= 1) { off += __shfl_xor(off, o); tot += __shfl_xor(tot, o); }
+      if (t == 0) done = !(off > 1e-30 * tot);
+    }
     __syncthreads();
     if (done) break;
     for (int r = 0; r < m - 1; ++r) {
@@ -631,11 +649,16 @@ __global__ __launch_bounds__(64) void sym_eig_small_k(const double* B, int n, do
   for (int e = t; e < n * n; e += 64) V[e] = Q[e];
   if (t < n) w[t] = A[t + n * t];
 }
-void sym_eig_small(const double* B, int n, double* w, double* V, hipStream_t s, const AdmmCtl* ctl) {
+void sym_eig_small(const double* B, int n, double* w, double* V, hipStream_t s, const AdmmCtl* ctl, bool relative) {
   AO_REQUIRE(n >= 1 && n <= kMaxRank, "sym_eig_small: n out of range");
   const size_t sh = ((size_t)2 * n * n + 64 + 64) * sizeof(double);
-  if (sh > 65536) ensure_dynamic_lds(reinterpret_cast<const void*>(sym_eig_small_k), (int)sh);
-  sym_eig_small_k<<<1, 64, sh, s>>>(B, n, w, V, ctl);
+  if (relative) {
+    if (sh > 65536) ensure_dynamic_lds(reinterpret_cast<const void*>(sym_eig_small_k<true>), (int)sh);
+    sym_eig_small_k<true><<<1, 64, sh, s>>>(B, n, w, V, ctl);
+  } else {
+    if (sh > 65536) ensure_dynamic_lds(reinterpret_cast<const void*>(sym_eig_small_k<false>), (int)sh);
+    sym_eig_small_k<false><<<1, 64, sh, s>>>(B, n, w, V, ctl);
+  }
   AO_KERNEL_CHECK();
 }
 

@@ -48,11 +48,11 @@ import zlib
 
 import numpy as np
 import pytest
-import scipy.linalg as sla
 
 from helpers import rel_fro
 from oracle import aoadmm as OA
 from oracle import prox as OP
+from prox_ref import gl_banded as _gl_banded
 
 pytestmark = pytest.mark.gpu
 
@@ -119,16 +119,6 @@ def host_prox(name, rows):
     if c[0] == 'simplex row-wise' and rows > 1000:
         return functools.partial(_simplex_rows, eta=c[1])
     return OP.constraints_to_prox([1], [c], [rows])[0][0]
-
-
-def _gl_banded(x, rho, eta):
-    n = x.shape[0]
-    g = 2.0 * eta / rho
-    ab = np.zeros((2, n))
-    ab[0, 1:] = -g                                   # upper diagonal of g*L + I, L = gl_laplacian(n)
-    ab[1, :] = 2.0 * g + 1.0
-    ab[1, 0] = ab[1, -1] = g + 1.0
-    return sla.solveh_banded(ab, x)
 
 
 def _simplex_rows(x, rho, eta):

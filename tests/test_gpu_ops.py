@@ -8,6 +8,7 @@ from oracle import prox as OP
 from oracle import aoadmm as OA
 from oracle.tensor_ops import mttkrp as o_mttkrp
 from helpers import rel_fro
+from prox_ref import gl_banded, unimodal_tied_check
 
 pytestmark = pytest.mark.gpu
 
@@ -110,21 +111,6 @@ def test_tv_prox_long_columns(eng, kind, rows):
     assert rel_fro(got, ref) < 1e-10 or np.max(np.abs(got - ref)) < 1e-12, rel_fro(got, ref)
 
 
-def _gl_banded(X, eta, rho):
-    """(2*eta/rho*L + I) \\ X with the path-graph Laplacian L (constraints_to_prox.m:68-76) by a banded solve: the
-    oracle builds the dense matrix (3 GB at 20 000 rows), so the long columns are checked against this and this
-    against the oracle at 4097 rows."""
-    from scipy.linalg import solve_banded
-    n = X.shape[0]
-    s2 = 2.0 * eta / rho
-    ab = np.zeros((3, n))
-    ab[0, 1:] = -s2
-    ab[2, :-1] = -s2
-    ab[1, :] = 2.0 * s2 + 1.0
-    ab[1, 0] = ab[1, -1] = s2 + 1.0
-    return solve_banded((1, 1), ab, X)
-
-
 @pytest.mark.parametrize('rows', [4097, 9000, 20011])
 @pytest.mark.parametrize('eta', [0.7, 40.0, 1e-3])
 def test_gl_prox_long_columns(eng, rows, eta):
@@ -133,7 +119,7 @@ def test_gl_prox_long_columns(eng, rows, eta):
     rng = np.random.default_rng(rows)
     X = np.cumsum(rng.standard_normal((rows, 3)), axis=0) * 0.05 + rng.standard_normal((rows, 3))
     c = ('GL smoothness', eta)
-    ref = _gl_banded(X, eta, 1.7)
+    ref = gl_banded(X, 1.7, eta)
     if rows == 4097:
         ops, _ = OP.constraints_to_prox([1], [c], [rows])
         assert rel_fro(ref, ops[0](X, 1.7)) < 1e-12
@@ -178,17 +164,8 @@ def test_shape_constraints_hard_inputs(eng, c, kind):
     ref = ops[0](X, 1.3)
     got = eng.prox(c, X, 1.3)
     if kind == 'ties' and c[0] == 'unimodality' and not (rel_fro(got, ref) < 1e-10):
-        # Integer data: many splits have exactly the same criterion value and the projection is not unique.  The
-        # reference's pick among them is decided by the rounding of its error sums (project_unimodal_vector.m:67-72
-        # accumulates them pool by pool); the device takes the first split within a few ulp of the minimum.  Every
-        # column must then be feasible and exactly as close to the input as the oracle's.
-        for r in range(X.shape[1]):
-            g = got[:, r]
-            pk = int(np.argmax(g))
-            assert np.all(np.diff(g[:pk + 1]) >= 0) and np.all(np.diff(g[pk:]) <= 0)
-            assert not c[1] or g.min() >= 0
-            eg, er = np.sum((g - X[:, r]) ** 2), np.sum((ref[:, r] - X[:, r]) ** 2)
-            assert abs(eg - er) <= 1e-12 * er, (r, eg, er)
+        # the split is tied: feasibility plus equal distance (prox_ref.unimodal_tied_check)
+        unimodal_tied_check(got, ref, X, c[1])
         return
     assert rel_fro(got, ref) < 1e-10 or np.max(np.abs(got - ref)) < 1e-12, rel_fro(got, ref)
 
